@@ -2,7 +2,7 @@
 """Headline benchmark: leapfrog steps/s (= forward + gradient evaluations/s) on the 200x100-cell,
 16-frequency synthetic of BASELINE.json, one independent HMC chain per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--dump-outputs DIR]
 
 A step is one leapfrog step of a REAL trajectory of the sampler (proposeLeapfrog, HMCSampler.jl:206-269): position
 update with the step clamp and the bound reflection, one pass of the hot path -- compDataGradient (:277-330) -- at
@@ -186,6 +186,15 @@ class Chain:
             self.rejected += 1
         return D1
 
+    def outputs(self):
+        """What the last trajectory handed its caller, copied to the host: the model the leapfrog ended at (the proposal),
+        its momentum, the predicted data and [misfit, mnorm] at that model, and the chain's state after the accept test."""
+        prop = self.m_cur if self.start_grad == 1 else self.m_prop      # (an accepted proposal was swapped into m_cur)
+        return {"proposal_model": prop.cpu().numpy(), "proposal_momentum": self.p.cpu().numpy(),
+                "predicted_data": self.d_pred.cpu().numpy(), "misfit_mnorm": self.scal.cpu().numpy(),
+                "chain_model": self.m_cur.cpu().numpy(),
+                "accepted_rejected_failed": np.array([self.accepted, self.rejected, self.failed], dtype=np.float64)}
+
     def run(self, nsteps):
         """exactly nsteps leapfrog steps (the last trajectory is shorter if need be)"""
         left = nsteps
@@ -205,6 +214,17 @@ class Chain:
                 "fp64_restarts": int(it[:, 2].sum()), "misfit_last": self.D0, "failed_trajectories": self.failed,
                 "ms_per_step_by_trajectory": [round(x, 3) for x in self.ms_per_step[-len(self.iters):]],
                 "last_error": self.last_error}
+
+
+def write_outputs(d, arrays, limit=64 << 20):
+    """DIR/<name>.npy per array, float64, at most `limit` bytes in all (the chain's outputs are far below it)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {limit}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def timed(torch, dist, fn):
@@ -331,6 +351,8 @@ def main():
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed-region legs (near_true_state, straight_line, cold_start)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed chain's last step computed (rank 0's chain) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -397,6 +419,7 @@ def main():
     if prof_every:
         prof_overhead_us = ctx.profile_overhead_us()
     elapsed = timed(torch, dist, lambda: chain.run(K))
+    dump = chain.outputs() if args.dump_outputs and rank == 0 else None    # (before the check below overwrites d_pred)
     prof = ctx.profile_read()
     cnt = ctx.profile_counters()
     ctx.profile(False)
@@ -732,6 +755,9 @@ def main():
         if world == 1 and not args.no_extras:
             ctx.close()                          # (a context on the whole device overlaps the two chains' shares)
             out["two_chains_per_gpu"] = two_chains_leg(torch, HipContext, mesh, data, inv, local, dev, m_true, mref, 48)
+        if dump is not None:
+            dump["observed_data"] = np.concatenate([obs.real, obs.imag])        # the input the chain sampled against
+            write_outputs(args.dump_outputs, dump)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     ctx.close()
     if dist is not None:

@@ -211,3 +211,20 @@ def test_cu_shares_follow_the_chains_that_actually_run():
     assert [cu_shares_for(4, n) for n in (1, 2, 3, 4, 7)] == [1, 2, 2, 4, 4]
     assert [cu_shares_for(2, n) for n in (1, 2, 3)] == [1, 2, 2]
     assert cu_shares_for(1, 8) == 1 and cu_shares_for(3, 8) == 2
+
+
+def test_bench_dump_writes_float64_npy_files_under_the_size_limit(tmp_path):
+    """bench.py --dump-outputs DIR: one DIR/<name>.npy per output, float64, and a dump beyond the limit is refused."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_dump", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    arrays = {"model": np.arange(5, dtype=np.float32), "scal": np.array([1.5, 2.5])}
+    bench.write_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["model.npy", "scal.npy"]
+    back = np.load(tmp_path / "d" / "model.npy")
+    assert back.dtype == np.float64 and np.array_equal(back, np.arange(5))
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "e"), {"big": np.zeros(9)}, limit=64)
+    assert not (tmp_path / "e").exists()
