@@ -58,6 +58,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_persist.h"
 #include "kernels_persist4.h"
 #include "kernels_path.h"
+#include "kernels_mass.h"
 
 }  // namespace
 
@@ -170,6 +171,24 @@ struct hmcmt_ctx {
     int* h_lfFlag = nullptr;                 // pinned copy of d_lfFlag (read after a synchronisation)
     double* d_gStart = nullptr;              // data gradient at the start model of the last trajectory (a rejection restarts there)
     bool havePrior = false, lfHaveGrad = false, lfFlagPending = false;
+    std::vector<long long> wmRowH, wmColH;   // host copy of the CSR of Wm (hmcmt_set_mass factors it)
+    std::vector<double> wmValH;
+    // mass matrix (hmcmt_set_mass, kernels_mass.h): the factor and the transforms belong to the Wm in key*; kept across
+    // hmcmt_set_prior calls with the same Wm (a host that re-registers the prior every trajectory does not refactor)
+    struct Mass {
+        int kind = HMCMT_MASS_DIAGONAL;
+        bool ready = false;
+        std::vector<long long> keyRow, keyCol;
+        std::vector<double> keyVal;
+        int bw = 0, separable = 0, nzb = 0, nyb = 0, pcgIters = 0;
+        double factorSec = 0.0;
+        double *d_L = nullptr, *d_Qz = nullptr, *d_QzT = nullptr, *d_Qy = nullptr, *d_QyT = nullptr, *d_lz = nullptr, *d_ly = nullptr;
+        double *d_T1 = nullptr, *d_T2 = nullptr;          // [nzb*nyb] box images
+        double *d_x = nullptr;                            // [nAC] Wm^-1 p of the leapfrog
+        double *d_in = nullptr, *d_out = nullptr;         // [nAC] staging of hmcmt_mass_apply / PCG solution
+        double *d_r = nullptr, *d_z = nullptr, *d_pp = nullptr, *d_q = nullptr, *d_s = nullptr;   // PCG vectors, scalars [8]
+        int* d_map = nullptr;                             // [nzb*nyb] active index of each box cell, -1 frozen
+    } mass;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)
     bool persistOn = true;                // HMCMT_PERSIST=0: the launch-per-phase loop only
@@ -2738,6 +2757,247 @@ int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, doub
     return 0;
 }
 
+// ---- mass matrix (hmcmt_set_mass / hmcmt_mass_apply, kernels_mass.h) --------------------------------------------------------
+constexpr int MASS_PCG_MAXIT = 1000;
+constexpr double MASS_PCG_TOL = 1e-13;
+
+static void mass_release(hmcmt_ctx* ctx) {
+    auto& M = ctx->mass;
+    for (void* old : {(void*)M.d_L, (void*)M.d_Qz, (void*)M.d_QzT, (void*)M.d_Qy, (void*)M.d_QyT, (void*)M.d_lz, (void*)M.d_ly,
+                      (void*)M.d_T1, (void*)M.d_T2, (void*)M.d_x, (void*)M.d_in, (void*)M.d_out, (void*)M.d_r, (void*)M.d_z,
+                      (void*)M.d_pp, (void*)M.d_q, (void*)M.d_s, (void*)M.d_map}) {
+        if (!old) continue;
+        auto it = std::find(ctx->allocs.begin(), ctx->allocs.end(), old);
+        if (it != ctx->allocs.end()) ctx->allocs.erase(it);
+        hipFree(old);
+    }
+    const int kind = M.kind;
+    M = hmcmt_ctx::Mass{};
+    M.kind = kind;
+}
+
+// Banded Cholesky of Wm (the CSR of hmcmt_set_prior) in the natural order, row by row (Cholesky-Banachiewicz; the dot products
+// run over contiguous stretches of two rows of the band).  Lb[i*(b+1) + j - i + b] = L[i][j].  Returns -1 - i for a pivot <= 0.
+static long long mass_factor(int n, int b, const std::vector<long long>& row, const std::vector<long long>& col,
+                             const std::vector<double>& val, std::vector<double>& Lb) {
+    const long long w = b + 1;
+    Lb.assign((size_t)n * w, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (long long t = row[i]; t < row[i + 1]; ++t)
+            if (col[t] <= i) Lb[(size_t)i * w + (col[t] - i + b)] += val[t];
+    for (int i = 0; i < n; ++i) {
+        double* Li = &Lb[(size_t)i * w];
+        const int j0 = std::max(0, i - b);
+        for (int j = j0; j <= i; ++j) {
+            const double* Lj = &Lb[(size_t)j * w];
+            double s = Li[j - i + b];
+            // sum over k = j0 .. j-1 of L[i][k] L[j][k]
+            const double* a = Li + (j0 - i + b);
+            const double* c = Lj + (j0 - j + b);
+            double acc = 0.0;
+            for (int k = 0; k < j - j0; ++k) acc += a[k] * c[k];
+            s -= acc;
+            if (j < i) Li[j - i + b] = s / Lj[b];
+            else {
+                if (!(s > 0.0)) return -1 - (long long)i;
+                Li[b] = std::sqrt(s);
+            }
+        }
+    }
+    return 0;
+}
+
+// Does Wm equal I (x) T_y + T_z (x) I on the active box (kernels_mass.h)?  Exact comparison of every stored entry.
+static bool mass_separable(int n, int nzb, int nyb, const std::vector<int>& map, const std::vector<long long>& row,
+                           const std::vector<long long>& col, const std::vector<double>& val) {
+    if ((long long)nzb * nyb != n) return false;
+    for (int iz = 0; iz < nzb; ++iz)
+        for (int jy = 0; jy < nyb; ++jy) {
+            const int a = map[(size_t)iz * nyb + jy];
+            int nb[4], cnt = 0;
+            if (jy > 0) nb[cnt++] = map[(size_t)iz * nyb + jy - 1];
+            if (jy < nyb - 1) nb[cnt++] = map[(size_t)iz * nyb + jy + 1];
+            if (iz > 0) nb[cnt++] = map[(size_t)(iz - 1) * nyb + jy];
+            if (iz < nzb - 1) nb[cnt++] = map[(size_t)(iz + 1) * nyb + jy];
+            double want[5], have[5] = {0, 0, 0, 0, 0};
+            int who[5];
+            who[0] = a; want[0] = cnt + (iz == 0 ? 1.0 : 0.0);
+            for (int q = 0; q < cnt; ++q) { who[q + 1] = nb[q]; want[q + 1] = -1.0; }
+            for (long long t = row[a]; t < row[a + 1]; ++t) {
+                int q = 0;
+                while (q <= cnt && who[q] != col[t]) ++q;
+                if (q > cnt) { if (val[t] != 0.0) return false; continue; }
+                have[q] += val[t];
+            }
+            for (int q = 0; q <= cnt; ++q) if (have[q] != want[q]) return false;
+        }
+    return true;
+}
+
+// the eigenpairs of T_y (Neumann, DCT-II) and T_z (air above the top row), columns = eigenvectors, unit 2-norm
+static void mass_eigen(int n, bool topDirichlet, std::vector<double>& Q, std::vector<double>& lam) {
+    const double pi = 3.14159265358979323846;
+    Q.assign((size_t)n * n, 0.0);
+    lam.assign(n, 0.0);
+    for (int k = 0; k < n; ++k) {
+        const double th = topDirichlet ? pi * (2 * k + 1) / (2.0 * n + 1.0) : pi * k / n;
+        lam[k] = 2.0 - 2.0 * std::cos(th);
+        double nn = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double q = topDirichlet ? std::sin(th * (i + 1)) : std::cos(th * (i + 0.5));
+            Q[(size_t)i * n + k] = q;
+            nn += q * q;
+        }
+        const double s = 1.0 / std::sqrt(nn);
+        for (int i = 0; i < n; ++i) Q[(size_t)i * n + k] *= s;
+    }
+}
+static std::vector<double> transposed(const std::vector<double>& Q, int n) {
+    std::vector<double> T(Q.size());
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < n; ++k) T[(size_t)k * n + i] = Q[(size_t)i * n + k];
+    return T;
+}
+
+static int mass_build(hmcmt_ctx* ctx) {
+    auto& M = ctx->mass;
+    const int n = ctx->v.nAC, ny = ctx->v.ny;
+    const auto& row = ctx->wmRowH; const auto& col = ctx->wmColH; const auto& val = ctx->wmValH;
+    mass_release(ctx);
+    int b = 0;
+    for (int i = 0; i < n; ++i)
+        for (long long t = row[i]; t < row[i + 1]; ++t) b = std::max<long long>(b, std::llabs(col[t] - i));
+    std::vector<double> Lb;
+    const auto t0 = std::chrono::steady_clock::now();
+    const long long fr = mass_factor(n, b, row, col, val, Lb);
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (fr) {
+        ctx->err = "hmcmt_set_mass: Wm is not positive definite (Cholesky pivot <= 0 at active cell " + std::to_string(-1 - fr) + ")";
+        return HMCMT_EINVAL;
+    }
+    // the box of the active cells and its map
+    int kz0 = 1 << 30, kz1 = -1, ky0 = 1 << 30, ky1 = -1;
+    for (int a = 0; a < n; ++a) {
+        const int c = ctx->hp.act[a], kz = c / ny, ky = c % ny;
+        kz0 = std::min(kz0, kz); kz1 = std::max(kz1, kz); ky0 = std::min(ky0, ky); ky1 = std::max(ky1, ky);
+    }
+    const int nzb = kz1 - kz0 + 1, nyb = ky1 - ky0 + 1;
+    std::vector<int> map((size_t)nzb * nyb, -1);
+    for (int a = 0; a < n; ++a) {
+        const int c = ctx->hp.act[a];
+        map[(size_t)(c / ny - kz0) * nyb + (c % ny - ky0)] = a;
+    }
+    std::vector<double> Qz, lz, Qy, ly;
+    mass_eigen(nzb, true, Qz, lz);
+    mass_eigen(nyb, false, Qy, ly);
+    int rc;
+    if ((rc = dupload(ctx, &M.d_L, Lb))) return rc;
+    if ((rc = dupload(ctx, &M.d_map, map))) return rc;
+    if ((rc = dupload(ctx, &M.d_Qz, Qz))) return rc;
+    if ((rc = dupload(ctx, &M.d_QzT, transposed(Qz, nzb)))) return rc;
+    if ((rc = dupload(ctx, &M.d_Qy, Qy))) return rc;
+    if ((rc = dupload(ctx, &M.d_QyT, transposed(Qy, nyb)))) return rc;
+    if ((rc = dupload(ctx, &M.d_lz, lz))) return rc;
+    if ((rc = dupload(ctx, &M.d_ly, ly))) return rc;
+    for (double** p : {&M.d_T1, &M.d_T2})
+        if ((rc = dalloc(ctx, p, (size_t)nzb * nyb))) return rc;
+    for (double** p : {&M.d_x, &M.d_in, &M.d_out, &M.d_r, &M.d_z, &M.d_pp, &M.d_q})
+        if ((rc = dalloc(ctx, p, (size_t)n))) return rc;
+    if ((rc = dalloc(ctx, &M.d_s, (size_t)8))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    M.bw = b; M.nzb = nzb; M.nyb = nyb; M.factorSec = sec;
+    M.separable = mass_separable(n, nzb, nyb, map, row, col, val) ? 1 : 0;
+    M.keyRow = row; M.keyCol = col; M.keyVal = val;
+    M.ready = true;
+    return 0;
+}
+
+// y = B^-1 x restricted to the active cells, B the box operator: four fp64 GEMMs (x, y [nAC] device; y may be x)
+static void mass_box_inv(hmcmt_ctx* ctx, const double* x, double* y) {
+    const auto& M = ctx->mass;
+    hipStream_t st = ctx->stream;
+    const int nz = M.nzb, ny = M.nyb;
+    const dim3 grid((ny + MG_T - 1) / MG_T, (nz + MG_T - 1) / MG_T), blk(256);
+    MassGemm g{nz, ny, nz, M.d_QzT, nullptr, M.d_T1, M.d_map, x, nullptr, M.d_lz, M.d_ly};
+    hipLaunchKernelGGL(k_mass_gemm<MG_SCATTER_B>, grid, blk, 0, st, g);               // Q_z' X
+    g = MassGemm{nz, ny, ny, M.d_T1, M.d_Qy, M.d_T2, M.d_map, nullptr, nullptr, M.d_lz, M.d_ly};
+    hipLaunchKernelGGL(k_mass_gemm<MG_DIVIDE>, grid, blk, 0, st, g);                  // (.. Q_y) ./ (lz_i + ly_j)
+    g = MassGemm{nz, ny, nz, M.d_Qz, M.d_T2, M.d_T1, M.d_map, nullptr, nullptr, M.d_lz, M.d_ly};
+    hipLaunchKernelGGL(k_mass_gemm<0>, grid, blk, 0, st, g);                          // Q_z ..
+    g = MassGemm{nz, ny, ny, M.d_T1, M.d_QyT, nullptr, M.d_map, nullptr, y, M.d_lz, M.d_ly};
+    hipLaunchKernelGGL(k_mass_gemm<MG_GATHER_C>, grid, blk, 0, st, g);                // (.. Q_y') restricted
+}
+
+// y = Wm^-1 b by PCG (fp64; preconditioner mass_box_inv).  Synchronises with the device once per iteration.
+static int mass_pcg(hmcmt_ctx* ctx, const double* b, double* y) {
+    auto& M = ctx->mass;
+    const int n = ctx->v.nAC;
+    hipStream_t st = ctx->stream;
+    const dim3 g1((n + 255) / 256), b1(256);
+    const size_t bytes = sizeof(double) * n;
+    M.pcgIters = 0;
+    double h[8];
+    HIPCHK(hipMemcpyAsync(M.d_r, b, bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(M.d_out, 0, bytes, st));
+    mass_box_inv(ctx, M.d_r, M.d_z);
+    HIPCHK(hipMemcpyAsync(M.d_pp, M.d_z, bytes, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_mass_dot, dim3(1), dim3(1024), 0, st, n, M.d_r, M.d_z, M.d_s, 0);
+    hipLaunchKernelGGL(k_mass_dot, dim3(1), dim3(1024), 0, st, n, M.d_r, M.d_r, M.d_s, 3);
+    HIPCHK(hipMemcpyAsync(h, M.d_s, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const double bnorm = std::sqrt(h[3]);
+    if (!std::isfinite(bnorm)) { ctx->err = "hmcmt_mass_apply: non-finite input"; return HMCMT_EBREAKDOWN; }
+    int it = 0;
+    if (bnorm > 0.0) {
+        for (;;) {
+            if (it == MASS_PCG_MAXIT) {
+                ctx->err = "hmcmt_mass_apply: PCG on Wm did not reach its tolerance within " + std::to_string(MASS_PCG_MAXIT) + " iterations";
+                M.pcgIters = it;
+                return HMCMT_ENOCONV;
+            }
+            ++it;
+            hipLaunchKernelGGL(k_mass_spmv, g1, b1, 0, st, n, ctx->d_wmRow, ctx->d_wmCol, ctx->d_wmVal, M.d_pp, M.d_q);
+            hipLaunchKernelGGL(k_mass_dot, dim3(1), dim3(1024), 0, st, n, M.d_pp, M.d_q, M.d_s, 1);
+            hipLaunchKernelGGL(k_mass_xr, g1, b1, 0, st, n, M.d_s, M.d_pp, M.d_q, M.d_out, M.d_r);
+            mass_box_inv(ctx, M.d_r, M.d_z);
+            hipLaunchKernelGGL(k_mass_dot, dim3(1), dim3(1024), 0, st, n, M.d_r, M.d_z, M.d_s, 2);
+            hipLaunchKernelGGL(k_mass_dot, dim3(1), dim3(1024), 0, st, n, M.d_r, M.d_r, M.d_s, 4);
+            HIPCHK(hipMemcpyAsync(h, M.d_s, sizeof(double) * 5, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (!(h[1] > 0.0) || !std::isfinite(h[2]) || !std::isfinite(h[4])) {
+                ctx->err = "hmcmt_mass_apply: PCG breakdown (p'Wm p <= 0 or non-finite values)";
+                M.pcgIters = it;
+                return HMCMT_EBREAKDOWN;
+            }
+            if (std::sqrt(h[4]) <= MASS_PCG_TOL * bnorm) break;
+            hipLaunchKernelGGL(k_mass_p, g1, b1, 0, st, n, M.d_s, M.d_z, M.d_pp);
+            HIPCHK(hipMemcpyAsync(M.d_s, M.d_s + 2, sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+    }
+    M.pcgIters = it;
+    HIPCHK(hipMemcpyAsync(y, M.d_out, bytes, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// y = M^-1 x or L x on device vectors, enqueued on the context's stream (PCG: complete on return)
+static int mass_apply_dev(hmcmt_ctx* ctx, int op, const double* x, double* y) {
+    auto& M = ctx->mass;
+    const int n = ctx->v.nAC;
+    hipStream_t st = ctx->stream;
+    if (M.kind == HMCMT_MASS_DIAGONAL) {
+        hipLaunchKernelGGL(k_mass_diag, dim3((n + 255) / 256), dim3(256), 0, st, n, ctx->d_invM, x, y, op);
+        return 0;
+    }
+    if (op == HMCMT_MASS_OP_SQRT) {
+        double* out = (x == y) ? M.d_out : y;
+        hipLaunchKernelGGL(k_mass_lmul, dim3((n + 3) / 4), dim3(256), 0, st, n, M.bw, M.d_L, x, out);
+        if (out != y) HIPCHK(hipMemcpyAsync(y, out, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    if (M.separable) { M.pcgIters = 0; mass_box_inv(ctx, x, y); return 0; }
+    return mass_pcg(ctx, x, y);
+}
+
 int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, const int64_t* colind,
                     const double* val, const double* invM) {
     if (!ctx || !mref || !rowptr || !colind || !val || !invM) return HMCMT_EINVAL;
@@ -2779,7 +3039,60 @@ int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, c
     }
     ctx->lfHaveGrad = false;
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->wmRowH = std::move(v_row); ctx->wmColH = std::move(v_col); ctx->wmValH = std::move(v_val);
+    ctx->mass.kind = HMCMT_MASS_DIAGONAL;                   // (hmcmt_set_mass chooses again; a factor of the same Wm is kept)
     ctx->havePrior = true;
+    return 0;
+}
+
+int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (!ctx->havePrior) { ctx->err = "hmcmt_set_mass: hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
+    if (kind != HMCMT_MASS_DIAGONAL && kind != HMCMT_MASS_WM) { ctx->err = "hmcmt_set_mass: kind must be HMCMT_MASS_DIAGONAL or HMCMT_MASS_WM"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the mass buffers)
+    ctx->mass.kind = HMCMT_MASS_DIAGONAL;
+    if (kind == HMCMT_MASS_DIAGONAL) return 0;
+    auto& M = ctx->mass;
+    if (!(M.ready && M.keyRow == ctx->wmRowH && M.keyCol == ctx->wmColH && M.keyVal == ctx->wmValH)) {
+        const int rc = mass_build(ctx);
+        if (rc) { mass_release(ctx); return rc; }
+    }
+    M.kind = HMCMT_MASS_WM;
+    return 0;
+}
+
+int hmcmt_mass_apply(hmcmt_ctx* ctx, int32_t op, const double* x, double* y, int32_t on_device) {
+    if (!ctx || !x || !y) return HMCMT_EINVAL;
+    if (!ctx->havePrior) { ctx->err = "hmcmt_mass_apply: hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
+    if (op != HMCMT_MASS_OP_INV && op != HMCMT_MASS_OP_SQRT) { ctx->err = "hmcmt_mass_apply: op must be HMCMT_MASS_OP_INV or HMCMT_MASS_OP_SQRT"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const int n = ctx->v.nAC;
+    int rc;
+    if (ctx->mass.kind == HMCMT_MASS_DIAGONAL && !ctx->mass.d_in) {
+        if ((rc = dalloc(ctx, &ctx->mass.d_in, (size_t)n))) return rc;
+        if ((rc = dalloc(ctx, &ctx->mass.d_out, (size_t)n))) return rc;
+    }
+    if (on_device) {
+        if ((rc = mass_apply_dev(ctx, op, x, y))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return 0;
+    }
+    auto& M = ctx->mass;
+    HIPCHK(hipMemcpyAsync(M.d_in, x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = mass_apply_dev(ctx, op, M.d_in, M.d_in))) return rc;
+    HIPCHK(hipMemcpyAsync(y, M.d_in, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int hmcmt_mass_info(const hmcmt_ctx* ctx, double* out) {
+    if (!ctx || !out) return HMCMT_EINVAL;
+    const auto& M = ctx->mass;
+    const double v[HMCMT_MASS_INFO_FIELDS] = {(double)M.kind, M.factorSec, (double)M.bw, (double)M.separable, (double)M.pcgIters,
+                                              (double)M.nzb, (double)M.nyb};
+    for (int i = 0; i < HMCMT_MASS_INFO_FIELDS; ++i) out[i] = v[i];
     return 0;
 }
 
@@ -2809,10 +3122,29 @@ static int leapfrog_core(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, in
     ++evals;                                                 // counted as the reference counts it (hmcprior.nfevals, :217)
     // (momentum update and the step bound of the position update behind it in one launch)
     hipLaunchKernelGGL(k_lf_momentum_max, dim3(LFNB), dim3(256), 0, st, lf, regParam, 0.5 * dt, dt);
+    // M = Wm (hmcmt_set_mass): x = Wm^-1 p after every momentum update, the step bound and the position update read x.  The
+    // position and momentum updates are then launches of their own (k_mass_step in front of the evaluation, k_lf_momentum_max
+    // behind it); the fused forms of the diagonal mass stay as they are.
+    const bool wm = ctx->mass.kind == HMCMT_MASS_WM;
+    auto mass_x_bound = [&]() -> int {
+        if (!ctx->mass.separable) {            // (PCG synchronises: the records of the evaluation in flight are read first)
+            const int r = collect_pending(ctx);
+            if (r) return r;
+        }
+        const int r = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, d_p, ctx->mass.d_x);
+        if (r) return r;
+        hipLaunchKernelGGL(k_mass_bound, dim3(LFNB), dim3(256), 0, st, n, ctx->mass.d_x, dt, ctx->d_lfPart);
+        return 0;
+    };
+    if (wm && (rc = mass_x_bound())) return rc;
     for (int k = 1; k <= L; ++k) {
-        ctx->lfStep = LfStep{1, lf, dt, lnSigMin, lnSigMax};            // (the position update: performed by the evaluation's first kernel)
-        // (... and the momentum update behind the gradient, with the step bound of the next position update, by its last one)
-        ctx->lfMom = LfMom{1, lf, regParam, (k < L ? 1.0 : 0.5) * dt, dt, ++ctx->lfGen, ctx->d_lfDone};
+        if (wm) {
+            hipLaunchKernelGGL(k_mass_step, g1, b1, 0, st, lf, ctx->mass.d_x, dt, lnSigMin, lnSigMax);
+        } else {
+            ctx->lfStep = LfStep{1, lf, dt, lnSigMin, lnSigMax};            // (the position update: performed by the evaluation's first kernel)
+            // (... and the momentum update behind the gradient, with the step bound of the next position update, by its last one)
+            ctx->lfMom = LfMom{1, lf, regParam, (k < L ? 1.0 : 0.5) * dt, dt, ++ctx->lfGen, ctx->d_lfDone};
+        }
         rc = evaluate(ctx, d_m, true, d_pred, d_misfit, ctx->d_g);      // (reports a failure of the step before)
         ctx->lfStep.on = 0;
         ctx->lfMom.on = 0;
@@ -2821,6 +3153,10 @@ static int leapfrog_core(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, in
         ctx->statsPending = true;
         ctx->pendingAdj = true;
         ++evals;
+        if (wm) {
+            hipLaunchKernelGGL(k_lf_momentum_max, dim3(LFNB), dim3(256), 0, st, lf, regParam, (k < L ? 1.0 : 0.5) * dt, dt);
+            if (k < L && (rc = mass_x_bound())) return rc;
+        }
     }
     if ((rc = collect_pending(ctx))) return rc;
     hipLaunchKernelGGL(k_lf_mnorm, dim3(LFNB), dim3(256), 0, st, lf, regParam);

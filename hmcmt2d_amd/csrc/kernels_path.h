@@ -40,8 +40,8 @@ struct LfView {
 constexpr int LFNB = 64;
 // m += dm (clamped to max |dm| = 3), reflect at the ln-sigma bounds, flip momentum (HMCSampler.jl:241-247, :515-559) for
 // parameter a; mx = the maximum of the partial step bounds.  Returns the new value (the old one on a non-finite step, flagged).
-__device__ __forceinline__ double lf_step_one(const LfView& L, int a, double dt, double lo, double hi, double mx) {
-    double dm = dt * L.invM[a] * L.p[a];
+// (lf_step_dm: the same with the step dm given -- the non-diagonal mass, kernels_mass.h)
+__device__ __forceinline__ double lf_step_dm(const LfView& L, int a, double dm, double lo, double hi, double mx) {
     if (mx > 3.0) dm = dm / mx * 3.0;
     double m = L.m[a] + dm, p = L.p[a];
     if (!isfinite(m)) { atomicExch(L.flag, 1); return L.m[a]; }
@@ -51,6 +51,9 @@ __device__ __forceinline__ double lf_step_one(const LfView& L, int a, double dt,
     }
     L.m[a] = m; L.p[a] = p;
     return m;
+}
+__device__ __forceinline__ double lf_step_one(const LfView& L, int a, double dt, double lo, double hi, double mx) {
+    return lf_step_dm(L, a, dt * L.invM[a] * L.p[a], lo, hi, mx);
 }
 __device__ __forceinline__ double lf_step_bound(const LfView& L) {
     double mx = 0.0;

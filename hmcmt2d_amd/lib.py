@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -29,6 +29,9 @@ def _warm_start_code(v):
     if isinstance(v, bool):
         return 2 if v else 0
     return {"cold": 0, "previous": 1, "extrapolate": 2, 0: 0, 1: 1, 2: 2}[v]
+# include/hmcmt.h: hmcmt_set_mass kinds and hmcmt_mass_apply operations
+HMCMT_MASS_DIAGONAL, HMCMT_MASS_WM = 0, 1
+HMCMT_MASS_OP_INV, HMCMT_MASS_OP_SQRT = 0, 1
 ERRORS = {-1: "EINVAL", -2: "ENODEV", -3: "EHIP", -10: "ENOCONV", -11: "EBREAKDOWN", -13: "ENOMEM"}
 
 
@@ -98,6 +101,9 @@ def load_library():
     lib.hmcmt_leapfrog_device.argtypes = [vp, vp, vp, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
                                           vp, vp, vp, C.POINTER(C.c_int32)]
     lib.hmcmt_get_fields.argtypes = [vp, C.c_int32, c_double_p, c_double_p]
+    lib.hmcmt_set_mass.argtypes = [vp, C.c_int32]
+    lib.hmcmt_mass_apply.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
+    lib.hmcmt_mass_info.argtypes = [vp, c_double_p]
     lib.hmcmt_profile.argtypes = [vp, C.c_int32]
     lib.hmcmt_profile_every.argtypes = [vp, C.c_int32]
     lib.hmcmt_profile_read.argtypes = [vp, c_double_p, c_int64_p]
@@ -129,7 +135,7 @@ def load_library():
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
                  "hmcmt_grad", "hmcmt_forward", "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async",
-                 "hmcmt_wait", "hmcmt_set_prior", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead",
+                 "hmcmt_wait", "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_mass_info", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead",
                  "hmcmt_dims", "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond",
                  "hmcmt_debug_fdm_fwd", "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_guard", "hmcmt_debug_hog", "hmcmt_next_cu_share", "hmcmt_persist_envelope", "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack"):
         getattr(lib, name).restype = C.c_int
@@ -141,13 +147,14 @@ def load_library():
 PRODUCT_SYMBOLS = ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
-                   "hmcmt_set_prior", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_guard", "hmcmt_next_cu_share",
+                   "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
+                   "hmcmt_guard", "hmcmt_next_cu_share",
                    "hmcmt_comm_id", "hmcmt_comm_create", "hmcmt_allgather_samples", "hmcmt_comm_destroy", "hmcmt_comm_last_error"]
 # include/hmcmt_debug.h: instrumentation, introspection of the persistent kernel, test hooks
 DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead", "hmcmt_dims",
                  "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond", "hmcmt_debug_fdm_fwd",
                  "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_debug_hog", "hmcmt_persist_envelope",
-                 "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack"]
+                 "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -355,6 +362,31 @@ class HipContext:
         a = self._prior
         self._check(self.lib.hmcmt_set_prior(self.h, _dp(a[0]), a[1].ctypes.data_as(c_int64_p),
                                              a[2].ctypes.data_as(c_int64_p), _dp(a[3]), _dp(a[4])))
+
+    def set_mass(self, kind):
+        """hmcmt_set_mass: HMCMT_MASS_DIAGONAL (the invM of set_prior) or HMCMT_MASS_WM (M = Wm of set_prior, factored here);
+        after set_prior, which returns to the diagonal kind."""
+        self._check(self.lib.hmcmt_set_mass(self.h, int(kind)))
+
+    def mass_apply(self, op, x):
+        """hmcmt_mass_apply on a host vector: M^-1 x (HMCMT_MASS_OP_INV) or L x (HMCMT_MASS_OP_SQRT)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.nAC,):
+            raise ValueError("vector has the wrong length")
+        y = np.empty(self.nAC)
+        self._check(self.lib.hmcmt_mass_apply(self.h, int(op), x.ctypes.data, y.ctypes.data, 0))
+        return y
+
+    def mass_apply_device(self, op, d_x, d_y):
+        """hmcmt_mass_apply on device pointers (ints); complete on return."""
+        self._check(self.lib.hmcmt_mass_apply(self.h, int(op), d_x, d_y, 1))
+
+    def mass_info(self):
+        """{kind, factor_s, bandwidth, separable, pcg_iters, box_rows, box_cols} (hmcmt_mass_info)."""
+        o = np.zeros(7)
+        self._check(self.lib.hmcmt_mass_info(self.h, _dp(o)))
+        return {"kind": int(o[0]), "factor_s": float(o[1]), "bandwidth": int(o[2]), "separable": bool(o[3]),
+                "pcg_iters": int(o[4]), "box_rows": int(o[5]), "box_cols": int(o[6])}
 
     def leapfrog(self, m0, p0, dt, L, regParam, lnSigMin, lnSigMax):
         m0 = np.ascontiguousarray(m0, dtype=np.float64)

@@ -3,7 +3,7 @@
 Same function names, argument order and return values as HMCMT/src/HMCSampler/HMCSampler.jl:
 `compDataGradient` (:277-330), `getHamiltonian` (:358-397), `proposeLeapfrog` (:206-269),
 `getKineticEnergy` / `getKineticGradient` (:407-431), `getMomentumVector` (:441-453),
-`setMassMatrix` (:463-474), `checkParameterBound` (:515-559), `runHMCSampler` (:72-196) and
+`setMassMatrix` (:463-489), `checkParameterBound` (:515-559), `runHMCSampler` (:72-196) and
 `parallelHMCSampler` (parallelHMC.jl:10-49).  The only compute they do themselves is O(nparam)
 vector arithmetic; the forward / adjoint solves go through `HipContext` (include/hmcmt.h).
 
@@ -116,8 +116,32 @@ def getMomentumVector(nparam, hmcParam: HMCParameter, rng):
 
 
 def setMassMatrix(nparam, scaling=1.0):
+    """setMassMatrix(nparam, scaling) -> (invM, sqrtM) diagonals (HMCSampler.jl:463-474); setMassMatrix(invParam, ctx) -> the
+    non-diagonal mass M = Wm (:478-489) as operators of `ctx` (hmcmt_set_mass / hmcmt_mass_apply): invM * p = Wm^-1 p,
+    sqrtM * z = L z with L = chol(Wm).L.  The second form registers invParam's prior on ctx (refModel, Wm) and factors Wm."""
+    if hasattr(nparam, "Wm"):
+        return _wm_mass(nparam, scaling)
     mass = scaling * np.ones(nparam)
     return 1.0 / mass, np.sqrt(mass)
+
+
+class MassOperator:
+    """One half of the non-diagonal mass matrix: `op * v` applies M^-1 (op = HMCMT_MASS_OP_INV) or L (HMCMT_MASS_OP_SQRT)
+    through the context, so getKineticEnergy, getKineticGradient and getMomentumVector run unchanged."""
+
+    def __init__(self, ctx, op):
+        self.ctx, self.op = ctx, op
+
+    def __mul__(self, v):
+        return self.ctx.mass_apply(self.op, np.asarray(v, dtype=np.float64))
+
+
+def _wm_mass(invParam, ctx):
+    from .lib import HMCMT_MASS_WM, HMCMT_MASS_OP_INV, HMCMT_MASS_OP_SQRT
+    n = len(invParam.strModel)
+    ctx.set_prior(invParam.refModel, invParam.Wm, np.ones(n))
+    ctx.set_mass(HMCMT_MASS_WM)
+    return MassOperator(ctx, HMCMT_MASS_OP_INV), MassOperator(ctx, HMCMT_MASS_OP_SQRT)
 
 
 def checkParameterBound(model, momentum, hmcprior):
@@ -217,6 +241,8 @@ def _run_fingerprint(invParam, hmcprior, shape):
     h.update(np.asarray([hmcprior.dt, hmcprior.regParam, *hmcprior.timestep, *hmcprior.sigBounds], dtype=np.float64).tobytes())
     for a in (invParam.obsData, invParam.dataW, invParam.refModel):
         h.update(np.ascontiguousarray(a).tobytes())
+    if hmcprior.massType != "diagonal":                  # (only then: checkpoints of diagonal runs stay valid)
+        h.update(b"massType=" + str(hmcprior.massType).encode())
     return h.hexdigest()
 
 
@@ -291,11 +317,12 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
-    if hmcprior.massType != "diagonal":
-        raise NotImplementedError("only the reference's default diagonal mass matrix is supported "
-                                  "(the dense variant needs nparam^2 memory, SURVEY App. B.14)")
     cur = initHMCParameter(nparam)
-    cur.invM, cur.sqrtM = setMassMatrix(nparam, 1.0)
+    diagonal = hmcprior.massType == "diagonal"             # (:80-86)
+    if diagonal:
+        cur.invM, cur.sqrtM = setMassMatrix(nparam, 1.0)
+    else:
+        cur.invM, cur.sqrtM = setMassMatrix(invParam, ctx)
     cur.rhomodel = invParam.strModel.copy()               # file start model stays the chain state (:88)
     cur.momentum = getMomentumVector(nparam, cur, rng)
     prop = HMCParameter(nparam, cur.rhomodel.copy(), cur.momentum.copy(), cur.invM, cur.sqrtM)
@@ -311,7 +338,10 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     startD, startK, startH, startM, predData = getHamiltonian(mtData, mtMesh, invParam, hmcprior, cur, ctx,
                                                               reuse_forward)
     if device_leapfrog:
-        ctx.set_prior(invParam.refModel, invParam.Wm, cur.invM)
+        ctx.set_prior(invParam.refModel, invParam.Wm, cur.invM if diagonal else np.ones(nparam))
+        if not diagonal:
+            from .lib import HMCMT_MASS_WM
+            ctx.set_mass(HMCMT_MASS_WM)                    # (the factor of setMassMatrix is kept: same Wm)
     nsamples = hmcprior.totalsamples
     hmcmodel = np.zeros((nparam, nsamples))
     hmcdata = np.zeros((ndata, nsamples + 1), dtype=np.complex128)

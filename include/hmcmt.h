@@ -145,9 +145,9 @@ int hmcmt_grad_device_async(hmcmt_ctx* ctx, const double* d_m, double* d_pred, d
 /* waits for everything enqueued on the context; returns the status of the last asynchronous evaluation */
 int hmcmt_wait(hmcmt_ctx* ctx);
 
-/* One leapfrog trajectory on the device (proposeLeapfrog, HMCSampler.jl:206-269; diagonal mass).
+/* One leapfrog trajectory on the device (proposeLeapfrog, HMCSampler.jl:206-269; the mass of hmcmt_set_mass).
  *   m0, p0 [nAC]      current model / momentum (host)
- *   invM [nAC]        diagonal of M^-1
+ *   invM [nAC]        diagonal of M^-1 (HMCMT_MASS_DIAGONAL)
  *   mref [nAC]        prior reference model; Wm in CSR (rowptr[nAC+1], colind, val; 0-based int64)
  *   dt, L, regParam, lnSigMin, lnSigMax     as in HMCPrior
  * Outputs (host): m1, p1 [nAC]; pred complex[nData] and misfit at the proposal (what the next
@@ -159,6 +159,25 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
                    double regParam, double lnSigMin, double lnSigMax,
                    double* m1, double* p1, double* pred, double* misfit, double* mnorm,
                    int32_t* nfevals);
+
+/* Mass matrix of hmcmt_leapfrog / hmcmt_leapfrog_device (runHMCSampler's choice by masstype, HMCSampler.jl:80-86).
+ *   HMCMT_MASS_DIAGONAL  the invM of hmcmt_set_prior (default; every hmcmt_set_prior call returns to it)
+ *   HMCMT_MASS_WM        M = Wm of hmcmt_set_prior (setMassMatrix(invParam), HMCSampler.jl:478-489): momentum p = L z with
+ *                        L = chol(Wm).L in the natural order of the active cells, position step dm = dt Wm^-1 p (then the step
+ *                        clamp and the reflection, which flips p), kinetic energy 0.5 p'Wm^-1 p.  hmcmt_set_mass factors Wm
+ *                        (banded Cholesky on the host, bandwidth from the CSR; kept on the device, and kept for a later
+ *                        hmcmt_set_prior with the same Wm): HMCMT_EINVAL if Wm is not positive definite.  Wm^-1 is a fast
+ *                        diagonalisation in fp64 when the active cells fill a box below the air (Wm then separates,
+ *                        kernels_mass.h), fp64 PCG on Wm otherwise (relative residual 1e-13, HMCMT_ENOCONV at its cap).
+ * hmcmt_mass_apply: y = M^-1 x (HMCMT_MASS_OP_INV) or y = L x (HMCMT_MASS_OP_SQRT) for the mass matrix that was set (for
+ *   HMCMT_MASS_DIAGONAL: invM .* x and x ./ sqrt(invM)); x, y [nAC], host (on_device = 0, synchronous) or device pointers
+ *   (on_device = 1, enqueued on the context's stream, complete on return). */
+#define HMCMT_MASS_DIAGONAL 0
+#define HMCMT_MASS_WM       1
+#define HMCMT_MASS_OP_INV   0
+#define HMCMT_MASS_OP_SQRT  1
+int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind);
+int hmcmt_mass_apply(hmcmt_ctx* ctx, int32_t op, const double* x, double* y, int32_t on_device);
 
 /* The same trajectory on DEVICE vectors: d_m, d_p [nAC] are updated in place (start model / momentum -> proposal), nothing
  * crosses PCIe.  start_grad says where the data gradient at the start model comes from:

@@ -84,6 +84,12 @@ int hmcmt_debug_persist_precond(hmcmt_ctx* ctx, int32_t sweeps, const double* r,
 int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out);   /* [2][S*vstride] complex: fused kernel | separate kernels */
 int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, double* out, double* sums);   /* out: [2][S*vstride] complex (fused | separate), sums[6] */
 
+/* The mass matrix of hmcmt_set_mass: out = {kind, seconds the host took to factor Wm (0: not factored), bandwidth of Wm,
+ * separable (1: Wm^-1 is the fast diagonalisation of the active box; 0: PCG), PCG iterations of the last Wm^-1 application
+ * (0 on the direct path), box rows, box columns} */
+#define HMCMT_MASS_INFO_FIELDS 7
+int hmcmt_mass_info(const hmcmt_ctx* ctx, double* out /*[HMCMT_MASS_INFO_FIELDS]*/);
+
 #ifdef __cplusplus
 }
 #endif

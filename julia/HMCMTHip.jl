@@ -187,22 +187,28 @@ end
 """
     setPrior!(ctx, invParam, hmcParam)
 
-Registers the prior (refModel, Wm) and the diagonal of M^-1 for device-resident trajectories (hmcmt_set_prior).
-Wm is symmetric, so its CSC arrays are its CSR arrays; they go over 0-based.  Only the reference's default, diagonal
-mass matrix is supported (setMassMatrix's dense option, HMCSampler.jl:478-489, is refused, not silently truncated).
+Registers the prior (refModel, Wm) and the mass matrix for device-resident trajectories (hmcmt_set_prior,
+hmcmt_set_mass).  Wm is symmetric, so its CSC arrays are its CSR arrays; they go over 0-based.  A diagonal invM goes
+over as its diagonal; any other is the reference's non-diagonal mass M = Wm (setMassMatrix(invParam),
+HMCSampler.jl:478-489, masstype: nondiagonal): the library factors Wm once (and keeps the factor while Wm stays the
+same) and runs the trajectory with Wm^-1 p and chol(Wm).L on the device.
 """
+const HMCMT_MASS_WM = Int32(1)
 function setPrior!(ctx::HipContext, invParam::InvDataModel, hmcParam::HMCParameter)
-    (hmcParam.invM isa Diagonal || isdiag(hmcParam.invM)) ||
-        error("HMCMTHip: only diagonal mass matrices are supported on the device (masstype: diagonal)")
+    diagonal = hmcParam.invM isa Diagonal || isdiag(hmcParam.invM)
     Wm = invParam.Wm
     rowptr = Vector{Int64}(Wm.colptr .- 1)
     colind = Vector{Int64}(Wm.rowval .- 1)
     val = Vector{Float64}(Wm.nzval)
-    invM = Vector{Float64}(diag(hmcParam.invM))
+    invM = diagonal ? Vector{Float64}(diag(hmcParam.invM)) : ones(Float64, length(invParam.refModel))
     rc = ccall((:hmcmt_set_prior, libhmcmt), Cint,
                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
                ctx.ptr, invParam.refModel, rowptr, colind, val, invM)
     checkerr(ctx.ptr, rc)
+    if !diagonal
+        rc = ccall((:hmcmt_set_mass, libhmcmt), Cint, (Ptr{Cvoid}, Int32), ctx.ptr, HMCMT_MASS_WM)
+        checkerr(ctx.ptr, rc)
+    end
     return ctx
 end
 
