@@ -229,7 +229,10 @@ struct hmcmt_ctx {
     int persistWhyOff = 0;                // why persistOn is false: 1 = a placement fallback (for good), 2 = a timed-out wait (backoff)
     long persistBackoff = 0;              // after a timed-out wait: solves on the launch-per-phase loop before the kernel is tried again (doubles per timeout)
     bool persistTimedOut = false;         // a wait of the last persistent launch timed out: evaluate() redoes the evaluation with the launch-per-phase loop
-    int dbgPlace = 0;                     // test hook (hmcmt_debug_flags bit 2): the next persistent launch's first group fails its placement check
+    int dbgPlace = 0;                     // test hook (hmcmt_debug_flags bit 2): 1 + index of the group of the next persistent launch that fails its placement check
+    bool dbgPlaceAdj = false;             // ... (bit 4) not the next launch but the next ADJOINT one: forward launches pass it by
+    int fbKind = -1;                      // the last placement fallback: kind of its launch (0 forward, 1 adjoint; -1 none yet) and the systems that
+    int fbStalled = -1;                   //   launch had started and left active -- stalled, continued from their own x and r -- (-1: not known there)
     bool counted = false;                 // this context is counted in g_quarterUse / holds a reference on the device lock
     // production guard on the error-estimate stopping rule: every guardEvery-th evaluation the TRUE residual of both
     // solves is formed (two vector passes and a read-back: ~0.1 ms once in guardEvery evaluations) -- hmcmt_guard
@@ -670,7 +673,8 @@ int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, in
     a.gateOut = precondOnly ? nullptr : ctx->d_gate + (kind == 1 ? 1 : 0);
     if (ctx->gateGen >= 0x3fffffff) ctx->gateGen = 0;           // (wrap BEFORE the increment: the followers are handed ctx->gateGen, the value this launch writes)
     a.gateGen = ++ctx->gateGen;
-    a.dbgPlace = ctx->dbgPlace; ctx->dbgPlace = 0;
+    if (ctx->dbgPlaceAdj && kind != 1) a.dbgPlace = 0;
+    else { a.dbgPlace = ctx->dbgPlace; ctx->dbgPlace = 0; ctx->dbgPlaceAdj = false; }
     a.order = ctx->psOrder[kind == 1].empty() ? nullptr : ctx->d_psOrder + (kind == 1 ? k.S : 0);
     a.resid = start.resid; a.begin = start.begin; a.nOn = ctx->nSysOn; a.sysOn = ctx->v.sysOn;
     a.doneCnt = ctx->d_psync + 32 * groups + 4;       // (in the block the kernel's last workgroup clears: exitCnt at +0, fail at +8)
@@ -854,12 +858,21 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
             // groups -- this context goes back to the launch-per-phase loop for good
             ctx->persistOn = false; ctx->persistWhyOff = 1; ctx->persistBackoff = 0; ++ctx->persistFallbacks;
             placeFallback = true;
+            ctx->fbKind = kind; ctx->fbStalled = -1;
+            if (start.begin && start.resid) {
+                // (rare, and behind a finished kernel: what it left is read back -- active 1: started and stalled, 2: never started)
+                std::vector<int> act(S);
+                HIPCHK(hipMemcpyAsync(act.data(), k.active, sizeof(int) * S, hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(hipStreamSynchronize(ctx->stream));
+                ctx->fbStalled = (int)std::count(act.begin(), act.end(), 1);
+            }
             ensure_dinv(ctx);
             if (start.begin) {
-                // (the kernel was to form the residual itself: the systems it did not touch -- still active -- have none yet; the
-                //  launch-per-phase loop's partial sums start from zero)
+                // (the kernel was to form the residual itself: the systems the misplaced groups did not touch -- active = 2 -- have none
+                //  yet; those a healthy group started and left stalled -- active = 1 -- keep their x and r: r is no longer the right-hand
+                //  side the adjoint start forms would read from it.  The launch-per-phase loop's partial sums start from zero)
                 HIPCHK(hipMemsetAsync(k.partB, 0, (size_t)S * MAXNB * sizeof(double), ctx->stream));
-                if (start.resid) hipLaunchKernelGGL(k_resid0, dim3(k.NB, S), dim3(VBLOCK), 0, ctx->stream, k, x, start.resid == PS_RESID_FULL ? 0 : start.resid, (const int*)nullptr, 1);
+                if (start.resid) hipLaunchKernelGGL(k_resid0, dim3(k.NB, S), dim3(VBLOCK), 0, ctx->stream, k, x, start.resid == PS_RESID_FULL ? 0 : start.resid, (const int*)nullptr, 2);
             }
             if (ctx->persistFallbacks == 1)
                 fprintf(stderr, "libhmcmt_hip: the workgroups of a system of the persistent solve kernel were not dispatched to one XCD (a partitioned device, "
@@ -2437,9 +2450,10 @@ int hmcmt_debug_transform(hmcmt_ctx* ctx, int32_t which, const double* A, double
 }
 
 int hmcmt_debug_flags(hmcmt_ctx* ctx, int32_t flags) {
-    if (!ctx || (flags & ~15)) return HMCMT_EINVAL;
+    if (!ctx || (flags & ~0xff1f) || ((flags & 16) && !(flags & 12)) || ((flags & 0xff00) && !(flags & 4))) return HMCMT_EINVAL;
     if (flags & 8) ctx->dbgPlace = -1;                    // (one-shot: EVERY group of the next persistent launch fails its placement check -- the all-fallback regime of a partitioned device)
-    else if (flags & 4) ctx->dbgPlace = 1;                     // (one-shot: the next persistent launch's first system group fails its placement check)
+    else if (flags & 4) ctx->dbgPlace = 1 + ((flags >> 8) & 0xff);   // (one-shot: the next persistent launch's first system group -- bits 8-15: the group of that index -- fails its placement check)
+    if (flags & 12) ctx->dbgPlaceAdj = (flags & 16) != 0;      // (bit 4: ... of the next ADJOINT launch -- forward launches pass it by)
     flags &= 3;
     ctx->dbgFlags = flags;
     ctx->memo[0].valid = ctx->memo[1].valid = false;      // (stored results belong to the flags they were computed under)
@@ -2512,7 +2526,8 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
         ctx->persistTimeouts,                 // timed-out waits (the evaluation was redone with the launch-per-phase loop)
         ctx->shareIdx, ctx->shareCnt,         // this context's share of every XCD's CUs (hmcmt_next_cu_share)
         ctx->persistCW ? ctx->persistStrips : 0,   // strips of tile rows per column: 2 (k_cocg_persist) or 4 (k_cocg_persist4: threads = strips x threads_half)
-        ctx->persistWhyOff};                  // why the kernel is off: 0 it is not / HMCMT_PERSIST=0, 1 placement (for good), 2 a timed-out wait (tried again after the backoff)
+        ctx->persistWhyOff,                   // why the kernel is off: 0 it is not / HMCMT_PERSIST=0, 1 placement (for good), 2 a timed-out wait (tried again after the backoff)
+        ctx->fbKind, ctx->fbStalled};         // the last placement fallback: kind of its launch, systems it found started and still active (stalled)
     for (int i = 0; i < nout && i < HMCMT_PERSIST_INFO_FIELDS; ++i) out[i] = v[i];
     return 0;
 }

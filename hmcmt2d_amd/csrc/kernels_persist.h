@@ -651,12 +651,14 @@ __global__ __launch_bounds__(2 * CW) void k_cocg_persist(PsLaunch L) {
     bool alive = __builtin_amdgcn_readfirstlane(sflag[0]) == 0;
     if (!alive && L.begin && jw == 0 && tid == 0 && sflag[0] == 1) {
         // (a misplaced group leaves its systems untouched -- with the solve's bookkeeping done in this kernel, that includes marking them
-        //  as still to be solved: the host's launch-per-phase loop forms their residual and takes them)
+        //  as still to be solved: the host's launch-per-phase loop forms their residual and takes them.  Where this kernel was to form the
+        //  residual, "never started" is active = 2: a system of a healthy group that stalls also leaves active (1), with ITS r and x, which
+        //  the host continues -- r is no longer the right-hand side a fresh residual would be formed from (k_resid0, onlyActive = 2)
         for (int round = 0;; ++round) {
             const int q = xcd + 8 * (slot + slots * round);
             if (q >= kb->S) break;
             const int s = L.order ? L.order[q] : q;
-            kb->active[s] = L.sysOn[s]; kb->iters[s] = 0; kb->status[s] = 0;
+            kb->active[s] = L.sysOn[s] && L.resid ? 2 : L.sysOn[s]; kb->iters[s] = 0; kb->status[s] = 0;
         }
     }
 

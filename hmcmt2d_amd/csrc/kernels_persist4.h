@@ -110,12 +110,12 @@ __global__ __launch_bounds__(4 * CW) void k_cocg_persist4(PsLaunch L) {
     }
     __syncthreads();
     bool alive = __builtin_amdgcn_readfirstlane(sflag[0]) == 0;
-    if (!alive && L.begin && jw == 0 && tid == 0 && sflag[0] == 1) {      // (a misplaced group: its systems stay to be solved, kernels_persist.h)
+    if (!alive && L.begin && jw == 0 && tid == 0 && sflag[0] == 1) {      // (a misplaced group: its systems stay to be solved -- 2: never started --, kernels_persist.h)
         for (int round = 0;; ++round) {
             const int q = xcd + 8 * (slot + slots * round);
             if (q >= kb->S) break;
             const int s = L.order ? L.order[q] : q;
-            kb->active[s] = L.sysOn[s]; kb->iters[s] = 0; kb->status[s] = 0;
+            kb->active[s] = L.sysOn[s] && L.resid ? 2 : L.sysOn[s]; kb->iters[s] = 0; kb->status[s] = 0;
         }
     }
 

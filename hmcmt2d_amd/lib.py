@@ -466,11 +466,16 @@ class HipContext:
         self._check(self.lib.hmcmt_debug_transform(self.h, which, _dp(A), _dp(Cc)))
         return Cc
 
-    def debug_flags(self, freeze_boundary=False, no_boundary_terms=False, fail_placement=False):
+    def debug_flags(self, freeze_boundary=False, no_boundary_terms=False, fail_placement=False, on="next", group=0):
         """Test hook (include/hmcmt_debug.h): hold the Dirichlet values at the previous evaluation's / leave dBC^T w out of the gradient /
-        (one-shot) let the first system group -- fail_placement="all": EVERY group -- of the next persistent launch fail its placement check."""
+        (one-shot) let the first system group -- `group`: the group of that index, xcd x slots_per_xcd + slot; fail_placement="all": EVERY
+        group -- of the next persistent launch fail its placement check (on="adjoint": of the next adjoint launch; forward launches pass it by)."""
+        if on not in ("next", "adjoint") or not 0 <= int(group) < 256:
+            raise ValueError(f"debug_flags: on={on!r} (\"next\" or \"adjoint\"), group={group!r} (0 .. 255)")
         self._cache = None
-        place = 8 if fail_placement == "all" else (4 if fail_placement else 0)
+        place = 8 if fail_placement == "all" else (4 | int(group) << 8 if fail_placement else 0)
+        if place and on == "adjoint":
+            place |= 16
         self._check(self.lib.hmcmt_debug_flags(self.h, (1 if freeze_boundary else 0) | (2 if no_boundary_terms else 0) | place))
 
     def debug_spmv(self, p):
@@ -493,10 +498,11 @@ class HipContext:
 
     def persist_info(self):
         """The persistent solve kernel and this context (kernels_persist.h): shape, whether it is enabled, how many solves it ran."""
-        out = (C.c_int64 * 14)()
-        self._check(self.lib.hmcmt_persist_info(self.h, out, 14))
+        out = (C.c_int64 * 16)()
+        self._check(self.lib.hmcmt_persist_info(self.h, out, 16))
         return dict(zip(("threads_half", "workgroups_per_system", "slots_per_xcd", "enabled", "solves", "placement_fallbacks", "usable_now", "slab_modes",
-                         "column_parts", "timeouts", "cu_share_index", "cu_share_count", "strips", "why_off"), (int(x) for x in out)))
+                         "column_parts", "timeouts", "cu_share_index", "cu_share_count", "strips", "why_off",
+                         "fallback_kind", "fallback_stalled"), (int(x) for x in out)))
 
     def persist_width(self):
         """Row width (padded nodes) of the width-specialised persistent kernel this context launches; 0: the generic kernel."""

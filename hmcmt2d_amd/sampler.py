@@ -479,7 +479,8 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
 
     if chains_per_gpu > 1 and len(mine) > 1:
         from concurrent.futures import ThreadPoolExecutor
-        workers = shares if int(chains_per_gpu) in (2, 4) else int(chains_per_gpu)
+        # (one worker per share: a worker without a share of its own would pop an empty list -- chains_per_gpu = 3 has two)
+        workers = shares if shares > 1 else int(chains_per_gpu)
         with ThreadPoolExecutor(max_workers=workers) as pool:      # (the library calls release the GIL)
             list(pool.map(one_chain, mine))
     else:

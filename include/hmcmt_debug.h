@@ -49,6 +49,10 @@ int hmcmt_debug_transform(hmcmt_ctx* ctx, int32_t which, const double* A, double
  *   workgroups were not on one XCD (tests/test_gpu_persist.py: the other groups finish, the launch-per-phase loop takes the rest).
  *   bit 3 (one-shot) -- EVERY group of the next persistent launch fails it: the all-fallback regime of a device in another partition
  *   mode or a driver with another dispatch order (the whole evaluation then runs the launch-per-phase loop, one line on stderr).
+ *   bits 8-15 (with bit 2) -- not the first group but the group of that index (xcd x slots per XCD + slot: the group that takes the
+ *   systems xcd + 8 slot, ... -- hmcmt_persist_info) fails it.
+ *   bit 4 (with bit 2 or 3) -- not the next persistent launch but the next ADJOINT one (forward launches pass the one-shot failure
+ *   by): a misplaced group beside systems the adjoint solve has started and stalled (tests/test_gpu_persist.py).
  *   0 restores the product behaviour; stored results of earlier calls are dropped. */
 int hmcmt_debug_flags(hmcmt_ctx* ctx, int32_t flags);
 int hmcmt_debug_spmv(hmcmt_ctx* ctx, const double* p, double* q);
@@ -57,7 +61,7 @@ int hmcmt_persist_envelope(int64_t ny, int64_t nz, int32_t cus_per_xcd, int64_t 
                                                              layers) run the one-launch-per-solve kernel on a device with cus_per_xcd CUs per XCD (MI355X: 32; a half / quarter CU
                                                              share: 16 / 8), and how: {column parts (0 = outside its envelope: the launch-per-phase loop), threads / 2, workgroups per
                                                              system, modes per slab, LDS bytes per workgroup, systems per XCD at a time} */
-#define HMCMT_PERSIST_INFO_FIELDS 14
+#define HMCMT_PERSIST_INFO_FIELDS 16
 int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout);  /* writes min(nout, HMCMT_PERSIST_INFO_FIELDS) values -- fields are only ever APPENDED, so a caller built against an
                                                                    older header passes its own count and gets the fields it knows --:
                                                                    {threads per strip (0: not applicable), workgroups per system, slots per XCD, enabled, solves, placement fallbacks,
@@ -67,7 +71,10 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout);  /* wr
                                                                    timed-out waits (each one: the evaluation redone with the launch-per-phase loop),
                                                                    CU share index, CU share count (hmcmt_next_cu_share),
                                                                    strips of tile rows per column (2: k_cocg_persist, 4: k_cocg_persist4; threads per workgroup = strips x threads per strip),
-                                                                   why the kernel is off (0: it is not, or HMCMT_PERSIST=0; 1: a placement fallback, for good; 2: a timed-out wait, tried again later)} */
+                                                                   why the kernel is off (0: it is not, or HMCMT_PERSIST=0; 1: a placement fallback, for good; 2: a timed-out wait, tried again later),
+                                                                   the last placement fallback: kind of its launch (0 forward, 1 adjoint; -1: none yet),
+                                                                   ... and the systems that launch had started itself and left active -- stalled, the host continues them from their
+                                                                   own x and r -- (-1: a launch that did not form the residual itself, where they are not told apart)} */
 int hmcmt_persist_order(const hmcmt_ctx* ctx, int32_t kind, int32_t* order, int64_t* rebalanced);   /* meshes whose systems take turns on the chip (more systems than 8 x
                                                              slots per XCD: cfg5): the order in which the persistent kernel's queues take the systems of a solve of
                                                              `kind` (0 forward, 1 adjoint) -- order[nsystems], position queue + queues * round -> system --, balanced from

@@ -370,7 +370,7 @@ def test_every_group_misplaced_is_the_all_fallback_regime_end_to_end(monkeypatch
 def test_misplaced_groups_when_the_kernel_was_to_start_the_solve(monkeypatch, which, start):
     """Round 6: the initial residual and the solve's bookkeeping are formed INSIDE the persistent kernel (PsLaunch::resid / begin;
     not under options.verify, which the other placement tests use).  A group that fails its placement check -- one, or every one --
-    then leaves systems that have no residual yet: it marks them "to be solved", the host forms their residual (k_resid0 on the active
+    then leaves systems that have no residual yet: it marks them "to be solved", the host forms their residual (k_resid0 on the never-started
     systems only: the other groups' results stay) and its launch-per-phase loop takes them.  Cold and warm-started evaluations, the
     forward and the adjoint solve (right-hand side on the receiver layer's rows), against HMCMT_PS_START=0 and the oracle."""
     monkeypatch.setenv("HMCMT_PS_START", start)
@@ -393,6 +393,66 @@ def test_misplaced_groups_when_the_kernel_was_to_start_the_solve(monkeypatch, wh
     po, mo, go = oracle_eval(mesh, data, inv, m)
     assert relmax(p, po) < 1e-9 and relmax(g, go) < 1e-7 and ctx.persist_info()["placement_fallbacks"] == 1
     ctx.close()
+
+
+_KERNELS = {"strips2": {"HMCMT_PERSIST_STRIPS": "2"}, "strips4": {"HMCMT_PERSIST_STRIPS": "4"},
+            "cs2": {"HMCMT_PERSIST_STRIPS": "2", "HMCMT_PERSIST_CS": "2"}}
+# (launch hit, start form, misplaced groups, forced stall, kernel): every stalled case; the stall-free ones on the two-strip kernel,
+# and on the other two for the adjoint launch
+_COMBINED = ([(w, s, "first", True, k) for w in ("fwd", "adj") for s in ("cold", "warm", "warm_full") for k in _KERNELS]
+             + [(w, s, g, False, "strips2") for w in ("fwd", "adj") for s in ("cold", "warm", "warm_full") for g in ("first", "all")]
+             + [("adj", s, g, False, k) for s in ("cold", "warm_full") for g in ("first", "all") for k in ("strips4", "cs2")])
+
+
+@pytest.mark.parametrize("which,start,groups,stall,kernel", _COMBINED)
+def test_misplaced_groups_beside_stalled_systems_of_the_same_launch(monkeypatch, which, start, groups, stall, kernel):
+    """Two exits of the persistent kernel in ONE launch: a group that fails its placement check (hmcmt_debug_flags bit 2 / 3, aimed at
+    the forward or -- bit 4 -- the adjoint launch) and systems of the healthy groups that stall (HMCMT_STALL_IT = 1 with one sweep
+    per side: a system whose error estimate does not drop tenfold within two iterations hands over).  Where the kernel forms the solve's start itself, a stalled system leaves
+    active with its CURRENT x and r; the host forms a fresh residual only for the systems the misplaced groups never started.  Had
+    it formed one for the stalled systems too, an adjoint start that reads its right-hand side from r (cold: the receiver layer's
+    rows, 2 + zid; warm; warm and guarded: PS_RESID_FULL) would solve A x = r_cur - A x_cur: a clean convergence to a wrong adjoint
+    field, a wrong gradient, no status.  Not under options.verify, which forms the start outside the kernel.  Against the oracle;
+    hmcmt_persist_info says which launch the fallback hit and how many started systems it found stalled there."""
+    for k, v in _KERNELS[kernel].items():
+        monkeypatch.setenv(k, v)
+    if "HMCMT_PERSIST_CS" not in _KERNELS[kernel]:
+        monkeypatch.delenv("HMCMT_PERSIST_CS", raising=False)
+    if stall:
+        monkeypatch.setenv("HMCMT_STALL_IT", "1")
+    else:
+        monkeypatch.delenv("HMCMT_STALL_IT", raising=False)
+    monkeypatch.setenv("HMCMT_GUARD_EVERY", "2" if start == "warm_full" else "100")     # (evaluation 2 guarded: the whole r is its right-hand side)
+    mesh, data, inv, m = make_problem("cfg2")
+    # (measured on cfg2 with the forced stall: at m one forward system stalls and no adjoint one; at m - 0.5 one adjoint system does,
+    #  cold and warm, beside whichever group is misplaced but one -- the first among them)
+    m = m - 0.5 if which == "adj" else m
+    ctx = _ctx(monkeypatch, mesh, data, inv, True, 1)
+    info = ctx.persist_info()
+    assert info["strips"] == int(_KERNELS[kernel]["HMCMT_PERSIST_STRIPS"]) and info["column_parts"] == (2 if kernel == "cs2" else 1)
+    mt = m
+    if start != "cold":
+        ctx.grad(m)                                        # a history: the next evaluation starts warm
+        mt = m + 0.02
+        assert ctx.persist_info()["solves"] == 2 and ctx.persist_info()["placement_fallbacks"] == 0
+    ctx.debug_flags(fail_placement="all" if groups == "all" else True, on="adjoint" if which == "adj" else "next")
+    p, f, g = ctx.grad(mt)
+    st, info = ctx.stats(), ctx.persist_info()
+    guard = ctx.guard()
+    ctx.close()
+    po, mo, go = oracle_eval(mesh, data, inv, mt)
+    # what happened in that launch: the one aimed at, and -- with the forced stall and a healthy group beside the misplaced one --
+    # started systems left stalled (every group misplaced: none started)
+    assert info["placement_fallbacks"] == 1 and info["fallback_kind"] == (1 if which == "adj" else 0)
+    if groups == "all":
+        assert info["fallback_stalled"] == 0
+    elif stall:
+        assert info["fallback_stalled"] >= 1
+    assert st["status"] == 0
+    if start == "warm_full":
+        assert guard["checks"] >= 1 and guard["trips"] == 0
+    assert relmax(p, po) < 1e-9 and abs(f - mo) / mo < 1e-9
+    assert relmax(g, go) < 1e-7, (relmax(g, go), info["fallback_stalled"])
 
 
 @pytest.mark.parametrize("which", [True, "all"])

@@ -213,6 +213,44 @@ def test_cu_shares_follow_the_chains_that_actually_run():
     assert cu_shares_for(1, 8) == 1 and cu_shares_for(3, 8) == 2
 
 
+@pytest.mark.parametrize("chains_per_gpu,nchains", [(3, 3), (3, 8), (5, 3), (5, 8), (8, 3), (8, 8)])
+def test_chains_per_gpu_outside_1_2_4_runs_every_chain_on_its_shares(monkeypatch, chains_per_gpu, nchains):
+    """chains_per_gpu = 3, 5, 8 (a warning, not an error): as many worker threads as CU shares, every chain on a share of its own
+    while it runs -- more workers than shares popped an empty share list (IndexError) -- and every chain's result returned."""
+    import threading
+    import time
+    import warnings
+    mesh, data, inv, m = make_problem("tiny")
+    prior = HMCPrior(totalsamples=2)
+    nparam, ndata = len(inv.strModel), len(inv.obsData)
+    shares = sampler.cu_shares_for(chains_per_gpu, nchains)
+    lock, running, seen = threading.Lock(), [0, 0], []
+
+    def factory(mesh_c, data_c, inv_c, dev):
+        return object()
+
+    def fake_run(mesh_c, data_c, inv_c, prior_c, rng, ctx=None, **kw):
+        with lock:
+            running[0] += 1
+            running[1] = max(running[1], running[0])
+        time.sleep(0.02)                                   # (long enough for the pool's other workers to be inside as well)
+        with lock:
+            running[0] -= 1
+            seen.append(float(rng.standard_normal()))
+        st = H.HMCStatus(1, 1, np.array([True, False]), np.zeros((4, 3)))
+        return np.full((nparam, 2), float(len(seen))), st, np.zeros((ndata, 3), complex)
+
+    monkeypatch.setattr(sampler, "runHMCSampler", fake_run)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        hm, hs, hd = sampler.parallelHMCSampler(mesh, data, inv, prior, nchains=nchains, seed=3, context_factory=factory,
+                                                chains_per_gpu=chains_per_gpu)
+    assert len(hm) == len(hs) == len(hd) == nchains and len(seen) == nchains
+    assert all(h is not None and h.shape == (nparam, 2) for h in hm)
+    assert sorted(float(h[0, 0]) for h in hm) == list(range(1, nchains + 1))      # every chain's own result
+    assert 1 <= running[1] <= shares
+
+
 def test_bench_dump_writes_float64_npy_files_under_the_size_limit(tmp_path):
     """bench.py --dump-outputs DIR: one DIR/<name>.npy per output, float64, and a dump beyond the limit is refused."""
     import importlib.util
