@@ -59,6 +59,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_persist4.h"
 #include "kernels_path.h"
 #include "kernels_mass.h"
+#include "kernels_jac.h"
 
 }  // namespace
 
@@ -256,6 +257,19 @@ struct hmcmt_ctx {
     Memo memo[2];
     int memoNext = 0;
     long long memoHits = 0;
+    // explicit Jacobian (hmcmt_jacobian / hmcmt_sensitivity, kernels_jac.h): its own solution and boundary arrays, the saved forward
+    // fields and extrapolation state of the context's evaluations, the batches' data lists and system flags (allocated on first use)
+    struct Jac {
+        bool ready = false;
+        cplx *lam = nullptr, *xSave = nullptr, *srcB = nullptr, *wL = nullptr, *wR = nullptr, *colw = nullptr, *gL = nullptr, *gR = nullptr;
+        cplx *qJ = nullptr, *pred = nullptr;
+        double *extSave = nullptr, *misfit = nullptr, *m = nullptr, *rows = nullptr, *sens = nullptr;
+        double* h_rows = nullptr;          // pinned staging of one batch's rows (host entry point)
+        JacEntry* list = nullptr;          // [nData]
+        JacGroup* groups = nullptr;        // [nData] runs of the list with one system
+        int* sysOn = nullptr;              // [nRx][S]
+        int maxRows = 0;                   // most data of one receiver
+    } jac;
 };
 
 static thread_local std::string g_createError;      // (per thread: contexts of different chains are created from different threads)
@@ -1636,6 +1650,7 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
 
     if (ctx->h_rec) hipHostFree(ctx->h_rec);
     if (ctx->h_stage) hipHostFree(ctx->h_stage);
+    if (ctx->jac.h_rows) hipHostFree(ctx->jac.h_rows);
     if (ctx->h_lfFlag) hipHostFree(ctx->h_lfFlag);
     if (ctx->h_psOrder) hipHostFree(ctx->h_psOrder);
     if (ctx->evModel) hipEventDestroy(ctx->evModel);
@@ -3260,6 +3275,284 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
     if (misfit) *misfit = hs[2 * n + 2 * nData];
     if (mnorm) *mnorm = hs[2 * n + 2 * nData + 1];
     if (nfevals) *nfevals = evals;
+    return 0;
+}
+
+// ----------------------------------------------------------------------------------------------
+// explicit Jacobian (kernels_jac.h): batches by receiver -- receiver j in every system is the shape and right-hand-side sparsity of
+// the gradient's adjoint solve, so every batch is one solve(ctx, x, 1) with the in-kernel sparse start and the same fallbacks.
+// The forward fields come from a cold evaluate() at the model; everything that evaluation and the batch solves move in the
+// context (warm-start fields and extrapolation state, sweep choice, iteration guesses, statistics, evaluation count, system
+// flags) is saved in front and put back behind (JacState), so the context's next evaluation computes what it would have.
+// ----------------------------------------------------------------------------------------------
+static int jac_alloc(hmcmt_ctx* ctx) {
+    hmcmt_ctx::Jac& J = ctx->jac;
+    if (J.ready) return 0;
+    const View& v = ctx->v;
+    const int S = v.S;
+    const size_t vec = (size_t)S * v.vstride;
+    std::vector<int> perRx(v.nRx, 0);
+    for (int p = 0; p < v.nData; ++p) ++perRx[ctx->hp.datRx[p]];
+    J.maxRows = std::max(1, *std::max_element(perRx.begin(), perRx.end()));
+    int rc = 0;
+    if ((rc = dalloc(ctx, &J.lam, vec)) || (rc = dalloc(ctx, &J.xSave, vec, false)) || (rc = dalloc(ctx, &J.srcB, (size_t)S * 4)) ||
+        (rc = dalloc(ctx, &J.wL, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.wR, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.colw, (size_t)S * v.ny)) ||
+        (rc = dalloc(ctx, &J.gL, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.gR, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.qJ, (size_t)S * v.ny)) ||
+        (rc = dalloc(ctx, &J.pred, (size_t)v.nData)) || (rc = dalloc(ctx, &J.extSave, (size_t)EXT_LEN, false)) || (rc = dalloc(ctx, &J.misfit, 1)) ||
+        (rc = dalloc(ctx, &J.m, (size_t)v.nAC)) || (rc = dalloc(ctx, &J.sens, (size_t)v.nAC)) ||
+        (rc = dalloc(ctx, &J.rows, (size_t)J.maxRows * v.nAC * 2)) || (rc = dalloc(ctx, &J.list, (size_t)v.nData)) ||
+        (rc = dalloc(ctx, &J.groups, (size_t)v.nData)) ||
+        (rc = dalloc(ctx, &J.sysOn, (size_t)v.nRx * S)))
+        return rc;
+    HIPCHK(hipHostMalloc((void**)&J.h_rows, sizeof(double) * (size_t)J.maxRows * v.nAC * 2));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    J.ready = true;
+    return 0;
+}
+
+// what a Jacobian call moves in the context and puts back
+struct JacState {
+    View v; Solver sv; hmcmt_options opt; hmcmt_stats stats;
+    long long evalCount; unsigned profMask; int guardEvery, dbgFlags, nSysOn;
+    bool haveFwd, haveAdj, haveModel, guardDropWarm, solveDone[2];
+    int lastItFwd, lastItAdj, sweepsKind[2], sweepsUsed[2], sweepsCount2[2], sweepsSince[2];
+    bool sweepsProbe[2];
+    std::vector<int> itersLast, psOrder[2];
+    std::vector<float> psCost[2];
+    long psRebalanced;
+    LfStep lfStep; LfMom lfMom;
+    bool persistOn; int persistWhyOff; long persistBackoff; long long persistTimeouts, persistFallbacks;
+};
+static void jac_save(hmcmt_ctx* c, JacState& t) {
+    t.v = c->v; t.sv = c->sv; t.opt = c->opt; t.stats = c->stats;
+    t.evalCount = c->evalCount; t.profMask = c->profMask; t.guardEvery = c->guardEvery; t.dbgFlags = c->dbgFlags; t.nSysOn = c->nSysOn;
+    t.haveFwd = c->haveFwd; t.haveAdj = c->haveAdj; t.haveModel = c->haveModel; t.guardDropWarm = c->guardDropWarm;
+    t.solveDone[0] = c->solveDone[0]; t.solveDone[1] = c->solveDone[1];
+    t.lastItFwd = c->lastItFwd; t.lastItAdj = c->lastItAdj;
+    for (int k = 0; k < 2; ++k) {
+        t.sweepsKind[k] = c->sweepsKind[k]; t.sweepsUsed[k] = c->sweepsUsed[k]; t.sweepsCount2[k] = c->sweepsCount2[k];
+        t.sweepsSince[k] = c->sweepsSince[k]; t.sweepsProbe[k] = c->sweepsProbe[k]; t.psOrder[k] = c->psOrder[k]; t.psCost[k] = c->psCost[k];
+    }
+    t.itersLast = c->itersLast; t.psRebalanced = c->psRebalanced;
+    t.lfStep = c->lfStep; t.lfMom = c->lfMom;
+    t.persistOn = c->persistOn; t.persistWhyOff = c->persistWhyOff; t.persistBackoff = c->persistBackoff;
+    t.persistTimeouts = c->persistTimeouts; t.persistFallbacks = c->persistFallbacks;
+}
+static void jac_restore(hmcmt_ctx* c, const JacState& t) {
+    c->v = t.v; c->sv = t.sv; c->opt = t.opt; c->stats = t.stats;
+    c->evalCount = t.evalCount; c->profMask = t.profMask; c->guardEvery = t.guardEvery; c->dbgFlags = t.dbgFlags; c->nSysOn = t.nSysOn;
+    c->haveFwd = t.haveFwd; c->haveAdj = t.haveAdj; c->haveModel = t.haveModel; c->guardDropWarm = t.guardDropWarm;
+    c->solveDone[0] = t.solveDone[0]; c->solveDone[1] = t.solveDone[1];
+    c->lastItFwd = t.lastItFwd; c->lastItAdj = t.lastItAdj;
+    for (int k = 0; k < 2; ++k) {
+        c->sweepsKind[k] = t.sweepsKind[k]; c->sweepsUsed[k] = t.sweepsUsed[k]; c->sweepsCount2[k] = t.sweepsCount2[k];
+        c->sweepsSince[k] = t.sweepsSince[k]; c->sweepsProbe[k] = t.sweepsProbe[k]; c->psOrder[k] = t.psOrder[k]; c->psCost[k] = t.psCost[k];
+    }
+    c->itersLast = t.itersLast; c->psRebalanced = t.psRebalanced;
+    c->lfStep = t.lfStep; c->lfMom = t.lfMom;
+    // the persistent kernel's backoff after a timed-out wait counts the context's own solves: the Jacobian's do not count.  A timeout
+    // or placement failure DURING the call is an event of the device, not of the call: its state (kernel off, a new backoff) stays
+    if (c->persistTimeouts == t.persistTimeouts && c->persistFallbacks == t.persistFallbacks) {
+        c->persistOn = t.persistOn; c->persistWhyOff = t.persistWhyOff; c->persistBackoff = t.persistBackoff;
+    }
+    c->psStart = hmcmt_ctx::PsStart{};
+    c->solveBegun = c->preDone = false;
+    c->specValid = false; c->solveFail = 0; c->lpFallback = false;
+}
+
+// the records k_solve_end left for solve kind `kind` (the caller has synchronised) -> totals of the Jacobian's statistics
+static void jac_records(hmcmt_ctx* ctx, int kind, const int* on, hmcmt_stats& st) {
+    const int S = ctx->v.S;
+    const int* it = reinterpret_cast<const int*>(ctx->h_rec);
+    const int* status = it + 2 * S;
+    const double* err = ctx->h_rec + 2 * S;
+    for (int s = 0; s < S; ++s) {
+        if (!on[s]) continue;
+        const int n = it[kind * S + s];
+        if (kind == 0) { st.iters_fwd_max = std::max(st.iters_fwd_max, n); st.iters_fwd_sum += n; }
+        else { st.iters_adj_max = std::max(st.iters_adj_max, n); st.iters_adj_sum += n; }
+        st.err_est_max = std::max(st.err_est_max, err[kind * S + s]);
+        if (status[kind * S + s] != 0 && st.status == 0) st.status = status[kind * S + s];
+    }
+}
+
+// rows [row0, row0 + nrows) of J (hostJ: host memory, else device memory; null: the sensitivity into ctx->jac.sens instead)
+static int jac_run(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int wrt, double* outJ, bool hostJ, bool sens,
+                   hmcmt_stats* stOut) {
+    hmcmt_ctx::Jac& J = ctx->jac;
+    const View& v0 = ctx->v;
+    const int S = v0.S, nAC = v0.nAC, nRx = v0.nRx;
+    const bool cplxOut = ctx->hp.datKind.empty() || ctx->hp.datKind[0] == 0;    // (the two data families cannot be mixed)
+    const int width = cplxOut ? 2 : 1;
+    // the batches: the receivers of the rows, in receiver order; per batch the data (in data order) and the systems they need
+    std::vector<std::vector<JacEntry>> lists(nRx);
+    std::vector<int> on((size_t)nRx * S, 0);
+    for (int64_t p = row0; p < row0 + nrows; ++p) {
+        const int j = ctx->hp.datRx[p], s = ctx->hp.datSys[p];
+        lists[j].push_back(JacEntry{(int)p, 0, s, ctx->hp.datKind[p]});
+        on[(size_t)j * S + s] = 1;
+    }
+    // (within a batch the data are grouped by system, in data order inside a group: one dZ row per system, JacGroup)
+    std::vector<JacEntry> flat;
+    std::vector<JacGroup> groups;
+    std::vector<int> gfirst(nRx, 0), ngroups(nRx, 0);
+    for (int j = 0; j < nRx; ++j) {
+        std::stable_sort(lists[j].begin(), lists[j].end(), [](const JacEntry& x, const JacEntry& y) { return x.s < y.s; });
+        gfirst[j] = (int)groups.size();
+        for (size_t q = 0; q < lists[j].size(); ++q) {
+            JacEntry e = lists[j][q];
+            e.row = hostJ ? (int)q : (int)(e.p - row0);      // (host: the batch's compact staging rows)
+            if (q == 0 || e.s != lists[j][q - 1].s) groups.push_back(JacGroup{(int)flat.size(), 0});
+            ++groups.back().count;
+            flat.push_back(e);
+        }
+        ngroups[j] = (int)groups.size() - gfirst[j];
+    }
+    hmcmt_stats st{};
+    st.nsystems = S;
+    if (flat.empty()) { if (stOut) *stOut = st; return 0; }
+    hipStream_t strm = ctx->stream;
+    HIPCHK(hipMemcpyAsync(J.list, flat.data(), sizeof(JacEntry) * flat.size(), hipMemcpyHostToDevice, strm));
+    HIPCHK(hipMemcpyAsync(J.sysOn, on.data(), sizeof(int) * on.size(), hipMemcpyHostToDevice, strm));
+    HIPCHK(hipMemcpyAsync(J.groups, groups.data(), sizeof(JacGroup) * groups.size(), hipMemcpyHostToDevice, strm));
+    HIPCHK(hipStreamSynchronize(strm));                  // (host vectors: the copies are complete before they go out of scope)
+    const size_t vecBytes = (size_t)S * v0.vstride * sizeof(cplx);
+
+    JacState saved;
+    jac_save(ctx, saved);
+    // the context's forward fields and extrapolation state: the Jacobian's cold forward evaluation overwrites them
+    HIPCHK(hipMemcpyAsync(J.xSave, v0.X, vecBytes, hipMemcpyDeviceToDevice, strm));
+    HIPCHK(hipMemcpyAsync(J.extSave, ctx->d_ext[0], sizeof(double) * EXT_LEN, hipMemcpyDeviceToDevice, strm));
+    auto put_back = [&]() {
+        (void)hipMemcpyAsync(ctx->v.X, J.xSave, vecBytes, hipMemcpyDeviceToDevice, strm);
+        (void)hipMemcpyAsync(ctx->d_ext[0], J.extSave, sizeof(double) * EXT_LEN, hipMemcpyDeviceToDevice, strm);
+        (void)hipStreamSynchronize(strm);
+        jac_restore(ctx, saved);
+    };
+    auto fail = [&](int rc) { const std::string e = ctx->err; put_back(); ctx->err = e; if (stOut) *stOut = st; return rc; };
+
+    // 1. forward fields at the model: a cold forward evaluation -- no guard, no sampled profiling, no test hooks, no leapfrog update
+    ctx->opt.warm_start = 0;
+    ctx->guardEvery = 0; ctx->profMask = 0; ctx->dbgFlags = 0;
+    ctx->lfStep.on = 0; ctx->lfMom.on = 0;
+    int rc = evaluate(ctx, d_m, false, reinterpret_cast<double*>(J.pred), J.misfit, nullptr);
+    if (rc) return fail(rc);
+    HIPCHK(hipStreamSynchronize(strm));
+    jac_records(ctx, 0, ctx->hp.sysOn.data(), st);
+    if (st.status) { ctx->err = st.status == HMCMT_EBREAKDOWN ? "Jacobian: the forward solve broke down" : "Jacobian: the forward solve did not converge"; return fail(st.status); }
+    // 2. what the gradient's side stream and k_rxall(wantGrad) provide: the boundary-derivative tables and the receiver functionals
+    View vj = ctx->v;
+    vj.m = d_m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
+    hipLaunchKernelGGL(k_sens_layers, dim3((vj.nz + 1 + 63) / 64, 3, S), dim3(64), 0, strm, vj);
+    hipLaunchKernelGGL(k_sens_profile, dim3((3 * S + 63) / 64), dim3(64), 0, strm, vj);
+    hipLaunchKernelGGL(k_bcsens_pre, dim3((vj.nz + 63) / 64, 3, S), dim3(64), 0, strm, vj);
+    hipLaunchKernelGGL(k_rx, grid1(S * nRx, 64), dim3(64), 0, strm, vj, 1);
+    vj.Lam = J.lam; vj.R = ctx->sv.r; vj.srcB = J.srcB; vj.wL = J.wL; vj.wR = J.wR; vj.colw = J.colw; vj.gL = J.gL; vj.gR = J.gR;
+    if (sens) HIPCHK(hipMemsetAsync(J.sens, 0, sizeof(double) * nAC, strm));
+    const int sweeps = (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2;    // (cold solves: well above the two-sweep threshold)
+    ctx->stats.smoother_sweeps = 0;
+    const int nsrc = (2 * (v0.ny + 1) + 127) / 128;
+    // 3. one batch per receiver
+    for (int j = 0; j < nRx; ++j) {
+        const int n = (int)lists[j].size();
+        if (n == 0) continue;
+        const int* onj = on.data() + (size_t)j * S;
+        vj.sysOn = J.sysOn + (size_t)j * S;
+        ctx->v.sysOn = vj.sysOn;
+        ctx->nSysOn = (int)std::count(onj, onj + S, 1);
+        for (int attempt = 0;; ++attempt) {
+            HIPCHK(hipMemsetAsync(J.lam, 0, vecBytes, strm));
+            const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 &&
+                                       !ctx->opt.verify && persist_ok(ctx);
+            if (!inKernelStart) HIPCHK(hipMemsetAsync(vj.R, 0, vecBytes, strm));     // (the whole right-hand side is the residual)
+            hipLaunchKernelGGL(k_jac_src, dim3(nsrc + (v0.ny + 127) / 128, S), dim3(128), 0, strm, vj, j, J.qJ, nsrc);
+            ctx->sv.sweeps = sweeps;
+            ctx->preDone = false;
+            if (inKernelStart) { ctx->psStart.resid = 2 + v0.zid; ctx->psStart.begin = 1; ctx->solveBegun = true; }
+            else ctx->solveBegun = false;
+            ctx->guardNow = false;
+            ctx->persistTimedOut = false;
+            const int fb0 = ctx->stats.fallback_solves;
+            rc = solve(ctx, J.lam, 1);
+            if (rc) return fail(rc);
+            if (ctx->persistTimedOut && attempt == 0) {
+                // (a wait of the persistent kernel timed out: the context is on the launch-per-phase loop now -- the batch again, there)
+                ctx->persistTimedOut = false;
+                (void)hipStreamSynchronize(strm); (void)hipGetLastError();
+                ctx->solveFail = 0; *(volatile int*)(ctx->h_stall + 1) = 0;
+                ctx->stats.fallback_solves = fb0;
+                continue;
+            }
+            if (ctx->stats.fallback_solves > fb0) ++st.fallback_solves;
+            break;
+        }
+        if (ctx->solveFail || !ctx->solveDone[1]) {
+            HIPCHK(hipStreamSynchronize(strm));
+            jac_records(ctx, 1, onj, st);
+            if (st.status == 0) st.status = ctx->solveFail ? ctx->solveFail : HMCMT_ENOCONV;
+            ctx->err = st.status == HMCMT_EBREAKDOWN ? "Jacobian: an adjoint solve broke down" : "Jacobian: an adjoint solve did not converge";
+            return fail(st.status == HMCMT_EBREAKDOWN ? HMCMT_EBREAKDOWN : HMCMT_ENOCONV);
+        }
+        hipLaunchKernelGGL(k_jac_wb, dim3((v0.nz + v0.ny + 127) / 128, S), dim3(128), 0, strm, vj);
+        hipLaunchKernelGGL(k_jac_contract, dim3((BCC_L * v0.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj);
+        const JacGroup* gl = J.groups + gfirst[j];
+        const dim3 ga((nAC + 127) / 128);
+        if (sens) hipLaunchKernelGGL(k_jac_sens, ga, dim3(128), 0, strm, vj, J.list, gl, ngroups[j], j, J.qJ, wrt, J.sens);
+        else hipLaunchKernelGGL(k_jac_rows, dim3(ga.x, ngroups[j]), dim3(128), 0, strm, vj, J.list, gl, j, J.qJ, wrt, cplxOut ? 1 : 0, hostJ ? J.rows : outJ);
+        if (!sens && hostJ) HIPCHK(hipMemcpyAsync(J.h_rows, J.rows, sizeof(double) * (size_t)n * nAC * width, hipMemcpyDeviceToHost, strm));
+        HIPCHK(hipStreamSynchronize(strm));
+        jac_records(ctx, 1, onj, st);
+        if (!sens && hostJ)
+            for (int q = 0; q < n; ++q)
+                std::memcpy(outJ + (size_t)(lists[j][q].p - row0) * nAC * width, J.h_rows + (size_t)q * nAC * width, sizeof(double) * nAC * width);
+    }
+    if (sens) hipLaunchKernelGGL(k_jac_sens_final, dim3((nAC + 127) / 128), dim3(128), 0, strm, J.sens, nAC);
+    HIPCHK(hipGetLastError());
+    st.smoother_sweeps = 10 * ctx->sweepsUsed[0] + sweeps;
+    put_back();
+    if (stOut) *stOut = st;
+    return 0;
+}
+
+static int jac_check(hmcmt_ctx* ctx, const void* m, int64_t row0, int64_t nrows, int32_t wrt, const void* out) {
+    if (!m || !out) { ctx->err = "Jacobian: null model or output pointer"; return HMCMT_EINVAL; }
+    if (wrt != HMCMT_JAC_WRT_SIGMA && wrt != HMCMT_JAC_WRT_LNSIGMA) { ctx->err = "Jacobian: wrt must be HMCMT_JAC_WRT_SIGMA or HMCMT_JAC_WRT_LNSIGMA"; return HMCMT_EINVAL; }
+    if (row0 < 0 || nrows < 0 || row0 > ctx->v.nData || nrows > ctx->v.nData - row0) { ctx->err = "Jacobian: row range outside [0, nData]"; return HMCMT_EINVAL; }
+    if (ctx->statsPending) { ctx->err = "Jacobian: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+int hmcmt_jacobian_device(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int32_t wrt, double* d_J, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = jac_check(ctx, d_m, row0, nrows, wrt, d_J)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = jac_alloc(ctx)) return rc;
+    return jac_run(ctx, d_m, row0, nrows, wrt, d_J, false, false, st);
+}
+
+int hmcmt_jacobian(hmcmt_ctx* ctx, const double* m, int64_t row0, int64_t nrows, int32_t wrt, double* J, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = jac_check(ctx, m, row0, nrows, wrt, J)) return rc;
+    for (int i = 0; i < ctx->v.nAC; ++i)
+        if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = jac_alloc(ctx)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->jac.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
+    return jac_run(ctx, ctx->jac.m, row0, nrows, wrt, J, true, false, st);
+}
+
+int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = jac_check(ctx, m, 0, ctx->v.nData, wrt, sens)) return rc;
+    for (int i = 0; i < ctx->v.nAC; ++i)
+        if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = jac_alloc(ctx)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->jac.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
+    int rc = jac_run(ctx, ctx->jac.m, 0, ctx->v.nData, wrt, nullptr, false, true, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(sens, ctx->jac.sens, sizeof(double) * ctx->v.nAC, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

@@ -594,4 +594,51 @@ HD void item_gradfinal(const View& v, int a) {
     v.grad[a] = exp(v.m[a]) * g;
 }
 
+// --- one entry of the explicit Jacobian by the adjoint route (compJacTMat.jl; J itself: compJacMat.jl:206-314):
+//     dZ/dsigma of cell (ky, kz) for system s, where v.Lam is the solution for ONE receiver's functional row as the
+//     source (unit coefficient) and srcB / colw / gL / gR are that solve's boundary arrays.  The terms of
+//     gradcell_freqs + gradfinal_sys + item_qterm for one system, kept complex: P-term, boundary term, Q-term (qJ:
+//     [S][ny] complex, the receiver layer's cells only).
+HD cplx jac_cell(const View& v, int s, int ky, int kz, const cplx* qJ) {
+    const double area = v.yLen[ky] * v.zLen[kz];
+    const cplx* L = v.Lam + (long)s * v.vstride;
+    cplx j;
+    if (s < v.nFreq) {
+        // -i w (1/4 area) sum over the 4 corner nodes e*lambda
+        const cplx* E = v.X + (long)s * v.vstride;
+        cplx sum = cplx{0, 0};
+        for (int dz = 0; dz < 2; ++dz)
+            for (int dy = 0; dy < 2; ++dy) {
+                long n = nidx(v, ky + dy, kz + dz);
+                sum += E[n] * L[n];
+            }
+        const double f = v.omega[s] * 0.25 * area;
+        j = cplx{f * sum.im, -(f * sum.re)};
+    } else {
+        cplx h00 = tm_field_sens(v, s, ky, kz), h10 = tm_field_sens(v, s, ky + 1, kz);
+        cplx h01 = tm_field_sens(v, s, ky, kz + 1), h11 = tm_field_sens(v, s, ky + 1, kz + 1);
+        cplx l00 = L[nidx(v, ky, kz)], l10 = L[nidx(v, ky + 1, kz)];
+        cplx l01 = L[nidx(v, ky, kz + 1)], l11 = L[nidx(v, ky + 1, kz + 1)];
+        const double iy2 = 1.0 / (v.yLen[ky] * v.yLen[ky]), iz2 = 1.0 / (v.zLen[kz] * v.zLen[kz]);
+        cplx sum = ((h10 - h00) * (l10 - l00) + (h11 - h01) * (l11 - l01)) * iy2 +
+                   ((h01 - h00) * (l01 - l00) + (h11 - h10) * (l11 - l10)) * iz2;
+        const double sg = v.sigma[(long)kz * v.ny + ky];
+        j = (0.5 * area / (sg * sg)) * sum;
+    }
+    const long o = (long)s * v.nz + kz;
+    j += v.gMn[o] * v.colw[(long)s * v.ny + ky];
+    if (ky == 0) j += v.gL[o];
+    if (ky == v.ny - 1) j += v.gR[o];
+    if (kz == v.zid) j += qJ[(long)s * v.ny + ky];
+    return j;
+}
+// --- the datum's row from the impedance's (item_resid's data kinds): 0 impedance dZ; 1 apparent resistivity
+//     (2/(w mu0)) Re(conj(Z) dZ); 2 phase in degrees (180/pi) Im(conj(Z) dZ)/|Z|^2 -- real for kinds 1, 2
+HD cplx jac_datum(int kind, cplx z, double omega, cplx dz) {
+    if (kind == 0) return dz;
+    const cplx c = conj(z) * dz;
+    if (kind == 1) return cplx{(2.0 / (omega * MU0)) * c.re, 0.0};
+    return cplx{(180.0 / 3.14159265358979323846) * c.im / cabs2(z), 0.0};
+}
+
 }  // namespace hmcmt

@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_jac.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -131,13 +131,17 @@ def load_library():
     lib.hmcmt_persist_pack.argtypes = [c_double_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), c_double_p]
     lib.hmcmt_persist_envelope.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int64, c_int64_p]
     lib.hmcmt_guard.argtypes = [vp, c_double_p]
+    lib.hmcmt_jacobian.argtypes = [vp, c_double_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, C.POINTER(Stats)]
+    lib.hmcmt_jacobian_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.POINTER(Stats)]
+    lib.hmcmt_sensitivity.argtypes = [vp, c_double_p, C.c_int32, c_double_p, C.POINTER(Stats)]
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
                  "hmcmt_grad", "hmcmt_forward", "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async",
                  "hmcmt_wait", "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_mass_info", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead",
                  "hmcmt_dims", "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond",
-                 "hmcmt_debug_fdm_fwd", "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_guard", "hmcmt_debug_hog", "hmcmt_next_cu_share", "hmcmt_persist_envelope", "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack"):
+                 "hmcmt_debug_fdm_fwd", "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_guard", "hmcmt_debug_hog", "hmcmt_next_cu_share", "hmcmt_persist_envelope", "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack",
+                 "hmcmt_jacobian", "hmcmt_jacobian_device", "hmcmt_sensitivity"):
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -148,7 +152,7 @@ PRODUCT_SYMBOLS = ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hm
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
-                   "hmcmt_guard", "hmcmt_next_cu_share",
+                   "hmcmt_guard", "hmcmt_next_cu_share", "hmcmt_jacobian", "hmcmt_jacobian_device", "hmcmt_sensitivity",
                    "hmcmt_comm_id", "hmcmt_comm_create", "hmcmt_allgather_samples", "hmcmt_comm_destroy", "hmcmt_comm_last_error"]
 # include/hmcmt_debug.h: instrumentation, introspection of the persistent kernel, test hooks
 DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead", "hmcmt_dims",
@@ -350,6 +354,52 @@ class HipContext:
         h = np.empty(nn * self.nFreq, dtype=np.complex128)
         self._check(self.lib.hmcmt_get_fields(self.h, int(adjoint), _dp(e), _dp(h)))
         return e.reshape(self.nFreq, nn).T.copy(), h.reshape(self.nFreq, nn).T.copy()
+
+    # -- explicit Jacobian (hmcmt_jacobian / hmcmt_sensitivity) ---------------------------------
+    JAC_WRT = {"sigma": 0, "lnsigma": 1}
+
+    def _model(self, m):
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        if m.shape != (self.nAC,):
+            raise ValueError("model vector has the wrong length")
+        return m
+
+    def _wrt(self, wrt):
+        if wrt not in self.JAC_WRT:
+            raise ValueError(f"wrt must be one of {sorted(self.JAC_WRT)}")
+        return self.JAC_WRT[wrt]
+
+    def jacobian(self, m, rows=None, wrt="sigma"):
+        """Rows of the data Jacobian J (data order) at model m: (nrows, nAC), complex for DataType Impedance, real for
+        Rho_Pha.  rows: None (all), a (start, stop) pair or a range with step 1.  wrt "sigma" (compJacMat's J) or "lnsigma"."""
+        m = self._model(m)
+        r0, r1 = (0, self.nData) if rows is None else ((rows.start, rows.stop) if isinstance(rows, range) else tuple(rows))
+        if isinstance(rows, range) and rows.step != 1:
+            raise ValueError("rows: a contiguous range")
+        if not 0 <= r0 <= r1 <= self.nData:
+            raise ValueError(f"rows ({r0}, {r1}): need 0 <= start <= stop <= nData = {self.nData}")
+        n = r1 - r0
+        width = 1 if self.args.real_data else 2
+        J = np.empty((n, self.nAC * width))
+        st = Stats()
+        self._check(self.lib.hmcmt_jacobian(self.h, _dp(m), r0, n, self._wrt(wrt), _dp(J), C.byref(st)))
+        self.jac_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return J if width == 1 else J.view(np.complex128)
+
+    def jacobian_device(self, d_m, row0, nrows, d_J, wrt="sigma"):
+        """Raw device pointers (ints): rows row0 .. row0+nrows-1 into d_J ([nrows][nAC], complex interleaved or real)."""
+        st = Stats()
+        self._check(self.lib.hmcmt_jacobian_device(self.h, d_m, int(row0), int(nrows), self._wrt(wrt), d_J, C.byref(st)))
+        self.jac_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+
+    def sensitivity(self, m, wrt="sigma"):
+        """sens[a] = sqrt(sum_k |dataW_k J_ka|^2) over all data (J not materialised)."""
+        m = self._model(m)
+        out = np.empty(self.nAC)
+        st = Stats()
+        self._check(self.lib.hmcmt_sensitivity(self.h, _dp(m), self._wrt(wrt), _dp(out), C.byref(st)))
+        self.jac_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return out
 
     # -- prior / leapfrog ---------------------------------------------------------------------
     def set_prior(self, mref, Wm, invM):

@@ -97,6 +97,18 @@ def compDataGradient(mtMesh, mtData, invParam, hmcprior, ctx: HipContext | None 
     return pred, misfit, grad
 
 
+def compJacMat(mtMesh, mtData, invParam, ctx: HipContext | None = None, wrt="sigma"):
+    """The data Jacobian at m = invParam.strModel (compJacMat.jl): (nData, nAC), d data / d sigma of the active cells
+    (wrt="lnsigma": d / d ln sigma); complex for DataType Impedance, real for Rho_Pha."""
+    ctx = ctx or get_context(mtMesh, mtData, invParam)
+    return ctx.jacobian(np.asarray(invParam.strModel, dtype=np.float64), wrt=wrt)
+
+
+def compJacTMat(mtMesh, mtData, invParam, ctx: HipContext | None = None, wrt="sigma"):
+    """J^T as the reference's compJacTMat.jl orients it: (nAC, nData)."""
+    return compJacMat(mtMesh, mtData, invParam, ctx=ctx, wrt=wrt).T
+
+
 def compDataMisfit(predData, invParam):
     res = invParam.dataW * (predData - invParam.obsData)
     return 0.5 * float(np.real(np.vdot(res, res)))

@@ -200,6 +200,29 @@ int hmcmt_leapfrog_device(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, i
  * the adjoint fields instead (interior = eVal of compJacTMatVec.jl:221, boundary 0). */
 int hmcmt_get_fields(hmcmt_ctx* ctx, int32_t adjoint, double* exTE, double* hxTM);
 
+/* Explicit data Jacobian (compJacMat / compJacTMat, MTSensitivity/compJacMat.jl, compJacTMat.jl) by the adjoint route: one
+ * adjoint solve per receiver and batch of systems (the gradient's solve with that receiver's functional row as its source),
+ * after a cold forward solve at m.  A Jacobian call leaves the context's evaluation state as it found it: warm-start fields
+ * and their extrapolation history, the memo, the sweep choice and queue tables, the evaluation count, hmcmt_get_stats.
+ *   wrt        HMCMT_JAC_WRT_SIGMA: d data / d sigma of the active cells (compJacMat's J); HMCMT_JAC_WRT_LNSIGMA: d / dm,
+ *              m = ln sigma (the sampler's parameter): columns times sigma
+ *   row0, nrows  rows row0 .. row0+nrows-1 of J in data order; only the receivers of those rows are solved, and only the
+ *              systems their data address
+ *   J          row-major [nrows][nAC]: complex (interleaved) for DataType Impedance, real for Rho_Pha (apparent resistivity
+ *              (2/(w mu0)) Re(conj(Z) dZ), phase in degrees (180/pi) Im(conj(Z) dZ)/|Z|^2).  Row-major J is column-major
+ *              J^T: Julia's compJacTMat layout
+ *   st         (may be NULL) the Jacobian's own solves: forward / adjoint iteration totals and maxima, max error estimate,
+ *              status, fallback solves
+ * HMCMT_EINVAL for a row range outside [0, nData], an unknown wrt, or a call between hmcmt_grad_device_async and hmcmt_wait;
+ * HMCMT_ENOCONV / HMCMT_EBREAKDOWN when a solve fails (the rows of that receiver's batch are not written).
+ * hmcmt_jacobian_device: d_m, d_J are device pointers on the context's GPU (complete on return).
+ * hmcmt_sensitivity: sens[nAC] = sqrt(sum_k |dataW_k J_ka|^2) over all data, without materialising J. */
+#define HMCMT_JAC_WRT_SIGMA   0
+#define HMCMT_JAC_WRT_LNSIGMA 1
+int hmcmt_jacobian(hmcmt_ctx* ctx, const double* m, int64_t row0, int64_t nrows, int32_t wrt, double* J, hmcmt_stats* st);
+int hmcmt_jacobian_device(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int32_t wrt, double* d_J, hmcmt_stats* st);
+int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens, hmcmt_stats* st);
+
 /* All-gather of the chains' sample blocks over RCCL (xGMI inside a node): one process per GPU, one communicator per
  * process.  Replaces parallelHMCSampler's collection of the workers' results (HMCSampler/parallelHMC.jl:23-45:
  * remotecall_fetch of hmcmodel / hmcstats / hmcdata per worker) for hosts that hold their chains in this library:

@@ -26,7 +26,7 @@ using SparseArrays
 using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
-export HipContext, hipContext, compDataGradient, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
+export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
        hipWait, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
@@ -167,6 +167,44 @@ function compDataGradient(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDat
     mtMesh.sigma = invParam.activeCell * exp.(m) + invParam.bgModel
     return (ctx.realData ? real.(pred) : pred), misfit[], grad
 end
+
+"""
+    compJacMat(mtMesh, mtData, invParam; wrt=:sigma) -> J (nData x nAC)
+
+The data Jacobian at invParam.strModel (MTSensitivity/compJacMat.jl): d data / d sigma of the active cells (wrt=:lnsigma:
+d / d ln sigma).  ComplexF64 for DataType Impedance, Float64 for Rho_Pha.  hmcmt_jacobian fills J^T column by column (its
+row-major [nData][nAC] is Julia's column-major [nAC, nData]).
+"""
+compJacMat(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel; wrt::Symbol=:sigma) =
+    permutedims(compJacTMat(mtMesh, mtData, invParam; wrt=wrt))
+
+"""
+    compJacTMat(mtMesh, mtData, invParam; wrt=:sigma) -> J^T (nAC x nData), as MTSensitivity/compJacTMat.jl orients it.
+"""
+function compJacTMat(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel; wrt::Symbol=:sigma)
+    ctx = getctx(mtMesh, mtData, invParam)
+    JT = ctx.realData ? Matrix{Float64}(undef, ctx.nAC, ctx.nData) : Matrix{ComplexF64}(undef, ctx.nAC, ctx.nData)
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_jacobian, libhmcmt), Cint,
+               (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int32, Ptr{Cvoid}, Ref{HmcmtStats}),
+               ctx.ptr, invParam.strModel, 0, ctx.nData, jacWrt(wrt), JT, st)
+    checkerr(ctx.ptr, rc)
+    return JT
+end
+
+"""
+    hipSensitivity(mtMesh, mtData, invParam; wrt=:sigma) -> sens (nAC): sqrt(sum_k |dataW_k J_ka|^2), J not formed
+"""
+function hipSensitivity(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel; wrt::Symbol=:sigma)
+    ctx = getctx(mtMesh, mtData, invParam)
+    sens = Vector{Float64}(undef, ctx.nAC)
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_sensitivity, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{HmcmtStats}),
+               ctx.ptr, invParam.strModel, jacWrt(wrt), sens, st)
+    checkerr(ctx.ptr, rc)
+    return sens
+end
+jacWrt(wrt::Symbol) = wrt === :sigma ? Int32(0) : wrt === :lnsigma ? Int32(1) : throw(ArgumentError("wrt: :sigma or :lnsigma"))
 
 """
     hipForward(mtMesh, mtData, invParam) -> (predData, dataMisfit)
