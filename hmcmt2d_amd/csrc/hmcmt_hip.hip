@@ -1963,7 +1963,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     HIPCHK(hipEventCreateWithFlags(&ctx->evExtA, evDev));
     const HostProblem& h = ctx->hp;
     View& v = ctx->v;
-    v.ny = h.ny; v.nz = h.nz; v.NYP = h.NYP; v.NZP = h.NZP; v.nFreq = h.nFreq; v.S = h.S; v.nRx = h.nRx;
+    v.ny = h.ny; v.nz = h.nz; v.NYP = h.NYP; v.NZP = h.NZP; v.nFreq = h.nFreq; v.S = h.S; v.nRx = h.nFun; v.nTip = h.nTip;
     v.nData = h.nData; v.nAC = h.nAC; v.nCell = h.nCell; v.zid = h.zid; v.vstride = (long)h.NZP * h.NYP;
     v.dbg = 0; v.ticks = nullptr;
     // (the lateral mean of the FDM background is the geometric mean of sigma for both modes.  Round 3's experiment HMCMT_BGMEAN --
@@ -1977,6 +1977,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     UP(rxIdn, h.rxIdn) UP(rxDy1, h.rxDy1) UP(rxDy2, h.rxDy2) UP(rxKL, h.rxKL) UP(rxKR, h.rxKR) UP(rxWL, h.rxWL) UP(rxWR, h.rxWR)
     UP(predSys, h.predSys) UP(predRx, h.predRx) UP(datSys, h.datSys) UP(datRx, h.datRx) UP(predKind, h.predKind) UP(datKind, h.datKind)
     UP(obs, h.obs) UP(dataW, h.dataW) UP(srStart, h.srStart) UP(srList, h.srList)
+    if (h.nTip) { UP(rxCL, h.rxCL) UP(rxCR, h.rxCR) UP(rxVL, h.rxVL) UP(rxVR, h.rxVR) }
 #undef UP
     {
         // fragment-order copies of V and V' (see k_transform)
@@ -2029,7 +2030,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     DA(v.cY, 2 * VS) DA(v.cZ, 2 * VS) DA(v.dK, 2 * VS) DA(v.dM, 2 * VS)
     DA(v.mzq, 2 * h.NZP) DA(v.dgz, 2 * h.NZP) DA(v.ofz, 2 * h.NZP) DA(v.mzs, 2 * h.NZP)
     DA(v.invp, S * VS) DA(v.X, S * VS) DA(v.Lam, S * VS) DA(v.R, S * VS)
-    DA(v.Zrx, S * h.nRx) DA(v.rxN0, S * h.nRx) DA(v.rxD, S * h.nRx * 11) DA(v.rxCoef, S * h.nRx)
+    DA(v.Zrx, S * h.nFun) DA(v.rxN0, S * h.nFun) DA(v.rxD, S * h.nFun * 11) DA(v.rxCoef, S * h.nFun)
     DA(v.pred, h.nData) DA(v.vbar, h.nData) DA(v.misfitPart, h.nData)
     DA(v.srcB, S * 4) DA(v.wL, S * h.nz) DA(v.wR, S * h.nz) DA(v.colw, S * h.ny)
     DA(v.gL, S * h.nz) DA(v.gR, S * h.nz) DA(v.gMn, S * h.nz) DA(v.dBC, S * 2 * (size_t)h.nz * h.nz) DA(v.bcsL, S * h.nz) DA(v.bcsR, S * h.nz) DA(v.bcsB, S)
@@ -3382,7 +3383,7 @@ static int jac_run(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrow
     hmcmt_ctx::Jac& J = ctx->jac;
     const View& v0 = ctx->v;
     const int S = v0.S, nAC = v0.nAC, nRx = v0.nRx;
-    const bool cplxOut = ctx->hp.datKind.empty() || ctx->hp.datKind[0] == 0;    // (the two data families cannot be mixed)
+    const bool cplxOut = !ctx->hp.rhoPhase;             // (the two data families cannot be mixed; TZY rows are complex too)
     const int width = cplxOut ? 2 : 1;
     // the batches: the receivers of the rows, in receiver order; per batch the data (in data order) and the systems they need
     std::vector<std::vector<JacEntry>> lists(nRx);

@@ -61,16 +61,24 @@ struct View {
     const int* rxKR;
     const double* rxWL;
     const double* rxWR;
-    cplx* Zrx;                     // [S][nRx]
+    // (nRx counts the receiver FUNCTIONALS: with tipper data (nTip = number of receivers) functional r < nRx - nTip is receiver r's
+    //  impedance and functional nRx - nTip + r its tipper T = Hz/Hy, TE systems only; the tables above repeat for the latter)
+    cplx* Zrx;                     // [S][nRx] Z, or T for a tipper functional
     int* rxN0;                     // [S][nRx] derivative window start
     cplx* rxD;                     // [S][nRx][11]: d0[4], d1[4], dq[3]
     cplx* rxCoef;                  // [S][nRx] sum of conj(W^T W r) over the data of (s, rx)
+    int nTip = 0;                  // number of tipper functionals (0: no tipper data, the tables below are not read)
+    const int* rxCL = nullptr;     // [nRx] linRxMap2 (linearInterp on the cell centres): cells of Hz ...
+    const int* rxCR = nullptr;
+    const double* rxVL = nullptr;  // ... and their weights
+    const double* rxVR = nullptr;
     // data
     const int* predSys;            // [nData] system of the p-th masked entry of the full table
     const int* predRx;             // [nData] receiver of it
     const int* datSys;             // [nData] system addressed by (freqID, dtID) of datum p
     const int* datRx;              // [nData] rxID-1
-    const int* predKind;           // [nData] what the p-th masked table entry is: 0 impedance, 1 apparent resistivity, 2 phase (degrees)
+    const int* predKind;           // [nData] what the p-th masked table entry is: 0 impedance, 1 apparent resistivity, 2 phase (degrees),
+                                   //   3 tipper T, 4 Re T, 5 Im T
     const int* datKind;            // [nData] the same for the component dtID of datum p addresses
     const cplx* obs;               // [nData]
     const double* dataW;           // [nData]
@@ -310,8 +318,27 @@ HD void item_rhs(const View& v, int s, int iy, int iz) {
     v.R[o] = -acc;
 }
 
+// --- tipper and its derivative at one tipper functional of one system (zero for TM systems, like an absent polarisation)
+HD void item_rx_tipper(const View& v, int s, int r, bool wantDeriv) {
+    const long k = (long)s * v.nRx + r;
+    if (!v.sysOn[s] || s >= v.nFreq) {
+        v.Zrx[k] = cplx{0, 0};
+        if (wantDeriv) {
+            v.rxN0[k] = 0;
+            for (int i = 0; i < 11; ++i) v.rxD[k * 11 + i] = cplx{0, 0};
+        }
+        return;
+    }
+    const cplx* F0 = v.X + (long)s * v.vstride + nidx(v, 0, v.zid);
+    cplx* D = wantDeriv ? v.rxD + k * 11 : nullptr;
+    v.Zrx[k] = rx_tipper_deriv(v.omega[s], v.ny, F0, F0 + v.NYP, v.yLen, v.sigma + (long)v.zid * v.ny, v.zLen[v.zid],
+                               v.rxKL[r], v.rxKR[r], v.rxWL[r], v.rxWR[r], v.rxCL[r], v.rxCR[r], v.rxVL[r], v.rxVR[r],
+                               &v.rxN0[k], D);
+}
+
 // --- impedance and its derivative at one receiver of one system
 HD void item_rx(const View& v, int s, int r, bool wantDeriv) {
+    if (r >= v.nRx - v.nTip) { item_rx_tipper(v, s, r, wantDeriv); return; }
     if (!v.sysOn[s]) {                                    // polarisation absent from the data set
         v.Zrx[(long)s * v.nRx + r] = cplx{0, 0};
         if (wantDeriv) {
@@ -346,12 +373,18 @@ HD void item_resid(const View& v, int p) {
     cplx val = z;
     if (kind == 1) val = cplx{cabs2(z) / (v.omega[sp] * MU0), 0.0};
     else if (kind == 2) val = cplx{atan2(z.im, z.re) * (180.0 / 3.14159265358979323846), 0.0};
+    else if (kind == 4) val = cplx{z.re, 0.0};
+    else if (kind == 5) val = cplx{z.im, 0.0};
     v.pred[p] = val;
     const cplx res = v.dataW[p] * (val - v.obs[p]);
     v.misfitPart[p] = 0.5 * cabs2(res);
     const cplx wr = v.dataW[p] * res;
     const int dk = v.datKind[p];
     if (dk == 0) { v.vbar[p] = conj(wr); return; }
+    // tipper (z is T): T conj(wr), Re T wr.re, Im T -i wr.re -- Re(vbar dT) is the datum's term of the gradient
+    if (dk == 3) { v.vbar[p] = conj(wr); return; }
+    if (dk == 4) { v.vbar[p] = cplx{wr.re, 0.0}; return; }
+    if (dk == 5) { v.vbar[p] = cplx{0.0, -wr.re}; return; }
     const int sd = v.datSys[p];
     const cplx zs = v.Zrx[(long)sd * v.nRx + v.datRx[p]];
     if (dk == 1) v.vbar[p] = (wr.re * 2.0 / (v.omega[sd] * MU0)) * conj(zs);
@@ -633,9 +666,12 @@ HD cplx jac_cell(const View& v, int s, int ky, int kz, const cplx* qJ) {
     return j;
 }
 // --- the datum's row from the impedance's (item_resid's data kinds): 0 impedance dZ; 1 apparent resistivity
-//     (2/(w mu0)) Re(conj(Z) dZ); 2 phase in degrees (180/pi) Im(conj(Z) dZ)/|Z|^2 -- real for kinds 1, 2
+//     (2/(w mu0)) Re(conj(Z) dZ); 2 phase in degrees (180/pi) Im(conj(Z) dZ)/|Z|^2 -- real for kinds 1, 2.  For a tipper
+//     functional dz is dT: 3 TZY dT, 4 Re dT, 5 Im dT
 HD cplx jac_datum(int kind, cplx z, double omega, cplx dz) {
-    if (kind == 0) return dz;
+    if (kind == 0 || kind == 3) return dz;
+    if (kind == 4) return cplx{dz.re, 0.0};
+    if (kind == 5) return cplx{dz.im, 0.0};
     const cplx c = conj(z) * dz;
     if (kind == 1) return cplx{(2.0 / (omega * MU0)) * c.re, 0.0};
     return cplx{(180.0 / 3.14159265358979323846) * c.im / cabs2(z), 0.0};

@@ -678,4 +678,67 @@ HD void rx_impedance_deriv(bool tm, double omega, int ny, const cplx* F0, const 
     }
 }
 
+// Tipper T = Hzr / Hyr of one receiver (TE only) and, with D non-null, its derivative as the 11-entry record of
+// rx_impedance_deriv, D = d0[4], d1[4], dq[3] (dataFuncSens.jl:44-112):
+//   Hzr = linRxMap2^T (Bz0 / mu0), Bz0 = ddx(ny) F0 ./ dy / (i w) on the cells of the receiver row -- cells (cL, cR), weights
+//         (vL, vR) from linearInterp(rxY, yCen) (sensUtils.jl:46-48);
+//   Hyr = linRxMap^T Hy0 with the normalised weights (kL, kR, wL, wR) of rx_impedance_deriv -- the same Hy;
+//   dT = dHzr / Hyr - (Hzr / Hyr^2) dHyr,  dT/dsig = -(Hzr / Hyr^2) dHyr/dsig  (:111-112).
+// Windows as rx_impedance_deriv's: nodes n0 = min(clampk(kL), clampk(kR)) - 1 ... n0+3, cells c0 = n0 ... c0+2.  Hz of cell c
+// reads nodes c, c+1; the host checks at create that cL, cR+1 lie in the node window (HostProblem::build_tipper_tables; slot_add
+// would drop, not misplace, a term outside it).  Hz does not depend on sigma, so dq is Hy's alone and stays in the cell window.
+HD cplx rx_tipper_deriv(double omega, int ny, const cplx* F0, const cplx* F1, const double* dy, const double* sig1, double dz1,
+                        int kL, int kR, double wL, double wR, int cL, int cR, double vL, double vR,
+                        int* n0_out, cplx* D) {
+    const int kk[2] = {clampk(kL, ny), clampk(kR, ny)}, cc[2] = {cL, cR};
+    const double ww[2] = {wL, wR}, vv[2] = {vL, vR};
+    const int n0 = (kk[0] < kk[1] ? kk[0] : kk[1]) - 1;
+    const cplx iw = cplx{0.0, omega};
+    cplx hz = cplx{0, 0}, hy = cplx{0, 0};
+    HMCMT_UNROLL
+    for (int t = 0; t < 2; ++t) {
+        hz += vv[t] * ((F0[cc[t] + 1] - F0[cc[t]]) / dy[cc[t]] / iw / MU0);
+        hy += ww[t] * te_Hy0(kk[t], omega, F0, F1, dy, sig1, dz1);
+    }
+    const cplx T = hz / hy;
+    if (!D) return T;
+    *n0_out = n0;
+    cplx *d0 = D, *d1 = D + 4, *dq = D + 8;
+    // dHz/dF0 in h0[], dHy/dF0, dF1, dsig in a0[], a1[], aq[] (the TE branch of rx_impedance_deriv)
+    cplx h0[4], a0[4], a1[4], aq[3];
+    HMCMT_UNROLL
+    for (int i = 0; i < 4; ++i) { h0[i] = cplx{0, 0}; a0[i] = cplx{0, 0}; a1[i] = cplx{0, 0}; }
+    HMCMT_UNROLL
+    for (int i = 0; i < 3; ++i) aq[i] = cplx{0, 0};
+    HMCMT_UNROLL
+    for (int t = 0; t < 2; ++t) {
+        const cplx b = vv[t] / (dy[cc[t]] * (iw * MU0));
+        slot_add<4>(h0, cc[t] - n0, -b);
+        slot_add<4>(h0, cc[t] + 1 - n0, b);
+        const int k = kk[t];
+        const double w = ww[t];
+        const int o = k - n0;
+        const double avl = 0.5 * dy[k - 1] + 0.5 * dy[k];
+        const double hzl = 0.5 * dz1;
+        const cplx g = 1.0 / (dz1 * (iw * MU0));
+        const double sv = (0.5 * (sig1[k - 1] * dy[k - 1]) + 0.5 * (sig1[k] * dy[k])) / avl;
+        const cplx ak = 1.0 / (dy[k] * (iw * MU0)), akm = 1.0 / (dy[k - 1] * (iw * MU0));
+        slot_add<4>(a0, o, w * (g + (sv * hzl) * cplx{0.75, 0} + (hzl / avl) * 0.75 * (ak + akm)));
+        slot_add<4>(a1, o, w * (-g + (sv * hzl) * cplx{0.25, 0} + (hzl / avl) * 0.25 * (ak + akm)));
+        slot_add<4>(a0, o + 1, w * (-(hzl / avl) * 0.75 * ak));
+        slot_add<4>(a1, o + 1, w * (-(hzl / avl) * 0.25 * ak));
+        slot_add<4>(a0, o - 1, w * (-(hzl / avl) * 0.75 * akm));
+        slot_add<4>(a1, o - 1, w * (-(hzl / avl) * 0.25 * akm));
+        const cplx ExQ = 0.75 * F0[k] + 0.25 * F1[k];
+        slot_add<3>(aq, o - 1, w * (hzl * (0.5 * dy[k - 1] / avl)) * ExQ);
+        slot_add<3>(aq, o, w * (hzl * (0.5 * dy[k] / avl)) * ExQ);
+    }
+    const cplx ih = 1.0 / hy, c2 = hz / (hy * hy);
+    HMCMT_UNROLL
+    for (int i = 0; i < 4; ++i) { d0[i] = ih * h0[i] - c2 * a0[i]; d1[i] = -(c2 * a1[i]); }
+    HMCMT_UNROLL
+    for (int i = 0; i < 3; ++i) dq[i] = -(c2 * aq[i]);
+    return T;
+}
+
 }  // namespace hmcmt

@@ -151,7 +151,7 @@ def readMT2DData(datafile: str):
                     obs[k] = float(t[3]); err[k] = float(t[4])
     if rxLoc is None or freqs is None or obs is None:
         raise ValueError(f"{datafile}: incomplete data file")
-    compTE = any("XY" in c for c in dataComp)
+    compTE = any("XY" in c or "TZY" in c for c in dataComp)     # (the tipper is a TE quantity)
     compTM = any("YX" in c for c in dataComp)
     nDt, nr, nf = len(dataComp), rxLoc.shape[0], len(freqs)
     dataID = np.zeros((nf, nr, nDt), dtype=bool)          # linear index = dt + nDt*(rx + nr*freq)

@@ -22,21 +22,27 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
-COMPONENT_CODES = {"ZXY": 1, "ZYX": 2, "RhoXY": 3, "PhsXY": 4, "RhoYX": 5, "PhsYX": 6}
+COMPONENT_CODES = {"ZXY": 1, "ZYX": 2, "RhoXY": 3, "PhsXY": 4, "RhoYX": 5, "PhsYX": 6,
+                   "TZY": 7, "RealTZY": 8, "ImagTZY": 9}
+TIPPER_CODES = (7, 8, 9)
+_IMPEDANCE_FAMILY = (1, 2, 7)
 
 
 def comp_modes(dataComp, dataType="Impedance"):
-    """Component codes of include/hmcmt.h: ZXY 1, ZYX 2 (DataType Impedance); RhoXY 3, PhsXY 4, RhoYX 5, PhsYX 6
-    (DataType Rho_Pha: the names compJacTMatVec.jl:106-113 looks for).  `log10Rho*` is refused: the reference's
-    forward returns the linear apparent resistivity for it while its sensitivity branch switches to log10
+    """Component codes of include/hmcmt.h: ZXY 1, ZYX 2, TZY 7 (DataType Impedance); RhoXY 3, PhsXY 4, RhoYX 5, PhsYX 6,
+    RealTZY 8, ImagTZY 9 (DataType Rho_Pha: the names compJacTMatVec.jl:104-131 looks for).  The tipper components
+    (T = Hz/Hy of the TE mode: complex T, or Re T and Im T) come after all the others.  `log10Rho*` is refused: the
+    reference's forward returns the linear apparent resistivity for it while its sensitivity branch switches to log10
     (mt2DTE.jl:253 vs dataFuncSens.jl:154-160)."""
     out = []
     for c in dataComp:
         if c not in COMPONENT_CODES:
             raise ValueError(f"unsupported data component {c!r} (supported: {', '.join(COMPONENT_CODES)})")
         code = COMPONENT_CODES[c]
-        if (code <= 2) != ("Impedance" in dataType):
+        if (code in _IMPEDANCE_FAMILY) != ("Impedance" in dataType):
             raise ValueError(f"data component {c!r} does not belong to DataType {dataType!r}")
+        if out and out[-1] in TIPPER_CODES and code not in TIPPER_CODES:
+            raise ValueError(f"data component {c!r} is listed after a tipper component (the tipper components come last)")
         out.append(code)
     return np.asarray(out, dtype=np.int64)
 

@@ -66,6 +66,26 @@ def make_rhophase_layout(freqs, rx_y, rx_z=0.0) -> MTData:
                   np.ones(4 * nR * nF, dtype=bool), True, True)
 
 
+def make_tipper_layout(freqs, rx_y, family="Impedance", with_impedance=True, rx_z=0.0) -> MTData:
+    """A survey with the tipper T = Hz/Hy: family "Impedance" lists ZXY ZYX (with_impedance) then TZY (complex T);
+    family "Rho_Pha" lists RhoXY PhsXY RhoYX PhsYX (with_impedance) then RealTZY ImagTZY (Re T, Im T).  Every datum
+    present, sorted (freq, rx, comp)."""
+    if family == "Impedance":
+        comps = (["ZXY", "ZYX"] if with_impedance else []) + ["TZY"]
+    elif family in ("Rho_Pha", "Rho_Phs"):
+        comps = (["RhoXY", "PhsXY", "RhoYX", "PhsYX"] if with_impedance else []) + ["RealTZY", "ImagTZY"]
+    else:
+        raise ValueError(f"unknown family {family!r} (Impedance or Rho_Pha)")
+    freqs = np.asarray(freqs, dtype=np.float64)
+    rx_y = np.asarray(rx_y, dtype=np.float64)
+    nF, nR, nC = len(freqs), len(rx_y), len(comps)
+    rxLoc = np.stack([rx_y, np.full(nR, rx_z)], axis=1)
+    f, r, d = np.meshgrid(np.arange(1, nF + 1), np.arange(1, nR + 1), np.arange(1, nC + 1), indexing="ij")
+    return MTData(rxLoc, freqs, "Impedance" if family == "Impedance" else "Rho_Pha", comps, r.reshape(-1).astype(np.int64),
+                  f.reshape(-1).astype(np.int64), d.reshape(-1).astype(np.int64),
+                  np.ones(nC * nR * nF, dtype=bool), True, with_impedance)
+
+
 def log_freqs(n, fmax=100.0, fmin=0.01):
     return np.logspace(np.log10(fmax), np.log10(fmin), n)
 

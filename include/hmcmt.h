@@ -92,7 +92,11 @@ void hmcmt_default_options(hmcmt_options* opts);
  *   compMode[nComp]   component code per entry of MTData.dataComp: 1 ZXY, 2 ZYX (DataType Impedance, complex data);
  *                     3 RhoXY, 4 PhsXY, 5 RhoYX, 6 PhsYX (DataType Rho_Pha: apparent resistivity |Z|^2/(w mu0) in Ohm-m and
  *                     phase in degrees, mt2DTE.jl:253-255 -- real data: obs / pred keep the complex layout with zero
- *                     imaginary parts).  The two families cannot be mixed
+ *                     imaginary parts).  The two families cannot be mixed.  The tipper T = Hz/Hy of the TE mode
+ *                     (dataFuncSens.jl:44-112): 7 TZY (Impedance family, complex T), 8 RealTZY / 9 ImagTZY (Rho_Pha family,
+ *                     Re T / Im T), listed after every other component; the response table per (freq, rx) is then the
+ *                     impedance / rho-phase entries followed by the tipper entries.  A tipper-only set solves TE systems only.
+ *                     HMCMT_EINVAL: a code outside 1..9, a tipper component of the other family or before a non-tipper one
  *   freqID/rxID/dtID[nData]  1-based, MTData fields; dataID[nComp*nRx*nFreq] mask, dt fastest
  *   obs[nData] complex, dataW[nData] = diag of InvDataModel.dataW
  *   activeIdx[nAC]    1-based cell id of each active cell (= activeCell.rowval), bgModel[ny*nz]

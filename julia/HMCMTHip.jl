@@ -64,7 +64,9 @@ mutable struct HipContext
 end
 
 # component codes of include/hmcmt.h (the same table as hmcmt2d_amd/marshal.py COMPONENT_CODES; tests/test_abi.py compares them)
-const COMPONENT_CODES = Dict("ZXY" => 1, "ZYX" => 2, "RhoXY" => 3, "PhsXY" => 4, "RhoYX" => 5, "PhsYX" => 6)
+# (7 TZY, 8 RealTZY, 9 ImagTZY: the tipper T = Hz/Hy, listed after the other components)
+const COMPONENT_CODES = Dict("ZXY" => 1, "ZYX" => 2, "RhoXY" => 3, "PhsXY" => 4, "RhoYX" => 5, "PhsYX" => 6,
+                             "TZY" => 7, "RealTZY" => 8, "ImagTZY" => 9)
 
 function compModes(dataComp, dataType::AbstractString)
     isimp = occursin("Impedance", dataType)
@@ -74,7 +76,9 @@ function compModes(dataComp, dataType::AbstractString)
     for c in dataComp
         haskey(COMPONENT_CODES, c) || error("unsupported data component $c (log10Rho*: the reference's forward and sensitivity disagree on it)")
         code = COMPONENT_CODES[c]
-        (code <= 2) == isimp || error("data component $c does not belong to DataType $dataType")
+        (code <= 2 || code == 7) == isimp || error("data component $c does not belong to DataType $dataType")
+        (!isempty(out) && out[end] >= 7 && code < 7) &&
+            error("data component $c is listed after a tipper component (the tipper components come last)")
         push!(out, code)
     end
     return out
