@@ -61,6 +61,14 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_mass.h"
 #include "kernels_jac.h"
 
+// an instantiation of the persistent solve kernel (g_psKernels, launch_persist): k_cocg_persist<cw, sw, mw, cs, nyk, st> (two
+// halves) or k_cocg_persist4<cw, sw, 32, nyk, 4, st> (four strips), strips x cw threads per workgroup
+struct PsKernel {
+    int strips, cw, sw, mw, cs, nyk;
+    bool st;
+    const void* fn;
+};
+
 }  // namespace
 
 // ----------------------------------------------------------------------------------------------
@@ -105,7 +113,7 @@ struct hmcmt_ctx {
     cplx* d_fieldsOut = nullptr;
     // pinned host staging
     int* h_nactive = nullptr;
-    int* h_stall = nullptr;               // pinned, mapped: Solver::stallHost
+    int* h_stall = nullptr;               // pinned, mapped: Solver::stallHost (HW_WORDS words, host_word)
     int* h_prog = nullptr;                // pinned, mapped: Solver::progHost
     double* h_rec = nullptr;              // packed per-solve records: [2][S] iters, [2][S] status (int), [2][S] err (double)
     double* h_stage = nullptr;            // m / grad / pred / misfit staging
@@ -195,7 +203,7 @@ struct hmcmt_ctx {
     bool persistOn = true;                // HMCMT_PERSIST=0: the launch-per-phase loop only
     bool persistFillsShare = false;
     int persistG = 0, persistSlots = 0, persistCW = 0;   // workgroups per system, system slots per XCD, threads / 2 (0: the problem does not fit the kernel)
-    size_t persistLds = 0;
+    size_t persistLds = 0;                // LDS bytes of psKern's kernels
     unsigned* d_psync = nullptr;          // [8 * slots][32] barrier words | exit counter | fail word
     size_t psyncBytes = 0;
     u4v* d_prec = nullptr;                // [S][MAXNB][2][8] records of the kernel's reductions (tagged, never cleared)
@@ -204,11 +212,8 @@ struct hmcmt_ctx {
     long long persistSolves = 0, persistFallbacks = 0, persistTimeouts = 0;
     int shareIdx = 0, shareCnt = 1;       // this context's share of every XCD's CUs (hmcmt_next_cu_share): index, 1 / 2 / 4 parts
     unsigned shareMask = 0xF;             // ... as quarters
-    int persistWidthK = 0;                // 112 / 208 / 416: the mesh's padded row width has a width-specialised persistent kernel (launch_persist)
     int persistCS = 1, persistGZ = 0;     // column parts of a row block (2: wide meshes, kernels_persist.h), row blocks per system
-    int persistStrips = 2;                // 4: the four-strip kernel (kernels_persist4.h: 4 x persistCW threads, four waves per SIMD); HMCMT_PERSIST_STRIPS=2 keeps k_cocg_persist
-    int persistRC = 8;                    // ... rows per chunk of its slab sweeps
-    size_t persistLds4 = 0;               // ... its LDS bytes
+    const PsKernel* psKern[2] = {};       // the instantiations launch_persist runs for one / two sweeps (g_psKernels; persist_setup)
     // the order in which the queues of the persistent kernel take the systems (PsLaunch::order; persist_balance): per solve kind
     int* d_psOrder = nullptr;             // [2][S]
     int* h_psOrder = nullptr;             // pinned staging of the same
@@ -645,6 +650,38 @@ bool persist_alone(const hmcmt_ctx* ctx) {
 bool persist_ok(const hmcmt_ctx* ctx) {
     return ctx->persistOn && ctx->persistCW > 0 && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && persist_alone(ctx);
 }
+// a word of the mapped host block (HostWord)
+volatile int& host_word(const hmcmt_ctx* ctx, HostWord w) { return reinterpret_cast<volatile int*>(ctx->h_stall)[w]; }
+
+// Every instantiation of the persistent solve kernel: persist_setup raises their LDS limit and picks the pair (one / two sweeps)
+// of this context (ps_pick), launch_persist launches it.  HMCMT_STAMPS=persist: the phase stamps compiled in, on the 512-thread
+// shapes the phase tables are made on; nyk: width-specialised (PS_WIDTHS: the row width is a compile-time constant).
+template <int CW, int SW, int MW, int CS, int NYK = 0, bool ST = false>
+PsKernel ps2() { return {2, CW, SW, MW, CS, NYK, ST, reinterpret_cast<const void*>(k_cocg_persist<CW, SW, MW, CS, NYK, ST>)}; }
+template <int CW, int SW, int NYK = 0, bool ST = false>
+PsKernel ps4() { return {4, CW, SW, 32, 1, NYK, ST, reinterpret_cast<const void*>(k_cocg_persist4<CW, SW, 32, NYK, 4, ST>)}; }
+const PsKernel g_psKernels[] = {
+    ps2<256, 1, 32, 1, 208, true>(), ps2<256, 2, 32, 1, 208, true>(), ps2<256, 1, 16, 2, 416, true>(), ps2<256, 2, 16, 2, 416, true>(),
+    ps2<256, 1, 32, 1, 0, true>(),   ps2<256, 2, 32, 1, 0, true>(),   ps2<256, 1, 16, 2, 0, true>(),   ps2<256, 2, 16, 2, 0, true>(),
+    ps2<256, 1, 32, 1, 208>(), ps2<256, 2, 32, 1, 208>(),
+    ps2<128, 1, 32, 1, 112>(), ps2<128, 2, 32, 1, 112>(),      // (the reference's example meshes: 96 cells)
+    ps2<256, 1, 16, 2, 416>(), ps2<256, 2, 16, 2, 416>(),
+    ps2<256, 1, 32, 1>(), ps2<256, 2, 32, 1>(), ps2<128, 1, 32, 1>(), ps2<128, 2, 32, 1>(), ps2<64, 1, 32, 1>(), ps2<64, 2, 32, 1>(),
+    ps2<256, 1, 16, 1>(), ps2<256, 2, 16, 1>(), ps2<128, 1, 16, 1>(), ps2<128, 2, 16, 1>(), ps2<64, 1, 16, 1>(), ps2<64, 2, 16, 1>(),
+    ps2<256, 1, 16, 2>(), ps2<256, 2, 16, 2>(), ps2<128, 1, 16, 2>(), ps2<128, 2, 16, 2>(), ps2<64, 1, 16, 2>(), ps2<64, 2, 16, 2>(),
+    ps4<256, 1, 208>(), ps4<256, 2, 208>(), ps4<256, 1, 208, true>(), ps4<256, 2, 208, true>(),
+    ps4<256, 1>(), ps4<256, 2>(), ps4<128, 1>(), ps4<128, 2>(), ps4<64, 1>(), ps4<64, 2>()};
+// The entry for a shape (strips, cw, mw, cs) of the kernel, the mesh's padded row width wk (0: generic only) and sw sweeps: the
+// most specialised entry the table has -- with stamps where asked for, then width-specialised, then generic.  That is: stamps on
+// cw = 256 with (cs, mw) = (1, 32) or (2, 16), and at four strips with width 208; width-specialised for (wk, cw, cs, mw) = (208,
+// 256, 1, 32), (112, 128, 1, 32), (416, 256, 2, 16), at four strips for (208, 256); null if the table has no entry at all.
+const PsKernel* ps_pick(int strips, int cw, int mw, int cs, int wk, bool stamps, int sw) {
+    for (const bool st : {stamps, false})
+        for (const int nyk : {wk, 0})
+            for (const PsKernel& e : g_psKernels)
+                if (e.strips == strips && e.cw == cw && e.sw == sw && e.mw == mw && e.cs == cs && e.nyk == nyk && e.st == st) return &e;
+    return nullptr;
+}
 // one launch = the whole solve (or, precondOnly, one application of the preconditioner to k.r -> zout)
 int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, int kind = 0, hmcmt_ctx::PsStart start = hmcmt_ctx::PsStart{}) {
     Solver& k = ctx->sv;
@@ -664,7 +701,7 @@ int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, in
     c.active = k.active; c.iters = k.iters; c.status = k.status; c.nactive = k.nactive; c.nactHost = k.nactHost;
     c.failHost = k.failHost; c.stallHost = k.stallHost; c.progHost = k.progHost; c.errEst = k.errEst; c.ticks = k.ticks;
     c.sync = ctx->d_psync; c.exitCnt = ctx->d_psync + 32 * groups; c.fail = reinterpret_cast<int*>(ctx->d_psync + 32 * groups + 8);
-    c.placeHost = k.stallHost + 2;
+    c.placeHost = k.stallHost + HW_PLACE;
     c.Vb = ctx->d_Vb; c.Vtb = ctx->d_Vtb;
     c.pubR = k.t2_32; c.pubZ = k.zs32; c.pubP = k.p32a;
     c.yhat = k.y32; c.yhat2 = ctx->d_yhat2; c.ysol = k.t32; c.tbuf = k.z4_32;
@@ -695,60 +732,20 @@ int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, in
     a.placedCnt = precondOnly ? nullptr : ctx->d_psync + 32 * groups + 5; a.nGroups = groups;
     if (start.begin) *(volatile int*)ctx->h_nactive = ctx->nSysOn;      // (mapped: "not all done yet" until the kernel's last converged system says otherwise)
     if (ctx->d_pstamps) HIPCHK(hipMemsetAsync(ctx->d_pstamps, 0, sizeof(long long) * 16 * 256, ctx->stream));
-    const dim3 grid(groups * ctx->persistG);
-    if (ctx->persistStrips == 4) {
-        // the four-strip kernel (kernels_persist4.h): 4 x CW threads, one column part, 32-mode slabs
-        const size_t lds4 = ctx->persistLds4;
-        const int cw = ctx->persistCW, wk4 = ctx->persistWidthK;
-        const bool st = ctx->d_pstamps != nullptr;
-#define PS4L(CW, NYK, RCC, STT) do { if (sweeps == 2) hipLaunchKernelGGL((k_cocg_persist4<CW, 2, 32, NYK, RCC, STT>), grid, dim3(4 * CW), lds4, ctx->stream, a); \
-                                     else hipLaunchKernelGGL((k_cocg_persist4<CW, 1, 32, NYK, RCC, STT>), grid, dim3(4 * CW), lds4, ctx->stream, a); } while (0)
-        if (cw == 256 && wk4 == 208) { if (st) PS4L(256, 208, 4, true); else PS4L(256, 208, 4, false); }
-        else if (cw == 256) PS4L(256, 0, 4, false);
-        else if (cw == 128) PS4L(128, 0, 4, false);
-        else PS4L(64, 0, 4, false);
-#undef PS4L
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    const size_t lds = ctx->persistLds;
-#define PSL(CW, SWP) do { if (ctx->persistCS > 1) hipLaunchKernelGGL((k_cocg_persist<CW, SWP, 16, 2>), grid, dim3(2 * CW), lds, ctx->stream, a); \
-                         else if (ctx->persistMW == 16) hipLaunchKernelGGL((k_cocg_persist<CW, SWP, 16, 1>), grid, dim3(2 * CW), lds, ctx->stream, a); \
-                         else hipLaunchKernelGGL((k_cocg_persist<CW, SWP, 32, 1>), grid, dim3(2 * CW), lds, ctx->stream, a); } while (0)
-    // width-specialised instantiations (PS_WIDTHS: the row width is a compile-time constant) where the mesh has one of those widths
-    const int wk = ctx->persistWidthK;
-    // HMCMT_STAMPS=persist: the instantiations with the phase stamps compiled in (the 512-thread shapes the phase tables are made on)
-    if (ctx->d_pstamps && ctx->persistCW == 256 && (ctx->persistCS == 2 || ctx->persistMW == 32)) {
-#define PSS(SWP) do { if (wk == 208 && ctx->persistCS == 1) hipLaunchKernelGGL((k_cocg_persist<256, SWP, 32, 1, 208, true>), grid, dim3(512), lds, ctx->stream, a); \
-                      else if (wk == 416 && ctx->persistCS == 2) hipLaunchKernelGGL((k_cocg_persist<256, SWP, 16, 2, 416, true>), grid, dim3(512), lds, ctx->stream, a); \
-                      else if (ctx->persistCS == 2) hipLaunchKernelGGL((k_cocg_persist<256, SWP, 16, 2, 0, true>), grid, dim3(512), lds, ctx->stream, a); \
-                      else hipLaunchKernelGGL((k_cocg_persist<256, SWP, 32, 1, 0, true>), grid, dim3(512), lds, ctx->stream, a); } while (0)
-        if (sweeps == 2) PSS(2); else PSS(1);
-#undef PSS
-    } else
-    if (wk == 208 && ctx->persistCW == 256 && ctx->persistCS == 1 && ctx->persistMW == 32) {
-        if (sweeps == 2) hipLaunchKernelGGL((k_cocg_persist<256, 2, 32, 1, 208>), grid, dim3(512), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_cocg_persist<256, 1, 32, 1, 208>), grid, dim3(512), lds, ctx->stream, a);
-    } else if (wk == 112 && ctx->persistCW == 128 && ctx->persistCS == 1 && ctx->persistMW == 32) {      // (the reference's example meshes: 96 cells)
-        if (sweeps == 2) hipLaunchKernelGGL((k_cocg_persist<128, 2, 32, 1, 112>), grid, dim3(256), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_cocg_persist<128, 1, 32, 1, 112>), grid, dim3(256), lds, ctx->stream, a);
-    } else if (wk == 416 && ctx->persistCW == 256 && ctx->persistCS == 2 && ctx->persistMW == 16) {
-        if (sweeps == 2) hipLaunchKernelGGL((k_cocg_persist<256, 2, 16, 2, 416>), grid, dim3(512), lds, ctx->stream, a);
-        else hipLaunchKernelGGL((k_cocg_persist<256, 1, 16, 2, 416>), grid, dim3(512), lds, ctx->stream, a);
-    } else
-    if (ctx->persistCW == 256) { if (sweeps == 2) PSL(256, 2); else PSL(256, 1); }
-    else if (ctx->persistCW == 128) { if (sweeps == 2) PSL(128, 2); else PSL(128, 1); }
-    else { if (sweeps == 2) PSL(64, 2); else PSL(64, 1); }
-#undef PSL
+    const PsKernel& e = *ctx->psKern[sweeps == 2 ? 1 : 0];
+    void* args[] = {&a};
+    (void)hipLaunchKernel(e.fn, dim3(groups * ctx->persistG), dim3(e.strips * e.cw), args, ctx->persistLds, ctx->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
-// spin on the mapped progress word until it holds `value` (see the polls of solve(): a spin on host memory wakes within a
-// microsecond; the stream is looked at every 2^16 spins; no progress for SPIN_LIMIT_S seconds is an error)
-int spin_progress(hmcmt_ctx* ctx, int value) {
+// spin until `reached()` (the polls of solve(): a spin on host memory wakes within a microsecond; `pause` leaves the core's other
+// hyper-thread its cycles, and the stream is looked at every 2^16 spins: a device error, or everything done, ends the wait; a
+// device that makes no progress for SPIN_LIMIT_S seconds is reported instead of spinning forever)
+template <class Reached>
+int spin_until(hmcmt_ctx* ctx, Reached reached) {
     long spins = 0;
     std::chrono::steady_clock::time_point t0;
-    while (*(volatile int*)ctx->h_prog != value) {
+    while (!reached()) {
         __builtin_ia32_pause();
         if ((++spins & 0xffff) == 0) {
             if (hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
@@ -757,7 +754,7 @@ int spin_progress(hmcmt_ctx* ctx, int value) {
             else if (std::chrono::duration<double>(now - t0).count() > SPIN_LIMIT_S) { ctx->err = "the device made no progress on a solve for 60 s"; return HMCMT_EHIP; }
         }
     }
-    if (*(volatile int*)ctx->h_prog != value) HIPCHK(hipStreamSynchronize(ctx->stream));   // reports the error, if any
+    if (!reached()) HIPCHK(hipStreamSynchronize(ctx->stream));   // reports the error, if any
     return 0;
 }
 constexpr double SWEEPS2_COST = 1.20;       // time of a two-sweep iteration / time of a one-sweep iteration on the launch-per-phase loop (59-60 us / 50 us at the headline size)
@@ -796,242 +793,193 @@ void ensure_dinv(hmcmt_ctx* ctx) {
     hipLaunchKernelGGL(k_dinv, dim3(ctx->sv.NB, ctx->sv.S), dim3(VBLOCK), 0, ctx->stream, ctx->sv, ctx->jacobiW);
     ctx->dinvValid = true;
 }
-int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn* spec = nullptr) {
+// What the persistent attempt of a solve came to (solve_persist)
+enum class PsOutcome {
+    NotRun,         // the persistent kernel does not apply to this solve
+    Misplaced,      // a group's workgroups were not on one XCD: the context has left the kernel, the launch-per-phase loop solves
+    Done,           // the kernel ran, every system converged
+    Stalled,        // ... a system stagnated: the fp64 restart loop continues the active systems
+    Unfinished      // ... neither: a system gave up or a wait timed out (the failure word says which), else the fp64 restart loop
+};
+// The persistent attempt: ONE launch solves every system (kernels_persist.h).  The kernel tells the host through mapped words: the
+// progress word when its last workgroup leaves, the active-system counter, the stagnation / failure / placement / timeout words.
+int solve_persist(hmcmt_ctx* ctx, int kind, hmcmt_ctx::PsStart start, const SpecFn* spec, PsOutcome& out) {
     Solver& k = ctx->sv;
-    const View& v = ctx->v;
-    k.x = x;
-    k.tol2 = ctx->opt.tol * ctx->opt.tol;
     const int S = k.S;
-    dim3 vg(k.NB, S), vb(VBLOCK);
-    const size_t vecBytes = (size_t)S * k.vstride * sizeof(cplx);
-    if (ctx->opt.verify) HIPCHK(hipMemcpyAsync(ctx->d_b, k.r, vecBytes, hipMemcpyDeviceToDevice, ctx->stream));
-    // production guard (every guardEvery-th evaluation): the true residual of this solve without options.verify -- the forward
-    // problem's right-hand side lives in x's boundary nodes (k_trueres forms it), the adjoint one was copied to d_b by evaluate()
-    const bool guard = !ctx->opt.verify && ctx->guardNow;
-    // all systems of the requested modes start active (device copy: no host round trip)
-    const hmcmt_ctx::PsStart start = ctx->psStart;          // (evaluate_once: residual and bookkeeping inside the persistent kernel)
-    ctx->psStart = hmcmt_ctx::PsStart{};
-    if (!ctx->solveBegun)           // (otherwise done by the residual kernel in front of this solve -- or about to be done by the persistent kernel)
-        hipLaunchKernelGGL(k_solve_begin, dim3((S * MAXNB + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->v.sysOn);
-    ctx->solveBegun = false;
-    if (k.cntActive) { ++ctx->profSolves; ctx->profStartSys += ctx->nSysOn; if (k.sweeps == 2) ++ctx->profSolves2; }
-    int& guess = kind == 0 ? ctx->lastItFwd : ctx->lastItAdj;
-    int nextCheck = guess > 2 ? guess : 4;
+    ctx->preDone = false;                          // (it does its own first pre-smoothing pass)
+    host_word(ctx, HW_STALL) = 0;
+    host_word(ctx, HW_PLACE) = 0;
+    host_word(ctx, HW_TIMEOUT) = 0;
+    *(volatile int*)ctx->h_prog = 0;
+    { ProfScope ps(ctx, 2); int prc = launch_persist(ctx, k.sweeps, 0, nullptr, kind, start); if (prc) return prc; }
+    ++ctx->persistSolves;
+    if (k.cntActive) ++ctx->profPersistSolves;
+    if (kind == 0 && ctx->sidePending) {
+        // (the host is free while the device solves.)  Not before the persistent kernel's whole grid is resident (progress word 1, behind
+        // the last group's placement check): the side streams do not wait for the kernels in front of the solve, and k_sens_fused's
+        // workgroups (LDS, 256 threads), dispatched first, sit on CUs this kernel's workgroups need -- at the stress size the solve
+        // started 0.1 ms late.  (A misplaced group never reports: the kernel then ends early, PS_DONE ends this wait as well.)
+        long spins = 0;
+        while (*(volatile int*)ctx->h_prog == 0 && ++spins < (1l << 26)) {
+            __builtin_ia32_pause();
+            if ((spins & 0xffff) == 0 && hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
+        }
+        launch_adjoint_side(ctx);
+    }
+    if (spec && ctx->specOn) (*spec)(ctx->d_gate + kind, ctx->gateGen);
+    { int prc = spin_until(ctx, [ctx] { return *(volatile int*)ctx->h_prog == PS_DONE; }); if (prc) return prc; }
+    if (host_word(ctx, HW_TIMEOUT)) {
+        // a wait inside the kernel timed out (a word of its own: a healthy group's system that ends with a status afterwards
+        // overwrites the shared status word, and the redo below would be skipped) (its grid was not co-resident: a foreign kernel holds CUs, a lock directory that
+        // does not coordinate): the systems are in no defined state.  This context leaves the persistent kernel -- for 256 solves
+        // after the first timeout, twice as long after every further one --, and evaluate() runs the evaluation again, cold,
+        // with the launch-per-phase loop, which works under any sharing
+        ctx->persistTimedOut = true;
+        ctx->persistOn = false; ctx->persistWhyOff = 2; ++ctx->persistTimeouts;
+        ctx->persistBackoff = 256l << std::min<long long>(ctx->persistTimeouts - 1, 6);     // (the tenant may leave: 256, 512, .. 16 384 solves, then another try)
+    }
+    if (host_word(ctx, HW_PLACE)) {
+        // the group's workgroups were not on one XCD (or the kernel could not be placed): nothing was touched by those
+        // groups -- this context goes back to the launch-per-phase loop for good
+        ctx->persistOn = false; ctx->persistWhyOff = 1; ctx->persistBackoff = 0; ++ctx->persistFallbacks;
+        ctx->fbKind = kind; ctx->fbStalled = -1;
+        if (start.begin && start.resid) {
+            // (rare, and behind a finished kernel: what it left is read back -- active 1: started and stalled, 2: never started)
+            std::vector<int> act(S);
+            HIPCHK(hipMemcpyAsync(act.data(), k.active, sizeof(int) * S, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            ctx->fbStalled = (int)std::count(act.begin(), act.end(), 1);
+        }
+        ensure_dinv(ctx);
+        if (start.begin) {
+            // (the kernel was to form the residual itself: the systems the misplaced groups did not touch -- active = 2 -- have none
+            //  yet; those a healthy group started and left stalled -- active = 1 -- keep their x and r: r is no longer the right-hand
+            //  side the adjoint start forms would read from it.  The launch-per-phase loop's partial sums start from zero)
+            HIPCHK(hipMemsetAsync(k.partB, 0, (size_t)S * MAXNB * sizeof(double), ctx->stream));
+            if (start.resid) hipLaunchKernelGGL(k_resid0, dim3(k.NB, S), dim3(VBLOCK), 0, ctx->stream, k, k.x, start.resid == PS_RESID_FULL ? 0 : start.resid, (const int*)nullptr, 2);
+        }
+        if (ctx->persistFallbacks == 1)
+            fprintf(stderr, "libhmcmt_hip: the workgroups of a system of the persistent solve kernel were not dispatched to one XCD (a partitioned device, "
+                            "another dispatch order?); this context runs the launch-per-phase loop from here on -- same results, several times slower "
+                            "(hmcmt_persist_info: placement_fallbacks, why_off)\n");
+        out = PsOutcome::Misplaced;
+        return 0;
+    }
+    out = *(volatile int*)ctx->h_nactive == 0 ? PsOutcome::Done : host_word(ctx, HW_STALL) ? PsOutcome::Stalled : PsOutcome::Unfinished;
+    return 0;
+}
+// The launch-per-phase loop of the mixed-precision path (the fused kernels): from it = 0 until every system is done, a system
+// stagnates or the iteration cap; `it` ends as the iterations launched (done: needed)
+int solve_fused(hmcmt_ctx* ctx, int kind, int nextCheck, bool& done, int& it) {
+    Solver& k = ctx->sv;
+    { int prc = apply_precond(ctx); if (prc) return prc; }          // z = P^-1 r and the partial sums of r'z, |z|^2
+    float2* pb[2] = {k.p32a, k.p32b};
+    cplx* rb[2] = {k.r, k.r2};
+    int rcur = 0;
+    // Convergence polls without events.  The device keeps three words in mapped pinned memory: the number of active
+    // systems and the stagnation flag (k_spmv_fused of iteration `it` updates them with its decision on the state
+    // after iteration it-1) and a progress word (the first thread of k_spmv_fused(it) stores `it` when it STARTS,
+    // i.e. when everything of iteration it-1 has completed).  From the iteration count of the previous call on, the
+    // host queues all of iteration `it`, then spins until the progress word says k_spmv_fused(it) has started --
+    // three launches (~40 us) are still queued behind it at that moment and a spin on host memory wakes within a
+    // microsecond, so the queue never drains -- and reads the counter.  (An event per polled iteration put a 6 us
+    // bubble behind every polled k_spmv_fused and its hipEventSynchronize took 50-100 us to wake; round 1 lost
+    // ~90 us per evaluation there.)  The launches queued behind a finished solve find every system inactive and
+    // exit at once.
+    host_word(ctx, HW_STALL) = 0;
+    *(volatile int*)ctx->h_prog = 0;
+    bool stalled = false;
+    // (HMCMT_SIDE_IT = n > 0: at iteration n; default: half-way through the expected solve, between 2 and 12)
+    static const int sideItEnv = getenv("HMCMT_SIDE_IT") ? atoi(getenv("HMCMT_SIDE_IT")) : 0;
+    const int sideIt = sideItEnv > 0 ? sideItEnv : std::max(2, std::min(12, nextCheck / 2));
+    while (!done && !stalled && it < ctx->opt.maxit + 1) {
+        ++it;
+        // decide convergence of the state after iteration it-1, p = z + beta p, q = A p
+        if (k.sweeps == 2 && k.merged2) {
+            ProfScope ps(ctx, 2, true);
+            launch_spmv<2>(ctx, (size_t)(k.RTS + 2) * k.NYP * sizeof(cplx) + (size_t)(k.RTS + 4) * k.NYP * sizeof(float2), pb[(it - 1) & 1], pb[it & 1], it);
+        } else { ProfScope ps(ctx, 2, true); launch_spmv<1>(ctx, (size_t)(k.RT + 2) * k.NYP * sizeof(cplx), pb[(it - 1) & 1], pb[it & 1], it); }
+        if (k.sweeps == 2) { ProfScope ps(ctx, 3, true); launch_update2(ctx, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0); }
+        else { ProfScope ps(ctx, 3, true); if (ctx->upd1Threads == 512) hipLaunchKernelGGL((k_update_fused<1, 512, 6>), tile_grid(k, k.NTR), dim3(512), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0);
+               else hipLaunchKernelGGL((k_update_fused<1, 256, 6>), tile_grid(k, k.NTR), dim3(256), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0); }
+        rcur ^= 1;
+        k.r = rb[rcur];
+        int prc;
+        if ((prc = launch_fdm_fwd(ctx, pb[it & 1]))) return prc;
+        if ((prc = launch_back_post(ctx))) return prc;
+        std::swap(k.z, k.t);
+        if (it >= nextCheck || it - 1 == ctx->opt.maxit) {
+            { int prc = spin_until(ctx, [ctx, it] { return *(volatile int*)ctx->h_prog >= it; }); if (prc) return prc; }
+            if (it - 1 == ctx->opt.maxit) HIPCHK(hipStreamSynchronize(ctx->stream));          // (k_spmv_fused(it) itself decides the cap)
+            if (*(volatile int*)ctx->h_nactive == 0) { done = true; break; }
+            if (host_word(ctx, HW_STALL)) stalled = true;
+        }
+        // (a dozen API calls, ~150 us of host time: issued half-way through the expected solve, at most a dozen
+        // iterations deep -- short solves, 5-6 iterations on smooth paths, would otherwise get them behind the solve and
+        // wait for the adjoint guess.  Without a tracer attached 2..12 measure the same within 1 %; under
+        // rocprofv3, whose launches cost twice as much, the early settings drain the main queue.)
+        if (kind == 0 && it == sideIt) launch_adjoint_side(ctx);
+        // (likewise the wait for the adjoint guess of the side stream, four iterations behind its launch)
+        if (kind == 0 && it == sideIt + 4 && ctx->extAWaitPending) { ctx->extAWaitPending = false; ctx->chainEnd = (size_t)-1; HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evExtA, 0)); }
+        // the gradient tail needs the sensitivity tables of the side stream (205 + 53 us of serial kernels beside the forward
+        // solve, long complete by the adjoint solve's 8th iteration): the wait goes into the queue HERE, where the host runs
+        // ahead of the device, not behind the solve, where the device waits for every call
+        if (kind == 1 && it == 8 && ctx->sensWaitPending) { ctx->sensWaitPending = false; ctx->chainEnd = (size_t)-1; HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evSens, 0)); }
+    }
+    if (!done) {
+        // stragglers (or the iteration cap): read the counter once more, then hand over to the classic loop
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (*(volatile int*)ctx->h_nactive == 0) done = true;
+    }
+    if (done) it = std::max(0, it - 1);
+    return 0;
+}
+// The classic loop with the fp64 preconditioner: the whole solve on the other preconditioners, and the restart of COCG from the
+// systems' x and r where the mixed-precision solve (fused) stagnated or reached the cap
+int solve_fp64(hmcmt_ctx* ctx, bool fused, int nextCheck, bool& done, int& it) {
+    Solver& k = ctx->sv;
+    const dim3 vg(k.NB, k.S), vb(VBLOCK);
     const int every = ctx->opt.check_every > 0 ? ctx->opt.check_every : 2;
-    int it = 0;
-    bool done = false;
-    ctx->lpFallback = false;
-    ctx->solveFail = 0;
-    *(volatile int*)(ctx->h_stall + 1) = 0;             // (ordered before this solve's kernels: the previous solve has been waited for)
     const int lpCap = 60;               // (classic loop only) mixed-precision safety net: stragglers continue with the fp64 preconditioner
-    const dim3 tg((k.ny - 1 + 63) / 64, S);
-    const bool fused = ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0;
-    cplx* const r_entry = k.r;
-    bool viaPersist = false, stalledP = false, specIssued = false, placeFallback = false;
-    ctx->specValid = false;
-    // (after a timed-out wait: another try when the backoff has run out -- a context that left the kernel because of its PLACEMENT
-    //  stays off for good: persistWhyOff)
-    if (!ctx->persistOn && ctx->persistWhyOff == 2 && ctx->persistBackoff > 0 && --ctx->persistBackoff == 0) { ctx->persistOn = true; ctx->persistWhyOff = 0; }
-    if (fused && persist_ok(ctx)) {
-        // ONE launch solves every system (kernels_persist.h).  The kernel tells the host through mapped words: the progress
-        // word when its last workgroup leaves, the active-system counter, the stagnation / failure / placement flags.
-        ctx->preDone = false;                          // (it does its own first pre-smoothing pass)
-        *(volatile int*)ctx->h_stall = 0;
-        *(volatile int*)(ctx->h_stall + 2) = 0;
-        *(volatile int*)(ctx->h_stall + 3) = 0;
-        *(volatile int*)ctx->h_prog = 0;
-        { ProfScope ps(ctx, 2); int prc = launch_persist(ctx, k.sweeps, 0, nullptr, kind, start); if (prc) return prc; }
-        ++ctx->persistSolves;
-        if (k.cntActive) ++ctx->profPersistSolves;
-        if (kind == 0 && ctx->sidePending) {
-            // (the host is free while the device solves.)  Not before the persistent kernel's whole grid is resident (progress word 1, behind
-            // the last group's placement check): the side streams do not wait for the kernels in front of the solve, and k_sens_fused's
-            // workgroups (LDS, 256 threads), dispatched first, sit on CUs this kernel's workgroups need -- at the stress size the solve
-            // started 0.1 ms late.  (A misplaced group never reports: the kernel then ends early, PS_DONE ends this wait as well.)
-            long spins = 0;
-            while (*(volatile int*)ctx->h_prog == 0 && ++spins < (1l << 26)) {
-                __builtin_ia32_pause();
-                if ((spins & 0xffff) == 0 && hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
-            }
-            launch_adjoint_side(ctx);
-        }
-        if (spec && ctx->specOn) { (*spec)(ctx->d_gate + kind, ctx->gateGen); specIssued = true; }
-        { int prc = spin_progress(ctx, PS_DONE); if (prc) return prc; }
-        if (*(volatile int*)(ctx->h_stall + 3)) {
-            // a wait inside the kernel timed out (a word of its own: a healthy group's system that ends with a status afterwards
-            // overwrites the shared status word, and the redo below would be skipped) (its grid was not co-resident: a foreign kernel holds CUs, a lock directory that
-            // does not coordinate): the systems are in no defined state.  This context leaves the persistent kernel -- for 256 solves
-            // after the first timeout, twice as long after every further one --, and evaluate() runs the evaluation again, cold,
-            // with the launch-per-phase loop, which works under any sharing
-            ctx->persistTimedOut = true;
-            ctx->persistOn = false; ctx->persistWhyOff = 2; ++ctx->persistTimeouts;
-            ctx->persistBackoff = 256l << std::min<long long>(ctx->persistTimeouts - 1, 6);     // (the tenant may leave: 256, 512, .. 16 384 solves, then another try)
-        }
-        if (*(volatile int*)(ctx->h_stall + 2)) {
-            // the group's workgroups were not on one XCD (or the kernel could not be placed): nothing was touched by those
-            // groups -- this context goes back to the launch-per-phase loop for good
-            ctx->persistOn = false; ctx->persistWhyOff = 1; ctx->persistBackoff = 0; ++ctx->persistFallbacks;
-            placeFallback = true;
-            ctx->fbKind = kind; ctx->fbStalled = -1;
-            if (start.begin && start.resid) {
-                // (rare, and behind a finished kernel: what it left is read back -- active 1: started and stalled, 2: never started)
-                std::vector<int> act(S);
-                HIPCHK(hipMemcpyAsync(act.data(), k.active, sizeof(int) * S, hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-                ctx->fbStalled = (int)std::count(act.begin(), act.end(), 1);
-            }
-            ensure_dinv(ctx);
-            if (start.begin) {
-                // (the kernel was to form the residual itself: the systems the misplaced groups did not touch -- active = 2 -- have none
-                //  yet; those a healthy group started and left stalled -- active = 1 -- keep their x and r: r is no longer the right-hand
-                //  side the adjoint start forms would read from it.  The launch-per-phase loop's partial sums start from zero)
-                HIPCHK(hipMemsetAsync(k.partB, 0, (size_t)S * MAXNB * sizeof(double), ctx->stream));
-                if (start.resid) hipLaunchKernelGGL(k_resid0, dim3(k.NB, S), dim3(VBLOCK), 0, ctx->stream, k, x, start.resid == PS_RESID_FULL ? 0 : start.resid, (const int*)nullptr, 2);
-            }
-            if (ctx->persistFallbacks == 1)
-                fprintf(stderr, "libhmcmt_hip: the workgroups of a system of the persistent solve kernel were not dispatched to one XCD (a partitioned device, "
-                                "another dispatch order?); this context runs the launch-per-phase loop from here on -- same results, several times slower "
-                                "(hmcmt_persist_info: placement_fallbacks, why_off)\n");
-        } else {
-            viaPersist = true;
-            if (*(volatile int*)ctx->h_nactive == 0) done = true;
-            else if (*(volatile int*)ctx->h_stall) stalledP = true;
-        }
+    // (a mesh wider than 447 cells has no fp64 eigen-transform to restart with: a NUMERICAL event -- a stagnating solve -- ends the
+    //  evaluation as "not converged", not as an invalid argument from launch_transform)
+    if (fused && ctx->hp.NYP / 16 > 28) {
+        ctx->err = "a mixed-precision solve stagnated on a mesh wider than 447 cells, where the fp64 restart does not exist (include/hmcmt.h, hmcmt_create): not converged";
+        return HMCMT_ENOCONV;
     }
-    if (!(viaPersist && done)) ensure_dinv(ctx);          // (everything below that touches the systems again reads the diagonals)
-    if (start.begin && !viaPersist && !placeFallback) {
-        // (the persistent kernel was to start this solve but did not run after all -- a second context has appeared on the device since
-        //  evaluate_once looked --: the start as launches of their own)
-        if (start.resid) hipLaunchKernelGGL(k_resid0, dim3(k.NB, S), dim3(VBLOCK), 0, ctx->stream, k, x, start.resid == PS_RESID_FULL ? 0 : start.resid, ctx->v.sysOn, 0);
-        else hipLaunchKernelGGL(k_solve_begin, dim3((S * MAXNB + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->v.sysOn);
-    }
-    if (start.begin && viaPersist && stalledP) HIPCHK(hipMemsetAsync(k.partB, 0, (size_t)S * MAXNB * sizeof(double), ctx->stream));   // (the fp64 restart's loop: its partial sums start from zero)
-    if (fused && !viaPersist) {
-        { int prc = apply_precond(ctx); if (prc) return prc; }          // z = P^-1 r and the partial sums of r'z, |z|^2
-        float2* pb[2] = {k.p32a, k.p32b};
-        cplx* rb[2] = {k.r, k.r2};
-        int rcur = 0;
-        // Convergence polls without events.  The device keeps three words in mapped pinned memory: the number of active
-        // systems and the stagnation flag (k_spmv_fused of iteration `it` updates them with its decision on the state
-        // after iteration it-1) and a progress word (the first thread of k_spmv_fused(it) stores `it` when it STARTS,
-        // i.e. when everything of iteration it-1 has completed).  From the iteration count of the previous call on, the
-        // host queues all of iteration `it`, then spins until the progress word says k_spmv_fused(it) has started --
-        // three launches (~40 us) are still queued behind it at that moment and a spin on host memory wakes within a
-        // microsecond, so the queue never drains -- and reads the counter.  (An event per polled iteration put a 6 us
-        // bubble behind every polled k_spmv_fused and its hipEventSynchronize took 50-100 us to wake; round 1 lost
-        // ~90 us per evaluation there.)  The launches queued behind a finished solve find every system inactive and
-        // exit at once.
-        *(volatile int*)ctx->h_stall = 0;
-        *(volatile int*)ctx->h_prog = 0;
-        bool stalled = false;
-        // (HMCMT_SIDE_IT = n > 0: at iteration n; default: half-way through the expected solve, between 2 and 12)
-        static const int sideItEnv = getenv("HMCMT_SIDE_IT") ? atoi(getenv("HMCMT_SIDE_IT")) : 0;
-        const int sideIt = sideItEnv > 0 ? sideItEnv : std::max(2, std::min(12, nextCheck / 2));
-        while (!done && !stalled && it < ctx->opt.maxit + 1) {
-            ++it;
-            // decide convergence of the state after iteration it-1, p = z + beta p, q = A p
-            if (k.sweeps == 2 && k.merged2) {
-                ProfScope ps(ctx, 2, true);
-                launch_spmv<2>(ctx, (size_t)(k.RTS + 2) * k.NYP * sizeof(cplx) + (size_t)(k.RTS + 4) * k.NYP * sizeof(float2), pb[(it - 1) & 1], pb[it & 1], it);
-            } else { ProfScope ps(ctx, 2, true); launch_spmv<1>(ctx, (size_t)(k.RT + 2) * k.NYP * sizeof(cplx), pb[(it - 1) & 1], pb[it & 1], it); }
-            if (k.sweeps == 2) { ProfScope ps(ctx, 3, true); launch_update2(ctx, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0); }
-            else { ProfScope ps(ctx, 3, true); if (ctx->upd1Threads == 512) hipLaunchKernelGGL((k_update_fused<1, 512, 6>), tile_grid(k, k.NTR), dim3(512), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0);
-                   else hipLaunchKernelGGL((k_update_fused<1, 256, 6>), tile_grid(k, k.NTR), dim3(256), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0); }
-            rcur ^= 1;
-            k.r = rb[rcur];
-            int prc;
-            if ((prc = launch_fdm_fwd(ctx, pb[it & 1]))) return prc;
-            if ((prc = launch_back_post(ctx))) return prc;
-            std::swap(k.z, k.t);
-            if (it >= nextCheck || it - 1 == ctx->opt.maxit) {
-                // (a spin on host memory wakes within a microsecond; `pause` leaves the core's other hyper-thread its
-                //  cycles, and the stream is looked at every 2^16 spins: a device error, or everything done, ends the wait;
-                //  a device that makes no progress for SPIN_LIMIT_S seconds is reported instead of spinning forever)
-                long spins = 0;
-                std::chrono::steady_clock::time_point t0;
-                bool hung = false;
-                while (*(volatile int*)ctx->h_prog < it) {
-                    __builtin_ia32_pause();
-                    if ((++spins & 0xffff) == 0) {
-                        if (hipStreamQuery(ctx->stream) != hipErrorNotReady) break;
-                        const auto now = std::chrono::steady_clock::now();
-                        if (spins == 0x10000) t0 = now;
-                        else if (std::chrono::duration<double>(now - t0).count() > SPIN_LIMIT_S) { hung = true; break; }
-                    }
-                }
-                if (hung) { ctx->err = "the device made no progress on a solve for 60 s"; return HMCMT_EHIP; }
-                if (*(volatile int*)ctx->h_prog < it) HIPCHK(hipStreamSynchronize(ctx->stream));   // reports the error, if any
-                if (it - 1 == ctx->opt.maxit) HIPCHK(hipStreamSynchronize(ctx->stream));          // (k_spmv_fused(it) itself decides the cap)
-                if (*(volatile int*)ctx->h_nactive == 0) { done = true; break; }
-                if (*(volatile int*)ctx->h_stall) stalled = true;
-            }
-            // (a dozen API calls, ~150 us of host time: issued half-way through the expected solve, at most a dozen
-            // iterations deep -- short solves, 5-6 iterations on smooth paths, would otherwise get them behind the solve and
-            // wait for the adjoint guess.  Without a tracer attached 2..12 measure the same within 1 %; under
-            // rocprofv3, whose launches cost twice as much, the early settings drain the main queue.)
-            if (kind == 0 && it == sideIt) launch_adjoint_side(ctx);
-            // (likewise the wait for the adjoint guess of the side stream, four iterations behind its launch)
-            if (kind == 0 && it == sideIt + 4 && ctx->extAWaitPending) { ctx->extAWaitPending = false; ctx->chainEnd = (size_t)-1; HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evExtA, 0)); }
-            // the gradient tail needs the sensitivity tables of the side stream (205 + 53 us of serial kernels beside the forward
-            // solve, long complete by the adjoint solve's 8th iteration): the wait goes into the queue HERE, where the host runs
-            // ahead of the device, not behind the solve, where the device waits for every call
-            if (kind == 1 && it == 8 && ctx->sensWaitPending) { ctx->sensWaitPending = false; ctx->chainEnd = (size_t)-1; HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->evSens, 0)); }
+    const bool restart = fused;      // coming from the fused loop: restart COCG with the fp64 preconditioner
+    if (restart) { ctx->lpFallback = true; ++ctx->stats.fallback_solves; }
+    // z = P^-1 r ; rho = r'z ; p = z
+    { int prc = apply_precond(ctx); if (prc) return prc; }
+    { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, restart ? 2 : 1, ctx->opt.maxit); }
+    { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 1); }
+    while (!done && it < ctx->opt.maxit) {
+        ++it;
+        if (it == lpCap + 1 && ctx->opt.fdm_precision == 0 && ctx->opt.precond != HMCMT_PRECOND_JACOBI && !ctx->lpFallback) {
+            ctx->lpFallback = true;     // restart COCG for the still-active systems: z = P64^-1 r, p = z
+            ++ctx->stats.fallback_solves;
+            { int prc = apply_precond(ctx); if (prc) return prc; }
+            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, 2, ctx->opt.maxit); }
+            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 1); }
         }
-        if (!done) {
-            // stragglers (or the iteration cap): read the counter once more, then hand over to the classic loop
+        { ProfScope ps(ctx, 2); hipLaunchKernelGGL(k_spmv, vg, vb, 0, ctx->stream, k); }
+        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_update, vg, vb, 0, ctx->stream, k); }
+        { int prc = apply_precond(ctx); if (prc) return prc; }
+        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, 0, ctx->opt.maxit); }
+        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 0); }
+        if (it >= nextCheck || it == ctx->opt.maxit) {
             HIPCHK(hipStreamSynchronize(ctx->stream));
             if (*(volatile int*)ctx->h_nactive == 0) done = true;
-        }
-        if (done) it = std::max(0, it - 1);
-    }
-    if (viaPersist) it = guess;          // (what the kernel needed is in its records: parse_stats)
-    (void)stalledP;
-    if (!done && !(viaPersist && *(volatile int*)(ctx->h_stall + 1))) {
-        if (viaPersist) it = 0;
-        // (a mesh wider than 447 cells has no fp64 eigen-transform to restart with: a NUMERICAL event -- a stagnating solve -- ends the
-        //  evaluation as "not converged", not as an invalid argument from launch_transform)
-        if (fused && ctx->hp.NYP / 16 > 28) {
-            ctx->err = "a mixed-precision solve stagnated on a mesh wider than 447 cells, where the fp64 restart does not exist (include/hmcmt.h, hmcmt_create): not converged";
-            return HMCMT_ENOCONV;
-        }
-        const bool restart = fused;      // coming from the fused loop: restart COCG with the fp64 preconditioner
-        if (restart) { ctx->lpFallback = true; ++ctx->stats.fallback_solves; }
-        // z = P^-1 r ; rho = r'z ; p = z
-        { int prc = apply_precond(ctx); if (prc) return prc; }
-        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, restart ? 2 : 1, ctx->opt.maxit); }
-        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 1); }
-        while (!done && it < ctx->opt.maxit) {
-            ++it;
-            if (it == lpCap + 1 && ctx->opt.fdm_precision == 0 && ctx->opt.precond != HMCMT_PRECOND_JACOBI && !ctx->lpFallback) {
-                ctx->lpFallback = true;     // restart COCG for the still-active systems: z = P64^-1 r, p = z
-                ++ctx->stats.fallback_solves;
-                { int prc = apply_precond(ctx); if (prc) return prc; }
-                { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, 2, ctx->opt.maxit); }
-                { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 1); }
-            }
-            { ProfScope ps(ctx, 2); hipLaunchKernelGGL(k_spmv, vg, vb, 0, ctx->stream, k); }
-            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_update, vg, vb, 0, ctx->stream, k); }
-            { int prc = apply_precond(ctx); if (prc) return prc; }
-            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, 0, ctx->opt.maxit); }
-            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 0); }
-            if (it >= nextCheck || it == ctx->opt.maxit) {
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-                if (*(volatile int*)ctx->h_nactive == 0) done = true;
-                nextCheck = it + every;
-            }
+            nextCheck = it + every;
         }
     }
-    // the fused loop ping-pongs r between the caller's buffer and r2: leave the struct as it was found
-    if (k.r != r_entry) { k.r2 = k.r; k.r = r_entry; }
-    // a system that hit the iteration cap or broke down has been deactivated like a converged one: "no active systems"
-    // is then not "solved" (the host learns it from the mapped failure word at the poll that ended the loop)
-    ctx->solveFail = *(volatile int*)(ctx->h_stall + 1);
-    if (ctx->solveFail) done = false;
-    guess = it;        // (launched iterations; collect_stats replaces it with the iterations actually needed)
-
-    ctx->solveDone[kind] = done;
-    ctx->specValid = specIssued && viaPersist && done && !stalledP;       // (the device decided the same from the same words: k_cocg_persist's exit)
-    // iteration counts / status / error estimates stay on the device; evaluate() reads both solves back at once
+    return 0;
+}
+// The solve's records (k_solve_end, unless deferEnd) and, with options.verify or the production guard, the true residual
+int solve_epilogue(hmcmt_ctx* ctx, int kind, const cplx* x, bool done, bool deferEnd, bool guard) {
+    const Solver& k = ctx->sv;
+    const int S = k.S;
+    const dim3 vg(k.NB, S), vb(VBLOCK);
     if (!deferEnd) launch_solve_end(ctx, kind);
     if (ctx->opt.verify || (guard && done)) {
         hipLaunchKernelGGL(k_trueres, vg, vb, 0, ctx->stream, k, (guard && kind == 0) ? (const cplx*)nullptr : ctx->d_b, x, ctx->d_partRes, ctx->d_partBn);
@@ -1055,8 +1003,67 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
             }
         }
     }
-    (void)v;
     return 0;
+}
+int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn* spec = nullptr) {
+    Solver& k = ctx->sv;
+    k.x = x;
+    k.tol2 = ctx->opt.tol * ctx->opt.tol;
+    const int S = k.S;
+    const size_t vecBytes = (size_t)S * k.vstride * sizeof(cplx);
+    if (ctx->opt.verify) HIPCHK(hipMemcpyAsync(ctx->d_b, k.r, vecBytes, hipMemcpyDeviceToDevice, ctx->stream));
+    // production guard (every guardEvery-th evaluation): the true residual of this solve without options.verify -- the forward
+    // problem's right-hand side lives in x's boundary nodes (k_trueres forms it), the adjoint one was copied to d_b by evaluate()
+    const bool guard = !ctx->opt.verify && ctx->guardNow;
+    // all systems of the requested modes start active (device copy: no host round trip)
+    const hmcmt_ctx::PsStart start = ctx->psStart;          // (evaluate_once: residual and bookkeeping inside the persistent kernel)
+    ctx->psStart = hmcmt_ctx::PsStart{};
+    if (!ctx->solveBegun)           // (otherwise done by the residual kernel in front of this solve -- or about to be done by the persistent kernel)
+        hipLaunchKernelGGL(k_solve_begin, dim3((S * MAXNB + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->v.sysOn);
+    ctx->solveBegun = false;
+    if (k.cntActive) { ++ctx->profSolves; ctx->profStartSys += ctx->nSysOn; if (k.sweeps == 2) ++ctx->profSolves2; }
+    int& guess = kind == 0 ? ctx->lastItFwd : ctx->lastItAdj;
+    const int nextCheck = guess > 2 ? guess : 4;
+    ctx->lpFallback = false;
+    ctx->solveFail = 0;
+    host_word(ctx, HW_FAIL) = 0;             // (ordered before this solve's kernels: the previous solve has been waited for)
+    const bool fused = ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0;
+    cplx* const r_entry = k.r;
+    ctx->specValid = false;
+    // (after a timed-out wait: another try when the backoff has run out -- a context that left the kernel because of its PLACEMENT
+    //  stays off for good: persistWhyOff)
+    if (!ctx->persistOn && ctx->persistWhyOff == 2 && ctx->persistBackoff > 0 && --ctx->persistBackoff == 0) { ctx->persistOn = true; ctx->persistWhyOff = 0; }
+    PsOutcome outcome = PsOutcome::NotRun;
+    if (fused && persist_ok(ctx)) { int prc = solve_persist(ctx, kind, start, spec, outcome); if (prc) return prc; }
+    const bool viaPersist = outcome == PsOutcome::Done || outcome == PsOutcome::Stalled || outcome == PsOutcome::Unfinished;
+    bool done = outcome == PsOutcome::Done;
+    int it = 0;
+    if (!done) ensure_dinv(ctx);          // (everything below that touches the systems again reads the diagonals)
+    if (start.begin && outcome == PsOutcome::NotRun) {
+        // (the persistent kernel was to start this solve but did not run after all -- a second context has appeared on the device since
+        //  evaluate_once looked --: the start as launches of their own)
+        if (start.resid) hipLaunchKernelGGL(k_resid0, dim3(k.NB, S), dim3(VBLOCK), 0, ctx->stream, k, x, start.resid == PS_RESID_FULL ? 0 : start.resid, ctx->v.sysOn, 0);
+        else hipLaunchKernelGGL(k_solve_begin, dim3((S * MAXNB + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->v.sysOn);
+    }
+    if (start.begin && outcome == PsOutcome::Stalled) HIPCHK(hipMemsetAsync(k.partB, 0, (size_t)S * MAXNB * sizeof(double), ctx->stream));   // (the fp64 restart's loop: its partial sums start from zero)
+    if (fused && !viaPersist) { int prc = solve_fused(ctx, kind, nextCheck, done, it); if (prc) return prc; }
+    if (viaPersist) it = guess;          // (what the kernel needed is in its records: parse_stats)
+    if (!done && !(viaPersist && host_word(ctx, HW_FAIL))) {
+        if (viaPersist) it = 0;
+        int prc = solve_fp64(ctx, fused, nextCheck, done, it);
+        if (prc) return prc;
+    }
+    // the fused loop ping-pongs r between the caller's buffer and r2: leave the struct as it was found
+    if (k.r != r_entry) { k.r2 = k.r; k.r = r_entry; }
+    // a system that hit the iteration cap or broke down has been deactivated like a converged one: "no active systems"
+    // is then not "solved" (the host learns it from the mapped failure word at the poll that ended the loop)
+    ctx->solveFail = host_word(ctx, HW_FAIL);
+    if (ctx->solveFail) done = false;
+    guess = it;        // (launched iterations; collect_stats replaces it with the iterations actually needed)
+
+    ctx->solveDone[kind] = done;
+    ctx->specValid = spec && ctx->specOn && outcome == PsOutcome::Done && done;       // (the device decided the same from the same words: k_cocg_persist's exit)
+    return solve_epilogue(ctx, kind, x, done, deferEnd, guard);
 }
 
 // residual + first pre-smoothing pass of a solve (k_resid_pre); threads by tile size like the stencil kernels of the iteration
@@ -1126,7 +1133,7 @@ int evaluate(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pred, d
         ctx->haveFwd = ctx->haveAdj = false; ctx->lastItFwd = ctx->lastItAdj = 0;
         ctx->lfStep.on = 0;
         ctx->solveFail = 0;
-        *(volatile int*)(ctx->h_stall + 1) = 0;
+        host_word(ctx, HW_FAIL) = 0;
         rc = evaluate_once(ctx, d_m, wantGrad, d_pred, d_misfit, d_grad);
     }
     return rc;
@@ -1724,31 +1731,16 @@ static int persist_setup(hmcmt_ctx* ctx) {
     if (!persist_shape(ctx, k.twist, cuPerXcd, G, cw, mw, lds, &cs)) return 0;
     if ((size_t)k.S * (size_t)k.vstride >= ((size_t)1 << 27)) return 0;      // (the kernel's 32-bit lane offsets carry the system's element offset: kernels_persist.h, so32)
     ctx->persistMW = mw;
-    const void* fns[32] = {reinterpret_cast<const void*>(k_cocg_persist<256, 1, 32, 1, 208, true>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 32, 1, 208, true>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 16, 2, 416, true>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 16, 2, 416, true>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 32, 1, 0, true>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 32, 1, 0, true>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 16, 2, 0, true>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 16, 2, 0, true>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 32, 1, 208>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 32, 1, 208>),
-                           reinterpret_cast<const void*>(k_cocg_persist<128, 1, 32, 1, 112>), reinterpret_cast<const void*>(k_cocg_persist<128, 2, 32, 1, 112>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 16, 2, 416>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 16, 2, 416>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 32, 1>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 32, 1>),
-                           reinterpret_cast<const void*>(k_cocg_persist<128, 1, 32, 1>), reinterpret_cast<const void*>(k_cocg_persist<128, 2, 32, 1>),
-                           reinterpret_cast<const void*>(k_cocg_persist<64, 1, 32, 1>), reinterpret_cast<const void*>(k_cocg_persist<64, 2, 32, 1>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 16, 1>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 16, 1>),
-                           reinterpret_cast<const void*>(k_cocg_persist<128, 1, 16, 1>), reinterpret_cast<const void*>(k_cocg_persist<128, 2, 16, 1>),
-                           reinterpret_cast<const void*>(k_cocg_persist<64, 1, 16, 1>), reinterpret_cast<const void*>(k_cocg_persist<64, 2, 16, 1>),
-                           reinterpret_cast<const void*>(k_cocg_persist<256, 1, 16, 2>), reinterpret_cast<const void*>(k_cocg_persist<256, 2, 16, 2>),
-                           reinterpret_cast<const void*>(k_cocg_persist<128, 1, 16, 2>), reinterpret_cast<const void*>(k_cocg_persist<128, 2, 16, 2>),
-                           reinterpret_cast<const void*>(k_cocg_persist<64, 1, 16, 2>), reinterpret_cast<const void*>(k_cocg_persist<64, 2, 16, 2>)};
-    for (const void* f : fns)
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    for (const PsKernel& e : g_psKernels)
+        if (e.strips == 2 && hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); return 0; }
 
     ctx->persistG = G;
     ctx->persistCS = cs;
     ctx->persistGZ = G / cs;
-    // the width-specialised instantiations (launch_persist); HMCMT_PERSIST_WIDTHK=0 keeps the generic kernels (A/B runs, tests)
-    ctx->persistWidthK = (((k.NYP == 208 || k.NYP == 112) && cs == 1) || (k.NYP == 416 && cs == 2)) ? k.NYP : 0;
-    if (const char* e = getenv("HMCMT_PERSIST_WIDTHK")) if (e[0] == '0') ctx->persistWidthK = 0;
+    // the width-specialised instantiations where the table has one for the mesh's padded row width (ps_pick); HMCMT_PERSIST_WIDTHK=0
+    // keeps the generic kernels (A/B runs, tests)
+    int wk = k.NYP;
+    if (const char* e = getenv("HMCMT_PERSIST_WIDTHK")) if (e[0] == '0') wk = 0;
     ctx->persistSlots = std::max(1, std::min((k.S + 7) / 8, cuPerXcd / G));
     ctx->persistFillsShare = ctx->persistSlots * G >= cuPerXcd;       // (no CU of this context's share left over beside a solve: launch_adjoint_side)
     ctx->persistLds = lds;
@@ -1799,21 +1791,16 @@ static int persist_setup(hmcmt_ctx* ctx) {
     }
     // the four-strip kernel where it applies: one column part, 32-mode slabs, a column tile of the transforms per wave, the slab
     // sweeps' chunks of four rows covering half the rows; HMCMT_PERSIST_STRIPS=2 keeps the two-half kernel (A/B)
-    ctx->persistStrips = 2;
+    int strips = 2;
     {
         const char* e = getenv("HMCMT_PERSIST_STRIPS");
         const int want = e ? atoi(e) : 2;      // (round 6: the four-strip kernel is opt-in -- it measured 530 against 600 steps/s at the headline size)
         const size_t lds4 = ps4_lds_bytes(k.NYP, k.NZP, k.nz, 32, 4 * cw);
         if (want == 4 && cs == 1 && mw == 32 && 4 * cw <= 1024 && k.NYP / 16 <= 4 * cw / 64 && ps4_slab_rc(k.nz, 32, 4 * cw) == 4 && lds4 <= (size_t)160 * 1024) {
-            const void* f4[] = {reinterpret_cast<const void*>(k_cocg_persist4<256, 1, 32, 208, 4, false>), reinterpret_cast<const void*>(k_cocg_persist4<256, 2, 32, 208, 4, false>),
-                                reinterpret_cast<const void*>(k_cocg_persist4<256, 1, 32, 208, 4, true>), reinterpret_cast<const void*>(k_cocg_persist4<256, 2, 32, 208, 4, true>),
-                                reinterpret_cast<const void*>(k_cocg_persist4<256, 1, 32, 0, 4, false>), reinterpret_cast<const void*>(k_cocg_persist4<256, 2, 32, 0, 4, false>),
-                                reinterpret_cast<const void*>(k_cocg_persist4<128, 1, 32, 0, 4, false>), reinterpret_cast<const void*>(k_cocg_persist4<128, 2, 32, 0, 4, false>),
-                                reinterpret_cast<const void*>(k_cocg_persist4<64, 1, 32, 0, 4, false>), reinterpret_cast<const void*>(k_cocg_persist4<64, 2, 32, 0, 4, false>)};
             bool ok4 = true;
-            for (const void* f : f4)
-                if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); ok4 = false; }
-            if (ok4) { ctx->persistStrips = 4; ctx->persistRC = 4; ctx->persistLds4 = lds4; }
+            for (const PsKernel& e4 : g_psKernels)
+                if (e4.strips == 4 && hipFuncSetAttribute(e4.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); ok4 = false; }
+            if (ok4) { strips = 4; ctx->persistLds = lds4; }
         }
     }
     if (const char* es = getenv("HMCMT_STAMPS")) if (!strcmp(es, "persist")) {
@@ -1821,6 +1808,10 @@ static int persist_setup(hmcmt_ctx* ctx) {
         HIPCHK(hipMemset(ctx->d_pstamps, 0, sizeof(long long) * 16 * 256));
         ctx->allocs.push_back(ctx->d_pstamps);
     }
+    for (int sw = 1; sw <= 2; ++sw)
+        if (!(ctx->psKern[sw - 1] = ps_pick(strips, cw, mw, cs, wk, ctx->d_pstamps != nullptr, sw))) {
+            ctx->err = "no instantiation of the persistent solve kernel for this shape (g_psKernels)"; return HMCMT_EINVAL;
+        }
     ctx->persistCW = cw;
     return 0;
 }
@@ -2113,10 +2104,10 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
 #undef DA
     HIPCHK(hipHostMalloc((void**)&ctx->h_nactive, sizeof(int), hipHostMallocMapped));
     HIPCHK(hipHostGetDevicePointer((void**)&k.nactHost, ctx->h_nactive, 0));
-    HIPCHK(hipHostMalloc((void**)&ctx->h_stall, 4 * sizeof(int), hipHostMallocMapped));     // [0] stagnation flag, [1] failure status, [2] persistent kernel: placement failed
-    ctx->h_stall[0] = ctx->h_stall[1] = ctx->h_stall[2] = ctx->h_stall[3] = 0;
+    HIPCHK(hipHostMalloc((void**)&ctx->h_stall, HW_WORDS * sizeof(int), hipHostMallocMapped));     // the HostWord block: stagnation, failure status, placement failed, wait timed out
+    for (int w = 0; w < HW_WORDS; ++w) ctx->h_stall[w] = 0;
     HIPCHK(hipHostGetDevicePointer((void**)&k.stallHost, ctx->h_stall, 0));
-    k.failHost = k.stallHost + 1;
+    k.failHost = k.stallHost + HW_FAIL;
     k.stallIt = STALL_IT;
     if (const char* es = getenv("HMCMT_STALL_IT")) k.stallIt = std::max(1, atoi(es));   // (tests force the fp64 restart with a short window)
     HIPCHK(hipHostMalloc((void**)&ctx->h_prog, sizeof(int), hipHostMallocMapped));
@@ -2541,7 +2532,7 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
         ctx->persistCW ? ctx->persistCS : 0,  // column parts per row block (2: wide meshes)
         ctx->persistTimeouts,                 // timed-out waits (the evaluation was redone with the launch-per-phase loop)
         ctx->shareIdx, ctx->shareCnt,         // this context's share of every XCD's CUs (hmcmt_next_cu_share)
-        ctx->persistCW ? ctx->persistStrips : 0,   // strips of tile rows per column: 2 (k_cocg_persist) or 4 (k_cocg_persist4: threads = strips x threads_half)
+        ctx->persistCW ? ctx->psKern[0]->strips : 0,   // strips of tile rows per column: 2 (k_cocg_persist) or 4 (k_cocg_persist4: threads = strips x threads_half)
         ctx->persistWhyOff,                   // why the kernel is off: 0 it is not / HMCMT_PERSIST=0, 1 placement (for good), 2 a timed-out wait (tried again after the backoff)
         ctx->fbKind, ctx->fbStalled};         // the last placement fallback: kind of its launch, systems it found started and still active (stalled)
     for (int i = 0; i < nout && i < HMCMT_PERSIST_INFO_FIELDS; ++i) out[i] = v[i];
@@ -2552,7 +2543,7 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
 // row: kernels_persist.h, NYK), 0 = the generic kernel (or no persistent kernel at all).
 int hmcmt_persist_width(const hmcmt_ctx* ctx, int32_t* width) {
     if (!ctx || !width) return HMCMT_EINVAL;
-    *width = ctx->persistCW ? ctx->persistWidthK : 0;
+    *width = ctx->persistCW ? ctx->psKern[0]->nyk : 0;
     return 0;
 }
 
@@ -2655,12 +2646,12 @@ int hmcmt_debug_persist_precond(hmcmt_ctx* ctx, int32_t sweeps, const double* r,
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(ctx->sv.z32, 0, n * sizeof(float2), ctx->stream));
     *(volatile int*)ctx->h_prog = 0;
-    *(volatile int*)(ctx->h_stall + 2) = 0;
+    host_word(ctx, HW_PLACE) = 0;
     ctx->sv.tol2 = ctx->opt.tol * ctx->opt.tol;
     if ((rc = launch_persist(ctx, sweeps, 1, ctx->sv.z32))) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (*(volatile int*)(ctx->h_stall + 2)) { ctx->err = "persistent kernel: the workgroups of a system were not placed on one XCD"; return HMCMT_EHIP; }
-    if (*(volatile int*)(ctx->h_stall + 1) || *(volatile int*)(ctx->h_stall + 3)) { ctx->err = "persistent kernel: a wait timed out"; return HMCMT_EHIP; }
+    if (host_word(ctx, HW_PLACE)) { ctx->err = "persistent kernel: the workgroups of a system were not placed on one XCD"; return HMCMT_EHIP; }
+    if (host_word(ctx, HW_FAIL) || host_word(ctx, HW_TIMEOUT)) { ctx->err = "persistent kernel: a wait timed out"; return HMCMT_EHIP; }
     std::vector<float2> h(n);
     HIPCHK(hipMemcpy(h.data(), ctx->sv.z32, n * sizeof(float2), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) { z[2 * i] = h[i].x; z[2 * i + 1] = h[i].y; }
@@ -3480,7 +3471,7 @@ static int jac_run(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrow
                 // (a wait of the persistent kernel timed out: the context is on the launch-per-phase loop now -- the batch again, there)
                 ctx->persistTimedOut = false;
                 (void)hipStreamSynchronize(strm); (void)hipGetLastError();
-                ctx->solveFail = 0; *(volatile int*)(ctx->h_stall + 1) = 0;
+                ctx->solveFail = 0; host_word(ctx, HW_FAIL) = 0;
                 ctx->stats.fallback_solves = fb0;
                 continue;
             }

@@ -6,6 +6,14 @@
 // ----------------------------------------------------------------------------------------------
 // solver state shared by the COCG kernels
 // ----------------------------------------------------------------------------------------------
+// the words of the mapped host block Solver::stallHost points to (hmcmt_create), by index
+enum HostWord {
+    HW_STALL = 0,                         // a system stagnated (the fused loop's stall watch; the persistent kernel's)
+    HW_FAIL = 1,                          // status of a system that has just given up (Solver::failHost)
+    HW_PLACE = 2,                         // the persistent kernel: a group's workgroups were not on one XCD (PsConst::placeHost)
+    HW_TIMEOUT = 3,                       // the persistent kernel: a wait timed out
+    HW_WORDS = 4
+};
 struct Solver {
     int S, NB, NYP, NZP, ny, nz, nFreq;
     long vstride, chunk;
@@ -54,7 +62,7 @@ struct Solver {
     int* errRefIt;                        // [S] iteration at which errRef was set
     int stallIt;                          // iterations allowed per 10-fold drop of the error estimate (STALL_IT; HMCMT_STALL_IT)
     int* progHost;                        // pinned host word: the iteration whose k_spmv_fused has STARTED (host throttle, see solve())
-    int* stallHost;                       // pinned host flag: a system has not improved its error estimate 10-fold in STALL_IT iterations
+    int* stallHost;                       // pinned host block of HW_WORDS words (HostWord); [HW_STALL]: a system has not improved its error estimate 10-fold in STALL_IT iterations
     int* failHost;                        // pinned host word: status (HMCMT_ENOCONV / HMCMT_EBREAKDOWN) of a system that has just given up --
                                           // the host must not build on this solve (adjoint on a failed forward, next leapfrog step)
     long long* ticks;                     // HMCMT_TICKS: View::ticks

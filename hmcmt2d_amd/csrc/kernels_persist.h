@@ -84,7 +84,7 @@ struct PsConst {
     unsigned* sync;            // [groups][32] per group: [0] barrier counter, [1] arrivals of the placement check, [2] OR of 1 << XCC_ID
     unsigned* exitCnt;         // workgroups that have left the kernel
     int* fail;                 // device word: 1 = a group's workgroups are not on one XCD, 2 = a wait timed out
-    int* placeHost;            // pinned host word: set when a group's workgroups are not on one XCD (the host then runs the launch-per-phase loop)
+    int* placeHost;            // pinned host word HW_PLACE (= stallHost + HW_PLACE): set when a group's workgroups are not on one XCD (the host then runs the launch-per-phase loop)
     const u4v *Vb, *Vtb;       // bf16 fragment-order copies of V, V'
     float2 *pubR, *pubZ, *pubP;   // [S][vstride] complex64: r', the pre-smoothed iterate (z2; one sweep: z1), p of the own nodes
     float2 *yhat, *yhat2;      // [S][vstride] complex64 rows of the forward transform (column parts: one partial product per part)
@@ -1536,7 +1536,7 @@ __global__ __launch_bounds__(2 * CW) void k_cocg_persist(PsLaunch L) {
     __syncthreads();
     tick_end(kb->ticks, L.tickId);
     if (tid == 0) {
-        if (sflag[0] == 2) { *kb->failHost = HMCMT_EHIP; kb->placeHost[1] = 1; }       // a wait timed out: the solve is void (the host redoes it with the launch-per-phase loop; a word of its own, stallHost[3]: the status word may be overwritten by a healthy group's system)
+        if (sflag[0] == 2) { *kb->failHost = HMCMT_EHIP; kb->placeHost[HW_TIMEOUT - HW_PLACE] = 1; }       // a wait timed out: the solve is void (the host redoes it with the launch-per-phase loop; a word of its own, HW_TIMEOUT: the status word may be overwritten by a healthy group's system)
         __threadfence_system();
         const unsigned nLeft = __hip_atomic_fetch_add(kb->exitCnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         sflag[1] = nLeft == gridDim.x - 1 ? 1 : 0;

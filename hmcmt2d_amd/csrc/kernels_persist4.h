@@ -802,7 +802,7 @@ __global__ __launch_bounds__(4 * CW) void k_cocg_persist4(PsLaunch L) {
     __syncthreads();
     tick_end(kb->ticks, L.tickId);
     if (tid == 0) {
-        if (sflag[0] == 2) { *kb->failHost = HMCMT_EHIP; kb->placeHost[1] = 1; }      // (a timed-out wait has a word of its own: stallHost[3])
+        if (sflag[0] == 2) { *kb->failHost = HMCMT_EHIP; kb->placeHost[HW_TIMEOUT - HW_PLACE] = 1; }      // (a timed-out wait has a word of its own: HW_TIMEOUT)
         __threadfence_system();
         const unsigned nLeft = __hip_atomic_fetch_add(kb->exitCnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         sflag[1] = nLeft == gridDim.x - 1 ? 1 : 0;
