@@ -60,6 +60,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_path.h"
 #include "kernels_mass.h"
 #include "kernels_jac.h"
+#include "kernels_jvp.h"
 
 // an instantiation of the persistent solve kernel (g_psKernels, launch_persist): k_cocg_persist<cw, sw, mw, cs, nyk, st> (two
 // halves) or k_cocg_persist4<cw, sw, 32, nyk, 4, st> (four strips), strips x cw threads per workgroup
@@ -275,6 +276,15 @@ struct hmcmt_ctx {
         int* sysOn = nullptr;              // [nRx][S]
         int maxRows = 0;                   // most data of one receiver
     } jac;
+    // matrix-free Jacobian products (hmcmt_linearize / hmcmt_jvp / hmcmt_jtvp / hmcmt_gn_hessvec, kernels_jvp.h): the linearisation
+    // point's model, the products' own work arrays (the solution and boundary-weight arrays are the Jacobian's: `jac`)
+    struct Jvp {
+        bool ready = false;
+        bool valid = false;                // a linearisation point is set and no evaluation has run since
+        double *m = nullptr, *vin = nullptr, *dSig = nullptr, *out = nullptr, *gPartG = nullptr, *qPart = nullptr, *misfit = nullptr;
+        double* scale = nullptr;           // [4] power-of-two normalisation of the tangent's / the adjoint's input (k_jvp_norm)
+        cplx *dbcL = nullptr, *dbcR = nullptr, *dbcB = nullptr, *jv = nullptr, *u = nullptr, *vbar = nullptr, *rxCoef = nullptr;
+    } jvp;
 };
 
 static thread_local std::string g_createError;      // (per thread: contexts of different chains are created from different threads)
@@ -1147,6 +1157,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
     hipStream_t st = ctx->stream;
     const int S = v.S;
     { int prc = collect_pending(ctx); if (prc) return prc; }      // (an earlier asynchronous evaluation's records / status)
+    ctx->jvp.valid = false;             // (the evaluation arrays leave the linearisation point of hmcmt_linearize)
     ctx->stats = hmcmt_stats{};
     ctx->stats.nsystems = S;
     ++ctx->evalCount;
@@ -2201,6 +2212,7 @@ int hmcmt_set_options(hmcmt_ctx* ctx, const hmcmt_options* o) {
     ctx->haveFwd = ctx->haveAdj = false;
     ctx->memo[0].valid = ctx->memo[1].valid = false;
     ctx->lfHaveGrad = false;            // (a gradient kept for start_grad = 1 / 2 was computed under the old options)
+    ctx->jvp.valid = false;
     return 0;
 }
 
@@ -2309,6 +2321,7 @@ static int host_eval(hmcmt_ctx* ctx, const double* m, double* pred, double* misf
             ctx->stats = e->stats;                                           // (this call itself iterated nothing)
             ctx->stats.iters_fwd_max = ctx->stats.iters_adj_max = ctx->stats.iters_fwd_sum = ctx->stats.iters_adj_sum = 0;
             ++ctx->memoHits;
+            ctx->jvp.valid = false;                                          // (an evaluating call, answered or not, ends a linearisation point)
             return 0;
         }
     std::memcpy(ctx->h_stage, m, sizeof(double) * nAC);
@@ -3547,5 +3560,253 @@ int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
+
+// ----------------------------------------------------------------------------------------------
+// matrix-free Jacobian products (kernels_jvp.h).  hmcmt_linearize is an ordinary cold forward evaluation plus what the gradient
+// computes in front of its adjoint solve (boundary-derivative tables, receiver functionals); a product is small launches around ONE
+// solve() per direction -- forward kind for the tangent field (dense right-hand side, zero guess), adjoint kind for J^T u (the
+// gradient's sparse start) -- on the Jacobian's solution and boundary arrays, bracketed by the Jacobian's save / restore of the
+// host solve state (JacState).  A product runs no evaluation: the context's fields, history and memo are not touched at all.
+// ----------------------------------------------------------------------------------------------
+static int jvp_alloc(hmcmt_ctx* ctx) {
+    if (int rc = jac_alloc(ctx)) return rc;
+    hmcmt_ctx::Jvp& P = ctx->jvp;
+    if (P.ready) return 0;
+    const View& v = ctx->v;
+    const size_t S = (size_t)v.S;
+    int rc = 0;
+    if ((rc = dalloc(ctx, &P.m, (size_t)v.nAC)) || (rc = dalloc(ctx, &P.vin, (size_t)v.nAC)) || (rc = dalloc(ctx, &P.dSig, (size_t)v.nCell)) ||
+        (rc = dalloc(ctx, &P.out, (size_t)v.nAC)) || (rc = dalloc(ctx, &P.gPartG, (size_t)2 * GRAD_NG * v.nCell)) ||
+        (rc = dalloc(ctx, &P.qPart, S * v.ny)) || (rc = dalloc(ctx, &P.misfit, 1)) || (rc = dalloc(ctx, &P.scale, 4)) ||
+        (rc = dalloc(ctx, &P.dbcL, S * v.nz)) || (rc = dalloc(ctx, &P.dbcR, S * v.nz)) || (rc = dalloc(ctx, &P.dbcB, S * (v.ny + 1))) ||
+        (rc = dalloc(ctx, &P.jv, (size_t)v.nData)) || (rc = dalloc(ctx, &P.u, (size_t)v.nData)) || (rc = dalloc(ctx, &P.vbar, (size_t)v.nData)) ||
+        (rc = dalloc(ctx, &P.rxCoef, S * v.nRx)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    P.ready = true;
+    return 0;
+}
+
+static int linearize_run(hmcmt_ctx* ctx) {
+    hmcmt_ctx::Jvp& P = ctx->jvp;
+    hipStream_t strm = ctx->stream;
+    P.valid = false;
+    ctx->haveFwd = false;                                // (always from a zero guess: the warm-start history starts again here)
+    int rc = evaluate(ctx, P.m, false, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if ((rc = collect_stats(ctx, false))) return rc;     // (includes the stream synchronisation)
+    prof_collect(ctx);
+    if ((rc = finish_status(ctx))) return rc;
+    // what the gradient's side stream and k_rxall(wantGrad) provide: the boundary-derivative tables and the receiver functionals
+    View vj = ctx->v;
+    vj.m = P.m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
+    const int S = vj.S;
+    hipLaunchKernelGGL(k_sens_layers, dim3((vj.nz + 1 + 63) / 64, 3, S), dim3(64), 0, strm, vj);
+    hipLaunchKernelGGL(k_sens_profile, dim3((3 * S + 63) / 64), dim3(64), 0, strm, vj);
+    hipLaunchKernelGGL(k_bcsens_pre, dim3((vj.nz + 63) / 64, 3, S), dim3(64), 0, strm, vj);
+    hipLaunchKernelGGL(k_rx, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj, 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(strm));
+    P.valid = true;
+    return 0;
+}
+
+static int linearize_check(hmcmt_ctx* ctx, const void* m) {
+    if (!m) { ctx->err = "linearize: null model pointer"; return HMCMT_EINVAL; }
+    if (ctx->statsPending) { ctx->err = "linearize: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+// one solve of a product: `fill` writes the right-hand side (again after a timed-out persistent launch, which destroys it);
+// sparseRow >= 0: the adjoint's sparse start on node rows sparseRow, sparseRow + 1 where the persistent kernel starts the solve
+static int prod_solve(hmcmt_ctx* ctx, cplx* x, int kind, int sweeps, int sparseRow, const std::function<void(bool)>& fill, hmcmt_stats& st) {
+    hipStream_t strm = ctx->stream;
+    const size_t vecBytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
+    for (int attempt = 0;; ++attempt) {
+        HIPCHK(hipMemsetAsync(x, 0, vecBytes, strm));
+        const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 &&
+                                   !ctx->opt.verify && persist_ok(ctx);
+        fill(inKernelStart);
+        ctx->sv.sweeps = sweeps;
+        ctx->preDone = false;
+        if (inKernelStart) { ctx->psStart.resid = sparseRow >= 0 ? 2 + sparseRow : 0; ctx->psStart.begin = 1; ctx->solveBegun = true; }
+        else ctx->solveBegun = false;
+        ctx->guardNow = false;
+        ctx->persistTimedOut = false;
+        const int fb0 = ctx->stats.fallback_solves;
+        int rc = solve(ctx, x, kind);
+        if (rc) return rc;
+        if (ctx->persistTimedOut && attempt == 0) {
+            ctx->persistTimedOut = false;
+            (void)hipStreamSynchronize(strm); (void)hipGetLastError();
+            ctx->solveFail = 0; host_word(ctx, HW_FAIL) = 0;
+            ctx->stats.fallback_solves = fb0;
+            continue;
+        }
+        if (ctx->stats.fallback_solves > fb0) ++st.fallback_solves;
+        break;
+    }
+    HIPCHK(hipStreamSynchronize(strm));
+    jac_records(ctx, kind, ctx->hp.sysOn.data(), st);
+    if (ctx->solveFail || !ctx->solveDone[kind]) {
+        if (st.status == 0) st.status = ctx->solveFail ? ctx->solveFail : HMCMT_ENOCONV;
+        const char* which = kind == 0 ? "tangent" : "adjoint";
+        ctx->err = std::string("Jacobian product: the ") + which + (st.status == HMCMT_EBREAKDOWN ? " solve broke down" : " solve did not converge");
+        return st.status == HMCMT_EBREAKDOWN ? HMCMT_EBREAKDOWN : HMCMT_ENOCONV;
+    }
+    return 0;
+}
+
+// J v -> vj.jv (d_v: device, [nAC])
+static int prod_tangent(hmcmt_ctx* ctx, View vj, const double* d_v, int wrt, int sweeps, hmcmt_stats& st) {
+    hipStream_t strm = ctx->stream;
+    const int S = vj.S;
+    vj.tanV = d_v;
+    vj.R = ctx->sv.r;
+    HIPCHK(hipMemsetAsync(vj.jv, 0, sizeof(cplx) * vj.nData, strm));
+    hipLaunchKernelGGL(k_jvp_dsig, grid1(vj.nCell, 256), dim3(256), 0, strm, vj, wrt);
+    hipLaunchKernelGGL(k_jvp_norm, dim3(1), dim3(1024), 0, strm, vj.dSig, (const double*)vj.sigma, (long)vj.nCell, ctx->jvp.scale);
+    vj.tanScale = ctx->jvp.scale;
+    hipLaunchKernelGGL(k_jvp_dbc, dim3((2 * vj.nz + vj.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S), dim3(64 * DBC_WAVES), 0, strm, vj);
+    auto fill = [&](bool) {
+        hipLaunchKernelGGL(k_jvp_rhs, dim3((unsigned)((vj.vstride + 255) / 256), S), dim3(256), 0, strm, vj);
+    };
+    if (int rc = prod_solve(ctx, ctx->jac.lam, 0, sweeps, -1, fill, st)) return rc;
+    vj.dF = ctx->jac.lam;
+    hipLaunchKernelGGL(k_jvp_data, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Re(J^T conj(u)) -> d_out (d_u: device, complex [nData]; d_out: device, [nAC])
+static int prod_adjoint(hmcmt_ctx* ctx, View vj, const cplx* d_u, int wrt, int sweeps, double* d_out, hmcmt_stats& st) {
+    hipStream_t strm = ctx->stream;
+    hmcmt_ctx::Jac& J = ctx->jac;
+    const int S = vj.S;
+    vj.uData = d_u;
+    vj.Lam = J.lam; vj.R = ctx->sv.r; vj.srcB = J.srcB; vj.wL = J.wL; vj.wR = J.wR; vj.colw = J.colw; vj.gL = J.gL; vj.gR = J.gR;
+    hipLaunchKernelGGL(k_jtvp_vbar, grid1(vj.nData, 256), dim3(256), 0, strm, vj);
+    hipLaunchKernelGGL(k_jvp_norm, dim3(1), dim3(1024), 0, strm, reinterpret_cast<double*>(vj.vbar), (const double*)nullptr, 2l * vj.nData, ctx->jvp.scale + 2);
+    hipLaunchKernelGGL(k_rxcoef, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj);
+    const int nsrc = (2 * (vj.ny + 1) + 127) / 128;
+    const size_t vecBytes = (size_t)S * vj.vstride * sizeof(cplx);
+    auto fill = [&](bool sparse) {
+        if (!sparse) (void)hipMemsetAsync(vj.R, 0, vecBytes, strm);           // (the whole right-hand side is the residual)
+        hipLaunchKernelGGL(k_src, dim3(nsrc + (vj.ny + 127) / 128, S), dim3(128), 0, strm, vj, ctx->jvp.misfit, nsrc);
+    };
+    if (int rc = prod_solve(ctx, J.lam, 1, sweeps, vj.zid, fill, st)) return rc;
+    hipLaunchKernelGGL(k_jac_wb, dim3((vj.nz + vj.ny + 127) / 128, S), dim3(128), 0, strm, vj);
+    hipLaunchKernelGGL(k_jac_contract, dim3((BCC_L * vj.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj);
+    hipLaunchKernelGGL(k_gradcell, dim3((vj.nCell + 127) / 128, 2, GRAD_NG), dim3(128), 0, strm, vj);
+    hipLaunchKernelGGL(k_jtvp_final, grid1(vj.nAC, 128), dim3(128), 0, strm, vj, wrt, (const double*)(ctx->jvp.scale + 2), d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+enum { PROD_JVP = 0, PROD_JTVP = 1, PROD_GN = 2 };
+// d_in / d_out: device pointers (jvp: v[nAC] -> Jv complex[nData]; jtvp: u complex[nData] -> [nAC]; gn: v[nAC] -> [nAC])
+static int prod_run(hmcmt_ctx* ctx, int what, const double* d_in, int wrt, double* d_out, hmcmt_stats* stOut) {
+    hmcmt_ctx::Jvp& P = ctx->jvp;
+    hipStream_t strm = ctx->stream;
+    hmcmt_stats st{};
+    st.nsystems = ctx->v.S;
+    JacState saved;
+    jac_save(ctx, saved);
+    auto leave = [&](int rc) {
+        const std::string e = ctx->err;
+        (void)hipStreamSynchronize(strm);
+        jac_restore(ctx, saved);
+        ctx->err = e;
+        if (stOut) *stOut = st;
+        return rc;
+    };
+    // no guard, no sampled profiling, no test hooks, no leapfrog update in the products' solves
+    ctx->guardEvery = 0; ctx->profMask = 0; ctx->dbgFlags = 0;
+    ctx->lfStep.on = 0; ctx->lfMom.on = 0;
+    ctx->sv.cntActive = nullptr;
+    ctx->stats = hmcmt_stats{};
+    View vj = ctx->v;
+    vj.m = P.m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
+    vj.dSig = P.dSig; vj.dbcL = P.dbcL; vj.dbcR = P.dbcR; vj.dbcB = P.dbcB;
+    vj.vbar = P.vbar; vj.rxCoef = P.rxCoef; vj.qPart = P.qPart; vj.gPartG = P.gPartG;
+    vj.jv = what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : P.jv;
+    const int sweeps = (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2;    // (cold solves: well above the two-sweep threshold)
+    int rc = 0;
+    if (what == PROD_JVP || what == PROD_GN) {
+        if ((rc = prod_tangent(ctx, vj, d_in, wrt, sweeps, st))) return leave(rc);
+        st.smoother_sweeps = 10 * sweeps;
+    }
+    if (what == PROD_GN) hipLaunchKernelGGL(k_jvp_w2, grid1(vj.nData, 256), dim3(256), 0, strm, vj, P.u);
+    if (what == PROD_JTVP || what == PROD_GN) {
+        const cplx* u = what == PROD_GN ? P.u : reinterpret_cast<const cplx*>(d_in);
+        if ((rc = prod_adjoint(ctx, vj, u, wrt, sweeps, d_out, st))) return leave(rc);
+        st.smoother_sweeps += sweeps;
+    }
+    return leave(0);
+}
+
+static int prod_check(hmcmt_ctx* ctx, const void* in, int32_t wrt, const void* out) {
+    if (!in || !out) { ctx->err = "Jacobian product: null input or output pointer"; return HMCMT_EINVAL; }
+    if (wrt != HMCMT_JAC_WRT_SIGMA && wrt != HMCMT_JAC_WRT_LNSIGMA) { ctx->err = "Jacobian product: wrt must be HMCMT_JAC_WRT_SIGMA or HMCMT_JAC_WRT_LNSIGMA"; return HMCMT_EINVAL; }
+    if (ctx->statsPending) { ctx->err = "Jacobian product: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
+    if (!ctx->jvp.ready || !ctx->jvp.valid) {
+        ctx->err = "Jacobian product: no valid linearisation point (call hmcmt_linearize; every evaluating call and hmcmt_set_options ends it)";
+        return HMCMT_EINVAL;
+    }
+    return 0;
+}
+
+// host entry: stage the input, run on the device buffers, bring the result back
+static int prod_host(hmcmt_ctx* ctx, int what, const double* in, int32_t wrt, double* out, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = prod_check(ctx, in, wrt, out)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hmcmt_ctx::Jvp& P = ctx->jvp;
+    const int nAC = ctx->v.nAC, nData = ctx->v.nData;
+    const bool inData = what == PROD_JTVP, outData = what == PROD_JVP;
+    const size_t nin = inData ? 2 * (size_t)nData : (size_t)nAC, nout = outData ? 2 * (size_t)nData : (size_t)nAC;
+    for (size_t i = 0; i < nin; ++i)
+        if (!std::isfinite(in[i])) { ctx->err = "Jacobian product: non-finite input value"; return HMCMT_EINVAL; }
+    // (staging: u in P.u, v in P.vin; J v comes back through P.u, the cell vectors through P.out)
+    double* d_in = inData ? reinterpret_cast<double*>(P.u) : P.vin;
+    double* d_out = outData ? reinterpret_cast<double*>(P.u) : P.out;
+    HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin, hipMemcpyHostToDevice, ctx->stream));
+    int rc = prod_run(ctx, what, d_in, wrt, d_out, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+static int prod_device(hmcmt_ctx* ctx, int what, const double* d_in, int32_t wrt, double* d_out, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = prod_check(ctx, d_in, wrt, d_out)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    return prod_run(ctx, what, d_in, wrt, d_out, st);
+}
+
+int hmcmt_linearize(hmcmt_ctx* ctx, const double* m) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = linearize_check(ctx, m)) return rc;
+    for (int i = 0; i < ctx->v.nAC; ++i)
+        if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = jvp_alloc(ctx)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->jvp.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
+    return linearize_run(ctx);
+}
+int hmcmt_linearize_device(hmcmt_ctx* ctx, const double* d_m) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = linearize_check(ctx, d_m)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = jvp_alloc(ctx)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->jvp.m, d_m, sizeof(double) * ctx->v.nAC, hipMemcpyDeviceToDevice, ctx->stream));
+    return linearize_run(ctx);
+}
+int hmcmt_jvp(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Jv, hmcmt_stats* st) { return prod_host(ctx, PROD_JVP, v, wrt, Jv, st); }
+int hmcmt_jtvp(hmcmt_ctx* ctx, const double* u, int32_t wrt, double* JTu, hmcmt_stats* st) { return prod_host(ctx, PROD_JTVP, u, wrt, JTu, st); }
+int hmcmt_gn_hessvec(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Hv, hmcmt_stats* st) { return prod_host(ctx, PROD_GN, v, wrt, Hv, st); }
+int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Jv, hmcmt_stats* st) { return prod_device(ctx, PROD_JVP, d_v, wrt, d_Jv, st); }
+int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st) { return prod_device(ctx, PROD_JTVP, d_u, wrt, d_JTu, st); }
+int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st) { return prod_device(ctx, PROD_GN, d_v, wrt, d_Hv, st); }
 
 }  // extern "C"

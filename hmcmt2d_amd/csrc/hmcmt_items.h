@@ -111,6 +111,16 @@ struct View {
     double* qPart;                 // [S][ny] Q-term (explicit sigma-dependence of the data functional) per system
     double* gPart;                 // [2][nCell] P-term partial sums per mode
     double* grad;                  // [nAC]
+    // matrix-free Jacobian products at a linearisation point (hmcmt_jvp / hmcmt_jtvp, kernels_jvp.h)
+    const double* tanV = nullptr;  // [nAC] direction v of J v
+    double* dSig = nullptr;        // [nCell] delta sigma on all cells
+    cplx* dbcL = nullptr;          // [S][nz]  tangent of the Dirichlet values, left-boundary nodes iz = 1..nz
+    cplx* dbcR = nullptr;          // [S][nz]
+    cplx* dbcB = nullptr;          // [S][ny+1] bottom nodes iy = 1..ny-1 (the corners belong to the sides)
+    const cplx* dF = nullptr;      // [S][NZP][NYP] tangent field (interior nodes)
+    const cplx* uData = nullptr;   // [nData] the caller's data vector u of J^T u
+    cplx* jv = nullptr;            // [nData] J v in the layout of pred
+    const double* tanScale = nullptr;  // [2] {2^-e, 2^e}: the power of two the product's input was normalised by (null: none)
 };
 
 HD long nidx(const View& v, int iy, int iz) { return (long)iz * v.NYP + iy; }
@@ -675,6 +685,154 @@ HD cplx jac_datum(int kind, cplx z, double omega, cplx dz) {
     const cplx c = conj(z) * dz;
     if (kind == 1) return cplx{(2.0 / (omega * MU0)) * c.re, 0.0};
     return cplx{(180.0 / 3.14159265358979323846) * c.im / cabs2(z), 0.0};
+}
+
+// ==============================================================================================
+// Tangent-linear route J v (compJacMat.jl:206-314 applied to a vector): the exact transposes of jac_cell's P-term,
+// item_wside / item_colw + item_bcsens_contract + gradfinal_sys (boundary terms) and item_src / item_qterm (data side).
+// ==============================================================================================
+// --- delta sigma on every cell from v on the active cells: wrt 0 d sigma = v, 1 d sigma = exp(m) v (m = ln sigma)
+HD void item_dsigma(const View& v, int cell, int wrt) {
+    const int a = v.cell2act[cell];
+    double d = 0.0;
+    if (a >= 0) d = wrt ? exp(v.m[a]) * v.tanV[a] : v.tanV[a];
+    v.dSig[cell] = d;
+}
+// --- tangent of the boundary values, dbc = dBC dsigma (MT1DSensitivity.jl:272-328): one term of the sum over the layers c
+//     side node iz (1..nz) of profile prof (0 left, 1 right): row iz-1 of v.dBC times dsigma of the first / last cell column
+HD cplx dbc_side_term(const View& v, int s, int prof, int iz, int c) {
+    const cplx d = v.dBC[(((long)s * 2 + prof) * v.nz + (iz - 1)) * v.nz + c];
+    return v.dSig[(long)c * v.ny + (prof ? v.ny - 1 : 0)] * d;
+}
+//     bottom node iy (1..ny-1): the mean profile's last row times the width-weighted dsigma of the two columns beside the node
+//     (the transpose of item_colw, MT1DSensitivity.jl:315-328)
+HD cplx dbc_bottom_term(const View& v, int s, int iy, int c) {
+    const double ya = v.yLen[iy - 1], yb = v.yLen[iy];
+    const double ds = (ya / (ya + yb)) * v.dSig[(long)c * v.ny + iy - 1] + (yb / (ya + yb)) * v.dSig[(long)c * v.ny + iy];
+    return ds * v.gMn[(long)s * v.nz + c];
+}
+// (serial forms, layers in order: the host instantiation; the GPU kernel spreads a row over a wavefront)
+HD void item_dbc_side(const View& v, int s, int prof, int iz) {
+    cplx acc = cplx{0, 0};
+    if (v.sysOn[s])
+        for (int c = 0; c < v.nz; ++c) acc += dbc_side_term(v, s, prof, iz, c);
+    (prof ? v.dbcR : v.dbcL)[(long)s * v.nz + iz - 1] = acc;
+}
+HD void item_dbc_bottom(const View& v, int s, int iy) {
+    cplx acc = cplx{0, 0};
+    if (v.sysOn[s])
+        for (int c = 0; c < v.nz; ++c) acc += dbc_bottom_term(v, s, iy, c);
+    v.dbcB[(long)s * (v.ny + 1) + iy] = acc;
+}
+// tangent of the Dirichlet value at a boundary node: top row 0, corners with the sides
+HD cplx dbc_at(const View& v, int s, int iy, int iz) {
+    if (iz == 0) return cplx{0, 0};
+    if (iy == 0) return v.dbcL[(long)s * v.nz + iz - 1];
+    if (iy == v.ny) return v.dbcR[(long)s * v.nz + iz - 1];
+    if (iz == v.nz) return v.dbcB[(long)s * (v.ny + 1) + iy];
+    return cplx{0, 0};
+}
+// --- tangent right-hand side b = -(dA/dsigma . dsigma) F - Aio dbc at one node of the padded grid (zero off the interior):
+//     TE  -i w e_n 1/4 sum over the 4 cells around n of area_c dsigma_c                 (jac_cell's TE term, transposed)
+//     TM  sum over the 4 cells c around n of (1/2 area_c dsigma_c / sigma_c^2) ((h~_n - h~_y)/dy_c^2 + (h~_n - h~_z)/dz_c^2),
+//         h~_y / h~_z the cell's other node on n's row / column, h~ = tm_field_sens    (jac_cell's TM term, transposed)
+//     and -c_{n->b} dbc_b for the Dirichlet neighbours b of n (item_rhs with dbc for the boundary values)
+HD cplx tangent_rhs(const View& v, int s, int iy, int iz) {
+    const bool interior = iz >= 1 && iz <= v.nz - 1 && iy >= 1 && iy <= v.ny - 1;
+    if (!interior || !v.sysOn[s]) return cplx{0, 0};
+    cplx b = cplx{0, 0};
+    if (s < v.nFreq) {
+        double q = 0.0;
+        for (int dz = -1; dz <= 0; ++dz)
+            for (int dy = -1; dy <= 0; ++dy)
+                q += v.yLen[iy + dy] * v.zLen[iz + dz] * v.dSig[(long)(iz + dz) * v.ny + iy + dy];
+        const cplx e = v.X[(long)s * v.vstride + nidx(v, iy, iz)];
+        const double f = v.omega[s] * 0.25 * q;
+        b = cplx{f * e.im, -(f * e.re)};
+    } else {
+        const cplx hn = tm_field_sens(v, s, iy, iz);
+        for (int dz = -1; dz <= 0; ++dz)
+            for (int dy = -1; dy <= 0; ++dy) {
+                const int ky = iy + dy, kz = iz + dz;
+                const double ly = v.yLen[ky], lz = v.zLen[kz], sg = v.sigma[(long)kz * v.ny + ky];
+                const cplx hy = tm_field_sens(v, s, dy ? iy - 1 : iy + 1, iz), hz = tm_field_sens(v, s, iy, dz ? iz - 1 : iz + 1);
+                const double w = 0.5 * ly * lz * v.dSig[(long)kz * v.ny + ky] / (sg * sg);
+                b += w * ((hn - hy) * (1.0 / (ly * ly)) + (hn - hz) * (1.0 / (lz * lz)));
+            }
+    }
+    const int mode = s >= v.nFreq;
+    const long mo = (long)mode * v.vstride, n = nidx(v, iy, iz);
+    cplx acc = cplx{0, 0};
+    if (iy == v.ny - 1) acc += v.cY[mo + n] * dbc_at(v, s, v.ny, iz);
+    if (iy == 1) acc += v.cY[mo + n - 1] * dbc_at(v, s, 0, iz);
+    if (iz == v.nz - 1) acc += v.cZ[mo + n] * dbc_at(v, s, iy, v.nz);
+    return b - acc;
+}
+HD void item_tangent_rhs(const View& v, int s, int iy, int iz) {
+    v.R[(long)s * v.vstride + nidx(v, iy, iz)] = iy <= v.ny ? tangent_rhs(v, s, iy, iz) : cplx{0, 0};
+}
+// --- data side: dZ of functional r of system s (item_src / item_qterm transposed; the tangent field on the side nodes
+//     iy = 0, ny is dbc -- the srcB positions), then every datum of (s, r) by jac_datum, scattered to data order
+HD cplx tangent_field_at(const View& v, int s, int iy, int iz) {
+    const bool interior = iz >= 1 && iz <= v.nz - 1 && iy >= 1 && iy <= v.ny - 1;
+    if (interior) return v.dF[(long)s * v.vstride + nidx(v, iy, iz)];
+    if (iz >= 1 && (iy == 0 || iy == v.ny)) return dbc_at(v, s, iy, iz);
+    return cplx{0, 0};
+}
+HD cplx tangent_dz(const View& v, int s, int r) {
+    const long k = (long)s * v.nRx + r;
+    const int n0 = v.rxN0[k];
+    const cplx* D = v.rxD + k * 11;
+    cplx acc = cplx{0, 0};
+    for (int row = 0; row < 2; ++row)
+        for (int o = 0; o < 4; ++o) {
+            const int iy = n0 + o;
+            if (iy >= 0 && iy <= v.ny) acc += D[row * 4 + o] * tangent_field_at(v, s, iy, v.zid + row);
+        }
+    for (int o = 0; o < 3; ++o) {
+        const int ky = n0 + o;
+        if (ky >= 0 && ky < v.ny) acc += v.dSig[(long)v.zid * v.ny + ky] * D[8 + o];
+    }
+    return acc;
+}
+HD void item_tangent_data(const View& v, int s, int r) {
+    if (!v.sysOn[s]) return;
+    const long k = (long)s * v.nRx + r;
+    if (v.srStart[k] == v.srStart[k + 1]) return;
+    const double up = v.tanScale ? v.tanScale[1] : 1.0;       // (the solve ran on 2^-e dsigma: exact in binary, undone here)
+    const cplx dz = up * tangent_dz(v, s, r), z = v.Zrx[k];
+    for (int t = v.srStart[k]; t < v.srStart[k + 1]; ++t) {
+        const int p = v.srList[t];
+        v.jv[p] = jac_datum(v.datKind[p], z, v.omega[s], dz);
+    }
+}
+// --- J^T u for a free data vector u (compJacTMatVec.jl:8 with datVec = u): item_resid's vbar with u in the place of
+//     W^T W (pred - obs); Re(vbar dZ) is the datum's term of Re(J^T conj(u))
+HD void item_vbar_free(const View& v, int p) {
+    const cplx wr = v.uData[p];
+    const int dk = v.datKind[p];
+    if (dk == 0 || dk == 3) { v.vbar[p] = conj(wr); return; }
+    if (dk == 4) { v.vbar[p] = cplx{wr.re, 0.0}; return; }
+    if (dk == 5) { v.vbar[p] = cplx{0.0, -wr.re}; return; }
+    const int sd = v.datSys[p];
+    const cplx zs = v.Zrx[(long)sd * v.nRx + v.datRx[p]];
+    if (dk == 1) v.vbar[p] = (wr.re * 2.0 / (v.omega[sd] * MU0)) * conj(zs);
+    else {
+        const cplx c = conj(zs);
+        v.vbar[p] = (wr.re * (180.0 / 3.14159265358979323846) / cabs2(zs)) * cplx{c.im, -c.re};
+    }
+}
+// --- final assembly of J^T u for one active cell: item_gradfinal without the residual's chain rule unless wrt = ln sigma
+HD double jtvp_cell(const View& v, int a, int wrt, const double* gPartG, int ngroups, double up = 1.0) {
+    const int cell = v.act[a];
+    const int ky = cell % v.ny, kz = cell / v.ny;
+    double g = 0.0;
+    for (int q = 0; q < ngroups; ++q) g += gPartG[(long)q * v.nCell + cell];
+    for (int s = 0; s < v.S; ++s) g += gradfinal_sys(v, s, ky, kz);
+    if (kz == v.zid)
+        for (int s = 0; s < v.S; ++s) g += v.qPart[(long)s * v.ny + ky];
+    g *= up;                                                  // (up: the power of two vbar was normalised by, undone)
+    return wrt ? exp(v.m[a]) * g : g;
 }
 
 }  // namespace hmcmt

@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_jac.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_jac.h", "kernels_jvp.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -134,6 +134,13 @@ def load_library():
     lib.hmcmt_jacobian.argtypes = [vp, c_double_p, C.c_int64, C.c_int64, C.c_int32, c_double_p, C.POINTER(Stats)]
     lib.hmcmt_jacobian_device.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32, vp, C.POINTER(Stats)]
     lib.hmcmt_sensitivity.argtypes = [vp, c_double_p, C.c_int32, c_double_p, C.POINTER(Stats)]
+    lib.hmcmt_linearize.argtypes = [vp, c_double_p]
+    lib.hmcmt_linearize_device.argtypes = [vp, vp]
+    for name in ("hmcmt_jvp", "hmcmt_jtvp", "hmcmt_gn_hessvec"):
+        getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, c_double_p, C.POINTER(Stats)]
+        getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, vp, C.POINTER(Stats)]
+    for name in JVP_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
@@ -147,8 +154,11 @@ def load_library():
     return lib
 
 
+# matrix-free Jacobian products at a linearisation point
+JVP_SYMBOLS = ["hmcmt_linearize", "hmcmt_linearize_device", "hmcmt_jvp", "hmcmt_jvp_device", "hmcmt_jtvp", "hmcmt_jtvp_device",
+               "hmcmt_gn_hessvec", "hmcmt_gn_hessvec_device"]
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -400,6 +410,57 @@ class HipContext:
         self._check(self.lib.hmcmt_sensitivity(self.h, _dp(m), self._wrt(wrt), _dp(out), C.byref(st)))
         self.jac_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
         return out
+
+    # -- matrix-free Jacobian products at a linearisation point ---------------------------------
+    def linearize(self, m):
+        """Sets the linearisation point of jvp / jtvp / gn_hessvec: a cold forward evaluation at m plus the receiver functionals
+        and boundary sensitivities.  Valid until the next evaluating call or set_options."""
+        self._check(self.lib.hmcmt_linearize(self.h, _dp(self._model(m))))
+
+    def linearize_device(self, d_m):
+        self._check(self.lib.hmcmt_linearize_device(self.h, d_m))
+
+    def _product(self, fn, x, wrt):
+        st = Stats()
+        out = np.empty(self.nAC if fn != "hmcmt_jvp" else 2 * self.nData)
+        self._check(getattr(self.lib, fn)(self.h, _dp(x), self._wrt(wrt), _dp(out), C.byref(st)))
+        self.jvp_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return out
+
+    def _data_vector(self, u):
+        u = np.ascontiguousarray(u, dtype=np.complex128)
+        if u.shape != (self.nData,):
+            raise ValueError("data vector has the wrong length")
+        return u.view(np.float64)
+
+    def jvp(self, v, wrt="sigma"):
+        """J v at the linearisation point (compJacMat(m) @ v, no J): data layout of pred -- complex, real for real data."""
+        out = self._product("hmcmt_jvp", self._model(v), wrt).view(np.complex128)
+        return out.real.copy() if self.args.real_data else out
+
+    def jtvp(self, u, wrt="sigma"):
+        """Re(J^T conj(u)) = real(compJacTMatVec(.., datVec = u, ..)) at the linearisation point: [nAC]."""
+        return self._product("hmcmt_jtvp", self._data_vector(u), wrt)
+
+    def gn_hessvec(self, v, wrt="sigma"):
+        """Gauss-Newton Hessian product Re(J^H W^2 J) v, W = dataW (no prior term): two solves, no stored matrix."""
+        return self._product("hmcmt_gn_hessvec", self._model(v), wrt)
+
+    def _product_device(self, fn, d_in, d_out, wrt):
+        st = Stats()
+        self._check(getattr(self.lib, fn)(self.h, d_in, self._wrt(wrt), d_out, C.byref(st)))
+        self.jvp_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+
+    def jvp_device(self, d_v, d_Jv, wrt="sigma"):
+        """Raw device pointers (ints): v[nAC] -> Jv interleaved complex [nData]."""
+        self._product_device("hmcmt_jvp_device", d_v, d_Jv, wrt)
+
+    def jtvp_device(self, d_u, d_JTu, wrt="sigma"):
+        """Raw device pointers: u interleaved complex [nData] -> [nAC]."""
+        self._product_device("hmcmt_jtvp_device", d_u, d_JTu, wrt)
+
+    def gn_hessvec_device(self, d_v, d_Hv, wrt="sigma"):
+        self._product_device("hmcmt_gn_hessvec_device", d_v, d_Hv, wrt)
 
     # -- prior / leapfrog ---------------------------------------------------------------------
     def set_prior(self, mref, Wm, invM):

@@ -109,6 +109,22 @@ def compJacTMat(mtMesh, mtData, invParam, ctx: HipContext | None = None, wrt="si
     return compJacMat(mtMesh, mtData, invParam, ctx=ctx, wrt=wrt).T
 
 
+def compJacMatVec(mtMesh, mtData, invParam, v, ctx: HipContext | None = None, wrt="sigma"):
+    """compJacMat(m) @ v at m = invParam.strModel without forming J (the tangent-linear route: one solve): the data layout of
+    predData.  Linearises the context at m; further products at the same point: ctx.jvp / ctx.jtvp / ctx.gn_hessvec."""
+    ctx = ctx or get_context(mtMesh, mtData, invParam)
+    ctx.linearize(np.asarray(invParam.strModel, dtype=np.float64))
+    return ctx.jvp(np.asarray(v, dtype=np.float64), wrt=wrt)
+
+
+def compJacTMatVec(mtMesh, mtData, invParam, datVec, ctx: HipContext | None = None, wrt="sigma"):
+    """real(compJacTMatVec(.., datVec, ..)) of the reference (compJacTMatVec.jl:8) for a free data vector: Re(J^T conj(datVec))
+    at m = invParam.strModel, [nAC].  compDataGradient's gradient is exp(m) * compJacTMatVec(.., dataW**2 * (pred - obs))."""
+    ctx = ctx or get_context(mtMesh, mtData, invParam)
+    ctx.linearize(np.asarray(invParam.strModel, dtype=np.float64))
+    return ctx.jtvp(datVec, wrt=wrt)
+
+
 def compDataMisfit(predData, invParam):
     res = invParam.dataW * (predData - invParam.obsData)
     return 0.5 * float(np.real(np.vdot(res, res)))

@@ -28,6 +28,9 @@
  *   hmcmt_leapfrog == proposeLeapfrog (HMCSampler.jl:206-269) with the trajectory kept on the
  *       device, plus the Hamiltonian terms getHamiltonian needs at the proposal.
  *   hmcmt_get_fields: exTE / hxTM of MT2DFwdData (MT2DFwdSolver.jl:44-53), reference node order.
+ *   hmcmt_jacobian == compJacMat / compJacTMat (MTSensitivity/compJacMat.jl, compJacTMat.jl), explicit rows.
+ *   hmcmt_linearize + hmcmt_jvp / hmcmt_jtvp / hmcmt_gn_hessvec: compJacMat(m) * v without J, compJacTMatVec with a free
+ *       datVec (MTSensitivity/compJacTMatVec.jl:8), and the Gauss-Newton product Re(J^H W^2 J) v built from the two.
  */
 #ifndef HMCMT_H
 #define HMCMT_H
@@ -226,6 +229,38 @@ int hmcmt_get_fields(hmcmt_ctx* ctx, int32_t adjoint, double* exTE, double* hxTM
 int hmcmt_jacobian(hmcmt_ctx* ctx, const double* m, int64_t row0, int64_t nrows, int32_t wrt, double* J, hmcmt_stats* st);
 int hmcmt_jacobian_device(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int32_t wrt, double* d_J, hmcmt_stats* st);
 int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens, hmcmt_stats* st);
+
+/* Matrix-free products with the data Jacobian at a linearisation point: J v by the forward (tangent-linear) route, J^T u by the
+ * adjoint route, and the Gauss-Newton Hessian product -- each ONE solve of the live systems per direction, no J anywhere.
+ *   hmcmt_linearize(m)   an evaluation at m that always runs (never answered from the stored results), from a zero guess:
+ *              conductivities, coefficients, forward fields, receiver functionals and the boundary sensitivities -- everything
+ *              hmcmt_grad computes in front of its adjoint solve.  It is an ordinary forward evaluation as far as the context's
+ *              state goes (statistics, evaluation count, hmcmt_get_fields), except that it starts cold: the forward warm-start
+ *              history begins again at m, like after hmcmt_set_options.  The point lives in the context's evaluation arrays and
+ *              stays valid until the next call that evaluates (hmcmt_grad*, hmcmt_forward*, hmcmt_leapfrog*, hmcmt_jacobian*,
+ *              hmcmt_sensitivity, hmcmt_linearize) or hmcmt_set_options.
+ *   wrt        HMCMT_JAC_WRT_SIGMA (d sigma = v; J^T u as it is) or HMCMT_JAC_WRT_LNSIGMA (d sigma = sigma .* v; J^T u times sigma)
+ *   hmcmt_jvp  Jv = compJacMat(m) * v (MTSensitivity/compJacMat.jl:206-314), v[nAC] real, Jv in the layout of pred: interleaved
+ *              complex [nData]; Rho_Pha and RealTZY / ImagTZY data real with zero imaginary parts
+ *   hmcmt_jtvp JTu[nAC] = real(compJacTMatVec(.., datVec = u, ..)) = Re(J^T conj(u)) (MTSensitivity/compJacTMatVec.jl:8) for any
+ *              u in the layout of pred (of real data the real part is read).  hmcmt_grad's gradient is
+ *              exp(m) .* hmcmt_jtvp(dataW^2 (pred - obs), HMCMT_JAC_WRT_SIGMA)
+ *   hmcmt_gn_hessvec   Hv[nAC] = Re(J^H W^2 J) v = jtvp(W^2 jvp(v)), W = dataW, the intermediate kept on the device; no prior term
+ *   st         (may be NULL) the product's own solves, as hmcmt_jacobian reports them: hmcmt_jvp one solve's forward-type
+ *              iterations, hmcmt_jtvp adjoint-type ones, hmcmt_gn_hessvec one of each.  Only the systems that carry data are solved
+ * A product leaves the context's evaluation state as it found it (forward fields, warm-start fields and history, the memo, the
+ * sweep choice and queue tables, the evaluation count, hmcmt_get_stats) and is bitwise repeatable.
+ * HMCMT_EINVAL (hmcmt_last_error says which): no valid linearisation point, a call between hmcmt_grad_device_async and
+ * hmcmt_wait, an unknown wrt, a NULL or non-finite argument; HMCMT_ENOCONV / HMCMT_EBREAKDOWN when the product's solve fails.
+ * The _device twins take device pointers on the context's GPU and are complete on return. */
+int hmcmt_linearize(hmcmt_ctx* ctx, const double* m);
+int hmcmt_linearize_device(hmcmt_ctx* ctx, const double* d_m);
+int hmcmt_jvp(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Jv, hmcmt_stats* st);
+int hmcmt_jtvp(hmcmt_ctx* ctx, const double* u, int32_t wrt, double* JTu, hmcmt_stats* st);
+int hmcmt_gn_hessvec(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Hv, hmcmt_stats* st);
+int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Jv, hmcmt_stats* st);
+int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st);
+int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st);
 
 /* All-gather of the chains' sample blocks over RCCL (xGMI inside a node): one process per GPU, one communicator per
  * process.  Replaces parallelHMCSampler's collection of the workers' results (HMCSampler/parallelHMC.jl:23-45:

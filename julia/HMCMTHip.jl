@@ -26,7 +26,7 @@ using SparseArrays
 using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
-export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
+export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, hipLinearize!, hipGNHessVec, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
        hipWait, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
@@ -207,6 +207,56 @@ function hipSensitivity(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataM
                ctx.ptr, invParam.strModel, jacWrt(wrt), sens, st)
     checkerr(ctx.ptr, rc)
     return sens
+end
+"""
+    hipLinearize!(mtMesh, mtData, invParam)
+
+Sets the linearisation point of the matrix-free Jacobian products at invParam.strModel (hmcmt_linearize): valid until the next
+evaluating call on the context.
+"""
+function hipLinearize!(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel)
+    ctx = getctx(mtMesh, mtData, invParam)
+    checkerr(ctx.ptr, ccall((:hmcmt_linearize, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}), ctx.ptr, invParam.strModel))
+    return ctx
+end
+
+"""
+    compJacMatVec(mtMesh, mtData, invParam, v; wrt=:sigma) -> compJacMat(...) * v (nData) by the tangent-linear route: one solve, no J
+"""
+function compJacMatVec(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel, v::Vector{Float64}; wrt::Symbol=:sigma)
+    ctx = hipLinearize!(mtMesh, mtData, invParam)
+    Jv = Vector{ComplexF64}(undef, ctx.nData)
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_jvp, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Cvoid}, Ref{HmcmtStats}), ctx.ptr, v, jacWrt(wrt), Jv, st)
+    checkerr(ctx.ptr, rc)
+    return ctx.realData ? real.(Jv) : Jv
+end
+
+"""
+    compJacTMatVec(mtMesh, mtData, invParam, datVec; wrt=:sigma) -> real(J^T conj(datVec)) (nAC)
+
+The reference's real(compJacTMatVec(exTE, hxTM, datVec, ...)) (MTSensitivity/compJacTMatVec.jl:8) for a free data vector.
+"""
+function compJacTMatVec(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel, datVec::AbstractVector; wrt::Symbol=:sigma)
+    ctx = hipLinearize!(mtMesh, mtData, invParam)
+    u = Vector{ComplexF64}(datVec)
+    out = Vector{Float64}(undef, ctx.nAC)
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_jtvp, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{HmcmtStats}), ctx.ptr, u, jacWrt(wrt), out, st)
+    checkerr(ctx.ptr, rc)
+    return out
+end
+
+"""
+    hipGNHessVec(mtMesh, mtData, invParam, v; wrt=:sigma) -> Re(J^H W^2 J) v (nAC), W = dataW; no prior term (hmcmt_gn_hessvec)
+"""
+function hipGNHessVec(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel, v::Vector{Float64}; wrt::Symbol=:sigma)
+    ctx = hipLinearize!(mtMesh, mtData, invParam)
+    out = Vector{Float64}(undef, ctx.nAC)
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_gn_hessvec, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{HmcmtStats}), ctx.ptr, v, jacWrt(wrt), out, st)
+    checkerr(ctx.ptr, rc)
+    return out
 end
 jacWrt(wrt::Symbol) = wrt === :sigma ? Int32(0) : wrt === :lnsigma ? Int32(1) : throw(ArgumentError("wrt: :sigma or :lnsigma"))
 
