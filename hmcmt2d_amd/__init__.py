@@ -11,7 +11,7 @@ from .structs import (TensorMesh2D, MTData, HMCPrior, HMCParameter, HMCStatus, I
 from .invsetup import setupInverseDataModel, setActiveElement, compDataWeightMat
 from .fileio import (readEMModel2D, writeEMModel2D, readMT2DData, writeMT2DData, readstartupFile,
                      outputHMCSamples, getPosteriorModel)
-from .sampler import (compDataGradient, compDataMisfit, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, getHamiltonian, proposeLeapfrog, proposeLeapfrogDevice,
+from .sampler import (compDataGradient, compDataMisfit, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, getHamiltonian, proposeLeapfrog, proposeLeapfrogDevice,
                       runHMCSampler,
                       parallelHMCSampler, getKineticEnergy, getKineticGradient, getMomentumVector,
                       setMassMatrix, checkParameterBound, get_context, release_context)

@@ -61,6 +61,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_mass.h"
 #include "kernels_jac.h"
 #include "kernels_jvp.h"
+#include "kernels_jvp_block.h"
 
 // an instantiation of the persistent solve kernel (g_psKernels, launch_persist): k_cocg_persist<cw, sw, mw, cs, nyk, st> (two
 // halves) or k_cocg_persist4<cw, sw, 32, nyk, 4, st> (four strips), strips x cw threads per workgroup
@@ -284,7 +285,30 @@ struct hmcmt_ctx {
         double *m = nullptr, *vin = nullptr, *dSig = nullptr, *out = nullptr, *gPartG = nullptr, *qPart = nullptr, *misfit = nullptr;
         double* scale = nullptr;           // [4] power-of-two normalisation of the tangent's / the adjoint's input (k_jvp_norm)
         cplx *dbcL = nullptr, *dbcR = nullptr, *dbcB = nullptr, *jv = nullptr, *u = nullptr, *vbar = nullptr, *rxCoef = nullptr;
+        long long gen = 0;                 // serial number of the linearisation points (the block products' replicated pivots belong to one)
     } jvp;
+    // block products (hmcmt_*_block, kernels_jvp_block.h): a second solver instance over nvec * S virtual systems -- its own
+    // per-system arrays, sync words, records and constant block -- and the products' work arrays per direction.  Allocated by the
+    // first block call, grown to the largest nvec seen, released at hmcmt_destroy (its own list: growing frees the smaller set)
+    struct Blk {
+        int cap = 0;                       // directions the arrays hold (0: none yet)
+        long long gen = -1; int genVec = 0;   // the linearisation point and nvec the replicated pivots were made for
+        std::vector<void*> allocs, hostAllocs;
+        Solver sv{};
+        cplx *lam = nullptr, *invp = nullptr, *d_b = nullptr, *d_sw = nullptr;
+        float2 *invp32 = nullptr, *yhat2 = nullptr;
+        double *omega = nullptr, *partZZ = nullptr, *partRes = nullptr, *partBn = nullptr;
+        unsigned* psync = nullptr; size_t psyncBytes = 0; int slots = 0;
+        u4v* prec = nullptr;
+        PsConst* psConst = nullptr; PsConst psShadow{}; bool psConstValid = false;
+        double *h_rec = nullptr, *d_recHost = nullptr;
+        int *h_onV = nullptr, *d_onVHost = nullptr;   // mapped: [cap S] the virtual systems solved, as k_blk_flags wrote them
+        int *dirOn = nullptr, *sysOnDir = nullptr, *sysOnV = nullptr;
+        // work arrays per direction (the single product's, [cap] times)
+        double *vin = nullptr, *out = nullptr, *dSig = nullptr, *gPartG = nullptr, *qPart = nullptr, *scale = nullptr;
+        cplx *dbcL = nullptr, *dbcR = nullptr, *dbcB = nullptr, *jv = nullptr, *u = nullptr, *vbar = nullptr, *rxCoef = nullptr;
+        cplx *srcB = nullptr, *wL = nullptr, *wR = nullptr, *colw = nullptr, *gL = nullptr, *gR = nullptr;
+    } blk;
 };
 
 static thread_local std::string g_createError;      // (per thread: contexts of different chains are created from different threads)
@@ -1661,6 +1685,8 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
         hipFree(ctx->sv.stamps);
     }
     for (void* p : ctx->allocs) hipFree(p);
+    for (void* p : ctx->blk.allocs) hipFree(p);
+    for (void* p : ctx->blk.hostAllocs) hipHostFree(p);
     for (hipEvent_t e : ctx->evPool) hipEventDestroy(e);
     if (ctx->h_nactive) hipHostFree(ctx->h_nactive);
     if (ctx->h_stall) hipHostFree(ctx->h_stall);
@@ -3608,6 +3634,7 @@ static int linearize_run(hmcmt_ctx* ctx) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(strm));
     P.valid = true;
+    ++P.gen;
     return 0;
 }
 
@@ -3619,7 +3646,8 @@ static int linearize_check(hmcmt_ctx* ctx, const void* m) {
 
 // one solve of a product: `fill` writes the right-hand side (again after a timed-out persistent launch, which destroys it);
 // sparseRow >= 0: the adjoint's sparse start on node rows sparseRow, sparseRow + 1 where the persistent kernel starts the solve
-static int prod_solve(hmcmt_ctx* ctx, cplx* x, int kind, int sweeps, int sparseRow, const std::function<void(bool)>& fill, hmcmt_stats& st) {
+static int prod_solve(hmcmt_ctx* ctx, cplx* x, int kind, int sweeps, int sparseRow, const std::function<void(bool)>& fill, hmcmt_stats& st,
+                      const int* on = nullptr /* [ctx->v.S] the systems solved (null: the problem's) */) {
     hipStream_t strm = ctx->stream;
     const size_t vecBytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     for (int attempt = 0;; ++attempt) {
@@ -3647,7 +3675,7 @@ static int prod_solve(hmcmt_ctx* ctx, cplx* x, int kind, int sweeps, int sparseR
         break;
     }
     HIPCHK(hipStreamSynchronize(strm));
-    jac_records(ctx, kind, ctx->hp.sysOn.data(), st);
+    jac_records(ctx, kind, on ? on : ctx->hp.sysOn.data(), st);
     if (ctx->solveFail || !ctx->solveDone[kind]) {
         if (st.status == 0) st.status = ctx->solveFail ? ctx->solveFail : HMCMT_ENOCONV;
         const char* which = kind == 0 ? "tangent" : "adjoint";
@@ -3808,5 +3836,302 @@ int hmcmt_gn_hessvec(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Hv, h
 int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Jv, hmcmt_stats* st) { return prod_device(ctx, PROD_JVP, d_v, wrt, d_Jv, st); }
 int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st) { return prod_device(ctx, PROD_JTVP, d_u, wrt, d_JTu, st); }
 int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st) { return prod_device(ctx, PROD_GN, d_v, wrt, d_Hv, st); }
+
+// ----------------------------------------------------------------------------------------------
+// block products (kernels_jvp_block.h): nvec directions, ONE solve() per route over the nvec * S virtual systems.  The solve runs
+// on a second solver instance (hmcmt_ctx::Blk): the context's Solver with S and nFreq multiplied by nvec, the frequency list and
+// the inverse pivots repeated per direction, per-system arrays, sync words, reduction records, constant block and host records of
+// its own; the stencil coefficients and eigen-transforms are per mode and shared.  It is put in the context's place for the call
+// (BlkSwap, inside the Jacobian's save / restore bracket), so solve(), the kernel table and the fallbacks see an ordinary problem.
+// ----------------------------------------------------------------------------------------------
+static void blk_release(hmcmt_ctx* ctx) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    for (void* p : B.allocs) hipFree(p);
+    for (void* p : B.hostAllocs) hipHostFree(p);
+    B = hmcmt_ctx::Blk{};
+}
+static int blk_dalloc(hmcmt_ctx* ctx, void** p, size_t bytes) {       // (zeroed, on the block instance's own list)
+    void* q = nullptr;
+    bytes = std::max<size_t>(bytes, 16);
+    HIPCHK(hipMalloc(&q, bytes));
+    ctx->blk.allocs.push_back(q);
+    HIPCHK(hipMemsetAsync(q, 0, bytes, ctx->stream));
+    *p = q;
+    return 0;
+}
+static int blk_alloc_impl(hmcmt_ctx* ctx, int nvec) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    const View& v = ctx->v;
+    const size_t K = (size_t)nvec, S = (size_t)v.S, SV = K * S, VS = (size_t)v.vstride;
+    Solver& k = B.sv;
+    k = ctx->sv;                                         // (tile shapes, launch-invariant pointers, the per-mode coefficients)
+    k.S = (int)SV; k.nFreq = nvec * v.nFreq;
+    k.cntActive = nullptr;
+    int rc = 0;
+#define BA(ptr, n) { void* q_ = nullptr; if ((rc = blk_dalloc(ctx, &q_, (size_t)(n) * sizeof(*(ptr))))) return rc; (ptr) = reinterpret_cast<decltype(ptr)>(q_); }
+    BA(B.omega, SV) BA(B.invp, SV * VS) BA(B.invp32, SV * VS) BA(B.lam, SV * VS) BA(k.r, SV * VS) BA(B.d_b, SV * VS) BA(B.d_sw, SV * VS)
+    BA(k.p, SV * VS) BA(k.q, SV * VS) BA(k.z, SV * VS) BA(k.y, SV * VS) BA(k.t, SV * VS) BA(k.dinv, SV * VS)
+    BA(k.t32, SV * VS + 64) BA(k.y32, SV * VS + 64)
+    BA(k.z32, SV * VS) BA(k.p32a, SV * VS) BA(k.p32b, SV * VS) BA(k.zs32, SV * VS) BA(k.z4_32, SV * VS) BA(k.t2_32, SV * VS) BA(k.partR, SV * MAXNB) BA(k.dinv32, SV * VS)
+    BA(k.p2, SV * VS) BA(k.r2, SV * VS) BA(k.partPQ, SV * MAXNB) BA(k.rho2, 2 * SV)
+    BA(k.partA, SV * MAXNB) BA(k.partB, SV * MAXNB) BA(B.partZZ, SV * MAXNB) BA(B.partRes, SV * MAXNB) BA(B.partBn, SV * MAXNB)
+    BA(k.rho, SV) BA(k.alphaBeta, SV) BA(k.active, SV) BA(k.iters, SV) BA(k.status, SV) BA(k.nactive, 1) BA(k.errEst, SV) BA(k.errRef, SV) BA(k.errRefIt, SV)
+    BA(B.dirOn, K) BA(B.sysOnDir, SV) BA(B.sysOnV, SV)
+    BA(B.vin, K * v.nAC) BA(B.out, K * v.nAC) BA(B.dSig, K * v.nCell) BA(B.gPartG, K * 2 * GRAD_NG * v.nCell) BA(B.qPart, SV * v.ny) BA(B.scale, 4 * K)
+    BA(B.dbcL, SV * v.nz) BA(B.dbcR, SV * v.nz) BA(B.dbcB, SV * (v.ny + 1)) BA(B.jv, K * v.nData) BA(B.u, K * v.nData) BA(B.vbar, K * v.nData) BA(B.rxCoef, SV * v.nRx)
+    BA(B.srcB, SV * 4) BA(B.wL, SV * v.nz) BA(B.wR, SV * v.nz) BA(B.colw, SV * v.ny) BA(B.gL, SV * v.nz) BA(B.gR, SV * v.nz)
+    k.omega = B.omega; k.invp = B.invp; k.invp32 = B.invp32;
+    // the persistent kernel's own words for this instance (persist_setup): more system slots where the share has the CUs for them;
+    // its 32-bit lane offsets carry the system's element offset, so a block beyond 2^27 elements runs the launch-per-phase loop
+    if (ctx->persistCW > 0 && SV * VS < ((size_t)1 << 27)) {
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
+        const int cuPerXcd = prop.multiProcessorCount / 8 / std::max(ctx->shareCnt, 1);
+        B.slots = std::max(1, std::min((int)((SV + 7) / 8), cuPerXcd / std::max(ctx->persistG, 1)));
+        B.psyncBytes = ((size_t)(32 * 8 * B.slots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
+        unsigned char* ps = nullptr; BA(ps, B.psyncBytes) B.psync = reinterpret_cast<unsigned*>(ps);
+        unsigned char* pr = nullptr; BA(pr, SV * MAXNB * 2 * 8 * 16) B.prec = reinterpret_cast<u4v*>(pr);
+        unsigned char* pc = nullptr; BA(pc, sizeof(PsConst)) B.psConst = reinterpret_cast<PsConst*>(pc);
+        if (ctx->persistCS > 1) BA(B.yhat2, SV * VS)
+    }
+#undef BA
+    HIPCHK(hipHostMalloc((void**)&B.h_rec, sizeof(double) * 4 * SV, hipHostMallocMapped));
+    B.hostAllocs.push_back(B.h_rec);
+    HIPCHK(hipHostGetDevicePointer((void**)&B.d_recHost, B.h_rec, 0));
+    HIPCHK(hipHostMalloc((void**)&B.h_onV, sizeof(int) * SV, hipHostMallocMapped));
+    B.hostAllocs.push_back(B.h_onV);
+    HIPCHK(hipHostGetDevicePointer((void**)&B.d_onVHost, B.h_onV, 0));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    B.cap = nvec;
+    return 0;
+}
+static int blk_alloc(hmcmt_ctx* ctx, int nvec) {
+    if (ctx->blk.cap >= nvec) return 0;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    blk_release(ctx);
+    const int rc = blk_alloc_impl(ctx, nvec);
+    if (rc) {                                            // (out of memory: nothing of the block instance is kept, the context goes on)
+        const std::string e = ctx->err;
+        (void)hipStreamSynchronize(ctx->stream);
+        blk_release(ctx);
+        (void)hipGetLastError();
+        ctx->err = "block Jacobian product: " + e;
+    }
+    return rc;
+}
+
+// what the block instance replaces in the context beside View / Solver (JacState), and puts back
+struct BlkSwap {
+    double *partZZ, *partRes, *partBn, *h_rec, *d_recHost;
+    cplx *d_b, *d_sw;
+    float2 *invp32, *yhat2;
+    unsigned* psync; size_t psyncBytes; int slots, persistCW;
+    u4v* prec;
+    PsConst* psConst; PsConst shadow; bool constValid, dinvValid;
+};
+static void blk_swap_in(hmcmt_ctx* c, BlkSwap& t) {
+    hmcmt_ctx::Blk& B = c->blk;
+    t.partZZ = c->d_partZZ; t.partRes = c->d_partRes; t.partBn = c->d_partBn; t.h_rec = c->h_rec; t.d_recHost = c->d_recHost;
+    t.d_b = c->d_b; t.d_sw = c->d_sw; t.invp32 = c->d_invp32; t.yhat2 = c->d_yhat2;
+    t.psync = c->d_psync; t.psyncBytes = c->psyncBytes; t.slots = c->persistSlots; t.persistCW = c->persistCW;
+    t.prec = c->d_prec; t.psConst = c->d_psConst; t.shadow = c->psShadow; t.constValid = c->psConstValid; t.dinvValid = c->dinvValid;
+    c->d_partZZ = B.partZZ; c->d_partRes = B.partRes; c->d_partBn = B.partBn; c->h_rec = B.h_rec; c->d_recHost = B.d_recHost;
+    c->d_b = B.d_b; c->d_sw = B.d_sw; c->d_invp32 = B.invp32; c->d_yhat2 = B.yhat2;
+    if (B.psync) { c->d_psync = B.psync; c->psyncBytes = B.psyncBytes; c->persistSlots = B.slots; c->d_prec = B.prec; c->d_psConst = B.psConst; }
+    else c->persistCW = 0;                               // (no persistent kernel for this block: persist_ok)
+    c->psShadow = B.psShadow; c->psConstValid = B.psConstValid;
+    c->dinvValid = false;                                // (the instance's Jacobi diagonals: written where a launch-per-phase kernel needs them)
+}
+static void blk_swap_out(hmcmt_ctx* c, const BlkSwap& t) {
+    hmcmt_ctx::Blk& B = c->blk;
+    B.psShadow = c->psShadow; B.psConstValid = c->psConstValid;
+    c->d_partZZ = t.partZZ; c->d_partRes = t.partRes; c->d_partBn = t.partBn; c->h_rec = t.h_rec; c->d_recHost = t.d_recHost;
+    c->d_b = t.d_b; c->d_sw = t.d_sw; c->d_invp32 = t.invp32; c->d_yhat2 = t.yhat2;
+    c->d_psync = t.psync; c->psyncBytes = t.psyncBytes; c->persistSlots = t.slots; c->persistCW = t.persistCW;
+    c->d_prec = t.prec; c->d_psConst = t.psConst; c->psShadow = t.shadow; c->psConstValid = t.constValid; c->dinvValid = t.dinvValid;
+}
+
+// the directions k_blk_norm found not identically zero -> the system flags by direction and by virtual system, made on the device
+// (k_blk_flags); the host reads the flags by virtual system from mapped memory.  One synchronisation, no copy.
+static int blk_systems(hmcmt_ctx* ctx, const int* d_realOn, int S, int nvec, int& nOn) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    const int n = nvec * S;
+    hipLaunchKernelGGL(k_blk_flags, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const int*)B.dirOn, d_realOn, B.sysOnDir, B.sysOnV, B.d_onVHost, S / 2, nvec);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    nOn = 0;
+    for (int i = 0; i < n; ++i) nOn += B.h_onV[i];
+    ctx->nSysOn = nOn;
+    return 0;
+}
+
+// J V -> vr.jv (d_V: device, [nvec][nAC]); vr: the REAL problem's View on the block's work arrays (kernels_jvp_block.h)
+static int blk_tangent(hmcmt_ctx* ctx, View vr, const int* d_realOn, const double* d_V, int nvec, int wrt, int sweeps, hmcmt_stats& st, int& nOn) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    hipStream_t strm = ctx->stream;
+    const int S = vr.S;
+    vr.tanV = d_V;
+    HIPCHK(hipMemsetAsync(vr.jv, 0, sizeof(cplx) * (size_t)nvec * vr.nData, strm));
+    hipLaunchKernelGGL(k_blk_dsig, dim3((vr.nCell + 255) / 256, nvec), dim3(256), 0, strm, vr, wrt, nvec);
+    hipLaunchKernelGGL(k_blk_norm, dim3(nvec), dim3(1024), 0, strm, vr.dSig, (const double*)vr.sigma, (long)vr.nCell, (long)vr.nCell, B.scale, 0, B.dirOn);
+    if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
+    if (nOn == 0) return 0;                              // (every direction zero: J V = 0 stands)
+    hipLaunchKernelGGL(k_blk_dbc, dim3((2 * vr.nz + vr.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S, (nvec + BLK_KB - 1) / BLK_KB), dim3(64 * DBC_WAVES), 0, strm, vr, nvec);
+    auto fill = [&](bool) {
+        hipLaunchKernelGGL(k_blk_rhs, dim3((unsigned)((vr.vstride + 255) / 256), S, nvec), dim3(256), 0, strm, vr, nvec);
+    };
+    if (int rc = prod_solve(ctx, B.lam, 0, sweeps, -1, fill, st, B.h_onV)) return rc;
+    hipLaunchKernelGGL(k_blk_data, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Re(J^T conj(U)) -> d_out (d_U: device, complex [nvec][nData]; d_out: device, [nvec][nAC])
+static int blk_adjoint(hmcmt_ctx* ctx, View vr, const int* d_realOn, const cplx* d_U, int nvec, int wrt, int sweeps, double* d_out, hmcmt_stats& st, int& nOn) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    hipStream_t strm = ctx->stream;
+    const int S = vr.S;
+    vr.uData = d_U;
+    hipLaunchKernelGGL(k_blk_vbar, grid1(vr.nData, 256), dim3(256), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_blk_norm, dim3(nvec), dim3(1024), 0, strm, reinterpret_cast<double*>(vr.vbar), (const double*)nullptr, 2l * vr.nData, 2l * vr.nData, B.scale, 2, B.dirOn);
+    if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
+    if (nOn == 0) { HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)nvec * vr.nAC, strm)); return 0; }
+    hipLaunchKernelGGL(k_blk_rxcoef, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
+    const int nsrc = (2 * (vr.ny + 1) + 127) / 128;
+    const size_t vecBytes = (size_t)nvec * S * vr.vstride * sizeof(cplx);
+    auto fill = [&](bool sparse) {
+        if (!sparse) (void)hipMemsetAsync(vr.R, 0, vecBytes, strm);           // (the whole right-hand side is the residual)
+        hipLaunchKernelGGL(k_blk_src, dim3(nsrc + (vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nsrc, nvec);
+    };
+    if (int rc = prod_solve(ctx, B.lam, 1, sweeps, vr.zid, fill, st, B.h_onV)) return rc;
+    hipLaunchKernelGGL(k_blk_wb, dim3((vr.nz + vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_blk_contract, dim3((BCC_L * vr.nz + 127) / 128, 2 * ((nvec + BLK_KB - 1) / BLK_KB), S), dim3(128), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_blk_gradcell, dim3((vr.nCell + 127) / 128, 2 * GRAD_NG, nvec), dim3(128), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_blk_final, grid1(vr.nAC, 128), dim3(128), 0, strm, vr, wrt, d_out, nvec);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int blk_run(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int wrt, double* d_out, hmcmt_stats* stOut) {
+    hmcmt_ctx::Jvp& P = ctx->jvp;
+    hmcmt_ctx::Blk& B = ctx->blk;
+    hipStream_t strm = ctx->stream;
+    hmcmt_stats st{};
+    // the inverse pivots of the linearisation point, per direction (again after a new point, or for more directions)
+    if (B.gen != P.gen || B.genVec != nvec) {
+        const unsigned gx = (unsigned)std::min<long>(64, (ctx->v.vstride + 255) / 256);
+        hipLaunchKernelGGL(k_blk_replicate, dim3(gx, ctx->v.S, nvec), dim3(256), 0, strm, (const cplx*)ctx->v.invp, (const float2*)ctx->d_invp32,
+                           B.invp, B.invp32, ctx->v.nFreq, nvec, ctx->v.vstride);
+        HIPCHK(hipGetLastError());
+        if (B.genVec != nvec) {                          // the frequency list, repeated per direction
+            const int nF = ctx->v.nFreq;
+            std::vector<double> om((size_t)nvec * 2 * nF);
+            for (int j = 0; j < nvec; ++j)
+                for (int f = 0; f < nF; ++f) {
+                    om[(size_t)j * nF + f] = ctx->hp.omega[f];
+                    om[((size_t)nvec + j) * nF + f] = ctx->hp.omega[nF + f];
+                }
+            HIPCHK(hipStreamSynchronize(strm));
+            HIPCHK(hipMemcpy(B.omega, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice));
+        }
+        B.gen = P.gen; B.genVec = nvec;
+    }
+    JacState saved;
+    jac_save(ctx, saved);
+    BlkSwap swapped;
+    blk_swap_in(ctx, swapped);
+    auto leave = [&](int rc) {
+        const std::string e = ctx->err;
+        (void)hipStreamSynchronize(strm);
+        blk_swap_out(ctx, swapped);
+        jac_restore(ctx, saved);
+        ctx->err = e;
+        if (stOut) *stOut = st;
+        return rc;
+    };
+    // no guard, no sampled profiling, no test hooks, no leapfrog update in the products' solves
+    ctx->guardEvery = 0; ctx->profMask = 0; ctx->dbgFlags = 0;
+    ctx->lfStep.on = 0; ctx->lfMom.on = 0;
+    ctx->stats = hmcmt_stats{};
+    ctx->psOrder[0].clear(); ctx->psOrder[1].clear();    // (the queue tables are the context's problem's: the kernel's own order here)
+    // the REAL problem's View on the block's work arrays, for the products' kernels ...
+    View vr = ctx->v;
+    const int* d_realOn = ctx->v.sysOn;                  // (the problem's own flags, [S])
+    vr.m = P.m; vr.gate = nullptr; vr.ticks = nullptr; vr.dbg = 0;
+    vr.dSig = B.dSig; vr.dbcL = B.dbcL; vr.dbcR = B.dbcR; vr.dbcB = B.dbcB;
+    vr.vbar = B.vbar; vr.rxCoef = B.rxCoef; vr.qPart = B.qPart; vr.gPartG = B.gPartG;
+    vr.srcB = B.srcB; vr.wL = B.wL; vr.wR = B.wR; vr.colw = B.colw; vr.gL = B.gL; vr.gR = B.gR;
+    vr.R = B.sv.r; vr.Lam = B.lam; vr.dF = B.lam; vr.tanScale = B.scale; vr.sysOn = B.sysOnDir;
+    vr.tanV = B.vin; vr.uData = B.u;
+    vr.jv = what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : B.jv;
+    // ... and the virtual problem in the context's place, for solve()
+    ctx->sv = B.sv;
+    ctx->v.S = nvec * vr.S; ctx->v.nFreq = nvec * vr.nFreq; ctx->v.omega = B.omega; ctx->v.invp = B.invp; ctx->v.sysOn = B.sysOnV;
+    ctx->v.Lam = B.lam; ctx->v.R = B.sv.r;
+    if (B.psync) ctx->persistSlots = std::max(1, std::min(B.slots, (ctx->v.S + 7) / 8));
+    ctx->sv.S = ctx->v.S; ctx->sv.nFreq = ctx->v.nFreq;  // (arrays of the largest block seen, this call's count of systems)
+    const int sweeps = (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2;    // (cold solves: well above the two-sweep threshold)
+    int rc = 0, nOn = 0;
+    if (what == PROD_JVP || what == PROD_GN) {
+        if ((rc = blk_tangent(ctx, vr, d_realOn, d_in, nvec, wrt, sweeps, st, nOn))) return leave(rc);
+        st.nsystems = nOn;
+        st.smoother_sweeps = 10 * sweeps;
+    }
+    if (what == PROD_GN) hipLaunchKernelGGL(k_blk_w2, grid1(vr.nData, 256), dim3(256), 0, strm, vr, B.u, nvec);
+    if (what == PROD_JTVP || what == PROD_GN) {
+        const cplx* u = what == PROD_GN ? B.u : reinterpret_cast<const cplx*>(d_in);
+        if ((rc = blk_adjoint(ctx, vr, d_realOn, u, nvec, wrt, sweeps, d_out, st, nOn))) return leave(rc);
+        if (what == PROD_JTVP) st.nsystems = nOn;
+        st.smoother_sweeps += sweeps;
+    }
+    return leave(0);
+}
+
+static int blk_check(hmcmt_ctx* ctx, const void* in, int32_t nvec, int32_t wrt, const void* out) {
+    if (nvec < 1 || nvec > HMCMT_BLOCK_MAX) { ctx->err = "block Jacobian product: nvec must be 1 .. HMCMT_BLOCK_MAX (32)"; return HMCMT_EINVAL; }
+    return prod_check(ctx, in, wrt, out);
+}
+// a block of one direction IS the single product (the contract defines direction j as the single call's result): the same code,
+// no second solver instance, no flags to read back.  A zero right-hand side leaves the solve at iteration 0 there as well.
+static int blk_single_stats(hmcmt_ctx* ctx, int rc, hmcmt_stats* st) {
+    if (st) st->nsystems = ctx->nSysOn;                  // (the block's count: the systems that carry data)
+    return rc;
+}
+static int blk_host(hmcmt_ctx* ctx, int what, const double* in, int32_t nvec, int32_t wrt, double* out, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = blk_check(ctx, in, nvec, wrt, out)) return rc;
+    if (nvec == 1) return blk_single_stats(ctx, prod_host(ctx, what, in, wrt, out, st), st);
+    const int nAC = ctx->v.nAC, nData = ctx->v.nData;
+    const bool inData = what == PROD_JTVP, outData = what == PROD_JVP;
+    const size_t nin = (size_t)nvec * (inData ? 2 * (size_t)nData : (size_t)nAC), nout = (size_t)nvec * (outData ? 2 * (size_t)nData : (size_t)nAC);
+    for (size_t i = 0; i < nin; ++i)
+        if (!std::isfinite(in[i])) { ctx->err = "block Jacobian product: non-finite input value"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = blk_alloc(ctx, nvec)) return rc;
+    hmcmt_ctx::Blk& B = ctx->blk;
+    // (staging: U in B.u, V in B.vin; J V comes back through B.u, the cell vectors through B.out)
+    double* d_in = inData ? reinterpret_cast<double*>(B.u) : B.vin;
+    double* d_out = outData ? reinterpret_cast<double*>(B.u) : B.out;
+    HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin, hipMemcpyHostToDevice, ctx->stream));
+    int rc = blk_run(ctx, what, d_in, nvec, wrt, d_out, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+static int blk_device(hmcmt_ctx* ctx, int what, const double* d_in, int32_t nvec, int32_t wrt, double* d_out, hmcmt_stats* st) {
+    if (!ctx) return HMCMT_EINVAL;
+    if (int rc = blk_check(ctx, d_in, nvec, wrt, d_out)) return rc;
+    if (nvec == 1) return blk_single_stats(ctx, prod_device(ctx, what, d_in, wrt, d_out, st), st);
+    HIPCHK(hipSetDevice(ctx->device));
+    if (int rc = blk_alloc(ctx, nvec)) return rc;
+    return blk_run(ctx, what, d_in, nvec, wrt, d_out, st);
+}
+int hmcmt_jvp_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* JV, hmcmt_stats* st) { return blk_host(ctx, PROD_JVP, V, nvec, wrt, JV, st); }
+int hmcmt_jtvp_block(hmcmt_ctx* ctx, const double* U, int32_t nvec, int32_t wrt, double* JTU, hmcmt_stats* st) { return blk_host(ctx, PROD_JTVP, U, nvec, wrt, JTU, st); }
+int hmcmt_gn_hessvec_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* HV, hmcmt_stats* st) { return blk_host(ctx, PROD_GN, V, nvec, wrt, HV, st); }
+int hmcmt_jvp_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_JV, hmcmt_stats* st) { return blk_device(ctx, PROD_JVP, d_V, nvec, wrt, d_JV, st); }
+int hmcmt_jtvp_block_device(hmcmt_ctx* ctx, const double* d_U, int32_t nvec, int32_t wrt, double* d_JTU, hmcmt_stats* st) { return blk_device(ctx, PROD_JTVP, d_U, nvec, wrt, d_JTU, st); }
+int hmcmt_gn_hessvec_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_HV, hmcmt_stats* st) { return blk_device(ctx, PROD_GN, d_V, nvec, wrt, d_HV, st); }
 
 }  // extern "C"

@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_jac.h", "kernels_jvp.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_jac.h", "kernels_jvp.h", "kernels_jvp_block.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -139,6 +139,9 @@ def load_library():
     for name in ("hmcmt_jvp", "hmcmt_jtvp", "hmcmt_gn_hessvec"):
         getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, c_double_p, C.POINTER(Stats)]
         getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, vp, C.POINTER(Stats)]
+    for name in ("hmcmt_jvp_block", "hmcmt_jtvp_block", "hmcmt_gn_hessvec_block"):
+        getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(Stats)]
+        getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(Stats)]
     for name in JVP_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
@@ -156,7 +159,10 @@ def load_library():
 
 # matrix-free Jacobian products at a linearisation point
 JVP_SYMBOLS = ["hmcmt_linearize", "hmcmt_linearize_device", "hmcmt_jvp", "hmcmt_jvp_device", "hmcmt_jtvp", "hmcmt_jtvp_device",
-               "hmcmt_gn_hessvec", "hmcmt_gn_hessvec_device"]
+               "hmcmt_gn_hessvec", "hmcmt_gn_hessvec_device",
+               "hmcmt_jvp_block", "hmcmt_jvp_block_device", "hmcmt_jtvp_block", "hmcmt_jtvp_block_device",
+               "hmcmt_gn_hessvec_block", "hmcmt_gn_hessvec_block_device"]
+BLOCK_MAX = 32      # include/hmcmt.h: HMCMT_BLOCK_MAX
 # include/hmcmt.h: the drop-in boundary
 PRODUCT_SYMBOLS = JVP_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
@@ -461,6 +467,62 @@ class HipContext:
 
     def gn_hessvec_device(self, d_v, d_Hv, wrt="sigma"):
         self._product_device("hmcmt_gn_hessvec_device", d_v, d_Hv, wrt)
+
+    # -- block products: several directions per solve -------------------------------------------
+    @staticmethod
+    def block_input(X, width, single, complex_in=False):
+        """A block of directions as a C-ordered (nvec, width) array of float64 (complex128 for data vectors); needs no device.
+        A 1-D input is refused: the single-direction method is the one for it."""
+        if isinstance(X, np.ndarray) and X.dtype.kind not in "fiuc":
+            raise TypeError(f"block of directions: a numeric array, not dtype {X.dtype}")
+        X = np.asarray(X)
+        if X.dtype.kind not in "fiuc" or (X.dtype.kind == "c" and not complex_in):
+            raise TypeError(f"block of directions: {'real or complex' if complex_in else 'real'} numbers, not dtype {X.dtype}")
+        if X.ndim == 1:
+            raise ValueError(f"block of directions: a 2-D array (nvec, {width}); for one direction use {single}")
+        if X.ndim != 2 or X.shape[1] != width:
+            raise ValueError(f"block of directions: shape (nvec, {width}), not {X.shape}")
+        if not 1 <= X.shape[0] <= BLOCK_MAX:
+            raise ValueError(f"block of directions: nvec = {X.shape[0]}, need 1 .. {BLOCK_MAX}")
+        return np.ascontiguousarray(X, dtype=np.complex128 if complex_in else np.float64)
+
+    def _product_block(self, fn, X, wrt, nout):
+        st = Stats()
+        nvec = X.shape[0]
+        out = np.empty((nvec, nout))
+        self._check(getattr(self.lib, fn)(self.h, _dp(X.view(np.float64)), nvec, self._wrt(wrt), _dp(out), C.byref(st)))
+        self.block_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+        return out
+
+    def jvp_block(self, V, wrt="sigma"):
+        """J V at the linearisation point for the rows of V (nvec, nAC), ONE forward-type solve for all of them: (nvec, nData),
+        complex, real for real data.  Row j is jvp(V[j])."""
+        out = self._product_block("hmcmt_jvp_block", self.block_input(V, self.nAC, "jvp"), wrt, 2 * self.nData).view(np.complex128)
+        return out.real.copy() if self.args.real_data else out
+
+    def jtvp_block(self, U, wrt="sigma"):
+        """Re(J^T conj(U_j)) for the rows of U (nvec, nData), ONE adjoint-type solve: (nvec, nAC)."""
+        return self._product_block("hmcmt_jtvp_block", self.block_input(U, self.nData, "jtvp", complex_in=True), wrt, self.nAC)
+
+    def gn_hessvec_block(self, V, wrt="sigma"):
+        """Re(J^H W^2 J) V for the rows of V (nvec, nAC): one solve of each type, the intermediate kept on the device."""
+        return self._product_block("hmcmt_gn_hessvec_block", self.block_input(V, self.nAC, "gn_hessvec"), wrt, self.nAC)
+
+    def _product_block_device(self, fn, d_in, nvec, d_out, wrt):
+        st = Stats()
+        self._check(getattr(self.lib, fn)(self.h, d_in, int(nvec), self._wrt(wrt), d_out, C.byref(st)))
+        self.block_stats = {f: getattr(st, f) for f, _ in Stats._fields_}
+
+    def jvp_block_device(self, d_V, nvec, d_JV, wrt="sigma"):
+        """Raw device pointers (ints): V [nvec][nAC] -> JV interleaved complex [nvec][nData]."""
+        self._product_block_device("hmcmt_jvp_block_device", d_V, nvec, d_JV, wrt)
+
+    def jtvp_block_device(self, d_U, nvec, d_JTU, wrt="sigma"):
+        """Raw device pointers: U interleaved complex [nvec][nData] -> [nvec][nAC]."""
+        self._product_block_device("hmcmt_jtvp_block_device", d_U, nvec, d_JTU, wrt)
+
+    def gn_hessvec_block_device(self, d_V, nvec, d_HV, wrt="sigma"):
+        self._product_block_device("hmcmt_gn_hessvec_block_device", d_V, nvec, d_HV, wrt)
 
     # -- prior / leapfrog ---------------------------------------------------------------------
     def set_prior(self, mref, Wm, invM):

@@ -125,6 +125,25 @@ def compJacTMatVec(mtMesh, mtData, invParam, datVec, ctx: HipContext | None = No
     return ctx.jtvp(datVec, wrt=wrt)
 
 
+def compJacMatMat(mtMesh, mtData, invParam, V, ctx: HipContext | None = None, wrt="sigma"):
+    """compJacMat(m) @ V.T for the rows of V (nvec, nAC) at m = invParam.strModel, (nvec, nData): the whole block in one solve
+    (HipContext.jvp_block).  Linearises the context at m; further blocks at the same point: ctx.jvp_block / ctx.jtvp_block /
+    ctx.gn_hessvec_block."""
+    ctx = ctx or get_context(mtMesh, mtData, invParam)
+    V = HipContext.block_input(V, ctx.nAC, "compJacMatVec")
+    ctx.linearize(np.asarray(invParam.strModel, dtype=np.float64))
+    return ctx.jvp_block(V, wrt=wrt)
+
+
+def compJacTMatMat(mtMesh, mtData, invParam, U, ctx: HipContext | None = None, wrt="sigma"):
+    """Re(J^T conj(U_j)) for the rows of U (nvec, nData) at m = invParam.strModel, (nvec, nAC): one adjoint-type solve for the
+    block (HipContext.jtvp_block)."""
+    ctx = ctx or get_context(mtMesh, mtData, invParam)
+    U = HipContext.block_input(U, ctx.nData, "compJacTMatVec", complex_in=True)
+    ctx.linearize(np.asarray(invParam.strModel, dtype=np.float64))
+    return ctx.jtvp_block(U, wrt=wrt)
+
+
 def compDataMisfit(predData, invParam):
     res = invParam.dataW * (predData - invParam.obsData)
     return 0.5 * float(np.real(np.vdot(res, res)))

@@ -262,6 +262,34 @@ int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_J
 int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st);
 int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st);
 
+/* Block products: nvec directions at the linearisation point in ONE solve per route -- a persistent launch over the nvec x (live
+ * systems) virtual systems instead of nvec launches that each leave most of a large device idle (randomized SVD of J or of the
+ * Gauss-Newton Hessian, block / subspace Gauss-Newton steps, Hessian probes, a few columns of J).
+ *   layout     direction j is contiguous: V[j*nAC ..), JV[j*2*nData ..) interleaved complex in the layout of pred, U likewise, JTU and
+ *              HV [nvec][nAC] -- rows of a C-ordered numpy array, columns of a Julia matrix
+ *   meaning    direction j of a result is what the single-direction call returns for direction j at the same point (wrt, real data,
+ *              Re(J^T conj(u)), the per-direction power-of-two normalisation), to the accuracy of the solves
+ *   hmcmt_jvp_block   one forward-type solve; hmcmt_jtvp_block one adjoint-type solve; hmcmt_gn_hessvec_block one of each, U = W^2 J V
+ *              kept on the device
+ *   zero       a direction that is identically zero has its systems switched off: exact zeros, no iterations
+ *   st         (may be NULL) the block's own solves as hmcmt_jacobian reports them: iteration sums over all virtual systems,
+ *              nsystems = the systems solved (directions that are not zero x systems that carry data; gn: of the forward-type solve)
+ *   nvec = 1   runs the single product's own code (no block arrays): the same bits as the single call; a zero direction's systems
+ *              leave that solve at iteration 0 and are counted in nsystems
+ *   nvec       1 .. HMCMT_BLOCK_MAX.  The block's solver arrays (about 300 bytes per node, system and direction) are allocated by
+ *              the first block call, grow to the largest nvec seen and are released by hmcmt_destroy; HMCMT_ENOMEM when they do not
+ *              fit -- the context stays usable, without them
+ * State rules, errors and repeatability are the single products': a block product needs the linearisation point, runs no evaluation,
+ * leaves the context's evaluation and solve state as it found it and is bitwise repeatable; HMCMT_EINVAL also for nvec out of range.
+ * HMCMT_ENOCONV / HMCMT_EBREAKDOWN when any virtual system fails: nothing is promised about the outputs then. */
+#define HMCMT_BLOCK_MAX 32
+int hmcmt_jvp_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* JV, hmcmt_stats* st);
+int hmcmt_jtvp_block(hmcmt_ctx* ctx, const double* U, int32_t nvec, int32_t wrt, double* JTU, hmcmt_stats* st);
+int hmcmt_gn_hessvec_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* HV, hmcmt_stats* st);
+int hmcmt_jvp_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_JV, hmcmt_stats* st);
+int hmcmt_jtvp_block_device(hmcmt_ctx* ctx, const double* d_U, int32_t nvec, int32_t wrt, double* d_JTU, hmcmt_stats* st);
+int hmcmt_gn_hessvec_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_HV, hmcmt_stats* st);
+
 /* All-gather of the chains' sample blocks over RCCL (xGMI inside a node): one process per GPU, one communicator per
  * process.  Replaces parallelHMCSampler's collection of the workers' results (HMCSampler/parallelHMC.jl:23-45:
  * remotecall_fetch of hmcmodel / hmcstats / hmcdata per worker) for hosts that hold their chains in this library:

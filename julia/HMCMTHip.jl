@@ -26,7 +26,7 @@ using SparseArrays
 using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
-export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, hipLinearize!, hipGNHessVec, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
+export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
        hipWait, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
@@ -257,6 +257,64 @@ function hipGNHessVec(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataMod
     rc = ccall((:hmcmt_gn_hessvec, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ref{HmcmtStats}), ctx.ptr, v, jacWrt(wrt), out, st)
     checkerr(ctx.ptr, rc)
     return out
+end
+"""
+    compJacMatMat(mtMesh, mtData, invParam, V; wrt=:sigma) -> compJacMat(...) * V (nData x nvec)
+
+The columns of V (nAC x nvec, nvec <= 32) in ONE solve of all systems and directions (hmcmt_jvp_block); column j is compJacMatVec(V[:, j]).
+"""
+function compJacMatMat(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel, V::Matrix{Float64}; wrt::Symbol=:sigma)
+    ctx = hipLinearize!(mtMesh, mtData, invParam)
+    size(V, 1) == ctx.nAC || throw(ArgumentError("V: nAC rows"))
+    JV = Matrix{ComplexF64}(undef, ctx.nData, size(V, 2))
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_jvp_block, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Cvoid}, Ref{HmcmtStats}), ctx.ptr, V, Int32(size(V, 2)), jacWrt(wrt), JV, st)
+    checkerr(ctx.ptr, rc)
+    return ctx.realData ? real.(JV) : JV
+end
+
+"""
+    compJacTMatMat(mtMesh, mtData, invParam, U; wrt=:sigma) -> real(J^T conj(U)) (nAC x nvec), one adjoint-type solve (hmcmt_jtvp_block)
+"""
+function compJacTMatMat(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel, U::AbstractMatrix; wrt::Symbol=:sigma)
+    ctx = hipLinearize!(mtMesh, mtData, invParam)
+    size(U, 1) == ctx.nData || throw(ArgumentError("U: nData rows"))
+    u = Matrix{ComplexF64}(U)
+    out = Matrix{Float64}(undef, ctx.nAC, size(u, 2))
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_jtvp_block, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ref{HmcmtStats}), ctx.ptr, u, Int32(size(u, 2)), jacWrt(wrt), out, st)
+    checkerr(ctx.ptr, rc)
+    return out
+end
+
+"""
+    hipGNHessMat(mtMesh, mtData, invParam, V; wrt=:sigma) -> Re(J^H W^2 J) V (nAC x nvec): one solve of each type (hmcmt_gn_hessvec_block)
+"""
+function hipGNHessMat(mtMesh::TensorMesh2D, mtData::MTData, invParam::InvDataModel, V::Matrix{Float64}; wrt::Symbol=:sigma)
+    ctx = hipLinearize!(mtMesh, mtData, invParam)
+    size(V, 1) == ctx.nAC || throw(ArgumentError("V: nAC rows"))
+    out = Matrix{Float64}(undef, ctx.nAC, size(V, 2))
+    st = Ref{HmcmtStats}()
+    rc = ccall((:hmcmt_gn_hessvec_block, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ref{HmcmtStats}), ctx.ptr, V, Int32(size(V, 2)), jacWrt(wrt), out, st)
+    checkerr(ctx.ptr, rc)
+    return out
+end
+
+# the same on device memory of the context's GPU (raw pointers; the point set by hipLinearize!): complete on return
+function hipJacMatMatDevice!(ctx, dV::Ptr{Cvoid}, nvec::Integer, dJV::Ptr{Cvoid}; wrt::Symbol=:sigma)
+    st = Ref{HmcmtStats}()
+    checkerr(ctx.ptr, ccall((:hmcmt_jvp_block_device, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ref{HmcmtStats}), ctx.ptr, dV, Int32(nvec), jacWrt(wrt), dJV, st))
+    return st[]
+end
+function hipJacTMatMatDevice!(ctx, dU::Ptr{Cvoid}, nvec::Integer, dJTU::Ptr{Cvoid}; wrt::Symbol=:sigma)
+    st = Ref{HmcmtStats}()
+    checkerr(ctx.ptr, ccall((:hmcmt_jtvp_block_device, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ref{HmcmtStats}), ctx.ptr, dU, Int32(nvec), jacWrt(wrt), dJTU, st))
+    return st[]
+end
+function hipGNHessMatDevice!(ctx, dV::Ptr{Cvoid}, nvec::Integer, dHV::Ptr{Cvoid}; wrt::Symbol=:sigma)
+    st = Ref{HmcmtStats}()
+    checkerr(ctx.ptr, ccall((:hmcmt_gn_hessvec_block_device, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ref{HmcmtStats}), ctx.ptr, dV, Int32(nvec), jacWrt(wrt), dHV, st))
+    return st[]
 end
 jacWrt(wrt::Symbol) = wrt === :sigma ? Int32(0) : wrt === :lnsigma ? Int32(1) : throw(ArgumentError("wrt: :sigma or :lnsigma"))
 
