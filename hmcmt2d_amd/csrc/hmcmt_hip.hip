@@ -1,7 +1,8 @@
 // libhmcmt_hip.so -- gfx950 (MI355X) implementation of the HMCMT2D hot path behind include/hmcmt.h.
 //
-// One translation unit in five files:
+// One translation unit in several files:
 //   hmcmt_hip.hip     this file: the context, the host orchestration of an evaluation (evaluate / solve), the C ABI
+//   host_jacobian.h   host code of the calls that borrow the context: explicit Jacobian, Jacobian products, block products
 //   kernels_cocg.h    Solver state, deterministic reductions (DPP wave sums), classic COCG kernels (Jacobi / plain FDM
 //                     preconditioners; the fp64 restart of a stagnating mixed-precision solve)
 //   kernels_fdm.h     fast-diagonalisation stage: y-eigenbasis transforms on the matrix cores (split-bf16
@@ -82,6 +83,57 @@ struct hmcmt_ctx {
     Solver sv{};
     hmcmt_options opt{};
     hmcmt_stats stats{};
+    // What a solve or an evaluation moves.  The explicit Jacobian, the Jacobian products and the block products borrow the context,
+    // solve, and give it back (Borrowed, host_jacobian.h): they copy this struct in front and assign it back behind, together with
+    // v, sv, opt and stats, so that the context's next evaluation computes bit for bit what it would have.  A member whose value a
+    // solve or an evaluation changes, and a later one reads, belongs HERE: as a plain member of hmcmt_ctx it leaves those calls
+    // changed, and nothing says so -- a chain that differs in the 12th digit after a Jacobian call.
+    struct SolveState {
+        long long evalCount = 0;
+        unsigned profMask = 0;            // bit c: time category c with HIP events
+        int guardEvery = 100;                 // HMCMT_GUARD_EVERY (0: off)
+        int dbgFlags = 0;                     // hmcmt_debug_flags
+        int nSysOn = 0;                       // systems switched on (View::sysOn)
+        bool haveFwd = false, haveAdj = false;   // previous fields usable as initial guesses
+        bool haveModel = false;
+        bool guardDropWarm = false;           // a trip: the next evaluation starts both solves cold
+        bool solveDone[2] = {true, true};
+        int lastItFwd = 0, lastItAdj = 0;
+        int sweepsKind[2] = {1, 1};              // sweepsMode ... what the forward / adjoint solve uses next (auto: from its last iteration count)
+        int sweepsUsed[2] = {1, 1};              // ... what the last evaluation's solves used
+        int sweepsCount2[2] = {0, 0}, sweepsSince[2] = {0, 0};   // ... iterations of the last two-sweep solve, solves since the last probe
+        bool sweepsProbe[2] = {false, false};    // ... the solve at hand is a one-sweep probe out of the two-sweep mode
+        std::vector<int> itersLast;           // [2*S]
+        std::vector<int> psOrder[2];          // what d_psOrder holds per solve kind (empty: the kernel's own order, no table passed)
+        std::vector<float> psCost[2];         // the costs the tables are made from (smoothed iteration counts)
+        long psRebalanced = 0;
+        LfStep lfStep{};                      // a position update of hmcmt_leapfrog* still to be performed (by k_sigma_rows, or k_lf_step in front of k_sigma)
+        LfMom lfMom{};                           // a momentum update of hmcmt_leapfrog* that the evaluation's last kernel performs (k_gradfinal)
+        bool persistOn = true;                // HMCMT_PERSIST=0: the launch-per-phase loop only
+        int persistWhyOff = 0;                // why persistOn is false: 1 = a placement fallback (for good), 2 = a timed-out wait (backoff)
+        long persistBackoff = 0;              // after a timed-out wait: solves on the launch-per-phase loop before the kernel is tried again (doubles per timeout)
+    } ss;
+    // The resources of one solver instance that are not in Solver: partial sums, records, spare vectors, the persistent kernel's
+    // words.  The context holds one set for its own problem, Blk one for the block products' virtual problem; a block call exchanges
+    // the two for its duration (blk_run), so solve(), the kernel table and the fallbacks see an ordinary problem.
+    struct Inst {
+        double* d_partZZ = nullptr;
+        double *d_partRes = nullptr, *d_partBn = nullptr;
+        double* h_rec = nullptr;              // packed per-solve records: [2][S] iters, [2][S] status (int), [2][S] err (double)
+        double* d_recHost = nullptr;          // device address of h_rec (pinned, mapped): k_solve_end writes it directly
+        cplx* d_b = nullptr;                  // copy of the right-hand side (verify)
+        cplx* d_sw = nullptr;                    // fp64 path with two sweeps per side: spare vector
+        float2* d_invp32 = nullptr;
+        float2* d_yhat2 = nullptr;            // column parts: the second part's partial product of the forward transform
+        unsigned* d_psync = nullptr;          // [8 * slots][32] barrier words | exit counter | fail word
+        size_t psyncBytes = 0;
+        int persistSlots = 0;                 // system slots per XCD
+        u4v* d_prec = nullptr;                // [S][MAXNB][2][8] records of the kernel's reductions (tagged, never cleared)
+        PsConst* d_psConst = nullptr;         // the kernel's launch-invariant state, read through a constant-address-space pointer
+        PsConst psShadow{};                   // what d_psConst holds (launch_persist refreshes the device copy when a field differs)
+        bool psConstValid = false;
+        bool dinvValid = true;                // Solver::dinv / dinv32 belong to the current model (ensure_dinv)
+    } inst;
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr;       // sigma-only sensitivity tables run beside the forward solve
@@ -94,14 +146,9 @@ struct hmcmt_ctx {
     // device scalars / buffers not in View
     u4v *d_Vb = nullptr, *d_Vtb = nullptr;        // bf16 fragment-order copies of V, V' (hi parts)
     u4v *d_Vbl = nullptr, *d_Vtbl = nullptr;      // ... lo parts: V = hi + lo to ~16 mantissa bits
-    float2* d_invp32 = nullptr;
-    double *d_m = nullptr, *d_V = nullptr, *d_Vt = nullptr, *d_partZZ = nullptr, *d_misfit = nullptr;
-    double *d_partRes = nullptr, *d_partBn = nullptr;
-    cplx* d_b = nullptr;                  // copy of the right-hand side (verify)
-    int dbgFlags = 0;                     // hmcmt_debug_flags
+    double *d_m = nullptr, *d_V = nullptr, *d_Vt = nullptr, *d_misfit = nullptr;
     double hostUs[4] = {0, 0, 0, 0}; long hostN = 0;      // HMCMT_TICKS: host time of the launch sequences around the solves
     int residThreads = 256;               // k_resid_pre
-    LfStep lfStep{};                      // a position update of hmcmt_leapfrog* still to be performed (by k_sigma_rows, or k_lf_step in front of k_sigma)
     bool sensWaitPending = false, extAWaitPending = false;
     bool noFusedStart = false, noSigmaRows = false, noCoefAll = false;     // environment knobs read at creation
     bool wantTicks = false;               // HMCMT_TICKS: in-kernel wall-clock stamps (View::ticks), printed at destroy
@@ -117,15 +164,8 @@ struct hmcmt_ctx {
     int* h_nactive = nullptr;
     int* h_stall = nullptr;               // pinned, mapped: Solver::stallHost (HW_WORDS words, host_word)
     int* h_prog = nullptr;                // pinned, mapped: Solver::progHost
-    double* h_rec = nullptr;              // packed per-solve records: [2][S] iters, [2][S] status (int), [2][S] err (double)
     double* h_stage = nullptr;            // m / grad / pred / misfit staging
     size_t stageDoubles = 0;
-    std::vector<int> itersLast;           // [2*S]
-    double* d_recHost = nullptr;          // device address of h_rec (pinned, mapped): k_solve_end writes it directly
-    bool solveDone[2] = {true, true};
-    int lastItFwd = 0, lastItAdj = 0;
-    bool haveModel = false;
-    bool haveFwd = false, haveAdj = false;   // previous fields usable as initial guesses
     cplx* d_prevField[2] = {nullptr, nullptr};   // the EXT_NP-1 previous solutions (warm_start == 2), per solve kind: a ring [EXT_NP-1][S*vstride]
     double* d_mHist[2] = {nullptr, nullptr};     // [EXT_NP+1][nAC] model history per solve kind (a ring: kernels_fused.h)
     double* d_ext[2] = {nullptr, nullptr};       // {w_0..w_{EXT_NP-1}, keep, count, ring heads, partial sums, ticket} (kernels_fused.h)
@@ -135,12 +175,7 @@ struct hmcmt_ctx {
     View sideView; const double* sideM = nullptr;   // deferred side-stream launches of the adjoint half (launch_adjoint_side)
     bool sidePending = false, sideExtrap = false, sideSens = false;
     bool fusedBack = true;                   // back transform + post-smoother in one kernel (HMCMT_FUSED_BACK=0: separate)
-    cplx* d_sw = nullptr;                    // fp64 path with two sweeps per side: spare vector
     int sweepsMode = 0;                      // HMCMT_SWEEPS: 1 / 2 damped Jacobi sweeps on each side of the FDM stage, 0 (default) = per solve
-    int sweepsKind[2] = {1, 1};              // ... what the forward / adjoint solve uses next (auto: from its last iteration count)
-    int sweepsUsed[2] = {1, 1};              // ... what the last evaluation's solves used
-    int sweepsCount2[2] = {0, 0}, sweepsSince[2] = {0, 0};   // ... iterations of the last two-sweep solve, solves since the last probe
-    bool sweepsProbe[2] = {false, false};    // ... the solve at hand is a one-sweep probe out of the two-sweep mode
     int sweepsUp = 12, sweepsDown = 6;       // auto: one sweep -> two above sweepsUp iterations (rounds 2-4: 30 -- a two-sweep iteration of the launch-per-phase loop cost 1.20 one-sweep
                                              // ones; in the persistent kernel 1.15 / 1.10, and solves of 18-24 iterations near the true model gain 2-7 % from two), two -> one below sweepsDown (12: the first,
                                              // cheap steps of every clamped burn-in trajectory switched back and the next ones up again)
@@ -154,9 +189,7 @@ struct hmcmt_ctx {
     size_t maxLds = 64 * 1024;               // dynamic LDS the fused kernels may request
     bool lpFallback = false;                 // this solve has switched its stragglers to the fp64 preconditioner
     // profiling
-    unsigned profMask = 0;            // bit c: time category c with HIP events
     int profEvery = 1;                // ... in every profEvery-th evaluation only (the brackets cost ~20 % if always on)
-    long long evalCount = 0;
     std::vector<hipEvent_t> evPool;
     struct Interval { uint32_t a, b; int cat; bool chained; };   // events in front of / behind a sampled launch (ProfScope)
     std::vector<Interval> ivs;
@@ -170,7 +203,6 @@ struct hmcmt_ctx {
     long long profStartSys = 0, profEvals = 0, profSolves = 0, profSolves2 = 0;
     long long profSerialIts = 0, profPersistSolves = 0;    // sampled: sum over solves of (iterations of the slowest system + 1), solves run by the persistent kernel
     bool evalSampled = false;              // the evaluation whose records are parsed next was a sampled one   // sampled: systems active at the start of a solve (summed), evaluations, solves, solves with two sweeps
-    int nSysOn = 0;
     // leapfrog / prior
     double *d_mref = nullptr, *d_invM = nullptr, *d_wmVal = nullptr, *d_p = nullptr, *d_mcur = nullptr, *d_g = nullptr;
     long long *d_wmRow = nullptr, *d_wmCol = nullptr;
@@ -178,7 +210,6 @@ struct hmcmt_ctx {
     int* d_lfFlag = nullptr;
     int* d_lfDone = nullptr;                 // [nAC] LfMom::done
     int lfGen = 0;                           // LfMom::gen of the last evaluation that carried a momentum update
-    LfMom lfMom{};                           // a momentum update of hmcmt_leapfrog* that the evaluation's last kernel performs (k_gradfinal)
     int* h_lfFlag = nullptr;                 // pinned copy of d_lfFlag (read after a synchronisation)
     double* d_gStart = nullptr;              // data gradient at the start model of the last trajectory (a rejection restarts there)
     bool havePrior = false, lfHaveGrad = false, lfFlagPending = false;
@@ -202,13 +233,9 @@ struct hmcmt_ctx {
     } mass;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)
-    bool persistOn = true;                // HMCMT_PERSIST=0: the launch-per-phase loop only
     bool persistFillsShare = false;
-    int persistG = 0, persistSlots = 0, persistCW = 0;   // workgroups per system, system slots per XCD, threads / 2 (0: the problem does not fit the kernel)
+    int persistG = 0, persistCW = 0;      // workgroups per system, threads / 2 (0: the problem does not fit the kernel)
     size_t persistLds = 0;                // LDS bytes of psKern's kernels
-    unsigned* d_psync = nullptr;          // [8 * slots][32] barrier words | exit counter | fail word
-    size_t psyncBytes = 0;
-    u4v* d_prec = nullptr;                // [S][MAXNB][2][8] records of the kernel's reductions (tagged, never cleared)
     unsigned long long persistTag = 0;    // ... the tag base of the next launch
     long long* d_pstamps = nullptr;       // HMCMT_STAMPS=persist
     long long persistSolves = 0, persistFallbacks = 0, persistTimeouts = 0;
@@ -219,23 +246,13 @@ struct hmcmt_ctx {
     // the order in which the queues of the persistent kernel take the systems (PsLaunch::order; persist_balance): per solve kind
     int* d_psOrder = nullptr;             // [2][S]
     int* h_psOrder = nullptr;             // pinned staging of the same
-    std::vector<int> psOrder[2];          // what the device copy holds (empty: the kernel's own order, no table passed)
     bool psBalance = true;                // HMCMT_PERSIST_BALANCE=0: never
-    std::vector<float> psCost[2];         // the costs the tables are made from (smoothed iteration counts)
     float psSmooth = 0.75f;               // weight of the older costs (HMCMT_PERSIST_BALANCE_SMOOTH; cfg5, 96-step chains: 0 -> 84.3, 0.5 -> 84.8, 0.75 -> 85.0 steps/s, index order 83.4)
-    long psRebalanced = 0;
-    PsConst psShadow{};                   // what d_psConst holds (launch_persist refreshes the device copy when a field differs)
-    PsConst* d_psConst = nullptr;         // the kernel's launch-invariant state, read through a constant-address-space pointer
-    bool psConstValid = false;
-    float2* d_yhat2 = nullptr;            // column parts: the second part's partial product of the forward transform
     unsigned persistSpin = PS_SPIN_LIMIT; // HMCMT_PS_SPIN: polls before a wait of the kernel gives up (tests shorten it)
     struct PsStart { int resid = 0, begin = 0; };      // the solve's start inside the persistent kernel (PsLaunch::resid / begin): set by evaluate_once for the NEXT solve
     PsStart psStart{};
     bool lazyDinv = true;                 // HMCMT_LAZY_DINV=0: k_coef_all writes every system's Jacobi diagonal in every evaluation, as until round 6 (A/B)
-    bool dinvValid = true;                // Solver::dinv / dinv32 belong to the current model (ensure_dinv)
     bool psInKernelStart = true;          // HMCMT_PS_START=0: k_resid0 / k_solve_begin in launches of their own, as until round 5 (A/B)
-    int persistWhyOff = 0;                // why persistOn is false: 1 = a placement fallback (for good), 2 = a timed-out wait (backoff)
-    long persistBackoff = 0;              // after a timed-out wait: solves on the launch-per-phase loop before the kernel is tried again (doubles per timeout)
     bool persistTimedOut = false;         // a wait of the last persistent launch timed out: evaluate() redoes the evaluation with the launch-per-phase loop
     int dbgPlace = 0;                     // test hook (hmcmt_debug_flags bit 2): 1 + index of the group of the next persistent launch that fails its placement check
     bool dbgPlaceAdj = false;             // ... (bit 4) not the next launch but the next ADJOINT one: forward launches pass it by
@@ -244,7 +261,6 @@ struct hmcmt_ctx {
     bool counted = false;                 // this context is counted in g_quarterUse / holds a reference on the device lock
     // production guard on the error-estimate stopping rule: every guardEvery-th evaluation the TRUE residual of both
     // solves is formed (two vector passes and a read-back: ~0.1 ms once in guardEvery evaluations) -- hmcmt_guard
-    int guardEvery = 100;                 // HMCMT_GUARD_EVERY (0: off)
     long long guardChecks = 0;
     double guardWorst = 0.0, guardLast = 0.0;
     double guardLimit = 1e-6;             // HMCMT_GUARD_LIMIT: a checked residual above it is a "trip" (warning, next evaluation starts cold)
@@ -256,7 +272,6 @@ struct hmcmt_ctx {
     bool specValid = false;               // the last solve's speculative followers ran (the solve ended clean)
     bool specOn = true;                   // HMCMT_SPEC=0: followers are queued after the host has seen the solve's outcome
     bool guardNow = false;                // the evaluation at hand is a guarded one
-    bool guardDropWarm = false;           // a trip: the next evaluation starts both solves cold
     // results of the last two host-API evaluations, keyed by the model: a sampler re-evaluates the model it has
     // just evaluated (getHamiltonian at the proposal, HMCSampler.jl:364; the first gradient of the next trajectory,
     // :217) or, after a rejection, the start model of the trajectory before -- those calls cost a memcmp
@@ -295,13 +310,10 @@ struct hmcmt_ctx {
         long long gen = -1; int genVec = 0;   // the linearisation point and nvec the replicated pivots were made for
         std::vector<void*> allocs, hostAllocs;
         Solver sv{};
-        cplx *lam = nullptr, *invp = nullptr, *d_b = nullptr, *d_sw = nullptr;
-        float2 *invp32 = nullptr, *yhat2 = nullptr;
-        double *omega = nullptr, *partZZ = nullptr, *partRes = nullptr, *partBn = nullptr;
-        unsigned* psync = nullptr; size_t psyncBytes = 0; int slots = 0;
-        u4v* prec = nullptr;
-        PsConst* psConst = nullptr; PsConst psShadow{}; bool psConstValid = false;
-        double *h_rec = nullptr, *d_recHost = nullptr;
+        Inst inst{};                       // (while a block call runs: the context's own, exchanged)
+        int slots = 0;                     // system slots per XCD the sync words were made for (inst.persistSlots: those of the call at hand)
+        cplx *lam = nullptr, *invp = nullptr;
+        double* omega = nullptr;
         int *h_onV = nullptr, *d_onVHost = nullptr;   // mapped: [cap S] the virtual systems solved, as k_blk_flags wrote them
         int *dirOn = nullptr, *sysOnDir = nullptr, *sysOnV = nullptr;
         // work arrays per direction (the single product's, [cap] times)
@@ -356,7 +368,7 @@ struct ProfScope {
         return i;
     }
     ProfScope(hmcmt_ctx* ctx, int cat_, bool chain_ = false) : c(ctx), cat(cat_), a((size_t)-1), chain(chain_), reused(false) {
-        const bool on = ((c->profMask >> cat) & 1u) && (c->evalCount % c->profEvery) == 0 && !c->lpFallback;   // (the fp64 restart of a
+        const bool on = ((c->ss.profMask >> cat) & 1u) && (c->ss.evalCount % c->profEvery) == 0 && !c->lpFallback;   // (the fp64 restart of a
         // straggling solve runs other kernels: not part of the sampled population)
         if (!on) { c->chainEnd = (size_t)-1; return; }
         if (chain && c->chainEnd != (size_t)-1) { a = c->chainEnd; reused = true; }
@@ -456,9 +468,9 @@ template <int SW>
 void launch_spmv(hmcmt_ctx* ctx, size_t lds, const float2* pin, float2* pout, int it) {
     const Solver& k = ctx->sv;
     const dim3 grid = tile_grid(k, SW == 2 ? (k.nz - 1 + k.RTS - 1) / k.RTS : k.NTR);
-    if (ctx->spmvThreads == 512) hipLaunchKernelGGL((k_spmv_fused<SW, 512>), grid, dim3(512), lds, ctx->stream, k, ctx->d_partZZ, pin, pout, it, ctx->opt.maxit);
-    else if (ctx->spmvThreads == 1024) hipLaunchKernelGGL((k_spmv_fused<SW, 1024>), grid, dim3(1024), lds, ctx->stream, k, ctx->d_partZZ, pin, pout, it, ctx->opt.maxit);
-    else hipLaunchKernelGGL((k_spmv_fused<SW, 256>), grid, dim3(256), lds, ctx->stream, k, ctx->d_partZZ, pin, pout, it, ctx->opt.maxit);
+    if (ctx->spmvThreads == 512) hipLaunchKernelGGL((k_spmv_fused<SW, 512>), grid, dim3(512), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
+    else if (ctx->spmvThreads == 1024) hipLaunchKernelGGL((k_spmv_fused<SW, 1024>), grid, dim3(1024), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
+    else hipLaunchKernelGGL((k_spmv_fused<SW, 256>), grid, dim3(256), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
 }
 // two sweeps per side exist on the fused mixed-precision path (and on the fp64 path of the restarts)
 bool sweeps2_ok(const hmcmt_ctx* ctx) {
@@ -481,26 +493,26 @@ int launch_back_post(hmcmt_ctx* ctx) {
         if (k.sweeps == 2) {
             { ProfScope ps(ctx, 0, true);
               hipLaunchKernelGGL((k_back_post<1, 2>), dim3(nwg, k.S), dim3(64 * NW), lds, ctx->stream, k, k.y32, ctx->d_Vtb, ctx->d_Vtbl,
-                                 ctx->d_partZZ, NW, ctx->backStamps); }
+                                 ctx->inst.d_partZZ, NW, ctx->backStamps); }
             if (k.merged2) return 0;                  // (the second post-sweep runs inside k_spmv_fused<2>)
             ProfScope ps(ctx, 7, true);
-            hipLaunchKernelGGL(k_post2, dim3(k.NTR, k.S), vb, (size_t)(k.RT + 2) * k.NYP * sizeof(float2), ctx->stream, k, ctx->d_partZZ);
+            hipLaunchKernelGGL(k_post2, dim3(k.NTR, k.S), vb, (size_t)(k.RT + 2) * k.NYP * sizeof(float2), ctx->stream, k, ctx->inst.d_partZZ);
             return 0;
         }
         ProfScope ps(ctx, 0, true);
         hipLaunchKernelGGL((k_back_post<1, 1>), dim3(nwg, k.S), dim3(64 * NW), lds, ctx->stream, k, k.y32, ctx->d_Vtb, ctx->d_Vtbl,
-                           ctx->d_partZZ, NW, ctx->backStamps);
+                           ctx->inst.d_partZZ, NW, ctx->backStamps);
         return 0;
     }
     int rc;
     if (k.sweeps == 2) {                     // wide meshes, two sweeps: F t as fp64, then z4 and the sums of the rho identity
         if ((rc = launch_transform_lp<1>(ctx, k.y32, true, k.z, k.active))) return rc;
-        { ProfScope ps(ctx, 7, true); hipLaunchKernelGGL(k_post_w2, vg, vb, 0, ctx->stream, k, ctx->d_partZZ); }
-        if (!k.merged2) { ProfScope ps2(ctx, 7, true); hipLaunchKernelGGL(k_post2, dim3(k.NTR, k.S), vb, (size_t)(k.RT + 2) * k.NYP * sizeof(float2), ctx->stream, k, ctx->d_partZZ); }
+        { ProfScope ps(ctx, 7, true); hipLaunchKernelGGL(k_post_w2, vg, vb, 0, ctx->stream, k, ctx->inst.d_partZZ); }
+        if (!k.merged2) { ProfScope ps2(ctx, 7, true); hipLaunchKernelGGL(k_post2, dim3(k.NTR, k.S), vb, (size_t)(k.RT + 2) * k.NYP * sizeof(float2), ctx->stream, k, ctx->inst.d_partZZ); }
         return 0;
     }
     if ((rc = launch_transform_lp<2>(ctx, k.y32, true, k.z, k.active))) return rc;   // z = F t + dinv r
-    { ProfScope ps(ctx, 7, true); hipLaunchKernelGGL(k_post, vg, vb, 0, ctx->stream, k, ctx->d_partZZ, k.z32); }
+    { ProfScope ps(ctx, 7, true); hipLaunchKernelGGL(k_post, vg, vb, 0, ctx->stream, k, ctx->inst.d_partZZ, k.z32); }
     return 0;
 }
 
@@ -532,9 +544,9 @@ int launch_fdm_fwd(hmcmt_ctx* ctx, const float2* pX = nullptr) {        // pX: t
         const dim3 grid(((k.NYP / 16 + ntw - 1) / ntw) * k.S), block(64 * nw);
         ProfScope ps(ctx, 1, true);
         if (ntw == 1)
-            hipLaunchKernelGGL(k_fdm_fwd<1>, grid, block, ldsFor(1), ctx->stream, k, k.t32, ctx->d_Vb, ctx->d_Vbl, ctx->d_invp32, k.y32, (long long*)nullptr, k.xInFwd ? pX : (const float2*)nullptr);
+            hipLaunchKernelGGL(k_fdm_fwd<1>, grid, block, ldsFor(1), ctx->stream, k, k.t32, ctx->d_Vb, ctx->d_Vbl, ctx->inst.d_invp32, k.y32, (long long*)nullptr, k.xInFwd ? pX : (const float2*)nullptr);
         else
-            hipLaunchKernelGGL(k_fdm_fwd<FW_NTW>, grid, block, ldsFor(FW_NTW), ctx->stream, k, k.t32, ctx->d_Vb, ctx->d_Vbl, ctx->d_invp32, k.y32, (long long*)nullptr, k.xInFwd ? pX : (const float2*)nullptr);
+            hipLaunchKernelGGL(k_fdm_fwd<FW_NTW>, grid, block, ldsFor(FW_NTW), ctx->stream, k, k.t32, ctx->d_Vb, ctx->d_Vbl, ctx->inst.d_invp32, k.y32, (long long*)nullptr, k.xInFwd ? pX : (const float2*)nullptr);
         return 0;
     }
     int rc;
@@ -550,7 +562,7 @@ int apply_precond(hmcmt_ctx* ctx) {
     dim3 vg(k.NB, k.S), vb(VBLOCK);
     if (ctx->opt.precond == HMCMT_PRECOND_JACOBI) {
         { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_jacobi, vg, vb, 0, ctx->stream, k); }
-        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_dots, vg, vb, 0, ctx->stream, k, ctx->d_partZZ); }
+        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_dots, vg, vb, 0, ctx->stream, k, ctx->inst.d_partZZ); }
         return 0;
     }
     const bool smooth = ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI;
@@ -572,22 +584,22 @@ int apply_precond(hmcmt_ctx* ctx) {
         } else {
             if ((rc = launch_transform_lp<1>(ctx, k.y32, true, k.z, k.active))) return rc;
             ProfScope ps(ctx, 3);
-            hipLaunchKernelGGL(k_dots, vg, vb, 0, ctx->stream, k, ctx->d_partZZ);
+            hipLaunchKernelGGL(k_dots, vg, vb, 0, ctx->stream, k, ctx->inst.d_partZZ);
         }
         return 0;
     }
     if (smooth && k.sweeps == 2) {                  // two sweeps per side, fp64 (fdm_precision = 1, and the restart of a stagnating solve)
-        if (!ctx->d_sw) { int rc2 = dalloc(ctx, &ctx->d_sw, (size_t)k.S * k.vstride); if (rc2) return rc2; }
+        if (!ctx->inst.d_sw) { int rc2 = dalloc(ctx, &ctx->inst.d_sw, (size_t)k.S * k.vstride); if (rc2) return rc2; }
         hipLaunchKernelGGL(k_pre, vg, vb, 0, ctx->stream, k);                                        // t1 = r - A D r
-        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, k.t, ctx->d_sw, 0);               // z2 = D (r + t1)
-        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, ctx->d_sw, k.t, 1);               // t2 = r - A z2
+        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, k.t, ctx->inst.d_sw, 0);               // z2 = D (r + t1)
+        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, ctx->inst.d_sw, k.t, 1);               // t2 = r - A z2
         if ((rc = launch_transform(ctx, k.t, ctx->d_V, k.y, k.active))) return rc;
         hipLaunchKernelGGL(k_thomas, tg, dim3(64), 0, ctx->stream, k);
         if ((rc = launch_transform(ctx, k.y, ctx->d_Vt, k.z, k.active))) return rc;
-        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, ctx->d_sw, k.z, 3);               // z3 = F t2 + z2
-        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, k.z, ctx->d_sw, 2);               // z4 = z3 + D (r - A z3)
-        Solver k2 = k; k2.z = ctx->d_sw;
-        hipLaunchKernelGGL(k_post, vg, vb, 0, ctx->stream, k2, ctx->d_partZZ, (float2*)nullptr);     // t = z4 + D (r - A z4), dots
+        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, ctx->inst.d_sw, k.z, 3);               // z3 = F t2 + z2
+        hipLaunchKernelGGL(k_sweep_exp, vg, vb, 0, ctx->stream, k, k.z, ctx->inst.d_sw, 2);               // z4 = z3 + D (r - A z3)
+        Solver k2 = k; k2.z = ctx->inst.d_sw;
+        hipLaunchKernelGGL(k_post, vg, vb, 0, ctx->stream, k2, ctx->inst.d_partZZ, (float2*)nullptr);     // t = z4 + D (r - A z4), dots
         std::swap(k.z, k.t);
         return 0;
     }
@@ -597,11 +609,11 @@ int apply_precond(hmcmt_ctx* ctx) {
     if ((rc = launch_transform(ctx, k.y, ctx->d_Vt, k.z, k.active))) return rc;
     if (smooth) {
         { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_mid, vg, vb, 0, ctx->stream, k); }
-        { ProfScope ps(ctx, 7); hipLaunchKernelGGL(k_post, vg, vb, 0, ctx->stream, k, ctx->d_partZZ, (float2*)nullptr); }
+        { ProfScope ps(ctx, 7); hipLaunchKernelGGL(k_post, vg, vb, 0, ctx->stream, k, ctx->inst.d_partZZ, (float2*)nullptr); }
         std::swap(k.z, k.t);                            // the smoothed result is the preconditioned residual
     } else {
         ProfScope ps(ctx, 3);
-        hipLaunchKernelGGL(k_dots, vg, vb, 0, ctx->stream, k, ctx->d_partZZ);
+        hipLaunchKernelGGL(k_dots, vg, vb, 0, ctx->stream, k, ctx->inst.d_partZZ);
     }
     return 0;
 }
@@ -682,7 +694,7 @@ bool persist_alone(const hmcmt_ctx* ctx) {
     return devlock_held(ctx->device);
 }
 bool persist_ok(const hmcmt_ctx* ctx) {
-    return ctx->persistOn && ctx->persistCW > 0 && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && persist_alone(ctx);
+    return ctx->ss.persistOn && ctx->persistCW > 0 && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && persist_alone(ctx);
 }
 // a word of the mapped host block (HostWord)
 volatile int& host_word(const hmcmt_ctx* ctx, HostWord w) { return reinterpret_cast<volatile int*>(ctx->h_stall)[w]; }
@@ -719,34 +731,34 @@ const PsKernel* ps_pick(int strips, int cw, int mw, int cs, int wk, bool stamps,
 // one launch = the whole solve (or, precondOnly, one application of the preconditioner to k.r -> zout)
 int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, int kind = 0, hmcmt_ctx::PsStart start = hmcmt_ctx::PsStart{}) {
     Solver& k = ctx->sv;
-    const int groups = 8 * ctx->persistSlots;
+    const int groups = 8 * ctx->inst.persistSlots;
     // the launch-invariant state: rebuilt from the solver's structures on every launch (a few hundred bytes of host work) and
     // compared with what the device copy holds -- any field that changes (an option, a buffer) refreshes it, nothing has to
     // remember to
     PsConst c{};
     c.S = k.S; c.nFreq = k.nFreq; c.NYP = k.NYP; c.NZP = k.NZP; c.ny = k.ny; c.nz = k.nz; c.twist = k.twist; c.stallIt = k.stallIt;
     c.vstride = k.vstride;
-    c.G = ctx->persistG; c.GZ = ctx->persistGZ; c.slots = ctx->persistSlots;
+    c.G = ctx->persistG; c.GZ = ctx->persistGZ; c.slots = ctx->inst.persistSlots;
     c.C0 = ctx->persistCS > 1 ? ps_split_col(k.NYP) : k.NYP; c.TW = ps_tile_width(k.NYP, ctx->persistCS); c.PLW = ctx->persistCS > 1 ? ps_plane_width(k.NYP) : k.NYP;
-    c.syncWords = (int)(ctx->psyncBytes / sizeof(unsigned));      // (zero at create; every launch's last workgroup leaves them zero)
+    c.syncWords = (int)(ctx->inst.psyncBytes / sizeof(unsigned));      // (zero at create; every launch's last workgroup leaves them zero)
     c.spinLimit = ctx->persistSpin;
     c.wJ = (float)ctx->jacobiW;
     c.omega = k.omega; c.ofz = k.ofz; c.dM = k.dM; c.cY = k.cY; c.cZ = k.cZ; c.cf32 = k.cf32;
     c.active = k.active; c.iters = k.iters; c.status = k.status; c.nactive = k.nactive; c.nactHost = k.nactHost;
     c.failHost = k.failHost; c.stallHost = k.stallHost; c.progHost = k.progHost; c.errEst = k.errEst; c.ticks = k.ticks;
-    c.sync = ctx->d_psync; c.exitCnt = ctx->d_psync + 32 * groups; c.fail = reinterpret_cast<int*>(ctx->d_psync + 32 * groups + 8);
+    c.sync = ctx->inst.d_psync; c.exitCnt = ctx->inst.d_psync + 32 * groups; c.fail = reinterpret_cast<int*>(ctx->inst.d_psync + 32 * groups + 8);
     c.placeHost = k.stallHost + HW_PLACE;
     c.Vb = ctx->d_Vb; c.Vtb = ctx->d_Vtb;
     c.pubR = k.t2_32; c.pubZ = k.zs32; c.pubP = k.p32a;
-    c.yhat = k.y32; c.yhat2 = ctx->d_yhat2; c.ysol = k.t32; c.tbuf = k.z4_32;
-    c.ip32 = ctx->d_invp32; c.rec = ctx->d_prec;
-    if (!ctx->psConstValid || std::memcmp(&c, &ctx->psShadow, sizeof c) != 0) {
+    c.yhat = k.y32; c.yhat2 = ctx->inst.d_yhat2; c.ysol = k.t32; c.tbuf = k.z4_32;
+    c.ip32 = ctx->inst.d_invp32; c.rec = ctx->inst.d_prec;
+    if (!ctx->inst.psConstValid || std::memcmp(&c, &ctx->inst.psShadow, sizeof c) != 0) {
         HIPCHK(hipStreamSynchronize(ctx->stream));             // (rare: an earlier launch may still read the old copy)
-        HIPCHK(hipMemcpy(ctx->d_psConst, &c, sizeof c, hipMemcpyHostToDevice));
-        ctx->psShadow = c; ctx->psConstValid = true;
+        HIPCHK(hipMemcpy(ctx->inst.d_psConst, &c, sizeof c, hipMemcpyHostToDevice));
+        ctx->inst.psShadow = c; ctx->inst.psConstValid = true;
     }
     PsLaunch a{};
-    a.kc = ctx->d_psConst;
+    a.kc = ctx->inst.d_psConst;
     a.x = k.x; a.r = k.r; a.tol2 = k.tol2; a.w2 = k.w2;
     a.maxit = ctx->opt.maxit; a.precondOnly = precondOnly;
     ctx->persistTag += std::max(1ull << 20, 2ull * ((unsigned long long)std::max(ctx->opt.maxit, 0) + 8));   // (an iteration takes two tags: a launch's range never reaches the next one's)
@@ -760,11 +772,11 @@ int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, in
     a.gateGen = ++ctx->gateGen;
     if (ctx->dbgPlaceAdj && kind != 1) a.dbgPlace = 0;
     else { a.dbgPlace = ctx->dbgPlace; ctx->dbgPlace = 0; ctx->dbgPlaceAdj = false; }
-    a.order = ctx->psOrder[kind == 1].empty() ? nullptr : ctx->d_psOrder + (kind == 1 ? k.S : 0);
-    a.resid = start.resid; a.begin = start.begin; a.nOn = ctx->nSysOn; a.sysOn = ctx->v.sysOn;
-    a.doneCnt = ctx->d_psync + 32 * groups + 4;       // (in the block the kernel's last workgroup clears: exitCnt at +0, fail at +8)
-    a.placedCnt = precondOnly ? nullptr : ctx->d_psync + 32 * groups + 5; a.nGroups = groups;
-    if (start.begin) *(volatile int*)ctx->h_nactive = ctx->nSysOn;      // (mapped: "not all done yet" until the kernel's last converged system says otherwise)
+    a.order = ctx->ss.psOrder[kind == 1].empty() ? nullptr : ctx->d_psOrder + (kind == 1 ? k.S : 0);
+    a.resid = start.resid; a.begin = start.begin; a.nOn = ctx->ss.nSysOn; a.sysOn = ctx->v.sysOn;
+    a.doneCnt = ctx->inst.d_psync + 32 * groups + 4;       // (in the block the kernel's last workgroup clears: exitCnt at +0, fail at +8)
+    a.placedCnt = precondOnly ? nullptr : ctx->inst.d_psync + 32 * groups + 5; a.nGroups = groups;
+    if (start.begin) *(volatile int*)ctx->h_nactive = ctx->ss.nSysOn;      // (mapped: "not all done yet" until the kernel's last converged system says otherwise)
     if (ctx->d_pstamps) HIPCHK(hipMemsetAsync(ctx->d_pstamps, 0, sizeof(long long) * 16 * 256, ctx->stream));
     const PsKernel& e = *ctx->psKern[sweeps == 2 ? 1 : 0];
     void* args[] = {&a};
@@ -801,17 +813,17 @@ constexpr int SWEEPS_PROBE_EVERY = 40;      // in two-sweep mode: every so many 
 // SWEEPS_PROBE_EVERY solves and keeps whichever is cheaper (parse_stats).
 int pick_sweeps(const hmcmt_ctx* ctx, int kind) {
     if (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) return 1;
-    return ctx->sweepsMode == 2 ? 2 : ctx->sweepsKind[kind];
+    return ctx->sweepsMode == 2 ? 2 : ctx->ss.sweepsKind[kind];
 }
 
 // Solves A x = r for all systems (x zero on interior on entry; r destroyed).  kind 0 forward, 1 adjoint.
 void launch_solve_end(hmcmt_ctx* ctx, int kind) {
     const int S = ctx->sv.S;
-    hipLaunchKernelGGL(k_solve_end, dim3((S + 63) / 64), dim3(64), 0, ctx->stream, ctx->sv, kind, (int*)ctx->d_recHost, ctx->d_recHost + 2 * S);
+    hipLaunchKernelGGL(k_solve_end, dim3((S + 63) / 64), dim3(64), 0, ctx->stream, ctx->sv, kind, (int*)ctx->inst.d_recHost, ctx->inst.d_recHost + 2 * S);
 }
 SolveRec solve_rec(hmcmt_ctx* ctx, int kind) {
     const Solver& k = ctx->sv;
-    return SolveRec{k.iters, k.status, k.errEst, (int*)ctx->d_recHost, ctx->d_recHost + 2 * k.S, kind, k.S};
+    return SolveRec{k.iters, k.status, k.errEst, (int*)ctx->inst.d_recHost, ctx->inst.d_recHost + 2 * k.S, kind, k.S};
 }
 
 // deferEnd: the caller's next kernel writes the per-solve records (k_rxall / k_wb with solve_rec) instead of k_solve_end
@@ -823,9 +835,9 @@ using SpecFn = std::function<void(const int* gate, int gen)>;
 // The Jacobi diagonals of every system for the kernels of the launch-per-phase loop, where k_coef_all left them out (an evaluation that
 // was to run in the persistent kernel: a placement fallback, a stagnated system's fp64 restart, a second context on the device).
 void ensure_dinv(hmcmt_ctx* ctx) {
-    if (ctx->dinvValid) return;
+    if (ctx->inst.dinvValid) return;
     hipLaunchKernelGGL(k_dinv, dim3(ctx->sv.NB, ctx->sv.S), dim3(VBLOCK), 0, ctx->stream, ctx->sv, ctx->jacobiW);
-    ctx->dinvValid = true;
+    ctx->inst.dinvValid = true;
 }
 // What the persistent attempt of a solve came to (solve_persist)
 enum class PsOutcome {
@@ -869,13 +881,13 @@ int solve_persist(hmcmt_ctx* ctx, int kind, hmcmt_ctx::PsStart start, const Spec
         // after the first timeout, twice as long after every further one --, and evaluate() runs the evaluation again, cold,
         // with the launch-per-phase loop, which works under any sharing
         ctx->persistTimedOut = true;
-        ctx->persistOn = false; ctx->persistWhyOff = 2; ++ctx->persistTimeouts;
-        ctx->persistBackoff = 256l << std::min<long long>(ctx->persistTimeouts - 1, 6);     // (the tenant may leave: 256, 512, .. 16 384 solves, then another try)
+        ctx->ss.persistOn = false; ctx->ss.persistWhyOff = 2; ++ctx->persistTimeouts;
+        ctx->ss.persistBackoff = 256l << std::min<long long>(ctx->persistTimeouts - 1, 6);     // (the tenant may leave: 256, 512, .. 16 384 solves, then another try)
     }
     if (host_word(ctx, HW_PLACE)) {
         // the group's workgroups were not on one XCD (or the kernel could not be placed): nothing was touched by those
         // groups -- this context goes back to the launch-per-phase loop for good
-        ctx->persistOn = false; ctx->persistWhyOff = 1; ctx->persistBackoff = 0; ++ctx->persistFallbacks;
+        ctx->ss.persistOn = false; ctx->ss.persistWhyOff = 1; ctx->ss.persistBackoff = 0; ++ctx->persistFallbacks;
         ctx->fbKind = kind; ctx->fbStalled = -1;
         if (start.begin && start.resid) {
             // (rare, and behind a finished kernel: what it left is read back -- active 1: started and stalled, 2: never started)
@@ -985,7 +997,7 @@ int solve_fp64(hmcmt_ctx* ctx, bool fused, int nextCheck, bool& done, int& it) {
     if (restart) { ctx->lpFallback = true; ++ctx->stats.fallback_solves; }
     // z = P^-1 r ; rho = r'z ; p = z
     { int prc = apply_precond(ctx); if (prc) return prc; }
-    { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, restart ? 2 : 1, ctx->opt.maxit); }
+    { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->inst.d_partZZ, restart ? 2 : 1, ctx->opt.maxit); }
     { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 1); }
     while (!done && it < ctx->opt.maxit) {
         ++it;
@@ -993,13 +1005,13 @@ int solve_fp64(hmcmt_ctx* ctx, bool fused, int nextCheck, bool& done, int& it) {
             ctx->lpFallback = true;     // restart COCG for the still-active systems: z = P64^-1 r, p = z
             ++ctx->stats.fallback_solves;
             { int prc = apply_precond(ctx); if (prc) return prc; }
-            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, 2, ctx->opt.maxit); }
+            { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->inst.d_partZZ, 2, ctx->opt.maxit); }
             { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 1); }
         }
         { ProfScope ps(ctx, 2); hipLaunchKernelGGL(k_spmv, vg, vb, 0, ctx->stream, k); }
         { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_update, vg, vb, 0, ctx->stream, k); }
         { int prc = apply_precond(ctx); if (prc) return prc; }
-        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->d_partZZ, 0, ctx->opt.maxit); }
+        { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_check, dim3(1), dim3(128), 0, ctx->stream, k, ctx->inst.d_partZZ, 0, ctx->opt.maxit); }
         { ProfScope ps(ctx, 3); hipLaunchKernelGGL(k_pupdate, vg, vb, 0, ctx->stream, k, 0); }
         if (it >= nextCheck || it == ctx->opt.maxit) {
             HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1016,10 +1028,10 @@ int solve_epilogue(hmcmt_ctx* ctx, int kind, const cplx* x, bool done, bool defe
     const dim3 vg(k.NB, S), vb(VBLOCK);
     if (!deferEnd) launch_solve_end(ctx, kind);
     if (ctx->opt.verify || (guard && done)) {
-        hipLaunchKernelGGL(k_trueres, vg, vb, 0, ctx->stream, k, (guard && kind == 0) ? (const cplx*)nullptr : ctx->d_b, x, ctx->d_partRes, ctx->d_partBn);
+        hipLaunchKernelGGL(k_trueres, vg, vb, 0, ctx->stream, k, (guard && kind == 0) ? (const cplx*)nullptr : ctx->inst.d_b, x, ctx->inst.d_partRes, ctx->inst.d_partBn);
         std::vector<double> pr((size_t)S * MAXNB), pb((size_t)S * MAXNB);
-        HIPCHK(hipMemcpyAsync(pr.data(), ctx->d_partRes, pr.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(pb.data(), ctx->d_partBn, pb.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(pr.data(), ctx->inst.d_partRes, pr.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(pb.data(), ctx->inst.d_partBn, pb.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         for (int s = 0; s < S; ++s) {
             double rr = 0, bb = 0;
@@ -1031,9 +1043,9 @@ int solve_epilogue(hmcmt_ctx* ctx, int kind, const cplx* x, bool done, bool defe
             if (!(ctx->guardLast <= ctx->guardLimit)) {
                 // the estimate ||z|| <= tol ||x|| stopped a solve whose residual is not small: say so, and do not warm-start from it
                 ++ctx->guardTrips;
-                ctx->guardDropWarm = true;
+                ctx->ss.guardDropWarm = true;
                 fprintf(stderr, "hmcmt: stopping-rule guard: evaluation %lld, %s solve: true residual %.3e > %.1e (tol %.1e)\n",
-                        ctx->evalCount, kind == 0 ? "forward" : "adjoint", ctx->guardLast, ctx->guardLimit, ctx->opt.tol);
+                        ctx->ss.evalCount, kind == 0 ? "forward" : "adjoint", ctx->guardLast, ctx->guardLimit, ctx->opt.tol);
             }
         }
     }
@@ -1045,7 +1057,7 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
     k.tol2 = ctx->opt.tol * ctx->opt.tol;
     const int S = k.S;
     const size_t vecBytes = (size_t)S * k.vstride * sizeof(cplx);
-    if (ctx->opt.verify) HIPCHK(hipMemcpyAsync(ctx->d_b, k.r, vecBytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if (ctx->opt.verify) HIPCHK(hipMemcpyAsync(ctx->inst.d_b, k.r, vecBytes, hipMemcpyDeviceToDevice, ctx->stream));
     // production guard (every guardEvery-th evaluation): the true residual of this solve without options.verify -- the forward
     // problem's right-hand side lives in x's boundary nodes (k_trueres forms it), the adjoint one was copied to d_b by evaluate()
     const bool guard = !ctx->opt.verify && ctx->guardNow;
@@ -1055,8 +1067,8 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
     if (!ctx->solveBegun)           // (otherwise done by the residual kernel in front of this solve -- or about to be done by the persistent kernel)
         hipLaunchKernelGGL(k_solve_begin, dim3((S * MAXNB + 255) / 256), dim3(256), 0, ctx->stream, k, ctx->v.sysOn);
     ctx->solveBegun = false;
-    if (k.cntActive) { ++ctx->profSolves; ctx->profStartSys += ctx->nSysOn; if (k.sweeps == 2) ++ctx->profSolves2; }
-    int& guess = kind == 0 ? ctx->lastItFwd : ctx->lastItAdj;
+    if (k.cntActive) { ++ctx->profSolves; ctx->profStartSys += ctx->ss.nSysOn; if (k.sweeps == 2) ++ctx->profSolves2; }
+    int& guess = kind == 0 ? ctx->ss.lastItFwd : ctx->ss.lastItAdj;
     const int nextCheck = guess > 2 ? guess : 4;
     ctx->lpFallback = false;
     ctx->solveFail = 0;
@@ -1066,7 +1078,7 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
     ctx->specValid = false;
     // (after a timed-out wait: another try when the backoff has run out -- a context that left the kernel because of its PLACEMENT
     //  stays off for good: persistWhyOff)
-    if (!ctx->persistOn && ctx->persistWhyOff == 2 && ctx->persistBackoff > 0 && --ctx->persistBackoff == 0) { ctx->persistOn = true; ctx->persistWhyOff = 0; }
+    if (!ctx->ss.persistOn && ctx->ss.persistWhyOff == 2 && ctx->ss.persistBackoff > 0 && --ctx->ss.persistBackoff == 0) { ctx->ss.persistOn = true; ctx->ss.persistWhyOff = 0; }
     PsOutcome outcome = PsOutcome::NotRun;
     if (fused && persist_ok(ctx)) { int prc = solve_persist(ctx, kind, start, spec, outcome); if (prc) return prc; }
     const bool viaPersist = outcome == PsOutcome::Done || outcome == PsOutcome::Stalled || outcome == PsOutcome::Unfinished;
@@ -1095,7 +1107,7 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
     if (ctx->solveFail) done = false;
     guess = it;        // (launched iterations; collect_stats replaces it with the iterations actually needed)
 
-    ctx->solveDone[kind] = done;
+    ctx->ss.solveDone[kind] = done;
     ctx->specValid = spec && ctx->specOn && outcome == PsOutcome::Done && done;       // (the device decided the same from the same words: k_cocg_persist's exit)
     return solve_epilogue(ctx, kind, x, done, deferEnd, guard);
 }
@@ -1160,12 +1172,12 @@ int evaluate(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pred, d
         // done by the first attempt's first kernel -- is not repeated, no warm start from fields in an undefined state
         ctx->persistTimedOut = false;
         fprintf(stderr, "libhmcmt_hip: a wait of the persistent solve kernel timed out (the device is shared?); this context continues with the "
-                        "launch-per-phase loop for the next %ld solves, the evaluation is redone\n", ctx->persistBackoff);
+                        "launch-per-phase loop for the next %ld solves, the evaluation is redone\n", ctx->ss.persistBackoff);
         (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->side);
         (void)hipGetLastError();
         ctx->statsPending = false; ctx->sidePending = false; ctx->sensWaitPending = ctx->extAWaitPending = false;
-        ctx->haveFwd = ctx->haveAdj = false; ctx->lastItFwd = ctx->lastItAdj = 0;
-        ctx->lfStep.on = 0;
+        ctx->ss.haveFwd = ctx->ss.haveAdj = false; ctx->ss.lastItFwd = ctx->ss.lastItAdj = 0;
+        ctx->ss.lfStep.on = 0;
         ctx->solveFail = 0;
         host_word(ctx, HW_FAIL) = 0;
         rc = evaluate_once(ctx, d_m, wantGrad, d_pred, d_misfit, d_grad);
@@ -1175,7 +1187,7 @@ int evaluate(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pred, d
 int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pred, double* d_misfit, double* d_grad) {
     View v = ctx->v;
     v.m = d_m;
-    v.dbg = ctx->dbgFlags;
+    v.dbg = ctx->ss.dbgFlags;
     if (d_pred) v.pred = reinterpret_cast<cplx*>(d_pred);
     if (d_grad) v.grad = d_grad;
     hipStream_t st = ctx->stream;
@@ -1184,21 +1196,21 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
     ctx->jvp.valid = false;             // (the evaluation arrays leave the linearisation point of hmcmt_linearize)
     ctx->stats = hmcmt_stats{};
     ctx->stats.nsystems = S;
-    ++ctx->evalCount;
-    ctx->sv.cntActive = (ctx->profMask && ctx->evalCount % ctx->profEvery == 0) ? ctx->d_cnt : nullptr;
+    ++ctx->ss.evalCount;
+    ctx->sv.cntActive = (ctx->ss.profMask && ctx->ss.evalCount % ctx->profEvery == 0) ? ctx->d_cnt : nullptr;
     if (ctx->sv.cntActive) ++ctx->profEvals;
     ctx->evalSampled = ctx->sv.cntActive != nullptr;
-    ctx->guardNow = !ctx->opt.verify && ctx->guardEvery > 0 && ctx->evalCount % ctx->guardEvery == 0;
-    if (ctx->guardDropWarm) { ctx->guardDropWarm = false; ctx->haveFwd = ctx->haveAdj = false; }
+    ctx->guardNow = !ctx->opt.verify && ctx->ss.guardEvery > 0 && ctx->ss.evalCount % ctx->ss.guardEvery == 0;
+    if (ctx->ss.guardDropWarm) { ctx->ss.guardDropWarm = false; ctx->ss.haveFwd = ctx->ss.haveAdj = false; }
     const int nodes = v.NZP * (v.ny + 1);
     const size_t vecBytes = (size_t)S * v.vstride * sizeof(cplx);
     // initial guesses (options.warm_start): verify checks against the cold right-hand side
     // (test hook hmcmt_debug_flags bit 0: the Dirichlet values stay those of the previous evaluation -- they live in the
     //  boundary nodes of X, so the forward solve must start from the previous fields)
-    const bool freezeBC = (ctx->dbgFlags & 1) && ctx->haveFwd;
+    const bool freezeBC = (ctx->ss.dbgFlags & 1) && ctx->ss.haveFwd;
     if (freezeBC && ctx->opt.verify) { ctx->err = "hmcmt_debug_flags: frozen boundary values and options.verify exclude each other"; return HMCMT_EINVAL; }
-    const bool warmF = (ctx->opt.warm_start && ctx->haveFwd && !ctx->opt.verify) || freezeBC;
-    const bool warmA = ctx->opt.warm_start && ctx->haveAdj && !ctx->opt.verify;
+    const bool warmF = (ctx->opt.warm_start && ctx->ss.haveFwd && !ctx->opt.verify) || freezeBC;
+    const bool warmA = ctx->opt.warm_start && ctx->ss.haveAdj && !ctx->opt.verify;
     const bool extrap = ctx->opt.warm_start == 2 && !ctx->opt.verify;
     // start of a solve on the default path: residual and first pre-smoothing pass in one launch (k_resid_pre)
     const size_t startLds = (size_t)(2 * ctx->sv.RT + 6) * v.NYP * sizeof(cplx);
@@ -1210,7 +1222,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
     const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && !ctx->opt.verify && persist_ok(ctx);
     ctx->sv.sweeps = sweepsF;
     ctx->stats.smoother_sweeps = 10 * sweepsF + (wantGrad ? sweepsA : 0);
-    ctx->sweepsUsed[0] = sweepsF; if (wantGrad) ctx->sweepsUsed[1] = sweepsA;
+    ctx->ss.sweepsUsed[0] = sweepsF; if (wantGrad) ctx->ss.sweepsUsed[1] = sweepsA;
     {
         ProfScope ps(ctx, 4);
         // conductivities and their lateral means, one wave per cell row (meshes of whole rows: always; k_sigma + k_rowmean otherwise)
@@ -1234,13 +1246,13 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
         // residual: 860 -> 870 steps/s on the straight-line trajectories, +0.5 % elsewhere; the other placement was removed in round 4).
         hipStream_t sA = ctx->side, sB = st;
         // (a position update of the device-resident leapfrog that is still due rides along: leapfrog_core)
-        if (ctx->lfStep.on && !(rows && ctx->lfStep.L.m == v.m)) {
-            hipLaunchKernelGGL(k_lf_step, dim3((ctx->lfStep.L.n + 127) / 128), dim3(128), 0, st, ctx->lfStep.L, ctx->lfStep.dt, ctx->lfStep.lo, ctx->lfStep.hi);
-            ctx->lfStep.on = 0;
+        if (ctx->ss.lfStep.on && !(rows && ctx->ss.lfStep.L.m == v.m)) {
+            hipLaunchKernelGGL(k_lf_step, dim3((ctx->ss.lfStep.L.n + 127) / 128), dim3(128), 0, st, ctx->ss.lfStep.L, ctx->ss.lfStep.dt, ctx->ss.lfStep.lo, ctx->ss.lfStep.hi);
+            ctx->ss.lfStep.on = 0;
         }
-        if (rows) hipLaunchKernelGGL(k_sigma_rows, dim3(v.nz), dim3(64), 0, st, v, ctx->lfStep);
+        if (rows) hipLaunchKernelGGL(k_sigma_rows, dim3(v.nz), dim3(64), 0, st, v, ctx->ss.lfStep);
         else hipLaunchKernelGGL(k_sigma, grid1(v.nCell, 256), dim3(256), 0, st, v);
-        ctx->lfStep.on = 0;
+        ctx->ss.lfStep.on = 0;
         HIPCHK(hipEventRecord(ctx->evModel, st));
         // Two chains start from sigma and meet at the forward residual (in-kernel timeline HMCMT_TICKS=1; near the true model
         // the first preconditioner application starts 92 us after k_sigma_rows, 131 us at the start of round 3):
@@ -1268,7 +1280,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             if (!rows) hipLaunchKernelGGL(k_rowmean, dim3(v.nz), dim3(64), 0, sp, v);
             if (pivots)
                 hipLaunchKernelGGL(k_pivot, dim3((v.ny - 1 + 63) / 64, S), dim3(64), 4 * (size_t)v.NZP * sizeof(double), sp, v,
-                                   ctx->opt.fdm_precision == 0 ? ctx->d_invp32 : (float2*)nullptr);
+                                   ctx->opt.fdm_precision == 0 ? ctx->inst.d_invp32 : (float2*)nullptr);
             else
                 hipLaunchKernelGGL(k_fdm_z, grid1(2 * v.NZP, 64), dim3(64), 0, sp, v);
             return hipEventRecord(ctx->evPiv, sp);
@@ -1286,7 +1298,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             const bool lazy = ctx->lazyDinv && inKernelStart;
             hipLaunchKernelGGL(k_coef_all, dim3(lazy ? std::max(ctx->sv.NB, (int)std::min<long>(512, (v.vstride + VBLOCK - 1) / VBLOCK)) : ctx->sv.NB, lazy ? 2 : S), dim3(VBLOCK), 0, sB, v, ctx->sv, ctx->jacobiW, const_cast<float4*>(ctx->sv.cf32),
                                lazy ? v.nFreq : 1);
-            ctx->dinvValid = !lazy;
+            ctx->inst.dinvValid = !lazy;
         } else {
             hipLaunchKernelGGL(k_coef, grid1(nodes, 256), dim3(256), 0, sB, v, 0, 1, 1, 0);
             if (ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI) {
@@ -1348,13 +1360,13 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
         if (ctx->sideSens && !ctx->sidePending) HIPCHK(hipStreamSynchronize(ctx->side));
         ctx->sensWaitPending = false;
         HIPCHK(hipEventRecord(ctx->evRec, st));
-        ctx->haveFwd = false;
+        ctx->ss.haveFwd = false;
         rc = collect_stats(ctx, false);
         return rc ? rc : finish_status(ctx);
     }
     const auto hostT1 = std::chrono::steady_clock::now();
     launch_adjoint_side(ctx);            // (no-op when the solve has already done it)
-    ctx->haveFwd = (rc == 0 && ctx->solveDone[0]);
+    ctx->ss.haveFwd = (rc == 0 && ctx->ss.solveDone[0]);
     if (rc) return rc;
     if (!specFwd) {
         ProfScope ps(ctx, 5);
@@ -1374,7 +1386,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
                 if (!sparseSrc) HIPCHK(hipMemsetAsync(v.R, 0, vecBytes, st));
                 hipLaunchKernelGGL(k_src, dim3(nsrcBlocks + (v.ny + 127) / 128, S), dim3(128), 0, st, v, misfitPtr, nsrcBlocks);
             }
-            if (ctx->guardNow) HIPCHK(hipMemcpyAsync(ctx->d_b, v.R, vecBytes, hipMemcpyDeviceToDevice, st));
+            if (ctx->guardNow) HIPCHK(hipMemcpyAsync(ctx->inst.d_b, v.R, vecBytes, hipMemcpyDeviceToDevice, st));
             if (ctx->extAWaitPending) { ctx->extAWaitPending = false; HIPCHK(hipStreamWaitEvent(st, ctx->evExtA, 0)); }   // (a forward solve too short to have issued it)
             if (inKernelStart && persist_ok(ctx)) {
                 // (warm start: r = b - A lambda0 with b on the receiver layer's two node rows; cold: the buffer k_src has filled IS the residual)
@@ -1400,14 +1412,14 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             { const int nwbx = (v.nz + v.ny + 127) / 128, ngcx = (v.nCell + 127) / 128;       // (k_wb + k_gradcell: one launch)
               hipLaunchKernelGGL(k_wb_gradcell, dim3(nwbx * S + ngcx * 2 * GRAD_NG), dim3(128), 0, st, vg, solve_rec(ctx, 1), nwbx, ngcx); }
             hipEventRecord(ctx->evRec, st);
-            hipLaunchKernelGGL(k_bcsens_contract, dim3((BCC_L * v.nz + 127) / 128, 2, S), dim3(128), 0, st, vg, ctx->lfMom.on ? ctx->lfMom.L.part : (double*)nullptr);
-            hipLaunchKernelGGL(k_gradfinal, grid1(GF_L * v.nAC, 128), dim3(128), 0, st, vg, ctx->lfMom);
+            hipLaunchKernelGGL(k_bcsens_contract, dim3((BCC_L * v.nz + 127) / 128, 2, S), dim3(128), 0, st, vg, ctx->ss.lfMom.on ? ctx->ss.lfMom.L.part : (double*)nullptr);
+            hipLaunchKernelGGL(k_gradfinal, grid1(GF_L * v.nAC, 128), dim3(128), 0, st, vg, ctx->ss.lfMom);
         };
         rc = solve(ctx, v.Lam, 1, true, specPlain ? &specA : nullptr);
         const bool specAdj = ctx->specValid;
         const auto hostT2 = std::chrono::steady_clock::now();
         if (warmA && fusedStart) std::swap(ctx->sv.r, ctx->sv.r2);
-        ctx->haveAdj = (rc == 0 && ctx->solveDone[1]);
+        ctx->ss.haveAdj = (rc == 0 && ctx->ss.solveDone[1]);
         if (rc) return rc;
         if (ctx->solveFail) {             // (as after the forward solve: no gradient from a failed adjoint, and the caller knows NOW)
             if (ctx->sensWaitPending) { ctx->sensWaitPending = false; HIPCHK(hipStreamSynchronize(ctx->side)); }   // (the tables of the side stream: not into the next evaluation)
@@ -1422,13 +1434,13 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             { const int nwbx = (v.nz + v.ny + 127) / 128, ngcx = (v.nCell + 127) / 128;       // (k_wb (+ the adjoint solve's records) + k_gradcell: one launch)
               hipLaunchKernelGGL(k_wb_gradcell, dim3(nwbx * S + ngcx * 2 * GRAD_NG), dim3(128), 0, st, v, solve_rec(ctx, 1), nwbx, ngcx); }
             HIPCHK(hipEventRecord(ctx->evRec, st));                        // behind the records of the last solve
-            hipLaunchKernelGGL(k_bcsens_contract, dim3((BCC_L * v.nz + 127) / 128, 2, S), dim3(128), 0, st, v, ctx->lfMom.on ? ctx->lfMom.L.part : (double*)nullptr);
-            hipLaunchKernelGGL(k_gradfinal, grid1(GF_L * v.nAC, 128), dim3(128), 0, st, v, ctx->lfMom);
+            hipLaunchKernelGGL(k_bcsens_contract, dim3((BCC_L * v.nz + 127) / 128, 2, S), dim3(128), 0, st, v, ctx->ss.lfMom.on ? ctx->ss.lfMom.L.part : (double*)nullptr);
+            hipLaunchKernelGGL(k_gradfinal, grid1(GF_L * v.nAC, 128), dim3(128), 0, st, v, ctx->ss.lfMom);
         }
         if (ctx->wantTicks) ctx->hostUs[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT2).count();
     }
     HIPCHK(hipGetLastError());
-    ctx->haveModel = true;
+    ctx->ss.haveModel = true;
     return 0;
 }
 
@@ -1462,17 +1474,17 @@ static void pack_queues(const float* cost, int S, int NQ, int* tab) {
     if (queues_makespan(cost, S, NQ, tab) > queues_makespan(cost, S, NQ, nullptr)) for (int i = 0; i < S; ++i) tab[i] = i;
 }
 void persist_balance(hmcmt_ctx* ctx, int kind) {
-    const int S = ctx->sv.S, NQ = 8 * ctx->persistSlots;
+    const int S = ctx->sv.S, NQ = 8 * ctx->inst.persistSlots;
     if (!ctx->psBalance || !ctx->d_psOrder || NQ <= 0 || S <= NQ) return;
     // (costs: the mean of the last solve's counts and the costs before it -- the counts of one system wander by one or two from
     //  step to step, and a table made from one solve's noise is a worse guess for the next than one made from several)
-    std::vector<float>& cost = ctx->psCost[kind];
-    const int* last = ctx->itersLast.data() + (size_t)kind * S;
+    std::vector<float>& cost = ctx->ss.psCost[kind];
+    const int* last = ctx->ss.itersLast.data() + (size_t)kind * S;
     if (cost.empty()) cost.assign(last, last + S);
     else for (int i = 0; i < S; ++i) cost[i] = ctx->psSmooth * cost[i] + (1.f - ctx->psSmooth) * (float)last[i];
     std::vector<int> tab(S);
     pack_queues(cost.data(), S, NQ, tab.data());
-    std::vector<int>& cur = ctx->psOrder[kind];
+    std::vector<int>& cur = ctx->ss.psOrder[kind];
     const double now = queues_makespan(cost.data(), S, NQ, cur.empty() ? nullptr : cur.data()), lpt = queues_makespan(cost.data(), S, NQ, tab.data());
     if (now <= 1.01 * lpt) return;
     std::memcpy(ctx->h_psOrder + (size_t)kind * S, tab.data(), sizeof(int) * S);
@@ -1482,20 +1494,20 @@ void persist_balance(hmcmt_ctx* ctx, int kind) {
         return;
     }
     cur = tab;
-    ++ctx->psRebalanced;
+    ++ctx->ss.psRebalanced;
 }
 
 // the per-solve records (written by k_solve_end into mapped pinned memory) -> statistics; the caller has waited for them
 void parse_stats(hmcmt_ctx* ctx, bool withAdjoint) {
     const int S = ctx->v.S, nk = withAdjoint ? 2 : 1;
-    const int* h_iters = reinterpret_cast<const int*>(ctx->h_rec);
+    const int* h_iters = reinterpret_cast<const int*>(ctx->inst.h_rec);
     const int* h_status = h_iters + 2 * S;
-    const double* h_err = ctx->h_rec + 2 * S;
+    const double* h_err = ctx->inst.h_rec + 2 * S;
     for (int kind = 0; kind < nk; ++kind) {
         int mx = 0, sum = 0;
         for (int s = 0; s < S; ++s) {
             const int itv = h_iters[kind * S + s];
-            ctx->itersLast[kind * S + s] = itv;
+            ctx->ss.itersLast[kind * S + s] = itv;
             mx = std::max(mx, itv); sum += itv;
             if (h_status[kind * S + s] != 0 && ctx->stats.status == 0) ctx->stats.status = h_status[kind * S + s];
             if (h_err[kind * S + s] > ctx->stats.err_est_max) ctx->stats.err_est_max = h_err[kind * S + s];
@@ -1505,34 +1517,34 @@ void parse_stats(hmcmt_ctx* ctx, bool withAdjoint) {
         else { ctx->stats.iters_adj_max = mx; ctx->stats.iters_adj_sum = sum; }
         // first convergence poll of the next evaluation: where this one actually finished (the loop itself only
         // knows how many iterations it launched, which includes the empty ones behind the last poll)
-        if (ctx->solveDone[kind] && mx > 0) (kind == 0 ? ctx->lastItFwd : ctx->lastItAdj) = mx;
-        if (ctx->solveDone[kind] && mx > 0 && ctx->stats.status == 0 && ctx->persistCW && ctx->persistOn) persist_balance(ctx, kind);
+        if (ctx->ss.solveDone[kind] && mx > 0) (kind == 0 ? ctx->ss.lastItFwd : ctx->ss.lastItAdj) = mx;
+        if (ctx->ss.solveDone[kind] && mx > 0 && ctx->stats.status == 0 && ctx->persistCW && ctx->ss.persistOn) persist_balance(ctx, kind);
         // ... and the smoother of the next solve of this kind (pick_sweeps): two sweeps per side when this one was long
-        if (ctx->sweepsMode == 0 && ctx->solveDone[kind] && mx > 0) {
-            int& next = ctx->sweepsKind[kind];
-            if (ctx->sweepsUsed[kind] == 1) {
-                if (ctx->sweepsProbe[kind]) {                 // a probe with one sweep: keep it if it is the cheaper one
-                    ctx->sweepsProbe[kind] = false;
-                    const double cost2 = (ctx->persistCW && ctx->persistOn) ? (ctx->persistCS > 1 ? SWEEPS2_COST_PERSIST_CS2 : SWEEPS2_COST_PERSIST) : SWEEPS2_COST;
-                    next = (double)mx <= cost2 * ctx->sweepsCount2[kind] ? 1 : 2;
+        if (ctx->sweepsMode == 0 && ctx->ss.solveDone[kind] && mx > 0) {
+            int& next = ctx->ss.sweepsKind[kind];
+            if (ctx->ss.sweepsUsed[kind] == 1) {
+                if (ctx->ss.sweepsProbe[kind]) {                 // a probe with one sweep: keep it if it is the cheaper one
+                    ctx->ss.sweepsProbe[kind] = false;
+                    const double cost2 = (ctx->persistCW && ctx->ss.persistOn) ? (ctx->persistCS > 1 ? SWEEPS2_COST_PERSIST_CS2 : SWEEPS2_COST_PERSIST) : SWEEPS2_COST;
+                    next = (double)mx <= cost2 * ctx->ss.sweepsCount2[kind] ? 1 : 2;
                 } else if (mx > ctx->sweepsUp) next = 2;
             } else {
-                ctx->sweepsCount2[kind] = mx;
+                ctx->ss.sweepsCount2[kind] = mx;
                 if (mx < ctx->sweepsDown) next = 1;
-                else if (++ctx->sweepsSince[kind] >= SWEEPS_PROBE_EVERY && mx < ctx->sweepsUp) {
-                    ctx->sweepsSince[kind] = 0; ctx->sweepsProbe[kind] = true; next = 1;
+                else if (++ctx->ss.sweepsSince[kind] >= SWEEPS_PROBE_EVERY && mx < ctx->sweepsUp) {
+                    ctx->ss.sweepsSince[kind] = 0; ctx->ss.sweepsProbe[kind] = true; next = 1;
                 }
             }
         }
-        if (!ctx->solveDone[kind] && ctx->stats.status == 0) ctx->stats.status = HMCMT_ENOCONV;
+        if (!ctx->ss.solveDone[kind] && ctx->stats.status == 0) ctx->stats.status = HMCMT_ENOCONV;
     }
     if (ctx->stats.status != 0) {
         // a failed evaluation (breakdown, non-finite values, iteration cap) must not seed the next one: its fields may
         // hold Inf/NaN, and so may the extrapolation history -- the next call starts cold
-        ctx->haveFwd = ctx->haveAdj = false;
-        ctx->lastItFwd = ctx->lastItAdj = 0;
+        ctx->ss.haveFwd = ctx->ss.haveAdj = false;
+        ctx->ss.lastItFwd = ctx->ss.lastItAdj = 0;
     }
-    if (!withAdjoint) for (int s = 0; s < S; ++s) ctx->itersLast[S + s] = 0;
+    if (!withAdjoint) for (int s = 0; s < S; ++s) ctx->ss.itersLast[S + s] = 0;
 }
 
 // after an evaluation: wait for the whole stream, then the statistics
@@ -1692,7 +1704,7 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
     if (ctx->h_stall) hipHostFree(ctx->h_stall);
     if (ctx->h_prog) hipHostFree(ctx->h_prog);
 
-    if (ctx->h_rec) hipHostFree(ctx->h_rec);
+    if (ctx->inst.h_rec) hipHostFree(ctx->inst.h_rec);
     if (ctx->h_stage) hipHostFree(ctx->h_stage);
     if (ctx->jac.h_rows) hipHostFree(ctx->jac.h_rows);
     if (ctx->h_lfFlag) hipHostFree(ctx->h_lfFlag);
@@ -1759,7 +1771,7 @@ static bool persist_shape(const hmcmt_ctx* ctx, int twist, int& cuPerXcd, int& G
 }
 static int persist_setup(hmcmt_ctx* ctx) {
     const Solver& k = ctx->sv;
-    if (const char* e = getenv("HMCMT_PERSIST")) ctx->persistOn = e[0] != '0';
+    if (const char* e = getenv("HMCMT_PERSIST")) ctx->ss.persistOn = e[0] != '0';
     if (const char* e = getenv("HMCMT_PS_START")) ctx->psInKernelStart = e[0] != '0';
     if (const char* e = getenv("HMCMT_PS_SPIN")) ctx->persistSpin = (unsigned)std::max(1024l, atol(e));
     ctx->persistCW = 0;
@@ -1778,13 +1790,13 @@ static int persist_setup(hmcmt_ctx* ctx) {
     // keeps the generic kernels (A/B runs, tests)
     int wk = k.NYP;
     if (const char* e = getenv("HMCMT_PERSIST_WIDTHK")) if (e[0] == '0') wk = 0;
-    ctx->persistSlots = std::max(1, std::min((k.S + 7) / 8, cuPerXcd / G));
-    ctx->persistFillsShare = ctx->persistSlots * G >= cuPerXcd;       // (no CU of this context's share left over beside a solve: launch_adjoint_side)
+    ctx->inst.persistSlots = std::max(1, std::min((k.S + 7) / 8, cuPerXcd / G));
+    ctx->persistFillsShare = ctx->inst.persistSlots * G >= cuPerXcd;       // (no CU of this context's share left over beside a solve: launch_adjoint_side)
     ctx->persistLds = lds;
-    ctx->psyncBytes = ((size_t)(32 * 8 * ctx->persistSlots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
+    ctx->inst.psyncBytes = ((size_t)(32 * 8 * ctx->inst.persistSlots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
     void* q = nullptr;
-    HIPCHK(hipMalloc(&q, ctx->psyncBytes));
-    HIPCHK(hipMemset(q, 0, ctx->psyncBytes));
+    HIPCHK(hipMalloc(&q, ctx->inst.psyncBytes));
+    HIPCHK(hipMemset(q, 0, ctx->inst.psyncBytes));
     {
         void* gq = nullptr;
         HIPCHK(hipMalloc(&gq, 2 * sizeof(int)));
@@ -1793,23 +1805,23 @@ static int persist_setup(hmcmt_ctx* ctx) {
         ctx->d_gate = reinterpret_cast<int*>(gq);
     }
     ctx->allocs.push_back(q);
-    ctx->d_psync = reinterpret_cast<unsigned*>(q);
+    ctx->inst.d_psync = reinterpret_cast<unsigned*>(q);
     {
         const size_t recBytes = (size_t)k.S * MAXNB * 2 * 8 * 16;
         void* r = nullptr;
         HIPCHK(hipMalloc(&r, recBytes));
         HIPCHK(hipMemset(r, 0, recBytes));
         ctx->allocs.push_back(r);
-        ctx->d_prec = reinterpret_cast<u4v*>(r);
+        ctx->inst.d_prec = reinterpret_cast<u4v*>(r);
     }
     {
         void* pc = nullptr;
         HIPCHK(hipMalloc(&pc, sizeof(PsConst)));
         ctx->allocs.push_back(pc);
-        ctx->d_psConst = reinterpret_cast<PsConst*>(pc);
-        ctx->psConstValid = false;
+        ctx->inst.d_psConst = reinterpret_cast<PsConst*>(pc);
+        ctx->inst.psConstValid = false;
     }
-    if (k.S > 8 * ctx->persistSlots) {          // (more than one round of systems: persist_balance)
+    if (k.S > 8 * ctx->inst.persistSlots) {          // (more than one round of systems: persist_balance)
         void* po = nullptr;
         HIPCHK(hipMalloc(&po, 2 * sizeof(int) * (size_t)k.S));
         ctx->allocs.push_back(po);
@@ -1824,7 +1836,7 @@ static int persist_setup(hmcmt_ctx* ctx) {
         HIPCHK(hipMalloc(&y2, nb));
         HIPCHK(hipMemset(y2, 0, nb));
         ctx->allocs.push_back(y2);
-        ctx->d_yhat2 = reinterpret_cast<float2*>(y2);
+        ctx->inst.d_yhat2 = reinterpret_cast<float2*>(y2);
     }
     // the four-strip kernel where it applies: one column part, 32-mode slabs, a column tile of the transforms per wave, the slab
     // sweeps' chunks of four rows covering half the rows; HMCMT_PERSIST_STRIPS=2 keeps the two-half kernel (A/B)
@@ -1914,7 +1926,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
         else (void)hipGetLastError();
         if (const char* ew = getenv("HMCMT_JACOBI_W")) ctx->jacobiW = std::min(1.2, std::max(0.1, atof(ew)));
         if (const char* es = getenv("HMCMT_SWEEPS")) ctx->sweepsMode = std::max(0, std::min(2, atoi(es)));     // 0 / "auto": per solve
-        if (const char* eg = getenv("HMCMT_GUARD_EVERY")) ctx->guardEvery = std::max(0, atoi(eg));
+        if (const char* eg = getenv("HMCMT_GUARD_EVERY")) ctx->ss.guardEvery = std::max(0, atoi(eg));
         if (const char* eg = getenv("HMCMT_SPEC")) ctx->specOn = eg[0] != '0';
         if (const char* eg = getenv("HMCMT_GUARD_LIMIT")) ctx->guardLimit = atof(eg);
         if (const char* es = getenv("HMCMT_SWEEPS_UP")) ctx->sweepsUp = std::max(1, atoi(es));
@@ -1965,7 +1977,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
         ctx->noSigmaRows = getenv("HMCMT_NO_SIGMA_ROWS") != nullptr;
         ctx->noCoefAll = getenv("HMCMT_NO_COEF_ALL") != nullptr;
         if (const char* el = getenv("HMCMT_LAZY_DINV")) ctx->lazyDinv = el[0] != '0';
-        if (const char* ed = getenv("HMCMT_DEBUG_FLAGS")) ctx->dbgFlags = atoi(ed);                  // (measurement only: hmcmt_debug_flags)
+        if (const char* ed = getenv("HMCMT_DEBUG_FLAGS")) ctx->ss.dbgFlags = atoi(ed);                  // (measurement only: hmcmt_debug_flags)
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fdm_fwd<FW_NTW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_fdm_fwd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess)
             ctx->maxLds = 160 * 1024;
@@ -2067,7 +2079,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     DA(v.sensDz1, S * 3 * (size_t)h.nz) DA(v.sensZ1, S * 3) DA(v.sensDead, S * 3)
     DA(v.qPart, S * h.ny) DA(v.gPart, 2 * (size_t)h.nCell) DA(v.gPartG, 2 * GRAD_NG * (size_t)h.nCell) DA(v.grad, h.nAC)
     DA(ctx->d_m, h.nAC) DA(ctx->d_misfit, 1) DA(ctx->d_cnt, 1)
-    for (int q : h.sysOn) ctx->nSysOn += q;
+    for (int q : h.sysOn) ctx->ss.nSysOn += q;
     for (int kd = 0; kd < 2; ++kd) { DA(ctx->d_prevField[kd], (EXT_NP - 1) * S * VS) DA(ctx->d_mHist[kd], (EXT_NP + 1) * (size_t)h.nAC) DA(ctx->d_ext[kd], EXT_LEN) }
     Solver& k = ctx->sv;
     k.S = h.S; k.NYP = h.NYP; k.NZP = h.NZP; k.ny = h.ny; k.nz = h.nz; k.nFreq = h.nFreq; k.vstride = v.vstride;
@@ -2129,14 +2141,14 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     { float4* cf = nullptr; if ((rc = dalloc(ctx, &cf, 2 * 2 * VS))) return rc; k.cf32 = cf; }
     k.r = v.R;
     DA(k.p, S * VS) DA(k.q, S * VS) DA(k.z, S * VS) DA(k.y, S * VS) DA(k.t, S * VS) DA(k.dinv, S * VS)
-    DA(k.t32, S * VS + 64) DA(k.y32, S * VS + 64) DA(ctx->d_invp32, S * VS)
+    DA(k.t32, S * VS + 64) DA(k.y32, S * VS + 64) DA(ctx->inst.d_invp32, S * VS)
     DA(k.z32, S * VS) DA(k.p32a, S * VS) DA(k.p32b, S * VS) DA(k.zs32, S * VS) DA(k.z4_32, S * VS) DA(k.t2_32, S * VS) DA(k.partR, S * MAXNB) DA(k.dinv32, S * VS)
     DA(k.p2, S * VS) DA(k.r2, S * VS) DA(k.partPQ, S * MAXNB) DA(k.rho2, 2 * S)
-    k.invp32 = ctx->d_invp32;
-    DA(k.partA, S * MAXNB) DA(k.partB, S * MAXNB) DA(ctx->d_partZZ, S * MAXNB)
-    DA(ctx->d_partRes, S * MAXNB) DA(ctx->d_partBn, S * MAXNB)
+    k.invp32 = ctx->inst.d_invp32;
+    DA(k.partA, S * MAXNB) DA(k.partB, S * MAXNB) DA(ctx->inst.d_partZZ, S * MAXNB)
+    DA(ctx->inst.d_partRes, S * MAXNB) DA(ctx->inst.d_partBn, S * MAXNB)
     DA(k.rho, S) DA(k.alphaBeta, S) DA(k.active, S) DA(k.iters, S) DA(k.status, S) DA(k.nactive, 1) DA(k.errEst, S) DA(k.errRef, S) DA(k.errRefIt, S)
-    DA(ctx->d_b, S * VS)
+    DA(ctx->inst.d_b, S * VS)
     DA(ctx->d_fieldsOut, (size_t)h.nFreq * (h.ny + 1) * (h.nz + 1))
 #undef DA
     HIPCHK(hipHostMalloc((void**)&ctx->h_nactive, sizeof(int), hipHostMallocMapped));
@@ -2150,11 +2162,11 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     HIPCHK(hipHostMalloc((void**)&ctx->h_prog, sizeof(int), hipHostMallocMapped));
     *ctx->h_prog = 0;
     HIPCHK(hipHostGetDevicePointer((void**)&k.progHost, ctx->h_prog, 0));
-    HIPCHK(hipHostMalloc((void**)&ctx->h_rec, sizeof(double) * 4 * h.S, hipHostMallocMapped));
-    HIPCHK(hipHostGetDevicePointer((void**)&ctx->d_recHost, ctx->h_rec, 0));
+    HIPCHK(hipHostMalloc((void**)&ctx->inst.h_rec, sizeof(double) * 4 * h.S, hipHostMallocMapped));
+    HIPCHK(hipHostGetDevicePointer((void**)&ctx->inst.d_recHost, ctx->inst.h_rec, 0));
     ctx->stageDoubles = (size_t)h.nAC * 4 + (size_t)h.nData * 2 + 16;
     HIPCHK(hipHostMalloc((void**)&ctx->h_stage, sizeof(double) * ctx->stageDoubles));
-    ctx->itersLast.assign(2 * h.S, 0);
+    ctx->ss.itersLast.assign(2 * h.S, 0);
     // constant halves of the stencils: TE stiffness (mesh only), TM mass (mesh only)
     const int nodes = v.NZP * (v.ny + 1);
     hipLaunchKernelGGL(k_coef, grid1(nodes, 256), dim3(256), 0, ctx->stream, v, 1, 0, 0, 1);
@@ -2234,8 +2246,8 @@ int hmcmt_set_options(hmcmt_ctx* ctx, const hmcmt_options* o) {
     if (const char* e = options_error(o)) { ctx->err = e; return HMCMT_EINVAL; }
     if (o->fdm_precision == 1 && ctx->hp.NYP / 16 > 28) { ctx->err = "fdm_precision = 1 on a mesh wider than 447 cells (the fp64 eigen-transform holds ny + 1 <= 448 nodes)"; return HMCMT_EINVAL; }
     ctx->opt = *o;
-    ctx->lastItFwd = ctx->lastItAdj = 0;
-    ctx->haveFwd = ctx->haveAdj = false;
+    ctx->ss.lastItFwd = ctx->ss.lastItAdj = 0;
+    ctx->ss.haveFwd = ctx->ss.haveAdj = false;
     ctx->memo[0].valid = ctx->memo[1].valid = false;
     ctx->lfHaveGrad = false;            // (a gradient kept for start_grad = 1 / 2 was computed under the old options)
     ctx->jvp.valid = false;
@@ -2250,7 +2262,7 @@ int hmcmt_get_stats(const hmcmt_ctx* ctx, hmcmt_stats* out) {
 
 int hmcmt_get_iters(const hmcmt_ctx* ctx, int32_t* iters) {
     if (!ctx || !iters) return HMCMT_EINVAL;
-    for (size_t i = 0; i < ctx->itersLast.size(); ++i) iters[i] = ctx->itersLast[i];
+    for (size_t i = 0; i < ctx->ss.itersLast.size(); ++i) iters[i] = ctx->ss.itersLast[i];
     return 0;
 }
 
@@ -2377,7 +2389,7 @@ int hmcmt_forward(hmcmt_ctx* ctx, const double* m, double* pred, double* misfit)
 
 int hmcmt_get_fields(hmcmt_ctx* ctx, int32_t adjoint, double* exTE, double* hxTM) {
     if (!ctx) return HMCMT_EINVAL;
-    if (!ctx->haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
+    if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     const View& v = ctx->v;
     const int nn = (v.ny + 1) * (v.nz + 1);
@@ -2394,7 +2406,7 @@ int hmcmt_get_fields(hmcmt_ctx* ctx, int32_t adjoint, double* exTE, double* hxTM
 
 int hmcmt_profile(hmcmt_ctx* ctx, int32_t enable) {
     if (!ctx) return HMCMT_EINVAL;
-    ctx->profMask = 0;
+    ctx->ss.profMask = 0;
     ctx->evUsed = 0;
     ctx->profOverheadMs = ctx->profOverheadChainMs = 0.0;
     ctx->ivs.clear(); ctx->chainEnd = (size_t)-1;
@@ -2440,7 +2452,7 @@ int hmcmt_profile(hmcmt_ctx* ctx, int32_t enable) {
         ctx->profOverheadChainMs = std::max(0.0, (double)t[t.size() / 2] - (SPIN_US + SPIN_EDGE_US) * 1e-3);
         for (auto& e : ev) hipEventDestroy(e);
     }
-    ctx->profMask = (unsigned)enable;
+    ctx->ss.profMask = (unsigned)enable;
     for (int i = 0; i < HMCMT_NCAT; ++i) { ctx->profMs[i] = 0; ctx->profN[i] = 0; }
     ctx->profStartSys = ctx->profEvals = ctx->profSolves = ctx->profSolves2 = 0;
     ctx->profSerialIts = ctx->profPersistSolves = 0;
@@ -2501,7 +2513,7 @@ int hmcmt_debug_flags(hmcmt_ctx* ctx, int32_t flags) {
     else if (flags & 4) ctx->dbgPlace = 1 + ((flags >> 8) & 0xff);   // (one-shot: the next persistent launch's first system group -- bits 8-15: the group of that index -- fails its placement check)
     if (flags & 12) ctx->dbgPlaceAdj = (flags & 16) != 0;      // (bit 4: ... of the next ADJOINT launch -- forward launches pass it by)
     flags &= 3;
-    ctx->dbgFlags = flags;
+    ctx->ss.dbgFlags = flags;
     ctx->memo[0].valid = ctx->memo[1].valid = false;      // (stored results belong to the flags they were computed under)
     ctx->lfHaveGrad = false;
     return 0;
@@ -2509,7 +2521,7 @@ int hmcmt_debug_flags(hmcmt_ctx* ctx, int32_t flags) {
 
 int hmcmt_debug_spmv(hmcmt_ctx* ctx, const double* p, double* q) {
     if (!ctx || !p || !q) return HMCMT_EINVAL;
-    if (!ctx->haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
+    if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     HIPCHK(hipMemcpy(ctx->sv.p, p, bytes, hipMemcpyHostToDevice));
@@ -2524,7 +2536,7 @@ int hmcmt_debug_spmv(hmcmt_ctx* ctx, const double* p, double* q) {
 
 int hmcmt_debug_precond(hmcmt_ctx* ctx, const double* r, double* z) {
     if (!ctx || !r || !z) return HMCMT_EINVAL;
-    if (!ctx->haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
+    if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     HIPCHK(hipMemcpy(ctx->sv.r, r, bytes, hipMemcpyHostToDevice));
@@ -2564,7 +2576,7 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
     if (!ctx || !out || nout < 0) return HMCMT_EINVAL;
     // (the caller says how many slots it has: fields are only ever appended, a caller built against an older header gets the ones it knows)
     const int64_t v[HMCMT_PERSIST_INFO_FIELDS] = {
-        ctx->persistCW, ctx->persistG, ctx->persistSlots, ctx->persistOn ? 1 : 0,
+        ctx->persistCW, ctx->persistG, ctx->inst.persistSlots, ctx->ss.persistOn ? 1 : 0,
         ctx->persistSolves, ctx->persistFallbacks,
         persist_ok(ctx) ? 1 : 0,              // would the next default-path solve use it (alone on the device, device lock held)
         ctx->persistCW ? ctx->persistMW : 0,  // modes per slab
@@ -2572,7 +2584,7 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
         ctx->persistTimeouts,                 // timed-out waits (the evaluation was redone with the launch-per-phase loop)
         ctx->shareIdx, ctx->shareCnt,         // this context's share of every XCD's CUs (hmcmt_next_cu_share)
         ctx->persistCW ? ctx->psKern[0]->strips : 0,   // strips of tile rows per column: 2 (k_cocg_persist) or 4 (k_cocg_persist4: threads = strips x threads_half)
-        ctx->persistWhyOff,                   // why the kernel is off: 0 it is not / HMCMT_PERSIST=0, 1 placement (for good), 2 a timed-out wait (tried again after the backoff)
+        ctx->ss.persistWhyOff,                   // why the kernel is off: 0 it is not / HMCMT_PERSIST=0, 1 placement (for good), 2 a timed-out wait (tried again after the backoff)
         ctx->fbKind, ctx->fbStalled};         // the last placement fallback: kind of its launch, systems it found started and still active (stalled)
     for (int i = 0; i < nout && i < HMCMT_PERSIST_INFO_FIELDS; ++i) out[i] = v[i];
     return 0;
@@ -2591,9 +2603,9 @@ int hmcmt_persist_width(const hmcmt_ctx* ctx, int32_t* width) {
 // use; *rebalanced = how often this context took a new table.
 int hmcmt_persist_order(const hmcmt_ctx* ctx, int32_t kind, int32_t* order, int64_t* rebalanced) {
     if (!ctx || kind < 0 || kind > 1) return HMCMT_EINVAL;
-    const std::vector<int>& t = ctx->psOrder[kind];
+    const std::vector<int>& t = ctx->ss.psOrder[kind];
     if (order) for (int q = 0; q < ctx->sv.S; ++q) order[q] = t.empty() ? q : t[q];
-    if (rebalanced) *rebalanced = ctx->psRebalanced;
+    if (rebalanced) *rebalanced = ctx->ss.psRebalanced;
     return 0;
 }
 
@@ -2675,7 +2687,7 @@ int hmcmt_debug_hog(hmcmt_ctx* ctx, int32_t nblocks, int32_t ms) {
 // hmcmt_debug_precond for tests/test_gpu_persist.py.  sweeps = 1 / 2 smoothing sweeps per side.
 int hmcmt_debug_persist_precond(hmcmt_ctx* ctx, int32_t sweeps, const double* r, double* z) {
     if (!ctx || !r || !z || (sweeps != 1 && sweeps != 2)) return HMCMT_EINVAL;
-    if (!ctx->haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
+    if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
     if (!ctx->persistCW) { ctx->err = "the persistent solve kernel does not apply to this problem"; return HMCMT_EINVAL; }
     if (!persist_alone(ctx)) { ctx->err = "the persistent solve kernel may not run now (another context or process holds the device)"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
@@ -2701,7 +2713,7 @@ int hmcmt_debug_persist_precond(hmcmt_ctx* ctx, int32_t sweeps, const double* r,
 // out[n..2n) = separate transform + tridiagonal kernels (complex64 pairs widened to double), n = S*vstride
 int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out) {
     if (!ctx || !t || !out) return HMCMT_EINVAL;
-    if (!ctx->haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
+    if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     Solver& k = ctx->sv;
     const size_t n = (size_t)ctx->v.S * ctx->v.vstride;
@@ -2719,7 +2731,7 @@ int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out) {
         hipLaunchKernelGGL(k_to_c64, dim3(k.NB, k.S), dim3(VBLOCK), 0, ctx->stream, k, k.r);
         for (int rep = 0; rep < 3; ++rep)
             hipLaunchKernelGGL(k_fdm_fwd<FW_NTW>, dim3(gx * k.S), dim3(64 * nw), lds, ctx->stream, k, k.t32, ctx->d_Vb, ctx->d_Vbl,
-                               ctx->d_invp32, k.y32, d_st);
+                               ctx->inst.d_invp32, k.y32, d_st);
         HIPCHK(hipStreamSynchronize(ctx->stream));
         std::vector<long long> st(8 * (size_t)nb);
         HIPCHK(hipMemcpy(st.data(), d_st, sizeof(long long) * 8 * nb, hipMemcpyDeviceToHost));
@@ -2761,7 +2773,7 @@ int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out) {
 // r't partials (re, im) of the two paths, sums[4] / [5] = of the |t|^2 partials
 int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, double* out, double* sums) {
     if (!ctx || !y || !r || !out || !sums) return HMCMT_EINVAL;
-    if (!ctx->haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
+    if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     Solver& k = ctx->sv;
     const size_t n = (size_t)ctx->v.S * ctx->v.vstride;
@@ -2807,7 +2819,7 @@ int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, doub
         std::vector<float2> hz(n);                              // both paths leave the result as complex64 in z32
         HIPCHK(hipMemcpyAsync(hz.data(), k.z32, n * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(pa.data(), k.partA, pa.size() * sizeof(cplx), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(pz.data(), ctx->d_partZZ, pz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(pz.data(), ctx->inst.d_partZZ, pz.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         for (size_t i = 0; i < n; ++i) { out[2 * (pass * n + i)] = hz[i].x; out[2 * (pass * n + i) + 1] = hz[i].y; }
         double are = 0, aim = 0, zz = 0;
@@ -3202,13 +3214,13 @@ static int leapfrog_core(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, in
         if (wm) {
             hipLaunchKernelGGL(k_mass_step, g1, b1, 0, st, lf, ctx->mass.d_x, dt, lnSigMin, lnSigMax);
         } else {
-            ctx->lfStep = LfStep{1, lf, dt, lnSigMin, lnSigMax};            // (the position update: performed by the evaluation's first kernel)
+            ctx->ss.lfStep = LfStep{1, lf, dt, lnSigMin, lnSigMax};            // (the position update: performed by the evaluation's first kernel)
             // (... and the momentum update behind the gradient, with the step bound of the next position update, by its last one)
-            ctx->lfMom = LfMom{1, lf, regParam, (k < L ? 1.0 : 0.5) * dt, dt, ++ctx->lfGen, ctx->d_lfDone};
+            ctx->ss.lfMom = LfMom{1, lf, regParam, (k < L ? 1.0 : 0.5) * dt, dt, ++ctx->lfGen, ctx->d_lfDone};
         }
         rc = evaluate(ctx, d_m, true, d_pred, d_misfit, ctx->d_g);      // (reports a failure of the step before)
-        ctx->lfStep.on = 0;
-        ctx->lfMom.on = 0;
+        ctx->ss.lfStep.on = 0;
+        ctx->ss.lfMom.on = 0;
         if (rc) return rc;
         // asynchronous, as hmcmt_grad_device_async: the next step's launches overlap this step's gradient tail
         ctx->statsPending = true;
@@ -3234,7 +3246,7 @@ static int leapfrog_flag(hmcmt_ctx* ctx) {
     ctx->lfFlagPending = false;
     if (*(volatile int*)ctx->h_lfFlag) {
         *ctx->h_lfFlag = 0;
-        ctx->haveFwd = ctx->haveAdj = false;
+        ctx->ss.haveFwd = ctx->ss.haveAdj = false;
         ctx->err = "non-finite model value during the trajectory";
         return HMCMT_EBREAKDOWN;
     }
@@ -3309,829 +3321,6 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
     return 0;
 }
 
-// ----------------------------------------------------------------------------------------------
-// explicit Jacobian (kernels_jac.h): batches by receiver -- receiver j in every system is the shape and right-hand-side sparsity of
-// the gradient's adjoint solve, so every batch is one solve(ctx, x, 1) with the in-kernel sparse start and the same fallbacks.
-// The forward fields come from a cold evaluate() at the model; everything that evaluation and the batch solves move in the
-// context (warm-start fields and extrapolation state, sweep choice, iteration guesses, statistics, evaluation count, system
-// flags) is saved in front and put back behind (JacState), so the context's next evaluation computes what it would have.
-// ----------------------------------------------------------------------------------------------
-static int jac_alloc(hmcmt_ctx* ctx) {
-    hmcmt_ctx::Jac& J = ctx->jac;
-    if (J.ready) return 0;
-    const View& v = ctx->v;
-    const int S = v.S;
-    const size_t vec = (size_t)S * v.vstride;
-    std::vector<int> perRx(v.nRx, 0);
-    for (int p = 0; p < v.nData; ++p) ++perRx[ctx->hp.datRx[p]];
-    J.maxRows = std::max(1, *std::max_element(perRx.begin(), perRx.end()));
-    int rc = 0;
-    if ((rc = dalloc(ctx, &J.lam, vec)) || (rc = dalloc(ctx, &J.xSave, vec, false)) || (rc = dalloc(ctx, &J.srcB, (size_t)S * 4)) ||
-        (rc = dalloc(ctx, &J.wL, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.wR, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.colw, (size_t)S * v.ny)) ||
-        (rc = dalloc(ctx, &J.gL, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.gR, (size_t)S * v.nz)) || (rc = dalloc(ctx, &J.qJ, (size_t)S * v.ny)) ||
-        (rc = dalloc(ctx, &J.pred, (size_t)v.nData)) || (rc = dalloc(ctx, &J.extSave, (size_t)EXT_LEN, false)) || (rc = dalloc(ctx, &J.misfit, 1)) ||
-        (rc = dalloc(ctx, &J.m, (size_t)v.nAC)) || (rc = dalloc(ctx, &J.sens, (size_t)v.nAC)) ||
-        (rc = dalloc(ctx, &J.rows, (size_t)J.maxRows * v.nAC * 2)) || (rc = dalloc(ctx, &J.list, (size_t)v.nData)) ||
-        (rc = dalloc(ctx, &J.groups, (size_t)v.nData)) ||
-        (rc = dalloc(ctx, &J.sysOn, (size_t)v.nRx * S)))
-        return rc;
-    HIPCHK(hipHostMalloc((void**)&J.h_rows, sizeof(double) * (size_t)J.maxRows * v.nAC * 2));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    J.ready = true;
-    return 0;
-}
-
-// what a Jacobian call moves in the context and puts back
-struct JacState {
-    View v; Solver sv; hmcmt_options opt; hmcmt_stats stats;
-    long long evalCount; unsigned profMask; int guardEvery, dbgFlags, nSysOn;
-    bool haveFwd, haveAdj, haveModel, guardDropWarm, solveDone[2];
-    int lastItFwd, lastItAdj, sweepsKind[2], sweepsUsed[2], sweepsCount2[2], sweepsSince[2];
-    bool sweepsProbe[2];
-    std::vector<int> itersLast, psOrder[2];
-    std::vector<float> psCost[2];
-    long psRebalanced;
-    LfStep lfStep; LfMom lfMom;
-    bool persistOn; int persistWhyOff; long persistBackoff; long long persistTimeouts, persistFallbacks;
-};
-static void jac_save(hmcmt_ctx* c, JacState& t) {
-    t.v = c->v; t.sv = c->sv; t.opt = c->opt; t.stats = c->stats;
-    t.evalCount = c->evalCount; t.profMask = c->profMask; t.guardEvery = c->guardEvery; t.dbgFlags = c->dbgFlags; t.nSysOn = c->nSysOn;
-    t.haveFwd = c->haveFwd; t.haveAdj = c->haveAdj; t.haveModel = c->haveModel; t.guardDropWarm = c->guardDropWarm;
-    t.solveDone[0] = c->solveDone[0]; t.solveDone[1] = c->solveDone[1];
-    t.lastItFwd = c->lastItFwd; t.lastItAdj = c->lastItAdj;
-    for (int k = 0; k < 2; ++k) {
-        t.sweepsKind[k] = c->sweepsKind[k]; t.sweepsUsed[k] = c->sweepsUsed[k]; t.sweepsCount2[k] = c->sweepsCount2[k];
-        t.sweepsSince[k] = c->sweepsSince[k]; t.sweepsProbe[k] = c->sweepsProbe[k]; t.psOrder[k] = c->psOrder[k]; t.psCost[k] = c->psCost[k];
-    }
-    t.itersLast = c->itersLast; t.psRebalanced = c->psRebalanced;
-    t.lfStep = c->lfStep; t.lfMom = c->lfMom;
-    t.persistOn = c->persistOn; t.persistWhyOff = c->persistWhyOff; t.persistBackoff = c->persistBackoff;
-    t.persistTimeouts = c->persistTimeouts; t.persistFallbacks = c->persistFallbacks;
-}
-static void jac_restore(hmcmt_ctx* c, const JacState& t) {
-    c->v = t.v; c->sv = t.sv; c->opt = t.opt; c->stats = t.stats;
-    c->evalCount = t.evalCount; c->profMask = t.profMask; c->guardEvery = t.guardEvery; c->dbgFlags = t.dbgFlags; c->nSysOn = t.nSysOn;
-    c->haveFwd = t.haveFwd; c->haveAdj = t.haveAdj; c->haveModel = t.haveModel; c->guardDropWarm = t.guardDropWarm;
-    c->solveDone[0] = t.solveDone[0]; c->solveDone[1] = t.solveDone[1];
-    c->lastItFwd = t.lastItFwd; c->lastItAdj = t.lastItAdj;
-    for (int k = 0; k < 2; ++k) {
-        c->sweepsKind[k] = t.sweepsKind[k]; c->sweepsUsed[k] = t.sweepsUsed[k]; c->sweepsCount2[k] = t.sweepsCount2[k];
-        c->sweepsSince[k] = t.sweepsSince[k]; c->sweepsProbe[k] = t.sweepsProbe[k]; c->psOrder[k] = t.psOrder[k]; c->psCost[k] = t.psCost[k];
-    }
-    c->itersLast = t.itersLast; c->psRebalanced = t.psRebalanced;
-    c->lfStep = t.lfStep; c->lfMom = t.lfMom;
-    // the persistent kernel's backoff after a timed-out wait counts the context's own solves: the Jacobian's do not count.  A timeout
-    // or placement failure DURING the call is an event of the device, not of the call: its state (kernel off, a new backoff) stays
-    if (c->persistTimeouts == t.persistTimeouts && c->persistFallbacks == t.persistFallbacks) {
-        c->persistOn = t.persistOn; c->persistWhyOff = t.persistWhyOff; c->persistBackoff = t.persistBackoff;
-    }
-    c->psStart = hmcmt_ctx::PsStart{};
-    c->solveBegun = c->preDone = false;
-    c->specValid = false; c->solveFail = 0; c->lpFallback = false;
-}
-
-// the records k_solve_end left for solve kind `kind` (the caller has synchronised) -> totals of the Jacobian's statistics
-static void jac_records(hmcmt_ctx* ctx, int kind, const int* on, hmcmt_stats& st) {
-    const int S = ctx->v.S;
-    const int* it = reinterpret_cast<const int*>(ctx->h_rec);
-    const int* status = it + 2 * S;
-    const double* err = ctx->h_rec + 2 * S;
-    for (int s = 0; s < S; ++s) {
-        if (!on[s]) continue;
-        const int n = it[kind * S + s];
-        if (kind == 0) { st.iters_fwd_max = std::max(st.iters_fwd_max, n); st.iters_fwd_sum += n; }
-        else { st.iters_adj_max = std::max(st.iters_adj_max, n); st.iters_adj_sum += n; }
-        st.err_est_max = std::max(st.err_est_max, err[kind * S + s]);
-        if (status[kind * S + s] != 0 && st.status == 0) st.status = status[kind * S + s];
-    }
-}
-
-// rows [row0, row0 + nrows) of J (hostJ: host memory, else device memory; null: the sensitivity into ctx->jac.sens instead)
-static int jac_run(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int wrt, double* outJ, bool hostJ, bool sens,
-                   hmcmt_stats* stOut) {
-    hmcmt_ctx::Jac& J = ctx->jac;
-    const View& v0 = ctx->v;
-    const int S = v0.S, nAC = v0.nAC, nRx = v0.nRx;
-    const bool cplxOut = !ctx->hp.rhoPhase;             // (the two data families cannot be mixed; TZY rows are complex too)
-    const int width = cplxOut ? 2 : 1;
-    // the batches: the receivers of the rows, in receiver order; per batch the data (in data order) and the systems they need
-    std::vector<std::vector<JacEntry>> lists(nRx);
-    std::vector<int> on((size_t)nRx * S, 0);
-    for (int64_t p = row0; p < row0 + nrows; ++p) {
-        const int j = ctx->hp.datRx[p], s = ctx->hp.datSys[p];
-        lists[j].push_back(JacEntry{(int)p, 0, s, ctx->hp.datKind[p]});
-        on[(size_t)j * S + s] = 1;
-    }
-    // (within a batch the data are grouped by system, in data order inside a group: one dZ row per system, JacGroup)
-    std::vector<JacEntry> flat;
-    std::vector<JacGroup> groups;
-    std::vector<int> gfirst(nRx, 0), ngroups(nRx, 0);
-    for (int j = 0; j < nRx; ++j) {
-        std::stable_sort(lists[j].begin(), lists[j].end(), [](const JacEntry& x, const JacEntry& y) { return x.s < y.s; });
-        gfirst[j] = (int)groups.size();
-        for (size_t q = 0; q < lists[j].size(); ++q) {
-            JacEntry e = lists[j][q];
-            e.row = hostJ ? (int)q : (int)(e.p - row0);      // (host: the batch's compact staging rows)
-            if (q == 0 || e.s != lists[j][q - 1].s) groups.push_back(JacGroup{(int)flat.size(), 0});
-            ++groups.back().count;
-            flat.push_back(e);
-        }
-        ngroups[j] = (int)groups.size() - gfirst[j];
-    }
-    hmcmt_stats st{};
-    st.nsystems = S;
-    if (flat.empty()) { if (stOut) *stOut = st; return 0; }
-    hipStream_t strm = ctx->stream;
-    HIPCHK(hipMemcpyAsync(J.list, flat.data(), sizeof(JacEntry) * flat.size(), hipMemcpyHostToDevice, strm));
-    HIPCHK(hipMemcpyAsync(J.sysOn, on.data(), sizeof(int) * on.size(), hipMemcpyHostToDevice, strm));
-    HIPCHK(hipMemcpyAsync(J.groups, groups.data(), sizeof(JacGroup) * groups.size(), hipMemcpyHostToDevice, strm));
-    HIPCHK(hipStreamSynchronize(strm));                  // (host vectors: the copies are complete before they go out of scope)
-    const size_t vecBytes = (size_t)S * v0.vstride * sizeof(cplx);
-
-    JacState saved;
-    jac_save(ctx, saved);
-    // the context's forward fields and extrapolation state: the Jacobian's cold forward evaluation overwrites them
-    HIPCHK(hipMemcpyAsync(J.xSave, v0.X, vecBytes, hipMemcpyDeviceToDevice, strm));
-    HIPCHK(hipMemcpyAsync(J.extSave, ctx->d_ext[0], sizeof(double) * EXT_LEN, hipMemcpyDeviceToDevice, strm));
-    auto put_back = [&]() {
-        (void)hipMemcpyAsync(ctx->v.X, J.xSave, vecBytes, hipMemcpyDeviceToDevice, strm);
-        (void)hipMemcpyAsync(ctx->d_ext[0], J.extSave, sizeof(double) * EXT_LEN, hipMemcpyDeviceToDevice, strm);
-        (void)hipStreamSynchronize(strm);
-        jac_restore(ctx, saved);
-    };
-    auto fail = [&](int rc) { const std::string e = ctx->err; put_back(); ctx->err = e; if (stOut) *stOut = st; return rc; };
-
-    // 1. forward fields at the model: a cold forward evaluation -- no guard, no sampled profiling, no test hooks, no leapfrog update
-    ctx->opt.warm_start = 0;
-    ctx->guardEvery = 0; ctx->profMask = 0; ctx->dbgFlags = 0;
-    ctx->lfStep.on = 0; ctx->lfMom.on = 0;
-    int rc = evaluate(ctx, d_m, false, reinterpret_cast<double*>(J.pred), J.misfit, nullptr);
-    if (rc) return fail(rc);
-    HIPCHK(hipStreamSynchronize(strm));
-    jac_records(ctx, 0, ctx->hp.sysOn.data(), st);
-    if (st.status) { ctx->err = st.status == HMCMT_EBREAKDOWN ? "Jacobian: the forward solve broke down" : "Jacobian: the forward solve did not converge"; return fail(st.status); }
-    // 2. what the gradient's side stream and k_rxall(wantGrad) provide: the boundary-derivative tables and the receiver functionals
-    View vj = ctx->v;
-    vj.m = d_m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
-    hipLaunchKernelGGL(k_sens_layers, dim3((vj.nz + 1 + 63) / 64, 3, S), dim3(64), 0, strm, vj);
-    hipLaunchKernelGGL(k_sens_profile, dim3((3 * S + 63) / 64), dim3(64), 0, strm, vj);
-    hipLaunchKernelGGL(k_bcsens_pre, dim3((vj.nz + 63) / 64, 3, S), dim3(64), 0, strm, vj);
-    hipLaunchKernelGGL(k_rx, grid1(S * nRx, 64), dim3(64), 0, strm, vj, 1);
-    vj.Lam = J.lam; vj.R = ctx->sv.r; vj.srcB = J.srcB; vj.wL = J.wL; vj.wR = J.wR; vj.colw = J.colw; vj.gL = J.gL; vj.gR = J.gR;
-    if (sens) HIPCHK(hipMemsetAsync(J.sens, 0, sizeof(double) * nAC, strm));
-    const int sweeps = (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2;    // (cold solves: well above the two-sweep threshold)
-    ctx->stats.smoother_sweeps = 0;
-    const int nsrc = (2 * (v0.ny + 1) + 127) / 128;
-    // 3. one batch per receiver
-    for (int j = 0; j < nRx; ++j) {
-        const int n = (int)lists[j].size();
-        if (n == 0) continue;
-        const int* onj = on.data() + (size_t)j * S;
-        vj.sysOn = J.sysOn + (size_t)j * S;
-        ctx->v.sysOn = vj.sysOn;
-        ctx->nSysOn = (int)std::count(onj, onj + S, 1);
-        for (int attempt = 0;; ++attempt) {
-            HIPCHK(hipMemsetAsync(J.lam, 0, vecBytes, strm));
-            const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 &&
-                                       !ctx->opt.verify && persist_ok(ctx);
-            if (!inKernelStart) HIPCHK(hipMemsetAsync(vj.R, 0, vecBytes, strm));     // (the whole right-hand side is the residual)
-            hipLaunchKernelGGL(k_jac_src, dim3(nsrc + (v0.ny + 127) / 128, S), dim3(128), 0, strm, vj, j, J.qJ, nsrc);
-            ctx->sv.sweeps = sweeps;
-            ctx->preDone = false;
-            if (inKernelStart) { ctx->psStart.resid = 2 + v0.zid; ctx->psStart.begin = 1; ctx->solveBegun = true; }
-            else ctx->solveBegun = false;
-            ctx->guardNow = false;
-            ctx->persistTimedOut = false;
-            const int fb0 = ctx->stats.fallback_solves;
-            rc = solve(ctx, J.lam, 1);
-            if (rc) return fail(rc);
-            if (ctx->persistTimedOut && attempt == 0) {
-                // (a wait of the persistent kernel timed out: the context is on the launch-per-phase loop now -- the batch again, there)
-                ctx->persistTimedOut = false;
-                (void)hipStreamSynchronize(strm); (void)hipGetLastError();
-                ctx->solveFail = 0; host_word(ctx, HW_FAIL) = 0;
-                ctx->stats.fallback_solves = fb0;
-                continue;
-            }
-            if (ctx->stats.fallback_solves > fb0) ++st.fallback_solves;
-            break;
-        }
-        if (ctx->solveFail || !ctx->solveDone[1]) {
-            HIPCHK(hipStreamSynchronize(strm));
-            jac_records(ctx, 1, onj, st);
-            if (st.status == 0) st.status = ctx->solveFail ? ctx->solveFail : HMCMT_ENOCONV;
-            ctx->err = st.status == HMCMT_EBREAKDOWN ? "Jacobian: an adjoint solve broke down" : "Jacobian: an adjoint solve did not converge";
-            return fail(st.status == HMCMT_EBREAKDOWN ? HMCMT_EBREAKDOWN : HMCMT_ENOCONV);
-        }
-        hipLaunchKernelGGL(k_jac_wb, dim3((v0.nz + v0.ny + 127) / 128, S), dim3(128), 0, strm, vj);
-        hipLaunchKernelGGL(k_jac_contract, dim3((BCC_L * v0.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj);
-        const JacGroup* gl = J.groups + gfirst[j];
-        const dim3 ga((nAC + 127) / 128);
-        if (sens) hipLaunchKernelGGL(k_jac_sens, ga, dim3(128), 0, strm, vj, J.list, gl, ngroups[j], j, J.qJ, wrt, J.sens);
-        else hipLaunchKernelGGL(k_jac_rows, dim3(ga.x, ngroups[j]), dim3(128), 0, strm, vj, J.list, gl, j, J.qJ, wrt, cplxOut ? 1 : 0, hostJ ? J.rows : outJ);
-        if (!sens && hostJ) HIPCHK(hipMemcpyAsync(J.h_rows, J.rows, sizeof(double) * (size_t)n * nAC * width, hipMemcpyDeviceToHost, strm));
-        HIPCHK(hipStreamSynchronize(strm));
-        jac_records(ctx, 1, onj, st);
-        if (!sens && hostJ)
-            for (int q = 0; q < n; ++q)
-                std::memcpy(outJ + (size_t)(lists[j][q].p - row0) * nAC * width, J.h_rows + (size_t)q * nAC * width, sizeof(double) * nAC * width);
-    }
-    if (sens) hipLaunchKernelGGL(k_jac_sens_final, dim3((nAC + 127) / 128), dim3(128), 0, strm, J.sens, nAC);
-    HIPCHK(hipGetLastError());
-    st.smoother_sweeps = 10 * ctx->sweepsUsed[0] + sweeps;
-    put_back();
-    if (stOut) *stOut = st;
-    return 0;
-}
-
-static int jac_check(hmcmt_ctx* ctx, const void* m, int64_t row0, int64_t nrows, int32_t wrt, const void* out) {
-    if (!m || !out) { ctx->err = "Jacobian: null model or output pointer"; return HMCMT_EINVAL; }
-    if (wrt != HMCMT_JAC_WRT_SIGMA && wrt != HMCMT_JAC_WRT_LNSIGMA) { ctx->err = "Jacobian: wrt must be HMCMT_JAC_WRT_SIGMA or HMCMT_JAC_WRT_LNSIGMA"; return HMCMT_EINVAL; }
-    if (row0 < 0 || nrows < 0 || row0 > ctx->v.nData || nrows > ctx->v.nData - row0) { ctx->err = "Jacobian: row range outside [0, nData]"; return HMCMT_EINVAL; }
-    if (ctx->statsPending) { ctx->err = "Jacobian: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
-    return 0;
-}
-
-int hmcmt_jacobian_device(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int32_t wrt, double* d_J, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = jac_check(ctx, d_m, row0, nrows, wrt, d_J)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = jac_alloc(ctx)) return rc;
-    return jac_run(ctx, d_m, row0, nrows, wrt, d_J, false, false, st);
-}
-
-int hmcmt_jacobian(hmcmt_ctx* ctx, const double* m, int64_t row0, int64_t nrows, int32_t wrt, double* J, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = jac_check(ctx, m, row0, nrows, wrt, J)) return rc;
-    for (int i = 0; i < ctx->v.nAC; ++i)
-        if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = jac_alloc(ctx)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->jac.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
-    return jac_run(ctx, ctx->jac.m, row0, nrows, wrt, J, true, false, st);
-}
-
-int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = jac_check(ctx, m, 0, ctx->v.nData, wrt, sens)) return rc;
-    for (int i = 0; i < ctx->v.nAC; ++i)
-        if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = jac_alloc(ctx)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->jac.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
-    int rc = jac_run(ctx, ctx->jac.m, 0, ctx->v.nData, wrt, nullptr, false, true, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(sens, ctx->jac.sens, sizeof(double) * ctx->v.nAC, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-// ----------------------------------------------------------------------------------------------
-// matrix-free Jacobian products (kernels_jvp.h).  hmcmt_linearize is an ordinary cold forward evaluation plus what the gradient
-// computes in front of its adjoint solve (boundary-derivative tables, receiver functionals); a product is small launches around ONE
-// solve() per direction -- forward kind for the tangent field (dense right-hand side, zero guess), adjoint kind for J^T u (the
-// gradient's sparse start) -- on the Jacobian's solution and boundary arrays, bracketed by the Jacobian's save / restore of the
-// host solve state (JacState).  A product runs no evaluation: the context's fields, history and memo are not touched at all.
-// ----------------------------------------------------------------------------------------------
-static int jvp_alloc(hmcmt_ctx* ctx) {
-    if (int rc = jac_alloc(ctx)) return rc;
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    if (P.ready) return 0;
-    const View& v = ctx->v;
-    const size_t S = (size_t)v.S;
-    int rc = 0;
-    if ((rc = dalloc(ctx, &P.m, (size_t)v.nAC)) || (rc = dalloc(ctx, &P.vin, (size_t)v.nAC)) || (rc = dalloc(ctx, &P.dSig, (size_t)v.nCell)) ||
-        (rc = dalloc(ctx, &P.out, (size_t)v.nAC)) || (rc = dalloc(ctx, &P.gPartG, (size_t)2 * GRAD_NG * v.nCell)) ||
-        (rc = dalloc(ctx, &P.qPart, S * v.ny)) || (rc = dalloc(ctx, &P.misfit, 1)) || (rc = dalloc(ctx, &P.scale, 4)) ||
-        (rc = dalloc(ctx, &P.dbcL, S * v.nz)) || (rc = dalloc(ctx, &P.dbcR, S * v.nz)) || (rc = dalloc(ctx, &P.dbcB, S * (v.ny + 1))) ||
-        (rc = dalloc(ctx, &P.jv, (size_t)v.nData)) || (rc = dalloc(ctx, &P.u, (size_t)v.nData)) || (rc = dalloc(ctx, &P.vbar, (size_t)v.nData)) ||
-        (rc = dalloc(ctx, &P.rxCoef, S * v.nRx)))
-        return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    P.ready = true;
-    return 0;
-}
-
-static int linearize_run(hmcmt_ctx* ctx) {
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    hipStream_t strm = ctx->stream;
-    P.valid = false;
-    ctx->haveFwd = false;                                // (always from a zero guess: the warm-start history starts again here)
-    int rc = evaluate(ctx, P.m, false, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    if ((rc = collect_stats(ctx, false))) return rc;     // (includes the stream synchronisation)
-    prof_collect(ctx);
-    if ((rc = finish_status(ctx))) return rc;
-    // what the gradient's side stream and k_rxall(wantGrad) provide: the boundary-derivative tables and the receiver functionals
-    View vj = ctx->v;
-    vj.m = P.m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
-    const int S = vj.S;
-    hipLaunchKernelGGL(k_sens_layers, dim3((vj.nz + 1 + 63) / 64, 3, S), dim3(64), 0, strm, vj);
-    hipLaunchKernelGGL(k_sens_profile, dim3((3 * S + 63) / 64), dim3(64), 0, strm, vj);
-    hipLaunchKernelGGL(k_bcsens_pre, dim3((vj.nz + 63) / 64, 3, S), dim3(64), 0, strm, vj);
-    hipLaunchKernelGGL(k_rx, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(strm));
-    P.valid = true;
-    ++P.gen;
-    return 0;
-}
-
-static int linearize_check(hmcmt_ctx* ctx, const void* m) {
-    if (!m) { ctx->err = "linearize: null model pointer"; return HMCMT_EINVAL; }
-    if (ctx->statsPending) { ctx->err = "linearize: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
-    return 0;
-}
-
-// one solve of a product: `fill` writes the right-hand side (again after a timed-out persistent launch, which destroys it);
-// sparseRow >= 0: the adjoint's sparse start on node rows sparseRow, sparseRow + 1 where the persistent kernel starts the solve
-static int prod_solve(hmcmt_ctx* ctx, cplx* x, int kind, int sweeps, int sparseRow, const std::function<void(bool)>& fill, hmcmt_stats& st,
-                      const int* on = nullptr /* [ctx->v.S] the systems solved (null: the problem's) */) {
-    hipStream_t strm = ctx->stream;
-    const size_t vecBytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
-    for (int attempt = 0;; ++attempt) {
-        HIPCHK(hipMemsetAsync(x, 0, vecBytes, strm));
-        const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 &&
-                                   !ctx->opt.verify && persist_ok(ctx);
-        fill(inKernelStart);
-        ctx->sv.sweeps = sweeps;
-        ctx->preDone = false;
-        if (inKernelStart) { ctx->psStart.resid = sparseRow >= 0 ? 2 + sparseRow : 0; ctx->psStart.begin = 1; ctx->solveBegun = true; }
-        else ctx->solveBegun = false;
-        ctx->guardNow = false;
-        ctx->persistTimedOut = false;
-        const int fb0 = ctx->stats.fallback_solves;
-        int rc = solve(ctx, x, kind);
-        if (rc) return rc;
-        if (ctx->persistTimedOut && attempt == 0) {
-            ctx->persistTimedOut = false;
-            (void)hipStreamSynchronize(strm); (void)hipGetLastError();
-            ctx->solveFail = 0; host_word(ctx, HW_FAIL) = 0;
-            ctx->stats.fallback_solves = fb0;
-            continue;
-        }
-        if (ctx->stats.fallback_solves > fb0) ++st.fallback_solves;
-        break;
-    }
-    HIPCHK(hipStreamSynchronize(strm));
-    jac_records(ctx, kind, on ? on : ctx->hp.sysOn.data(), st);
-    if (ctx->solveFail || !ctx->solveDone[kind]) {
-        if (st.status == 0) st.status = ctx->solveFail ? ctx->solveFail : HMCMT_ENOCONV;
-        const char* which = kind == 0 ? "tangent" : "adjoint";
-        ctx->err = std::string("Jacobian product: the ") + which + (st.status == HMCMT_EBREAKDOWN ? " solve broke down" : " solve did not converge");
-        return st.status == HMCMT_EBREAKDOWN ? HMCMT_EBREAKDOWN : HMCMT_ENOCONV;
-    }
-    return 0;
-}
-
-// J v -> vj.jv (d_v: device, [nAC])
-static int prod_tangent(hmcmt_ctx* ctx, View vj, const double* d_v, int wrt, int sweeps, hmcmt_stats& st) {
-    hipStream_t strm = ctx->stream;
-    const int S = vj.S;
-    vj.tanV = d_v;
-    vj.R = ctx->sv.r;
-    HIPCHK(hipMemsetAsync(vj.jv, 0, sizeof(cplx) * vj.nData, strm));
-    hipLaunchKernelGGL(k_jvp_dsig, grid1(vj.nCell, 256), dim3(256), 0, strm, vj, wrt);
-    hipLaunchKernelGGL(k_jvp_norm, dim3(1), dim3(1024), 0, strm, vj.dSig, (const double*)vj.sigma, (long)vj.nCell, ctx->jvp.scale);
-    vj.tanScale = ctx->jvp.scale;
-    hipLaunchKernelGGL(k_jvp_dbc, dim3((2 * vj.nz + vj.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S), dim3(64 * DBC_WAVES), 0, strm, vj);
-    auto fill = [&](bool) {
-        hipLaunchKernelGGL(k_jvp_rhs, dim3((unsigned)((vj.vstride + 255) / 256), S), dim3(256), 0, strm, vj);
-    };
-    if (int rc = prod_solve(ctx, ctx->jac.lam, 0, sweeps, -1, fill, st)) return rc;
-    vj.dF = ctx->jac.lam;
-    hipLaunchKernelGGL(k_jvp_data, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Re(J^T conj(u)) -> d_out (d_u: device, complex [nData]; d_out: device, [nAC])
-static int prod_adjoint(hmcmt_ctx* ctx, View vj, const cplx* d_u, int wrt, int sweeps, double* d_out, hmcmt_stats& st) {
-    hipStream_t strm = ctx->stream;
-    hmcmt_ctx::Jac& J = ctx->jac;
-    const int S = vj.S;
-    vj.uData = d_u;
-    vj.Lam = J.lam; vj.R = ctx->sv.r; vj.srcB = J.srcB; vj.wL = J.wL; vj.wR = J.wR; vj.colw = J.colw; vj.gL = J.gL; vj.gR = J.gR;
-    hipLaunchKernelGGL(k_jtvp_vbar, grid1(vj.nData, 256), dim3(256), 0, strm, vj);
-    hipLaunchKernelGGL(k_jvp_norm, dim3(1), dim3(1024), 0, strm, reinterpret_cast<double*>(vj.vbar), (const double*)nullptr, 2l * vj.nData, ctx->jvp.scale + 2);
-    hipLaunchKernelGGL(k_rxcoef, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj);
-    const int nsrc = (2 * (vj.ny + 1) + 127) / 128;
-    const size_t vecBytes = (size_t)S * vj.vstride * sizeof(cplx);
-    auto fill = [&](bool sparse) {
-        if (!sparse) (void)hipMemsetAsync(vj.R, 0, vecBytes, strm);           // (the whole right-hand side is the residual)
-        hipLaunchKernelGGL(k_src, dim3(nsrc + (vj.ny + 127) / 128, S), dim3(128), 0, strm, vj, ctx->jvp.misfit, nsrc);
-    };
-    if (int rc = prod_solve(ctx, J.lam, 1, sweeps, vj.zid, fill, st)) return rc;
-    hipLaunchKernelGGL(k_jac_wb, dim3((vj.nz + vj.ny + 127) / 128, S), dim3(128), 0, strm, vj);
-    hipLaunchKernelGGL(k_jac_contract, dim3((BCC_L * vj.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj);
-    hipLaunchKernelGGL(k_gradcell, dim3((vj.nCell + 127) / 128, 2, GRAD_NG), dim3(128), 0, strm, vj);
-    hipLaunchKernelGGL(k_jtvp_final, grid1(vj.nAC, 128), dim3(128), 0, strm, vj, wrt, (const double*)(ctx->jvp.scale + 2), d_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-enum { PROD_JVP = 0, PROD_JTVP = 1, PROD_GN = 2 };
-// d_in / d_out: device pointers (jvp: v[nAC] -> Jv complex[nData]; jtvp: u complex[nData] -> [nAC]; gn: v[nAC] -> [nAC])
-static int prod_run(hmcmt_ctx* ctx, int what, const double* d_in, int wrt, double* d_out, hmcmt_stats* stOut) {
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    hipStream_t strm = ctx->stream;
-    hmcmt_stats st{};
-    st.nsystems = ctx->v.S;
-    JacState saved;
-    jac_save(ctx, saved);
-    auto leave = [&](int rc) {
-        const std::string e = ctx->err;
-        (void)hipStreamSynchronize(strm);
-        jac_restore(ctx, saved);
-        ctx->err = e;
-        if (stOut) *stOut = st;
-        return rc;
-    };
-    // no guard, no sampled profiling, no test hooks, no leapfrog update in the products' solves
-    ctx->guardEvery = 0; ctx->profMask = 0; ctx->dbgFlags = 0;
-    ctx->lfStep.on = 0; ctx->lfMom.on = 0;
-    ctx->sv.cntActive = nullptr;
-    ctx->stats = hmcmt_stats{};
-    View vj = ctx->v;
-    vj.m = P.m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
-    vj.dSig = P.dSig; vj.dbcL = P.dbcL; vj.dbcR = P.dbcR; vj.dbcB = P.dbcB;
-    vj.vbar = P.vbar; vj.rxCoef = P.rxCoef; vj.qPart = P.qPart; vj.gPartG = P.gPartG;
-    vj.jv = what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : P.jv;
-    const int sweeps = (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2;    // (cold solves: well above the two-sweep threshold)
-    int rc = 0;
-    if (what == PROD_JVP || what == PROD_GN) {
-        if ((rc = prod_tangent(ctx, vj, d_in, wrt, sweeps, st))) return leave(rc);
-        st.smoother_sweeps = 10 * sweeps;
-    }
-    if (what == PROD_GN) hipLaunchKernelGGL(k_jvp_w2, grid1(vj.nData, 256), dim3(256), 0, strm, vj, P.u);
-    if (what == PROD_JTVP || what == PROD_GN) {
-        const cplx* u = what == PROD_GN ? P.u : reinterpret_cast<const cplx*>(d_in);
-        if ((rc = prod_adjoint(ctx, vj, u, wrt, sweeps, d_out, st))) return leave(rc);
-        st.smoother_sweeps += sweeps;
-    }
-    return leave(0);
-}
-
-static int prod_check(hmcmt_ctx* ctx, const void* in, int32_t wrt, const void* out) {
-    if (!in || !out) { ctx->err = "Jacobian product: null input or output pointer"; return HMCMT_EINVAL; }
-    if (wrt != HMCMT_JAC_WRT_SIGMA && wrt != HMCMT_JAC_WRT_LNSIGMA) { ctx->err = "Jacobian product: wrt must be HMCMT_JAC_WRT_SIGMA or HMCMT_JAC_WRT_LNSIGMA"; return HMCMT_EINVAL; }
-    if (ctx->statsPending) { ctx->err = "Jacobian product: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
-    if (!ctx->jvp.ready || !ctx->jvp.valid) {
-        ctx->err = "Jacobian product: no valid linearisation point (call hmcmt_linearize; every evaluating call and hmcmt_set_options ends it)";
-        return HMCMT_EINVAL;
-    }
-    return 0;
-}
-
-// host entry: stage the input, run on the device buffers, bring the result back
-static int prod_host(hmcmt_ctx* ctx, int what, const double* in, int32_t wrt, double* out, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = prod_check(ctx, in, wrt, out)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    const int nAC = ctx->v.nAC, nData = ctx->v.nData;
-    const bool inData = what == PROD_JTVP, outData = what == PROD_JVP;
-    const size_t nin = inData ? 2 * (size_t)nData : (size_t)nAC, nout = outData ? 2 * (size_t)nData : (size_t)nAC;
-    for (size_t i = 0; i < nin; ++i)
-        if (!std::isfinite(in[i])) { ctx->err = "Jacobian product: non-finite input value"; return HMCMT_EINVAL; }
-    // (staging: u in P.u, v in P.vin; J v comes back through P.u, the cell vectors through P.out)
-    double* d_in = inData ? reinterpret_cast<double*>(P.u) : P.vin;
-    double* d_out = outData ? reinterpret_cast<double*>(P.u) : P.out;
-    HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin, hipMemcpyHostToDevice, ctx->stream));
-    int rc = prod_run(ctx, what, d_in, wrt, d_out, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-static int prod_device(hmcmt_ctx* ctx, int what, const double* d_in, int32_t wrt, double* d_out, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = prod_check(ctx, d_in, wrt, d_out)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    return prod_run(ctx, what, d_in, wrt, d_out, st);
-}
-
-int hmcmt_linearize(hmcmt_ctx* ctx, const double* m) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = linearize_check(ctx, m)) return rc;
-    for (int i = 0; i < ctx->v.nAC; ++i)
-        if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = jvp_alloc(ctx)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->jvp.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
-    return linearize_run(ctx);
-}
-int hmcmt_linearize_device(hmcmt_ctx* ctx, const double* d_m) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = linearize_check(ctx, d_m)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = jvp_alloc(ctx)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->jvp.m, d_m, sizeof(double) * ctx->v.nAC, hipMemcpyDeviceToDevice, ctx->stream));
-    return linearize_run(ctx);
-}
-int hmcmt_jvp(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Jv, hmcmt_stats* st) { return prod_host(ctx, PROD_JVP, v, wrt, Jv, st); }
-int hmcmt_jtvp(hmcmt_ctx* ctx, const double* u, int32_t wrt, double* JTu, hmcmt_stats* st) { return prod_host(ctx, PROD_JTVP, u, wrt, JTu, st); }
-int hmcmt_gn_hessvec(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Hv, hmcmt_stats* st) { return prod_host(ctx, PROD_GN, v, wrt, Hv, st); }
-int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Jv, hmcmt_stats* st) { return prod_device(ctx, PROD_JVP, d_v, wrt, d_Jv, st); }
-int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st) { return prod_device(ctx, PROD_JTVP, d_u, wrt, d_JTu, st); }
-int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st) { return prod_device(ctx, PROD_GN, d_v, wrt, d_Hv, st); }
-
-// ----------------------------------------------------------------------------------------------
-// block products (kernels_jvp_block.h): nvec directions, ONE solve() per route over the nvec * S virtual systems.  The solve runs
-// on a second solver instance (hmcmt_ctx::Blk): the context's Solver with S and nFreq multiplied by nvec, the frequency list and
-// the inverse pivots repeated per direction, per-system arrays, sync words, reduction records, constant block and host records of
-// its own; the stencil coefficients and eigen-transforms are per mode and shared.  It is put in the context's place for the call
-// (BlkSwap, inside the Jacobian's save / restore bracket), so solve(), the kernel table and the fallbacks see an ordinary problem.
-// ----------------------------------------------------------------------------------------------
-static void blk_release(hmcmt_ctx* ctx) {
-    hmcmt_ctx::Blk& B = ctx->blk;
-    for (void* p : B.allocs) hipFree(p);
-    for (void* p : B.hostAllocs) hipHostFree(p);
-    B = hmcmt_ctx::Blk{};
-}
-static int blk_dalloc(hmcmt_ctx* ctx, void** p, size_t bytes) {       // (zeroed, on the block instance's own list)
-    void* q = nullptr;
-    bytes = std::max<size_t>(bytes, 16);
-    HIPCHK(hipMalloc(&q, bytes));
-    ctx->blk.allocs.push_back(q);
-    HIPCHK(hipMemsetAsync(q, 0, bytes, ctx->stream));
-    *p = q;
-    return 0;
-}
-static int blk_alloc_impl(hmcmt_ctx* ctx, int nvec) {
-    hmcmt_ctx::Blk& B = ctx->blk;
-    const View& v = ctx->v;
-    const size_t K = (size_t)nvec, S = (size_t)v.S, SV = K * S, VS = (size_t)v.vstride;
-    Solver& k = B.sv;
-    k = ctx->sv;                                         // (tile shapes, launch-invariant pointers, the per-mode coefficients)
-    k.S = (int)SV; k.nFreq = nvec * v.nFreq;
-    k.cntActive = nullptr;
-    int rc = 0;
-#define BA(ptr, n) { void* q_ = nullptr; if ((rc = blk_dalloc(ctx, &q_, (size_t)(n) * sizeof(*(ptr))))) return rc; (ptr) = reinterpret_cast<decltype(ptr)>(q_); }
-    BA(B.omega, SV) BA(B.invp, SV * VS) BA(B.invp32, SV * VS) BA(B.lam, SV * VS) BA(k.r, SV * VS) BA(B.d_b, SV * VS) BA(B.d_sw, SV * VS)
-    BA(k.p, SV * VS) BA(k.q, SV * VS) BA(k.z, SV * VS) BA(k.y, SV * VS) BA(k.t, SV * VS) BA(k.dinv, SV * VS)
-    BA(k.t32, SV * VS + 64) BA(k.y32, SV * VS + 64)
-    BA(k.z32, SV * VS) BA(k.p32a, SV * VS) BA(k.p32b, SV * VS) BA(k.zs32, SV * VS) BA(k.z4_32, SV * VS) BA(k.t2_32, SV * VS) BA(k.partR, SV * MAXNB) BA(k.dinv32, SV * VS)
-    BA(k.p2, SV * VS) BA(k.r2, SV * VS) BA(k.partPQ, SV * MAXNB) BA(k.rho2, 2 * SV)
-    BA(k.partA, SV * MAXNB) BA(k.partB, SV * MAXNB) BA(B.partZZ, SV * MAXNB) BA(B.partRes, SV * MAXNB) BA(B.partBn, SV * MAXNB)
-    BA(k.rho, SV) BA(k.alphaBeta, SV) BA(k.active, SV) BA(k.iters, SV) BA(k.status, SV) BA(k.nactive, 1) BA(k.errEst, SV) BA(k.errRef, SV) BA(k.errRefIt, SV)
-    BA(B.dirOn, K) BA(B.sysOnDir, SV) BA(B.sysOnV, SV)
-    BA(B.vin, K * v.nAC) BA(B.out, K * v.nAC) BA(B.dSig, K * v.nCell) BA(B.gPartG, K * 2 * GRAD_NG * v.nCell) BA(B.qPart, SV * v.ny) BA(B.scale, 4 * K)
-    BA(B.dbcL, SV * v.nz) BA(B.dbcR, SV * v.nz) BA(B.dbcB, SV * (v.ny + 1)) BA(B.jv, K * v.nData) BA(B.u, K * v.nData) BA(B.vbar, K * v.nData) BA(B.rxCoef, SV * v.nRx)
-    BA(B.srcB, SV * 4) BA(B.wL, SV * v.nz) BA(B.wR, SV * v.nz) BA(B.colw, SV * v.ny) BA(B.gL, SV * v.nz) BA(B.gR, SV * v.nz)
-    k.omega = B.omega; k.invp = B.invp; k.invp32 = B.invp32;
-    // the persistent kernel's own words for this instance (persist_setup): more system slots where the share has the CUs for them;
-    // its 32-bit lane offsets carry the system's element offset, so a block beyond 2^27 elements runs the launch-per-phase loop
-    if (ctx->persistCW > 0 && SV * VS < ((size_t)1 << 27)) {
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
-        const int cuPerXcd = prop.multiProcessorCount / 8 / std::max(ctx->shareCnt, 1);
-        B.slots = std::max(1, std::min((int)((SV + 7) / 8), cuPerXcd / std::max(ctx->persistG, 1)));
-        B.psyncBytes = ((size_t)(32 * 8 * B.slots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
-        unsigned char* ps = nullptr; BA(ps, B.psyncBytes) B.psync = reinterpret_cast<unsigned*>(ps);
-        unsigned char* pr = nullptr; BA(pr, SV * MAXNB * 2 * 8 * 16) B.prec = reinterpret_cast<u4v*>(pr);
-        unsigned char* pc = nullptr; BA(pc, sizeof(PsConst)) B.psConst = reinterpret_cast<PsConst*>(pc);
-        if (ctx->persistCS > 1) BA(B.yhat2, SV * VS)
-    }
-#undef BA
-    HIPCHK(hipHostMalloc((void**)&B.h_rec, sizeof(double) * 4 * SV, hipHostMallocMapped));
-    B.hostAllocs.push_back(B.h_rec);
-    HIPCHK(hipHostGetDevicePointer((void**)&B.d_recHost, B.h_rec, 0));
-    HIPCHK(hipHostMalloc((void**)&B.h_onV, sizeof(int) * SV, hipHostMallocMapped));
-    B.hostAllocs.push_back(B.h_onV);
-    HIPCHK(hipHostGetDevicePointer((void**)&B.d_onVHost, B.h_onV, 0));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    B.cap = nvec;
-    return 0;
-}
-static int blk_alloc(hmcmt_ctx* ctx, int nvec) {
-    if (ctx->blk.cap >= nvec) return 0;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    blk_release(ctx);
-    const int rc = blk_alloc_impl(ctx, nvec);
-    if (rc) {                                            // (out of memory: nothing of the block instance is kept, the context goes on)
-        const std::string e = ctx->err;
-        (void)hipStreamSynchronize(ctx->stream);
-        blk_release(ctx);
-        (void)hipGetLastError();
-        ctx->err = "block Jacobian product: " + e;
-    }
-    return rc;
-}
-
-// what the block instance replaces in the context beside View / Solver (JacState), and puts back
-struct BlkSwap {
-    double *partZZ, *partRes, *partBn, *h_rec, *d_recHost;
-    cplx *d_b, *d_sw;
-    float2 *invp32, *yhat2;
-    unsigned* psync; size_t psyncBytes; int slots, persistCW;
-    u4v* prec;
-    PsConst* psConst; PsConst shadow; bool constValid, dinvValid;
-};
-static void blk_swap_in(hmcmt_ctx* c, BlkSwap& t) {
-    hmcmt_ctx::Blk& B = c->blk;
-    t.partZZ = c->d_partZZ; t.partRes = c->d_partRes; t.partBn = c->d_partBn; t.h_rec = c->h_rec; t.d_recHost = c->d_recHost;
-    t.d_b = c->d_b; t.d_sw = c->d_sw; t.invp32 = c->d_invp32; t.yhat2 = c->d_yhat2;
-    t.psync = c->d_psync; t.psyncBytes = c->psyncBytes; t.slots = c->persistSlots; t.persistCW = c->persistCW;
-    t.prec = c->d_prec; t.psConst = c->d_psConst; t.shadow = c->psShadow; t.constValid = c->psConstValid; t.dinvValid = c->dinvValid;
-    c->d_partZZ = B.partZZ; c->d_partRes = B.partRes; c->d_partBn = B.partBn; c->h_rec = B.h_rec; c->d_recHost = B.d_recHost;
-    c->d_b = B.d_b; c->d_sw = B.d_sw; c->d_invp32 = B.invp32; c->d_yhat2 = B.yhat2;
-    if (B.psync) { c->d_psync = B.psync; c->psyncBytes = B.psyncBytes; c->persistSlots = B.slots; c->d_prec = B.prec; c->d_psConst = B.psConst; }
-    else c->persistCW = 0;                               // (no persistent kernel for this block: persist_ok)
-    c->psShadow = B.psShadow; c->psConstValid = B.psConstValid;
-    c->dinvValid = false;                                // (the instance's Jacobi diagonals: written where a launch-per-phase kernel needs them)
-}
-static void blk_swap_out(hmcmt_ctx* c, const BlkSwap& t) {
-    hmcmt_ctx::Blk& B = c->blk;
-    B.psShadow = c->psShadow; B.psConstValid = c->psConstValid;
-    c->d_partZZ = t.partZZ; c->d_partRes = t.partRes; c->d_partBn = t.partBn; c->h_rec = t.h_rec; c->d_recHost = t.d_recHost;
-    c->d_b = t.d_b; c->d_sw = t.d_sw; c->d_invp32 = t.invp32; c->d_yhat2 = t.yhat2;
-    c->d_psync = t.psync; c->psyncBytes = t.psyncBytes; c->persistSlots = t.slots; c->persistCW = t.persistCW;
-    c->d_prec = t.prec; c->d_psConst = t.psConst; c->psShadow = t.shadow; c->psConstValid = t.constValid; c->dinvValid = t.dinvValid;
-}
-
-// the directions k_blk_norm found not identically zero -> the system flags by direction and by virtual system, made on the device
-// (k_blk_flags); the host reads the flags by virtual system from mapped memory.  One synchronisation, no copy.
-static int blk_systems(hmcmt_ctx* ctx, const int* d_realOn, int S, int nvec, int& nOn) {
-    hmcmt_ctx::Blk& B = ctx->blk;
-    const int n = nvec * S;
-    hipLaunchKernelGGL(k_blk_flags, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const int*)B.dirOn, d_realOn, B.sysOnDir, B.sysOnV, B.d_onVHost, S / 2, nvec);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    nOn = 0;
-    for (int i = 0; i < n; ++i) nOn += B.h_onV[i];
-    ctx->nSysOn = nOn;
-    return 0;
-}
-
-// J V -> vr.jv (d_V: device, [nvec][nAC]); vr: the REAL problem's View on the block's work arrays (kernels_jvp_block.h)
-static int blk_tangent(hmcmt_ctx* ctx, View vr, const int* d_realOn, const double* d_V, int nvec, int wrt, int sweeps, hmcmt_stats& st, int& nOn) {
-    hmcmt_ctx::Blk& B = ctx->blk;
-    hipStream_t strm = ctx->stream;
-    const int S = vr.S;
-    vr.tanV = d_V;
-    HIPCHK(hipMemsetAsync(vr.jv, 0, sizeof(cplx) * (size_t)nvec * vr.nData, strm));
-    hipLaunchKernelGGL(k_blk_dsig, dim3((vr.nCell + 255) / 256, nvec), dim3(256), 0, strm, vr, wrt, nvec);
-    hipLaunchKernelGGL(k_blk_norm, dim3(nvec), dim3(1024), 0, strm, vr.dSig, (const double*)vr.sigma, (long)vr.nCell, (long)vr.nCell, B.scale, 0, B.dirOn);
-    if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
-    if (nOn == 0) return 0;                              // (every direction zero: J V = 0 stands)
-    hipLaunchKernelGGL(k_blk_dbc, dim3((2 * vr.nz + vr.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S, (nvec + BLK_KB - 1) / BLK_KB), dim3(64 * DBC_WAVES), 0, strm, vr, nvec);
-    auto fill = [&](bool) {
-        hipLaunchKernelGGL(k_blk_rhs, dim3((unsigned)((vr.vstride + 255) / 256), S, nvec), dim3(256), 0, strm, vr, nvec);
-    };
-    if (int rc = prod_solve(ctx, B.lam, 0, sweeps, -1, fill, st, B.h_onV)) return rc;
-    hipLaunchKernelGGL(k_blk_data, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Re(J^T conj(U)) -> d_out (d_U: device, complex [nvec][nData]; d_out: device, [nvec][nAC])
-static int blk_adjoint(hmcmt_ctx* ctx, View vr, const int* d_realOn, const cplx* d_U, int nvec, int wrt, int sweeps, double* d_out, hmcmt_stats& st, int& nOn) {
-    hmcmt_ctx::Blk& B = ctx->blk;
-    hipStream_t strm = ctx->stream;
-    const int S = vr.S;
-    vr.uData = d_U;
-    hipLaunchKernelGGL(k_blk_vbar, grid1(vr.nData, 256), dim3(256), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_norm, dim3(nvec), dim3(1024), 0, strm, reinterpret_cast<double*>(vr.vbar), (const double*)nullptr, 2l * vr.nData, 2l * vr.nData, B.scale, 2, B.dirOn);
-    if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
-    if (nOn == 0) { HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)nvec * vr.nAC, strm)); return 0; }
-    hipLaunchKernelGGL(k_blk_rxcoef, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
-    const int nsrc = (2 * (vr.ny + 1) + 127) / 128;
-    const size_t vecBytes = (size_t)nvec * S * vr.vstride * sizeof(cplx);
-    auto fill = [&](bool sparse) {
-        if (!sparse) (void)hipMemsetAsync(vr.R, 0, vecBytes, strm);           // (the whole right-hand side is the residual)
-        hipLaunchKernelGGL(k_blk_src, dim3(nsrc + (vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nsrc, nvec);
-    };
-    if (int rc = prod_solve(ctx, B.lam, 1, sweeps, vr.zid, fill, st, B.h_onV)) return rc;
-    hipLaunchKernelGGL(k_blk_wb, dim3((vr.nz + vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_contract, dim3((BCC_L * vr.nz + 127) / 128, 2 * ((nvec + BLK_KB - 1) / BLK_KB), S), dim3(128), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_gradcell, dim3((vr.nCell + 127) / 128, 2 * GRAD_NG, nvec), dim3(128), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_final, grid1(vr.nAC, 128), dim3(128), 0, strm, vr, wrt, d_out, nvec);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int blk_run(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int wrt, double* d_out, hmcmt_stats* stOut) {
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    hmcmt_ctx::Blk& B = ctx->blk;
-    hipStream_t strm = ctx->stream;
-    hmcmt_stats st{};
-    // the inverse pivots of the linearisation point, per direction (again after a new point, or for more directions)
-    if (B.gen != P.gen || B.genVec != nvec) {
-        const unsigned gx = (unsigned)std::min<long>(64, (ctx->v.vstride + 255) / 256);
-        hipLaunchKernelGGL(k_blk_replicate, dim3(gx, ctx->v.S, nvec), dim3(256), 0, strm, (const cplx*)ctx->v.invp, (const float2*)ctx->d_invp32,
-                           B.invp, B.invp32, ctx->v.nFreq, nvec, ctx->v.vstride);
-        HIPCHK(hipGetLastError());
-        if (B.genVec != nvec) {                          // the frequency list, repeated per direction
-            const int nF = ctx->v.nFreq;
-            std::vector<double> om((size_t)nvec * 2 * nF);
-            for (int j = 0; j < nvec; ++j)
-                for (int f = 0; f < nF; ++f) {
-                    om[(size_t)j * nF + f] = ctx->hp.omega[f];
-                    om[((size_t)nvec + j) * nF + f] = ctx->hp.omega[nF + f];
-                }
-            HIPCHK(hipStreamSynchronize(strm));
-            HIPCHK(hipMemcpy(B.omega, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice));
-        }
-        B.gen = P.gen; B.genVec = nvec;
-    }
-    JacState saved;
-    jac_save(ctx, saved);
-    BlkSwap swapped;
-    blk_swap_in(ctx, swapped);
-    auto leave = [&](int rc) {
-        const std::string e = ctx->err;
-        (void)hipStreamSynchronize(strm);
-        blk_swap_out(ctx, swapped);
-        jac_restore(ctx, saved);
-        ctx->err = e;
-        if (stOut) *stOut = st;
-        return rc;
-    };
-    // no guard, no sampled profiling, no test hooks, no leapfrog update in the products' solves
-    ctx->guardEvery = 0; ctx->profMask = 0; ctx->dbgFlags = 0;
-    ctx->lfStep.on = 0; ctx->lfMom.on = 0;
-    ctx->stats = hmcmt_stats{};
-    ctx->psOrder[0].clear(); ctx->psOrder[1].clear();    // (the queue tables are the context's problem's: the kernel's own order here)
-    // the REAL problem's View on the block's work arrays, for the products' kernels ...
-    View vr = ctx->v;
-    const int* d_realOn = ctx->v.sysOn;                  // (the problem's own flags, [S])
-    vr.m = P.m; vr.gate = nullptr; vr.ticks = nullptr; vr.dbg = 0;
-    vr.dSig = B.dSig; vr.dbcL = B.dbcL; vr.dbcR = B.dbcR; vr.dbcB = B.dbcB;
-    vr.vbar = B.vbar; vr.rxCoef = B.rxCoef; vr.qPart = B.qPart; vr.gPartG = B.gPartG;
-    vr.srcB = B.srcB; vr.wL = B.wL; vr.wR = B.wR; vr.colw = B.colw; vr.gL = B.gL; vr.gR = B.gR;
-    vr.R = B.sv.r; vr.Lam = B.lam; vr.dF = B.lam; vr.tanScale = B.scale; vr.sysOn = B.sysOnDir;
-    vr.tanV = B.vin; vr.uData = B.u;
-    vr.jv = what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : B.jv;
-    // ... and the virtual problem in the context's place, for solve()
-    ctx->sv = B.sv;
-    ctx->v.S = nvec * vr.S; ctx->v.nFreq = nvec * vr.nFreq; ctx->v.omega = B.omega; ctx->v.invp = B.invp; ctx->v.sysOn = B.sysOnV;
-    ctx->v.Lam = B.lam; ctx->v.R = B.sv.r;
-    if (B.psync) ctx->persistSlots = std::max(1, std::min(B.slots, (ctx->v.S + 7) / 8));
-    ctx->sv.S = ctx->v.S; ctx->sv.nFreq = ctx->v.nFreq;  // (arrays of the largest block seen, this call's count of systems)
-    const int sweeps = (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2;    // (cold solves: well above the two-sweep threshold)
-    int rc = 0, nOn = 0;
-    if (what == PROD_JVP || what == PROD_GN) {
-        if ((rc = blk_tangent(ctx, vr, d_realOn, d_in, nvec, wrt, sweeps, st, nOn))) return leave(rc);
-        st.nsystems = nOn;
-        st.smoother_sweeps = 10 * sweeps;
-    }
-    if (what == PROD_GN) hipLaunchKernelGGL(k_blk_w2, grid1(vr.nData, 256), dim3(256), 0, strm, vr, B.u, nvec);
-    if (what == PROD_JTVP || what == PROD_GN) {
-        const cplx* u = what == PROD_GN ? B.u : reinterpret_cast<const cplx*>(d_in);
-        if ((rc = blk_adjoint(ctx, vr, d_realOn, u, nvec, wrt, sweeps, d_out, st, nOn))) return leave(rc);
-        if (what == PROD_JTVP) st.nsystems = nOn;
-        st.smoother_sweeps += sweeps;
-    }
-    return leave(0);
-}
-
-static int blk_check(hmcmt_ctx* ctx, const void* in, int32_t nvec, int32_t wrt, const void* out) {
-    if (nvec < 1 || nvec > HMCMT_BLOCK_MAX) { ctx->err = "block Jacobian product: nvec must be 1 .. HMCMT_BLOCK_MAX (32)"; return HMCMT_EINVAL; }
-    return prod_check(ctx, in, wrt, out);
-}
-// a block of one direction IS the single product (the contract defines direction j as the single call's result): the same code,
-// no second solver instance, no flags to read back.  A zero right-hand side leaves the solve at iteration 0 there as well.
-static int blk_single_stats(hmcmt_ctx* ctx, int rc, hmcmt_stats* st) {
-    if (st) st->nsystems = ctx->nSysOn;                  // (the block's count: the systems that carry data)
-    return rc;
-}
-static int blk_host(hmcmt_ctx* ctx, int what, const double* in, int32_t nvec, int32_t wrt, double* out, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = blk_check(ctx, in, nvec, wrt, out)) return rc;
-    if (nvec == 1) return blk_single_stats(ctx, prod_host(ctx, what, in, wrt, out, st), st);
-    const int nAC = ctx->v.nAC, nData = ctx->v.nData;
-    const bool inData = what == PROD_JTVP, outData = what == PROD_JVP;
-    const size_t nin = (size_t)nvec * (inData ? 2 * (size_t)nData : (size_t)nAC), nout = (size_t)nvec * (outData ? 2 * (size_t)nData : (size_t)nAC);
-    for (size_t i = 0; i < nin; ++i)
-        if (!std::isfinite(in[i])) { ctx->err = "block Jacobian product: non-finite input value"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = blk_alloc(ctx, nvec)) return rc;
-    hmcmt_ctx::Blk& B = ctx->blk;
-    // (staging: U in B.u, V in B.vin; J V comes back through B.u, the cell vectors through B.out)
-    double* d_in = inData ? reinterpret_cast<double*>(B.u) : B.vin;
-    double* d_out = outData ? reinterpret_cast<double*>(B.u) : B.out;
-    HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin, hipMemcpyHostToDevice, ctx->stream));
-    int rc = blk_run(ctx, what, d_in, nvec, wrt, d_out, st);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-static int blk_device(hmcmt_ctx* ctx, int what, const double* d_in, int32_t nvec, int32_t wrt, double* d_out, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = blk_check(ctx, d_in, nvec, wrt, d_out)) return rc;
-    if (nvec == 1) return blk_single_stats(ctx, prod_device(ctx, what, d_in, wrt, d_out, st), st);
-    HIPCHK(hipSetDevice(ctx->device));
-    if (int rc = blk_alloc(ctx, nvec)) return rc;
-    return blk_run(ctx, what, d_in, nvec, wrt, d_out, st);
-}
-int hmcmt_jvp_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* JV, hmcmt_stats* st) { return blk_host(ctx, PROD_JVP, V, nvec, wrt, JV, st); }
-int hmcmt_jtvp_block(hmcmt_ctx* ctx, const double* U, int32_t nvec, int32_t wrt, double* JTU, hmcmt_stats* st) { return blk_host(ctx, PROD_JTVP, U, nvec, wrt, JTU, st); }
-int hmcmt_gn_hessvec_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* HV, hmcmt_stats* st) { return blk_host(ctx, PROD_GN, V, nvec, wrt, HV, st); }
-int hmcmt_jvp_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_JV, hmcmt_stats* st) { return blk_device(ctx, PROD_JVP, d_V, nvec, wrt, d_JV, st); }
-int hmcmt_jtvp_block_device(hmcmt_ctx* ctx, const double* d_U, int32_t nvec, int32_t wrt, double* d_JTU, hmcmt_stats* st) { return blk_device(ctx, PROD_JTVP, d_U, nvec, wrt, d_JTU, st); }
-int hmcmt_gn_hessvec_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_HV, hmcmt_stats* st) { return blk_device(ctx, PROD_GN, d_V, nvec, wrt, d_HV, st); }
-
 }  // extern "C"
+
+#include "host_jacobian.h"
