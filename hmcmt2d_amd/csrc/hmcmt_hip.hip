@@ -62,7 +62,6 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_mass.h"
 #include "kernels_jac.h"
 #include "kernels_jvp.h"
-#include "kernels_jvp_block.h"
 
 // an instantiation of the persistent solve kernel (g_psKernels, launch_persist): k_cocg_persist<cw, sw, mw, cs, nyk, st> (two
 // halves) or k_cocg_persist4<cw, sw, 32, nyk, 4, st> (four strips), strips x cw threads per workgroup
@@ -115,7 +114,7 @@ struct hmcmt_ctx {
     } ss;
     // The resources of one solver instance that are not in Solver: partial sums, records, spare vectors, the persistent kernel's
     // words.  The context holds one set for its own problem, Blk one for the block products' virtual problem; a block call exchanges
-    // the two for its duration (blk_run), so solve(), the kernel table and the fallbacks see an ordinary problem.
+    // the two for its duration (prod_run), so solve(), the kernel table and the fallbacks see an ordinary problem.
     struct Inst {
         double* d_partZZ = nullptr;
         double *d_partRes = nullptr, *d_partBn = nullptr;
@@ -279,12 +278,19 @@ struct hmcmt_ctx {
     Memo memo[2];
     int memoNext = 0;
     long long memoHits = 0;
+    // the adjoint side of the Jacobian family: solution, boundary sources, boundary weights and their contraction with dBC
+    struct AdjArrays { cplx *lam = nullptr, *srcB = nullptr, *wL = nullptr, *wR = nullptr, *colw = nullptr, *gL = nullptr, *gR = nullptr; };
+    // the products' work arrays, [directions] times one direction's (kernels_jvp.h); scale: [4] per direction, the power-of-two
+    // normalisation of the tangent's / the adjoint's input (k_dir_norm)
+    struct ProdArrays {
+        double *vin = nullptr, *out = nullptr, *dSig = nullptr, *gPartG = nullptr, *qPart = nullptr, *scale = nullptr;
+        cplx *dbcL = nullptr, *dbcR = nullptr, *dbcB = nullptr, *jv = nullptr, *u = nullptr, *vbar = nullptr, *rxCoef = nullptr;
+    };
     // explicit Jacobian (hmcmt_jacobian / hmcmt_sensitivity, kernels_jac.h): its own solution and boundary arrays, the saved forward
     // fields and extrapolation state of the context's evaluations, the batches' data lists and system flags (allocated on first use)
-    struct Jac {
+    struct Jac : AdjArrays {
         bool ready = false;
-        cplx *lam = nullptr, *xSave = nullptr, *srcB = nullptr, *wL = nullptr, *wR = nullptr, *colw = nullptr, *gL = nullptr, *gR = nullptr;
-        cplx *qJ = nullptr, *pred = nullptr;
+        cplx *xSave = nullptr, *qJ = nullptr, *pred = nullptr;
         double *extSave = nullptr, *misfit = nullptr, *m = nullptr, *rows = nullptr, *sens = nullptr;
         double* h_rows = nullptr;          // pinned staging of one batch's rows (host entry point)
         JacEntry* list = nullptr;          // [nData]
@@ -292,34 +298,29 @@ struct hmcmt_ctx {
         int* sysOn = nullptr;              // [nRx][S]
         int maxRows = 0;                   // most data of one receiver
     } jac;
-    // matrix-free Jacobian products (hmcmt_linearize / hmcmt_jvp / hmcmt_jtvp / hmcmt_gn_hessvec, kernels_jvp.h): the linearisation
-    // point's model, the products' own work arrays (the solution and boundary-weight arrays are the Jacobian's: `jac`)
-    struct Jvp {
+    // matrix-free Jacobian products (hmcmt_linearize, hmcmt_jvp / hmcmt_jtvp / hmcmt_gn_hessvec and their _block forms,
+    // kernels_jvp.h): the linearisation point's model and the work arrays of ONE direction -- a product of one direction runs on
+    // these, with the Jacobian's adjoint arrays (`jac`) and the context's own solver
+    struct Jvp : ProdArrays {
         bool ready = false;
         bool valid = false;                // a linearisation point is set and no evaluation has run since
-        double *m = nullptr, *vin = nullptr, *dSig = nullptr, *out = nullptr, *gPartG = nullptr, *qPart = nullptr, *misfit = nullptr;
-        double* scale = nullptr;           // [4] power-of-two normalisation of the tangent's / the adjoint's input (k_jvp_norm)
-        cplx *dbcL = nullptr, *dbcR = nullptr, *dbcB = nullptr, *jv = nullptr, *u = nullptr, *vbar = nullptr, *rxCoef = nullptr;
-        long long gen = 0;                 // serial number of the linearisation points (the block products' replicated pivots belong to one)
+        double *m = nullptr, *misfit = nullptr;
+        long long gen = 0;                 // serial number of the linearisation points (the block's replicated pivots belong to one)
     } jvp;
-    // block products (hmcmt_*_block, kernels_jvp_block.h): a second solver instance over nvec * S virtual systems -- its own
-    // per-system arrays, sync words, records and constant block -- and the products' work arrays per direction.  Allocated by the
-    // first block call, grown to the largest nvec seen, released at hmcmt_destroy (its own list: growing frees the smaller set)
-    struct Blk {
+    // products of nvec > 1 directions: a second solver instance over nvec * S virtual systems -- its own per-system arrays, sync
+    // words, records and constant block -- and work and adjoint arrays per direction.  Allocated by the first such call, grown to
+    // the largest nvec seen, released at hmcmt_destroy (its own list: growing frees the smaller set)
+    struct Blk : ProdArrays, AdjArrays {
         int cap = 0;                       // directions the arrays hold (0: none yet)
         long long gen = -1; int genVec = 0;   // the linearisation point and nvec the replicated pivots were made for
         std::vector<void*> allocs, hostAllocs;
         Solver sv{};
         Inst inst{};                       // (while a block call runs: the context's own, exchanged)
         int slots = 0;                     // system slots per XCD the sync words were made for (inst.persistSlots: those of the call at hand)
-        cplx *lam = nullptr, *invp = nullptr;
+        cplx* invp = nullptr;
         double* omega = nullptr;
         int *h_onV = nullptr, *d_onVHost = nullptr;   // mapped: [cap S] the virtual systems solved, as k_blk_flags wrote them
         int *dirOn = nullptr, *sysOnDir = nullptr, *sysOnV = nullptr;
-        // work arrays per direction (the single product's, [cap] times)
-        double *vin = nullptr, *out = nullptr, *dSig = nullptr, *gPartG = nullptr, *qPart = nullptr, *scale = nullptr;
-        cplx *dbcL = nullptr, *dbcR = nullptr, *dbcB = nullptr, *jv = nullptr, *u = nullptr, *vbar = nullptr, *rxCoef = nullptr;
-        cplx *srcB = nullptr, *wL = nullptr, *wR = nullptr, *colw = nullptr, *gL = nullptr, *gR = nullptr;
     } blk;
 };
 

@@ -1,8 +1,8 @@
-// host_jacobian.h -- the calls that borrow the context, solve, and give it back: the explicit Jacobian (kernels_jac.h), the
-// matrix-free Jacobian products (kernels_jvp.h) and the block products (kernels_jvp_block.h).  Host code of hmcmt_hip.hip's
-// translation unit, included at its end: behind the context, solve() and evaluate().
+// host_jacobian.h -- the calls that borrow the context, solve, and give it back: the explicit Jacobian (kernels_jac.h) and the
+// matrix-free Jacobian products of one direction or a block of them (kernels_jvp.h).  Host code of hmcmt_hip.hip's translation
+// unit, included at its end: behind the context, solve() and evaluate().
 //
-// All three run between one bracket (Borrowed) and through one solve loop (borrowed_solve); DESIGN.md 4.6-4.8.
+// All of them run between one bracket (Borrowed) and through one solve loop (borrowed_solve); DESIGN.md 4.6-4.8.
 
 // ----------------------------------------------------------------------------------------------
 // what the family shares
@@ -59,18 +59,17 @@ static View quiet_view(const hmcmt_ctx* ctx, const double* m) {
     vj.m = m; vj.gate = nullptr; vj.ticks = nullptr; vj.dbg = 0;
     return vj;
 }
-// ... with the adjoint solution, right-hand side and boundary-weight arrays of `a` (hmcmt_ctx::Jac or Blk) and the residual r
-template <class A>
-static void adjoint_arrays(View& vj, const A& a, cplx* r) {
+// ... with the adjoint solution, right-hand side and boundary-weight arrays `a` and the residual r
+static void adjoint_arrays(View& vj, const hmcmt_ctx::AdjArrays& a, cplx* r) {
     vj.Lam = a.lam; vj.R = r; vj.srcB = a.srcB; vj.wL = a.wL; vj.wR = a.wR; vj.colw = a.colw; vj.gL = a.gL; vj.gR = a.gR;
 }
-// ... with the products' work arrays `w` (hmcmt_ctx::Jvp or Blk); J v goes to `jv` where it is the call's result
-template <class W>
-static View product_view(const hmcmt_ctx* ctx, const W& w, cplx* jv) {
+// ... with the products' work arrays `w`; J v goes to `jv` where it is the call's result
+static View product_view(const hmcmt_ctx* ctx, const hmcmt_ctx::ProdArrays& w, cplx* jv) {
     View vj = quiet_view(ctx, ctx->jvp.m);
     vj.dSig = w.dSig; vj.dbcL = w.dbcL; vj.dbcR = w.dbcR; vj.dbcB = w.dbcB;
     vj.vbar = w.vbar; vj.rxCoef = w.rxCoef; vj.qPart = w.qPart; vj.gPartG = w.gPartG;
     vj.jv = jv ? jv : w.jv;
+    vj.tanV = w.vin; vj.uData = w.u; vj.tanScale = w.scale;
     return vj;
 }
 
@@ -277,8 +276,9 @@ static int jac_run(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrow
         };
         // (the records of a batch that ended clean: behind the batch's one synchronisation, below)
         if ((rc = borrowed_solve(ctx, J.lam, 1, sweeps, v0.zid, fill, st, onj, "Jacobian: an adjoint", true))) return rc;
-        hipLaunchKernelGGL(k_jac_wb, dim3((v0.nz + v0.ny + 127) / 128, S), dim3(128), 0, strm, vj);
-        hipLaunchKernelGGL(k_jac_contract, dim3((BCC_L * v0.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj);
+        // (the products' kernels, one direction)
+        hipLaunchKernelGGL(k_dir_wb, dim3((v0.nz + v0.ny + 127) / 128, S), dim3(128), 0, strm, vj, 1);
+        hipLaunchKernelGGL(k_contract<1>, dim3((BCC_L * v0.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj, 1);
         const JacGroup* gl = J.groups + gfirst[j];
         const dim3 ga((nAC + 127) / 128);
         if (sens) hipLaunchKernelGGL(k_jac_sens, ga, dim3(128), 0, strm, vj, J.list, gl, ngroups[j], j, J.qJ, wrt, J.sens);
@@ -339,10 +339,18 @@ int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens
 
 // ----------------------------------------------------------------------------------------------
 // matrix-free Jacobian products (kernels_jvp.h).  hmcmt_linearize is an ordinary cold forward evaluation plus what the gradient
-// computes in front of its adjoint solve (boundary-derivative tables, receiver functionals); a product is small launches around ONE
-// solve per direction -- forward kind for the tangent field (dense right-hand side, zero guess), adjoint kind for J^T u (the
-// gradient's sparse start) -- on the Jacobian's solution and boundary arrays, inside the bracket (Borrowed).  A product runs no
-// evaluation: the context's fields, history and memo are not touched at all.
+// computes in front of its adjoint solve (boundary-derivative tables, receiver functionals); a product of nvec directions is small
+// launches around ONE solve per route -- forward kind for the tangent fields (dense right-hand sides, zero guess), adjoint kind for
+// J^T U (the gradient's sparse start) -- inside the bracket (Borrowed).  A product runs no evaluation: the context's fields, history
+// and memo are not touched at all.
+//   nvec = 1  the solve is the context's own, of its S systems with the problem's own flags, on the work arrays of hmcmt_ctx::Jvp
+//             and the explicit Jacobian's solution and boundary arrays (hmcmt_ctx::Jac).
+//   nvec > 1  the solve is over the nvec * S virtual systems, on a second solver instance (hmcmt_ctx::Blk): the context's Solver
+//             with S and nFreq multiplied by nvec, the frequency list and the inverse pivots repeated per direction, per-system
+//             arrays, sync words, reduction records, constant block and host records of its own (hmcmt_ctx::Inst); the stencil
+//             coefficients and eigen-transforms are per mode and shared.  It is put in the context's place for the call (inside the
+//             bracket, blk_enter), so solve(), the kernel table and the fallbacks see an ordinary problem.  The flags of the virtual
+//             systems -- (direction not identically zero) and (system carries data) -- are made on the device and read back.
 // ----------------------------------------------------------------------------------------------
 static int jvp_alloc(hmcmt_ctx* ctx) {
     if (int rc = jac_alloc(ctx)) return rc;
@@ -387,75 +395,6 @@ static int linearize_check(hmcmt_ctx* ctx, const void* m) {
     return 0;
 }
 
-// J v -> vj.jv (d_v: device, [nAC])
-static int prod_tangent(hmcmt_ctx* ctx, View vj, const double* d_v, int wrt, int sweeps, hmcmt_stats& st) {
-    hipStream_t strm = ctx->stream;
-    const int S = vj.S;
-    vj.tanV = d_v;
-    vj.R = ctx->sv.r;
-    HIPCHK(hipMemsetAsync(vj.jv, 0, sizeof(cplx) * vj.nData, strm));
-    hipLaunchKernelGGL(k_jvp_dsig, grid1(vj.nCell, 256), dim3(256), 0, strm, vj, wrt);
-    hipLaunchKernelGGL(k_jvp_norm, dim3(1), dim3(1024), 0, strm, vj.dSig, (const double*)vj.sigma, (long)vj.nCell, ctx->jvp.scale);
-    vj.tanScale = ctx->jvp.scale;
-    hipLaunchKernelGGL(k_jvp_dbc, dim3((2 * vj.nz + vj.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S), dim3(64 * DBC_WAVES), 0, strm, vj);
-    auto fill = [&](bool) {
-        hipLaunchKernelGGL(k_jvp_rhs, dim3((unsigned)((vj.vstride + 255) / 256), S), dim3(256), 0, strm, vj);
-    };
-    if (int rc = borrowed_solve(ctx, ctx->jac.lam, 0, sweeps, -1, fill, st, ctx->hp.sysOn.data(), "Jacobian product: the tangent")) return rc;
-    vj.dF = ctx->jac.lam;
-    hipLaunchKernelGGL(k_jvp_data, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Re(J^T conj(u)) -> d_out (d_u: device, complex [nData]; d_out: device, [nAC])
-static int prod_adjoint(hmcmt_ctx* ctx, View vj, const cplx* d_u, int wrt, int sweeps, double* d_out, hmcmt_stats& st) {
-    hipStream_t strm = ctx->stream;
-    hmcmt_ctx::Jac& J = ctx->jac;
-    const int S = vj.S;
-    vj.uData = d_u;
-    adjoint_arrays(vj, J, ctx->sv.r);
-    hipLaunchKernelGGL(k_jtvp_vbar, grid1(vj.nData, 256), dim3(256), 0, strm, vj);
-    hipLaunchKernelGGL(k_jvp_norm, dim3(1), dim3(1024), 0, strm, reinterpret_cast<double*>(vj.vbar), (const double*)nullptr, 2l * vj.nData, ctx->jvp.scale + 2);
-    hipLaunchKernelGGL(k_rxcoef, grid1(S * vj.nRx, 64), dim3(64), 0, strm, vj);
-    const int nsrc = (2 * (vj.ny + 1) + 127) / 128;
-    const size_t vecBytes = (size_t)S * vj.vstride * sizeof(cplx);
-    auto fill = [&](bool sparse) {
-        if (!sparse) (void)hipMemsetAsync(vj.R, 0, vecBytes, strm);           // (the whole right-hand side is the residual)
-        hipLaunchKernelGGL(k_src, dim3(nsrc + (vj.ny + 127) / 128, S), dim3(128), 0, strm, vj, ctx->jvp.misfit, nsrc);
-    };
-    if (int rc = borrowed_solve(ctx, J.lam, 1, sweeps, vj.zid, fill, st, ctx->hp.sysOn.data(), "Jacobian product: the adjoint")) return rc;
-    hipLaunchKernelGGL(k_jac_wb, dim3((vj.nz + vj.ny + 127) / 128, S), dim3(128), 0, strm, vj);
-    hipLaunchKernelGGL(k_jac_contract, dim3((BCC_L * vj.nz + 127) / 128, 2, S), dim3(128), 0, strm, vj);
-    hipLaunchKernelGGL(k_gradcell, dim3((vj.nCell + 127) / 128, 2, GRAD_NG), dim3(128), 0, strm, vj);
-    hipLaunchKernelGGL(k_jtvp_final, grid1(vj.nAC, 128), dim3(128), 0, strm, vj, wrt, (const double*)(ctx->jvp.scale + 2), d_out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-enum { PROD_JVP = 0, PROD_JTVP = 1, PROD_GN = 2 };
-// d_in / d_out: device pointers (jvp: v[nAC] -> Jv complex[nData]; jtvp: u complex[nData] -> [nAC]; gn: v[nAC] -> [nAC])
-static int prod_run(hmcmt_ctx* ctx, int what, const double* d_in, int wrt, double* d_out, hmcmt_stats* stOut) {
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    hipStream_t strm = ctx->stream;
-    Borrowed b(ctx, stOut);
-    hmcmt_stats& st = b.st;
-    st.nsystems = ctx->v.S;
-    View vj = product_view(ctx, P, what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : nullptr);
-    const int sweeps = cold_sweeps(ctx);
-    if (what == PROD_JVP || what == PROD_GN) {
-        if (int rc = prod_tangent(ctx, vj, d_in, wrt, sweeps, st)) return rc;
-        st.smoother_sweeps = 10 * sweeps;
-    }
-    if (what == PROD_GN) hipLaunchKernelGGL(k_jvp_w2, grid1(vj.nData, 256), dim3(256), 0, strm, vj, P.u);
-    if (what == PROD_JTVP || what == PROD_GN) {
-        const cplx* u = what == PROD_GN ? P.u : reinterpret_cast<const cplx*>(d_in);
-        if (int rc = prod_adjoint(ctx, vj, u, wrt, sweeps, d_out, st)) return rc;
-        st.smoother_sweeps += sweeps;
-    }
-    return 0;
-}
-
 static int prod_check(hmcmt_ctx* ctx, const void* in, int32_t wrt, const void* out) {
     if (int rc = family_check(ctx, "Jacobian product", "input", in, out, wrt)) return rc;
     if (!ctx->jvp.ready || !ctx->jvp.valid) {
@@ -486,11 +425,7 @@ int hmcmt_linearize_device(hmcmt_ctx* ctx, const double* d_m) {
 }  // extern "C"
 
 // ----------------------------------------------------------------------------------------------
-// block products (kernels_jvp_block.h): nvec directions, ONE solve per route over the nvec * S virtual systems.  The solve runs
-// on a second solver instance (hmcmt_ctx::Blk): the context's Solver with S and nFreq multiplied by nvec, the frequency list and
-// the inverse pivots repeated per direction, per-system arrays, sync words, reduction records, constant block and host records of
-// its own (hmcmt_ctx::Inst); the stencil coefficients and eigen-transforms are per mode and shared.  It is put in the context's
-// place for the call (inside the bracket, blk_run), so solve(), the kernel table and the fallbacks see an ordinary problem.
+// the second solver instance of products of nvec > 1 directions
 // ----------------------------------------------------------------------------------------------
 static void blk_release(hmcmt_ctx* ctx) {
     hmcmt_ctx::Blk& B = ctx->blk;
@@ -568,7 +503,51 @@ static int blk_alloc(hmcmt_ctx* ctx, int nvec) {
     return rc;
 }
 
-// the directions k_blk_norm found not identically zero -> the system flags by direction and by virtual system, made on the device
+// the inverse pivots of the linearisation point per direction (again after a new point, or for another nvec), and the frequency
+// list repeated per direction
+static int blk_pivots(hmcmt_ctx* ctx, int nvec) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    hipStream_t strm = ctx->stream;
+    if (B.gen == ctx->jvp.gen && B.genVec == nvec) return 0;
+    const unsigned gx = (unsigned)std::min<long>(64, (ctx->v.vstride + 255) / 256);
+    hipLaunchKernelGGL(k_blk_replicate, dim3(gx, ctx->v.S, nvec), dim3(256), 0, strm, (const cplx*)ctx->v.invp, (const float2*)ctx->inst.d_invp32,
+                       B.invp, B.inst.d_invp32, ctx->v.nFreq, nvec, ctx->v.vstride);
+    HIPCHK(hipGetLastError());
+    if (B.genVec != nvec) {
+        const int nF = ctx->v.nFreq;
+        std::vector<double> om((size_t)nvec * 2 * nF);
+        for (int j = 0; j < nvec; ++j)
+            for (int f = 0; f < nF; ++f) {
+                om[(size_t)j * nF + f] = ctx->hp.omega[f];
+                om[((size_t)nvec + j) * nF + f] = ctx->hp.omega[nF + f];
+            }
+        HIPCHK(hipStreamSynchronize(strm));
+        HIPCHK(hipMemcpy(B.omega, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice));
+    }
+    B.gen = ctx->jvp.gen; B.genVec = nvec;
+    return 0;
+}
+
+// the block instance in the context's place, and the virtual problem's Solver and View, for solve() (inside the bracket, which puts
+// View, Solver and the queue tables back; blk_leave: the instance)
+static void blk_enter(hmcmt_ctx* ctx, int nvec) {
+    hmcmt_ctx::Blk& B = ctx->blk;
+    std::swap(ctx->inst, B.inst);                        // (its psShadow / psConstValid come along, and go back with it: they survive between calls)
+    if (!ctx->inst.d_psync) ctx->persistCW = 0;          // (no sync words, no persistent kernel for this block: persist_ok)
+    else ctx->inst.persistSlots = std::max(1, std::min(B.slots, (nvec * ctx->v.S + 7) / 8));   // (words of the largest block seen, this call's count of systems)
+    ctx->inst.dinvValid = false;                         // (the instance's Jacobi diagonals: written where a launch-per-phase kernel needs them)
+    ctx->ss.psOrder[0].clear(); ctx->ss.psOrder[1].clear();    // (the queue tables are the context's problem's: the kernel's own order here)
+    ctx->sv = B.sv;
+    ctx->v.S *= nvec; ctx->v.nFreq *= nvec; ctx->v.omega = B.omega; ctx->v.invp = B.invp; ctx->v.sysOn = B.sysOnV;
+    ctx->v.Lam = B.lam; ctx->v.R = B.sv.r;
+    ctx->sv.S = ctx->v.S; ctx->sv.nFreq = ctx->v.nFreq;  // (arrays of the largest block seen, this call's count of systems)
+}
+static void blk_leave(hmcmt_ctx* ctx, int ownCW) {
+    std::swap(ctx->inst, ctx->blk.inst);
+    ctx->persistCW = ownCW;
+}
+
+// the directions k_dir_norm found not identically zero -> the system flags by direction and by virtual system, made on the device
 // (k_blk_flags); the host reads the flags by virtual system from mapped memory.  One synchronisation, no copy.
 static int blk_systems(hmcmt_ctx* ctx, const int* d_realOn, int S, int nvec, int& nOn) {
     hmcmt_ctx::Blk& B = ctx->blk;
@@ -582,175 +561,159 @@ static int blk_systems(hmcmt_ctx* ctx, const int* d_realOn, int S, int nvec, int
     return 0;
 }
 
-// J V -> vr.jv (d_V: device, [nvec][nAC]); vr: the REAL problem's View on the block's work arrays (kernels_jvp_block.h)
-static int blk_tangent(hmcmt_ctx* ctx, View vr, const int* d_realOn, const double* d_V, int nvec, int wrt, int sweeps, hmcmt_stats& st, int& nOn) {
-    hmcmt_ctx::Blk& B = ctx->blk;
+// ----------------------------------------------------------------------------------------------
+// the products' one pipeline.  vr: the REAL problem's View on the call's work arrays; the directions' systems (vr.sysOn, and `on`
+// for the records) are the problem's own for nvec = 1 -- no flags to make, no synchronisation or read-back in front of the solve:
+// an all-zero direction is a zero right-hand side, which leaves the solve at iteration 0 -- and blk_systems' for nvec > 1.
+// ----------------------------------------------------------------------------------------------
+static const int* prod_on(const hmcmt_ctx* ctx, int nvec) { return nvec > 1 ? ctx->blk.h_onV : ctx->hp.sysOn.data(); }
+// the work arrays of a call: one direction's (hmcmt_ctx::Jvp), or the block's
+static const hmcmt_ctx::ProdArrays& prod_arrays(const hmcmt_ctx* ctx, int nvec) {
+    if (nvec > 1) return ctx->blk;
+    return ctx->jvp;
+}
+
+// J V -> vr.jv (d_V: device, [nvec][nAC])
+static int prod_tangent(hmcmt_ctx* ctx, View vr, const int* d_realOn, const double* d_V, int nvec, int wrt, int sweeps, hmcmt_stats& st, int& nOn) {
     hipStream_t strm = ctx->stream;
     const int S = vr.S;
     vr.tanV = d_V;
     HIPCHK(hipMemsetAsync(vr.jv, 0, sizeof(cplx) * (size_t)nvec * vr.nData, strm));
-    hipLaunchKernelGGL(k_blk_dsig, dim3((vr.nCell + 255) / 256, nvec), dim3(256), 0, strm, vr, wrt, nvec);
-    hipLaunchKernelGGL(k_blk_norm, dim3(nvec), dim3(1024), 0, strm, vr.dSig, (const double*)vr.sigma, (long)vr.nCell, (long)vr.nCell, B.scale, 0, B.dirOn);
-    if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
-    if (nOn == 0) return 0;                              // (every direction zero: J V = 0 stands)
-    hipLaunchKernelGGL(k_blk_dbc, dim3((2 * vr.nz + vr.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S, (nvec + BLK_KB - 1) / BLK_KB), dim3(64 * DBC_WAVES), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_dir_dsig, dim3((vr.nCell + 255) / 256, nvec), dim3(256), 0, strm, vr, wrt, nvec);
+    hipLaunchKernelGGL(k_dir_norm, dim3(nvec), dim3(1024), 0, strm, vr.dSig, (const double*)vr.sigma, (long)vr.nCell, (long)vr.nCell,
+                       prod_arrays(ctx, nvec).scale, 0, nvec > 1 ? ctx->blk.dirOn : nullptr);
+    if (nvec > 1) {
+        if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
+        if (nOn == 0) return 0;                          // (every direction zero: J V = 0 stands)
+    }
+    const dim3 gd((2 * vr.nz + vr.ny - 1 + DBC_WAVES - 1) / DBC_WAVES, S, nvec > 1 ? (nvec + BLK_KB - 1) / BLK_KB : 1);
+    const auto kdbc = nvec > 1 ? k_dbc<BLK_KB> : k_dbc<1>;
+    hipLaunchKernelGGL(kdbc, gd, dim3(64 * DBC_WAVES), 0, strm, vr, nvec);
     auto fill = [&](bool) {
-        hipLaunchKernelGGL(k_blk_rhs, dim3((unsigned)((vr.vstride + 255) / 256), S, nvec), dim3(256), 0, strm, vr, nvec);
+        hipLaunchKernelGGL(k_dir_rhs, dim3((unsigned)((vr.vstride + 255) / 256), S, nvec), dim3(256), 0, strm, vr, nvec);
     };
-    if (int rc = borrowed_solve(ctx, B.lam, 0, sweeps, -1, fill, st, B.h_onV, "Jacobian product: the tangent")) return rc;
-    hipLaunchKernelGGL(k_blk_data, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
+    if (int rc = borrowed_solve(ctx, vr.Lam, 0, sweeps, -1, fill, st, prod_on(ctx, nvec), "Jacobian product: the tangent")) return rc;
+    hipLaunchKernelGGL(k_dir_data, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 // Re(J^T conj(U)) -> d_out (d_U: device, complex [nvec][nData]; d_out: device, [nvec][nAC])
-static int blk_adjoint(hmcmt_ctx* ctx, View vr, const int* d_realOn, const cplx* d_U, int nvec, int wrt, int sweeps, double* d_out, hmcmt_stats& st, int& nOn) {
-    hmcmt_ctx::Blk& B = ctx->blk;
+static int prod_adjoint(hmcmt_ctx* ctx, View vr, const int* d_realOn, const cplx* d_U, int nvec, int wrt, int sweeps, double* d_out, hmcmt_stats& st, int& nOn) {
     hipStream_t strm = ctx->stream;
     const int S = vr.S;
     vr.uData = d_U;
-    hipLaunchKernelGGL(k_blk_vbar, grid1(vr.nData, 256), dim3(256), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_norm, dim3(nvec), dim3(1024), 0, strm, reinterpret_cast<double*>(vr.vbar), (const double*)nullptr, 2l * vr.nData, 2l * vr.nData, B.scale, 2, B.dirOn);
-    if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
-    if (nOn == 0) { HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)nvec * vr.nAC, strm)); return 0; }
-    hipLaunchKernelGGL(k_blk_rxcoef, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_dir_vbar, grid1(vr.nData, 256), dim3(256), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_dir_norm, dim3(nvec), dim3(1024), 0, strm, reinterpret_cast<double*>(vr.vbar), (const double*)nullptr, 2l * vr.nData, 2l * vr.nData,
+                       prod_arrays(ctx, nvec).scale, 2, nvec > 1 ? ctx->blk.dirOn : nullptr);
+    if (nvec > 1) {
+        if (int rc = blk_systems(ctx, d_realOn, S, nvec, nOn)) return rc;
+        if (nOn == 0) { HIPCHK(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)nvec * vr.nAC, strm)); return 0; }
+    }
+    hipLaunchKernelGGL(k_dir_rxcoef, dim3((vr.nRx + 63) / 64, S), dim3(64), 0, strm, vr, nvec);
     const int nsrc = (2 * (vr.ny + 1) + 127) / 128;
     const size_t vecBytes = (size_t)nvec * S * vr.vstride * sizeof(cplx);
     auto fill = [&](bool sparse) {
         if (!sparse) (void)hipMemsetAsync(vr.R, 0, vecBytes, strm);           // (the whole right-hand side is the residual)
-        hipLaunchKernelGGL(k_blk_src, dim3(nsrc + (vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nsrc, nvec);
+        // (one direction: the gradient's own k_src, with the receiver table in LDS -- the one place with two kernels, k_blk_src)
+        if (nvec > 1) hipLaunchKernelGGL(k_blk_src, dim3(nsrc + (vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nsrc, nvec);
+        else hipLaunchKernelGGL(k_src, dim3(nsrc + (vr.ny + 127) / 128, S), dim3(128), 0, strm, vr, ctx->jvp.misfit, nsrc);
     };
-    if (int rc = borrowed_solve(ctx, B.lam, 1, sweeps, vr.zid, fill, st, B.h_onV, "Jacobian product: the adjoint")) return rc;
-    hipLaunchKernelGGL(k_blk_wb, dim3((vr.nz + vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_contract, dim3((BCC_L * vr.nz + 127) / 128, 2 * ((nvec + BLK_KB - 1) / BLK_KB), S), dim3(128), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_gradcell, dim3((vr.nCell + 127) / 128, 2 * GRAD_NG, nvec), dim3(128), 0, strm, vr, nvec);
-    hipLaunchKernelGGL(k_blk_final, grid1(vr.nAC, 128), dim3(128), 0, strm, vr, wrt, d_out, nvec);
+    if (int rc = borrowed_solve(ctx, vr.Lam, 1, sweeps, vr.zid, fill, st, prod_on(ctx, nvec), "Jacobian product: the adjoint")) return rc;
+    hipLaunchKernelGGL(k_dir_wb, dim3((vr.nz + vr.ny + 127) / 128, S, nvec), dim3(128), 0, strm, vr, nvec);
+    const dim3 gc((BCC_L * vr.nz + 127) / 128, nvec > 1 ? 2 * ((nvec + BLK_KB - 1) / BLK_KB) : 2, S);
+    const auto kcontract = nvec > 1 ? k_contract<BLK_KB> : k_contract<1>;
+    hipLaunchKernelGGL(kcontract, gc, dim3(128), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_dir_gradcell, dim3((vr.nCell + 127) / 128, 2 * GRAD_NG, nvec), dim3(128), 0, strm, vr, nvec);
+    hipLaunchKernelGGL(k_dir_final, grid1(vr.nAC, 128), dim3(128), 0, strm, vr, wrt, d_out, nvec);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-static int blk_run(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int wrt, double* d_out, hmcmt_stats* stOut) {
-    hmcmt_ctx::Jvp& P = ctx->jvp;
+enum { PROD_JVP = 0, PROD_JTVP = 1, PROD_GN = 2 };
+// d_in / d_out: device pointers, [nvec] times (jvp: v[nAC] -> Jv complex[nData]; jtvp: u complex[nData] -> [nAC]; gn: v[nAC] -> [nAC]).
+// Statistics: nsystems is S from the single entry points and the count of systems solved from the block ones (blockStats).
+static int prod_run(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int wrt, double* d_out, bool blockStats, hmcmt_stats* stOut) {
     hmcmt_ctx::Blk& B = ctx->blk;
     hipStream_t strm = ctx->stream;
-    // the inverse pivots of the linearisation point, per direction (again after a new point, or for more directions)
-    if (B.gen != P.gen || B.genVec != nvec) {
-        const unsigned gx = (unsigned)std::min<long>(64, (ctx->v.vstride + 255) / 256);
-        hipLaunchKernelGGL(k_blk_replicate, dim3(gx, ctx->v.S, nvec), dim3(256), 0, strm, (const cplx*)ctx->v.invp, (const float2*)ctx->inst.d_invp32,
-                           B.invp, B.inst.d_invp32, ctx->v.nFreq, nvec, ctx->v.vstride);
-        HIPCHK(hipGetLastError());
-        if (B.genVec != nvec) {                          // the frequency list, repeated per direction
-            const int nF = ctx->v.nFreq;
-            std::vector<double> om((size_t)nvec * 2 * nF);
-            for (int j = 0; j < nvec; ++j)
-                for (int f = 0; f < nF; ++f) {
-                    om[(size_t)j * nF + f] = ctx->hp.omega[f];
-                    om[((size_t)nvec + j) * nF + f] = ctx->hp.omega[nF + f];
-                }
-            HIPCHK(hipStreamSynchronize(strm));
-            HIPCHK(hipMemcpy(B.omega, om.data(), sizeof(double) * om.size(), hipMemcpyHostToDevice));
-        }
-        B.gen = P.gen; B.genVec = nvec;
-    }
+    if (nvec > 1)
+        if (int rc = blk_pivots(ctx, nvec)) return rc;
     Borrowed b(ctx, stOut);
     hmcmt_stats& st = b.st;
-    // the block instance in the context's place ...
-    const int ownCW = ctx->persistCW;
-    std::swap(ctx->inst, B.inst);                        // (its psShadow / psConstValid come along, and go back with it: they survive between calls)
-    AtExit instanceBack([&] { std::swap(ctx->inst, B.inst); ctx->persistCW = ownCW; });
-    if (!ctx->inst.d_psync) ctx->persistCW = 0;          // (no sync words, no persistent kernel for this block: persist_ok)
-    else ctx->inst.persistSlots = std::max(1, std::min(B.slots, (nvec * ctx->v.S + 7) / 8));   // (words of the largest block seen, this call's count of systems)
-    ctx->inst.dinvValid = false;                         // (the instance's Jacobi diagonals: written where a launch-per-phase kernel needs them)
-    ctx->ss.psOrder[0].clear(); ctx->ss.psOrder[1].clear();    // (the queue tables are the context's problem's: the kernel's own order here)
-    // ... the REAL problem's View on the block's work arrays, for the products' kernels ...
-    View vr = product_view(ctx, B, what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : nullptr);
+    // the REAL problem's View on the work arrays, for the products' kernels ...
+    const hmcmt_ctx::ProdArrays& W = prod_arrays(ctx, nvec);
+    View vr = product_view(ctx, W, what == PROD_JVP ? reinterpret_cast<cplx*>(d_out) : nullptr);
     const int* d_realOn = ctx->v.sysOn;                  // (the problem's own flags, [S])
-    adjoint_arrays(vr, B, B.sv.r);
-    vr.dF = B.lam; vr.tanScale = B.scale; vr.sysOn = B.sysOnDir;
-    vr.tanV = B.vin; vr.uData = B.u;
-    // ... and the virtual problem's Solver and View, for solve()
-    ctx->sv = B.sv;
-    ctx->v.S = nvec * vr.S; ctx->v.nFreq = nvec * vr.nFreq; ctx->v.omega = B.omega; ctx->v.invp = B.invp; ctx->v.sysOn = B.sysOnV;
-    ctx->v.Lam = B.lam; ctx->v.R = B.sv.r;
-    ctx->sv.S = ctx->v.S; ctx->sv.nFreq = ctx->v.nFreq;  // (arrays of the largest block seen, this call's count of systems)
+    int nOn = ctx->ss.nSysOn;                            // (one direction: the systems that carry data)
+    st.nsystems = !blockStats ? vr.S : nvec == 1 ? nOn : 0;
+    // ... and for solve(): the context itself for one direction -- no second solver instance --, the block instance in its place
+    const int ownCW = ctx->persistCW;
+    AtExit instanceBack([&] { if (nvec > 1) blk_leave(ctx, ownCW); });
+    if (nvec > 1) { blk_enter(ctx, nvec); vr.sysOn = B.sysOnDir; }
+    if (nvec > 1) adjoint_arrays(vr, B, ctx->sv.r);
+    else adjoint_arrays(vr, ctx->jac, ctx->sv.r);        // (one direction: the explicit Jacobian's arrays)
+    vr.dF = vr.Lam;
     const int sweeps = cold_sweeps(ctx);
-    int nOn = 0;
     if (what == PROD_JVP || what == PROD_GN) {
-        if (int rc = blk_tangent(ctx, vr, d_realOn, d_in, nvec, wrt, sweeps, st, nOn)) return rc;
-        st.nsystems = nOn;
+        if (int rc = prod_tangent(ctx, vr, d_realOn, d_in, nvec, wrt, sweeps, st, nOn)) return rc;
+        if (blockStats) st.nsystems = nOn;
         st.smoother_sweeps = 10 * sweeps;
     }
-    if (what == PROD_GN) hipLaunchKernelGGL(k_blk_w2, grid1(vr.nData, 256), dim3(256), 0, strm, vr, B.u, nvec);
+    if (what == PROD_GN) hipLaunchKernelGGL(k_dir_w2, grid1(vr.nData, 256), dim3(256), 0, strm, vr, W.u, nvec);
     if (what == PROD_JTVP || what == PROD_GN) {
-        const cplx* u = what == PROD_GN ? B.u : reinterpret_cast<const cplx*>(d_in);
-        if (int rc = blk_adjoint(ctx, vr, d_realOn, u, nvec, wrt, sweeps, d_out, st, nOn)) return rc;
-        if (what == PROD_JTVP) st.nsystems = nOn;
+        const cplx* u = what == PROD_GN ? W.u : reinterpret_cast<const cplx*>(d_in);
+        if (int rc = prod_adjoint(ctx, vr, d_realOn, u, nvec, wrt, sweeps, d_out, st, nOn)) return rc;
+        if (blockStats && what == PROD_JTVP) st.nsystems = nOn;
         st.smoother_sweeps += sweeps;
     }
     return 0;
 }
 
-// ----------------------------------------------------------------------------------------------
-// the products' entry points: nvec = 1 is the single product, more the block
-// ----------------------------------------------------------------------------------------------
+// (one direction allocates nothing: a context that only ever makes single products has no block arrays)
 static int prod_ready(hmcmt_ctx* ctx, int nvec) {
     HIPCHK(hipSetDevice(ctx->device));
     return nvec > 1 ? blk_alloc(ctx, nvec) : 0;
 }
-// d_in / d_out: device pointers, [nvec] times the single product's
-static int prod_device(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int wrt, double* d_out, hmcmt_stats* st) {
-    return nvec == 1 ? prod_run(ctx, what, d_in, wrt, d_out, st) : blk_run(ctx, what, d_in, nvec, wrt, d_out, st);
-}
 // host pointers: stage the input, run on the device buffers, bring the result back
-static int prod_host(hmcmt_ctx* ctx, int what, const double* in, int nvec, int wrt, double* out, hmcmt_stats* st) {
+static int prod_host(hmcmt_ctx* ctx, int what, const double* in, int nvec, int wrt, double* out, bool blockStats, hmcmt_stats* st) {
     const size_t nAC = ctx->v.nAC, nData = ctx->v.nData;
     const bool inData = what == PROD_JTVP, outData = what == PROD_JVP;
     const size_t nin = (size_t)nvec * (inData ? 2 * nData : nAC), nout = (size_t)nvec * (outData ? 2 * nData : nAC);
     for (size_t i = 0; i < nin; ++i)
         if (!std::isfinite(in[i])) { ctx->err = std::string(nvec > 1 ? "block " : "") + "Jacobian product: non-finite input value"; return HMCMT_EINVAL; }
     if (int rc = prod_ready(ctx, nvec)) return rc;
-    // (staging: u in the instance's u, v in vin; J v comes back through u, the cell vectors through out)
-    hmcmt_ctx::Jvp& P = ctx->jvp;
-    hmcmt_ctx::Blk& B = ctx->blk;
-    cplx* const du = nvec == 1 ? P.u : B.u;
-    double* d_in = inData ? reinterpret_cast<double*>(du) : nvec == 1 ? P.vin : B.vin;
-    double* d_out = outData ? reinterpret_cast<double*>(du) : nvec == 1 ? P.out : B.out;
+    // (staging: u in the set's u, v in vin; J v comes back through u, the cell vectors through out)
+    const hmcmt_ctx::ProdArrays& W = prod_arrays(ctx, nvec);
+    double* d_in = inData ? reinterpret_cast<double*>(W.u) : W.vin;
+    double* d_out = outData ? reinterpret_cast<double*>(W.u) : W.out;
     HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = prod_device(ctx, what, d_in, nvec, wrt, d_out, st)) return rc;
+    if (int rc = prod_run(ctx, what, d_in, nvec, wrt, d_out, blockStats, st)) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
-static int prod_entry(hmcmt_ctx* ctx, bool host, int what, const double* in, int32_t wrt, double* out, hmcmt_stats* st) {
-    if (!ctx) return HMCMT_EINVAL;
-    if (int rc = prod_check(ctx, in, wrt, out)) return rc;
-    if (host) return prod_host(ctx, what, in, 1, wrt, out, st);
-    if (int rc = prod_ready(ctx, 1)) return rc;
-    return prod_device(ctx, what, in, 1, wrt, out, st);
-}
-// a block of one direction IS the single product (the contract defines direction j as the single call's result): the same code,
-// no second solver instance, no flags to read back.  A zero right-hand side leaves the solve at iteration 0 there as well.
-static int blk_entry(hmcmt_ctx* ctx, bool host, int what, const double* in, int32_t nvec, int32_t wrt, double* out, hmcmt_stats* st) {
+// the entry points: nvec directions; a block of one direction IS the single product (the contract defines direction j as the
+// single call's result) -- the two kinds of entry point differ in their argument check and in what nsystems counts
+static int prod_entry(hmcmt_ctx* ctx, bool host, bool block, int what, const double* in, int32_t nvec, int32_t wrt, double* out, hmcmt_stats* st) {
     if (!ctx) return HMCMT_EINVAL;
     if (nvec < 1 || nvec > HMCMT_BLOCK_MAX) { ctx->err = "block Jacobian product: nvec must be 1 .. HMCMT_BLOCK_MAX (32)"; return HMCMT_EINVAL; }
     if (int rc = prod_check(ctx, in, wrt, out)) return rc;
-    int rc = 0;
-    if (host) rc = prod_host(ctx, what, in, nvec, wrt, out, st);
-    else if (!(rc = prod_ready(ctx, nvec))) rc = prod_device(ctx, what, in, nvec, wrt, out, st);
-    if (nvec == 1 && st) st->nsystems = ctx->ss.nSysOn;  // (the block's count: the systems that carry data)
-    return rc;
+    if (host) return prod_host(ctx, what, in, nvec, wrt, out, block, st);
+    if (int rc = prod_ready(ctx, nvec)) return rc;
+    return prod_run(ctx, what, in, nvec, wrt, out, block, st);
 }
+
 extern "C" {
-int hmcmt_jvp(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Jv, hmcmt_stats* st) { return prod_entry(ctx, true, PROD_JVP, v, wrt, Jv, st); }
-int hmcmt_jtvp(hmcmt_ctx* ctx, const double* u, int32_t wrt, double* JTu, hmcmt_stats* st) { return prod_entry(ctx, true, PROD_JTVP, u, wrt, JTu, st); }
-int hmcmt_gn_hessvec(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Hv, hmcmt_stats* st) { return prod_entry(ctx, true, PROD_GN, v, wrt, Hv, st); }
-int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Jv, hmcmt_stats* st) { return prod_entry(ctx, false, PROD_JVP, d_v, wrt, d_Jv, st); }
-int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st) { return prod_entry(ctx, false, PROD_JTVP, d_u, wrt, d_JTu, st); }
-int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st) { return prod_entry(ctx, false, PROD_GN, d_v, wrt, d_Hv, st); }
-int hmcmt_jvp_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* JV, hmcmt_stats* st) { return blk_entry(ctx, true, PROD_JVP, V, nvec, wrt, JV, st); }
-int hmcmt_jtvp_block(hmcmt_ctx* ctx, const double* U, int32_t nvec, int32_t wrt, double* JTU, hmcmt_stats* st) { return blk_entry(ctx, true, PROD_JTVP, U, nvec, wrt, JTU, st); }
-int hmcmt_gn_hessvec_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* HV, hmcmt_stats* st) { return blk_entry(ctx, true, PROD_GN, V, nvec, wrt, HV, st); }
-int hmcmt_jvp_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_JV, hmcmt_stats* st) { return blk_entry(ctx, false, PROD_JVP, d_V, nvec, wrt, d_JV, st); }
-int hmcmt_jtvp_block_device(hmcmt_ctx* ctx, const double* d_U, int32_t nvec, int32_t wrt, double* d_JTU, hmcmt_stats* st) { return blk_entry(ctx, false, PROD_JTVP, d_U, nvec, wrt, d_JTU, st); }
-int hmcmt_gn_hessvec_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_HV, hmcmt_stats* st) { return blk_entry(ctx, false, PROD_GN, d_V, nvec, wrt, d_HV, st); }
+int hmcmt_jvp(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Jv, hmcmt_stats* st) { return prod_entry(ctx, true, false, PROD_JVP, v, 1, wrt, Jv, st); }
+int hmcmt_jtvp(hmcmt_ctx* ctx, const double* u, int32_t wrt, double* JTu, hmcmt_stats* st) { return prod_entry(ctx, true, false, PROD_JTVP, u, 1, wrt, JTu, st); }
+int hmcmt_gn_hessvec(hmcmt_ctx* ctx, const double* v, int32_t wrt, double* Hv, hmcmt_stats* st) { return prod_entry(ctx, true, false, PROD_GN, v, 1, wrt, Hv, st); }
+int hmcmt_jvp_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Jv, hmcmt_stats* st) { return prod_entry(ctx, false, false, PROD_JVP, d_v, 1, wrt, d_Jv, st); }
+int hmcmt_jtvp_device(hmcmt_ctx* ctx, const double* d_u, int32_t wrt, double* d_JTu, hmcmt_stats* st) { return prod_entry(ctx, false, false, PROD_JTVP, d_u, 1, wrt, d_JTu, st); }
+int hmcmt_gn_hessvec_device(hmcmt_ctx* ctx, const double* d_v, int32_t wrt, double* d_Hv, hmcmt_stats* st) { return prod_entry(ctx, false, false, PROD_GN, d_v, 1, wrt, d_Hv, st); }
+int hmcmt_jvp_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* JV, hmcmt_stats* st) { return prod_entry(ctx, true, true, PROD_JVP, V, nvec, wrt, JV, st); }
+int hmcmt_jtvp_block(hmcmt_ctx* ctx, const double* U, int32_t nvec, int32_t wrt, double* JTU, hmcmt_stats* st) { return prod_entry(ctx, true, true, PROD_JTVP, U, nvec, wrt, JTU, st); }
+int hmcmt_gn_hessvec_block(hmcmt_ctx* ctx, const double* V, int32_t nvec, int32_t wrt, double* HV, hmcmt_stats* st) { return prod_entry(ctx, true, true, PROD_GN, V, nvec, wrt, HV, st); }
+int hmcmt_jvp_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_JV, hmcmt_stats* st) { return prod_entry(ctx, false, true, PROD_JVP, d_V, nvec, wrt, d_JV, st); }
+int hmcmt_jtvp_block_device(hmcmt_ctx* ctx, const double* d_U, int32_t nvec, int32_t wrt, double* d_JTU, hmcmt_stats* st) { return prod_entry(ctx, false, true, PROD_JTVP, d_U, nvec, wrt, d_JTU, st); }
+int hmcmt_gn_hessvec_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_HV, hmcmt_stats* st) { return prod_entry(ctx, false, true, PROD_GN, d_V, nvec, wrt, d_HV, st); }
 }  // extern "C"

@@ -36,42 +36,8 @@ __global__ __launch_bounds__(128) void k_jac_src(View v, int j, cplx* qJ, int ns
     else if (iy == v.ny) v.srcB[(long)s * 4 + row * 2 + 1] = acc;
 }
 
-// boundary weights -Aio^T s (+ the source's boundary part) and the bottom-row column weights: k_wb's items
-__global__ __launch_bounds__(128) void k_jac_wb(View v) {
-    const int s = blockIdx.y, e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (!v.sysOn[s]) return;
-    if (e < v.nz) item_wside(v, s, e + 1);
-    else if (e < v.nz + v.ny) item_colw(v, s, e - v.nz);
-}
-
-// dBC^T w per edge profile: k_bcsens_contract's arithmetic (BCC_L lanes per column, contiguous quarters of the rows, the
-// quarters added in lane order)
-__global__ __launch_bounds__(128) void k_jac_contract(View v) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x, c = t / BCC_L, l = t % BCC_L, prof = blockIdx.y, s = blockIdx.z;
-    cplx acc = cplx{0.0, 0.0};
-    const bool on = c < v.nz && v.sysOn[s];
-    if (on) {
-        const cplx* D = v.dBC + ((long)s * 2 + prof) * v.nz * v.nz + c;
-        const cplx* w = (prof == 0 ? v.wL : v.wR) + (long)s * v.nz;
-        const int per = (v.nz + BCC_L - 1) / BCC_L, j0 = l * per, j1 = min(j0 + per, v.nz);
-        int j = j0;
-        for (; j + 8 <= j1; j += 8) {
-            cplx d[8], ww[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { d[q] = D[(long)(j + q) * v.nz]; ww[q] = w[j + q]; }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc += d[q] * ww[q];
-        }
-        for (; j < j1; ++j) acc += D[(long)j * v.nz] * w[j];
-    }
-    const double r1 = __shfl_down(acc.re, 1, BCC_L), r2 = __shfl_down(acc.re, 2, BCC_L), r3 = __shfl_down(acc.re, 3, BCC_L);
-    const double i1 = __shfl_down(acc.im, 1, BCC_L), i2 = __shfl_down(acc.im, 2, BCC_L), i3 = __shfl_down(acc.im, 3, BCC_L);
-    if (on && l == 0) {
-        const cplx tot = cplx{((acc.re + r1) + r2) + r3, ((acc.im + i1) + i2) + i3};
-        const long o = (long)s * v.nz + c;
-        if (prof == 0) v.gL[o] = tot; else v.gR[o] = tot;
-    }
-}
+// (behind the batch's solve: the boundary weights and the dBC contraction are the products' kernels at one direction, k_dir_wb and
+// k_contract<1> of kernels_jvp.h)
 
 // The rows of one batch are grouped by system (JacGroup: a run of the batch's list with one system): dZ of the system is formed
 // once per cell (jac_cell), and every datum of the group -- for Rho_Pha the apparent resistivity and the phase of one receiver and

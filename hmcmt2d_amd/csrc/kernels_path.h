@@ -588,7 +588,6 @@ __global__ __launch_bounds__(64) void k_rxall(View v, int wantGrad, SolveRec rec
     if (wantGrad) v.rxCoef[e] = c;
     tick_end(v.ticks, TK_RXALL);
 }
-__global__ void k_rxcoef(View v) { int e = TID1; if (e < v.S * v.nRx) item_rxcoef(v, e / v.nRx, e % v.nRx); }
 // adjoint sources; workgroup (0,0) also adds up the misfit terms (a reduction nothing on the device waits for: no
 // launch of its own on the critical path between the solves)
 __global__ __launch_bounds__(128) void k_src(View v, double* misfitOut, int nsrc) {
@@ -658,19 +657,11 @@ __global__ __launch_bounds__(128) void k_src(View v, double* misfitOut, int nsrc
     }
     tick_end(v.ticks, TK_SRC);
 }
-__global__ void k_wb(View v, SolveRec rec) {
-    if (gate_closed(v)) return;
-    int e = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
-    tick_begin(v.ticks, TK_WB);
-    if (rec.recI && e == 0) write_solve_rec(rec, s);
-    if (e < v.nz) item_wside(v, s, e + 1);
-    else if (e < v.nz + v.ny) item_colw(v, s, e - v.nz);
-    tick_end(v.ticks, TK_WB);
-}
-// k_wb and k_gradcell in ONE launch (end of round 5): the per-cell P-terms read the two solves' fields only, the boundary weights
-// feed k_bcsens_contract -- nothing of one is read by the other, and as two launches of a few microseconds each they were two
-// boundaries of the serial tail behind the adjoint solve.  Blocks [0, nwb) are k_wb's (nwbx per system), the rest k_gradcell's
-// (ngcx per mode and frequency group).
+// The boundary weights (item_wside / item_colw: k_wb until then) and the per-cell P-terms (item_gradcell_group: k_gradcell) in ONE
+// launch (end of round 5): the P-terms read the two solves' fields only, the boundary weights feed k_bcsens_contract -- nothing of
+// one is read by the other, and as two launches of a few microseconds each they were two boundaries of the serial tail behind the
+// adjoint solve.  Blocks [0, nwb) are the boundary weights' (nwbx per system), the rest the P-terms' (ngcx per mode and frequency
+// group).
 __global__ __launch_bounds__(128) void k_wb_gradcell(View v, SolveRec rec, int nwbx, int ngcx) {
     if (gate_closed(v)) return;
     const int nwb = nwbx * v.S;
@@ -729,17 +720,6 @@ __global__ void k_bcsens_contract(View v, double* lfPart) {
         if (prof == 0) v.gL[o] = tot; else v.gR[o] = tot;
     }
     tick_end(v.ticks, TK_BCSENS);
-}
-__global__ void k_gradcell(View v) {
-    if (gate_closed(v)) return;
-    int c = blockIdx.x * blockDim.x + threadIdx.x, mode = blockIdx.y, grp = blockIdx.z;
-    tick_begin(v.ticks, TK_GRADCELL);
-    if (c < v.nCell) item_gradcell_group(v, mode, grp, c);
-    tick_end(v.ticks, TK_GRADCELL);
-}
-__global__ __launch_bounds__(64) void k_qterm(View v) {
-    int ky = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
-    if (ky < v.ny) item_qterm(v, s, ky);
 }
 // final assembly with EIGHT lanes per active cell (round 6; four until then: a latency-bound loop over the systems -- the last kernel of a
 // leapfrog step, and the next step's first waits for it), each taking every eighth system / partial sum; the eight partial sums are

@@ -10,7 +10,8 @@ import pytest
 
 from hmcmt2d_amd import lib as L
 from hmcmt2d_amd.lib import HipContext, HmcmtError
-from tests.helpers import make_problem, relmax
+from tests import tipper_ref as TR
+from tests.helpers import make_problem, ragged_problem, rhophase_problem, relmax
 from tests.test_gpu_jacobian import SHALLOW_TOL, DEEP_TOL, _ran_the_persistent_kernel
 from tests.test_gpu_jvp import ROUTES_TOL, _case, _deep, _chain
 
@@ -275,10 +276,16 @@ def test_fp64_preconditioner_blocks_of_16_2_16_cfg2():
     assert worst < ROUTES_TOL, worst
 
 
-def test_a_block_of_one_is_the_single_product_tiny():
-    """nvec = 1 is the single product's own code: the same bits; nsystems is the count of systems that carry data; an all-zero
-    direction is exactly zero and costs no iteration."""
-    mesh, data, inv, m = make_problem("tiny")
+def _a_block_of_one_is_the_single_product(name):
+    """nvec = 1 runs the one pipeline without its block-only steps, as the single entry points do: the same bits; nsystems is the
+    count of systems that carry data (ragged: a quarter of the data masked); an all-zero direction is
+    exactly zero and costs no iteration.  The problems are test_gpu_jvp._case's, without their oracle Jacobians."""
+    if name == "rhophase_tiny":
+        mesh, data, inv, m = rhophase_problem("tiny")[:4]
+    elif name == "tipper":
+        mesh, data, inv, m = TR.tipper_problem("tiny", "Impedance", with_impedance=False)
+    else:
+        mesh, data, inv, m = ragged_problem(23, 17, 3, 3, 3, 4) if name == "ragged" else make_problem(name)
     rng = np.random.default_rng(25)
     v = rng.standard_normal(len(m))
     u = rng.standard_normal(len(inv.dataW)) + 1j * rng.standard_normal(len(inv.dataW))
@@ -293,6 +300,16 @@ def test_a_block_of_one_is_the_single_product_tiny():
         st = ctx.block_stats
         assert not np.any(z) and st["iters_fwd_sum"] == 0 and st["iters_adj_sum"] == 0 and st["status"] == 0, st
     ctx.close()
+
+
+def test_a_block_of_one_is_the_single_product_tiny():
+    _a_block_of_one_is_the_single_product("tiny")
+
+
+@pytest.mark.parametrize("name", ["ragged", "rhophase_tiny", "tipper"])
+def test_a_block_of_one_is_the_single_product(name):
+    """the same on the suite's other smallest problems: masked data and a fixed cell, real data, TE systems only"""
+    _a_block_of_one_is_the_single_product(name)
 
 
 def test_block_products_equal_the_single_products_cfg5_device():

@@ -3,10 +3,11 @@ declarations, exports and prototypes against the ctypes argtypes and the Julia c
 the Python wrappers' shape and dtype checks, and the premise of the solver route -- a problem whose frequency list is repeated k
 times has, per repeated system, the operator and the pivots of the original system (host instantiation, tests/emul/emul.cpp).
 
-The block kernels (kernels_jvp_block.h) add no item function and change none: they call the single products' item functions of
-hmcmt_items.h on a View whose pointers are moved to a direction (dir_view), and the two dBC contractions repeat the single kernels'
-arithmetic per direction.  Neither has a host instantiation: the index mapping of dir_view / blk_sv and the contractions are held
-to the single products only on the GPU (tests/test_gpu_jvp_block.py); the mapping sv(j, s) itself is the one checked here."""
+The products' kernels (kernels_jvp.h: one family, launched with the count of directions) add no item function and change none:
+they call the item functions of hmcmt_items.h on a View whose pointers are moved to a direction (dir_view), and the two dBC
+contractions (k_dbc, k_contract) repeat the item functions' arithmetic per direction.  Neither has a host instantiation: the index
+mapping of dir_view / blk_sv and the contractions are held to the oracle and to the single entry points only on the GPU
+(tests/test_gpu_jvp.py, tests/test_gpu_jvp_block.py); the mapping sv(j, s) itself is the one checked here."""
 import copy
 import ctypes as C
 import os
