@@ -10,11 +10,11 @@ from .structs import (TensorMesh2D, MTData, HMCPrior, HMCParameter, HMCStatus, I
                       initHMCPrior, initHMCParameter, initHMCStatus)
 from .invsetup import setupInverseDataModel, setActiveElement, compDataWeightMat
 from .fileio import (readEMModel2D, writeEMModel2D, readMT2DData, writeMT2DData, readstartupFile,
-                     outputHMCSamples, getPosteriorModel)
+                     outputHMCSamples, getPosteriorModel, getPosteriorModelFromMoments)
 from .sampler import (compDataGradient, compDataMisfit, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, getHamiltonian, proposeLeapfrog, proposeLeapfrogDevice,
                       runHMCSampler,
                       parallelHMCSampler, getKineticEnergy, getKineticGradient, getMomentumVector,
-                      setMassMatrix, checkParameterBound, get_context, release_context)
+                      setMassMatrix, checkParameterBound, get_context, release_context, mergeMoments, gelmanRubin)
 from .lib import HipContext, HmcmtError, build_library
 
 # aliases used by BASELINE.json's north_star / the user guide

@@ -11,6 +11,7 @@
 //   kernels_fused.h   the fused COCG iteration (k_spmv_fused, k_update_fused), solve start / end, initial guesses
 //   kernels_persist.h the whole COCG solve as ONE persistent kernel (round 4: a system = 8 workgroups of one XCD, r in
 //                     registers, per-system barriers in the XCD's L2) -- the default where it applies
+//   kernels_chain.h   the vector kernels of the device-resident HMC chain (hmcmt_chain_*); host_chain.h is its host code
 //   kernels_path.h    "item" kernels, one thread per node / cell / receiver / boundary column with bodies in
 //                     hmcmt_items.h (assembly from sigma, 1-D boundary fields and sensitivities, receiver functionals,
 //                     adjoint sources, J^T v accumulation), and the leapfrog vector kernels
@@ -60,6 +61,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_persist4.h"
 #include "kernels_path.h"
 #include "kernels_mass.h"
+#include "kernels_chain.h"
 #include "kernels_jac.h"
 #include "kernels_jvp.h"
 
@@ -230,6 +232,24 @@ struct hmcmt_ctx {
         double *d_r = nullptr, *d_z = nullptr, *d_pp = nullptr, *d_q = nullptr, *d_s = nullptr;   // PCG vectors, scalars [8]
         int* d_map = nullptr;                             // [nzb*nyb] active index of each box cell, -1 frozen
     } mass;
+    // the device-resident HMC chain (hmcmt_chain_*, host_chain.h, kernels_chain.h)
+    long long stateGen = 0;               // counts the evaluations and option changes of the context: a chain compares it with the value it left
+                                          // (a plain member ON PURPOSE: the calls that borrow the context count too)
+    struct Chain {
+        bool active = false, haveMomentum = false;
+        int cur = 0;                      // d_m[cur] / d_pred[cur]: the current state, [cur ^ 1]: the proposal
+        double *d_m[2] = {nullptr, nullptr}, *d_pred[2] = {nullptr, nullptr};
+        double *d_p = nullptr, *d_z = nullptr, *d_mean = nullptr, *d_m2 = nullptr;
+        double *d_part = nullptr;         // [2][LFNB] partial sums of the kinetic energy at the start / at the proposal
+        double *d_scal = nullptr;         // [CHAIN_SCAL]
+        double *h_rec = nullptr;          // pinned: [CHAIN_REC] the sample's scalars, then [LFNB] partial sums (hmcmt_chain_momentum)
+        double dt = 0, regParam = 0, lo = 0, hi = 0;
+        double D = 0, M = 0, K0 = 0;
+        long long burnin = 0, nsamples = 0, nmoments = 0;
+        int nextStart = 0;                // start_grad of the next step: 0 evaluate, 1 accepted, 2 rejected
+        long long gen = 0;                // stateGen when the chain last left the context
+        std::vector<void*> allocs;
+    } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)
     bool persistFillsShare = false;
@@ -1198,6 +1218,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
     ctx->stats = hmcmt_stats{};
     ctx->stats.nsystems = S;
     ++ctx->ss.evalCount;
+    ++ctx->stateGen;
     ctx->sv.cntActive = (ctx->ss.profMask && ctx->ss.evalCount % ctx->profEvery == 0) ? ctx->d_cnt : nullptr;
     if (ctx->sv.cntActive) ++ctx->profEvals;
     ctx->evalSampled = ctx->sv.cntActive != nullptr;
@@ -1594,6 +1615,8 @@ __global__ __launch_bounds__(64) void k_hog(long long ticks, int* started) {
 // ----------------------------------------------------------------------------------------------
 extern "C" {
 
+static void chain_release(hmcmt_ctx* ctx);      // (host_chain.h)
+
 void hmcmt_default_options(hmcmt_options* o) {
     if (!o) return;
     o->precond = HMCMT_PRECOND_FDM_JACOBI;
@@ -1697,6 +1720,7 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
         }
         hipFree(ctx->sv.stamps);
     }
+    chain_release(ctx);
     for (void* p : ctx->allocs) hipFree(p);
     for (void* p : ctx->blk.allocs) hipFree(p);
     for (void* p : ctx->blk.hostAllocs) hipHostFree(p);
@@ -2251,6 +2275,7 @@ int hmcmt_set_options(hmcmt_ctx* ctx, const hmcmt_options* o) {
     ctx->ss.haveFwd = ctx->ss.haveAdj = false;
     ctx->memo[0].valid = ctx->memo[1].valid = false;
     ctx->lfHaveGrad = false;            // (a gradient kept for start_grad = 1 / 2 was computed under the old options)
+    ++ctx->stateGen;                    // (... and so was a chain's: hmcmt_chain_step evaluates its start gradient again)
     ctx->jvp.valid = false;
     return 0;
 }
@@ -3085,6 +3110,7 @@ int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, c
     std::vector<long long> v_row(rowptr, rowptr + n + 1), v_col(colind, colind + nnz);
     int rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the previous prior)
+    chain_release(ctx);                                     // (a chain belongs to the prior it began with)
     // a repeated call replaces the previous prior: its buffers are released, not kept until hmcmt_destroy
     for (void* old : {(void*)ctx->d_mref, (void*)ctx->d_invM, (void*)ctx->d_wmVal, (void*)ctx->d_wmRow, (void*)ctx->d_wmCol}) {
         if (!old) continue;
@@ -3125,6 +3151,7 @@ int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
     if (kind != HMCMT_MASS_DIAGONAL && kind != HMCMT_MASS_WM) { ctx->err = "hmcmt_set_mass: kind must be HMCMT_MASS_DIAGONAL or HMCMT_MASS_WM"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the mass buffers)
+    chain_release(ctx);                                     // (... and to the mass)
     ctx->mass.kind = HMCMT_MASS_DIAGONAL;
     if (kind == HMCMT_MASS_DIAGONAL) return 0;
     auto& M = ctx->mass;
@@ -3321,6 +3348,8 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
     if (nfevals) *nfevals = evals;
     return 0;
 }
+
+#include "host_chain.h"
 
 }  // extern "C"
 

@@ -835,4 +835,45 @@ HD double jtvp_cell(const View& v, int a, int wrt, const double* gPartG, int ngr
     return wrt ? exp(v.m[a]) * g : g;
 }
 
+// ----------------------------------------------------------------------------------------------
+// the device-resident HMC chain (hmcmt_chain_*, kernels_chain.h): per-parameter bodies
+// ----------------------------------------------------------------------------------------------
+// The reductions keep the leapfrog kernels' layout: CHAIN_NB workgroups of CHAIN_NT threads, parameter a belongs to partial sum
+// chain_part_of(a); the partial sums are added in index order (item_chain_total), so the bits repeat.
+constexpr int CHAIN_NB = 64;       // == LFNB (kernels_path.h)
+constexpr int CHAIN_NT = 256;
+constexpr double CHAIN_ZCLIP = 2.5;   // getMomentumVector clips the normals at +-2.5 (HMCSampler.jl:444-447)
+HD int chain_part_of(int a) { return (a / CHAIN_NT) % CHAIN_NB; }
+// momentum of parameter a for the diagonal mass: p = sqrtM * clip(z) = clip(z) / sqrt(invM); returns its term of p' M^-1 p
+HD double item_chain_momentum(const double* z, const double* invM, double* p, int a) {
+    double zc = z[a];
+    zc = zc > CHAIN_ZCLIP ? CHAIN_ZCLIP : (zc < -CHAIN_ZCLIP ? -CHAIN_ZCLIP : zc);
+    const double pa = zc / sqrt(invM[a]);
+    p[a] = pa;
+    return pa * (invM[a] * pa);
+}
+HD double item_chain_clip(const double* z, int a) {
+    const double zc = z[a];
+    return zc > CHAIN_ZCLIP ? CHAIN_ZCLIP : (zc < -CHAIN_ZCLIP ? -CHAIN_ZCLIP : zc);
+}
+// parameter a's term of p' M^-1 p: x = M^-1 p given (M = Wm, from the mass solve), or the diagonal invM
+HD double item_chain_kinetic(const double* p, const double* x, const double* invM, int a) {
+    return x ? p[a] * x[a] : p[a] * (invM[a] * p[a]);
+}
+// the final stage of a reduction: the partial sums in index order
+HD double item_chain_total(const double* part) {
+    double acc = 0.0;
+    for (int b = 0; b < CHAIN_NB; ++b) acc += part[b];
+    return acc;
+}
+// Welford's update of the running mean and the sum of squared deviations with sample m; count includes this sample.
+// A cell that holds the same value in every sample keeps m2 == 0 exactly (d == 0 from the second sample on; the first
+// sample gives mean = m, m - mean = 0).
+HD void item_chain_welford(const double* m, double* mean, double* m2, double count, int a) {
+    const double x = m[a], d = x - mean[a];
+    const double mu = mean[a] + d / count;
+    mean[a] = mu;
+    m2[a] += d * (x - mu);
+}
+
 }  // namespace hmcmt

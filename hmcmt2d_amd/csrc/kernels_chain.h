@@ -1,0 +1,51 @@
+// kernels_chain.h -- part of libhmcmt_hip.so; included by hmcmt_hip.hip INSIDE its anonymous namespace (one translation unit).
+// The vector kernels of the device-resident HMC chain (hmcmt_chain_*, host_chain.h): momentum draw, kinetic energy, the four
+// Hamiltonian scalars of a sample, streaming posterior moments.  Bodies in hmcmt_items.h (item_chain_*).
+//
+// Plain streaming kernels over nAC doubles in the leapfrog kernels' pattern (kernels_path.h): LFNB workgroups of 256 threads
+// leave LFNB partial sums, one thread adds them in index order -- no floating-point atomics, so the bits repeat.
+#pragma once
+
+static_assert(CHAIN_NB == LFNB && CHAIN_NT == 256, "the chain's reductions use the leapfrog kernels' launch shape");
+
+// scalars of one sample, device side (Chain::d_scal); the first CHAIN_REC go to the pinned record in one copy
+enum { CH_K0 = 0, CH_K1 = 1, CH_D1 = 2, CH_M1 = 3, CH_FLAG = 4, CHAIN_REC = 5, CHAIN_SCAL = 8 };
+
+// p = clip(z, +-2.5) / sqrt(invM) and the partial sums of p' M^-1 p in one pass (diagonal mass)
+__global__ __launch_bounds__(256) void k_chain_momentum(int n, const double* __restrict__ z, const double* __restrict__ invM,
+                                                        double* __restrict__ p, double* __restrict__ part) {
+    __shared__ double sh[32];
+    double acc = 0.0, dummy = 0.0;
+    for (int a = blockIdx.x * 256 + threadIdx.x; a < n; a += 256 * LFNB) acc += item_chain_momentum(z, invM, p, a);
+    block_sum2(acc, dummy, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+// M = Wm: the clipped normals, which chol(Wm).L then multiplies (mass_apply_dev)
+__global__ void k_chain_clip(int n, const double* __restrict__ z, double* __restrict__ out) {
+    const int a = TID1;
+    if (a < n) out[a] = item_chain_clip(z, a);
+}
+// partial sums of p' M^-1 p: x = M^-1 p from the mass solve (M = Wm), or x == nullptr and the diagonal invM
+__global__ __launch_bounds__(256) void k_chain_kinetic(int n, const double* __restrict__ p, const double* __restrict__ x,
+                                                       const double* __restrict__ invM, double* __restrict__ part) {
+    __shared__ double sh[32];
+    double acc = 0.0, dummy = 0.0;
+    for (int a = blockIdx.x * 256 + threadIdx.x; a < n; a += 256 * LFNB) acc += item_chain_kinetic(p, x, invM, a);
+    block_sum2(acc, dummy, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+// the final stage: [K0, K1, D1, M1, non-finite flag] of the sample.  partK0 / partK1: the partial sums at the start / at the
+// proposal; D1 is where the trajectory's last evaluation left it (scal[CH_D1]); mnorm, flag: the leapfrog's own (LfView)
+__global__ void k_chain_final(const double* __restrict__ partK0, const double* __restrict__ partK1, const double* __restrict__ mnorm,
+                              const int* __restrict__ flag, double* __restrict__ scal) {
+    if (TID1 != 0) return;
+    scal[CH_K0] = 0.5 * item_chain_total(partK0);
+    scal[CH_K1] = 0.5 * item_chain_total(partK1);
+    scal[CH_M1] = mnorm[0];
+    scal[CH_FLAG] = (double)flag[0];
+}
+// running mean and sum of squared deviations with the chain's current model; count includes this sample
+__global__ void k_chain_welford(int n, const double* __restrict__ m, double* __restrict__ mean, double* __restrict__ m2, double count) {
+    const int a = TID1;
+    if (a < n) item_chain_welford(m, mean, m2, count, a);
+}

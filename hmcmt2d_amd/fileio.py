@@ -281,3 +281,26 @@ def getPosteriorModel(hmcmodel, mtMesh, invParam, hmcprior, outdir=".", write=Tr
         mtMesh.sigma = sigma
         writeEMModel2D(os.path.join(outdir, "stdModel.model"), mtMesh)
     return meanModel, stdModel
+
+
+def getPosteriorModelFromMoments(moments, mtMesh, invParam, outdir=".", write=True):
+    """getPosteriorModel from streaming moments instead of the sample history: moments = (count, mean, m2) of the samples behind
+    the burn-in (HMCStatus.moments of runHMCSampler(device_chain=True), or sampler.mergeMoments of several chains), m2 the sum
+    of squared deviations from the mean.  The variance is m2 / count (the reference's population variance), floored at eps like
+    the reference's; writes the same meanModel.model / stdModel.model.  Returns (meanModel, stdModel)."""
+    import os
+    count, mean, m2 = moments
+    if int(count) < 1:
+        raise ValueError("getPosteriorModelFromMoments: the moments hold no sample (all of the chain inside the burn-in?)")
+    meanModel = np.asarray(mean, dtype=np.float64).copy()
+    var = np.asarray(m2, dtype=np.float64) / int(count)
+    var[var <= 0] = np.finfo(float).eps
+    stdModel = np.sqrt(var)
+    if write:
+        sigma = invParam.bgModel.copy(); sigma[invParam.activeIdx] += np.exp(meanModel)
+        mtMesh.sigma = sigma
+        writeEMModel2D(os.path.join(outdir, "meanModel.model"), mtMesh)
+        sigma = invParam.bgModel.copy(); sigma[invParam.activeIdx] += stdModel
+        mtMesh.sigma = sigma
+        writeEMModel2D(os.path.join(outdir, "stdModel.model"), mtMesh)
+    return meanModel, stdModel

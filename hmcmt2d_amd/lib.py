@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_jac.h", "kernels_jvp.h", "host_jacobian.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_chain.h", "kernels_jac.h", "kernels_jvp.h", "host_jacobian.h", "host_chain.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -52,6 +52,16 @@ class Stats(C.Structure):
                 ("iters_fwd_sum", C.c_int32), ("iters_adj_sum", C.c_int32),
                 ("err_est_max", C.c_double), ("true_res_max", C.c_double),
                 ("status", C.c_int32), ("nsystems", C.c_int32), ("fallback_solves", C.c_int32), ("smoother_sweeps", C.c_int32)]
+
+
+class ChainRecord(C.Structure):
+    """hmcmt_chain_record (include/hmcmt.h): what hmcmt_chain_step reports of one sample."""
+    _fields_ = [("accepted", C.c_int32), ("nfevals", C.c_int32), ("K0", C.c_double), ("K1", C.c_double),
+                ("D1", C.c_double), ("M1", C.c_double), ("D", C.c_double), ("M", C.c_double), ("hdif", C.c_double),
+                ("nsamples", C.c_int64), ("nmoments", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 def build_library(force=False, verbose=False):
@@ -142,8 +152,16 @@ def load_library():
     for name in ("hmcmt_jvp_block", "hmcmt_jtvp_block", "hmcmt_gn_hessvec_block"):
         getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(Stats)]
         getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(Stats)]
-    for name in JVP_SYMBOLS:
+    for name in JVP_SYMBOLS + CHAIN_SYMBOLS:
         getattr(lib, name).restype = C.c_int
+    lib.hmcmt_chain_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.hmcmt_chain_momentum.argtypes = [vp, c_double_p, C.POINTER(C.c_double)]
+    lib.hmcmt_chain_step.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(ChainRecord), c_double_p, c_double_p]
+    lib.hmcmt_chain_state.argtypes = [vp, c_double_p, c_double_p, c_double_p]
+    lib.hmcmt_chain_moments.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, C.c_int32]
+    lib.hmcmt_chain_end.argtypes = [vp]
+    lib.hmcmt_chain_set_energy.argtypes = [vp, C.c_double, C.c_double]
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
@@ -163,8 +181,11 @@ JVP_SYMBOLS = ["hmcmt_linearize", "hmcmt_linearize_device", "hmcmt_jvp", "hmcmt_
                "hmcmt_jvp_block", "hmcmt_jvp_block_device", "hmcmt_jtvp_block", "hmcmt_jtvp_block_device",
                "hmcmt_gn_hessvec_block", "hmcmt_gn_hessvec_block_device"]
 BLOCK_MAX = 32      # include/hmcmt.h: HMCMT_BLOCK_MAX
+# the device-resident HMC chain
+CHAIN_SYMBOLS = ["hmcmt_chain_begin", "hmcmt_chain_momentum", "hmcmt_chain_step", "hmcmt_chain_state", "hmcmt_chain_moments",
+                 "hmcmt_chain_end", "hmcmt_chain_set_energy"]
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -580,6 +601,60 @@ class HipContext:
         self._check(self.lib.hmcmt_leapfrog_device(self.h, d_m, d_p, dt, L, regParam, lnSigMin, lnSigMax, start_grad,
                                                    d_pred, d_misfit, d_mnorm, C.byref(nf)))
         return nf.value
+
+    # -- the HMC chain on the device (hmcmt_chain_*) ---------------------------------------------
+    def chain_begin(self, m_start, dt, regParam, lnSigMin, lnSigMax, burnin=0):
+        """Starts a chain at m_start (after set_prior / set_mass): one forward evaluation there.  Returns (D0, M0): data misfit and
+        0.5*regParam*(m-mref)'Wm(m-mref) at the start; the predicted data: chain_state()."""
+        D0, M0 = C.c_double(), C.c_double()
+        self._check(self.lib.hmcmt_chain_begin(self.h, _dp(self._model(m_start)), float(dt), float(regParam), float(lnSigMin),
+                                               float(lnSigMax), int(burnin), C.byref(D0), C.byref(M0)))
+        return D0.value, M0.value
+
+    def chain_momentum(self, z):
+        """p = sqrtM * clip(z, +-2.5) on the device from standard normals z[nAC]; returns the kinetic energy 0.5 p'M^-1 p."""
+        K = C.c_double()
+        self._check(self.lib.hmcmt_chain_momentum(self.h, _dp(self._model(z)), C.byref(K)))
+        return K.value
+
+    def chain_step(self, L, u, outputs=True):
+        """One sample: trajectory of L steps, accept test with the uniform u, commit.  Returns (record dict, model, predData): the
+        chain's current model and predicted data after the decision, or None for both with outputs=False (nothing O(nAC) comes back)."""
+        rec = ChainRecord()
+        m = np.empty(self.nAC) if outputs else None
+        pred = np.empty(self.nData, dtype=np.complex128) if outputs else None
+        self._check(self.lib.hmcmt_chain_step(self.h, int(L), float(u), C.byref(rec), _dp(m) if outputs else None,
+                                              _dp(pred) if outputs else None))
+        if outputs and self.args.real_data:
+            pred = pred.real.copy()
+        return rec.as_dict(), m, pred
+
+    def chain_state(self):
+        """(current model, momentum buffer, current predicted data) of the chain."""
+        m, p = np.empty(self.nAC), np.empty(self.nAC)
+        pred = np.empty(self.nData, dtype=np.complex128)
+        self._check(self.lib.hmcmt_chain_state(self.h, _dp(m), _dp(p), _dp(pred)))
+        return m, p, (pred.real.copy() if self.args.real_data else pred)
+
+    def chain_moments(self):
+        """(count, mean[nAC], m2[nAC]) of the samples behind the burn-in: m2 = sum of squared deviations from the mean (Welford)."""
+        n = C.c_int64()
+        mean, m2 = np.empty(self.nAC), np.empty(self.nAC)
+        self._check(self.lib.hmcmt_chain_moments(self.h, C.byref(n), mean.ctypes.data, m2.ctypes.data, 0))
+        return int(n.value), mean, m2
+
+    def chain_moments_device(self, d_mean, d_m2):
+        """The same into device pointers (ints); returns count."""
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_moments(self.h, C.byref(n), d_mean, d_m2, 1))
+        return int(n.value)
+
+    def chain_set_energy(self, D, M):
+        """Replaces the data misfit and prior term the chain holds for its current model (what the next accept test starts from)."""
+        self._check(self.lib.hmcmt_chain_set_energy(self.h, float(D), float(M)))
+
+    def chain_end(self):
+        self._check(self.lib.hmcmt_chain_end(self.h))
 
     # -- instrumentation ----------------------------------------------------------------------
     def profile(self, enable=True, every=1):

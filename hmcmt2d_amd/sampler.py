@@ -345,11 +345,114 @@ def _load_checkpoint(path, hmcmodel, hmcdata, stats, cur, rng, invParam, hmcprio
         return it, tuple(float(x) for x in g["start"])
 
 
+def mergeMoments(list_of_moments):
+    """(count, mean, m2) of the union of sample sets given by their own (count, mean, m2): Chan's pairwise formula, applied from
+    left to right.  m2 is the sum of squared deviations from the mean; empty sets (count 0) are passed over."""
+    n, mean, m2 = 0, None, None
+    for nb, mb, qb in list_of_moments:
+        nb = int(nb)
+        if nb == 0:
+            continue
+        mb, qb = np.asarray(mb, dtype=np.float64), np.asarray(qb, dtype=np.float64)
+        if n == 0:
+            n, mean, m2 = nb, mb.copy(), qb.copy()
+            continue
+        tot = n + nb
+        delta = mb - mean
+        mean = mean + delta * (nb / tot)
+        m2 = m2 + qb + delta * delta * (n * nb / tot)
+        n = tot
+    if n == 0:
+        raise ValueError("mergeMoments: no samples")
+    return n, mean, m2
+
+
+def gelmanRubin(list_of_moments):
+    """Per-cell potential scale reduction R-hat (Gelman & Rubin 1992) of m >= 2 chains of equal length n >= 2 from their
+    (count, mean, m2): W = mean_j s_j^2 with s_j^2 = m2_j / (n - 1), B = n / (m - 1) * sum_j (mean_j - grand mean)^2,
+    R-hat = sqrt(((n - 1) / n * W + B / n) / W).  A cell that never moved in any chain (W == 0) gives nan."""
+    counts = [int(c) for c, _, _ in list_of_moments]
+    m = len(counts)
+    if m < 2 or len(set(counts)) != 1 or counts[0] < 2:
+        raise ValueError("gelmanRubin: at least two chains of the same count >= 2")
+    n = counts[0]
+    means = np.stack([np.asarray(mu, dtype=np.float64) for _, mu, _ in list_of_moments])
+    W = np.stack([np.asarray(q, dtype=np.float64) for _, _, q in list_of_moments]).sum(axis=0) / (n - 1) / m
+    B = n / (m - 1) * ((means - means.mean(axis=0)) ** 2).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt(((n - 1) / n * W + B / n) / W)
+
+
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples):
+    """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
+    moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
+    Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals."""
+    from .lib import HMCMT_MASS_WM
+    nparam, ndata = len(invParam.strModel), len(invParam.obsData)
+    diagonal = hmcprior.massType == "diagonal"
+    fileModel = np.asarray(invParam.strModel, dtype=np.float64).copy()    # the file's start model stays the chain's state (:88)
+    z = rng.standard_normal(nparam)                         # getMomentumVector's draw (:90)
+    rho0 = 1.0 / np.exp(invParam.strModel[0])
+    if rhoref is None:
+        rhoref = np.round(rho0 * 0.5 + (rho0 * 1.5 - rho0 * 0.5) * rng.random())
+    if verbose:
+        print(f"Homogeneous starting model with a resistivity of {rhoref} Ωm is used.")
+    strModel = np.log(np.ones(nparam) / rhoref)
+    invParam.strModel = strModel.copy()
+    invParam.refModel = strModel.copy()
+    ctx.set_prior(invParam.refModel, invParam.Wm, setMassMatrix(nparam, 1.0)[0] if diagonal else np.ones(nparam))
+    if not diagonal:
+        ctx.set_mass(HMCMT_MASS_WM)
+    lo, hi = np.log(hmcprior.sigBounds[0]), np.log(hmcprior.sigBounds[1])
+    # the reference takes its first Hamiltonian at the homogeneous model (:100-112) and its first trajectory from the file's
+    startD, startM = ctx.chain_begin(strModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
+    predStart = ctx.chain_state()[2]
+    if not np.array_equal(fileModel, strModel):
+        ctx.chain_begin(fileModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
+        ctx.chain_set_energy(startD, startM)
+    startK = ctx.chain_momentum(z)
+    nsamples = hmcprior.totalsamples
+    nkeep = nsamples if keep_samples else 0
+    hmcmodel = np.zeros((nparam, nkeep))
+    hmcdata = np.zeros((ndata, nkeep + 1), dtype=np.complex128)
+    hmcdata[:, 0] = predStart
+    stats: HMCStatus = initHMCStatus(nsamples)
+    stats.hmstats[:, 0] = [startD, startM, startK, startD + startM + startK]
+    for it in range(1, nsamples + 1):
+        L = int(rng.integers(hmcprior.timestep[0], hmcprior.timestep[1] + 1))
+        u = rng.random()
+        rec, model, pred = ctx.chain_step(L, u, outputs=keep_samples)
+        hmcprior.nfevals += rec["nfevals"]
+        if rec["accepted"]:
+            stats.nAccept += 1
+            stats.acceptstats[it - 1] = True
+        else:
+            stats.nReject += 1
+        if verbose:
+            print(f"iterNo={it:6d} dtMisfit={rec['D1']:8.3e} mNorm={rec['M1']:8.3e} KEnergy={rec['K1']:8.3e} "
+                  f"HEnergy={rec['D1'] + rec['K1'] + rec['M1']:8.3e} {'accepted' if rec['accepted'] else 'rejected'} "
+                  f"p={min(1.0, float(np.exp(min(rec['hdif'], 0.0)))):.3f}")
+        startK = ctx.chain_momentum(rng.standard_normal(nparam))
+        stats.hmstats[:, it] = [rec["D"], rec["M"], startK, rec["D"] + rec["M"] + startK]
+        if keep_samples:
+            hmcmodel[:, it - 1] = model
+            hmcdata[:, it] = pred if rec["accepted"] else hmcdata[:, it - 1]      # (:164-168: a rejection repeats the column)
+    stats.moments = ctx.chain_moments()
+    return hmcmodel, stats, hmcdata
+
+
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
-                  checkpoint=None, checkpoint_every=0):
+                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
+
+    `device_chain=True`: the loop runs through the library's chain API (hmcmt_chain_*) -- the chain's state never leaves the GPU,
+    the random numbers are drawn here in the same order, so a seed gives the same chain as the host loop to solver tolerance.
+    hmcstats.moments = (count, mean, m2) then holds the streaming posterior moments of the samples behind hmcprior.burninsamples
+    (fileio.getPosteriorModelFromMoments).  `keep_samples=False` (with device_chain): no sample comes back -- hmcmodel has zero
+    columns and hmcdata its first column only; the moments are the result.  Checkpointing is not available with device_chain
+    (ValueError): the warm-start history of the solves is part of a device chain's state.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -361,8 +464,14 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     deterministic direct-solve context, tests/test_host.py).  A checkpoint of a different run -- other sizes, dt,
     timestep, regParam, sigBounds, data, weights or reference model -- is refused."""
     _check_solver(hmcprior)
+    if device_chain and checkpoint:
+        raise ValueError("runHMCSampler: checkpoint is not available with device_chain=True (use the host loop or device_leapfrog=True)")
+    if not keep_samples and not device_chain:
+        raise ValueError("runHMCSampler: keep_samples=False needs device_chain=True (only the device chain streams the posterior moments)")
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
+    if device_chain:
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -467,7 +576,14 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     (hmcmt_allgather_samples, include/hmcmt.h -- what a non-Python host would call) instead of torch's; the process
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
-    `path.chain<k>` per chain).
+    `path.chain<k>` per chain; device_chain=True, keep_samples=False).
+    Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
+    count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
+    gelmanRubin).  A chain's block in the gather is, in doubles,
+        nparam * ncols + 4 * (nsamples + 1) + nsamples + 2 * ndata * (ncols + 1) + 2   [+ 1 + 2 * nparam with moments],
+    ncols = nsamples, or 0 with keep_samples=False: then 2 * nparam + 5 * nsamples + 2 * ndata + 7 instead of
+    nparam * nsamples + ...  Without either keyword the layout is what it was.  With fewer chains than ranks, the ranks that run none
+    take ncols and the moments flag from those that do (one all-reduce of two integers in front of the gather, only in that case).
     Returns (hmcmodel[list], hmcstats[list], hmcdata[list]) indexed by chain.
     """
     import copy
@@ -534,10 +650,26 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
         for c in mine:
             one_chain(c)
 
-    nparam, nsamples = next(iter(results.values()))[0].shape if results else (len(invParam.strModel), hmcprior.totalsamples)
+    # the block layout: from this rank's chains; a rank without one takes it from the keywords, then from the other ranks (below)
+    if results:
+        model0, stats0 = next(iter(results.values()))[:2]
+        nparam, ncols = model0.shape
+        nsamples = len(stats0.acceptstats)
+        with_moments = getattr(stats0, "moments", None) is not None
+    else:
+        nparam, nsamples = len(invParam.strModel), hmcprior.totalsamples
+        ncols = nsamples if sampler_kw.get("keep_samples", True) else 0
+        with_moments = bool(sampler_kw.get("device_chain")) and run_chain is None
+    if have_pg and world > 1 and 0 < nchains < world:
+        # ranks without a chain: what the keywords cannot tell (a `run_chain` that returns no columns or sets moments) comes from
+        # the ranks that ran one -- two integers, and only in this case, which every rank sees alike
+        lay = torch.tensor([ncols if results else -1, int(with_moments) if results else -1], dtype=torch.int64,
+                           device=torch.device("cuda", dev_id) if use_cuda else torch.device("cpu"))
+        dist.all_reduce(lay, op=dist.ReduceOp.MAX)
+        ncols, with_moments = int(lay[0]), bool(lay[1])
     ndata = len(invParam.obsData)
     per = (nchains + world - 1) // world                   # chain slots per rank (padded)
-    blk = nparam * nsamples + 4 * (nsamples + 1) + nsamples + 2 * ndata * (nsamples + 1) + 2
+    blk = nparam * ncols + 4 * (nsamples + 1) + nsamples + 2 * ndata * (ncols + 1) + 2 + ((1 + 2 * nparam) if with_moments else 0)
 
     def pack(slot):
         c = rank + slot * world
@@ -549,7 +681,10 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
             buf[o:o + stats.hmstats.size] = stats.hmstats.reshape(-1); o += stats.hmstats.size
             buf[o:o + nsamples] = stats.acceptstats.astype(float); o += nsamples
             buf[o:o + 2 * data.size] = data.reshape(-1).view(np.float64); o += 2 * data.size
-            buf[o] = secs; buf[o + 1] = 1.0
+            buf[o] = secs; buf[o + 1] = 1.0; o += 2
+            if with_moments:
+                count, mean, m2 = stats.moments
+                buf[o] = count; buf[o + 1:o + 1 + nparam] = mean; buf[o + 1 + nparam:o + 1 + 2 * nparam] = m2
         return buf
 
     local = np.concatenate([pack(s) for s in range(per)]) if per else np.zeros(0)
@@ -578,14 +713,16 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                 continue
             buf = allbuf[r, s]
             o = 0
-            model = buf[o:o + nparam * nsamples].reshape(nparam, nsamples).copy(); o += nparam * nsamples
+            model = buf[o:o + nparam * ncols].reshape(nparam, ncols).copy(); o += nparam * ncols
             hm = buf[o:o + 4 * (nsamples + 1)].reshape(4, nsamples + 1).copy(); o += 4 * (nsamples + 1)
             acc = buf[o:o + nsamples] > 0.5; o += nsamples
-            data = buf[o:o + 2 * ndata * (nsamples + 1)].copy().view(np.complex128).reshape(ndata, nsamples + 1)
-            o += 2 * ndata * (nsamples + 1)
-            secs[c] = float(buf[o])
+            data = buf[o:o + 2 * ndata * (ncols + 1)].copy().view(np.complex128).reshape(ndata, ncols + 1)
+            o += 2 * ndata * (ncols + 1)
+            secs[c] = float(buf[o]); o += 2
             hmcmodel[c], hmcdata[c] = model, data
             hmcstats[c] = HMCStatus(int(acc.sum()), int((~acc).sum()), acc, hm)
+            if with_moments:
+                hmcstats[c].moments = (int(round(buf[o])), buf[o + 1:o + 1 + nparam].copy(), buf[o + 1 + nparam:o + 1 + 2 * nparam].copy())
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

@@ -84,6 +84,8 @@ class HMCStatus:
     nReject: int
     acceptstats: np.ndarray       # bool[nsamples]
     hmstats: np.ndarray           # (4, nsamples+1): dataMisfit, mnorm, kinetic, hamiltonian
+    moments: object = None        # (count, mean[nparam], m2[nparam]) of the samples behind the burn-in, when the chain ran
+                                  # on the device (runHMCSampler(device_chain=True)); not a field of the reference's struct
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

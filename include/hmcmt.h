@@ -201,6 +201,67 @@ int hmcmt_leapfrog_device(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, i
                           double lnSigMin, double lnSigMax, int32_t start_grad, double* d_pred, double* d_misfit,
                           double* d_mnorm, int32_t* nfevals);
 
+/* The HMC chain on the device: one sample of runHMCSampler's loop (HMCSampler.jl:132-186) per hmcmt_chain_step, with the chain's
+ * state -- current and proposal model, momentum, their predicted data -- and streaming posterior moments (Welford: what
+ * getPosteriorModel, HMCSampler.jl:605-642, computes from the sample history) kept in device memory.  Random numbers stay with the
+ * caller: standard normals for every momentum, one uniform per sample.  Per sample the host sends nAC normals and receives one record.
+ *   hmcmt_chain_begin     after hmcmt_set_prior (and hmcmt_set_mass if M = Wm is wanted; HMCMT_EINVAL without a prior).  Uploads
+ *                         m_start[nAC], runs one forward evaluation there (D0 = data misfit, the predicted data), computes
+ *                         M0 = 0.5*regParam*(m-mref)'Wm(m-mref), zeroes moments and counters.  The chain's buffers are its own,
+ *                         allocated here: HMCMT_ENOMEM leaves the context usable, without a chain.  A chain that is running is replaced
+ *                         (its buffers are kept and zeroed: a second begin allocates nothing).
+ *                         dt, regParam, lnSigMin, lnSigMax as in hmcmt_leapfrog; the first `burnin` samples stay out of the moments
+ *                         (getPosteriorModel's burnin+1:nsamples).  D0, M0 may be NULL
+ *   hmcmt_chain_momentum  getMomentumVector + getKineticEnergy (HMCSampler.jl:407-447): p = sqrtM * clip(z, +-2.5) for the mass that
+ *                         is set -- z ./ sqrt(invM), or L z for HMCMT_MASS_WM -- and K = 0.5 p'M^-1 p (K may be NULL).  z: host [nAC]
+ *   hmcmt_chain_step      copies the current model into the proposal buffer, runs the trajectory of L steps there (start gradient: evaluated
+ *                         on the first step, else the one the previous decision left on the device), forms [K0, K1, D1, M1], waits once,
+ *                         decides on the host -- accept iff hdif > 0 || u < exp(hdif), hdif = (D + M + K0) - (D1 + K1 + M1) -- and
+ *                         enqueues the commit without waiting for it: current <-> proposal on acceptance, then the moments' update with the
+ *                         chain's current model (also after a rejection: the sample repeats).  m_out [nAC] / pred_out complex[nData]
+ *                         (host, each may be NULL): the chain's current model / predicted data AFTER the decision; with both NULL
+ *                         nothing of O(nAC) or O(nData) leaves the device.  Needs a momentum set since the last step
+ *   hmcmt_chain_state     current model [nAC], momentum buffer [nAC] (after a step: the proposal's momentum), current predicted data
+ *                         complex[nData] -> host; each may be NULL
+ *   hmcmt_chain_moments   count = samples in the moments, mean[nAC], m2[nAC] = sum of squared deviations from the mean (each may be
+ *                         NULL); on_device = 0: host buffers, = 1: device pointers; complete on return.  The reference's standard
+ *                         deviation is sqrt(max(m2/count, eps))
+ *   hmcmt_chain_set_energy   replaces the D and M the chain holds for its current model -- what the next accept test adds to K0.  For a
+ *                         host that restores a chain whose terms it has kept, and for the reference's own start: runHMCSampler computes the
+ *                         first Hamiltonian at its homogeneous start model but runs the first trajectory from the file's model
+ *                         (HMCSampler.jl:88 against :100-112), and a chain that is to take the reference's decisions does the same
+ *   hmcmt_chain_end       releases the chain's buffers (hmcmt_destroy does it too)
+ * record.nfevals: the gradient evaluations the step performed -- L + 1 when it evaluated its start gradient, L when it reused one
+ *   (hmcmt_leapfrog_device's count, less the reused gradient).
+ * State rules.  A chain call evaluates: it ends a linearisation point (hmcmt_linearize).  Any other evaluating call, hmcmt_leapfrog* or
+ *   hmcmt_set_options on the context between two steps is allowed: the context counts its evaluations, the chain compares the count with
+ *   the one it left, and the next step then evaluates its start gradient again instead of trusting the one on the device (nfevals = L + 1).
+ *   hmcmt_set_prior / hmcmt_set_mass END the chain: later chain calls return HMCMT_EINVAL until a new hmcmt_chain_begin.  Between
+ *   hmcmt_grad_device_async and hmcmt_wait every chain call returns HMCMT_EINVAL.
+ * A step whose trajectory fails (HMCMT_ENOCONV, HMCMT_EBREAKDOWN, a non-finite model) returns that code; the chain stays exactly where
+ *   it was -- current model, predicted data, D, M, counters, moments --, the momentum counts as consumed, the next step evaluates its
+ *   start gradient.  Whether that is a rejection is the caller's decision.
+ * HMCMT_EINVAL also: no chain, no momentum since the last step, L < 1, a NULL or non-finite argument.
+ * A chain is bitwise repeatable: the same history of the context and the same inputs give the same bits in every record and moment. */
+typedef struct hmcmt_chain_record {
+    int32_t accepted;      /* 1 / 0 */
+    int32_t nfevals;       /* gradient evaluations of this step */
+    double  K0, K1;        /* kinetic energy at the start / at the proposal */
+    double  D1, M1;        /* data misfit and 0.5*lambda*(m-mref)'Wm(m-mref) at the proposal */
+    double  D, M;          /* the chain's current state AFTER the decision */
+    double  hdif;          /* H(start) - H(proposal), what the accept test saw */
+    int64_t nsamples;      /* samples committed so far */
+    int64_t nmoments;      /* ... those behind the burn-in: in the moments */
+} hmcmt_chain_record;
+int hmcmt_chain_begin(hmcmt_ctx* ctx, const double* m_start, double dt, double regParam, double lnSigMin, double lnSigMax,
+                      int64_t burnin, double* D0, double* M0);
+int hmcmt_chain_momentum(hmcmt_ctx* ctx, const double* z, double* K);
+int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* rec, double* m_out, double* pred_out);
+int hmcmt_chain_set_energy(hmcmt_ctx* ctx, double D, double M);
+int hmcmt_chain_state(hmcmt_ctx* ctx, double* m_cur, double* p_cur, double* pred_cur);
+int hmcmt_chain_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device);
+int hmcmt_chain_end(hmcmt_ctx* ctx);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -53,6 +53,22 @@ struct HmcmtStats
     nsystems::Int32
     fallback_solves::Int32
     smoother_sweeps::Int32
+end
+
+# hmcmt_chain_record of include/hmcmt.h: what hmcmt_chain_step reports of one sample (tests/test_chain_host.py compares the fields
+# with the ctypes mirror)
+struct HmcmtChainRecord
+    accepted::Int32
+    nfevals::Int32
+    K0::Float64
+    K1::Float64
+    D1::Float64
+    M1::Float64
+    D::Float64
+    M::Float64
+    hdif::Float64
+    nsamples::Int64
+    nmoments::Int64
 end
 
 mutable struct HipContext
@@ -413,6 +429,130 @@ function proposeLeapfrogDevice!(ctx::HipContext, d_m::Ptr, d_p::Ptr, dt::Real, L
                Int32(startGrad), d_pred, d_misfit, d_mnorm, nf)
     checkerr(ctx.ptr, rc)
     return Int(nf[])
+end
+
+"""
+    chainBegin!(ctx, mStart, dt, regParam, lnSigMin, lnSigMax; burnin=0) -> (D0, M0)
+    chainMomentum!(ctx, z) -> K;  chainStep!(ctx, L, u; mOut=nothing, predOut=nothing) -> HmcmtChainRecord
+    chainState(ctx) -> (m, p, pred);  chainMoments(ctx) -> (count, mean, m2);  chainEnd!(ctx)
+
+The HMC chain on the device (hmcmt_chain_*, include/hmcmt.h): runHMCSampler's loop (HMCSampler.jl:132-186) with model, momentum,
+predicted data and the streaming posterior moments in GPU memory.  Call `setPrior!` first.  The random numbers are the caller's:
+`z` standard normals (clipped at +-2.5 by the library, getMomentumVector), `u` one uniform per sample.  `run_chain!` is the loop.
+"""
+function chainBegin!(ctx::HipContext, mStart::Vector{Float64}, dt::Real, regParam::Real, lnSigMin::Real, lnSigMax::Real;
+                     burnin::Integer=0)
+    D0 = Ref{Float64}(0.0); M0 = Ref{Float64}(0.0)
+    rc = ccall((:hmcmt_chain_begin, libhmcmt), Cint,
+               (Ptr{Cvoid}, Ptr{Float64}, Float64, Float64, Float64, Float64, Int64, Ref{Float64}, Ref{Float64}),
+               ctx.ptr, mStart, Float64(dt), Float64(regParam), Float64(lnSigMin), Float64(lnSigMax), Int64(burnin), D0, M0)
+    checkerr(ctx.ptr, rc)
+    return D0[], M0[]
+end
+
+function chainMomentum!(ctx::HipContext, z::Vector{Float64})
+    K = Ref{Float64}(0.0)
+    rc = ccall((:hmcmt_chain_momentum, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}), ctx.ptr, z, K)
+    checkerr(ctx.ptr, rc)
+    return K[]
+end
+
+# (the record travels as Ref{HmcmtChainRecord}: an isbits struct with the C layout)
+function chainStep!(ctx::HipContext, L::Integer, u::Real; mOut::Union{Nothing,Vector{Float64}}=nothing,
+                    predOut::Union{Nothing,Vector{ComplexF64}}=nothing)
+    rec = Ref(HmcmtChainRecord(0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0))
+    pm = mOut === nothing ? Ptr{Float64}(C_NULL) : pointer(mOut)
+    pp = predOut === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(predOut)
+    rc = GC.@preserve mOut predOut @ccall libhmcmt.hmcmt_chain_step(ctx.ptr::Ptr{Cvoid}, Int32(L)::Int32, Float64(u)::Float64,
+                                                                   rec::Ref{HmcmtChainRecord}, pm::Ptr{Float64}, pp::Ptr{ComplexF64})::Cint
+    checkerr(ctx.ptr, rc)
+    return rec[]
+end
+
+function chainState(ctx::HipContext)
+    m = Vector{Float64}(undef, ctx.nAC); p = Vector{Float64}(undef, ctx.nAC)
+    pred = Vector{ComplexF64}(undef, ctx.nData)
+    rc = ccall((:hmcmt_chain_state, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{ComplexF64}), ctx.ptr, m, p, pred)
+    checkerr(ctx.ptr, rc)
+    return m, p, (ctx.realData ? real.(pred) : pred)
+end
+
+function chainMoments(ctx::HipContext)
+    count = Ref{Int64}(0)
+    mean = Vector{Float64}(undef, ctx.nAC); m2 = Vector{Float64}(undef, ctx.nAC)
+    rc = ccall((:hmcmt_chain_moments, libhmcmt), Cint, (Ptr{Cvoid}, Ref{Int64}, Ptr{Float64}, Ptr{Float64}, Int32),
+               ctx.ptr, count, mean, m2, Int32(0))
+    checkerr(ctx.ptr, rc)
+    return Int(count[]), mean, m2
+end
+
+# replaces the D and M the chain holds for its current model (hmcmt_chain_set_energy): a restored chain, or the reference's start
+chainSetEnergy!(ctx::HipContext, D::Real, M::Real) =
+    checkerr(ctx.ptr, ccall((:hmcmt_chain_set_energy, libhmcmt), Cint, (Ptr{Cvoid}, Float64, Float64), ctx.ptr, Float64(D), Float64(M)))
+
+chainEnd!(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_chain_end, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
+
+"""
+    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing) -> (hmcmodel, hmcstats, hmcdata, moments)
+
+runHMCSampler (HMCSampler.jl:72-196) through the chain API, step for step what hmcmt2d_amd/sampler.py's device chain does, the
+reference's start included: the chain's state starts at the file's model invParam.strModel (:88), while start and reference model
+become the homogeneous one of `rhoref` Ωm (drawn as :100-104 draws it when `nothing`) and the first Hamiltonian is taken there
+(:112-115) -- one `chainBegin!` at the homogeneous model for D, M and the first data column, one at the file's model, and
+`chainSetEnergy!` with the first one's D and M.  The mass is hmcParam's (`setPrior!`).  Draw order: the first momentum's normals,
+rhoref; per sample L, u, the next momentum's normals.  `keepSamples=false`: no sample leaves the GPU (hmcmodel has no column,
+hmcdata its first only); `moments` = (count, mean, m2) of the samples behind hmcprior.burninsamples either way.
+"""
+function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior, hmcParam::HMCParameter; keepSamples::Bool=true,
+                    rhoref::Union{Nothing,Real}=nothing)
+    n, nd = ctx.nAC, ctx.nData
+    nsamples = hmcprior.totalsamples
+    fileModel = Vector{Float64}(invParam.strModel)
+    z = randn(n)
+    rho0 = 1.0 / exp(invParam.strModel[1])
+    if rhoref === nothing
+        rhoref = round(rho0 * 0.5 + (rho0 * 1.5 - rho0 * 0.5) * rand())
+    end
+    println("Homogeneous starting model with a resistivity of $(rhoref) Ωm is used.")
+    strModel = log.(ones(n) ./ rhoref)
+    invParam.strModel = copy(strModel)
+    invParam.refModel = copy(strModel)
+    setPrior!(ctx, invParam, hmcParam)
+    lo, hi = log(hmcprior.sigBounds[1]), log(hmcprior.sigBounds[2])
+    D, M = chainBegin!(ctx, strModel, hmcprior.dt, hmcprior.regParam, lo, hi; burnin=hmcprior.burninsamples)
+    predStart = chainState(ctx)[3]
+    if fileModel != strModel
+        chainBegin!(ctx, fileModel, hmcprior.dt, hmcprior.regParam, lo, hi; burnin=hmcprior.burninsamples)
+        chainSetEnergy!(ctx, D, M)
+    end
+    K = chainMomentum!(ctx, z)
+    ncols = keepSamples ? nsamples : 0
+    hmcmodel = zeros(Float64, n, ncols)
+    hmcdata = zeros(ComplexF64, nd, ncols + 1)
+    hmcdata[:, 1] = predStart
+    hmcstats = initHMCStatus(nsamples)
+    hmcstats.hmstats[:, 1] = [D, M, K, D + M + K]
+    mOut = keepSamples ? Vector{Float64}(undef, n) : nothing
+    predOut = keepSamples ? Vector{ComplexF64}(undef, nd) : nothing
+    for it = 1:nsamples
+        L = rand(hmcprior.timestep[1]:hmcprior.timestep[2])
+        u = rand()
+        rec = chainStep!(ctx, L, u; mOut=mOut, predOut=predOut)
+        hmcprior.nfevals += rec.nfevals
+        if rec.accepted == 1
+            hmcstats.nAccept += 1
+            hmcstats.acceptstats[it] = true
+        else
+            hmcstats.nReject += 1
+        end
+        K = chainMomentum!(ctx, randn(n))
+        hmcstats.hmstats[:, it + 1] = [rec.D, rec.M, K, rec.D + rec.M + K]
+        if keepSamples
+            hmcmodel[:, it] = mOut
+            hmcdata[:, it + 1] = rec.accepted == 1 ? predOut : hmcdata[:, it]      # (:164-168: a rejection repeats the column)
+        end
+    end
+    return hmcmodel, hmcstats, hmcdata, chainMoments(ctx)
 end
 
 hipWait(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_wait, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))

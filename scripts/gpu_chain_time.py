@@ -1,0 +1,99 @@
+"""Wall time per sample of the three samplers, interleaved in one session on one MI355X -> profiles/chain_time.log.
+
+  (a) runHMCSampler(device_leapfrog=True): the host loop around hmcmt_leapfrog (the parent's product sampler)
+  (b) runHMCSampler(device_chain=True)
+  (c) runHMCSampler(device_chain=True, keep_samples=False)
+at cfg3 and cfg5 with bench.py's settings near the true model (L = 8, dt = 0.03), and beside them the floor: L times the per-step
+time bench.py reports for its near_true_state chain in the same session.  Every figure: median of REPS runs of NS samples, with the
+minimum and maximum (the spread).  The requirement read off the log: (b) and (c) are not slower than (a) by more than that spread.
+
+    python scripts/gpu_chain_time.py [cfg3 cfg5] [--reps 5] [--samples 6]
+
+One JSON line per configuration is appended to the log; every line carries its own repetitions, samples per run and command line.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from hmcmt2d_amd import sampler, synthetic as S                      # noqa: E402
+from hmcmt2d_amd.lib import HipContext                               # noqa: E402
+from hmcmt2d_amd.structs import HMCPrior                             # noqa: E402
+from tests.helpers import make_problem                               # noqa: E402
+
+L, DT, RHOREF = 8, 0.03, 100.0
+MODES = {"a_host_loop_device_leapfrog": dict(device_leapfrog=True),
+         "b_device_chain": dict(device_chain=True),
+         "c_device_chain_no_samples": dict(device_chain=True, keep_samples=False)}
+
+
+def one_run(name, kw, ns, seed):
+    mesh, data, inv, _ = make_problem(name)
+    inv.strModel = np.log(S.true_model_sigma(mesh, block=True)[inv.activeIdx])
+    prior = HMCPrior(totalsamples=ns, burninsamples=0, dt=DT, timestep=[L, L], sigBounds=[1e-4, 1.0], regParam=1.0)
+    ctx = HipContext(mesh, data, inv, device_id=0)
+    try:
+        warm = HMCPrior(totalsamples=1, burninsamples=0, dt=DT, timestep=[L, L], sigBounds=[1e-4, 1.0], regParam=1.0)
+        import copy
+        sampler.runHMCSampler(mesh, data, copy.deepcopy(inv), warm, np.random.default_rng(seed), rhoref=RHOREF, ctx=ctx, **kw)   # untimed
+        t0 = time.perf_counter()
+        _, st, _ = sampler.runHMCSampler(mesh, data, inv, prior, np.random.default_rng(seed), rhoref=RHOREF, ctx=ctx, **kw)
+        dt = time.perf_counter() - t0
+    finally:
+        ctx.close()
+    return 1e3 * dt / ns, st.nAccept
+
+
+def bench_floor(name):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "96", "--warmup", "16", "--config", name, "--no-cpu-baseline"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900).stdout
+    res = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
+    near = res.get("extras", res).get("near_true_state", {})
+    sps = near.get("steps_per_s", res.get("value"))
+    return 1e3 * L / sps, sps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("configs", nargs="*", default=["cfg3", "cfg5"])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--samples", type=int, default=6)
+    ap.add_argument("--no-floor", action="store_true")
+    a = ap.parse_args()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    log = open(os.path.join(ROOT, "profiles", "chain_time.log"), "a")
+    for name in a.configs:
+        ms = {k: [] for k in MODES}
+        acc = {}
+        for rep in range(a.reps):                       # interleaved: a, b, c, a, b, c, ...
+            for k, kw in MODES.items():
+                t, nacc = one_run(name, kw, a.samples, 100 + rep)
+                ms[k].append(t); acc[k] = nacc
+                print(f"{name} rep {rep} {k}: {t:.3f} ms per sample", file=sys.stderr, flush=True)
+        line = {"config": name, "argv": sys.argv[1:], "L": L, "dt": DT, "samples_per_run": a.samples, "reps": a.reps, "ms_per_sample": {}}
+        for k, v in ms.items():
+            line["ms_per_sample"][k] = {"median": statistics.median(v), "min": min(v), "max": max(v), "accepted_last_run": acc[k]}
+        spread = max(max(v) - min(v) for v in ms.values())
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        line["spread_ms"] = spread
+        line["b_minus_a_ms"] = med["b_device_chain"] - med["a_host_loop_device_leapfrog"]
+        line["c_minus_a_ms"] = med["c_device_chain_no_samples"] - med["a_host_loop_device_leapfrog"]
+        line["b_and_c_within_spread_of_a"] = bool(line["b_minus_a_ms"] <= spread and line["c_minus_a_ms"] <= spread)
+        if not a.no_floor:
+            floor, sps = bench_floor(name)
+            line["floor_ms_per_sample_L_times_bench_step"] = floor
+            line["bench_near_true_steps_per_s"] = sps
+            line["c_above_floor"] = med["c_device_chain_no_samples"] / floor - 1.0
+        print(json.dumps(line)); log.write(json.dumps(line) + "\n"); log.flush()
+
+
+if __name__ == "__main__":
+    main()
