@@ -13,6 +13,7 @@ from hmcmt2d_amd import fileio, sampler
 from hmcmt2d_amd import lib as L
 from hmcmt2d_amd.structs import HMCParameter, HMCPrior
 from tests.conftest import ROOT
+from tests import chain_ref as R
 from tests.emul import emul_chain_py as E
 from tests.helpers import OracleContext, make_problem
 
@@ -91,6 +92,67 @@ def test_welford_cells_that_never_move_have_zero_m2():
 
 def _moments(x):
     return x.shape[1], x.mean(axis=1), ((x - x.mean(axis=1, keepdims=True)) ** 2).sum(axis=1)
+
+
+# ---- tests/chain_ref.py, the reference of tests/test_gpu_chain_kernels.py, against the item functions -------------------------------
+@pytest.mark.parametrize("n", SIZES)
+def test_reference_against_the_item_functions(n):
+    """chain_ref.momentum / kinetic / moments (longdouble sums) against the emulation, at the bounds of the tests above (the momentum
+    per element); a non-unit mass, the clip's edge cases planted."""
+    rng = np.random.default_rng(1000 + n)
+    z = 2.0 * rng.standard_normal(n)
+    z[0] = 7.5
+    if n > 3:
+        z[-1], z[1], z[2] = -3.25, 2.5, -0.0
+    invM = rng.uniform(0.25, 4.0, n)
+    p, K = E.momentum(z, invM)
+    pr, Kr = R.momentum(z, invM)
+    assert np.all(np.abs(p - pr) <= 4 * EPS * np.abs(pr))
+    assert abs(K - Kr) <= 1e-14 * Kr
+    x = invM * p
+    assert abs(E.kinetic(p, invM=invM) - R.kinetic(p, invM=invM)) <= 1e-14 * Kr
+    assert abs(E.kinetic(p, x=x) - R.kinetic(p, x=x)) <= 1e-14 * Kr
+    assert abs(R.kinetic(p, invM=invM) - Kr) <= 4 * EPS * Kr        # (the rounded p: its own 1/2 ulp, twice)
+    ens = _ensemble(rng, nparam=n)
+    count, mean, m2 = E.welford(ens, burnin=3)
+    cr, mr, m2r = R.moments(ens[:, 3:])
+    bmean, bvar = R.moments_bounds(mr, m2r, cr)
+    assert count == cr == 9
+    assert np.abs(mean - mr).max() <= bmean
+    assert np.all(np.abs(m2 / count - m2r / cr) <= bvar)
+
+
+def test_reference_moments_of_a_chain_that_stands_still():
+    ens = np.repeat(np.array([[-4.605170185988091], [0.1], [-13.815510557964274]]), 5, axis=1)
+    count, mean, m2 = R.moments(ens)
+    assert count == 5 and np.array_equal(mean, ens[:, 0]) and np.all(m2 == 0.0)
+
+
+def test_reference_prior_term_and_misfit_against_numpy():
+    mesh, data, inv, m = make_problem("tiny")
+    n = len(m)
+    rng = np.random.default_rng(8)
+    mref = m + 0.1 * np.sin(np.arange(n) / 7.0)
+    d = m - mref
+    val, S = R.mnorm(m, mref, inv.Wm, 1.7)
+    plain = 0.5 * float(d @ (inv.Wm @ d)) * 1.7
+    nnz = int(np.diff(inv.Wm.tocsr().indptr).max())
+    assert S >= abs(val) > 0 and abs(plain - val) <= (nnz + 8) * EPS * S
+    assert R.mnorm(m, mref, inv.Wm.toarray(), 1.7) == (val, S)
+    assert R.mnorm(mref, mref, inv.Wm, 1.7) == (0.0, 0.0)
+    pred = inv.obsData * (1.0 + 0.05 * rng.standard_normal(len(inv.obsData))) + 1e-3j * rng.standard_normal(len(inv.obsData))
+    ref = R.misfit(pred, inv)
+    assert ref > 0 and abs(sampler.compDataMisfit(pred, inv) - ref) <= (np.log2(len(pred)) + 8) * EPS * ref   # (numpy sums pairwise)
+
+
+def test_reference_decision_rule():
+    # downhill: accepted whatever u; uphill: u against exp(hdif); the order of operations is hmcmt_chain_step's
+    assert R.decision(10.0, 1.0, 2.0, 9.0, 2.0, 1.0, 0.999) == (1.0, True)
+    h, acc = R.decision(10.0, 1.0, 2.0, 10.5, 2.0, 1.0, 0.5)
+    assert h == -0.5 and acc and not R.decision(10.0, 1.0, 2.0, 10.5, 2.0, 1.0, 0.7)[1]
+    assert R.decision(0.1, 0.2, 0.3, 0.0, 0.0, 0.0, 0.5)[0] == (0.1 + 0.2 + 0.3) - 0.0
+    assert R.decision(3.0 + 1e12, 1.0, 2.0, 5.0, 2.0, 1.0, 1.0)[1]                  # a forced acceptance
+    assert R.decision(3.0 - 1e12, 1.0, 2.0, 5.0, 2.0, 1.0, 0.0) == ((3.0 - 1e12 + 1.0 + 2.0) - (5.0 + 2.0 + 1.0), False)   # and rejection
 
 
 def test_merge_moments_of_unequal_splits():

@@ -149,7 +149,15 @@ def test_moments_on_tiny(tiny12):
         assert np.abs(mean - post.mean(axis=1)).max() <= 1e-14 * np.abs(post.mean(axis=1)).max()
         var = post.var(axis=1)
         moved = var > 0
-        assert np.all(np.abs(m2 / count - var)[moved] <= 1e-12 * var[moved]) and np.all(m2[~moved] == 0)
+        # Welford subtracts the running mean from a sample, which cancels |mean| / std digits: 16 eps max(|mean| / std, 1) relative,
+        # the bound at any number of parameters (tests/chain_ref.py: moments_bounds).  A few cells of this chain barely move (|mean| / std
+        # up to 1e4, measured): for them the flat 1e-12 this test has always held is the tighter of the two, and it stays
+        err = (np.abs(m2 / count - var)[moved] / var[moved])
+        cond = np.maximum(np.abs(post.mean(axis=1)[moved]) / np.sqrt(var[moved]), 1.0)
+        bound = np.minimum(16 * np.finfo(float).eps * cond, 1e-12)
+        print(f"\n[moments on tiny] |mean| / std {np.median(cond):.1f} (median) to {cond.max():.1f}; relative variance error {err.max():.2e}, "
+              f"at most {(err / bound).max():.2f} of its bound ({int((bound == 1e-12).sum())} of {moved.sum()} cells at the flat 1e-12)")
+        assert np.all(err <= bound) and np.all(m2[~moved] == 0)
     assert np.array_equal(moments[1], st.moments[1]) and np.array_equal(moments[2], st.moments[2])
 
 
