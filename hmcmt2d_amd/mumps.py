@@ -92,8 +92,29 @@ def factorMUMPS(A, sym=0, ooc=0) -> MUMPSfactorization:
     return MUMPSfactorization(int(p), A.shape[0], cm)
 
 
+def _solution_array(factor, x, shape, dt):
+    """MUMPSfuncs.jl:89-95: the caller's x is the output (an empty one is replaced, a wrong-sized one refused).
+    Returns (x to return, the column-major buffer the library writes)."""
+    if x is not None and np.size(x) == 0:
+        x = None
+    if x is None:
+        xf = np.zeros((shape[0], int(np.prod(shape[1:], dtype=int))), dtype=dt, order="F")
+        return None, xf
+    if not isinstance(x, np.ndarray):
+        raise TypeError("applyMUMPS: x must be a numpy array (it is written in place)")
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"applyMUMPS: wrong size of x, size(A)={factor.n}, size(rhs)={tuple(shape)}, "
+                         f"size(x)={tuple(x.shape)} provided")
+    if factor.cmplx and not np.iscomplexobj(x):
+        raise TypeError("real x for a complex factorization")
+    if x.dtype == dt and x.flags.writeable and (x.flags.f_contiguous if x.ndim > 1 else x.flags.c_contiguous):
+        return x, x.reshape(shape[0], -1, order="F")             # a view: the library writes into the caller's memory
+    return x, np.zeros((shape[0], int(np.prod(shape[1:], dtype=int))), dtype=dt, order="F")
+
+
 def applyMUMPS(factor: MUMPSfactorization, rhs, x=None, tr=0):
-    """MUMPSfuncs.jl:75-146: dense (n or n x nrhs, column-major like Julia) or sparse CSC right-hand sides."""
+    """MUMPSfuncs.jl:75-146: dense (n or n x nrhs, column-major like Julia) or sparse CSC right-hand sides.  A given
+    `x` of the right-hand side's shape is filled and returned, as the reference's applyMUMPS does."""
     so = _so()
     dt = np.complex128 if factor.cmplx else np.float64
     if sp.issparse(rhs):
@@ -102,25 +123,33 @@ def applyMUMPS(factor: MUMPSfactorization, rhs, x=None, tr=0):
         if R.shape[0] != factor.n:
             raise ValueError("applyMUMPS: wrong size of rhs")
         nrhs = R.shape[1]
-        xf = np.zeros((factor.n, nrhs), dtype=dt, order="F")
+        x, xf = _solution_array(factor, x, (factor.n, nrhs), dt)
         nz = np.ascontiguousarray(R.data)
         rowval = np.ascontiguousarray(R.indices, dtype=np.int64) + 1
         colptr = np.ascontiguousarray(R.indptr, dtype=np.int64) + 1
         f = so.solve_mumps_cmplx_sparse_rhs_ if factor.cmplx else so.solve_mumps_sparse_rhs_
         f(_ref(factor.ptr), _ref(R.nnz), _ref(nrhs), _ptr(nz, _dp), _ptr(rowval, _i64p), _ptr(colptr, _i64p),
           _ptr(xf, _dp), _ref(tr))
-        return xf
+        if x is None:
+            return xf
+        if not np.shares_memory(x, xf):
+            x[...] = xf
+        return x
     rhs = np.asarray(rhs)
     if rhs.shape[0] != factor.n:
         raise ValueError(f"applyMUMPS: wrong size of rhs, size(A)={factor.n}, size(rhs)={rhs.shape}")
     if np.iscomplexobj(rhs) and not factor.cmplx:
         raise TypeError("complex right-hand side for a real factorization")
     nrhs = 1 if rhs.ndim == 1 else rhs.shape[1]
+    x, xf = _solution_array(factor, x, rhs.shape, dt)
     rf = np.asfortranarray(rhs.reshape(factor.n, nrhs), dtype=dt)
-    xf = np.zeros((factor.n, nrhs), dtype=dt, order="F")
     f = so.solve_mumps_cmplx_ if factor.cmplx else so.solve_mumps_
     f(_ref(factor.ptr), _ref(nrhs), _ptr(rf, _dp), _ptr(xf, _dp), _ref(tr))
-    return xf[:, 0].copy() if rhs.ndim == 1 else xf
+    if x is None:
+        return xf[:, 0].copy() if rhs.ndim == 1 else xf
+    if not np.shares_memory(x, xf):
+        x[...] = xf.reshape(x.shape, order="F")
+    return x
 
 
 def destroyMUMPS(factor: MUMPSfactorization):
