@@ -249,6 +249,21 @@ struct hmcmt_ctx {
         int nextStart = 0;                // start_grad of the next step: 0 evaluate, 1 accepted, 2 rejected
         long long gen = 0;                // stateGen when the chain last left the context
         std::vector<void*> allocs;
+        // the optional accumulators of the commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*): buffers of their own, released
+        // with the chain and by every hmcmt_chain_begin
+        struct Hist {
+            bool on = false;
+            long long ntarget = 0, count = 0;
+            int nbins = 0;
+            double lo = 0, hi = 0, scale = 0, w = 0;
+            long long* d_target = nullptr;            // [ntarget] active-cell indices
+            unsigned int* d_counts = nullptr;         // [nbins][ntarget], bin-major (hmcmt_items.h)
+        } hist;
+        struct DataMoments {
+            bool on = false;
+            long long count = 0;
+            double *d_mean = nullptr, *d_m2 = nullptr;   // [2 nData] each
+        } dmom;
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)

@@ -875,5 +875,40 @@ HD void item_chain_welford(const double* m, double* mean, double* m2, double cou
     mean[a] = mu;
     m2[a] += d * (x - mu);
 }
+// Histograms of the committed models (hmcmt_chain_hist_*).  The counters lie BIN-MAJOR, counts[b * ntarget + r]: row r belongs to
+// thread r alone, and the rows of a wavefront -- neighbouring cells, whose values fall into the same or adjacent bins -- touch a few
+// cache lines per commit where a target-major array would touch one line per lane; the quantile scan reads the same way.
+constexpr int CHAIN_HIST_MAXBINS = 4096;
+// the bin of value m: one subtraction, then one product (nothing to contract), clamped into the edge bins
+HD int item_chain_hist_bin(double m, double lo, double scale, int nbins) {
+    const double t = (m - lo) * scale;
+    return t < 0 ? 0 : (t >= (double)nbins ? nbins - 1 : (int)t);
+}
+HD void item_chain_hist(const double* m, const long long* target, unsigned int* counts, long long ntarget, int nbins, double lo,
+                        double scale, long long r) {
+    const int b = item_chain_hist_bin(m[target[r]], lo, scale, nbins);
+    counts[(long long)b * ntarget + r] += 1u;
+}
+// the x-th sample of row r, x = q * N in [0, N], linear inside its bin: the first bin with count_b > 0 and cum_b >= x.  *bin: that bin
+HD double item_chain_quantile(const unsigned int* counts, long long ntarget, int nbins, double lo, double w, double x, long long r,
+                              int* bin) {
+    unsigned long long cum = 0;
+    int b = 0, last = -1;
+    unsigned long long cumLast = 0;
+    for (; b < nbins; ++b) {
+        const unsigned int c = counts[(long long)b * ntarget + r];
+        if (c == 0) continue;
+        if ((double)(cum + c) >= x) break;
+        last = b; cumLast = cum;
+        cum += c;
+    }
+    if (b == nbins) {                 // (x beyond the row's sum: cannot happen for q <= 1 -- the last occupied bin then)
+        if (last < 0) { *bin = -1; return lo; }
+        b = last; cum = cumLast;
+    }
+    *bin = b;
+    const double c = (double)counts[(long long)b * ntarget + r];
+    return lo + w * ((double)b + (x - (double)cum) / c);
+}
 
 }  // namespace hmcmt

@@ -3,10 +3,27 @@
 //
 // One sample = hmcmt_chain_momentum + hmcmt_chain_step.  What crosses PCIe per sample: nAC normals up, LFNB partial sums and
 // CHAIN_REC scalars down; with outputs, nAC + 2 nData doubles more.  Launches per sample beyond leapfrog_core's (diagonal mass):
-// k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford.
+// k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
+// k_chain_hist and a second k_chain_welford (the predicted data) behind them.
+
+// ends the commit's optional accumulators (histogram, data moments) and frees their buffers
+static void chain_acc_release(hmcmt_ctx* ctx) {
+    auto& C = ctx->chain;
+    void* bufs[] = {C.hist.d_target, C.hist.d_counts, C.dmom.d_mean, C.dmom.d_m2};
+    bool any = false;
+    for (void* p : bufs) any = any || p;
+    if (any) {
+        hipSetDevice(ctx->device);
+        if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be counting)
+        for (void* p : bufs) if (p) hipFree(p);
+    }
+    C.hist = hmcmt_ctx::Chain::Hist{};
+    C.dmom = hmcmt_ctx::Chain::DataMoments{};
+}
 
 static void chain_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
+    chain_acc_release(ctx);
     if (!C.allocs.empty() || C.h_rec) {
         hipSetDevice(ctx->device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be running on the buffers)
@@ -74,7 +91,7 @@ int hmcmt_chain_begin(hmcmt_ctx* ctx, const double* m_start, double dt, double r
     auto& C = ctx->chain;
     // a begin on a context that holds a chain keeps that chain's buffers (their sizes belong to the context) and zeroes them
     const bool reuse = C.h_rec != nullptr;
-    if (reuse) C.active = C.haveMomentum = false;
+    if (reuse) { C.active = C.haveMomentum = false; chain_acc_release(ctx); }
     else chain_release(ctx);
     hipStream_t st = ctx->stream;
     auto build = [&]() -> int {
@@ -205,6 +222,16 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
     if (C.nsamples > C.burnin) {
         ++C.nmoments;
         hipLaunchKernelGGL(k_chain_welford, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_m[C.cur], C.d_mean, C.d_m2, (double)C.nmoments);
+        if (C.hist.on) {
+            ++C.hist.count;
+            hipLaunchKernelGGL(k_chain_hist, dim3((unsigned)((C.hist.ntarget + 255) / 256)), dim3(256), 0, st, C.hist.ntarget, C.hist.nbins,
+                               C.hist.lo, C.hist.scale, C.d_m[C.cur], C.hist.d_target, C.hist.d_counts);
+        }
+        if (C.dmom.on && nData > 0) {
+            ++C.dmom.count;
+            hipLaunchKernelGGL(k_chain_welford, dim3((2 * nData + 255) / 256), dim3(256), 0, st, 2 * nData, C.d_pred[C.cur], C.dmom.d_mean,
+                               C.dmom.d_m2, (double)C.dmom.count);
+        }
     }
     C.gen = ctx->stateGen;
     rec->accepted = accepted ? 1 : 0;
@@ -258,6 +285,169 @@ int hmcmt_chain_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2
     if (m2) HIPCHK(hipMemcpyAsync(m2, C.d_m2, bytes, kind, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (count) *count = C.nmoments;
+    return 0;
+}
+
+// ---- the commit's optional accumulators: histograms of the model, moments of the predicted data ------------------------------------
+static int chain_acc_alloc(hmcmt_ctx* ctx, const char* fn, void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        ctx->err = std::string(fn) + ": device allocation failed: " + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? HMCMT_ENOMEM : HMCMT_EHIP;
+    }
+    return 0;
+}
+
+int hmcmt_chain_hist_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* target, int32_t nbins, double lo, double hi) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_hist_begin", true);
+    if (rc) return rc;
+    if (!target || ntarget < 1 || nbins < 1 || nbins > CHAIN_HIST_MAXBINS || !std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo) ||
+        !std::isfinite(hi - lo)) {
+        ctx->err = "hmcmt_chain_hist_begin: need target, ntarget >= 1, 1 <= nbins <= 4096 and finite lo < hi";
+        return HMCMT_EINVAL;
+    }
+    const int n = ctx->v.nAC;
+    for (int64_t i = 0; i < ntarget; ++i)
+        if (target[i] < 0 || target[i] >= n) {
+            ctx->err = "hmcmt_chain_hist_begin: target " + std::to_string(i) + " = " + std::to_string(target[i]) + " is no active cell (0.." +
+                       std::to_string(n - 1) + ")";
+            return HMCMT_EINVAL;
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    auto& C = ctx->chain;
+    auto& H = C.hist;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be counting into the histogram this one replaces)
+    for (void* p : {(void*)H.d_target, (void*)H.d_counts}) if (p) hipFree(p);
+    H = hmcmt_ctx::Chain::Hist{};
+    const size_t nb = (size_t)ntarget * sizeof(long long), cb = (size_t)ntarget * (size_t)nbins * sizeof(unsigned int);
+    auto build = [&]() -> int {
+        int r;
+        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_hist_begin", (void**)&H.d_target, nb))) return r;
+        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_hist_begin", (void**)&H.d_counts, cb))) return r;
+        static_assert(sizeof(long long) == sizeof(int64_t), "the target list is uploaded as it is");
+        HIPCHK(hipMemcpyAsync(H.d_target, target, nb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(H.d_counts, 0, cb, st));
+        HIPCHK(hipStreamSynchronize(st));                    // (the caller's list is free again on return)
+        return 0;
+    };
+    if ((rc = build())) {
+        for (void* p : {(void*)H.d_target, (void*)H.d_counts}) if (p) hipFree(p);
+        H = hmcmt_ctx::Chain::Hist{};
+        return rc;
+    }
+    H.ntarget = ntarget; H.nbins = nbins; H.lo = lo; H.hi = hi;
+    H.scale = (double)nbins / (hi - lo);
+    H.w = (hi - lo) / (double)nbins;
+    H.count = 0;
+    H.on = true;
+    return 0;
+}
+
+int hmcmt_chain_hist(hmcmt_ctx* ctx, int64_t* count, uint32_t* counts, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, "hmcmt_chain_hist", true);
+    if (rc) return rc;
+    auto& H = ctx->chain.hist;
+    if (!H.on) { ctx->err = "hmcmt_chain_hist: no histogram (hmcmt_chain_hist_begin first)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const long long total = H.ntarget * H.nbins;
+    if (counts && on_device) {
+        hipLaunchKernelGGL(k_chain_hist_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, H.ntarget, H.nbins, H.d_counts, counts);
+        HIPCHK(hipGetLastError());
+    } else if (counts) {
+        // bin-major on the device, target-major for the caller: turned here, no second device array
+        std::vector<unsigned int> tmp;
+        try { tmp.resize((size_t)total); } catch (const std::bad_alloc&) { ctx->err = "hmcmt_chain_hist: host allocation failed"; return HMCMT_ENOMEM; }
+        HIPCHK(hipMemcpyAsync(tmp.data(), H.d_counts, sizeof(unsigned int) * (size_t)total, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (long long r0 = 0; r0 < H.ntarget; r0 += 256) {   // (in blocks of rows: the strided side stays in cache)
+            const long long r1 = std::min(r0 + 256, H.ntarget);
+            for (int b = 0; b < H.nbins; ++b) {
+                const unsigned int* src = tmp.data() + (size_t)b * H.ntarget;
+                for (long long r = r0; r < r1; ++r) counts[(size_t)r * H.nbins + b] = src[r];
+            }
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (count) *count = H.count;
+    return 0;
+}
+
+int hmcmt_chain_hist_quantiles(hmcmt_ctx* ctx, int32_t nq, const double* q, double* out, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_hist_quantiles", true);
+    if (rc) return rc;
+    auto& H = ctx->chain.hist;
+    if (!H.on) { ctx->err = "hmcmt_chain_hist_quantiles: no histogram (hmcmt_chain_hist_begin first)"; return HMCMT_EINVAL; }
+    if (!q || !out || nq < 1) { ctx->err = "hmcmt_chain_hist_quantiles: need q, out and nq >= 1"; return HMCMT_EINVAL; }
+    for (int i = 0; i < nq; ++i)
+        if (!(q[i] >= 0.0 && q[i] <= 1.0)) { ctx->err = "hmcmt_chain_hist_quantiles: every q must lie in [0, 1]"; return HMCMT_EINVAL; }
+    if (H.count == 0) { ctx->err = "hmcmt_chain_hist_quantiles: the histogram is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    std::vector<double> x((size_t)nq);
+    for (int i = 0; i < nq; ++i) x[i] = q[i] * (double)H.count;       // (one product: what a host restatement forms)
+    double *d_x = nullptr, *d_out = nullptr;
+    const size_t ob = sizeof(double) * (size_t)nq * (size_t)H.ntarget;
+    auto run = [&]() -> int {
+        int r;
+        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_hist_quantiles", (void**)&d_x, sizeof(double) * nq))) return r;
+        if (!on_device && (r = chain_acc_alloc(ctx, "hmcmt_chain_hist_quantiles", (void**)&d_out, ob))) return r;
+        double* dst = on_device ? out : d_out;
+        HIPCHK(hipMemcpyAsync(d_x, x.data(), sizeof(double) * nq, hipMemcpyHostToDevice, st));
+        for (int q0 = 0; q0 < nq; q0 += 32768) {             // (a grid's y extent)
+            const int nc = std::min(nq - q0, 32768);
+            hipLaunchKernelGGL(k_chain_quantiles, dim3((unsigned)((H.ntarget + 255) / 256), (unsigned)nc), dim3(256), 0, st, H.ntarget, H.nbins,
+                               nc, H.lo, H.w, d_x + q0, H.d_counts, dst + (size_t)q0 * H.ntarget);
+        }
+        HIPCHK(hipGetLastError());
+        if (!on_device) HIPCHK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st);
+    if (d_x) hipFree(d_x);
+    if (d_out) hipFree(d_out);
+    return rc;
+}
+
+int hmcmt_chain_data_moments_begin(hmcmt_ctx* ctx) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_data_moments_begin", true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    auto& M = ctx->chain.dmom;
+    hipStream_t st = ctx->stream;
+    const size_t bytes = sizeof(double) * std::max<size_t>((size_t)2 * ctx->v.nData, 1);
+    M.on = false;
+    if (!M.d_mean && (rc = chain_acc_alloc(ctx, "hmcmt_chain_data_moments_begin", (void**)&M.d_mean, bytes))) return rc;
+    if (!M.d_m2 && (rc = chain_acc_alloc(ctx, "hmcmt_chain_data_moments_begin", (void**)&M.d_m2, bytes))) return rc;
+    HIPCHK(hipMemsetAsync(M.d_mean, 0, bytes, st));          // (behind a commit that may still be running on them)
+    HIPCHK(hipMemsetAsync(M.d_m2, 0, bytes, st));
+    M.count = 0;
+    M.on = true;
+    return 0;
+}
+
+int hmcmt_chain_data_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, "hmcmt_chain_data_moments", true);
+    if (rc) return rc;
+    auto& M = ctx->chain.dmom;
+    if (!M.on) { ctx->err = "hmcmt_chain_data_moments: no data moments (hmcmt_chain_data_moments_begin first)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * 2 * ctx->v.nData;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (mean) HIPCHK(hipMemcpyAsync(mean, M.d_mean, bytes, kind, ctx->stream));
+    if (m2) HIPCHK(hipMemcpyAsync(m2, M.d_m2, bytes, kind, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (count) *count = M.count;
     return 0;
 }
 

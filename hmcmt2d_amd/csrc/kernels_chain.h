@@ -49,3 +49,28 @@ __global__ void k_chain_welford(int n, const double* __restrict__ m, double* __r
     const int a = TID1;
     if (a < n) item_chain_welford(m, mean, m2, count, a);
 }
+// one count per target row for the chain's current model: thread r owns row r (bin-major counters, hmcmt_items.h), no atomics
+__global__ __launch_bounds__(256) void k_chain_hist(long long ntarget, int nbins, double lo, double scale, const double* __restrict__ m,
+                                                    const long long* __restrict__ target, unsigned int* __restrict__ counts) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < ntarget) item_chain_hist(m, target, counts, ntarget, nbins, lo, scale, r);
+}
+// out[iq][r]: one thread per (quantile, target) scans its row; the lanes of a wavefront read neighbouring rows of one bin together
+__global__ __launch_bounds__(256) void k_chain_quantiles(long long ntarget, int nbins, int nq, double lo, double w,
+                                                         const double* __restrict__ x, const unsigned int* __restrict__ counts,
+                                                         double* __restrict__ out) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int iq = blockIdx.y;
+    if (r >= ntarget || iq >= nq) return;
+    int bin;
+    out[(long long)iq * ntarget + r] = item_chain_quantile(counts, ntarget, nbins, lo, w, x[iq], r, &bin);
+}
+// the counters as hmcmt_chain_hist returns them: target-major
+__global__ __launch_bounds__(256) void k_chain_hist_out(long long ntarget, int nbins, const unsigned int* __restrict__ counts,
+                                                        unsigned int* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ntarget * nbins) return;
+    const long long r = i / nbins;
+    const int b = (int)(i - r * nbins);
+    out[i] = counts[(long long)b * ntarget + r];
+}

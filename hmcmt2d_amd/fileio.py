@@ -304,3 +304,62 @@ def getPosteriorModelFromMoments(moments, mtMesh, invParam, outdir=".", write=Tr
         mtMesh.sigma = sigma
         writeEMModel2D(os.path.join(outdir, "stdModel.model"), mtMesh)
     return meanModel, stdModel
+
+
+def writeSitePPD(filename, yCoord, zCoord, hist):
+    """sitePPD.dat in outputPosterior's layout (HMCSampler.jl:719-756) from a histogram over sampler.sitePPDTargets(mesh, inv, yCoord,
+    zCoord): three header blocks of a count line and a %6g value line -- the sites' y, the depths, the nbins + 1 bin edges in
+    log10 Ohm-m (labelled as such; the reference prints "y coordinate" there a second time) -- then per site and per depth one
+    line of nbins %5d counts over ascending resistivity, a blank line behind every site."""
+    from .sampler import histToLog10Rho
+    yCoord, zCoord = np.atleast_1d(np.asarray(yCoord, dtype=float)), np.atleast_1d(np.asarray(zCoord, dtype=float))
+    edges, counts = histToLog10Rho(hist)
+    if counts.shape[0] != len(yCoord) * len(zCoord):
+        raise ValueError(f"writeSitePPD: {counts.shape[0]} histogram rows for {len(yCoord)} sites x {len(zCoord)} depths")
+    with open(filename, "w") as f:
+        for label, vals in (("y coordinate", yCoord), ("z coordinate", zCoord), ("log10 rho edges", edges)):
+            f.write("%s: %5d\n" % (label, len(vals)))
+            f.write("".join("%6g " % v for v in vals) + "\n")
+        for j in range(len(yCoord)):
+            for k in range(len(zCoord)):
+                f.write("".join("%5d " % c for c in counts[j * len(zCoord) + k]) + "\n")
+            f.write("\n")
+
+
+def readSitePPD(filename):
+    """(yCoord, zCoord, edges[nbins + 1], counts[nsite, nz, nbins]) of a file of writeSitePPD, the values as printed (%6g)."""
+    with open(filename) as f:
+        lines = f.read().split("\n")
+    blocks = []
+    for i in range(3):
+        n = int(lines[2 * i].rsplit(":", 1)[1])
+        vals = np.array(lines[2 * i + 1].split(), dtype=float)
+        if len(vals) != n:
+            raise ValueError(f"{filename}: header block {i + 1} announces {n} values and holds {len(vals)}")
+        blocks.append(vals)
+    y, z, edges = blocks
+    rows = [np.array(ln.split(), dtype=np.int64) for ln in lines[6:] if ln.strip()]
+    if len(rows) != len(y) * len(z) or any(len(r) != len(edges) - 1 for r in rows):
+        raise ValueError(f"{filename}: expected {len(y) * len(z)} rows of {len(edges) - 1} counts")
+    return y, z, edges, np.array(rows).reshape(len(y), len(z), len(edges) - 1)
+
+
+def getPosteriorQuantileModels(hist, q, mtMesh, invParam, outdir=".", write=True):
+    """Credible-interval models from an all-cells histogram (hist's targets = 0 .. nparam-1 in order: runHMCSampler's default): for
+    every q the model of the cells' q-quantiles of ln sigma (sampler.histQuantiles), written as p05Model.model, p50Model.model, ...
+    (the percent, rounded to 0.01, dots as 'p').  Returns [nq, nparam]."""
+    import os
+    from .sampler import histQuantiles
+    nparam = len(invParam.activeIdx)
+    targets = np.asarray(hist[3])
+    if targets.shape != (nparam,) or not np.array_equal(targets, np.arange(nparam)):
+        raise ValueError("getPosteriorQuantileModels: needs a histogram of every active cell, in order (hist targets = arange(nparam))")
+    q = np.atleast_1d(np.asarray(q, dtype=float))
+    models = histQuantiles(hist, q)
+    if write:
+        for qi, m in zip(q, models):
+            pct = ("%05.2f" % (100.0 * qi)).rstrip("0").rstrip(".").replace(".", "p")
+            sigma = invParam.bgModel.copy(); sigma[invParam.activeIdx] += np.exp(m)
+            mtMesh.sigma = sigma
+            writeEMModel2D(os.path.join(outdir, "p%sModel.model" % pct.zfill(2)), mtMesh)
+    return models

@@ -152,7 +152,7 @@ def load_library():
     for name in ("hmcmt_jvp_block", "hmcmt_jtvp_block", "hmcmt_gn_hessvec_block"):
         getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(Stats)]
         getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(Stats)]
-    for name in JVP_SYMBOLS + CHAIN_SYMBOLS:
+    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib.hmcmt_chain_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -162,6 +162,11 @@ def load_library():
     lib.hmcmt_chain_moments.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, C.c_int32]
     lib.hmcmt_chain_end.argtypes = [vp]
     lib.hmcmt_chain_set_energy.argtypes = [vp, C.c_double, C.c_double]
+    lib.hmcmt_chain_hist_begin.argtypes = [vp, C.c_int64, c_int64_p, C.c_int32, C.c_double, C.c_double]
+    lib.hmcmt_chain_hist.argtypes = [vp, C.POINTER(C.c_int64), vp, C.c_int32]
+    lib.hmcmt_chain_hist_quantiles.argtypes = [vp, C.c_int32, c_double_p, vp, C.c_int32]
+    lib.hmcmt_chain_data_moments_begin.argtypes = [vp]
+    lib.hmcmt_chain_data_moments.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, C.c_int32]
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
@@ -184,8 +189,12 @@ BLOCK_MAX = 32      # include/hmcmt.h: HMCMT_BLOCK_MAX
 # the device-resident HMC chain
 CHAIN_SYMBOLS = ["hmcmt_chain_begin", "hmcmt_chain_momentum", "hmcmt_chain_step", "hmcmt_chain_state", "hmcmt_chain_moments",
                  "hmcmt_chain_end", "hmcmt_chain_set_energy"]
+# the optional accumulators of the chain's commit: histograms of the model, moments of the predicted data
+CHAIN_HIST_SYMBOLS = ["hmcmt_chain_hist_begin", "hmcmt_chain_hist", "hmcmt_chain_hist_quantiles",
+                      "hmcmt_chain_data_moments_begin", "hmcmt_chain_data_moments"]
+HIST_MAXBINS = 4096   # include/hmcmt.h: nbins of hmcmt_chain_hist_begin
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -655,6 +664,62 @@ class HipContext:
 
     def chain_end(self):
         self._check(self.lib.hmcmt_chain_end(self.h))
+
+    # -- marginal posteriors from the chain's commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*) --
+    def chain_hist_begin(self, targets, nbins, lo, hi):
+        """Starts per-cell histograms of ln sigma over [lo, hi) in nbins bins (values outside are clamped into the edge bins) for the
+        active-cell indices `targets` (0-based, repeats allowed): every later commit behind the burn-in counts.  Replaces a
+        histogram that is running."""
+        t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+        self._check(self.lib.hmcmt_chain_hist_begin(self.h, len(t), t.ctypes.data_as(c_int64_p), int(nbins), float(lo), float(hi)))
+        self._hist_shape = (len(t), int(nbins))
+
+    def chain_hist(self):
+        """(count, counts[ntarget, nbins] uint32): commits in the histogram and its rows."""
+        n = C.c_int64()
+        counts = np.empty(self._hist_shape_or_raise(), dtype=np.uint32)
+        self._check(self.lib.hmcmt_chain_hist(self.h, C.byref(n), counts.ctypes.data, 0))
+        return int(n.value), counts
+
+    def chain_hist_device(self, d_counts):
+        """The same into a device pointer (int) to ntarget * nbins uint32, target-major; returns count."""
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_hist(self.h, C.byref(n), d_counts, 1))
+        return int(n.value)
+
+    def chain_quantiles(self, q, d_out=None):
+        """Quantiles q (each in [0, 1]) of every target's histogram, linear inside the bin, computed on the device: [nq, ntarget] in
+        ln sigma -- or into the device pointer d_out (int), returning None."""
+        q = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
+        if d_out is not None:
+            self._check(self.lib.hmcmt_chain_hist_quantiles(self.h, len(q), _dp(q), d_out, 1))
+            return None
+        out = np.empty((len(q), self._hist_shape_or_raise()[0]))
+        self._check(self.lib.hmcmt_chain_hist_quantiles(self.h, len(q), _dp(q), out.ctypes.data, 0))
+        return out
+
+    def _hist_shape_or_raise(self):
+        # (the library knows whether a histogram is running: a zero-length call gets its error, and its message)
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_hist(self.h, C.byref(n), None, 0))
+        return self._hist_shape
+
+    def chain_data_moments_begin(self):
+        """Starts the Welford moments of the chain's predicted data: every later commit behind the burn-in counts."""
+        self._check(self.lib.hmcmt_chain_data_moments_begin(self.h))
+
+    def chain_data_moments(self, raw=False):
+        """(count, mean[nData], m2[nData]) of the predicted data at the counted commits: complex mean, and m2 = re + i im with the sums
+        of squared deviations of the real and the imaginary parts (real arrays for a real data type, whose imaginary slots hold
+        exact zeros).  raw=True: the library's own 2 nData doubles each, re and im interleaved."""
+        n = C.c_int64()
+        mean, m2 = np.empty(2 * self.nData), np.empty(2 * self.nData)
+        self._check(self.lib.hmcmt_chain_data_moments(self.h, C.byref(n), mean.ctypes.data, m2.ctypes.data, 0))
+        if raw:
+            return int(n.value), mean, m2
+        if self.args.real_data:
+            return int(n.value), mean[0::2].copy(), m2[0::2].copy()
+        return int(n.value), mean.view(np.complex128), m2.view(np.complex128)
 
     # -- instrumentation ----------------------------------------------------------------------
     def profile(self, enable=True, every=1):

@@ -383,7 +383,81 @@ def gelmanRubin(list_of_moments):
         return np.sqrt(((n - 1) / n * W + B / n) / W)
 
 
-def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples):
+def sitePPDTargets(mtMesh, invParam, yCoord, zCoord):
+    """Active-cell indices for the histograms under sites: for every (y, z) of yCoord x zCoord the cell whose centre is nearest,
+    separately in y and in z, among the rows below the air -- the reference's model2DInterp ("interpolate to the nearest node, not
+    by linear interpolation", HMCSampler.jl:684-711); a tie goes to the lower index.  int64[len(yCoord) * len(zCoord)], depth
+    fastest.  A point whose cell is not active (fixed by the inversion setup) raises ValueError."""
+    yCoord, zCoord = np.atleast_1d(np.asarray(yCoord, dtype=np.float64)), np.atleast_1d(np.asarray(zCoord, dtype=np.float64))
+    yNode = np.concatenate([[0.0], np.cumsum(mtMesh.yLen)]) - mtMesh.origin[0]
+    zNode = np.concatenate([[0.0], np.cumsum(mtMesh.zLen)]) - mtMesh.origin[1]
+    yCen = yNode[:-1] + np.diff(yNode) / 2
+    zCen = zNode[:-1] + np.diff(zNode) / 2
+    ny, nair = len(mtMesh.yLen), len(mtMesh.airLayer)
+    cell2act = np.full(ny * len(mtMesh.zLen), -1, dtype=np.int64)
+    cell2act[np.asarray(invParam.activeIdx)] = np.arange(len(invParam.activeIdx))
+    out = np.empty(len(yCoord) * len(zCoord), dtype=np.int64)
+    for j, y in enumerate(yCoord):
+        iy = int(np.argmin(np.abs(yCen - y)))                      # (argmin: the first of equal distances)
+        for k, z in enumerate(zCoord):
+            iz = nair + int(np.argmin(np.abs(zCen[nair:] - z)))
+            a = cell2act[iz * ny + iy]
+            if a < 0:
+                raise ValueError(f"sitePPDTargets: the cell nearest to (y, z) = ({y:g}, {z:g}) -- column {iy}, row {iz} -- is not active")
+            out[j * len(zCoord) + k] = a
+    return out
+
+
+def mergeHistograms(list_of_hists):
+    """The histogram of the union of sample sets -- several chains -- from their own (count, counts, (nbins, lo, hi), targets): counts
+    and counters add (int64).  Histograms of different bins or targets are refused (ValueError)."""
+    if not list_of_hists:
+        raise ValueError("mergeHistograms: no histogram")
+    count0, counts0, bins0, targets0 = list_of_hists[0]
+    bins0, targets0 = tuple(bins0), np.asarray(targets0)
+    total, acc = int(count0), np.asarray(counts0).astype(np.int64)
+    for count, counts, bins, targets in list_of_hists[1:]:
+        if tuple(bins) != bins0 or not np.array_equal(np.asarray(targets), targets0) or np.shape(counts) != acc.shape:
+            raise ValueError("mergeHistograms: the histograms differ in (nbins, lo, hi) or in their targets")
+        total += int(count)
+        acc = acc + np.asarray(counts).astype(np.int64)
+    return total, acc, bins0, targets0.copy()
+
+
+def histQuantiles(hist, q):
+    """Quantiles q (each in [0, 1]) of every row of hist = (count, counts, (nbins, lo, hi), targets), [nq, ntarget] in ln sigma, by
+    the library's definition (hmcmt_chain_hist_quantiles): with x = q * count, the first bin b with counts_b > 0 whose inclusive
+    cumulative count reaches x, and lo + w * (b + (x - cum_{b-1}) / counts_b), w = (hi - lo) / nbins."""
+    count, counts, (nbins, lo, hi), _ = hist
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if int(count) < 1:
+        raise ValueError("histQuantiles: the histogram holds no sample")
+    if not np.all((q >= 0) & (q <= 1)):
+        raise ValueError("histQuantiles: every q must lie in [0, 1]")
+    counts = np.asarray(counts).astype(np.int64)
+    cum = np.cumsum(counts, axis=1)
+    w = (float(hi) - float(lo)) / int(nbins)
+    rows = np.arange(counts.shape[0])
+    out = np.empty((len(q), counts.shape[0]))
+    for i, qi in enumerate(q):
+        x = float(qi) * float(int(count))
+        b = np.argmax((counts > 0) & (cum.astype(np.float64) >= x), axis=1)
+        cb = counts[rows, b]
+        out[i] = float(lo) + w * (b.astype(np.float64) + (x - (cum[rows, b] - cb).astype(np.float64)) / cb.astype(np.float64))
+    return out
+
+
+def histToLog10Rho(hist):
+    """hist in ln sigma -> (edges[nbins + 1] in log10 of resistivity (Ohm-m), ascending, counts[ntarget, nbins] to match):
+    log10 rho = -m / ln 10 turns the axis round, so the bins come out in reverse order."""
+    _, counts, (nbins, lo, hi), _ = hist
+    w = (float(hi) - float(lo)) / int(nbins)
+    edges_m = float(lo) + w * np.arange(int(nbins) + 1)
+    edges_m[-1] = float(hi)
+    return (-edges_m / np.log(10.0))[::-1].copy(), np.asarray(counts)[:, ::-1].copy()
+
+
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals."""
@@ -410,6 +484,15 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     if not np.array_equal(fileModel, strModel):
         ctx.chain_begin(fileModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
         ctx.chain_set_energy(startD, startM)
+    if hist is not None:                                    # (behind the second begin: a begin ends the accumulators)
+        unknown = set(hist) - {"targets", "nbins", "lo", "hi"}
+        if unknown:
+            raise ValueError(f"runHMCSampler: hist has no key {sorted(unknown)} (targets, nbins, lo, hi)")
+        targets = np.arange(nparam, dtype=np.int64) if hist.get("targets") is None else np.asarray(hist["targets"], dtype=np.int64)
+        bins = (int(hist.get("nbins", 300)), float(hist.get("lo", lo)), float(hist.get("hi", hi)))     # (300: the reference's npBins)
+        ctx.chain_hist_begin(targets, *bins)
+    if data_moments:
+        ctx.chain_data_moments_begin()
     startK = ctx.chain_momentum(z)
     nsamples = hmcprior.totalsamples
     nkeep = nsamples if keep_samples else 0
@@ -438,12 +521,16 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
             hmcmodel[:, it - 1] = model
             hmcdata[:, it] = pred if rec["accepted"] else hmcdata[:, it - 1]      # (:164-168: a rejection repeats the column)
     stats.moments = ctx.chain_moments()
+    if hist is not None:
+        stats.hist = ctx.chain_hist() + (bins, targets.copy())
+    if data_moments:
+        stats.dataMoments = ctx.chain_data_moments()
     return hmcmodel, stats, hmcdata
 
 
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
-                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True):
+                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -453,6 +540,13 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     (fileio.getPosteriorModelFromMoments).  `keep_samples=False` (with device_chain): no sample comes back -- hmcmodel has zero
     columns and hmcdata its first column only; the moments are the result.  Checkpointing is not available with device_chain
     (ValueError): the warm-start history of the solves is part of a device chain's state.
+    `hist={...}` (with device_chain): per-cell histograms of ln sigma, streamed in the chain's commit like the moments, so that
+    marginal distributions and credible intervals need no sample history.  Keys, all optional: `targets` (active-cell indices, default
+    every cell; `sitePPDTargets` gives the cells under sites), `nbins` (300, the reference's npBins), `lo`, `hi` (ln of
+    hmcprior.sigBounds).  hmcstats.hist = (count, counts[ntarget, nbins], (nbins, lo, hi), targets): see histQuantiles,
+    histToLog10Rho, mergeHistograms, fileio.writeSitePPD, fileio.getPosteriorQuantileModels.  `data_moments=True` (with
+    device_chain): hmcstats.dataMoments = (count, mean[ndata], m2[ndata]) of the predicted data at the same samples -- the
+    posterior-predictive spread.  Neither changes the order of the random draws.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -468,10 +562,12 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
         raise ValueError("runHMCSampler: checkpoint is not available with device_chain=True (use the host loop or device_leapfrog=True)")
     if not keep_samples and not device_chain:
         raise ValueError("runHMCSampler: keep_samples=False needs device_chain=True (only the device chain streams the posterior moments)")
+    if (hist is not None or data_moments) and not device_chain:
+        raise ValueError("runHMCSampler: hist and data_moments need device_chain=True (they are streamed in the device chain's commit)")
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)

@@ -86,6 +86,8 @@ class HMCStatus:
     hmstats: np.ndarray           # (4, nsamples+1): dataMisfit, mnorm, kinetic, hamiltonian
     moments: object = None        # (count, mean[nparam], m2[nparam]) of the samples behind the burn-in, when the chain ran
                                   # on the device (runHMCSampler(device_chain=True)); not a field of the reference's struct
+    hist: object = None           # (count, counts[ntarget, nbins], (nbins, lo, hi), targets): runHMCSampler(device_chain=True, hist=...)
+    dataMoments: object = None    # (count, mean[ndata], m2[ndata]) of the predicted data: runHMCSampler(..., data_moments=True)
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

@@ -262,6 +262,37 @@ int hmcmt_chain_state(hmcmt_ctx* ctx, double* m_cur, double* p_cur, double* pred
 int hmcmt_chain_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device);
 int hmcmt_chain_end(hmcmt_ctx* ctx);
 
+/* Marginal posteriors from the chain's commit (optional; nothing above changes when they are off).  Two accumulators, each fed by the
+ * commits that fall behind the burn-in -- the samples of the moments, a rejection's repeat included -- from its own begin call on, each
+ * with its own count.  A begin call may come at any point between two steps; only later commits count.
+ *   hmcmt_chain_hist_begin   per-cell histograms of m = ln sigma (the reference's sitePPD, HMCSampler.jl:646-680): target[ntarget] are
+ *                         0-based indices into the active cells, repeats allowed (two depths in one cell are two rows), ntarget >= 1,
+ *                         1 <= nbins <= 4096, lo < hi finite.  Every counted commit adds 1 to ONE bin of every target's row:
+ *                             t = (m[target] - lo) * scale,  scale = (double)nbins / (hi - lo)   (one subtraction, then one product)
+ *                             b = t < 0 ? 0 : t >= nbins ? nbins - 1 : (int)t
+ *                         -- values outside [lo, hi) are CLAMPED into the edge bins, so every row sums to the count.  Allocates
+ *                         ntarget * nbins zeroed uint32 counters and the target list on the device; on HMCMT_ENOMEM the chain goes on
+ *                         without a histogram.  A second call replaces the first histogram
+ *   hmcmt_chain_hist      count = commits in the histogram, counts[ntarget][nbins] (target-major; each may be NULL); on_device = 0: host
+ *                         buffer, = 1: device pointer; complete on return
+ *   hmcmt_chain_hist_quantiles   out[nq][ntarget] (host, or a device pointer with on_device = 1) for q[nq] (host), every q in [0, 1],
+ *                         computed on the device from the counters.  With N = count and x = q * (double)N: b is the first bin with
+ *                         count_b > 0 whose inclusive cumulative count cum_b >= x, and the value is
+ *                             lo + w * (b + (x - cum_{b-1}) / count_b),  w = (hi - lo) / nbins
+ *                         -- linear inside the bin.  HMCMT_EINVAL when N = 0
+ *   hmcmt_chain_data_moments_begin / hmcmt_chain_data_moments   Welford mean and m2 of the chain's current predicted data: 2 nData
+ *                         doubles each, re and im interleaved as in pred_out (real data types: exact zeros in the imaginary slots);
+ *                         count, mean, m2 may each be NULL, on_device as above
+ * hmcmt_chain_begin (also over a running chain), hmcmt_chain_end, hmcmt_set_prior and hmcmt_set_mass end both accumulators and release
+ * their buffers; a step that fails touches neither.  HMCMT_EINVAL: NULL context, target, q or out, a size, range or index outside
+ * the above, no chain, no accumulator begun, a call between hmcmt_grad_device_async and hmcmt_wait.  Counts, quantiles and data
+ * moments repeat bitwise (every counter row and every datum has one owner thread: no atomics). */
+extern int hmcmt_chain_hist_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* target, int32_t nbins, double lo, double hi);
+extern int hmcmt_chain_hist(hmcmt_ctx* ctx, int64_t* count, uint32_t* counts, int32_t on_device);
+extern int hmcmt_chain_hist_quantiles(hmcmt_ctx* ctx, int32_t nq, const double* q, double* out, int32_t on_device);
+extern int hmcmt_chain_data_moments_begin(hmcmt_ctx* ctx);
+extern int hmcmt_chain_data_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -491,6 +491,60 @@ chainSetEnergy!(ctx::HipContext, D::Real, M::Real) =
     checkerr(ctx.ptr, ccall((:hmcmt_chain_set_energy, libhmcmt), Cint, (Ptr{Cvoid}, Float64, Float64), ctx.ptr, Float64(D), Float64(M)))
 
 chainEnd!(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_chain_end, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
+
+"""
+    chainHistBegin!(ctx, targets, nbins, lo, hi);  chainHist(ctx, ntarget, nbins) -> (count, counts[nbins, ntarget])
+    chainQuantiles(ctx, q, ntarget) -> values[ntarget, nq];  chainDataMomentsBegin!(ctx);  chainDataMoments(ctx) -> (count, mean, m2)
+    chain_hist!(ctx, invParam, hmcprior; targets=all cells, nbins=300) -> (targets, nbins, lo, hi)
+
+Marginal posteriors from the chain's commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*, include/hmcmt.h): per-cell histograms of
+ln sigma over [lo, hi) -- values outside are clamped into the edge bins -- and the Welford moments of the predicted data, both fed by
+the commits behind the burn-in from their begin call on.  `targets` are 1-based active-cell indices here (0-based in C).  The arrays
+come back in C's row-major layout, i.e. with Julia's first index running over the bins / the targets.  Call the begin functions behind
+`chainBegin!` (which ends both accumulators) and in front of the first `chainMomentum!`; `chain_hist!` does so with the reference's
+sitePPD settings: 300 bins over the ln of hmcprior.sigBounds.
+"""
+function chainHistBegin!(ctx::HipContext, targets::Vector{<:Integer}, nbins::Integer, lo::Real, hi::Real)
+    t0 = Int64.(targets) .- 1
+    rc = @ccall libhmcmt.hmcmt_chain_hist_begin(ctx.ptr::Ptr{Cvoid}, Int64(length(t0))::Int64, t0::Ptr{Int64}, Int32(nbins)::Int32,
+                                                Float64(lo)::Float64, Float64(hi)::Float64)::Cint
+    checkerr(ctx.ptr, rc)
+end
+
+function chainHist(ctx::HipContext, ntarget::Integer, nbins::Integer)
+    count = Ref{Int64}(0)
+    counts = Matrix{UInt32}(undef, nbins, ntarget)
+    rc = @ccall libhmcmt.hmcmt_chain_hist(ctx.ptr::Ptr{Cvoid}, count::Ref{Int64}, counts::Ptr{UInt32}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return Int(count[]), counts
+end
+
+function chainQuantiles(ctx::HipContext, q::Vector{Float64}, ntarget::Integer)
+    out = Matrix{Float64}(undef, ntarget, length(q))
+    rc = @ccall libhmcmt.hmcmt_chain_hist_quantiles(ctx.ptr::Ptr{Cvoid}, Int32(length(q))::Int32, q::Ptr{Float64}, out::Ptr{Float64},
+                                                    Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return out
+end
+
+chainDataMomentsBegin!(ctx::HipContext) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_data_moments_begin(ctx.ptr::Ptr{Cvoid})::Cint)
+
+function chainDataMoments(ctx::HipContext)
+    count = Ref{Int64}(0)
+    mean = Vector{ComplexF64}(undef, ctx.nData); m2 = Vector{ComplexF64}(undef, ctx.nData)
+    pmean = Ptr{Float64}(pointer(mean)); pm2 = Ptr{Float64}(pointer(m2))
+    rc = GC.@preserve mean m2 @ccall libhmcmt.hmcmt_chain_data_moments(ctx.ptr::Ptr{Cvoid}, count::Ref{Int64}, pmean::Ptr{Float64},
+                                                                       pm2::Ptr{Float64}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return Int(count[]), (ctx.realData ? real.(mean) : mean), (ctx.realData ? real.(m2) : m2)
+end
+
+function chain_hist!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior; targets::Vector{<:Integer}=collect(1:ctx.nAC),
+                     nbins::Integer=300)
+    lo = log(hmcprior.sigBounds[1]); hi = log(hmcprior.sigBounds[2])
+    chainHistBegin!(ctx, targets, nbins, lo, hi)
+    return targets, nbins, lo, hi
+end
 
 """
     run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing) -> (hmcmodel, hmcstats, hmcdata, moments)

@@ -1,8 +1,11 @@
-"""Wall time per sample of the three samplers, interleaved in one session on one MI355X -> profiles/chain_time.log.
+"""Wall time per sample of the samplers, interleaved in one session on one MI355X -> profiles/chain_time.log.
 
   (a) runHMCSampler(device_leapfrog=True): the host loop around hmcmt_leapfrog (the parent's product sampler)
   (b) runHMCSampler(device_chain=True)
   (c) runHMCSampler(device_chain=True, keep_samples=False)
+  (d) (c) with both accumulators of the commit on: hist={} (every cell, 300 bins) and data_moments=True.  Its figure leaves out the
+      one read-back of the counters at the end of the run (timed again on the live chain and reported as d_readback_ms): with a
+      handful of samples per run it would otherwise be the figure
 at cfg3 and cfg5 with bench.py's settings near the true model (L = 8, dt = 0.03), and beside them the floor: L times the per-step
 time bench.py reports for its near_true_state chain in the same session.  Every figure: median of REPS runs of NS samples, with the
 minimum and maximum (the spread).  The requirement read off the log: (b) and (c) are not slower than (a) by more than that spread.
@@ -32,7 +35,9 @@ from tests.helpers import make_problem                               # noqa: E40
 L, DT, RHOREF = 8, 0.03, 100.0
 MODES = {"a_host_loop_device_leapfrog": dict(device_leapfrog=True),
          "b_device_chain": dict(device_chain=True),
-         "c_device_chain_no_samples": dict(device_chain=True, keep_samples=False)}
+         "c_device_chain_no_samples": dict(device_chain=True, keep_samples=False),
+         "d_device_chain_no_samples_hist_data_moments": dict(device_chain=True, keep_samples=False, hist={}, data_moments=True)}
+D = "d_device_chain_no_samples_hist_data_moments"
 
 
 def one_run(name, kw, ns, seed):
@@ -47,9 +52,14 @@ def one_run(name, kw, ns, seed):
         t0 = time.perf_counter()
         _, st, _ = sampler.runHMCSampler(mesh, data, inv, prior, np.random.default_rng(seed), rhoref=RHOREF, ctx=ctx, **kw)
         dt = time.perf_counter() - t0
+        back = 0.0
+        if kw.get("hist") is not None:                  # the chain is still there: the same read-back once more
+            t1 = time.perf_counter()
+            ctx.chain_hist()
+            back = time.perf_counter() - t1
     finally:
         ctx.close()
-    return 1e3 * dt / ns, st.nAccept
+    return 1e3 * (dt - back) / ns, st.nAccept, 1e3 * back
 
 
 def bench_floor(name):
@@ -72,11 +82,13 @@ def main():
     log = open(os.path.join(ROOT, "profiles", "chain_time.log"), "a")
     for name in a.configs:
         ms = {k: [] for k in MODES}
-        acc = {}
+        acc, back = {}, []
         for rep in range(a.reps):                       # interleaved: a, b, c, a, b, c, ...
             for k, kw in MODES.items():
-                t, nacc = one_run(name, kw, a.samples, 100 + rep)
+                t, nacc, rb = one_run(name, kw, a.samples, 100 + rep)
                 ms[k].append(t); acc[k] = nacc
+                if k == D:
+                    back.append(rb)
                 print(f"{name} rep {rep} {k}: {t:.3f} ms per sample", file=sys.stderr, flush=True)
         line = {"config": name, "argv": sys.argv[1:], "L": L, "dt": DT, "samples_per_run": a.samples, "reps": a.reps, "ms_per_sample": {}}
         for k, v in ms.items():
@@ -87,6 +99,9 @@ def main():
         line["b_minus_a_ms"] = med["b_device_chain"] - med["a_host_loop_device_leapfrog"]
         line["c_minus_a_ms"] = med["c_device_chain_no_samples"] - med["a_host_loop_device_leapfrog"]
         line["b_and_c_within_spread_of_a"] = bool(line["b_minus_a_ms"] <= spread and line["c_minus_a_ms"] <= spread)
+        line["d_minus_c_ms"] = med[D] - med["c_device_chain_no_samples"]
+        line["d_within_spread_of_c"] = bool(abs(line["d_minus_c_ms"]) <= spread)
+        line["d_readback_ms"] = statistics.median(back)
         if not a.no_floor:
             floor, sps = bench_floor(name)
             line["floor_ms_per_sample_L_times_bench_step"] = floor
