@@ -264,6 +264,20 @@ struct hmcmt_ctx {
             long long count = 0;
             double *d_mean = nullptr, *d_m2 = nullptr;   // [2 nData] each
         } dmom;
+        struct Acov {                                 // hmcmt_chain_acov_*: lagged autocovariances, every array lag-major (hmcmt_items.h)
+            bool on = false;
+            long long ntarget = 0, count = 0;
+            int K = 0;
+            long long* d_target = nullptr;            // [ntarget] active-cell indices; nullptr: every cell, row j = cell j
+            double *d_x0 = nullptr, *d_tot = nullptr; // [ntarget] pivot and sum of y
+            double *d_S = nullptr, *d_H = nullptr, *d_ring = nullptr;   // [K + 1][ntarget] each
+            // hmcmt_debug_chain_acov_time (measurement only): a pair of events round every k_chain_acov launch
+            bool timing = false;
+            std::vector<hipEvent_t> ev;               // pool, two per pending launch
+            std::vector<int> pending;                 // class of each pending launch: 0 some lag still fills H_k (t < K), 1 steady
+            double ms[2] = {0, 0};
+            long long launches[2] = {0, 0};
+        } acov;
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)

@@ -910,5 +910,86 @@ HD double item_chain_quantile(const unsigned int* counts, long long ntarget, int
     const double c = (double)counts[(long long)b * ntarget + r];
     return lo + w * ((double)b + (x - (double)cum) / c);
 }
+// Lagged autocovariances of the committed models (hmcmt_chain_acov_*).  Every array with a lag or a ring slot lies LAG-MAJOR,
+// a[k * ntarget + j]: the lanes of a wavefront are neighbouring targets j of one lag and touch adjacent doubles.  Counted commits are
+// t = 0, 1, ...; y_t = m[target] - x0 with x0 the value at t = 0 (one subtraction).  Per target: tot = sum y_t (serial adds),
+// S_k = sum_{t >= k} fma(y_t, y_{t-k}, .), H_k = sum_{t < k} y_t, and a ring of K + 1 slots, slot t mod (K + 1) = y_t: the slot written
+// at commit t held y_{t-K-1}, which no lag of this commit reads.
+constexpr int CHAIN_ACOV_MAXLAG = 1023;
+constexpr int CHAIN_ACOV_RUN = 8;     // lags per thread of k_chain_acov: y_t, the pivot and the ring index stay in registers
+// commit t of target j for the lags k0 <= k < k1 (k1 <= K + 1); target == nullptr: row j is cell j.  The owner of lag 0 also owns
+// x0, tot and the ring slot of this commit; at t = 0 nobody reads x0 (y_0 = 0 by definition).
+HD void item_chain_acov(const double* m, const long long* target, double* x0, double* tot, double* S, double* H, double* ring,
+                        long long ntarget, int K, long long t, long long j, int k0, int k1) {
+    const double x = m[target ? target[j] : j];
+    const double y = t == 0 ? 0.0 : x - x0[j];
+    const int nslot = K + 1;
+    int slot = (int)((t + nslot - (k0 % nslot)) % nslot);          // slot of y_{t-k0}
+    for (int k = k0; k < k1; ++k) {
+        const long long i = (long long)k * ntarget + j;
+        if (k == 0) {
+            if (t == 0) x0[j] = x;
+            tot[j] += y;
+            ring[(long long)slot * ntarget + j] = y;
+            S[i] = fma(y, y, S[i]);
+        } else if (t >= k) {
+            S[i] = fma(y, ring[(long long)slot * ntarget + j], S[i]);
+        } else {
+            H[i] += y;                                             // (t < k: y_t is one of the first k samples)
+        }
+        slot = slot == 0 ? K : slot - 1;
+    }
+}
+// c_k, k = 0 .. K, of target j from the state after N >= 1 commits, and mean = x0 + ybar (each output may be nullptr): the owner of
+// the target walks its lags with T_k, the sum of the last k samples, running newest first from the ring: T_k = T_{k-1} + y_{N-k}.
+HD void item_chain_acov_out(const double* x0, const double* tot, const double* S, const double* H, const double* ring, long long ntarget,
+                            int K, long long N, long long j, double* mean, double* acov) {
+    const double tt = tot[j], ybar = tt / (double)N;
+    if (mean) mean[j] = x0[j] + ybar;
+    if (!acov) return;
+    int slot = (int)((N - 1) % (K + 1));                           // slot of y_{N-1}
+    double T = 0.0;
+    for (int k = 0; k <= K; ++k) {
+        const long long i = (long long)k * ntarget + j;
+        if (k >= N) { acov[i] = 0.0; continue; }
+        if (k > 0) {
+            T += ring[(long long)slot * ntarget + j];
+            slot = slot == 0 ? K : slot - 1;
+        }
+        const double A = tt - H[i], B = tt - T;
+        acov[i] = (S[i] - ybar * (A + B) + (double)(N - k) * (ybar * ybar)) / (double)N;
+    }
+}
+// Geyer's initial positive sequence on acov[(K + 1)][ntarget] of N >= 1 commits: Gamma_m = (c_2m + c_2m+1) / c_0 summed while > 0;
+// tau = -1 + 2 sum; window = +pairs summed if a non-positive pair ended the sum, -pairs if the lags ran out.  cap = N max(1, log10 N)
+// and capTau = 1 / max(1, log10 N) come from the host (one log10 for all targets).  Each of tau, ess, window may be nullptr.
+HD void item_chain_ess(const double* acov, long long ntarget, int K, long long N, double cap, double capTau, long long j, double* tau,
+                       double* ess, int* window) {
+    const double c0 = acov[j];
+    double t, e;
+    int w;
+    if (!(c0 > 0.0)) {                                             // a constant cell
+        t = (double)N; e = 1.0; w = 0;
+    } else {
+        const int kmax = (int)(N - 1 < (long long)K ? N - 1 : (long long)K);
+        const int npairs = kmax >= 1 ? (kmax - 1) / 2 + 1 : 0;
+        double sum = 0.0;
+        int M = 0;
+        bool ended = false;
+        for (int p = 0; p < npairs; ++p) {
+            const double G = (acov[(long long)(2 * p) * ntarget + j] + acov[(long long)(2 * p + 1) * ntarget + j]) / c0;
+            if (!(G > 0.0)) { ended = true; break; }
+            sum += G;
+            ++M;
+        }
+        t = -1.0 + 2.0 * sum;
+        w = ended ? M : -M;
+        const double r = (double)N / t;
+        e = (t <= capTau || r > cap) ? cap : r;
+    }
+    if (tau) tau[j] = t;
+    if (ess) ess[j] = e;
+    if (window) window[j] = w;
+}
 
 }  // namespace hmcmt

@@ -4,12 +4,35 @@
 // One sample = hmcmt_chain_momentum + hmcmt_chain_step.  What crosses PCIe per sample: nAC normals up, LFNB partial sums and
 // CHAIN_REC scalars down; with outputs, nAC + 2 nData doubles more.  Launches per sample beyond leapfrog_core's (diagonal mass):
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
-// k_chain_hist and a second k_chain_welford (the predicted data) behind them.
+// k_chain_hist, a second k_chain_welford (the predicted data) and k_chain_acov (lagged autocovariances) behind them.
 
-// ends the commit's optional accumulators (histogram, data moments) and frees their buffers
+// measurement only (hmcmt_debug_chain_acov_time): the event pairs round the k_chain_acov launches
+static void chain_acov_time_collect(hmcmt_ctx* ctx) {
+    auto& A = ctx->chain.acov;
+    if (A.pending.empty()) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    for (size_t i = 0; i < A.pending.size(); ++i) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, A.ev[2 * i], A.ev[2 * i + 1]) == hipSuccess) { A.ms[A.pending[i]] += ms; A.launches[A.pending[i]] += 1; }
+    }
+    A.pending.clear();
+}
+static void chain_acov_time_free(hmcmt_ctx* ctx) {
+    auto& A = ctx->chain.acov;
+    if (A.ev.empty()) return;
+    hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (hipEvent_t e : A.ev) hipEventDestroy(e);
+    A.ev.clear(); A.pending.clear();
+    A.timing = false;
+}
+
+// ends the commit's optional accumulators (histogram, data moments, autocovariances) and frees their buffers
 static void chain_acc_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
-    void* bufs[] = {C.hist.d_target, C.hist.d_counts, C.dmom.d_mean, C.dmom.d_m2};
+    void* bufs[] = {C.hist.d_target, C.hist.d_counts, C.dmom.d_mean, C.dmom.d_m2, C.acov.d_target, C.acov.d_x0, C.acov.d_tot,
+                    C.acov.d_S, C.acov.d_H, C.acov.d_ring};
+    chain_acov_time_free(ctx);
     bool any = false;
     for (void* p : bufs) any = any || p;
     if (any) {
@@ -19,6 +42,7 @@ static void chain_acc_release(hmcmt_ctx* ctx) {
     }
     C.hist = hmcmt_ctx::Chain::Hist{};
     C.dmom = hmcmt_ctx::Chain::DataMoments{};
+    C.acov = hmcmt_ctx::Chain::Acov{};
 }
 
 static void chain_release(hmcmt_ctx* ctx) {
@@ -231,6 +255,21 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
             ++C.dmom.count;
             hipLaunchKernelGGL(k_chain_welford, dim3((2 * nData + 255) / 256), dim3(256), 0, st, 2 * nData, C.d_pred[C.cur], C.dmom.d_mean,
                                C.dmom.d_m2, (double)C.dmom.count);
+        }
+        if (C.acov.on) {
+            auto& A = C.acov;                                // (the commit's number t is the count before it: t = 0 sets the pivot)
+            bool timed = false;
+            if (A.timing) {                                  // (measurement only: the next pair of the pool, grown as needed)
+                if (A.pending.size() >= 1024) chain_acov_time_collect(ctx);
+                const size_t i = A.pending.size();
+                while (A.ev.size() < 2 * i + 2) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); break; } A.ev.push_back(e); }
+                timed = A.ev.size() >= 2 * i + 2;
+                if (timed) hipEventRecord(A.ev[2 * i], st);
+            }
+            hipLaunchKernelGGL(k_chain_acov, dim3((unsigned)((A.ntarget + 255) / 256), (unsigned)(A.K / CHAIN_ACOV_RUN + 1)), dim3(256), 0, st,
+                               A.ntarget, A.K, A.count, C.d_m[C.cur], A.d_target, A.d_x0, A.d_tot, A.d_S, A.d_H, A.d_ring);
+            if (timed) { hipEventRecord(A.ev[2 * A.pending.size() + 1], st); A.pending.push_back(A.count >= A.K ? 1 : 0); }
+            ++A.count;
         }
     }
     C.gen = ctx->stateGen;
@@ -448,6 +487,164 @@ int hmcmt_chain_data_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, doubl
     if (m2) HIPCHK(hipMemcpyAsync(m2, M.d_m2, bytes, kind, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (count) *count = M.count;
+    return 0;
+}
+
+// ---- lagged autocovariances and the effective sample size (k_chain_acov, k_chain_acov_out, k_chain_ess) ----------------------------
+static void chain_acov_free(hmcmt_ctx* ctx) {
+    auto& A = ctx->chain.acov;
+    chain_acov_time_free(ctx);
+    for (void* p : {(void*)A.d_target, (void*)A.d_x0, (void*)A.d_tot, (void*)A.d_S, (void*)A.d_H, (void*)A.d_ring}) if (p) hipFree(p);
+    A = hmcmt_ctx::Chain::Acov{};
+}
+
+int hmcmt_chain_acov_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* target, int32_t maxlag) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_acov_begin", true);
+    if (rc) return rc;
+    const int n = ctx->v.nAC;
+    const bool all = !target && ntarget == 0;
+    if ((!all && (!target || ntarget < 1)) || maxlag < 1 || maxlag > CHAIN_ACOV_MAXLAG) {
+        ctx->err = "hmcmt_chain_acov_begin: need target and ntarget >= 1 (or NULL and 0: every active cell) and 1 <= maxlag <= 1023";
+        return HMCMT_EINVAL;
+    }
+    for (int64_t i = 0; i < ntarget; ++i)
+        if (target[i] < 0 || target[i] >= n) {
+            ctx->err = "hmcmt_chain_acov_begin: target " + std::to_string(i) + " = " + std::to_string(target[i]) + " is no active cell (0.." +
+                       std::to_string(n - 1) + ")";
+            return HMCMT_EINVAL;
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    auto& A = ctx->chain.acov;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be adding to the accumulator this one replaces)
+    chain_acov_free(ctx);
+    const long long nt = all ? n : ntarget;
+    const size_t tb = (size_t)nt * sizeof(long long), vb = (size_t)nt * sizeof(double), lb = vb * (size_t)(maxlag + 1);
+    auto build = [&]() -> int {
+        int r;
+        if (!all && (r = chain_acc_alloc(ctx, "hmcmt_chain_acov_begin", (void**)&A.d_target, tb))) return r;
+        const std::pair<double**, size_t> bufs[] = {{&A.d_x0, vb}, {&A.d_tot, vb}, {&A.d_S, lb}, {&A.d_H, lb}, {&A.d_ring, lb}};
+        for (const auto& b : bufs) {
+            if ((r = chain_acc_alloc(ctx, "hmcmt_chain_acov_begin", (void**)b.first, b.second))) return r;
+            HIPCHK(hipMemsetAsync(*b.first, 0, b.second, st));
+        }
+        if (!all) HIPCHK(hipMemcpyAsync(A.d_target, target, tb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));                    // (the caller's list is free again on return)
+        return 0;
+    };
+    if ((rc = build())) {
+        (void)hipStreamSynchronize(st);
+        chain_acov_free(ctx);
+        return rc;
+    }
+    A.ntarget = nt; A.K = maxlag; A.count = 0;
+    A.on = true;
+    return 0;
+}
+
+// mean and acov into device pointers (each may be nullptr), enqueued
+static void chain_acov_launch(hmcmt_ctx* ctx, double* d_mean, double* d_acov) {
+    auto& A = ctx->chain.acov;
+    hipLaunchKernelGGL(k_chain_acov_out, dim3((unsigned)((A.ntarget + 255) / 256)), dim3(256), 0, ctx->stream,
+                       A.ntarget, A.K, A.count, A.d_x0, A.d_tot, A.d_S, A.d_H, A.d_ring, d_mean, d_acov);
+}
+
+int hmcmt_chain_acov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* acov, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_acov", true);
+    if (rc) return rc;
+    auto& A = ctx->chain.acov;
+    if (!A.on) { ctx->err = "hmcmt_chain_acov: no autocovariances (hmcmt_chain_acov_begin first)"; return HMCMT_EINVAL; }
+    if ((mean || acov) && A.count == 0) { ctx->err = "hmcmt_chain_acov: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t mb = sizeof(double) * (size_t)A.ntarget, ab = mb * (size_t)(A.K + 1);
+    double *d_mean = nullptr, *d_acov = nullptr;
+    auto run = [&]() -> int {
+        int r;
+        if (!mean && !acov) return 0;
+        if (on_device) { d_mean = mean; d_acov = acov; }
+        else {
+            if (mean && (r = chain_acc_alloc(ctx, "hmcmt_chain_acov", (void**)&d_mean, mb))) return r;
+            if (acov && (r = chain_acc_alloc(ctx, "hmcmt_chain_acov", (void**)&d_acov, ab))) return r;
+        }
+        chain_acov_launch(ctx, d_mean, d_acov);
+        HIPCHK(hipGetLastError());
+        if (!on_device) {
+            if (mean) HIPCHK(hipMemcpyAsync(mean, d_mean, mb, hipMemcpyDeviceToHost, st));
+            if (acov) HIPCHK(hipMemcpyAsync(acov, d_acov, ab, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st);
+    if (!on_device) { if (d_mean) hipFree(d_mean); if (d_acov) hipFree(d_acov); }
+    if (!rc && count) *count = A.count;
+    return rc;
+}
+
+int hmcmt_chain_ess(hmcmt_ctx* ctx, double* tau, double* ess, int32_t* window, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_ess", true);
+    if (rc) return rc;
+    auto& A = ctx->chain.acov;
+    if (!A.on) { ctx->err = "hmcmt_chain_ess: no autocovariances (hmcmt_chain_acov_begin first)"; return HMCMT_EINVAL; }
+    if (A.count == 0) { ctx->err = "hmcmt_chain_ess: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    if (!tau && !ess && !window) return 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t mb = sizeof(double) * (size_t)A.ntarget, ab = mb * (size_t)(A.K + 1), wb = sizeof(int) * (size_t)A.ntarget;
+    const double lg = std::max(1.0, std::log10((double)A.count));
+    double *d_acov = nullptr, *d_tau = nullptr, *d_ess = nullptr;
+    int* d_win = nullptr;
+    static_assert(sizeof(int) == sizeof(int32_t), "window is written as int");
+    auto run = [&]() -> int {
+        int r;
+        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_acov, ab))) return r;
+        if (on_device) { d_tau = tau; d_ess = ess; d_win = (int*)window; }
+        else {
+            if (tau && (r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_tau, mb))) return r;
+            if (ess && (r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_ess, mb))) return r;
+            if (window && (r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_win, wb))) return r;
+        }
+        chain_acov_launch(ctx, nullptr, d_acov);
+        hipLaunchKernelGGL(k_chain_ess, dim3((unsigned)((A.ntarget + 255) / 256)), dim3(256), 0, st, A.ntarget, A.K, A.count,
+                           (double)A.count * lg, 1.0 / lg, d_acov, d_tau, d_ess, d_win);
+        HIPCHK(hipGetLastError());
+        if (!on_device) {
+            if (tau) HIPCHK(hipMemcpyAsync(tau, d_tau, mb, hipMemcpyDeviceToHost, st));
+            if (ess) HIPCHK(hipMemcpyAsync(ess, d_ess, mb, hipMemcpyDeviceToHost, st));
+            if (window) HIPCHK(hipMemcpyAsync(window, d_win, wb, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st);
+    if (d_acov) hipFree(d_acov);
+    if (!on_device) { if (d_tau) hipFree(d_tau); if (d_ess) hipFree(d_ess); if (d_win) hipFree(d_win); }
+    return rc;
+}
+
+// measurement only (include/hmcmt_debug.h)
+int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, "hmcmt_debug_chain_acov_time", true);
+    if (rc) return rc;
+    auto& A = ctx->chain.acov;
+    if (!A.on) { ctx->err = "hmcmt_debug_chain_acov_time: no autocovariances (hmcmt_chain_acov_begin first)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    chain_acov_time_collect(ctx);
+    for (int i = 0; i < 2; ++i) {
+        if (ms) ms[i] = A.ms[i];
+        if (launches) launches[i] = A.launches[i];
+    }
+    if (enable >= 0) {                                       // (the sums up to here went out; a switch starts new ones)
+        A.timing = enable != 0;
+        for (int i = 0; i < 2; ++i) { A.ms[i] = 0; A.launches[i] = 0; }
+    }
     return 0;
 }
 

@@ -74,3 +74,30 @@ __global__ __launch_bounds__(256) void k_chain_hist_out(long long ntarget, int n
     const int b = (int)(i - r * nbins);
     out[i] = counts[(long long)b * ntarget + r];
 }
+// one counted commit of the autocovariance accumulator: thread (j, run) owns target j's lags [run * CHAIN_ACOV_RUN, ...) -- the lanes of
+// a wavefront are neighbouring targets, every array lag-major (hmcmt_items.h); no thread reads what another writes in this launch
+__global__ __launch_bounds__(256) void k_chain_acov(long long ntarget, int K, long long t, const double* __restrict__ m,
+                                                    const long long* __restrict__ target, double* __restrict__ x0, double* __restrict__ tot,
+                                                    double* __restrict__ S, double* __restrict__ H, double* ring) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int k0 = (int)blockIdx.y * CHAIN_ACOV_RUN;
+    if (j >= ntarget || k0 > K) return;
+    const int k1 = k0 + CHAIN_ACOV_RUN < K + 1 ? k0 + CHAIN_ACOV_RUN : K + 1;
+    item_chain_acov(m, target, x0, tot, S, H, ring, ntarget, K, t, j, k0, k1);
+}
+// acov[k][j] and mean[j]: one thread per target walks its lags with a running T_k (O(K) per target); neighbouring targets of one
+// lag or ring slot are read and written together
+__global__ __launch_bounds__(256) void k_chain_acov_out(long long ntarget, int K, long long N, const double* __restrict__ x0,
+                                                        const double* __restrict__ tot, const double* __restrict__ S,
+                                                        const double* __restrict__ H, const double* __restrict__ ring,
+                                                        double* __restrict__ mean, double* __restrict__ acov) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j < ntarget) item_chain_acov_out(x0, tot, S, H, ring, ntarget, K, N, j, mean, acov);
+}
+// tau, ess and window: one thread per target walks its lags, neighbouring targets of one lag read together (as k_chain_quantiles)
+__global__ __launch_bounds__(256) void k_chain_ess(long long ntarget, int K, long long N, double cap, double capTau,
+                                                   const double* __restrict__ acov, double* __restrict__ tau, double* __restrict__ ess,
+                                                   int* __restrict__ window) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j < ntarget) item_chain_ess(acov, ntarget, K, N, cap, capTau, j, tau, ess, window);
+}

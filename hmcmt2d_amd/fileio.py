@@ -363,3 +363,19 @@ def getPosteriorQuantileModels(hist, q, mtMesh, invParam, outdir=".", write=True
             mtMesh.sigma = sigma
             writeEMModel2D(os.path.join(outdir, "p%sModel.model" % pct.zfill(2)), mtMesh)
     return models
+
+
+def getESSModel(path, ess_stats, mtMesh, invParam, write=True):
+    """The map of the effective sample size as a .model file: ess_stats = hmcstats.ess of runHMCSampler(device_chain=True, ess={})
+    over every active cell, in order (its default targets), or sampler.mergeAcov of several chains.  Every active cell holds its
+    ESS on top of the background, the way stdModel.model holds the standard deviation.  Returns ess[nparam]."""
+    nparam = len(invParam.activeIdx)
+    targets = np.asarray(ess_stats["targets"])
+    if targets.shape != (nparam,) or not np.array_equal(targets, np.arange(nparam)):
+        raise ValueError("getESSModel: needs the effective sample size of every active cell, in order (ess targets = arange(nparam))")
+    ess = np.asarray(ess_stats["ess"], dtype=np.float64).copy()
+    if write:
+        sigma = invParam.bgModel.copy(); sigma[invParam.activeIdx] += ess
+        mtMesh.sigma = sigma
+        writeEMModel2D(path, mtMesh)
+    return ess

@@ -152,7 +152,7 @@ def load_library():
     for name in ("hmcmt_jvp_block", "hmcmt_jtvp_block", "hmcmt_gn_hessvec_block"):
         getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(Stats)]
         getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(Stats)]
-    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS:
+    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib.hmcmt_chain_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -167,6 +167,11 @@ def load_library():
     lib.hmcmt_chain_hist_quantiles.argtypes = [vp, C.c_int32, c_double_p, vp, C.c_int32]
     lib.hmcmt_chain_data_moments_begin.argtypes = [vp]
     lib.hmcmt_chain_data_moments.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, C.c_int32]
+    lib.hmcmt_chain_acov_begin.argtypes = [vp, C.c_int64, c_int64_p, C.c_int32]
+    lib.hmcmt_chain_acov.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, C.c_int32]
+    lib.hmcmt_chain_ess.argtypes = [vp, vp, vp, vp, C.c_int32]
+    lib.hmcmt_debug_chain_acov_time.argtypes = [vp, C.c_int32, c_double_p, c_int64_p]
+    lib.hmcmt_debug_chain_acov_time.restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
@@ -193,8 +198,11 @@ CHAIN_SYMBOLS = ["hmcmt_chain_begin", "hmcmt_chain_momentum", "hmcmt_chain_step"
 CHAIN_HIST_SYMBOLS = ["hmcmt_chain_hist_begin", "hmcmt_chain_hist", "hmcmt_chain_hist_quantiles",
                       "hmcmt_chain_data_moments_begin", "hmcmt_chain_data_moments"]
 HIST_MAXBINS = 4096   # include/hmcmt.h: nbins of hmcmt_chain_hist_begin
+# ... and the third one: lagged autocovariances, integrated autocorrelation time and effective sample size
+CHAIN_ACOV_SYMBOLS = ["hmcmt_chain_acov_begin", "hmcmt_chain_acov", "hmcmt_chain_ess"]
+ACOV_MAXLAG = 1023    # include/hmcmt.h: maxlag of hmcmt_chain_acov_begin
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -204,7 +212,7 @@ PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + ["hmcmt_def
 DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead", "hmcmt_dims",
                  "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond", "hmcmt_debug_fdm_fwd",
                  "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_debug_hog", "hmcmt_persist_envelope",
-                 "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info"]
+                 "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -720,6 +728,67 @@ class HipContext:
         if self.args.real_data:
             return int(n.value), mean[0::2].copy(), m2[0::2].copy()
         return int(n.value), mean.view(np.complex128), m2.view(np.complex128)
+
+    # -- effective sample size from the chain's commit (hmcmt_chain_acov_*, hmcmt_chain_ess) --
+    def chain_acov_begin(self, targets=None, maxlag=63):
+        """Starts per-cell lagged autocovariances of ln sigma for the lags 0 .. maxlag (1 .. 1023) of the active-cell indices `targets`
+        (0-based, repeats allowed; None: every active cell): every later commit behind the burn-in counts.  Replaces an accumulator
+        that is running."""
+        if targets is None:
+            self._check(self.lib.hmcmt_chain_acov_begin(self.h, 0, None, int(maxlag)))
+            nt = self.nAC
+        else:
+            t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+            if len(t) == 0:
+                raise ValueError("chain_acov_begin: no target (None means every active cell)")
+            self._check(self.lib.hmcmt_chain_acov_begin(self.h, len(t), t.ctypes.data_as(c_int64_p), int(maxlag)))
+            nt = len(t)
+        self._acov_shape = (int(maxlag) + 1, nt)
+
+    def chain_acov_count(self):
+        """Commits in the accumulator (the read-outs need at least one)."""
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_acov(self.h, C.byref(n), None, None, 0))
+        return int(n.value)
+
+    def _acov_shape_or_raise(self):
+        self.chain_acov_count()
+        return self._acov_shape
+
+    def chain_acov_timing(self, enable=None):
+        """Measurement only (hmcmt_debug_chain_acov_time): enable = True / False switches HIP-event pairs round every k_chain_acov
+        launch on / off and zeroes the sums, None only reads.  Returns the sums up to the call: {"filling": (ms, launches), "steady": (ms, launches)}: the
+        commits with count < maxlag, where some lag still fills its H_k, and those behind them."""
+        ms, n = np.zeros(2), np.zeros(2, dtype=np.int64)
+        self._check(self.lib.hmcmt_debug_chain_acov_time(self.h, -1 if enable is None else int(bool(enable)), _dp(ms),
+                                                         n.ctypes.data_as(c_int64_p)))
+        return {"filling": (float(ms[0]), int(n[0])), "steady": (float(ms[1]), int(n[1]))}
+
+    def chain_acov(self):
+        """(count, mean[ntarget], acov[maxlag + 1, ntarget]): commits in the accumulator, the targets' means and the biased
+        autocovariance estimates c_k, lag-major (c_k = 0 for k >= count)."""
+        n = C.c_int64()
+        shape = self._acov_shape_or_raise()
+        mean, acov = np.empty(shape[1]), np.empty(shape)
+        self._check(self.lib.hmcmt_chain_acov(self.h, C.byref(n), mean.ctypes.data, acov.ctypes.data, 0))
+        return int(n.value), mean, acov
+
+    def chain_acov_device(self, d_mean=None, d_acov=None):
+        """The same into device pointers (int; each may be None) to ntarget and (maxlag + 1) * ntarget doubles; returns count."""
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_acov(self.h, C.byref(n), d_mean, d_acov, 1))
+        return int(n.value)
+
+    def chain_ess(self, d_tau=None, d_ess=None, d_window=None):
+        """(tau[ntarget], ess[ntarget], window[ntarget] int32) by Geyer's initial positive sequence, computed on the device
+        (include/hmcmt.h) -- or, with any of the device pointers (int) given, into those, returning None."""
+        if d_tau is not None or d_ess is not None or d_window is not None:
+            self._check(self.lib.hmcmt_chain_ess(self.h, d_tau, d_ess, d_window, 1))
+            return None
+        nt = self._acov_shape_or_raise()[1]
+        tau, ess, window = np.empty(nt), np.empty(nt), np.empty(nt, dtype=np.int32)
+        self._check(self.lib.hmcmt_chain_ess(self.h, tau.ctypes.data, ess.ctypes.data, window.ctypes.data, 0))
+        return tau, ess, window
 
     # -- instrumentation ----------------------------------------------------------------------
     def profile(self, enable=True, every=1):

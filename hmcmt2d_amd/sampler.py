@@ -457,7 +457,115 @@ def histToLog10Rho(hist):
     return (-edges_m / np.log(10.0))[::-1].copy(), np.asarray(counts)[:, ::-1].copy()
 
 
-def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False):
+def acovOf(x, maxlag):
+    """The biased autocovariance estimates c_k = (1/N) sum_{t=k}^{N-1} (x_t - xbar)(x_{t-k} - xbar), k = 0 .. maxlag, of the chain(s)
+    x[N] or x[ntarget, N] (rows = cells, columns = samples, as hmcmodel): acov[maxlag + 1] or acov[maxlag + 1, ntarget], lag-major as
+    the library returns them (hmcmt_chain_acov); c_k = 0 for k >= N."""
+    x = np.asarray(x, dtype=np.float64)
+    rows = np.atleast_2d(x)
+    N, K = rows.shape[1], int(maxlag)
+    if N < 1 or K < 1:
+        raise ValueError("acovOf: needs at least one sample and maxlag >= 1")
+    d = rows - rows.mean(axis=1, keepdims=True)
+    out = np.zeros((K + 1, rows.shape[0]))
+    for k in range(min(K, N - 1) + 1):
+        out[k] = (d[:, k:] * d[:, :N - k]).sum(axis=1) / N
+    return out[:, 0] if x.ndim == 1 else out
+
+
+def _initial_positive_sequence(gamma):
+    """Geyer's rule on the pair sums gamma[npairs, ntarget]: (tau, window)."""
+    npairs, nt = gamma.shape
+    tau, window = np.empty(nt), np.zeros(nt, dtype=np.int32)
+    for j in range(nt):
+        s, M, ended = 0.0, 0, False
+        for m in range(npairs):
+            G = gamma[m, j]
+            if not G > 0.0:
+                ended = True
+                break
+            s += G
+            M += 1
+        tau[j] = -1.0 + 2.0 * s
+        window[j] = M if ended else -M
+    return tau, window
+
+
+def _npairs(K, N):
+    nlag = min(K, N - 1)
+    return (nlag - 1) // 2 + 1 if nlag >= 1 else 0
+
+
+def _ess_of_tau(tau, n):
+    lg = max(1.0, float(np.log10(n)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = n / tau
+    return np.where((tau <= 1.0 / lg) | (r > n * lg), n * lg, r)
+
+
+def essFromAcov(acov, count):
+    """(tau, ess, window) from acov[maxlag + 1(, ntarget)] of `count` samples by the library's rule (hmcmt_chain_ess): Geyer's initial
+    positive sequence over Gamma_m = (c_2m + c_2m+1) / c_0, tau = -1 + 2 sum Gamma_m, ess = min(N / tau, N max(1, log10 N)) (the cap
+    also when tau <= 1 / max(1, log10 N)), window = +pairs when a non-positive pair ended the sum and -pairs when the lags ran out;
+    a constant cell (c_0 > 0 false) has tau = N, ess = 1, window = 0."""
+    a = np.asarray(acov, dtype=np.float64)
+    a2 = a.reshape(a.shape[0], -1)
+    N, K = int(count), a2.shape[0] - 1
+    if N < 1 or K < 1:
+        raise ValueError("essFromAcov: needs count >= 1 and at least the lags 0 and 1")
+    moved = a2[0] > 0.0
+    P = _npairs(K, N)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gamma = np.where(moved, (a2[0:2 * P:2] + a2[1:2 * P:2]) / a2[0], 0.0)
+    tau, window = _initial_positive_sequence(gamma)
+    ess = _ess_of_tau(tau, N)
+    tau, ess, window = np.where(moved, tau, float(N)), np.where(moved, ess, 1.0), np.where(moved, window, 0).astype(np.int32)
+    if a.ndim == 1:
+        return float(tau[0]), float(ess[0]), int(window[0])
+    return tau, ess, window
+
+
+def mcseOfMean(ess_stats, moments):
+    """Monte-Carlo standard error of the posterior mean of every target of hmcstats.ess: sqrt(m2 / count / ess) with
+    moments = (count, mean, m2) = hmcstats.moments (the posterior variance m2 / count over the effective sample size)."""
+    count, _, m2 = moments
+    t = np.asarray(ess_stats["targets"])
+    return np.sqrt(np.asarray(m2)[t] / float(count) / np.asarray(ess_stats["ess"]))
+
+
+def mergeAcov(list_of_ess):
+    """The effective sample size of several chains of equal count N from their hmcstats.ess, in the BDA3 / Stan form: with the
+    per-chain c^_k = c_k N / (N - 1), W = mean_c c^_0, B / N = var_c(mean_c, ddof=1) (0 for one chain),
+    var+ = W (N - 1) / N + B / N and rho_k = 1 - (W - mean_c c^_k) / var+, the initial positive sequence over rho_2m + rho_2m+1,
+    tau = -1 + 2 sum, ess = C N / tau capped at C N max(1, log10(C N)).  Chains of different counts, lags or targets: ValueError.
+    Returns a dict: count (= C N), nchains, maxlag, targets, mean, rho, tau, ess, window."""
+    if not list_of_ess:
+        raise ValueError("mergeAcov: no chain")
+    first = list_of_ess[0]
+    N, K, t0 = int(first["count"]), int(first["maxlag"]), np.asarray(first["targets"])
+    for e in list_of_ess[1:]:
+        if int(e["count"]) != N or int(e["maxlag"]) != K or not np.array_equal(np.asarray(e["targets"]), t0):
+            raise ValueError("mergeAcov: the chains differ in count, maxlag or targets")
+    if N < 2:
+        raise ValueError("mergeAcov: needs at least two samples per chain")
+    C = len(list_of_ess)
+    chat = np.array([np.asarray(e["acov"], dtype=np.float64) for e in list_of_ess]) * (N / (N - 1.0))      # [C, K + 1, ntarget]
+    means = np.array([np.asarray(e["mean"], dtype=np.float64) for e in list_of_ess])
+    W = chat[:, 0].mean(axis=0)
+    BN = means.var(axis=0, ddof=1) if C > 1 else np.zeros_like(W)
+    varp = W * (N - 1.0) / N + BN
+    moved = varp > 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = np.where(moved, 1.0 - (W - chat.mean(axis=0)) / varp, 0.0)
+    P = _npairs(K, N)
+    tau, window = _initial_positive_sequence(rho[0:2 * P:2] + rho[1:2 * P:2])
+    ess = _ess_of_tau(tau, C * N)
+    return {"count": C * N, "nchains": C, "maxlag": K, "targets": t0.copy(), "mean": means.mean(axis=0), "rho": rho,
+            "tau": np.where(moved, tau, float(C * N)), "ess": np.where(moved, ess, 1.0),
+            "window": np.where(moved, window, 0).astype(np.int32)}
+
+
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False, ess=None):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals."""
@@ -485,14 +593,15 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
         ctx.chain_begin(fileModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
         ctx.chain_set_energy(startD, startM)
     if hist is not None:                                    # (behind the second begin: a begin ends the accumulators)
-        unknown = set(hist) - {"targets", "nbins", "lo", "hi"}
-        if unknown:
-            raise ValueError(f"runHMCSampler: hist has no key {sorted(unknown)} (targets, nbins, lo, hi)")
         targets = np.arange(nparam, dtype=np.int64) if hist.get("targets") is None else np.asarray(hist["targets"], dtype=np.int64)
         bins = (int(hist.get("nbins", 300)), float(hist.get("lo", lo)), float(hist.get("hi", hi)))     # (300: the reference's npBins)
         ctx.chain_hist_begin(targets, *bins)
     if data_moments:
         ctx.chain_data_moments_begin()
+    if ess is not None:
+        ess_targets = None if ess.get("targets") is None else np.asarray(ess["targets"], dtype=np.int64)
+        maxlag = int(ess.get("maxlag", 63))
+        ctx.chain_acov_begin(ess_targets, maxlag)
     startK = ctx.chain_momentum(z)
     nsamples = hmcprior.totalsamples
     nkeep = nsamples if keep_samples else 0
@@ -525,12 +634,23 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
         stats.hist = ctx.chain_hist() + (bins, targets.copy())
     if data_moments:
         stats.dataMoments = ctx.chain_data_moments()
+    if ess is not None:
+        # (a chain that ends inside its burn-in has counted nothing: the read-outs need a commit, the rest of the result stands)
+        count = ctx.chain_acov_count()
+        (_, mean, acov), (tau, e, window) = (ctx.chain_acov(), ctx.chain_ess()) if count > 0 else ((0, None, None), (None, None, None))
+        stats.ess = {"count": count, "maxlag": maxlag, "targets": np.arange(nparam, dtype=np.int64) if ess_targets is None else ess_targets.copy(),
+                     "mean": mean, "acov": acov, "tau": tau, "ess": e, "window": window, "misfit": None}
+        D = stats.hmstats[0, 1 + hmcprior.burninsamples:]      # the data misfit of the counted samples: the same estimator on the host
+        if len(D):
+            a = acovOf(D, maxlag)
+            t1, e1, w1 = essFromAcov(a, len(D))
+            stats.ess["misfit"] = {"count": len(D), "mean": float(D.mean()), "acov": a, "tau": t1, "ess": e1, "window": w1}
     return hmcmodel, stats, hmcdata
 
 
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
-                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False):
+                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -547,6 +667,11 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     histToLog10Rho, mergeHistograms, fileio.writeSitePPD, fileio.getPosteriorQuantileModels.  `data_moments=True` (with
     device_chain): hmcstats.dataMoments = (count, mean[ndata], m2[ndata]) of the predicted data at the same samples -- the
     posterior-predictive spread.  Neither changes the order of the random draws.
+    `ess={...}` (with device_chain): per-cell lagged autocovariances streamed in the commit, and from them the integrated
+    autocorrelation time and the effective sample size, computed on the GPU.  Keys, both optional: `targets` (default every cell) and
+    `maxlag` (63).  hmcstats.ess is a dict: count, maxlag, targets, mean, acov[maxlag + 1, ntarget], tau, ess, window (hmcmt_chain_ess,
+    include/hmcmt.h: window < 0 means the lags ran out and tau is a lower bound), and `misfit`, the same estimator applied here to the
+    data misfit of the counted samples.  A chain that ends inside its burn-in gives count 0 and None for the rest.  See acovOf, essFromAcov, mcseOfMean, mergeAcov, fileio.getESSModel.  The draws keep their order.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -564,10 +689,16 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
         raise ValueError("runHMCSampler: keep_samples=False needs device_chain=True (only the device chain streams the posterior moments)")
     if (hist is not None or data_moments) and not device_chain:
         raise ValueError("runHMCSampler: hist and data_moments need device_chain=True (they are streamed in the device chain's commit)")
+    if ess is not None and not device_chain:
+        raise ValueError("runHMCSampler: ess needs device_chain=True (the autocovariances are streamed in the device chain's commit)")
+    for name, given, keys in (("hist", hist, ("targets", "nbins", "lo", "hi")), ("ess", ess, ("targets", "maxlag"))):
+        unknown = set(given or ()) - set(keys)                 # (before the context is touched and the first number is drawn)
+        if unknown:
+            raise ValueError(f"runHMCSampler: {name} has no key {sorted(unknown)} ({', '.join(keys)})")
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments, ess)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -672,7 +803,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     (hmcmt_allgather_samples, include/hmcmt.h -- what a non-Python host would call) instead of torch's; the process
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
-    `path.chain<k>` per chain; device_chain=True, keep_samples=False).
+    `path.chain<k>` per chain; device_chain=True, keep_samples=False, hist=..., ess=...).
     Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
     count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
     gelmanRubin).  A chain's block in the gather is, in doubles,
@@ -819,6 +950,8 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
             hmcstats[c] = HMCStatus(int(acc.sum()), int((~acc).sum()), acc, hm)
             if with_moments:
                 hmcstats[c].moments = (int(round(buf[o])), buf[o + 1:o + 1 + nparam].copy(), buf[o + 1 + nparam:o + 1 + 2 * nparam].copy())
+            if c in results:                                # (ess= is not gathered: a chain's own rank keeps it, for mergeAcov)
+                hmcstats[c].ess = getattr(results[c][1], "ess", None)
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

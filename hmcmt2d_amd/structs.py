@@ -88,6 +88,7 @@ class HMCStatus:
                                   # on the device (runHMCSampler(device_chain=True)); not a field of the reference's struct
     hist: object = None           # (count, counts[ntarget, nbins], (nbins, lo, hi), targets): runHMCSampler(device_chain=True, hist=...)
     dataMoments: object = None    # (count, mean[ndata], m2[ndata]) of the predicted data: runHMCSampler(..., data_moments=True)
+    ess: object = None            # dict count, maxlag, targets, mean, acov, tau, ess, window, misfit: runHMCSampler(..., ess=...)
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

@@ -293,6 +293,36 @@ extern int hmcmt_chain_hist_quantiles(hmcmt_ctx* ctx, int32_t nq, const double* 
 extern int hmcmt_chain_data_moments_begin(hmcmt_ctx* ctx);
 extern int hmcmt_chain_data_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device);
 
+/* Effective sample size from the chain's commit (optional, a third accumulator under the rules above: fed by the commits behind the
+ * burn-in from its begin call on, a rejection's repeat included, with its own count N; nothing above changes when it is off).
+ *   hmcmt_chain_acov_begin   per-cell lagged autocovariances of m = ln sigma for the lags 0 .. K = maxlag, 1 <= maxlag <= 1023.
+ *                         target[ntarget] are 0-based active-cell indices, repeats allowed (rows of their own); target = NULL with
+ *                         ntarget = 0: every active cell, in order.  Counted commits are t = 0, 1, ...; per target, with the pivot
+ *                         x0 = the value at t = 0 and y_t = m[target] - x0 (one subtraction), the device holds
+ *                             tot = sum y_t (serial adds),  S_k = sum_{t >= k} y_t y_{t-k} (S_k = fma(y_t, y_{t-k}, S_k)),
+ *                             H_k = sum_{t < k} y_t (serial adds),  and a ring of the last K + 1 values y
+ *                         -- about (3 (K + 1) + 2) * 8 bytes per target, zeroed here.  On HMCMT_ENOMEM the chain goes on without the
+ *                         accumulator.  A second call replaces the first accumulator
+ *   hmcmt_chain_acov      count = N, mean[ntarget], acov[(K + 1)][ntarget] (LAG-MAJOR, the device's layout; each may be NULL);
+ *                         on_device as for hmcmt_chain_hist; complete on return.  With ybar = tot / N, T_k the sum of the last k
+ *                         values y added newest first, A_k = tot - H_k and B_k = tot - T_k:
+ *                             c_k = (S_k - ybar (A_k + B_k) + (N - k) ybar^2) / N  for k < N,  c_k = 0 for k >= N,  mean = x0 + ybar
+ *                         -- the biased estimator c_k = (1/N) sum_{t=k}^{N-1} (x_t - xbar)(x_{t-k} - xbar); a cell that never moved
+ *                         gives c_k == 0.0 exactly.  HMCMT_EINVAL when N = 0 and mean or acov is asked for
+ *   hmcmt_chain_ess       tau[ntarget], ess[ntarget], window[ntarget] (each may be NULL), computed on the device by Geyer's initial
+ *                         positive sequence: Gamma_m = (c_2m + c_2m+1) / c_0 for m = 0 .. floor((min(K, N - 1) - 1) / 2), summed while
+ *                         Gamma_m > 0, M pairs; tau = -1 + 2 sum Gamma_m (reported raw); ess = min(N / tau, N max(1, log10 N)), the
+ *                         cap also when tau <= 1 / max(1, log10 N); window = M if a non-positive pair ended the sum, -M if the lags
+ *                         ran out first (tau is then a lower bound).  A cell with c_0 > 0 false is constant: tau = N, ess = 1,
+ *                         window = 0.  HMCMT_EINVAL when N = 0
+ * hmcmt_chain_begin (also over a running chain), hmcmt_chain_end, hmcmt_set_prior and hmcmt_set_mass end the accumulator and release
+ * its buffers; a step that fails touches nothing.  HMCMT_EINVAL: NULL context, a size, lag or index outside the above, no chain, no
+ * accumulator begun, a call between hmcmt_grad_device_async and hmcmt_wait.  Results repeat bitwise (every (target, lag) has one
+ * owner thread: no atomics). */
+extern int hmcmt_chain_acov_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* target, int32_t maxlag);
+extern int hmcmt_chain_acov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* acov, int32_t on_device);
+extern int hmcmt_chain_ess(hmcmt_ctx* ctx, double* tau, double* ess, int32_t* window, int32_t on_device);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -97,6 +97,12 @@ int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, doub
 #define HMCMT_MASS_INFO_FIELDS 7
 int hmcmt_mass_info(const hmcmt_ctx* ctx, double* out /*[HMCMT_MASS_INFO_FIELDS]*/);
 
+/* Measurement only: HIP-event pairs round every k_chain_acov launch of the running autocovariance accumulator (hmcmt_chain_acov_begin),
+ * in place in the chain's commit.  ms[2], launches[2] (each may be NULL) receive the sums since the last switch; then enable = 1 / 0
+ * switches on / off and zeroes the sums, enable = -1 leaves them (read only).  Of each pair [0] the commits in which some lag still fills its H_k (count < maxlag), [1] the
+ * steady commits (count >= maxlag: every lag reads the ring and updates S_k).  An interval includes the cost of its two event records */
+int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]*/, int64_t* launches /*[2]*/);
+
 #ifdef __cplusplus
 }
 #endif

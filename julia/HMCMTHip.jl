@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -544,6 +544,49 @@ function chain_hist!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior
     lo = log(hmcprior.sigBounds[1]); hi = log(hmcprior.sigBounds[2])
     chainHistBegin!(ctx, targets, nbins, lo, hi)
     return targets, nbins, lo, hi
+end
+
+"""
+    chainAcovBegin!(ctx, targets, maxlag);  chainAcov(ctx, ntarget, maxlag) -> (count, mean[ntarget], acov[ntarget, maxlag + 1])
+    chainEss(ctx, ntarget) -> (tau, ess, window);  chain_ess!(ctx; targets=all cells, maxlag=63) -> (targets, maxlag)
+
+Effective sample size from the chain's commit (hmcmt_chain_acov_*, hmcmt_chain_ess, include/hmcmt.h): per-cell lagged autocovariances of
+ln sigma for the lags 0 .. maxlag (at most 1023), fed by the commits behind the burn-in from the begin call on, and from them the
+integrated autocorrelation time `tau`, the effective sample size `ess` and the `window` of Geyer's initial positive sequence, computed
+on the GPU (window < 0: the lags ran out, tau is a lower bound).  `targets` are 1-based active-cell indices here (0-based in C); an
+empty vector means every active cell.  `acov` comes back in C's lag-major layout, i.e. with Julia's first index running over the
+targets.  Call the begin function behind `chainBegin!` (which ends the accumulator) and in front of the first `chainMomentum!`;
+`chain_ess!` does so with the defaults of the Python sampler.
+"""
+function chainAcovBegin!(ctx::HipContext, targets::Vector{<:Integer}, maxlag::Integer)
+    t0 = Int64.(targets) .- 1
+    ptr = isempty(t0) ? Ptr{Int64}(C_NULL) : pointer(t0)
+    rc = GC.@preserve t0 @ccall libhmcmt.hmcmt_chain_acov_begin(ctx.ptr::Ptr{Cvoid}, Int64(length(t0))::Int64, ptr::Ptr{Int64},
+                                                                Int32(maxlag)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+end
+
+function chainAcov(ctx::HipContext, ntarget::Integer, maxlag::Integer)
+    count = Ref{Int64}(0)
+    mean = Vector{Float64}(undef, ntarget)
+    acov = Matrix{Float64}(undef, ntarget, maxlag + 1)
+    rc = @ccall libhmcmt.hmcmt_chain_acov(ctx.ptr::Ptr{Cvoid}, count::Ref{Int64}, mean::Ptr{Float64}, acov::Ptr{Float64},
+                                          Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return Int(count[]), mean, acov
+end
+
+function chainEss(ctx::HipContext, ntarget::Integer)
+    tau = Vector{Float64}(undef, ntarget); ess = Vector{Float64}(undef, ntarget); window = Vector{Int32}(undef, ntarget)
+    rc = @ccall libhmcmt.hmcmt_chain_ess(ctx.ptr::Ptr{Cvoid}, tau::Ptr{Float64}, ess::Ptr{Float64}, window::Ptr{Int32},
+                                         Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return tau, ess, window
+end
+
+function chain_ess!(ctx::HipContext; targets::Vector{<:Integer}=Int[], maxlag::Integer=63)
+    chainAcovBegin!(ctx, targets, maxlag)
+    return (isempty(targets) ? collect(1:ctx.nAC) : targets), maxlag
 end
 
 """

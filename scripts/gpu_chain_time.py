@@ -6,6 +6,13 @@
   (d) (c) with both accumulators of the commit on: hist={} (every cell, 300 bins) and data_moments=True.  Its figure leaves out the
       one read-back of the counters at the end of the run (timed again on the live chain and reported as d_readback_ms): with a
       handful of samples per run it would otherwise be the figure
+  (e) (c) with the autocovariance accumulator on: ess={} (every cell, 63 lags).  Its figure leaves out the two read-outs at the end
+      of the run (chain_acov and chain_ess, timed again on the live chain and reported apart as e_acov_readout_ms and
+      e_ess_readout_ms), for the same reason.  With a handful of samples per run every commit of (e) has count < maxlag, so most
+      lags still fill their head sums H_k (16 bytes per lag) and the steady branch (ring read, fma into S_k: 24 bytes per lag) is
+      not in (e)'s figure.  It is timed apart: one more chain with ess={} of maxlag + 1 + STEADY samples, with HIP-event pairs round
+      every k_chain_acov launch in place in the commit (hmcmt_debug_chain_acov_time) -> acov_commit_us: the mean per launch of the
+      commits with count < maxlag ("filling") and of those behind them ("steady"), each interval including its two event records
 at cfg3 and cfg5 with bench.py's settings near the true model (L = 8, dt = 0.03), and beside them the floor: L times the per-step
 time bench.py reports for its near_true_state chain in the same session.  Every figure: median of REPS runs of NS samples, with the
 minimum and maximum (the spread).  The requirement read off the log: (b) and (c) are not slower than (a) by more than that spread.
@@ -38,6 +45,9 @@ MODES = {"a_host_loop_device_leapfrog": dict(device_leapfrog=True),
          "c_device_chain_no_samples": dict(device_chain=True, keep_samples=False),
          "d_device_chain_no_samples_hist_data_moments": dict(device_chain=True, keep_samples=False, hist={}, data_moments=True)}
 D = "d_device_chain_no_samples_hist_data_moments"
+E = "e_device_chain_no_samples_ess"
+MAXLAG, STEADY = 63, 24
+MODES[E] = dict(device_chain=True, keep_samples=False, ess={})
 
 
 def one_run(name, kw, ns, seed):
@@ -57,9 +67,41 @@ def one_run(name, kw, ns, seed):
             t1 = time.perf_counter()
             ctx.chain_hist()
             back = time.perf_counter() - t1
+        if kw.get("ess") is not None:                   # ... and the two read-outs, apart
+            t1 = time.perf_counter()
+            ctx.chain_acov()
+            t2 = time.perf_counter()
+            ctx.chain_ess()
+            back = (t2 - t1, time.perf_counter() - t2)
     finally:
         ctx.close()
+    if isinstance(back, tuple):
+        return 1e3 * (dt - sum(back)) / ns, st.nAccept, tuple(1e3 * b for b in back)
     return 1e3 * (dt - back) / ns, st.nAccept, 1e3 * back
+
+
+def commit_time(name, seed):
+    """mean microseconds per k_chain_acov launch, by HIP events in place, over one chain of MAXLAG + 1 + STEADY samples"""
+    mesh, data, inv, _ = make_problem(name)
+    inv.strModel = np.log(S.true_model_sigma(mesh, block=True)[inv.activeIdx])
+    prior = HMCPrior(totalsamples=MAXLAG + 1 + STEADY, burninsamples=0, dt=DT, timestep=[L, L], sigBounds=[1e-4, 1.0], regParam=1.0)
+    ctx = HipContext(mesh, data, inv, device_id=0)
+    try:
+        begin = ctx.chain_acov_begin
+
+        def begin_timed(*a, **k):                       # (the sampler begins the accumulator: the events go on right behind it)
+            begin(*a, **k)
+            ctx.chain_acov_timing(True)
+
+        ctx.chain_acov_begin = begin_timed
+        _, st, _ = sampler.runHMCSampler(mesh, data, inv, prior, np.random.default_rng(seed), rhoref=RHOREF, ctx=ctx,
+                                         device_chain=True, keep_samples=False, ess={"maxlag": MAXLAG})
+        t = ctx.chain_acov_timing()
+    finally:
+        ctx.close()
+    out = {k: {"mean_us": 1e3 * ms / max(n, 1), "launches": n} for k, (ms, n) in t.items()}
+    out.update(ntarget=len(st.ess["targets"]), maxlag=MAXLAG, samples=prior.totalsamples, accepted=st.nAccept)
+    return out
 
 
 def bench_floor(name):
@@ -82,13 +124,15 @@ def main():
     log = open(os.path.join(ROOT, "profiles", "chain_time.log"), "a")
     for name in a.configs:
         ms = {k: [] for k in MODES}
-        acc, back = {}, []
-        for rep in range(a.reps):                       # interleaved: a, b, c, a, b, c, ...
+        acc, back, eback = {}, [], []
+        for rep in range(a.reps):                       # interleaved: a, b, c, d, e, a, b, ...
             for k, kw in MODES.items():
                 t, nacc, rb = one_run(name, kw, a.samples, 100 + rep)
                 ms[k].append(t); acc[k] = nacc
                 if k == D:
                     back.append(rb)
+                if k == E:
+                    eback.append(rb)
                 print(f"{name} rep {rep} {k}: {t:.3f} ms per sample", file=sys.stderr, flush=True)
         line = {"config": name, "argv": sys.argv[1:], "L": L, "dt": DT, "samples_per_run": a.samples, "reps": a.reps, "ms_per_sample": {}}
         for k, v in ms.items():
@@ -102,6 +146,11 @@ def main():
         line["d_minus_c_ms"] = med[D] - med["c_device_chain_no_samples"]
         line["d_within_spread_of_c"] = bool(abs(line["d_minus_c_ms"]) <= spread)
         line["d_readback_ms"] = statistics.median(back)
+        line["e_minus_c_ms"] = med[E] - med["c_device_chain_no_samples"]
+        line["e_within_spread_of_c"] = bool(abs(line["e_minus_c_ms"]) <= spread)
+        line["e_acov_readout_ms"] = statistics.median(b[0] for b in eback)
+        line["e_ess_readout_ms"] = statistics.median(b[1] for b in eback)
+        line["acov_commit_us"] = commit_time(name, 100)
         if not a.no_floor:
             floor, sps = bench_floor(name)
             line["floor_ms_per_sample_L_times_bench_step"] = floor
