@@ -278,6 +278,21 @@ struct hmcmt_ctx {
             double ms[2] = {0, 0};
             long long launches[2] = {0, 0};
         } acov;
+        struct Cov {                                  // hmcmt_chain_cov_*: cross moments of the cells, cell index fastest (hmcmt_items.h)
+            bool on = false;
+            long long nrow = 0, count = 0;
+            int B = 0, npend = 0;                     // batch length; commits in d_pend not yet folded into d_S
+            long long* d_row = nullptr;               // [nrow] active-cell indices; nullptr: every cell, row r = cell r
+            double *d_x0 = nullptr, *d_tot = nullptr, *d_q = nullptr;   // [nAC] pivot, sum of y, sum of y^2
+            double *d_pend = nullptr;                 // [B][nAC]
+            double *d_S = nullptr;                    // [nrow][nAC]
+            // hmcmt_debug_chain_cov_time (measurement only): a pair of events round every k_chain_cov_commit / k_chain_cov_flush launch
+            bool timing = false;
+            std::vector<hipEvent_t> ev;               // pool, two per pending launch
+            std::vector<int> pending;                 // class of each pending launch: 0 commit, 1 flush
+            double ms[2] = {0, 0};
+            long long launches[2] = {0, 0};
+        } cov;
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)

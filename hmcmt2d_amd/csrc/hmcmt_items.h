@@ -991,5 +991,65 @@ HD void item_chain_ess(const double* acov, long long ntarget, int K, long long N
     if (ess) ess[j] = e;
     if (window) window[j] = w;
 }
+// Cross moments of the committed models (hmcmt_chain_cov_*).  Every array has the CELL INDEX FASTEST: the lanes of a wavefront are
+// neighbouring cells a of one row or slot and touch adjacent doubles.  Counted commits are t = 0, 1, ...; y_t[a] = m[a] - x0[a] with
+// x0 the value at t = 0 (one subtraction; y_0 = 0 by definition).  Per cell: tot = sum y_t (serial adds), q = fma(y_t, y_t, q).  Per
+// row r with cell rho = row[r]: S[r][a] = fma(y_t[rho], y_t[a], S[r][a]) over t in commit order.  The commit only parks y_t in the next
+// of B slots pend[b][a]; a flush applies the parked commits to S in slot order, so every S[r][a] sees the same fmas in the same
+// order whatever B is.
+constexpr int CHAIN_COV_BATCH_MAX = 16;
+constexpr int CHAIN_COV_BATCH_DEFAULT = 8;
+constexpr int CHAIN_COV_TILE_COLS = 256;   // k_chain_cov_flush: cells of a workgroup, one per thread
+constexpr int CHAIN_COV_TILE_ROWS = 32;    // ... and the rows it walks; the row panel in LDS is TILE_ROWS x BATCH_MAX doubles (4 KiB)
+// commit t of cell a into the slot `slot` of pend
+HD void item_chain_cov_commit(const double* m, double* x0, double* tot, double* q, double* pend, long long n, long long t, int slot,
+                              long long a) {
+    const double x = m[a];
+    if (t == 0) x0[a] = x;
+    const double y = t == 0 ? 0.0 : x - x0[a];
+    tot[a] += y;
+    q[a] = fma(y, y, q[a]);
+    pend[(long long)slot * n + a] = y;
+}
+// one element of S through a flush of NB parked commits: prow[b] = pend[b][rho], ycol[b] = pend[b][a], in slot order
+template <int NB>
+HD double item_chain_cov_flush(const double* prow, const double* ycol, double s) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) s = fma(prow[b], ycol[b], s);
+    return s;
+}
+// the read-out of N >= 1 commits (dN = (double)N).  Each formula is product, division, subtraction, division: nothing that a
+// compiler could contract into an fma, so the host and the device give the same bits
+HD double item_chain_cov_value(double s, double totr, double tota, double dN) {
+    const double p = totr * tota;
+    const double c = p / dN;
+    const double d = s - c;
+    return d / dN;
+}
+// element (r, a): cov[r][a]; the owner of row 0 also writes mean[a] and var[a] (each output may be nullptr; row == nullptr: row r is
+// cell r)
+HD void item_chain_cov_out(const double* x0, const double* tot, const double* q, const double* S, const long long* row, long long n,
+                           double dN, long long r, long long a, double* mean, double* var, double* cov) {
+    const double ta = tot[a];
+    if (r == 0) {
+        if (mean) mean[a] = x0[a] + ta / dN;
+        if (var) var[a] = item_chain_cov_value(q[a], ta, ta, dN);
+    }
+    if (cov) cov[r * n + a] = item_chain_cov_value(S[r * n + a], tot[row ? row[r] : r], ta, dN);
+}
+// element (r, a) of the correlation: cov / sqrt(var_rho var_a) clamped into [-1, 1]; 0 unless both variances are positive
+HD void item_chain_corr(const double* tot, const double* q, const double* S, const long long* row, long long n, double dN, long long r,
+                        long long a, double* corr) {
+    const long long rho = row ? row[r] : r;
+    const double tr = tot[rho], ta = tot[a];
+    const double vr = item_chain_cov_value(q[rho], tr, tr, dN), va = item_chain_cov_value(q[a], ta, ta, dN);
+    double c = 0.0;
+    if (vr > 0.0 && va > 0.0) {
+        const double vv = vr * va;
+        c = item_chain_cov_value(S[r * n + a], tr, ta, dN) / sqrt(vv);
+        c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+    }
+    corr[r * n + a] = c;
+}
 
 }  // namespace hmcmt

@@ -4,7 +4,8 @@
 // One sample = hmcmt_chain_momentum + hmcmt_chain_step.  What crosses PCIe per sample: nAC normals up, LFNB partial sums and
 // CHAIN_REC scalars down; with outputs, nAC + 2 nData doubles more.  Launches per sample beyond leapfrog_core's (diagonal mass):
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
-// k_chain_hist, a second k_chain_welford (the predicted data) and k_chain_acov (lagged autocovariances) behind them.
+// k_chain_hist, a second k_chain_welford (the predicted data), k_chain_acov (lagged autocovariances) and k_chain_cov_commit (cross
+// moments; every `batch` commits k_chain_cov_flush) behind them.
 
 // measurement only (hmcmt_debug_chain_acov_time): the event pairs round the k_chain_acov launches
 static void chain_acov_time_collect(hmcmt_ctx* ctx) {
@@ -27,12 +28,69 @@ static void chain_acov_time_free(hmcmt_ctx* ctx) {
     A.timing = false;
 }
 
-// ends the commit's optional accumulators (histogram, data moments, autocovariances) and frees their buffers
+// measurement only (hmcmt_debug_chain_cov_time): the event pairs round the k_chain_cov_commit and k_chain_cov_flush launches
+static void chain_cov_time_collect(hmcmt_ctx* ctx) {
+    auto& V = ctx->chain.cov;
+    if (V.pending.empty()) return;
+    (void)hipStreamSynchronize(ctx->stream);
+    for (size_t i = 0; i < V.pending.size(); ++i) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, V.ev[2 * i], V.ev[2 * i + 1]) == hipSuccess) { V.ms[V.pending[i]] += ms; V.launches[V.pending[i]] += 1; }
+    }
+    V.pending.clear();
+}
+static void chain_cov_time_free(hmcmt_ctx* ctx) {
+    auto& V = ctx->chain.cov;
+    if (V.ev.empty()) return;
+    hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (hipEvent_t e : V.ev) hipEventDestroy(e);
+    V.ev.clear(); V.pending.clear();
+    V.timing = false;
+}
+// the first event of the next pair of the pool, recorded (false: not timing, or no event to be had); chain_cov_time_stop closes it
+static bool chain_cov_time_start(hmcmt_ctx* ctx) {
+    auto& V = ctx->chain.cov;
+    if (!V.timing) return false;
+    if (V.pending.size() >= 1024) chain_cov_time_collect(ctx);
+    const size_t i = V.pending.size();
+    while (V.ev.size() < 2 * i + 2) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return false; } V.ev.push_back(e); }
+    hipEventRecord(V.ev[2 * i], ctx->stream);
+    return true;
+}
+static void chain_cov_time_stop(hmcmt_ctx* ctx, int cls) {
+    auto& V = ctx->chain.cov;
+    hipEventRecord(V.ev[2 * V.pending.size() + 1], ctx->stream);
+    V.pending.push_back(cls);
+}
+
+// folds the parked commits into S (enqueued): the commit calls it when the batch is full, a read-out when any is parked
+static void chain_cov_flush(hmcmt_ctx* ctx) {
+    auto& V = ctx->chain.cov;
+    if (V.npend == 0) return;
+    const bool timed = chain_cov_time_start(ctx);
+    const long long n = ctx->v.nAC, tiles = (V.nrow + CHAIN_COV_TILE_ROWS - 1) / CHAIN_COV_TILE_ROWS;
+    const dim3 grid((unsigned)((n + CHAIN_COV_TILE_COLS - 1) / CHAIN_COV_TILE_COLS), (unsigned)std::min<long long>(tiles, 32768));
+    static_assert(CHAIN_COV_BATCH_MAX == 16, "one instantiation of k_chain_cov_flush per batch length below");
+    switch (V.npend) {
+#define HMCMT_COV_FLUSH(NB) \
+    case NB: hipLaunchKernelGGL(k_chain_cov_flush<NB>, grid, dim3(CHAIN_COV_TILE_COLS), 0, ctx->stream, n, V.nrow, V.d_row, V.d_pend, V.d_S); break;
+        HMCMT_COV_FLUSH(1) HMCMT_COV_FLUSH(2) HMCMT_COV_FLUSH(3) HMCMT_COV_FLUSH(4) HMCMT_COV_FLUSH(5) HMCMT_COV_FLUSH(6)
+        HMCMT_COV_FLUSH(7) HMCMT_COV_FLUSH(8) HMCMT_COV_FLUSH(9) HMCMT_COV_FLUSH(10) HMCMT_COV_FLUSH(11) HMCMT_COV_FLUSH(12)
+        HMCMT_COV_FLUSH(13) HMCMT_COV_FLUSH(14) HMCMT_COV_FLUSH(15) HMCMT_COV_FLUSH(16)
+#undef HMCMT_COV_FLUSH
+    }
+    if (timed) chain_cov_time_stop(ctx, 1);
+    V.npend = 0;
+}
+
+// ends the commit's optional accumulators (histogram, data moments, autocovariances, cross moments) and frees their buffers
 static void chain_acc_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     void* bufs[] = {C.hist.d_target, C.hist.d_counts, C.dmom.d_mean, C.dmom.d_m2, C.acov.d_target, C.acov.d_x0, C.acov.d_tot,
-                    C.acov.d_S, C.acov.d_H, C.acov.d_ring};
+                    C.acov.d_S, C.acov.d_H, C.acov.d_ring, C.cov.d_row, C.cov.d_x0, C.cov.d_tot, C.cov.d_q, C.cov.d_pend, C.cov.d_S};
     chain_acov_time_free(ctx);
+    chain_cov_time_free(ctx);
     bool any = false;
     for (void* p : bufs) any = any || p;
     if (any) {
@@ -43,6 +101,7 @@ static void chain_acc_release(hmcmt_ctx* ctx) {
     C.hist = hmcmt_ctx::Chain::Hist{};
     C.dmom = hmcmt_ctx::Chain::DataMoments{};
     C.acov = hmcmt_ctx::Chain::Acov{};
+    C.cov = hmcmt_ctx::Chain::Cov{};
 }
 
 static void chain_release(hmcmt_ctx* ctx) {
@@ -270,6 +329,15 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
                                A.ntarget, A.K, A.count, C.d_m[C.cur], A.d_target, A.d_x0, A.d_tot, A.d_S, A.d_H, A.d_ring);
             if (timed) { hipEventRecord(A.ev[2 * A.pending.size() + 1], st); A.pending.push_back(A.count >= A.K ? 1 : 0); }
             ++A.count;
+        }
+        if (C.cov.on) {
+            auto& V = C.cov;                                 // (t = the count before this commit; the slot = the commits parked so far)
+            const bool timed = chain_cov_time_start(ctx);
+            hipLaunchKernelGGL(k_chain_cov_commit, dim3((n + 255) / 256), dim3(256), 0, st, (long long)n, V.count, V.npend, C.d_m[C.cur],
+                               V.d_x0, V.d_tot, V.d_q, V.d_pend);
+            if (timed) chain_cov_time_stop(ctx, 0);
+            ++V.count;
+            if (++V.npend == V.B) chain_cov_flush(ctx);
         }
     }
     C.gen = ctx->stateGen;
@@ -644,6 +712,158 @@ int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int6
     if (enable >= 0) {                                       // (the sums up to here went out; a switch starts new ones)
         A.timing = enable != 0;
         for (int i = 0; i < 2; ++i) { A.ms[i] = 0; A.launches[i] = 0; }
+    }
+    return 0;
+}
+
+// ---- posterior covariance and correlation (k_chain_cov_commit, k_chain_cov_flush, k_chain_cov_out, k_chain_corr) --------------------
+static void chain_cov_free(hmcmt_ctx* ctx) {
+    auto& V = ctx->chain.cov;
+    chain_cov_time_free(ctx);
+    for (void* p : {(void*)V.d_row, (void*)V.d_x0, (void*)V.d_tot, (void*)V.d_q, (void*)V.d_pend, (void*)V.d_S}) if (p) hipFree(p);
+    V = hmcmt_ctx::Chain::Cov{};
+}
+
+int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* row, int32_t batch) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_cov_begin", true);
+    if (rc) return rc;
+    static_assert(CHAIN_COV_BATCH_MAX == HMCMT_COV_BATCH_MAX, "the header's bound is the kernels'");
+    const int n = ctx->v.nAC;
+    const bool all = !row && nrow == 0;
+    if ((!all && (!row || nrow < 1)) || batch < 0 || batch > CHAIN_COV_BATCH_MAX) {
+        ctx->err = "hmcmt_chain_cov_begin: need row and nrow >= 1 (or NULL and 0: every active cell) and 1 <= batch <= 16 (0: the default, 8)";
+        return HMCMT_EINVAL;
+    }
+    for (int64_t i = 0; i < nrow; ++i)
+        if (row[i] < 0 || row[i] >= n) {
+            ctx->err = "hmcmt_chain_cov_begin: row " + std::to_string(i) + " = " + std::to_string(row[i]) + " is no active cell (0.." +
+                       std::to_string(n - 1) + ")";
+            return HMCMT_EINVAL;
+        }
+    HIPCHK(hipSetDevice(ctx->device));
+    auto& V = ctx->chain.cov;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be adding to the accumulator this one replaces)
+    chain_cov_free(ctx);
+    const long long nr = all ? n : nrow;
+    const int B = batch == 0 ? CHAIN_COV_BATCH_DEFAULT : batch;
+    const size_t rb = (size_t)nr * sizeof(long long), vb = (size_t)n * sizeof(double);
+    auto build = [&]() -> int {
+        int r;
+        if (!all && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov_begin", (void**)&V.d_row, rb))) return r;
+        const std::pair<double**, size_t> bufs[] = {{&V.d_x0, vb}, {&V.d_tot, vb}, {&V.d_q, vb}, {&V.d_pend, vb * (size_t)B}, {&V.d_S, vb * (size_t)nr}};
+        for (const auto& b : bufs) {
+            if ((r = chain_acc_alloc(ctx, "hmcmt_chain_cov_begin", (void**)b.first, b.second))) return r;
+            HIPCHK(hipMemsetAsync(*b.first, 0, b.second, st));
+        }
+        static_assert(sizeof(long long) == sizeof(int64_t), "the row list is uploaded as it is");
+        if (!all) HIPCHK(hipMemcpyAsync(V.d_row, row, rb, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));                    // (the caller's list is free again on return)
+        return 0;
+    };
+    if ((rc = build())) {
+        (void)hipStreamSynchronize(st);
+        chain_cov_free(ctx);
+        return rc;
+    }
+    V.nrow = nr; V.B = B; V.npend = 0; V.count = 0;
+    V.on = true;
+    return 0;
+}
+
+static dim3 chain_cov_grid(hmcmt_ctx* ctx, long long nrow) {
+    return dim3((unsigned)((ctx->v.nAC + 255) / 256), (unsigned)std::min<long long>(nrow, 32768));
+}
+
+int hmcmt_chain_cov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* var, double* cov, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_cov", true);
+    if (rc) return rc;
+    auto& V = ctx->chain.cov;
+    if (!V.on) { ctx->err = "hmcmt_chain_cov: no covariance (hmcmt_chain_cov_begin first)"; return HMCMT_EINVAL; }
+    if ((mean || var || cov) && V.count == 0) { ctx->err = "hmcmt_chain_cov: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const long long n = ctx->v.nAC;
+    const size_t mb = sizeof(double) * (size_t)n, cb = mb * (size_t)V.nrow;
+    double *d_mean = nullptr, *d_var = nullptr, *d_cov = nullptr;
+    auto run = [&]() -> int {
+        int r;
+        if (!mean && !var && !cov) return 0;
+        if (on_device) { d_mean = mean; d_var = var; d_cov = cov; }
+        else {
+            if (mean && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov", (void**)&d_mean, mb))) return r;
+            if (var && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov", (void**)&d_var, mb))) return r;
+            if (cov && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov", (void**)&d_cov, cb))) return r;
+        }
+        if (cov) chain_cov_flush(ctx);                       // (the parked commits first: the later bits stay what they would have been)
+        const long long rows = cov ? V.nrow : 1;             // (row 0's owners write mean and var)
+        hipLaunchKernelGGL(k_chain_cov_out, chain_cov_grid(ctx, rows), dim3(256), 0, st, n, rows, (double)V.count, V.d_x0, V.d_tot, V.d_q,
+                           V.d_S, V.d_row, d_mean, d_var, d_cov);
+        HIPCHK(hipGetLastError());
+        if (!on_device) {
+            if (mean) HIPCHK(hipMemcpyAsync(mean, d_mean, mb, hipMemcpyDeviceToHost, st));
+            if (var) HIPCHK(hipMemcpyAsync(var, d_var, mb, hipMemcpyDeviceToHost, st));
+            if (cov) HIPCHK(hipMemcpyAsync(cov, d_cov, cb, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st);
+    if (!on_device) { if (d_mean) hipFree(d_mean); if (d_var) hipFree(d_var); if (d_cov) hipFree(d_cov); }
+    if (!rc && count) *count = V.count;
+    return rc;
+}
+
+int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device) {
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, "hmcmt_chain_corr", true);
+    if (rc) return rc;
+    auto& V = ctx->chain.cov;
+    if (!V.on) { ctx->err = "hmcmt_chain_corr: no covariance (hmcmt_chain_cov_begin first)"; return HMCMT_EINVAL; }
+    if (V.count == 0) { ctx->err = "hmcmt_chain_corr: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    if (!corr) return 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const long long n = ctx->v.nAC;
+    const size_t cb = sizeof(double) * (size_t)n * (size_t)V.nrow;
+    double* d_corr = nullptr;
+    auto run = [&]() -> int {
+        int r;
+        if (on_device) d_corr = corr;
+        else if ((r = chain_acc_alloc(ctx, "hmcmt_chain_corr", (void**)&d_corr, cb))) return r;
+        chain_cov_flush(ctx);
+        hipLaunchKernelGGL(k_chain_corr, chain_cov_grid(ctx, V.nrow), dim3(256), 0, st, n, V.nrow, (double)V.count, V.d_tot, V.d_q, V.d_S,
+                           V.d_row, d_corr);
+        HIPCHK(hipGetLastError());
+        if (!on_device) HIPCHK(hipMemcpyAsync(corr, d_corr, cb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    rc = run();
+    if (rc) (void)hipStreamSynchronize(st);
+    if (!on_device && d_corr) hipFree(d_corr);
+    return rc;
+}
+
+// measurement only (include/hmcmt_debug.h)
+int hmcmt_debug_chain_cov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, "hmcmt_debug_chain_cov_time", true);
+    if (rc) return rc;
+    auto& V = ctx->chain.cov;
+    if (!V.on) { ctx->err = "hmcmt_debug_chain_cov_time: no covariance (hmcmt_chain_cov_begin first)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    chain_cov_time_collect(ctx);
+    for (int i = 0; i < 2; ++i) {
+        if (ms) ms[i] = V.ms[i];
+        if (launches) launches[i] = V.launches[i];
+    }
+    if (enable >= 0) {                                       // (the sums up to here went out; a switch starts new ones)
+        V.timing = enable != 0;
+        for (int i = 0; i < 2; ++i) { V.ms[i] = 0; V.launches[i] = 0; }
     }
     return 0;
 }

@@ -101,3 +101,57 @@ __global__ __launch_bounds__(256) void k_chain_ess(long long ntarget, int K, lon
     const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
     if (j < ntarget) item_chain_ess(acov, ntarget, K, N, cap, capTau, j, tau, ess, window);
 }
+// one counted commit of the cross-moment accumulator: thread a owns cell a's pivot, sums and its double in the slot of this commit
+__global__ __launch_bounds__(256) void k_chain_cov_commit(long long n, long long t, int slot, const double* __restrict__ m,
+                                                          double* __restrict__ x0, double* __restrict__ tot, double* __restrict__ q,
+                                                          double* __restrict__ pend) {
+    const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (a < n) item_chain_cov_commit(m, x0, tot, q, pend, n, t, slot, a);
+}
+// the rank-NB update of S from the parked commits.  A workgroup owns the tile rows [blockIdx.y * TILE_ROWS, ...) x cells
+// [blockIdx.x * TILE_COLS, ...); thread = one cell a, so a wavefront reads and writes 512 contiguous bytes of one row of S.  The
+// thread keeps pend[0 .. NB)[a] in registers; the rows' values pend[b][rho] are the same for every lane and come from a panel in
+// LDS ([row of the tile][b]: one address per read, a broadcast).  Every S[r][a] has this one owner, which applies its NB fmas in slot
+// order: no atomics, and the bits do not depend on how the commits were cut into flushes.  16 bytes of traffic per element against
+// 2 NB flops: plain fp64 FMA.
+template <int NB>
+__global__ __launch_bounds__(CHAIN_COV_TILE_COLS) void k_chain_cov_flush(long long n, long long nrow, const long long* __restrict__ row,
+                                                                         const double* __restrict__ pend, double* __restrict__ S) {
+    __shared__ double panel[CHAIN_COV_TILE_ROWS * NB];
+    const long long a = (long long)blockIdx.x * CHAIN_COV_TILE_COLS + threadIdx.x;
+    double ycol[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) ycol[b] = a < n ? pend[(long long)b * n + a] : 0.0;
+    // (blockIdx.y strides over the row tiles: the same trips for every thread of the workgroup, so the barriers are met by all)
+    for (long long r0 = (long long)blockIdx.y * CHAIN_COV_TILE_ROWS; r0 < nrow; r0 += (long long)gridDim.y * CHAIN_COV_TILE_ROWS) {
+        const int nr = (int)(nrow - r0 < CHAIN_COV_TILE_ROWS ? nrow - r0 : CHAIN_COV_TILE_ROWS);
+        for (int i = threadIdx.x; i < nr * NB; i += CHAIN_COV_TILE_COLS) {
+            const int r = i / NB, b = i - r * NB;
+            const long long rho = row ? row[r0 + r] : r0 + r;
+            panel[i] = pend[(long long)b * n + rho];
+        }
+        __syncthreads();
+        if (a < n) {
+            double* s = S + r0 * n + a;
+#pragma unroll 4
+            for (int r = 0; r < nr; ++r) s[(long long)r * n] = item_chain_cov_flush<NB>(panel + r * NB, ycol, s[(long long)r * n]);
+        }
+        __syncthreads();
+    }
+}
+// cov[r][a], and from row 0's owners mean[a] and var[a]: blockIdx.y strides over the rows
+__global__ __launch_bounds__(256) void k_chain_cov_out(long long n, long long nrow, double dN, const double* __restrict__ x0,
+                                                       const double* __restrict__ tot, const double* __restrict__ q,
+                                                       const double* __restrict__ S, const long long* __restrict__ row,
+                                                       double* __restrict__ mean, double* __restrict__ var, double* __restrict__ cov) {
+    const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    for (long long r = blockIdx.y; r < nrow; r += gridDim.y) item_chain_cov_out(x0, tot, q, S, row, n, dN, r, a, mean, var, cov);
+}
+__global__ __launch_bounds__(256) void k_chain_corr(long long n, long long nrow, double dN, const double* __restrict__ tot,
+                                                    const double* __restrict__ q, const double* __restrict__ S,
+                                                    const long long* __restrict__ row, double* __restrict__ corr) {
+    const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (a >= n) return;
+    for (long long r = blockIdx.y; r < nrow; r += gridDim.y) item_chain_corr(tot, q, S, row, n, dN, r, a, corr);
+}

@@ -379,3 +379,26 @@ def getESSModel(path, ess_stats, mtMesh, invParam, write=True):
         mtMesh.sigma = sigma
         writeEMModel2D(path, mtMesh)
     return ess
+
+
+def getCorrelationModel(path, cov_stats, r, mtMesh, invParam, write=True):
+    """Row r's correlation map as a .model file: cov_stats = hmcstats.cov of runHMCSampler(device_chain=True, cov={...}) (or
+    sampler.mergeCov / sampler.covOf), r an index into its rows.  Every active cell holds its posterior correlation with the cell
+    cov_stats["rows"][r] (1.0 at that cell itself, values in [-1, 1]) on top of the background, the way getESSModel writes its map.
+    Returns corr[nparam]."""
+    nparam = len(invParam.activeIdx)
+    corr = np.asarray(cov_stats["corr"], dtype=np.float64)
+    if corr.ndim != 2 or corr.shape[1] != nparam or not 0 <= int(r) < corr.shape[0]:
+        raise ValueError("getCorrelationModel: needs corr[nrow, nparam] over every active cell and 0 <= r < nrow")
+    row = corr[int(r)].copy()
+    if write:
+        sigma = invParam.bgModel.copy(); sigma[invParam.activeIdx] += row
+        mtMesh.sigma = sigma
+        writeEMModel2D(path, mtMesh)
+    return row
+
+
+def readCorrelationModel(path, invParam):
+    """The map getCorrelationModel wrote, back as corr[nparam] (to the three digits a .model file keeps)."""
+    sigma = readEMModel2D(path).sigma
+    return sigma[invParam.activeIdx] - invParam.bgModel[invParam.activeIdx]

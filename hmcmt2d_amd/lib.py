@@ -152,7 +152,7 @@ def load_library():
     for name in ("hmcmt_jvp_block", "hmcmt_jtvp_block", "hmcmt_gn_hessvec_block"):
         getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(Stats)]
         getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(Stats)]
-    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS:
+    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib.hmcmt_chain_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -172,6 +172,11 @@ def load_library():
     lib.hmcmt_chain_ess.argtypes = [vp, vp, vp, vp, C.c_int32]
     lib.hmcmt_debug_chain_acov_time.argtypes = [vp, C.c_int32, c_double_p, c_int64_p]
     lib.hmcmt_debug_chain_acov_time.restype = C.c_int
+    lib.hmcmt_chain_cov_begin.argtypes = [vp, C.c_int64, c_int64_p, C.c_int32]
+    lib.hmcmt_chain_cov.argtypes = [vp, C.POINTER(C.c_int64), vp, vp, vp, C.c_int32]
+    lib.hmcmt_chain_corr.argtypes = [vp, vp, C.c_int32]
+    lib.hmcmt_debug_chain_cov_time.argtypes = [vp, C.c_int32, c_double_p, c_int64_p]
+    lib.hmcmt_debug_chain_cov_time.restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
@@ -201,8 +206,11 @@ HIST_MAXBINS = 4096   # include/hmcmt.h: nbins of hmcmt_chain_hist_begin
 # ... and the third one: lagged autocovariances, integrated autocorrelation time and effective sample size
 CHAIN_ACOV_SYMBOLS = ["hmcmt_chain_acov_begin", "hmcmt_chain_acov", "hmcmt_chain_ess"]
 ACOV_MAXLAG = 1023    # include/hmcmt.h: maxlag of hmcmt_chain_acov_begin
+# ... and the fourth one: posterior covariance and correlation between cells
+CHAIN_COV_SYMBOLS = ["hmcmt_chain_cov_begin", "hmcmt_chain_cov", "hmcmt_chain_corr"]
+COV_BATCH_MAX = 16    # include/hmcmt.h: HMCMT_COV_BATCH_MAX
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -212,7 +220,8 @@ PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_
 DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead", "hmcmt_dims",
                  "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond", "hmcmt_debug_fdm_fwd",
                  "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_debug_hog", "hmcmt_persist_envelope",
-                 "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time"]
+                 "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time",
+                 "hmcmt_debug_chain_cov_time"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -789,6 +798,64 @@ class HipContext:
         tau, ess, window = np.empty(nt), np.empty(nt), np.empty(nt, dtype=np.int32)
         self._check(self.lib.hmcmt_chain_ess(self.h, tau.ctypes.data, ess.ctypes.data, window.ctypes.data, 0))
         return tau, ess, window
+
+    # -- posterior covariance and correlation from the chain's commit (hmcmt_chain_cov_*, hmcmt_chain_corr) --
+    def chain_cov_begin(self, rows=None, batch=0):
+        """Starts the cross moments of ln sigma between the active-cell indices `rows` (0-based, repeats allowed; None: every active
+        cell, the full matrix) and every active cell: every later commit behind the burn-in counts.  `batch` commits (1 .. 16, 0: the
+        default 8) are folded into the sums by one kernel; the results do not depend on it.  Replaces an accumulator that is running."""
+        if rows is None:
+            self._check(self.lib.hmcmt_chain_cov_begin(self.h, 0, None, int(batch)))
+            nr = self.nAC
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            if len(r) == 0:
+                raise ValueError("chain_cov_begin: no row (None means every active cell)")
+            self._check(self.lib.hmcmt_chain_cov_begin(self.h, len(r), r.ctypes.data_as(c_int64_p), int(batch)))
+            nr = len(r)
+        self._cov_shape = (nr, self.nAC)
+
+    def chain_cov_count(self):
+        """Commits in the accumulator (the read-outs need at least one)."""
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_cov(self.h, C.byref(n), None, None, None, 0))
+        return int(n.value)
+
+    def chain_cov_timing(self, enable=None):
+        """Measurement only (hmcmt_debug_chain_cov_time): enable = True / False switches HIP-event pairs round every commit and flush
+        kernel of the accumulator on / off and zeroes the sums, None only reads.  Returns the sums up to the call:
+        {"commit": (ms, launches), "flush": (ms, launches)}."""
+        ms, n = np.zeros(2), np.zeros(2, dtype=np.int64)
+        self._check(self.lib.hmcmt_debug_chain_cov_time(self.h, -1 if enable is None else int(bool(enable)), _dp(ms),
+                                                        n.ctypes.data_as(c_int64_p)))
+        return {"commit": (float(ms[0]), int(n[0])), "flush": (float(ms[1]), int(n[1]))}
+
+    def chain_cov(self):
+        """(count, mean[nAC], var[nAC], cov[nrow, nAC]): commits in the accumulator, the cells' means and biased variances, and the
+        biased covariance of every row's cell with every cell (include/hmcmt.h)."""
+        n = C.c_int64()
+        self.chain_cov_count()
+        shape = self._cov_shape
+        mean, var, cov = np.empty(shape[1]), np.empty(shape[1]), np.empty(shape)
+        self._check(self.lib.hmcmt_chain_cov(self.h, C.byref(n), mean.ctypes.data, var.ctypes.data, cov.ctypes.data, 0))
+        return int(n.value), mean, var, cov
+
+    def chain_cov_device(self, d_mean=None, d_var=None, d_cov=None):
+        """The same into device pointers (int; each may be None) to nAC, nAC and nrow * nAC doubles; returns count."""
+        n = C.c_int64()
+        self._check(self.lib.hmcmt_chain_cov(self.h, C.byref(n), d_mean, d_var, d_cov, 1))
+        return int(n.value)
+
+    def chain_corr(self, d_corr=None):
+        """corr[nrow, nAC] = cov / sqrt(var_row var_cell) clamped into [-1, 1], 0 where a variance is not positive, computed on the
+        device -- or, with the device pointer (int) given, into that, returning None."""
+        if d_corr is not None:
+            self._check(self.lib.hmcmt_chain_corr(self.h, d_corr, 1))
+            return None
+        self.chain_cov_count()
+        corr = np.empty(self._cov_shape)
+        self._check(self.lib.hmcmt_chain_corr(self.h, corr.ctypes.data, 0))
+        return corr
 
     # -- instrumentation ----------------------------------------------------------------------
     def profile(self, enable=True, every=1):

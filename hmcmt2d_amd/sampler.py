@@ -565,7 +565,60 @@ def mergeAcov(list_of_ess):
             "window": np.where(moved, window, 0).astype(np.int32)}
 
 
-def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False, ess=None):
+def _corr_of(cov, var, rows):
+    """cov / sqrt(var_row var_cell) clamped into [-1, 1]; 0 where a variance is not positive (hmcmt_chain_corr's rule)"""
+    vr, va = np.asarray(var)[rows][:, None], np.asarray(var)[None, :]
+    ok = (vr > 0.0) & (va > 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = np.where(ok, cov / np.sqrt(np.where(ok, vr * va, 1.0)), 0.0)
+    return np.clip(c, -1.0, 1.0)
+
+
+def covOf(x, rows=None):
+    """The library's covariance estimator (hmcmt_chain_cov, include/hmcmt.h) from a sample history x[nparam, N] (rows = cells, columns =
+    samples, as hmcmodel): the biased two-pass cov[r, a] = (1/N) sum_t (x[rows[r], t] - xbar[rows[r]]) (x[a, t] - xbar[a]) of the cells
+    `rows` (0-based; None: every cell, the full matrix) with every cell.  Returns a dict like hmcstats.cov: count, rows, mean[nparam],
+    var[nparam], cov[nrow, nparam], corr[nrow, nparam]."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("covOf: needs x[nparam, N] with at least one sample")
+    n, N = x.shape
+    r = np.arange(n, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    mean = x.mean(axis=1)
+    d = x - mean[:, None]
+    var = (d * d).sum(axis=1) / N
+    cov = (d[r] @ d.T) / N
+    return {"count": N, "rows": r, "mean": mean, "var": var, "cov": cov, "corr": _corr_of(cov, var, r)}
+
+
+def mergeCov(list_of_cov):
+    """Pools the hmcstats.cov (or covOf) of several chains over the same rows: N = sum N_c, xbar = sum N_c xbar_c / N and, with
+    d_c = xbar_c - xbar, cov = sum N_c (cov_c + d_c[rows] d_c[cells]) / N (var likewise); corr is recomputed from the pooled cov and
+    var.  Chains of different rows or sizes: ValueError.  Returns a dict: count, nchains, rows, mean, var, cov, corr."""
+    chains = [c for c in list_of_cov if c is not None and int(c["count"]) > 0]
+    if not chains:
+        raise ValueError("mergeCov: no chain with a counted sample")
+    r = np.asarray(chains[0]["rows"], dtype=np.int64)
+    for c in chains[1:]:
+        if not np.array_equal(np.asarray(c["rows"]), r) or np.shape(c["cov"]) != np.shape(chains[0]["cov"]):
+            raise ValueError("mergeCov: the chains differ in rows or size")
+    Ns = np.array([float(c["count"]) for c in chains])
+    N = Ns.sum()
+    means = np.array([np.asarray(c["mean"], dtype=np.float64) for c in chains])
+    mean = (Ns[:, None] * means).sum(axis=0) / N
+    var, cov = np.zeros_like(mean), np.zeros(np.shape(chains[0]["cov"]))
+    for Nc, mc, c in zip(Ns, means, chains):
+        d = mc - mean
+        var += Nc * (np.asarray(c["var"], dtype=np.float64) + d * d)
+        cov += Nc * (np.asarray(c["cov"], dtype=np.float64) + d[r][:, None] * d[None, :])
+    var /= N
+    cov /= N
+    return {"count": int(round(N)), "nchains": len(chains), "rows": r.copy(), "mean": mean, "var": var, "cov": cov,
+            "corr": _corr_of(cov, var, r)}
+
+
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False, ess=None,
+                      cov=None):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals."""
@@ -602,6 +655,9 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
         ess_targets = None if ess.get("targets") is None else np.asarray(ess["targets"], dtype=np.int64)
         maxlag = int(ess.get("maxlag", 63))
         ctx.chain_acov_begin(ess_targets, maxlag)
+    if cov is not None:
+        cov_rows = None if cov.get("rows") is None else np.asarray(cov["rows"], dtype=np.int64)
+        ctx.chain_cov_begin(cov_rows, int(cov.get("batch", 0)))
     startK = ctx.chain_momentum(z)
     nsamples = hmcprior.totalsamples
     nkeep = nsamples if keep_samples else 0
@@ -645,12 +701,19 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
             a = acovOf(D, maxlag)
             t1, e1, w1 = essFromAcov(a, len(D))
             stats.ess["misfit"] = {"count": len(D), "mean": float(D.mean()), "acov": a, "tau": t1, "ess": e1, "window": w1}
+    if cov is not None:
+        # (as for ess: a chain that ends inside its burn-in has counted nothing)
+        count = ctx.chain_cov_count()
+        (_, mean, var, c), corr = (ctx.chain_cov(), ctx.chain_corr()) if count > 0 else ((0, None, None, None), None)
+        stats.cov = {"count": count, "rows": np.arange(nparam, dtype=np.int64) if cov_rows is None else cov_rows.copy(),
+                     "mean": mean, "var": var, "cov": c, "corr": corr}
     return hmcmodel, stats, hmcdata
 
 
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
-                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None):
+                  checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
+                  cov=None):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -672,6 +735,12 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     `maxlag` (63).  hmcstats.ess is a dict: count, maxlag, targets, mean, acov[maxlag + 1, ntarget], tau, ess, window (hmcmt_chain_ess,
     include/hmcmt.h: window < 0 means the lags ran out and tau is a lower bound), and `misfit`, the same estimator applied here to the
     data misfit of the counted samples.  A chain that ends inside its burn-in gives count 0 and None for the rest.  See acovOf, essFromAcov, mcseOfMean, mergeAcov, fileio.getESSModel.  The draws keep their order.
+    `cov={...}` (with device_chain): the posterior covariance and correlation between cells, streamed in the commit as cross moments
+    and folded in by a batched kernel, so that trade-offs between cells need no sample history.  Keys, both optional: `rows` (the
+    active-cell indices whose rows of the matrix are kept; default every cell, the full nparam x nparam matrix) and `batch` (commits
+    per update kernel, 1 .. 16, default 8; the results do not depend on it).  hmcstats.cov is a dict: count, rows, mean[nparam],
+    var[nparam], cov[nrow, nparam], corr[nrow, nparam] (biased estimator; hmcmt_chain_cov, include/hmcmt.h).  A chain that ends inside
+    its burn-in gives count 0 and None for the rest.  See covOf, mergeCov, fileio.getCorrelationModel.  The draws keep their order.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -691,14 +760,17 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
         raise ValueError("runHMCSampler: hist and data_moments need device_chain=True (they are streamed in the device chain's commit)")
     if ess is not None and not device_chain:
         raise ValueError("runHMCSampler: ess needs device_chain=True (the autocovariances are streamed in the device chain's commit)")
-    for name, given, keys in (("hist", hist, ("targets", "nbins", "lo", "hi")), ("ess", ess, ("targets", "maxlag"))):
+    if cov is not None and not device_chain:
+        raise ValueError("runHMCSampler: cov needs device_chain=True (the cross moments are streamed in the device chain's commit)")
+    for name, given, keys in (("hist", hist, ("targets", "nbins", "lo", "hi")), ("ess", ess, ("targets", "maxlag")),
+                              ("cov", cov, ("rows", "batch"))):
         unknown = set(given or ()) - set(keys)                 # (before the context is touched and the first number is drawn)
         if unknown:
             raise ValueError(f"runHMCSampler: {name} has no key {sorted(unknown)} ({', '.join(keys)})")
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments, ess)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments, ess, cov)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -803,7 +875,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     (hmcmt_allgather_samples, include/hmcmt.h -- what a non-Python host would call) instead of torch's; the process
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
-    `path.chain<k>` per chain; device_chain=True, keep_samples=False, hist=..., ess=...).
+    `path.chain<k>` per chain; device_chain=True, keep_samples=False, hist=..., ess=..., cov=...).
     Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
     count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
     gelmanRubin).  A chain's block in the gather is, in doubles,
@@ -952,6 +1024,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                 hmcstats[c].moments = (int(round(buf[o])), buf[o + 1:o + 1 + nparam].copy(), buf[o + 1 + nparam:o + 1 + 2 * nparam].copy())
             if c in results:                                # (ess= is not gathered: a chain's own rank keeps it, for mergeAcov)
                 hmcstats[c].ess = getattr(results[c][1], "ess", None)
+                hmcstats[c].cov = getattr(results[c][1], "cov", None)     # (nor is cov=: see mergeCov)
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

@@ -89,6 +89,7 @@ class HMCStatus:
     hist: object = None           # (count, counts[ntarget, nbins], (nbins, lo, hi), targets): runHMCSampler(device_chain=True, hist=...)
     dataMoments: object = None    # (count, mean[ndata], m2[ndata]) of the predicted data: runHMCSampler(..., data_moments=True)
     ess: object = None            # dict count, maxlag, targets, mean, acov, tau, ess, window, misfit: runHMCSampler(..., ess=...)
+    cov: object = None            # dict count, rows, mean, var, cov, corr: runHMCSampler(..., cov=...)
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

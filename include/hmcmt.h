@@ -323,6 +323,38 @@ extern int hmcmt_chain_acov_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t
 extern int hmcmt_chain_acov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* acov, int32_t on_device);
 extern int hmcmt_chain_ess(hmcmt_ctx* ctx, double* tau, double* ess, int32_t* window, int32_t on_device);
 
+/* Posterior covariance and correlation from the chain's commit (optional, a fourth accumulator under the rules above: fed by the
+ * commits behind the burn-in from its begin call on, a rejection's repeat included, with its own count N; nothing above changes
+ * when it is off, and every record, model, moment, histogram and autocovariance keeps its bits when it is on).
+ *   hmcmt_chain_cov_begin  cross moments of m = ln sigma between the cells row[nrow] (0-based active-cell indices, repeats allowed
+ *                         and rows of their own) and every active cell; row = NULL with nrow = 0: every active cell in order, the
+ *                         full matrix.  batch = 1 .. HMCMT_COV_BATCH_MAX commits are parked before one kernel folds them into S
+ *                         (0: the default, 8); the results do not depend on it, bit for bit.  Counted commits are t = 0, 1, ...;
+ *                         per cell a, with the pivot x0[a] = the value at t = 0 and y_t[a] = m[a] - x0[a] (one subtraction), the
+ *                         device holds
+ *                             tot[a] = sum y_t[a] (serial adds),  q[a] = fma(y_t[a], y_t[a], q[a]),
+ *                             S[r][a] = fma(y_t[row[r]], y_t[a], S[r][a])  in commit order,  and the y of up to `batch` commits
+ *                         -- about 8 (nrow + batch + 3) nAC bytes, zeroed here.  On HMCMT_ENOMEM the chain goes on without the
+ *                         accumulator.  A second call replaces the first accumulator
+ *   hmcmt_chain_cov       count = N, mean[nAC], var[nAC], cov[nrow][nAC] (row-major; each may be NULL); on_device as for
+ *                         hmcmt_chain_acov; complete on return.  With N as a double and rho = row[r]:
+ *                             mean[a] = x0[a] + tot[a] / N,   var[a] = (q[a] - (tot[a] tot[a]) / N) / N,
+ *                             cov[r][a] = (S[r][a] - (tot[rho] tot[a]) / N) / N
+ *                         -- the biased estimator (1/N) sum (x_rho - xbar_rho)(x_a - xbar_a), the convention of c_0 above.
+ *                         cov[r][row[r]] == var[row[r]] bitwise; with the full matrix cov equals its transpose bitwise; a cell that
+ *                         never moved gives exact zeros in its row and column.  HMCMT_EINVAL when N = 0 and an array is asked for
+ *   hmcmt_chain_corr      corr[nrow][nAC] = cov[r][a] / sqrt(var[rho] var[a]) clamped into [-1, 1], computed on the device; 0.0
+ *                         where var[rho] > 0 && var[a] > 0 is false; corr[r][row[r]] == 1.0 for a cell that moved.  HMCMT_EINVAL
+ *                         when N = 0
+ * hmcmt_chain_begin (also over a running chain), hmcmt_chain_end, hmcmt_set_prior and hmcmt_set_mass end the accumulator and release
+ * its buffers; a step that fails touches nothing.  HMCMT_EINVAL: NULL context, a size, batch or index outside the above, no chain, no
+ * accumulator begun, a call between hmcmt_grad_device_async and hmcmt_wait.  Results repeat bitwise (every S[r][a] has one owner
+ * thread: no atomics). */
+#define HMCMT_COV_BATCH_MAX 16
+extern int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* row, int32_t batch);
+extern int hmcmt_chain_cov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* var, double* cov, int32_t on_device);
+extern int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

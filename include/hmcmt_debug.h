@@ -103,6 +103,10 @@ int hmcmt_mass_info(const hmcmt_ctx* ctx, double* out /*[HMCMT_MASS_INFO_FIELDS]
  * steady commits (count >= maxlag: every lag reads the ring and updates S_k).  An interval includes the cost of its two event records */
 int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]*/, int64_t* launches /*[2]*/);
 
+/* Measurement only: the same for the running covariance accumulator (hmcmt_chain_cov_begin): of each pair [0] the k_chain_cov_commit
+ * launches, [1] the k_chain_cov_flush launches (a read-out's flush of a partly filled batch included).  It changes no result */
+int hmcmt_debug_chain_cov_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]*/, int64_t* launches /*[2]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -590,7 +590,49 @@ function chain_ess!(ctx::HipContext; targets::Vector{<:Integer}=Int[], maxlag::I
 end
 
 """
-    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing) -> (hmcmodel, hmcstats, hmcdata, moments)
+    chainCovBegin!(ctx, rows, batch);  chainCov(ctx, nrow) -> (count, mean[nAC], var[nAC], cov[nAC, nrow])
+    chainCorr(ctx, nrow) -> corr[nAC, nrow];  chain_cov!(ctx; rows=all cells, batch=0) -> (rows, batch)
+
+Posterior covariance and correlation from the chain's commit (hmcmt_chain_cov_*, hmcmt_chain_corr, include/hmcmt.h): the cross moments
+of ln sigma between the cells `rows` and every active cell, fed by the commits behind the burn-in from the begin call on and folded in
+by a kernel every `batch` commits (1 .. 16; 0: the default, 8; the results do not depend on it).  `rows` are 1-based active-cell
+indices here (0-based in C); an empty vector means every active cell, the full matrix.  `cov` and `corr` come back in C's row-major
+layout, i.e. with Julia's first index running over the cells: column r is the map of `rows[r]`.  Biased estimator (1/N).  Call the
+begin function behind `chainBegin!` (which ends the accumulator) and in front of the first `chainMomentum!`; `chain_cov!` does so
+with the defaults of the Python sampler, and `run_chain!(...; cov=(rows=..., batch=...))` does both ends.
+"""
+function chainCovBegin!(ctx::HipContext, rows::Vector{<:Integer}, batch::Integer)
+    r0 = Int64.(rows) .- 1
+    ptr = isempty(r0) ? Ptr{Int64}(C_NULL) : pointer(r0)
+    rc = GC.@preserve r0 @ccall libhmcmt.hmcmt_chain_cov_begin(ctx.ptr::Ptr{Cvoid}, Int64(length(r0))::Int64, ptr::Ptr{Int64},
+                                                               Int32(batch)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+end
+
+function chainCov(ctx::HipContext, nrow::Integer)
+    count = Ref{Int64}(0)
+    mean = Vector{Float64}(undef, ctx.nAC); var = Vector{Float64}(undef, ctx.nAC)
+    cov = Matrix{Float64}(undef, ctx.nAC, nrow)
+    rc = @ccall libhmcmt.hmcmt_chain_cov(ctx.ptr::Ptr{Cvoid}, count::Ref{Int64}, mean::Ptr{Float64}, var::Ptr{Float64}, cov::Ptr{Float64},
+                                         Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return Int(count[]), mean, var, cov
+end
+
+function chainCorr(ctx::HipContext, nrow::Integer)
+    corr = Matrix{Float64}(undef, ctx.nAC, nrow)
+    rc = @ccall libhmcmt.hmcmt_chain_corr(ctx.ptr::Ptr{Cvoid}, corr::Ptr{Float64}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return corr
+end
+
+function chain_cov!(ctx::HipContext; rows::Vector{<:Integer}=Int[], batch::Integer=0)
+    chainCovBegin!(ctx, rows, batch)
+    return (isempty(rows) ? collect(1:ctx.nAC) : rows), batch
+end
+
+"""
+    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, cov=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov])
 
 runHMCSampler (HMCSampler.jl:72-196) through the chain API, step for step what hmcmt2d_amd/sampler.py's device chain does, the
 reference's start included: the chain's state starts at the file's model invParam.strModel (:88), while start and reference model
@@ -599,9 +641,11 @@ become the homogeneous one of `rhoref` Ωm (drawn as :100-104 draws it when `not
 `chainSetEnergy!` with the first one's D and M.  The mass is hmcParam's (`setPrior!`).  Draw order: the first momentum's normals,
 rhoref; per sample L, u, the next momentum's normals.  `keepSamples=false`: no sample leaves the GPU (hmcmodel has no column,
 hmcdata its first only); `moments` = (count, mean, m2) of the samples behind hmcprior.burninsamples either way.
+`cov=(rows=Int[], batch=0)` (both optional; see `chainCovBegin!`) streams the posterior covariance beside the moments and appends a fifth
+result, the named tuple (count, rows, mean, var, cov, corr) -- `nothing` for the arrays of a chain that ends inside its burn-in.
 """
 function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior, hmcParam::HMCParameter; keepSamples::Bool=true,
-                    rhoref::Union{Nothing,Real}=nothing)
+                    rhoref::Union{Nothing,Real}=nothing, cov::Union{Nothing,NamedTuple}=nothing)
     n, nd = ctx.nAC, ctx.nData
     nsamples = hmcprior.totalsamples
     fileModel = Vector{Float64}(invParam.strModel)
@@ -622,6 +666,7 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
         chainBegin!(ctx, fileModel, hmcprior.dt, hmcprior.regParam, lo, hi; burnin=hmcprior.burninsamples)
         chainSetEnergy!(ctx, D, M)
     end
+    covRows = cov === nothing ? Int[] : first(chain_cov!(ctx; rows=Vector{Int}(get(cov, :rows, Int[])), batch=get(cov, :batch, 0)))
     K = chainMomentum!(ctx, z)
     ncols = keepSamples ? nsamples : 0
     hmcmodel = zeros(Float64, n, ncols)
@@ -649,7 +694,14 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
             hmcdata[:, it + 1] = rec.accepted == 1 ? predOut : hmcdata[:, it]      # (:164-168: a rejection repeats the column)
         end
     end
-    return hmcmodel, hmcstats, hmcdata, chainMoments(ctx)
+    cov === nothing && return hmcmodel, hmcstats, hmcdata, chainMoments(ctx)
+    if nsamples > hmcprior.burninsamples
+        count, cmean, cvar, cmat = chainCov(ctx, length(covRows))
+        covStats = (count=count, rows=covRows, mean=cmean, var=cvar, cov=cmat, corr=chainCorr(ctx, length(covRows)))
+    else
+        covStats = (count=0, rows=covRows, mean=nothing, var=nothing, cov=nothing, corr=nothing)
+    end
+    return hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats
 end
 
 hipWait(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_wait, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
