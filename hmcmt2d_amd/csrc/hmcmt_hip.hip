@@ -170,6 +170,8 @@ struct hmcmt_ctx {
     cplx* d_prevField[2] = {nullptr, nullptr};   // the EXT_NP-1 previous solutions (warm_start == 2), per solve kind: a ring [EXT_NP-1][S*vstride]
     double* d_mHist[2] = {nullptr, nullptr};     // [EXT_NP+1][nAC] model history per solve kind (a ring: kernels_fused.h)
     double* d_ext[2] = {nullptr, nullptr};       // {w_0..w_{EXT_NP-1}, keep, count, ring heads, partial sums, ticket} (kernels_fused.h)
+    cplx* d_guessCap[2] = {nullptr, nullptr};    // test hook hmcmt_debug_guess_capture: the initial guesses of the last evaluation [S*vstride] (allocated when first enabled)
+    bool guessCapture = false;
     double jacobiW = 0.8;                    // damping of the point-Jacobi halves (HMCMT_JACOBI_W; 0.7 in round 1: 0.8 saves 3-8 % of the iterations on structured models, costs 6-25 % on white-noise models of std >= 1)
     int extrapNp = EXT_NP;                   // fields used by the initial-guess extrapolation (HMCMT_EXTRAP_POINTS = 2..EXT_NP)
     bool fusedFwd = true;                    // forward transform + tridiagonal solve in one kernel (HMCMT_FUSED_FWD=0: separate)
@@ -1204,6 +1206,7 @@ void launch_adjoint_side(hmcmt_ctx* ctx) {
     if (ctx->sideExtrap) {
         launch_extrap_weights(ctx, ctx->sideM, 1, ctx->side);
         hipLaunchKernelGGL(k_extrap, dim3(ctx->sv.NB, S), dim3(VBLOCK), 0, ctx->side, ctx->sv, v.Lam, ctx->d_prevField[1], ctx->d_ext[1]);
+        if (ctx->guessCapture) hipMemcpyAsync(ctx->d_guessCap[1], v.Lam, (size_t)S * v.vstride * sizeof(cplx), hipMemcpyDeviceToDevice, ctx->side);
         hipEventRecord(ctx->evExtA, ctx->side);
         ctx->extAWaitPending = true;
     }
@@ -1356,6 +1359,8 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             // (interior nodes only -- the boundary-value kernel owns the boundary nodes of X)
             launch_extrap_weights(ctx, d_m, 0, sA);
             hipLaunchKernelGGL(k_extrap, dim3(ctx->sv.NB, S), dim3(VBLOCK), 0, sA, ctx->sv, v.X, ctx->d_prevField[0], ctx->d_ext[0]);
+            // (test hook: the boundary nodes of this copy race with the boundary-value kernel on the main stream -- interior nodes only)
+            if (ctx->guessCapture) HIPCHK(hipMemcpyAsync(ctx->d_guessCap[0], v.X, vecBytes, hipMemcpyDeviceToDevice, sA));
             HIPCHK(hipEventRecord(ctx->evExtF, sA));
         }
         HIPCHK(issue_pivot(sA));
@@ -2601,6 +2606,43 @@ int hmcmt_debug_spmv(hmcmt_ctx* ctx, const double* p, double* q) {
     hipLaunchKernelGGL(k_spmv, dim3(ctx->sv.NB, ctx->v.S), dim3(VBLOCK), 0, ctx->stream, ctx->sv);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(q, ctx->sv.q, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the extrapolation state of solve kind `kind` as the last evaluation left it: {w_0..w_5, keep, count, field-ring head, model-ring head}
+int hmcmt_debug_extrap(hmcmt_ctx* ctx, int32_t kind, double* out) {
+    if (!ctx || !out || kind < 0 || kind > 1) return HMCMT_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->side));
+    HIPCHK(hipMemcpy(out, ctx->d_ext[kind], EXT_PART * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// capture of the initial guesses on / off: while on, every evaluation that extrapolates copies X (Lam) behind k_extrap, on its stream
+int hmcmt_debug_guess_capture(hmcmt_ctx* ctx, int32_t enable) {
+    if (!ctx) return HMCMT_EINVAL;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->side));
+    if (enable && !ctx->d_guessCap[0]) {
+        const size_t n = (size_t)ctx->v.S * ctx->v.vstride;
+        int rc;
+        if ((rc = dalloc(ctx, &ctx->d_guessCap[0], n)) || (rc = dalloc(ctx, &ctx->d_guessCap[1], n))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->guessCapture = enable != 0;
+    return 0;
+}
+
+// the captured guess of solve kind `kind`: complex [S][NZP][NYP], the padded layout of hmcmt_debug_spmv
+int hmcmt_debug_guess(hmcmt_ctx* ctx, int32_t kind, double* out) {
+    if (!ctx || !out || kind < 0 || kind > 1) return HMCMT_EINVAL;
+    if (!ctx->guessCapture || !ctx->d_guessCap[kind]) { ctx->err = "hmcmt_debug_guess: the capture is off (hmcmt_debug_guess_capture)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->side));
+    HIPCHK(hipMemcpy(out, ctx->d_guessCap[kind], (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -767,64 +767,8 @@ __global__ void k_solve_end(Solver k, int kind, int* __restrict__ recI, double* 
 // nearly collinear with the last one and of comparable length adds a point (and an order) to the Lagrange
 // extrapolation, up to EXT_NP fields.  A repeated model (getHamiltonian after the last leapfrog step) keeps the
 // history untouched.
-constexpr int EXT_NP = 6;          // fields kept per solve kind: the current one + EXT_NP-1 earlier ones (Lagrange order <= EXT_NP-1)
-constexpr int EXT_NBLK = 32;       // blocks of the partial-sum pass
-constexpr int EXT_NS = 2 * EXT_NP; // partial sums per block: <d_j,d1> (j = 0..NP-1), <d_j,d_j> (j = 0, 2..NP-1), <m_k,m_k>
-constexpr int EXT_KEEP = EXT_NP, EXT_COUNT = EXT_NP + 1, EXT_HEAD = EXT_NP + 2, EXT_MHEAD = EXT_NP + 3, EXT_PART = EXT_NP + 4;
-// ext = {w_0..w_{NP-1}, keep, count, head of the field ring, head of the model ring, partial sums [NBLK][NS], ticket}
-constexpr int EXT_TICKET = EXT_PART + EXT_NS * EXT_NBLK, EXT_LEN = EXT_TICKET + 1;
-
-// The weights from the summed partials (one thread).
-// coldUnlessSmooth (the adjoint solve): without at least three collinear points the weights are all zero -- the adjoint's
-// right-hand side is the weighted residual, which changes by O(1) from step to step, so its previous solution is no
-// better a guess than zero (measured on the sampler's trajectories: 0-4 iterations WORSE than a cold start) unless the
-// model path is smooth enough for the extrapolation proper.  Returns keep (the model is a repeat: nothing moves).
-__device__ bool extrap_weights(const double* a, double* ext, int maxNp, int coldUnlessSmooth) {
-    const int count = (int)ext[EXT_COUNT];
-    const double d1d1 = a[1], d0d0 = a[EXT_NP], mkmk = a[EXT_NS - 1];
-    const bool keep = count >= 1 && d0d0 <= 1e-28 * mkmk;
-    double wts[EXT_NP];                                       // weights of x_k, x_{k-1}, ...
-    for (int i = 0; i < EXT_NP; ++i) wts[i] = i == 0 ? 1.0 : 0.0;
-    if (coldUnlessSmooth && !keep) wts[0] = 0.0;
-    if (!keep && count >= 2 && d1d1 > 0) {
-        const double alpha = fmin(2.0, fmax(-1.0, a[0] / d1d1));
-        wts[0] = 1.0 + alpha; wts[1] = -alpha;
-        // "times" of the models on the line through the last step: 0, -1, -1-g2, -1-g2-g3, ...; a further point is used
-        // while its step is nearly collinear with the last one and of comparable length
-        double tau[EXT_NP];
-        tau[0] = 0.0; tau[1] = -1.0;
-        int np = 2;
-        if (d0d0 > 0 && a[0] / sqrt(d0d0 * d1d1) > 0.95 && alpha > 0.5 && alpha < 2.0) {
-            for (int j = 2; j < EXT_NP; ++j) {
-                const double djdj = a[EXT_NP + j - 1], g = a[j] / d1d1;
-                if (!(count >= j + 1 && djdj > 0 && a[j] / sqrt(djdj * d1d1) > 0.95 && g > 0.5 && g < 2.0)) break;
-                tau[j] = tau[j - 1] - g;
-                np = j + 1;
-            }
-        }
-        np = min(maxNp, np);
-        if (coldUnlessSmooth && np <= 2) wts[0] = wts[1] = 0.0;
-        if (np > 2) {
-            for (int i = 0; i < EXT_NP; ++i) {
-                double l = i < np ? 1.0 : 0.0;
-                for (int j = 0; j < np; ++j)
-                    if (j != i && i < np) l *= (alpha - tau[j]) / (tau[i] - tau[j]);
-                wts[i] = l;
-            }
-        }
-    }
-    for (int i = 0; i < EXT_NP; ++i) ext[i] = wts[i];
-    ext[EXT_KEEP] = keep ? 1.0 : 0.0;
-    if (!keep) {
-        ext[EXT_COUNT] = (double)min(count + 1, EXT_NP);
-        // both histories are rings: the heads move back by one, the model ring's onto the slot k_extrap_prepare has just
-        // filled with the new model, the field ring's onto its oldest entry, which receives the solution that is about to
-        // be replaced by the new guess (k_extrap)
-        ext[EXT_HEAD] = (double)(((int)ext[EXT_HEAD] + EXT_NP - 2) % (EXT_NP - 1));
-        ext[EXT_MHEAD] = (double)(((int)ext[EXT_MHEAD] + EXT_NP) % (EXT_NP + 1));
-    }
-    return keep;
-}
+// (EXT_* constants and extrap_weights, the one thread that turns the summed partials into weights: hmcmt_items.h, where the host
+// tests instantiate it)
 
 // One launch (round 1: three in a row in front of every k_extrap -- 45 us of serial side-stream time that the forward
 // residual waited for): per-block partial sums over the model history -- a ring hist[slot][nAC] of NP+1 slots, the model

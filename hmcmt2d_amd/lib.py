@@ -179,6 +179,11 @@ def load_library():
     lib.hmcmt_debug_chain_cov_time.restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
+    lib.hmcmt_debug_extrap.argtypes = [vp, C.c_int32, c_double_p]
+    lib.hmcmt_debug_guess_capture.argtypes = [vp, C.c_int32]
+    lib.hmcmt_debug_guess.argtypes = [vp, C.c_int32, c_double_p]
+    for name in ("hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess"):
+        getattr(lib, name).restype = C.c_int
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
                  "hmcmt_grad", "hmcmt_forward", "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async",
                  "hmcmt_wait", "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_mass_info", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead",
@@ -221,7 +226,7 @@ DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "
                  "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond", "hmcmt_debug_fdm_fwd",
                  "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_debug_hog", "hmcmt_persist_envelope",
                  "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time",
-                 "hmcmt_debug_chain_cov_time"]
+                 "hmcmt_debug_chain_cov_time", "hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -938,6 +943,26 @@ class HipContext:
         z = np.empty_like(r)
         self._check(self.lib.hmcmt_debug_precond(self.h, _dp(r), _dp(z)))
         return z
+
+    EXTRAP_POINTS = 6     # csrc/hmcmt_items.h: EXT_NP, the fields of the initial-guess extrapolation (the field ring has one slot less, the model ring one more)
+
+    def debug_extrap(self, adjoint=False):
+        """The extrapolation state of the forward (adjoint) solve as the last evaluation left it (hmcmt_debug_extrap): weights of
+        x_k, x_{k-1}, ..., the repeat flag, the models in the history and the heads of the two rings."""
+        out = np.empty(10)
+        self._check(self.lib.hmcmt_debug_extrap(self.h, int(adjoint), _dp(out)))
+        return {"weights": out[:6].copy(), "keep": int(out[6]), "count": int(out[7]), "head": int(out[8]), "model_head": int(out[9])}
+
+    def debug_guess_capture(self, on=True):
+        """Switches the capture of the solves' initial guesses on / off (hmcmt_debug_guess_capture)."""
+        self._check(self.lib.hmcmt_debug_guess_capture(self.h, int(bool(on))))
+
+    def debug_guess(self, adjoint=False):
+        """The initial guess the last evaluation's forward (adjoint) solve started from: complex (S, NZP, NYP), the padded layout of
+        debug_spmv; interior nodes [:, 1:nz, 1:ny] only (hmcmt_debug_guess)."""
+        out = np.empty(self.S * self.NZP * self.NYP, dtype=np.complex128)
+        self._check(self.lib.hmcmt_debug_guess(self.h, int(adjoint), _dp(out)))
+        return out.reshape(self.S, self.NZP, self.NYP)
 
     def guard(self):
         """Production guard of the stopping rule (hmcmt_guard): true residuals formed every HMCMT_GUARD_EVERY-th evaluation."""

@@ -107,6 +107,23 @@ int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]
  * launches, [1] the k_chain_cov_flush launches (a read-out's flush of a partly filled batch included).  It changes no result */
 int hmcmt_debug_chain_cov_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]*/, int64_t* launches /*[2]*/);
 
+/* Test hooks of the initial-guess extrapolation (options.warm_start == 2; DESIGN 4.4, tests/test_gpu_extrap.py).  Read-only: they
+ * wait for the context's streams and change no result.
+ * hmcmt_debug_extrap: the extrapolation state of solve kind `kind` (0 forward, 1 adjoint) as the last evaluation left it,
+ *   out = {w_0 .. w_5 (weights of x_k, x_{k-1}, ..., x_{k-5}), keep (1: the model was a repeat, nothing moved), count (models in the
+ *   history after the call, <= 6), head of the field ring (5 slots), head of the model ring (7 slots)}.
+ * hmcmt_debug_guess_capture: enable = 1 / 0 switches the capture of the initial guesses on / off.  While on, every evaluation that
+ *   extrapolates copies X (and, with a gradient, Lam) device-to-device behind the extrapolation kernel, on that kernel's stream, into
+ *   buffers allocated when the capture is first enabled; while off there is no launch, no copy and no allocation.
+ * hmcmt_debug_guess: the captured guess of solve kind `kind`, the vector the last evaluation's solve started from: out = host
+ *   complex[S*NZP*NYP] in the padded nodal layout of hmcmt_debug_spmv (system s = mode * nFreq + f, node iz * NYP + iy).  Defined on
+ *   the interior nodes 1 <= iy <= ny-1, 1 <= iz <= nz-1 only: the forward solve's boundary nodes are written by the boundary-value
+ *   kernel on another stream at the same time, so the copy may hold either their old or their new values.  On a cold start the
+ *   guess is the zero fill.  An evaluation that does not extrapolate (warm_start != 2, options.verify) leaves the capture as it was. */
+int hmcmt_debug_extrap(hmcmt_ctx* ctx, int32_t kind, double* out /*[10]*/);
+int hmcmt_debug_guess_capture(hmcmt_ctx* ctx, int32_t enable);
+int hmcmt_debug_guess(hmcmt_ctx* ctx, int32_t kind, double* out);
+
 #ifdef __cplusplus
 }
 #endif
