@@ -43,6 +43,14 @@ struct Emul {
         sensEu.assign((size_t)h.S * 3 * (h.nz + 1), cplx{0, 0}); sensEd = sensEu; sensMix.assign((size_t)h.S * 12 * h.nz, cplx{0, 0});
         sensDz1.assign((size_t)h.S * 3 * h.nz, cplx{0, 0}); sensZ1.assign((size_t)h.S * 3, cplx{0, 0}); sensDead.assign((size_t)h.S * 3, 0);
         iters.assign(2 * h.S, 0);
+        // the tipper's functionals nRx .. 2 nRx-1 and their tables (hmcmt_host.h: build_tipper_tables)
+        v.nTip = h.nTip;
+        if (h.nTip) {
+            v.nRx = h.nFun;
+            Zrx.assign((size_t)h.S * h.nFun, cplx{0, 0}); rxN0.assign((size_t)h.S * h.nFun, 0);
+            rxD.assign((size_t)h.S * h.nFun * 11, cplx{0, 0}); rxCoef.assign((size_t)h.S * h.nFun, cplx{0, 0});
+            v.rxCL = h.rxCL.data(); v.rxCR = h.rxCR.data(); v.rxVL = h.rxVL.data(); v.rxVR = h.rxVR.data();
+        }
         v.yLen = h.yLen.data(); v.zLen = h.zLen.data(); v.omega = h.omega.data(); v.lam = h.lam.data(); v.sysOn = h.sysOn.data();
         v.m = m.data(); v.sigma = sigma.data(); v.cell2act = h.cell2act.data(); v.bg = h.bg.data(); v.act = h.act.data();
         v.sigMeanA = sigMeanA.data(); v.sigMeanG = sigMeanG.data();
@@ -250,6 +258,9 @@ int emul_grad(void* h, const double* m, int wantGrad, int precond, double tol, i
     std::memcpy(iters, e->iters.data(), sizeof(int) * 2 * e->v.S);
     return 0;
 }
+
+// hmcmt_debug_flags' bit 1: the boundary-derivative terms left out of the gradient
+void emul_debug_flags(void* h, int flags) { ((Emul*)h)->v.dbg = flags & 2; }
 
 int emul_dims(void* h, int* out /* NYP, NZP, S, ny, nz, zid */) {
     Emul* e = (Emul*)h;

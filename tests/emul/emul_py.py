@@ -39,6 +39,7 @@ def lib():
         _lib.emul_destroy.argtypes = [C.c_void_p]
         _lib.emul_grad.argtypes = [C.c_void_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_int,
                                    c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int)]
+        _lib.emul_debug_flags.argtypes = [C.c_void_p, C.c_int]
         _lib.emul_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         _lib.emul_apply.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p]
         _lib.emul_get.restype = C.c_long
@@ -70,6 +71,9 @@ class Emul:
                         pred.ctypes.data_as(c_double_p), C.byref(misfit), grad.ctypes.data_as(c_double_p), iters)
         self.iters = np.array(list(iters)).reshape(2, self.S)
         return pred, misfit.value, grad
+
+    def debug_flags(self, no_boundary_terms=False):
+        lib().emul_debug_flags(self.h, 2 if no_boundary_terms else 0)
 
     def get(self, name, complex_=None):
         which = self.GET[name]

@@ -133,7 +133,9 @@ def _setup(mesh, sigma):
 
 
 def tipper_table(mesh, data, fwd):
-    """T[f, r] from the TE fields of an oracle forward solution."""
+    """T[f, r] from the TE fields of an oracle forward solution, or from an (nNode, nFreq) array of TE fields fetched
+    elsewhere (tests/replay_ref.py)."""
+    fwd = fwd if hasattr(fwd, "exTE") else O.MT2DFwdData(np.asarray(fwd), None, None, None, "")
     ny, nz = mesh.gridSize
     yN = np.concatenate([[0.0], np.cumsum(mesh.yLen)]) - mesh.origin[0]
     zN = np.concatenate([[0.0], np.cumsum(mesh.zLen)]) - mesh.origin[1]
