@@ -75,6 +75,21 @@ struct PsKernel {
 
 }  // namespace
 
+// measurement only (hmcmt_debug_chain_*_time): HIP-event pairs round the launches of one accumulator of the chain's commit, summed
+// in two classes (host_chain.h)
+struct ChainTimer {
+    bool timing = false;
+    std::vector<hipEvent_t> ev;           // pool, two per pending launch
+    std::vector<int> pending;             // class of each pending launch
+    double ms[2] = {0, 0};
+    long long launches[2] = {0, 0};
+    bool start(hipStream_t st);
+    void stop(hipStream_t st, int cls);
+    void collect(hipStream_t st);
+    void free(int device, hipStream_t st);
+    void report(hipStream_t st, int enable, double* msOut, int64_t* launchesOut);
+};
+
 // ----------------------------------------------------------------------------------------------
 // context
 // ----------------------------------------------------------------------------------------------
@@ -251,8 +266,9 @@ struct hmcmt_ctx {
         int nextStart = 0;                // start_grad of the next step: 0 evaluate, 1 accepted, 2 rejected
         long long gen = 0;                // stateGen when the chain last left the context
         std::vector<void*> allocs;
-        // the optional accumulators of the commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*): buffers of their own, released
-        // with the chain and by every hmcmt_chain_begin
+        // the optional accumulators of the commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*, hmcmt_chain_acov_*, hmcmt_chain_cov_*):
+        // each owns its buffers through `allocs` (chain_acc_alloc / chain_acc_free; the d_ pointers only name them), released with the
+        // chain and by every hmcmt_chain_begin
         struct Hist {
             bool on = false;
             long long ntarget = 0, count = 0;
@@ -260,11 +276,13 @@ struct hmcmt_ctx {
             double lo = 0, hi = 0, scale = 0, w = 0;
             long long* d_target = nullptr;            // [ntarget] active-cell indices
             unsigned int* d_counts = nullptr;         // [nbins][ntarget], bin-major (hmcmt_items.h)
+            std::vector<void*> allocs;
         } hist;
         struct DataMoments {
             bool on = false;
             long long count = 0;
             double *d_mean = nullptr, *d_m2 = nullptr;   // [2 nData] each
+            std::vector<void*> allocs;
         } dmom;
         struct Acov {                                 // hmcmt_chain_acov_*: lagged autocovariances, every array lag-major (hmcmt_items.h)
             bool on = false;
@@ -273,12 +291,8 @@ struct hmcmt_ctx {
             long long* d_target = nullptr;            // [ntarget] active-cell indices; nullptr: every cell, row j = cell j
             double *d_x0 = nullptr, *d_tot = nullptr; // [ntarget] pivot and sum of y
             double *d_S = nullptr, *d_H = nullptr, *d_ring = nullptr;   // [K + 1][ntarget] each
-            // hmcmt_debug_chain_acov_time (measurement only): a pair of events round every k_chain_acov launch
-            bool timing = false;
-            std::vector<hipEvent_t> ev;               // pool, two per pending launch
-            std::vector<int> pending;                 // class of each pending launch: 0 some lag still fills H_k (t < K), 1 steady
-            double ms[2] = {0, 0};
-            long long launches[2] = {0, 0};
+            std::vector<void*> allocs;
+            ChainTimer timer;                         // every k_chain_acov launch: class 0 some lag still fills H_k (t < K), 1 steady
         } acov;
         struct Cov {                                  // hmcmt_chain_cov_*: cross moments of the cells, cell index fastest (hmcmt_items.h)
             bool on = false;
@@ -288,12 +302,8 @@ struct hmcmt_ctx {
             double *d_x0 = nullptr, *d_tot = nullptr, *d_q = nullptr;   // [nAC] pivot, sum of y, sum of y^2
             double *d_pend = nullptr;                 // [B][nAC]
             double *d_S = nullptr;                    // [nrow][nAC]
-            // hmcmt_debug_chain_cov_time (measurement only): a pair of events round every k_chain_cov_commit / k_chain_cov_flush launch
-            bool timing = false;
-            std::vector<hipEvent_t> ev;               // pool, two per pending launch
-            std::vector<int> pending;                 // class of each pending launch: 0 commit, 1 flush
-            double ms[2] = {0, 0};
-            long long launches[2] = {0, 0};
+            std::vector<void*> allocs;
+            ChainTimer timer;                         // every launch of the commit: class 0 k_chain_cov_commit, 1 k_chain_cov_flush
         } cov;
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none

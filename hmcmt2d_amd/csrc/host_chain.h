@@ -6,69 +6,185 @@
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
 // k_chain_hist, a second k_chain_welford (the predicted data), k_chain_acov (lagged autocovariances) and k_chain_cov_commit (cross
 // moments; every `batch` commits k_chain_cov_flush) behind them.
+//
+// The four accumulators share their host scaffolding, which stands in front of them: ChainTimer (the event pairs of the measurement
+// hooks), chain_acc_alloc / chain_acc_free (each accumulator's struct owns its buffers through `allocs`), chain_acc_ready (the
+// guards of an entry point), chain_cell_list / chain_cell_upload (a begin's list of active cells) and ChainReadout (the outputs of
+// one read-out: the caller's device pointers, or temporaries copied back).  A further accumulator is its kernels, its struct in
+// hmcmt_ctx::Chain, its launch in hmcmt_chain_step's commit, a line in chain_acc_release, and a begin and a read-out written with these.
 
-// measurement only (hmcmt_debug_chain_acov_time): the event pairs round the k_chain_acov launches
-static void chain_acov_time_collect(hmcmt_ctx* ctx) {
-    auto& A = ctx->chain.acov;
-    if (A.pending.empty()) return;
-    (void)hipStreamSynchronize(ctx->stream);
-    for (size_t i = 0; i < A.pending.size(); ++i) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, A.ev[2 * i], A.ev[2 * i + 1]) == hipSuccess) { A.ms[A.pending[i]] += ms; A.launches[A.pending[i]] += 1; }
+// what every chain call checks first
+static int chain_ready(hmcmt_ctx* ctx, const char* fn, bool needChain) {
+    if (ctx->statsPending) { ctx->err = std::string(fn) + ": an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
+    if (needChain && !ctx->chain.active) {
+        ctx->err = std::string(fn) + ": no chain (hmcmt_chain_begin first; hmcmt_set_prior and hmcmt_set_mass end a chain)";
+        return HMCMT_EINVAL;
     }
-    A.pending.clear();
-}
-static void chain_acov_time_free(hmcmt_ctx* ctx) {
-    auto& A = ctx->chain.acov;
-    if (A.ev.empty()) return;
-    hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (hipEvent_t e : A.ev) hipEventDestroy(e);
-    A.ev.clear(); A.pending.clear();
-    A.timing = false;
+    return 0;
 }
 
-// measurement only (hmcmt_debug_chain_cov_time): the event pairs round the k_chain_cov_commit and k_chain_cov_flush launches
-static void chain_cov_time_collect(hmcmt_ctx* ctx) {
-    auto& V = ctx->chain.cov;
-    if (V.pending.empty()) return;
-    (void)hipStreamSynchronize(ctx->stream);
-    for (size_t i = 0; i < V.pending.size(); ++i) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, V.ev[2 * i], V.ev[2 * i + 1]) == hipSuccess) { V.ms[V.pending[i]] += ms; V.launches[V.pending[i]] += 1; }
-    }
-    V.pending.clear();
-}
-static void chain_cov_time_free(hmcmt_ctx* ctx) {
-    auto& V = ctx->chain.cov;
-    if (V.ev.empty()) return;
-    hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (hipEvent_t e : V.ev) hipEventDestroy(e);
-    V.ev.clear(); V.pending.clear();
-    V.timing = false;
-}
-// the first event of the next pair of the pool, recorded (false: not timing, or no event to be had); chain_cov_time_stop closes it
-static bool chain_cov_time_start(hmcmt_ctx* ctx) {
-    auto& V = ctx->chain.cov;
-    if (!V.timing) return false;
-    if (V.pending.size() >= 1024) chain_cov_time_collect(ctx);
-    const size_t i = V.pending.size();
-    while (V.ev.size() < 2 * i + 2) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return false; } V.ev.push_back(e); }
-    hipEventRecord(V.ev[2 * i], ctx->stream);
+// ---- what the accumulators share: the timer, the owner of their buffers, the guards of their entry points, the read-out ------------
+// the first event of the next pair of the pool, recorded (false: not timing, or no event to be had); stop closes the pair
+bool ChainTimer::start(hipStream_t st) {
+    if (!timing) return false;
+    if (pending.size() >= 1024) collect(st);
+    const size_t i = pending.size();
+    while (ev.size() < 2 * i + 2) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return false; } ev.push_back(e); }
+    hipEventRecord(ev[2 * i], st);
     return true;
 }
-static void chain_cov_time_stop(hmcmt_ctx* ctx, int cls) {
-    auto& V = ctx->chain.cov;
-    hipEventRecord(V.ev[2 * V.pending.size() + 1], ctx->stream);
-    V.pending.push_back(cls);
+void ChainTimer::stop(hipStream_t st, int cls) {
+    hipEventRecord(ev[2 * pending.size() + 1], st);
+    pending.push_back(cls);
+}
+void ChainTimer::collect(hipStream_t st) {
+    if (pending.empty()) return;
+    (void)hipStreamSynchronize(st);
+    for (size_t i = 0; i < pending.size(); ++i) {
+        float t = 0;
+        if (hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]) == hipSuccess) { ms[pending[i]] += t; launches[pending[i]] += 1; }
+    }
+    pending.clear();
+}
+void ChainTimer::free(int device, hipStream_t st) {
+    if (ev.empty()) return;
+    hipSetDevice(device);
+    if (st) (void)hipStreamSynchronize(st);
+    for (hipEvent_t e : ev) hipEventDestroy(e);
+    ev.clear(); pending.clear();
+    timing = false;
+}
+// the sums since the last switch go out; enable = 1 / 0 switches and starts new ones, -1 only reads
+void ChainTimer::report(hipStream_t st, int enable, double* msOut, int64_t* launchesOut) {
+    collect(st);
+    for (int i = 0; i < 2; ++i) {
+        if (msOut) msOut[i] = ms[i];
+        if (launchesOut) launchesOut[i] = launches[i];
+    }
+    if (enable >= 0) {
+        timing = enable != 0;
+        for (int i = 0; i < 2; ++i) { ms[i] = 0; launches[i] = 0; }
+    }
+}
+
+// a device buffer that `owner` (an accumulator's allocs, a read-out's) frees
+static int chain_acc_alloc(hmcmt_ctx* ctx, const char* fn, std::vector<void*>& owner, void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        ctx->err = std::string(fn) + ": device allocation failed: " + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? HMCMT_ENOMEM : HMCMT_EHIP;
+    }
+    owner.push_back(*p);
+    return 0;
+}
+// ... zeroed (enqueued)
+static int chain_acc_zeroed(hmcmt_ctx* ctx, const char* fn, std::vector<void*>& owner, void** p, size_t bytes) {
+    const int rc = chain_acc_alloc(ctx, fn, owner, p, bytes);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(*p, 0, bytes, ctx->stream));
+    return 0;
+}
+// frees an accumulator's buffers (the caller resets it: X = {}); the caller has made sure that no commit still runs on them
+static void chain_acc_free(std::vector<void*>& allocs) {
+    for (void* p : allocs) hipFree(p);
+    allocs.clear();
+}
+
+// what the messages call an accumulator
+struct ChainAccName { const char *noun, *begin, *empty; };
+static const ChainAccName CHAIN_HIST = {"histogram", "hmcmt_chain_hist_begin", "the histogram"},
+                          CHAIN_DMOM = {"data moments", "hmcmt_chain_data_moments_begin", "the accumulator"},
+                          CHAIN_ACOV = {"autocovariances", "hmcmt_chain_acov_begin", "the accumulator"},
+                          CHAIN_COV = {"covariance", "hmcmt_chain_cov_begin", "the accumulator"};
+// what a call on a running accumulator checks first: chain_ready, that it runs, and (needCommits) that it has counted a commit
+static int chain_acc_ready(hmcmt_ctx* ctx, const char* fn, bool on, long long count, bool needCommits, const ChainAccName& name) {
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    if (!on) { ctx->err = std::string(fn) + ": no " + name.noun + " (" + name.begin + " first)"; return HMCMT_EINVAL; }
+    if (needCommits && count == 0) { ctx->err = std::string(fn) + ": " + name.empty + " is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+// the "list of active cells" argument of a begin (`what`: "target" / "row"): *count = the list's length, or with allowAll the number
+// of active cells for NULL and 0.  `need`, the call's requirement sentence, is the error where the list's shape or the call's other
+// arguments (restOk) miss it.
+static int chain_cell_list(hmcmt_ctx* ctx, const char* fn, const char* what, int64_t n, const int64_t* list, bool allowAll, bool restOk,
+                           const char* need, long long* count) {
+    const int nAC = ctx->v.nAC;
+    const bool all = allowAll && !list && n == 0;
+    if ((!all && (!list || n < 1)) || !restOk) { ctx->err = std::string(fn) + ": need " + need; return HMCMT_EINVAL; }
+    for (int64_t i = 0; i < n; ++i)
+        if (list[i] < 0 || list[i] >= nAC) {
+            ctx->err = std::string(fn) + ": " + what + " " + std::to_string(i) + " = " + std::to_string(list[i]) + " is no active cell (0.." +
+                       std::to_string(nAC - 1) + ")";
+            return HMCMT_EINVAL;
+        }
+    *count = all ? nAC : n;
+    return 0;
+}
+// the list's device copy, owned by `owner` (enqueued: the caller waits before it returns); NULL, every cell, has none
+static int chain_cell_upload(hmcmt_ctx* ctx, const char* fn, std::vector<void*>& owner, long long** d_list, const int64_t* list, long long n) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the list is uploaded as it is");
+    if (!list) return 0;
+    const int rc = chain_acc_alloc(ctx, fn, owner, (void**)d_list, (size_t)n * sizeof(long long));
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(*d_list, list, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+// One read-out's outputs.  out(): the device pointer to launch into for an output of the caller's -- the caller's own with on_device
+// (nullptr where it passed none), else a temporary that finish() copies back; scratch(): a device-only temporary.  A failed
+// allocation leaves rc (and nullptr, as every later call does).  finish(): the launches' status, the copies back, one wait.  Left
+// without a finish() that succeeded, it waits for the stream first; it frees what it allocated, never a pointer of the caller's.
+struct ChainReadout {
+    hmcmt_ctx* ctx;
+    const char* fn;
+    bool onDevice, done = false;
+    int rc = 0, nback = 0;
+    std::vector<void*> allocs;
+    struct { void *host, *dev; size_t bytes; } back[3];
+    ChainReadout(hmcmt_ctx* c, const char* f, bool dev) : ctx(c), fn(f), onDevice(dev) {}
+    ChainReadout(const ChainReadout&) = delete;
+    void* scratch(size_t bytes) {
+        void* p = nullptr;
+        if (!rc) rc = chain_acc_alloc(ctx, fn, allocs, &p, bytes);
+        return p;
+    }
+    void* out(void* caller, size_t bytes) {
+        if (onDevice || !caller) return caller;
+        void* p = scratch(bytes);
+        if (p) back[nback++] = {caller, p, bytes};
+        return p;
+    }
+    int finish() {
+        HIPCHK(hipGetLastError());
+        for (int i = 0; i < nback; ++i) HIPCHK(hipMemcpyAsync(back[i].host, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        done = true;
+        return 0;
+    }
+    ~ChainReadout() {
+        if (!done) (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : allocs) hipFree(p);
+    }
+};
+
+// the Welford read-out of hmcmt_chain_moments and hmcmt_chain_data_moments: two copies, one wait
+static int chain_welford_out(hmcmt_ctx* ctx, size_t bytes, const double* d_mean, const double* d_m2, double* mean, double* m2, int32_t on_device) {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (mean) HIPCHK(hipMemcpyAsync(mean, d_mean, bytes, kind, ctx->stream));
+    if (m2) HIPCHK(hipMemcpyAsync(m2, d_m2, bytes, kind, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // folds the parked commits into S (enqueued): the commit calls it when the batch is full, a read-out when any is parked
 static void chain_cov_flush(hmcmt_ctx* ctx) {
     auto& V = ctx->chain.cov;
     if (V.npend == 0) return;
-    const bool timed = chain_cov_time_start(ctx);
+    const bool timed = V.timer.start(ctx->stream);
     const long long n = ctx->v.nAC, tiles = (V.nrow + CHAIN_COV_TILE_ROWS - 1) / CHAIN_COV_TILE_ROWS;
     const dim3 grid((unsigned)((n + CHAIN_COV_TILE_COLS - 1) / CHAIN_COV_TILE_COLS), (unsigned)std::min<long long>(tiles, 32768));
     static_assert(CHAIN_COV_BATCH_MAX == 16, "one instantiation of k_chain_cov_flush per batch length below");
@@ -80,28 +196,23 @@ static void chain_cov_flush(hmcmt_ctx* ctx) {
         HMCMT_COV_FLUSH(13) HMCMT_COV_FLUSH(14) HMCMT_COV_FLUSH(15) HMCMT_COV_FLUSH(16)
 #undef HMCMT_COV_FLUSH
     }
-    if (timed) chain_cov_time_stop(ctx, 1);
+    if (timed) V.timer.stop(ctx->stream, 1);
     V.npend = 0;
 }
 
 // ends the commit's optional accumulators (histogram, data moments, autocovariances, cross moments) and frees their buffers
 static void chain_acc_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
-    void* bufs[] = {C.hist.d_target, C.hist.d_counts, C.dmom.d_mean, C.dmom.d_m2, C.acov.d_target, C.acov.d_x0, C.acov.d_tot,
-                    C.acov.d_S, C.acov.d_H, C.acov.d_ring, C.cov.d_row, C.cov.d_x0, C.cov.d_tot, C.cov.d_q, C.cov.d_pend, C.cov.d_S};
-    chain_acov_time_free(ctx);
-    chain_cov_time_free(ctx);
-    bool any = false;
-    for (void* p : bufs) any = any || p;
-    if (any) {
+    C.acov.timer.free(ctx->device, ctx->stream);
+    C.cov.timer.free(ctx->device, ctx->stream);
+    if (!C.hist.allocs.empty() || !C.dmom.allocs.empty() || !C.acov.allocs.empty() || !C.cov.allocs.empty()) {
         hipSetDevice(ctx->device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be counting)
-        for (void* p : bufs) if (p) hipFree(p);
     }
-    C.hist = hmcmt_ctx::Chain::Hist{};
-    C.dmom = hmcmt_ctx::Chain::DataMoments{};
-    C.acov = hmcmt_ctx::Chain::Acov{};
-    C.cov = hmcmt_ctx::Chain::Cov{};
+    chain_acc_free(C.hist.allocs); C.hist = {};
+    chain_acc_free(C.dmom.allocs); C.dmom = {};
+    chain_acc_free(C.acov.allocs); C.acov = {};
+    chain_acc_free(C.cov.allocs); C.cov = {};
 }
 
 static void chain_release(hmcmt_ctx* ctx) {
@@ -128,16 +239,6 @@ static int chain_alloc(hmcmt_ctx* ctx, double** p, size_t n) {
     ctx->chain.allocs.push_back(q);
     HIPCHK(hipMemsetAsync(q, 0, bytes, ctx->stream));
     *p = (double*)q;
-    return 0;
-}
-
-// what every chain call checks first
-static int chain_ready(hmcmt_ctx* ctx, const char* fn, bool needChain) {
-    if (ctx->statsPending) { ctx->err = std::string(fn) + ": an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }
-    if (needChain && !ctx->chain.active) {
-        ctx->err = std::string(fn) + ": no chain (hmcmt_chain_begin first; hmcmt_set_prior and hmcmt_set_mass end a chain)";
-        return HMCMT_EINVAL;
-    }
     return 0;
 }
 
@@ -317,25 +418,18 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
         }
         if (C.acov.on) {
             auto& A = C.acov;                                // (the commit's number t is the count before it: t = 0 sets the pivot)
-            bool timed = false;
-            if (A.timing) {                                  // (measurement only: the next pair of the pool, grown as needed)
-                if (A.pending.size() >= 1024) chain_acov_time_collect(ctx);
-                const size_t i = A.pending.size();
-                while (A.ev.size() < 2 * i + 2) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); break; } A.ev.push_back(e); }
-                timed = A.ev.size() >= 2 * i + 2;
-                if (timed) hipEventRecord(A.ev[2 * i], st);
-            }
+            const bool timed = A.timer.start(st);
             hipLaunchKernelGGL(k_chain_acov, dim3((unsigned)((A.ntarget + 255) / 256), (unsigned)(A.K / CHAIN_ACOV_RUN + 1)), dim3(256), 0, st,
                                A.ntarget, A.K, A.count, C.d_m[C.cur], A.d_target, A.d_x0, A.d_tot, A.d_S, A.d_H, A.d_ring);
-            if (timed) { hipEventRecord(A.ev[2 * A.pending.size() + 1], st); A.pending.push_back(A.count >= A.K ? 1 : 0); }
+            if (timed) A.timer.stop(st, A.count >= A.K ? 1 : 0);
             ++A.count;
         }
         if (C.cov.on) {
             auto& V = C.cov;                                 // (t = the count before this commit; the slot = the commits parked so far)
-            const bool timed = chain_cov_time_start(ctx);
+            const bool timed = V.timer.start(st);
             hipLaunchKernelGGL(k_chain_cov_commit, dim3((n + 255) / 256), dim3(256), 0, st, (long long)n, V.count, V.npend, C.d_m[C.cur],
                                V.d_x0, V.d_tot, V.d_q, V.d_pend);
-            if (timed) chain_cov_time_stop(ctx, 0);
+            if (timed) V.timer.stop(st, 0);
             ++V.count;
             if (++V.npend == V.B) chain_cov_flush(ctx);
         }
@@ -382,71 +476,43 @@ int hmcmt_chain_state(hmcmt_ctx* ctx, double* m_cur, double* p_cur, double* pred
 
 int hmcmt_chain_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device) {
     if (!ctx) return HMCMT_EINVAL;
-    const int rc = chain_ready(ctx, "hmcmt_chain_moments", true);
+    int rc = chain_ready(ctx, "hmcmt_chain_moments", true);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     auto& C = ctx->chain;
-    const size_t bytes = sizeof(double) * ctx->v.nAC;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (mean) HIPCHK(hipMemcpyAsync(mean, C.d_mean, bytes, kind, ctx->stream));
-    if (m2) HIPCHK(hipMemcpyAsync(m2, C.d_m2, bytes, kind, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if ((rc = chain_welford_out(ctx, sizeof(double) * ctx->v.nAC, C.d_mean, C.d_m2, mean, m2, on_device))) return rc;
     if (count) *count = C.nmoments;
     return 0;
 }
 
 // ---- the commit's optional accumulators: histograms of the model, moments of the predicted data ------------------------------------
-static int chain_acc_alloc(hmcmt_ctx* ctx, const char* fn, void** p, size_t bytes) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        ctx->err = std::string(fn) + ": device allocation failed: " + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? HMCMT_ENOMEM : HMCMT_EHIP;
-    }
-    return 0;
-}
-
 int hmcmt_chain_hist_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* target, int32_t nbins, double lo, double hi) {
+    const char* fn = "hmcmt_chain_hist_begin";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_hist_begin", true);
+    int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
-    if (!target || ntarget < 1 || nbins < 1 || nbins > CHAIN_HIST_MAXBINS || !std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo) ||
-        !std::isfinite(hi - lo)) {
-        ctx->err = "hmcmt_chain_hist_begin: need target, ntarget >= 1, 1 <= nbins <= 4096 and finite lo < hi";
-        return HMCMT_EINVAL;
-    }
-    const int n = ctx->v.nAC;
-    for (int64_t i = 0; i < ntarget; ++i)
-        if (target[i] < 0 || target[i] >= n) {
-            ctx->err = "hmcmt_chain_hist_begin: target " + std::to_string(i) + " = " + std::to_string(target[i]) + " is no active cell (0.." +
-                       std::to_string(n - 1) + ")";
-            return HMCMT_EINVAL;
-        }
+    const bool restOk = nbins >= 1 && nbins <= CHAIN_HIST_MAXBINS && std::isfinite(lo) && std::isfinite(hi) && hi > lo && std::isfinite(hi - lo);
+    long long nt = 0;
+    if ((rc = chain_cell_list(ctx, fn, "target", ntarget, target, false, restOk, "target, ntarget >= 1, 1 <= nbins <= 4096 and finite lo < hi", &nt)))
+        return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    auto& C = ctx->chain;
-    auto& H = C.hist;
+    auto& H = ctx->chain.hist;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be counting into the histogram this one replaces)
-    for (void* p : {(void*)H.d_target, (void*)H.d_counts}) if (p) hipFree(p);
-    H = hmcmt_ctx::Chain::Hist{};
-    const size_t nb = (size_t)ntarget * sizeof(long long), cb = (size_t)ntarget * (size_t)nbins * sizeof(unsigned int);
+    chain_acc_free(H.allocs); H = {};
     auto build = [&]() -> int {
         int r;
-        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_hist_begin", (void**)&H.d_target, nb))) return r;
-        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_hist_begin", (void**)&H.d_counts, cb))) return r;
-        static_assert(sizeof(long long) == sizeof(int64_t), "the target list is uploaded as it is");
-        HIPCHK(hipMemcpyAsync(H.d_target, target, nb, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(H.d_counts, 0, cb, st));
+        if ((r = chain_cell_upload(ctx, fn, H.allocs, &H.d_target, target, nt))) return r;
+        if ((r = chain_acc_zeroed(ctx, fn, H.allocs, (void**)&H.d_counts, (size_t)nt * (size_t)nbins * sizeof(unsigned int)))) return r;
         HIPCHK(hipStreamSynchronize(st));                    // (the caller's list is free again on return)
         return 0;
     };
     if ((rc = build())) {
-        for (void* p : {(void*)H.d_target, (void*)H.d_counts}) if (p) hipFree(p);
-        H = hmcmt_ctx::Chain::Hist{};
+        (void)hipStreamSynchronize(st);
+        chain_acc_free(H.allocs); H = {};
         return rc;
     }
-    H.ntarget = ntarget; H.nbins = nbins; H.lo = lo; H.hi = hi;
+    H.ntarget = nt; H.nbins = nbins; H.lo = lo; H.hi = hi;
     H.scale = (double)nbins / (hi - lo);
     H.w = (hi - lo) / (double)nbins;
     H.count = 0;
@@ -456,10 +522,9 @@ int hmcmt_chain_hist_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* targe
 
 int hmcmt_chain_hist(hmcmt_ctx* ctx, int64_t* count, uint32_t* counts, int32_t on_device) {
     if (!ctx) return HMCMT_EINVAL;
-    const int rc = chain_ready(ctx, "hmcmt_chain_hist", true);
-    if (rc) return rc;
     auto& H = ctx->chain.hist;
-    if (!H.on) { ctx->err = "hmcmt_chain_hist: no histogram (hmcmt_chain_hist_begin first)"; return HMCMT_EINVAL; }
+    const int rc = chain_acc_ready(ctx, "hmcmt_chain_hist", H.on, H.count, false, CHAIN_HIST);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const long long total = H.ntarget * H.nbins;
@@ -486,56 +551,46 @@ int hmcmt_chain_hist(hmcmt_ctx* ctx, int64_t* count, uint32_t* counts, int32_t o
 }
 
 int hmcmt_chain_hist_quantiles(hmcmt_ctx* ctx, int32_t nq, const double* q, double* out, int32_t on_device) {
+    const char* fn = "hmcmt_chain_hist_quantiles";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_hist_quantiles", true);
-    if (rc) return rc;
     auto& H = ctx->chain.hist;
-    if (!H.on) { ctx->err = "hmcmt_chain_hist_quantiles: no histogram (hmcmt_chain_hist_begin first)"; return HMCMT_EINVAL; }
+    int rc = chain_acc_ready(ctx, fn, H.on, H.count, false, CHAIN_HIST);
+    if (rc) return rc;
     if (!q || !out || nq < 1) { ctx->err = "hmcmt_chain_hist_quantiles: need q, out and nq >= 1"; return HMCMT_EINVAL; }
     for (int i = 0; i < nq; ++i)
         if (!(q[i] >= 0.0 && q[i] <= 1.0)) { ctx->err = "hmcmt_chain_hist_quantiles: every q must lie in [0, 1]"; return HMCMT_EINVAL; }
-    if (H.count == 0) { ctx->err = "hmcmt_chain_hist_quantiles: the histogram is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    if ((rc = chain_acc_ready(ctx, fn, H.on, H.count, true, CHAIN_HIST))) return rc;      // (empty: reported behind the arguments)
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     std::vector<double> x((size_t)nq);
     for (int i = 0; i < nq; ++i) x[i] = q[i] * (double)H.count;       // (one product: what a host restatement forms)
-    double *d_x = nullptr, *d_out = nullptr;
-    const size_t ob = sizeof(double) * (size_t)nq * (size_t)H.ntarget;
-    auto run = [&]() -> int {
-        int r;
-        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_hist_quantiles", (void**)&d_x, sizeof(double) * nq))) return r;
-        if (!on_device && (r = chain_acc_alloc(ctx, "hmcmt_chain_hist_quantiles", (void**)&d_out, ob))) return r;
-        double* dst = on_device ? out : d_out;
-        HIPCHK(hipMemcpyAsync(d_x, x.data(), sizeof(double) * nq, hipMemcpyHostToDevice, st));
-        for (int q0 = 0; q0 < nq; q0 += 32768) {             // (a grid's y extent)
-            const int nc = std::min(nq - q0, 32768);
-            hipLaunchKernelGGL(k_chain_quantiles, dim3((unsigned)((H.ntarget + 255) / 256), (unsigned)nc), dim3(256), 0, st, H.ntarget, H.nbins,
-                               nc, H.lo, H.w, d_x + q0, H.d_counts, dst + (size_t)q0 * H.ntarget);
-        }
-        HIPCHK(hipGetLastError());
-        if (!on_device) HIPCHK(hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(st);
-    if (d_x) hipFree(d_x);
-    if (d_out) hipFree(d_out);
-    return rc;
+    ChainReadout R(ctx, fn, on_device);
+    double* d_x = (double*)R.scratch(sizeof(double) * nq);
+    double* dst = (double*)R.out(out, sizeof(double) * (size_t)nq * (size_t)H.ntarget);
+    if (R.rc) return R.rc;
+    HIPCHK(hipMemcpyAsync(d_x, x.data(), sizeof(double) * nq, hipMemcpyHostToDevice, st));
+    for (int q0 = 0; q0 < nq; q0 += 32768) {                 // (a grid's y extent)
+        const int nc = std::min(nq - q0, 32768);
+        hipLaunchKernelGGL(k_chain_quantiles, dim3((unsigned)((H.ntarget + 255) / 256), (unsigned)nc), dim3(256), 0, st, H.ntarget, H.nbins,
+                           nc, H.lo, H.w, d_x + q0, H.d_counts, dst + (size_t)q0 * H.ntarget);
+    }
+    return R.finish();
 }
 
 int hmcmt_chain_data_moments_begin(hmcmt_ctx* ctx) {
+    const char* fn = "hmcmt_chain_data_moments_begin";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_data_moments_begin", true);
+    int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     auto& M = ctx->chain.dmom;
     hipStream_t st = ctx->stream;
     const size_t bytes = sizeof(double) * std::max<size_t>((size_t)2 * ctx->v.nData, 1);
     M.on = false;
-    if (!M.d_mean && (rc = chain_acc_alloc(ctx, "hmcmt_chain_data_moments_begin", (void**)&M.d_mean, bytes))) return rc;
-    if (!M.d_m2 && (rc = chain_acc_alloc(ctx, "hmcmt_chain_data_moments_begin", (void**)&M.d_m2, bytes))) return rc;
-    HIPCHK(hipMemsetAsync(M.d_mean, 0, bytes, st));          // (behind a commit that may still be running on them)
+    // (a running accumulator's buffers are kept and zeroed behind a commit that may still be running on them: no wait)
+    if (!M.d_mean && (rc = chain_acc_alloc(ctx, fn, M.allocs, (void**)&M.d_mean, bytes))) return rc;
+    if (!M.d_m2 && (rc = chain_acc_alloc(ctx, fn, M.allocs, (void**)&M.d_m2, bytes))) return rc;
+    HIPCHK(hipMemsetAsync(M.d_mean, 0, bytes, st));
     HIPCHK(hipMemsetAsync(M.d_m2, 0, bytes, st));
     M.count = 0;
     M.on = true;
@@ -544,66 +599,44 @@ int hmcmt_chain_data_moments_begin(hmcmt_ctx* ctx) {
 
 int hmcmt_chain_data_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2, int32_t on_device) {
     if (!ctx) return HMCMT_EINVAL;
-    const int rc = chain_ready(ctx, "hmcmt_chain_data_moments", true);
-    if (rc) return rc;
     auto& M = ctx->chain.dmom;
-    if (!M.on) { ctx->err = "hmcmt_chain_data_moments: no data moments (hmcmt_chain_data_moments_begin first)"; return HMCMT_EINVAL; }
+    int rc = chain_acc_ready(ctx, "hmcmt_chain_data_moments", M.on, M.count, false, CHAIN_DMOM);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * 2 * ctx->v.nData;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (mean) HIPCHK(hipMemcpyAsync(mean, M.d_mean, bytes, kind, ctx->stream));
-    if (m2) HIPCHK(hipMemcpyAsync(m2, M.d_m2, bytes, kind, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if ((rc = chain_welford_out(ctx, sizeof(double) * 2 * ctx->v.nData, M.d_mean, M.d_m2, mean, m2, on_device))) return rc;
     if (count) *count = M.count;
     return 0;
 }
 
 // ---- lagged autocovariances and the effective sample size (k_chain_acov, k_chain_acov_out, k_chain_ess) ----------------------------
-static void chain_acov_free(hmcmt_ctx* ctx) {
-    auto& A = ctx->chain.acov;
-    chain_acov_time_free(ctx);
-    for (void* p : {(void*)A.d_target, (void*)A.d_x0, (void*)A.d_tot, (void*)A.d_S, (void*)A.d_H, (void*)A.d_ring}) if (p) hipFree(p);
-    A = hmcmt_ctx::Chain::Acov{};
-}
-
 int hmcmt_chain_acov_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* target, int32_t maxlag) {
+    const char* fn = "hmcmt_chain_acov_begin";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_acov_begin", true);
+    int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
-    const int n = ctx->v.nAC;
-    const bool all = !target && ntarget == 0;
-    if ((!all && (!target || ntarget < 1)) || maxlag < 1 || maxlag > CHAIN_ACOV_MAXLAG) {
-        ctx->err = "hmcmt_chain_acov_begin: need target and ntarget >= 1 (or NULL and 0: every active cell) and 1 <= maxlag <= 1023";
-        return HMCMT_EINVAL;
-    }
-    for (int64_t i = 0; i < ntarget; ++i)
-        if (target[i] < 0 || target[i] >= n) {
-            ctx->err = "hmcmt_chain_acov_begin: target " + std::to_string(i) + " = " + std::to_string(target[i]) + " is no active cell (0.." +
-                       std::to_string(n - 1) + ")";
-            return HMCMT_EINVAL;
-        }
+    long long nt = 0;
+    if ((rc = chain_cell_list(ctx, fn, "target", ntarget, target, true, maxlag >= 1 && maxlag <= CHAIN_ACOV_MAXLAG,
+                              "target and ntarget >= 1 (or NULL and 0: every active cell) and 1 <= maxlag <= 1023", &nt)))
+        return rc;
     HIPCHK(hipSetDevice(ctx->device));
     auto& A = ctx->chain.acov;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be adding to the accumulator this one replaces)
-    chain_acov_free(ctx);
-    const long long nt = all ? n : ntarget;
-    const size_t tb = (size_t)nt * sizeof(long long), vb = (size_t)nt * sizeof(double), lb = vb * (size_t)(maxlag + 1);
+    A.timer.free(ctx->device, st);
+    chain_acc_free(A.allocs); A = {};
+    const size_t vb = (size_t)nt * sizeof(double), lb = vb * (size_t)(maxlag + 1);
     auto build = [&]() -> int {
         int r;
-        if (!all && (r = chain_acc_alloc(ctx, "hmcmt_chain_acov_begin", (void**)&A.d_target, tb))) return r;
+        if ((r = chain_cell_upload(ctx, fn, A.allocs, &A.d_target, target, nt))) return r;
         const std::pair<double**, size_t> bufs[] = {{&A.d_x0, vb}, {&A.d_tot, vb}, {&A.d_S, lb}, {&A.d_H, lb}, {&A.d_ring, lb}};
-        for (const auto& b : bufs) {
-            if ((r = chain_acc_alloc(ctx, "hmcmt_chain_acov_begin", (void**)b.first, b.second))) return r;
-            HIPCHK(hipMemsetAsync(*b.first, 0, b.second, st));
-        }
-        if (!all) HIPCHK(hipMemcpyAsync(A.d_target, target, tb, hipMemcpyHostToDevice, st));
+        for (const auto& b : bufs)
+            if ((r = chain_acc_zeroed(ctx, fn, A.allocs, (void**)b.first, b.second))) return r;
         HIPCHK(hipStreamSynchronize(st));                    // (the caller's list is free again on return)
         return 0;
     };
     if ((rc = build())) {
         (void)hipStreamSynchronize(st);
-        chain_acov_free(ctx);
+        chain_acc_free(A.allocs); A = {};
         return rc;
     }
     A.ntarget = nt; A.K = maxlag; A.count = 0;
@@ -619,152 +652,91 @@ static void chain_acov_launch(hmcmt_ctx* ctx, double* d_mean, double* d_acov) {
 }
 
 int hmcmt_chain_acov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* acov, int32_t on_device) {
+    const char* fn = "hmcmt_chain_acov";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_acov", true);
-    if (rc) return rc;
     auto& A = ctx->chain.acov;
-    if (!A.on) { ctx->err = "hmcmt_chain_acov: no autocovariances (hmcmt_chain_acov_begin first)"; return HMCMT_EINVAL; }
-    if ((mean || acov) && A.count == 0) { ctx->err = "hmcmt_chain_acov: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t mb = sizeof(double) * (size_t)A.ntarget, ab = mb * (size_t)(A.K + 1);
-    double *d_mean = nullptr, *d_acov = nullptr;
-    auto run = [&]() -> int {
-        int r;
-        if (!mean && !acov) return 0;
-        if (on_device) { d_mean = mean; d_acov = acov; }
-        else {
-            if (mean && (r = chain_acc_alloc(ctx, "hmcmt_chain_acov", (void**)&d_mean, mb))) return r;
-            if (acov && (r = chain_acc_alloc(ctx, "hmcmt_chain_acov", (void**)&d_acov, ab))) return r;
-        }
+    int rc = chain_acc_ready(ctx, fn, A.on, A.count, mean || acov, CHAIN_ACOV);
+    if (rc) return rc;
+    if (mean || acov) {
+        HIPCHK(hipSetDevice(ctx->device));
+        const size_t mb = sizeof(double) * (size_t)A.ntarget;
+        ChainReadout R(ctx, fn, on_device);
+        double *d_mean = (double*)R.out(mean, mb), *d_acov = (double*)R.out(acov, mb * (size_t)(A.K + 1));
+        if (R.rc) return R.rc;
         chain_acov_launch(ctx, d_mean, d_acov);
-        HIPCHK(hipGetLastError());
-        if (!on_device) {
-            if (mean) HIPCHK(hipMemcpyAsync(mean, d_mean, mb, hipMemcpyDeviceToHost, st));
-            if (acov) HIPCHK(hipMemcpyAsync(acov, d_acov, ab, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(st);
-    if (!on_device) { if (d_mean) hipFree(d_mean); if (d_acov) hipFree(d_acov); }
-    if (!rc && count) *count = A.count;
-    return rc;
-}
-
-int hmcmt_chain_ess(hmcmt_ctx* ctx, double* tau, double* ess, int32_t* window, int32_t on_device) {
-    if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_ess", true);
-    if (rc) return rc;
-    auto& A = ctx->chain.acov;
-    if (!A.on) { ctx->err = "hmcmt_chain_ess: no autocovariances (hmcmt_chain_acov_begin first)"; return HMCMT_EINVAL; }
-    if (A.count == 0) { ctx->err = "hmcmt_chain_ess: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
-    if (!tau && !ess && !window) return 0;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t mb = sizeof(double) * (size_t)A.ntarget, ab = mb * (size_t)(A.K + 1), wb = sizeof(int) * (size_t)A.ntarget;
-    const double lg = std::max(1.0, std::log10((double)A.count));
-    double *d_acov = nullptr, *d_tau = nullptr, *d_ess = nullptr;
-    int* d_win = nullptr;
-    static_assert(sizeof(int) == sizeof(int32_t), "window is written as int");
-    auto run = [&]() -> int {
-        int r;
-        if ((r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_acov, ab))) return r;
-        if (on_device) { d_tau = tau; d_ess = ess; d_win = (int*)window; }
-        else {
-            if (tau && (r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_tau, mb))) return r;
-            if (ess && (r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_ess, mb))) return r;
-            if (window && (r = chain_acc_alloc(ctx, "hmcmt_chain_ess", (void**)&d_win, wb))) return r;
-        }
-        chain_acov_launch(ctx, nullptr, d_acov);
-        hipLaunchKernelGGL(k_chain_ess, dim3((unsigned)((A.ntarget + 255) / 256)), dim3(256), 0, st, A.ntarget, A.K, A.count,
-                           (double)A.count * lg, 1.0 / lg, d_acov, d_tau, d_ess, d_win);
-        HIPCHK(hipGetLastError());
-        if (!on_device) {
-            if (tau) HIPCHK(hipMemcpyAsync(tau, d_tau, mb, hipMemcpyDeviceToHost, st));
-            if (ess) HIPCHK(hipMemcpyAsync(ess, d_ess, mb, hipMemcpyDeviceToHost, st));
-            if (window) HIPCHK(hipMemcpyAsync(window, d_win, wb, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(st);
-    if (d_acov) hipFree(d_acov);
-    if (!on_device) { if (d_tau) hipFree(d_tau); if (d_ess) hipFree(d_ess); if (d_win) hipFree(d_win); }
-    return rc;
-}
-
-// measurement only (include/hmcmt_debug.h)
-int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches) {
-    if (!ctx) return HMCMT_EINVAL;
-    const int rc = chain_ready(ctx, "hmcmt_debug_chain_acov_time", true);
-    if (rc) return rc;
-    auto& A = ctx->chain.acov;
-    if (!A.on) { ctx->err = "hmcmt_debug_chain_acov_time: no autocovariances (hmcmt_chain_acov_begin first)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    chain_acov_time_collect(ctx);
-    for (int i = 0; i < 2; ++i) {
-        if (ms) ms[i] = A.ms[i];
-        if (launches) launches[i] = A.launches[i];
+        if ((rc = R.finish())) return rc;
     }
-    if (enable >= 0) {                                       // (the sums up to here went out; a switch starts new ones)
-        A.timing = enable != 0;
-        for (int i = 0; i < 2; ++i) { A.ms[i] = 0; A.launches[i] = 0; }
-    }
+    if (count) *count = A.count;
     return 0;
 }
 
-// ---- posterior covariance and correlation (k_chain_cov_commit, k_chain_cov_flush, k_chain_cov_out, k_chain_corr) --------------------
-static void chain_cov_free(hmcmt_ctx* ctx) {
-    auto& V = ctx->chain.cov;
-    chain_cov_time_free(ctx);
-    for (void* p : {(void*)V.d_row, (void*)V.d_x0, (void*)V.d_tot, (void*)V.d_q, (void*)V.d_pend, (void*)V.d_S}) if (p) hipFree(p);
-    V = hmcmt_ctx::Chain::Cov{};
+int hmcmt_chain_ess(hmcmt_ctx* ctx, double* tau, double* ess, int32_t* window, int32_t on_device) {
+    const char* fn = "hmcmt_chain_ess";
+    if (!ctx) return HMCMT_EINVAL;
+    auto& A = ctx->chain.acov;
+    const int rc = chain_acc_ready(ctx, fn, A.on, A.count, true, CHAIN_ACOV);
+    if (rc) return rc;
+    if (!tau && !ess && !window) return 0;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t mb = sizeof(double) * (size_t)A.ntarget;
+    const double lg = std::max(1.0, std::log10((double)A.count));
+    static_assert(sizeof(int) == sizeof(int32_t), "window is written as int");
+    ChainReadout R(ctx, fn, on_device);
+    double* d_acov = (double*)R.scratch(mb * (size_t)(A.K + 1));
+    double *d_tau = (double*)R.out(tau, mb), *d_ess = (double*)R.out(ess, mb);
+    int* d_win = (int*)R.out(window, sizeof(int) * (size_t)A.ntarget);
+    if (R.rc) return R.rc;
+    chain_acov_launch(ctx, nullptr, d_acov);
+    hipLaunchKernelGGL(k_chain_ess, dim3((unsigned)((A.ntarget + 255) / 256)), dim3(256), 0, ctx->stream, A.ntarget, A.K, A.count,
+                       (double)A.count * lg, 1.0 / lg, d_acov, d_tau, d_ess, d_win);
+    return R.finish();
 }
 
-int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* row, int32_t batch) {
+// measurement only (include/hmcmt_debug.h): the two timing entry points behind their guards
+static int chain_timer_report(hmcmt_ctx* ctx, const char* fn, bool on, const ChainAccName& name, ChainTimer& T, int32_t enable, double* ms,
+                              int64_t* launches) {
+    const int rc = chain_acc_ready(ctx, fn, on, 0, false, name);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    T.report(ctx->stream, enable, ms, launches);
+    return 0;
+}
+int hmcmt_debug_chain_acov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches) {
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_cov_begin", true);
+    return chain_timer_report(ctx, "hmcmt_debug_chain_acov_time", ctx->chain.acov.on, CHAIN_ACOV, ctx->chain.acov.timer, enable, ms, launches);
+}
+
+// ---- posterior covariance and correlation (k_chain_cov_commit, k_chain_cov_flush, k_chain_cov_out, k_chain_corr) --------------------
+int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* row, int32_t batch) {
+    const char* fn = "hmcmt_chain_cov_begin";
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
     static_assert(CHAIN_COV_BATCH_MAX == HMCMT_COV_BATCH_MAX, "the header's bound is the kernels'");
-    const int n = ctx->v.nAC;
-    const bool all = !row && nrow == 0;
-    if ((!all && (!row || nrow < 1)) || batch < 0 || batch > CHAIN_COV_BATCH_MAX) {
-        ctx->err = "hmcmt_chain_cov_begin: need row and nrow >= 1 (or NULL and 0: every active cell) and 1 <= batch <= 16 (0: the default, 8)";
-        return HMCMT_EINVAL;
-    }
-    for (int64_t i = 0; i < nrow; ++i)
-        if (row[i] < 0 || row[i] >= n) {
-            ctx->err = "hmcmt_chain_cov_begin: row " + std::to_string(i) + " = " + std::to_string(row[i]) + " is no active cell (0.." +
-                       std::to_string(n - 1) + ")";
-            return HMCMT_EINVAL;
-        }
+    long long nr = 0;
+    if ((rc = chain_cell_list(ctx, fn, "row", nrow, row, true, batch >= 0 && batch <= CHAIN_COV_BATCH_MAX,
+                              "row and nrow >= 1 (or NULL and 0: every active cell) and 1 <= batch <= 16 (0: the default, 8)", &nr)))
+        return rc;
     HIPCHK(hipSetDevice(ctx->device));
     auto& V = ctx->chain.cov;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be adding to the accumulator this one replaces)
-    chain_cov_free(ctx);
-    const long long nr = all ? n : nrow;
+    V.timer.free(ctx->device, st);
+    chain_acc_free(V.allocs); V = {};
     const int B = batch == 0 ? CHAIN_COV_BATCH_DEFAULT : batch;
-    const size_t rb = (size_t)nr * sizeof(long long), vb = (size_t)n * sizeof(double);
+    const size_t vb = (size_t)ctx->v.nAC * sizeof(double);
     auto build = [&]() -> int {
         int r;
-        if (!all && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov_begin", (void**)&V.d_row, rb))) return r;
+        if ((r = chain_cell_upload(ctx, fn, V.allocs, &V.d_row, row, nr))) return r;
         const std::pair<double**, size_t> bufs[] = {{&V.d_x0, vb}, {&V.d_tot, vb}, {&V.d_q, vb}, {&V.d_pend, vb * (size_t)B}, {&V.d_S, vb * (size_t)nr}};
-        for (const auto& b : bufs) {
-            if ((r = chain_acc_alloc(ctx, "hmcmt_chain_cov_begin", (void**)b.first, b.second))) return r;
-            HIPCHK(hipMemsetAsync(*b.first, 0, b.second, st));
-        }
-        static_assert(sizeof(long long) == sizeof(int64_t), "the row list is uploaded as it is");
-        if (!all) HIPCHK(hipMemcpyAsync(V.d_row, row, rb, hipMemcpyHostToDevice, st));
+        for (const auto& b : bufs)
+            if ((r = chain_acc_zeroed(ctx, fn, V.allocs, (void**)b.first, b.second))) return r;
         HIPCHK(hipStreamSynchronize(st));                    // (the caller's list is free again on return)
         return 0;
     };
     if ((rc = build())) {
         (void)hipStreamSynchronize(st);
-        chain_cov_free(ctx);
+        chain_acc_free(V.allocs); V = {};
         return rc;
     }
     V.nrow = nr; V.B = B; V.npend = 0; V.count = 0;
@@ -777,95 +749,49 @@ static dim3 chain_cov_grid(hmcmt_ctx* ctx, long long nrow) {
 }
 
 int hmcmt_chain_cov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* var, double* cov, int32_t on_device) {
+    const char* fn = "hmcmt_chain_cov";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_cov", true);
-    if (rc) return rc;
     auto& V = ctx->chain.cov;
-    if (!V.on) { ctx->err = "hmcmt_chain_cov: no covariance (hmcmt_chain_cov_begin first)"; return HMCMT_EINVAL; }
-    if ((mean || var || cov) && V.count == 0) { ctx->err = "hmcmt_chain_cov: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const long long n = ctx->v.nAC;
-    const size_t mb = sizeof(double) * (size_t)n, cb = mb * (size_t)V.nrow;
-    double *d_mean = nullptr, *d_var = nullptr, *d_cov = nullptr;
-    auto run = [&]() -> int {
-        int r;
-        if (!mean && !var && !cov) return 0;
-        if (on_device) { d_mean = mean; d_var = var; d_cov = cov; }
-        else {
-            if (mean && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov", (void**)&d_mean, mb))) return r;
-            if (var && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov", (void**)&d_var, mb))) return r;
-            if (cov && (r = chain_acc_alloc(ctx, "hmcmt_chain_cov", (void**)&d_cov, cb))) return r;
-        }
+    int rc = chain_acc_ready(ctx, fn, V.on, V.count, mean || var || cov, CHAIN_COV);
+    if (rc) return rc;
+    if (mean || var || cov) {
+        HIPCHK(hipSetDevice(ctx->device));
+        const long long n = ctx->v.nAC;
+        const size_t mb = sizeof(double) * (size_t)n;
+        ChainReadout R(ctx, fn, on_device);
+        double *d_mean = (double*)R.out(mean, mb), *d_var = (double*)R.out(var, mb), *d_cov = (double*)R.out(cov, mb * (size_t)V.nrow);
+        if (R.rc) return R.rc;
         if (cov) chain_cov_flush(ctx);                       // (the parked commits first: the later bits stay what they would have been)
         const long long rows = cov ? V.nrow : 1;             // (row 0's owners write mean and var)
-        hipLaunchKernelGGL(k_chain_cov_out, chain_cov_grid(ctx, rows), dim3(256), 0, st, n, rows, (double)V.count, V.d_x0, V.d_tot, V.d_q,
-                           V.d_S, V.d_row, d_mean, d_var, d_cov);
-        HIPCHK(hipGetLastError());
-        if (!on_device) {
-            if (mean) HIPCHK(hipMemcpyAsync(mean, d_mean, mb, hipMemcpyDeviceToHost, st));
-            if (var) HIPCHK(hipMemcpyAsync(var, d_var, mb, hipMemcpyDeviceToHost, st));
-            if (cov) HIPCHK(hipMemcpyAsync(cov, d_cov, cb, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(st);
-    if (!on_device) { if (d_mean) hipFree(d_mean); if (d_var) hipFree(d_var); if (d_cov) hipFree(d_cov); }
-    if (!rc && count) *count = V.count;
-    return rc;
+        hipLaunchKernelGGL(k_chain_cov_out, chain_cov_grid(ctx, rows), dim3(256), 0, ctx->stream, n, rows, (double)V.count, V.d_x0, V.d_tot,
+                           V.d_q, V.d_S, V.d_row, d_mean, d_var, d_cov);
+        if ((rc = R.finish())) return rc;
+    }
+    if (count) *count = V.count;
+    return 0;
 }
 
 int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device) {
+    const char* fn = "hmcmt_chain_corr";
     if (!ctx) return HMCMT_EINVAL;
-    int rc = chain_ready(ctx, "hmcmt_chain_corr", true);
-    if (rc) return rc;
     auto& V = ctx->chain.cov;
-    if (!V.on) { ctx->err = "hmcmt_chain_corr: no covariance (hmcmt_chain_cov_begin first)"; return HMCMT_EINVAL; }
-    if (V.count == 0) { ctx->err = "hmcmt_chain_corr: the accumulator is empty (no commit behind the burn-in yet)"; return HMCMT_EINVAL; }
+    const int rc = chain_acc_ready(ctx, fn, V.on, V.count, true, CHAIN_COV);
+    if (rc) return rc;
     if (!corr) return 0;
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     const long long n = ctx->v.nAC;
-    const size_t cb = sizeof(double) * (size_t)n * (size_t)V.nrow;
-    double* d_corr = nullptr;
-    auto run = [&]() -> int {
-        int r;
-        if (on_device) d_corr = corr;
-        else if ((r = chain_acc_alloc(ctx, "hmcmt_chain_corr", (void**)&d_corr, cb))) return r;
-        chain_cov_flush(ctx);
-        hipLaunchKernelGGL(k_chain_corr, chain_cov_grid(ctx, V.nrow), dim3(256), 0, st, n, V.nrow, (double)V.count, V.d_tot, V.d_q, V.d_S,
-                           V.d_row, d_corr);
-        HIPCHK(hipGetLastError());
-        if (!on_device) HIPCHK(hipMemcpyAsync(corr, d_corr, cb, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    };
-    rc = run();
-    if (rc) (void)hipStreamSynchronize(st);
-    if (!on_device && d_corr) hipFree(d_corr);
-    return rc;
+    ChainReadout R(ctx, fn, on_device);
+    double* d_corr = (double*)R.out(corr, sizeof(double) * (size_t)n * (size_t)V.nrow);
+    if (R.rc) return R.rc;
+    chain_cov_flush(ctx);
+    hipLaunchKernelGGL(k_chain_corr, chain_cov_grid(ctx, V.nrow), dim3(256), 0, ctx->stream, n, V.nrow, (double)V.count, V.d_tot, V.d_q, V.d_S,
+                       V.d_row, d_corr);
+    return R.finish();
 }
 
-// measurement only (include/hmcmt_debug.h)
 int hmcmt_debug_chain_cov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches) {
     if (!ctx) return HMCMT_EINVAL;
-    const int rc = chain_ready(ctx, "hmcmt_debug_chain_cov_time", true);
-    if (rc) return rc;
-    auto& V = ctx->chain.cov;
-    if (!V.on) { ctx->err = "hmcmt_debug_chain_cov_time: no covariance (hmcmt_chain_cov_begin first)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
-    chain_cov_time_collect(ctx);
-    for (int i = 0; i < 2; ++i) {
-        if (ms) ms[i] = V.ms[i];
-        if (launches) launches[i] = V.launches[i];
-    }
-    if (enable >= 0) {                                       // (the sums up to here went out; a switch starts new ones)
-        V.timing = enable != 0;
-        for (int i = 0; i < 2; ++i) { V.ms[i] = 0; V.launches[i] = 0; }
-    }
-    return 0;
+    return chain_timer_report(ctx, "hmcmt_debug_chain_cov_time", ctx->chain.cov.on, CHAIN_COV, ctx->chain.cov.timer, enable, ms, launches);
 }
 
 int hmcmt_chain_end(hmcmt_ctx* ctx) {

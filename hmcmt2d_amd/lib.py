@@ -743,20 +743,29 @@ class HipContext:
             return int(n.value), mean[0::2].copy(), m2[0::2].copy()
         return int(n.value), mean.view(np.complex128), m2.view(np.complex128)
 
+    def _cell_list(self, arg, what):
+        """(n, list, rows) of a begin's list of active cells: what the library takes (0, None for arg = None: every active cell) and
+        the rows the accumulator gets; `what`: the error of an empty list."""
+        if arg is None:
+            return 0, None, self.nAC
+        t = np.ascontiguousarray(arg, dtype=np.int64).reshape(-1)
+        if len(t) == 0:
+            raise ValueError(f"{what} (None means every active cell)")
+        return len(t), t.ctypes.data_as(c_int64_p), len(t)
+
+    def _chain_timing(self, fn, enable, names):
+        """{name: (ms, launches)} of the two classes of a measurement-only timer of the commit (include/hmcmt_debug.h)."""
+        ms, n = np.zeros(2), np.zeros(2, dtype=np.int64)
+        self._check(fn(self.h, -1 if enable is None else int(bool(enable)), _dp(ms), n.ctypes.data_as(c_int64_p)))
+        return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(names)}
+
     # -- effective sample size from the chain's commit (hmcmt_chain_acov_*, hmcmt_chain_ess) --
     def chain_acov_begin(self, targets=None, maxlag=63):
         """Starts per-cell lagged autocovariances of ln sigma for the lags 0 .. maxlag (1 .. 1023) of the active-cell indices `targets`
         (0-based, repeats allowed; None: every active cell): every later commit behind the burn-in counts.  Replaces an accumulator
         that is running."""
-        if targets is None:
-            self._check(self.lib.hmcmt_chain_acov_begin(self.h, 0, None, int(maxlag)))
-            nt = self.nAC
-        else:
-            t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
-            if len(t) == 0:
-                raise ValueError("chain_acov_begin: no target (None means every active cell)")
-            self._check(self.lib.hmcmt_chain_acov_begin(self.h, len(t), t.ctypes.data_as(c_int64_p), int(maxlag)))
-            nt = len(t)
+        n, t, nt = self._cell_list(targets, "chain_acov_begin: no target")
+        self._check(self.lib.hmcmt_chain_acov_begin(self.h, n, t, int(maxlag)))
         self._acov_shape = (int(maxlag) + 1, nt)
 
     def chain_acov_count(self):
@@ -773,10 +782,7 @@ class HipContext:
         """Measurement only (hmcmt_debug_chain_acov_time): enable = True / False switches HIP-event pairs round every k_chain_acov
         launch on / off and zeroes the sums, None only reads.  Returns the sums up to the call: {"filling": (ms, launches), "steady": (ms, launches)}: the
         commits with count < maxlag, where some lag still fills its H_k, and those behind them."""
-        ms, n = np.zeros(2), np.zeros(2, dtype=np.int64)
-        self._check(self.lib.hmcmt_debug_chain_acov_time(self.h, -1 if enable is None else int(bool(enable)), _dp(ms),
-                                                         n.ctypes.data_as(c_int64_p)))
-        return {"filling": (float(ms[0]), int(n[0])), "steady": (float(ms[1]), int(n[1]))}
+        return self._chain_timing(self.lib.hmcmt_debug_chain_acov_time, enable, ("filling", "steady"))
 
     def chain_acov(self):
         """(count, mean[ntarget], acov[maxlag + 1, ntarget]): commits in the accumulator, the targets' means and the biased
@@ -809,15 +815,8 @@ class HipContext:
         """Starts the cross moments of ln sigma between the active-cell indices `rows` (0-based, repeats allowed; None: every active
         cell, the full matrix) and every active cell: every later commit behind the burn-in counts.  `batch` commits (1 .. 16, 0: the
         default 8) are folded into the sums by one kernel; the results do not depend on it.  Replaces an accumulator that is running."""
-        if rows is None:
-            self._check(self.lib.hmcmt_chain_cov_begin(self.h, 0, None, int(batch)))
-            nr = self.nAC
-        else:
-            r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-            if len(r) == 0:
-                raise ValueError("chain_cov_begin: no row (None means every active cell)")
-            self._check(self.lib.hmcmt_chain_cov_begin(self.h, len(r), r.ctypes.data_as(c_int64_p), int(batch)))
-            nr = len(r)
+        n, r, nr = self._cell_list(rows, "chain_cov_begin: no row")
+        self._check(self.lib.hmcmt_chain_cov_begin(self.h, n, r, int(batch)))
         self._cov_shape = (nr, self.nAC)
 
     def chain_cov_count(self):
@@ -830,10 +829,7 @@ class HipContext:
         """Measurement only (hmcmt_debug_chain_cov_time): enable = True / False switches HIP-event pairs round every commit and flush
         kernel of the accumulator on / off and zeroes the sums, None only reads.  Returns the sums up to the call:
         {"commit": (ms, launches), "flush": (ms, launches)}."""
-        ms, n = np.zeros(2), np.zeros(2, dtype=np.int64)
-        self._check(self.lib.hmcmt_debug_chain_cov_time(self.h, -1 if enable is None else int(bool(enable)), _dp(ms),
-                                                        n.ctypes.data_as(c_int64_p)))
-        return {"commit": (float(ms[0]), int(n[0])), "flush": (float(ms[1]), int(n[1]))}
+        return self._chain_timing(self.lib.hmcmt_debug_chain_cov_time, enable, ("commit", "flush"))
 
     def chain_cov(self):
         """(count, mean[nAC], var[nAC], cov[nrow, nAC]): commits in the accumulator, the cells' means and biased variances, and the

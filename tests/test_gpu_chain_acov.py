@@ -158,6 +158,49 @@ def test_a_begin_in_front_of_step_5_counts_only_later_commits():
     check_acov(early, early["committed"], None, 8, P.n)
 
 
+def test_device_read_out_with_any_of_the_outputs_null():
+    """The device paths of hmcmt_chain_acov and hmcmt_chain_ess with every choice of outputs: each one asked for holds the bytes of
+    the read-out of all of them (which are the host path's) between intact guard words, and hmcmt_chain_acov's count comes with each.
+    Ten commits on tiny, 7 lags, a target list with a repeat."""
+    import itertools
+    import torch
+    P = problem("tiny")
+    n, G, K = P.n, 16, 7
+    seq = SEQ + SEQ[:4]
+    targets = np.array([5, 5, n - 1, 0])
+    nt = len(targets)
+    sizes = {"mean": nt, "acov": (K + 1) * nt, "tau": nt, "ess": nt, "window": nt}
+    dev = torch.device("cuda", 0)
+    ctx = P.context()
+
+    def read(fn, names, which):
+        """fn into guarded device arrays for the outputs `which` of its outputs `names`, None for the others"""
+        fill = lambda k: (torch.int32, 7) if k == "window" else (torch.float64, -77.0)
+        bufs = {k: torch.full((G + sizes[k] + G,), fill(k)[1], dtype=fill(k)[0], device=dev) for k in which}
+        torch.cuda.synchronize()
+        ret = fn(*(bufs[k][G:].data_ptr() if k in bufs else None for k in names))
+        out = {}
+        for k, t in bufs.items():
+            a = t.cpu().numpy()
+            assert np.all(a[:G] == fill(k)[1]) and np.all(a[G + sizes[k]:] == fill(k)[1]), (which, k)
+            out[k] = a[G:G + sizes[k]].tobytes()
+        return ret, out
+
+    try:
+        run_chain(P, ctx, seq, seed=SEED, full=False, between=lambda it: ctx.chain_acov_begin(targets, K) if it == 0 else None)
+        ncommit = len(seq) - BURNIN
+        host = dict(zip(sizes, ctx.chain_acov()[1:] + ctx.chain_ess()))
+        for fn, names in ((ctx.chain_acov_device, ("mean", "acov")), (ctx.chain_ess, ("tau", "ess", "window"))):
+            ret, full = read(fn, names, names)
+            assert ret == (ncommit if fn == ctx.chain_acov_device else None) and all(full[k] == host[k].tobytes() for k in names)
+            for r in range(0 if fn == ctx.chain_acov_device else 1, len(names)):      # (chain_ess without a pointer is the host path)
+                for which in itertools.combinations(names, r):
+                    got = read(fn, names, which)
+                    assert got[0] == ret and set(got[1]) == set(which) and all(got[1][k] == full[k] for k in which), which
+    finally:
+        ctx.close()
+
+
 def test_an_all_rejected_chain_gives_exact_zeros():
     P = problem("tiny")
     run = chain(P, acov=(None, 7), seq="R" * 8)

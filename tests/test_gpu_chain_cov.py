@@ -181,6 +181,66 @@ def test_a_begin_in_front_of_step_5_and_a_read_out_inside_a_batch():
     assert same(mid["cov"][1:] + (mid["corr"],), whole)
 
 
+def test_device_read_out_with_any_of_the_outputs_null():
+    """The device path of hmcmt_chain_cov with every choice of outputs: each one asked for holds the bytes of the read-out of all
+    three between intact guard words, the count comes with each.  Ten commits at batch 8 on tiny (one flush in the commit, two
+    commits parked), a row list with a repeat.  Read-outs of the mean, the variance or both inside a batch flush nothing (the flush
+    launches are counted by the timing hook), and the read-out of all three behind them gives the bits of the chain that was never
+    read out in between."""
+    import itertools
+    import torch
+    P = problem("tiny")
+    n, G = P.n, 16
+    seq = SEQ + SEQ[:4]
+    ncommit = len(seq) - BURNIN
+    rows = np.array([5, 5, n - 1, 0])
+    sizes = {"mean": n, "var": n, "cov": len(rows) * n}
+    dev = torch.device("cuda", 0)
+
+    def read(ctx, which):
+        bufs = {k: torch.full((G + sizes[k] + G,), -77.0, dtype=torch.float64, device=dev) for k in which}
+        torch.cuda.synchronize()
+        count = ctx.chain_cov_device(*(bufs[k][G:].data_ptr() if k in bufs else None for k in sizes))
+        out = {}
+        for k, t in bufs.items():
+            a = t.cpu().numpy()
+            assert np.all(a[:G] == -77.0) and np.all(a[G + sizes[k]:] == -77.0), (which, k)
+            out[k] = a[G:G + sizes[k]].tobytes()
+        return count, out
+
+    def run(mid):
+        ctx = P.context()
+        seen = []
+        try:
+            def between(it):
+                if it == 0:
+                    ctx.chain_cov_begin(rows, 8)
+                    ctx.chain_cov_timing(True)
+                if it > BURNIN:
+                    seen.append(ctx.chain_state()[0])                 # (what step it - 1 committed)
+                if mid and it in (5, 11):                             # three commits parked, one parked
+                    for which in (("mean",), ("var",), ("mean", "var")):
+                        count, got = read(ctx, which)
+                        st = E.accumulate(np.array(seen).T, rows, 8)
+                        assert count == it - BURNIN == len(seen) and all(got[k] == a.tobytes() for k, a in zip(("mean", "var"), E.readout(st)) if k in got)
+
+            run_chain(P, ctx, seq, seed=SEED, full=False, between=between)
+            assert ctx.chain_cov_timing()["flush"][1] == 1            # (the commit's, at the eighth)
+            count, full = read(ctx, tuple(sizes))
+            assert count == ncommit and ctx.chain_cov_timing()["flush"][1] == 2
+            if not mid:
+                assert all(full[k] == a.tobytes() for k, a in zip(sizes, ctx.chain_cov()[1:]))      # (the host path)
+                for r in range(len(sizes)):
+                    for which in itertools.combinations(sizes, r):
+                        count, got = read(ctx, which)
+                        assert count == ncommit and set(got) == set(which) and all(got[k] == full[k] for k in which), which
+            return full
+        finally:
+            ctx.close()
+
+    assert run(mid=True) == run(mid=False)
+
+
 def test_an_all_rejected_chain_gives_exact_zeros():
     P = problem("tiny")
     run = chain(P, cov=(None, 3), seq="R" * 8)
