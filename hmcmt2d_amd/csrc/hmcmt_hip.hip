@@ -305,6 +305,17 @@ struct hmcmt_ctx {
             std::vector<void*> allocs;
             ChainTimer timer;                         // every launch of the commit: class 0 k_chain_cov_commit, 1 k_chain_cov_flush
         } cov;
+        struct Adapt {                                // hmcmt_chain_adapt_*: warm-up of dt and of the diagonal of M^-1 (hmcmt_items.h: item_adapt_*)
+            bool begun = false, active = false;       // begun: in this chain, running or ended (hmcmt_chain_adapt_info)
+            hmcmt_adapt_options opt{};
+            AdaptDA da{};
+            long long c = 0;                          // steps adapted so far
+            long long wcount = 0, wnext = -1, wsize = 0;   // samples in the open window, its last step (-1: none follows), its length
+            int windowsDone = 0;
+            double alphaLast = 0, alphaSum = 0;
+            double *d_mean = nullptr, *d_m2 = nullptr;   // [nAC] each: the window's Welford accumulator (adapt_mass)
+            std::vector<void*> allocs;
+        } adapt;
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)

@@ -878,6 +878,55 @@ HD void item_chain_welford(const double* m, double* mean, double* m2, double cou
     mean[a] = mu;
     m2[a] += d * (x - mu);
 }
+// Warm-up adaptation (hmcmt_chain_adapt_*, include/hmcmt.h has the semantics).  The dual averaging of the step size (Nesterov's, in
+// Stan's form) is scalar host work in double; the window's variance is item_chain_welford on the window's own buffers, and
+// item_adapt_mass turns it into the diagonal of M^-1.  x = ln dt throughout.
+struct AdaptDA {
+    double mu = 0, s_bar = 0, x_bar = 0, x = 0;
+    long long t = 0;               // updates since the last restart
+};
+// a restart around the step size dt: at the begin call and behind every mass update
+HD void item_adapt_restart(AdaptDA& d, double dt) {
+    d.mu = log(10.0 * dt);
+    d.s_bar = d.x_bar = 0.0;
+    d.x = log(dt);
+    d.t = 0;
+}
+// one update with the acceptance probability alpha of the step just decided, in exactly this order; returns x
+HD double item_adapt_update(AdaptDA& d, double alpha, double delta, double gamma, double t0, double kappa) {
+    d.t += 1;
+    const double t = (double)d.t;
+    const double eta = 1.0 / (t + t0);
+    d.s_bar = (1.0 - eta) * d.s_bar + eta * (delta - alpha);
+    d.x = d.mu - d.s_bar * sqrt(t) / gamma;
+    const double x_eta = pow(t, -kappa);
+    d.x_bar = (1.0 - x_eta) * d.x_bar + x_eta * d.x;
+    return d.x;
+}
+// dt = exp(x) clipped into [dt_min, dt_max] where set (0: no bound on that side); x is held to +-700 first, so that dt and 10 dt
+// stay finite and positive whatever the acceptances were
+HD double item_adapt_dt(double x, double dt_min, double dt_max) {
+    double dt = exp(x > 700.0 ? 700.0 : (x < -700.0 ? -700.0 : x));
+    if (dt_min > 0.0 && dt < dt_min) dt = dt_min;
+    if (dt_max > 0.0 && dt > dt_max) dt = dt_max;
+    return dt;
+}
+// Stan's window schedule, steps counted from 0.  The first window ends at step init + base - 1 (*size = base).  `end` is the step whose
+// window just closed and *size that window's length: returns the step the next window ends at and doubles *size, or -1 when `end` was
+// the last one, W - term - 1.  A window that would leave less than its own double in front of the terminal buffer runs up to it.
+HD long long item_adapt_next_window(long long end, long long* size, long long W, long long term) {
+    const long long last = W - term - 1;
+    if (end == last) return -1;
+    *size *= 2;
+    long long next = end + *size;
+    if (next != last && next + 2 * *size >= W - term) next = last;
+    return next;
+}
+// cell a's entry of diag(M^-1) from a window of n >= 2 samples: the sample variance m2 / (n - 1) shrunk towards 1e-3;
+// nm1 = n - 1, w = n / (n + 5) and f = 1e-3 * 5 / (n + 5) are formed by the caller as doubles.  m2 == 0 gives f exactly.
+HD double item_adapt_mass(const double* m2, double nm1, double w, double f, int a) {
+    return (m2[a] / nm1) * w + f;
+}
 // Histograms of the committed models (hmcmt_chain_hist_*).  The counters lie BIN-MAJOR, counts[b * ntarget + r]: row r belongs to
 // thread r alone, and the rows of a wavefront -- neighbouring cells, whose values fall into the same or adjacent bins -- touch a few
 // cache lines per commit where a target-major array would touch one line per lane; the quantile scan reads the same way.

@@ -5,7 +5,8 @@
 // CHAIN_REC scalars down; with outputs, nAC + 2 nData doubles more.  Launches per sample beyond leapfrog_core's (diagonal mass):
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
 // k_chain_hist, a second k_chain_welford (the predicted data), k_chain_acov (lagged autocovariances) and k_chain_cov_commit (cross
-// moments; every `batch` commits k_chain_cov_flush) behind them.
+// moments; every `batch` commits k_chain_cov_flush) behind them.  During a warm-up (hmcmt_chain_adapt_*) a k_chain_welford on the
+// window's buffers inside a window and k_chain_adapt_mass at a window's end follow the commit.
 //
 // The four accumulators share their host scaffolding, which stands in front of them: ChainTimer (the event pairs of the measurement
 // hooks), chain_acc_alloc / chain_acc_free (each accumulator's struct owns its buffers through `allocs`), chain_acc_ready (the
@@ -205,7 +206,7 @@ static void chain_acc_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     C.acov.timer.free(ctx->device, ctx->stream);
     C.cov.timer.free(ctx->device, ctx->stream);
-    if (!C.hist.allocs.empty() || !C.dmom.allocs.empty() || !C.acov.allocs.empty() || !C.cov.allocs.empty()) {
+    if (!C.hist.allocs.empty() || !C.dmom.allocs.empty() || !C.acov.allocs.empty() || !C.cov.allocs.empty() || !C.adapt.allocs.empty()) {
         hipSetDevice(ctx->device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be counting)
     }
@@ -213,6 +214,7 @@ static void chain_acc_release(hmcmt_ctx* ctx) {
     chain_acc_free(C.dmom.allocs); C.dmom = {};
     chain_acc_free(C.acov.allocs); C.acov = {};
     chain_acc_free(C.cov.allocs); C.cov = {};
+    chain_acc_free(C.adapt.allocs); C.adapt = {};
 }
 
 static void chain_release(hmcmt_ctx* ctx) {
@@ -254,6 +256,41 @@ static int chain_fail(hmcmt_ctx* ctx, int rc) {
     ctx->lfHaveGrad = false;
     ctx->chain.nextStart = 0;
     return rc;
+}
+
+// One counted step of the warm-up (hmcmt.h: 1. to 5.), behind the decision and the commit: launches on the context's stream and scalar
+// host work, no wait.  The mass kernel runs behind the commit, in front of the next k_chain_momentum.
+static void chain_adapt_step(hmcmt_ctx* ctx, double hdif) {
+    auto& C = ctx->chain;
+    auto& A = C.adapt;
+    const hmcmt_adapt_options& o = A.opt;
+    const int n = ctx->v.nAC;
+    hipStream_t st = ctx->stream;
+    const double alpha = hdif > 0 ? 1.0 : std::exp(hdif);
+    A.alphaLast = alpha;
+    A.alphaSum += alpha;
+    const bool inWindow = o.adapt_mass && A.c >= o.init_buffer && A.c < o.nwarmup - o.term_buffer;
+    if (inWindow) {
+        ++A.wcount;
+        hipLaunchKernelGGL(k_chain_welford, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_m[C.cur], A.d_mean, A.d_m2, (double)A.wcount);
+    }
+    C.dt = item_adapt_dt(item_adapt_update(A.da, alpha, o.delta, o.gamma, o.t0, o.kappa), o.dt_min, o.dt_max);
+    if (inWindow && A.c == A.wnext) {
+        if (A.wcount >= 2) {
+            const double dn = (double)A.wcount, w = dn / (dn + 5.0), f = 1e-3 * 5.0 / (dn + 5.0);
+            hipLaunchKernelGGL(k_chain_adapt_mass, dim3((n + 255) / 256), dim3(256), 0, st, n, A.d_m2, dn - 1.0, w, f, ctx->d_invM);
+            ++A.windowsDone;
+            item_adapt_restart(A.da, C.dt);
+        }
+        (void)hipMemsetAsync(A.d_mean, 0, sizeof(double) * n, st);
+        (void)hipMemsetAsync(A.d_m2, 0, sizeof(double) * n, st);
+        A.wcount = 0;
+        A.wnext = item_adapt_next_window(A.c, &A.wsize, o.nwarmup, o.term_buffer);
+    }
+    if (++A.c == o.nwarmup) {
+        if (A.da.t > 0) C.dt = item_adapt_dt(A.da.x_bar, o.dt_min, o.dt_max);
+        A.active = false;
+    }
 }
 
 int hmcmt_chain_begin(hmcmt_ctx* ctx, const double* m_start, double dt, double regParam, double lnSigMin, double lnSigMax,
@@ -434,6 +471,7 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
             if (++V.npend == V.B) chain_cov_flush(ctx);
         }
     }
+    if (C.adapt.active) chain_adapt_step(ctx, hdif);
     C.gen = ctx->stateGen;
     rec->accepted = accepted ? 1 : 0;
     rec->nfevals = evals - (startGrad != 0 ? 1 : 0);
@@ -792,6 +830,143 @@ int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device) {
 int hmcmt_debug_chain_cov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches) {
     if (!ctx) return HMCMT_EINVAL;
     return chain_timer_report(ctx, "hmcmt_debug_chain_cov_time", ctx->chain.cov.on, CHAIN_COV, ctx->chain.cov.timer, enable, ms, launches);
+}
+
+// ---- the chain's step size and diagonal mass between two steps, and their warm-up adaptation (chain_adapt_step, k_chain_adapt_mass) ----
+int hmcmt_chain_set_dt(hmcmt_ctx* ctx, double dt) {
+    const char* fn = "hmcmt_chain_set_dt";
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    if (!(dt > 0) || !std::isfinite(dt)) { ctx->err = std::string(fn) + ": need a finite dt > 0"; return HMCMT_EINVAL; }
+    if (ctx->chain.adapt.active) { ctx->err = std::string(fn) + ": an adaptation is active (hmcmt_chain_adapt_end first)"; return HMCMT_EINVAL; }
+    ctx->chain.dt = dt;
+    return 0;
+}
+
+int hmcmt_chain_set_mass_diag(hmcmt_ctx* ctx, const double* invM) {
+    const char* fn = "hmcmt_chain_set_mass_diag";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!invM) { ctx->err = std::string(fn) + ": invM is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    auto& C = ctx->chain;
+    if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) { ctx->err = std::string(fn) + ": the mass is HMCMT_MASS_WM, which has no diagonal to set"; return HMCMT_EINVAL; }
+    if (C.adapt.active && C.adapt.opt.adapt_mass) {
+        ctx->err = std::string(fn) + ": an adaptation of the mass is active (hmcmt_chain_adapt_end first)";
+        return HMCMT_EINVAL;
+    }
+    const int n = ctx->v.nAC;
+    for (int i = 0; i < n; ++i)
+        if (!(invM[i] > 0) || !std::isfinite(invM[i])) { ctx->err = std::string(fn) + ": every entry must be finite and > 0"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->device));
+    C.haveMomentum = false;                                  // (its K0 belongs to the old mass)
+    std::memcpy(ctx->h_stage, invM, sizeof(double) * n);
+    HIPCHK(hipMemcpyAsync(ctx->d_invM, ctx->h_stage, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (the staging buffer is free again on return)
+    return 0;
+}
+
+int hmcmt_chain_mass_diag(hmcmt_ctx* ctx, double* invM, int32_t on_device) {
+    const char* fn = "hmcmt_chain_mass_diag";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!invM) { ctx->err = std::string(fn) + ": invM is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(invM, ctx->d_invM, sizeof(double) * ctx->v.nAC, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+void hmcmt_default_adapt_options(hmcmt_adapt_options* o) {
+    if (!o) return;
+    *o = hmcmt_adapt_options{};
+    o->adapt_mass = 1;
+    o->init_buffer = 75; o->term_buffer = 50; o->base_window = 25;
+    o->delta = 0.8; o->gamma = 0.05; o->t0 = 10.0; o->kappa = 0.75;
+}
+
+int hmcmt_chain_adapt_begin(hmcmt_ctx* ctx, const hmcmt_adapt_options* o) {
+    const char* fn = "hmcmt_chain_adapt_begin";
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    if (!o) { ctx->err = std::string(fn) + ": options is NULL (the defaults leave nwarmup open)"; return HMCMT_EINVAL; }
+    const bool finite = std::isfinite(o->delta) && std::isfinite(o->gamma) && std::isfinite(o->t0) && std::isfinite(o->kappa) &&
+                        std::isfinite(o->dt_min) && std::isfinite(o->dt_max);
+    if (!finite || o->nwarmup < 1 || !(o->delta > 0 && o->delta < 1) || !(o->gamma > 0) || !(o->t0 > 0) || !(o->kappa > 0.5 && o->kappa <= 1) ||
+        o->dt_min < 0 || o->dt_max < 0 || (o->dt_min > 0 && o->dt_max > 0 && o->dt_min > o->dt_max)) {
+        ctx->err = std::string(fn) + ": need nwarmup >= 1, 0 < delta < 1, gamma > 0, t0 > 0, 0.5 < kappa <= 1 and finite 0 <= dt_min <= dt_max (0: no bound)";
+        return HMCMT_EINVAL;
+    }
+    if (o->adapt_mass) {
+        if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) { ctx->err = std::string(fn) + ": adapt_mass needs HMCMT_MASS_DIAGONAL"; return HMCMT_EINVAL; }
+        if (o->init_buffer < 0 || o->term_buffer < 0 || o->base_window < 1 ||
+            (int64_t)o->init_buffer + o->base_window + o->term_buffer > o->nwarmup) {
+            ctx->err = std::string(fn) + ": adapt_mass needs init_buffer, term_buffer >= 0, base_window >= 1 and init_buffer + base_window + term_buffer <= nwarmup";
+            return HMCMT_EINVAL;
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    auto& C = ctx->chain;
+    auto& A = C.adapt;
+    hipStream_t st = ctx->stream;
+    if (!A.allocs.empty()) HIPCHK(hipStreamSynchronize(st));    // (a step may still be adding to the window this one replaces)
+    chain_acc_free(A.allocs); A = {};
+    if (o->adapt_mass) {
+        const size_t vb = sizeof(double) * (size_t)ctx->v.nAC;
+        if ((rc = chain_acc_zeroed(ctx, fn, A.allocs, (void**)&A.d_mean, vb)) || (rc = chain_acc_zeroed(ctx, fn, A.allocs, (void**)&A.d_m2, vb))) {
+            (void)hipStreamSynchronize(st);
+            chain_acc_free(A.allocs); A = {};
+            return rc;
+        }
+    }
+    A.opt = *o;
+    A.opt.adapt_mass = o->adapt_mass ? 1 : 0;
+    item_adapt_restart(A.da, C.dt);
+    A.wsize = o->base_window;
+    A.wnext = o->adapt_mass ? (long long)o->init_buffer + o->base_window - 1 : -1;
+    A.begun = A.active = true;
+    return 0;
+}
+
+// what the info and end calls check first
+static int chain_adapt_ready(hmcmt_ctx* ctx, const char* fn) {
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    if (!ctx->chain.adapt.begun) { ctx->err = std::string(fn) + ": no adaptation in this chain (hmcmt_chain_adapt_begin first)"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+int hmcmt_chain_adapt_info(hmcmt_ctx* ctx, hmcmt_adapt_info* info) {
+    const char* fn = "hmcmt_chain_adapt_info";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!info) { ctx->err = std::string(fn) + ": info is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_adapt_ready(ctx, fn);
+    if (rc) return rc;
+    const auto& C = ctx->chain;
+    const auto& A = C.adapt;
+    std::memset(info, 0, sizeof *info);                      // (the padding too: two infos of one state compare equal as bytes)
+    info->step = A.c; info->nwarmup = A.opt.nwarmup; info->window_count = A.wcount; info->next_window_end = A.wnext;
+    info->active = A.active ? 1 : 0; info->windows_done = A.windowsDone;
+    info->dt = C.dt;
+    info->dt_bar = A.da.t > 0 ? item_adapt_dt(A.da.x_bar, A.opt.dt_min, A.opt.dt_max) : C.dt;
+    info->mu = A.da.mu; info->s_bar = A.da.s_bar; info->alpha_last = A.alphaLast; info->alpha_sum = A.alphaSum;
+    return 0;
+}
+
+int hmcmt_chain_adapt_end(hmcmt_ctx* ctx) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_adapt_ready(ctx, "hmcmt_chain_adapt_end");
+    if (rc) return rc;
+    auto& C = ctx->chain;
+    auto& A = C.adapt;
+    if (A.active) {
+        if (A.da.t > 0) C.dt = item_adapt_dt(A.da.x_bar, A.opt.dt_min, A.opt.dt_max);
+        A.active = false;                                    // (the window's buffers go with the chain, or with the next begin call)
+    }
+    return 0;
 }
 
 int hmcmt_chain_end(hmcmt_ctx* ctx) {

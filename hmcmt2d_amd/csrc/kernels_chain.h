@@ -49,6 +49,11 @@ __global__ void k_chain_welford(int n, const double* __restrict__ m, double* __r
     const int a = TID1;
     if (a < n) item_chain_welford(m, mean, m2, count, a);
 }
+// the end of a warm-up window (hmcmt_chain_adapt_*): the diagonal of M^-1 from the window's sums of squared deviations
+__global__ void k_chain_adapt_mass(int n, const double* __restrict__ m2, double nm1, double w, double f, double* __restrict__ invM) {
+    const int a = TID1;
+    if (a < n) invM[a] = item_adapt_mass(m2, nm1, w, f, a);
+}
 // one count per target row for the chain's current model: thread r owns row r (bin-major counters, hmcmt_items.h), no atomics
 __global__ __launch_bounds__(256) void k_chain_hist(long long ntarget, int nbins, double lo, double scale, const double* __restrict__ m,
                                                     const long long* __restrict__ target, unsigned int* __restrict__ counts) {

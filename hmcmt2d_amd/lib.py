@@ -64,6 +64,20 @@ class ChainRecord(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class AdaptOptions(C.Structure):
+    """hmcmt_adapt_options (include/hmcmt.h): the warm-up hmcmt_chain_adapt_begin starts."""
+    _fields_ = [("nwarmup", C.c_int64), ("adapt_mass", C.c_int32), ("init_buffer", C.c_int32), ("term_buffer", C.c_int32),
+                ("base_window", C.c_int32), ("delta", C.c_double), ("gamma", C.c_double), ("t0", C.c_double), ("kappa", C.c_double),
+                ("dt_min", C.c_double), ("dt_max", C.c_double)]
+
+
+class AdaptInfo(C.Structure):
+    """hmcmt_adapt_info (include/hmcmt.h): where a warm-up stands."""
+    _fields_ = [("step", C.c_int64), ("nwarmup", C.c_int64), ("window_count", C.c_int64), ("next_window_end", C.c_int64),
+                ("active", C.c_int32), ("windows_done", C.c_int32), ("dt", C.c_double), ("dt_bar", C.c_double), ("mu", C.c_double),
+                ("s_bar", C.c_double), ("alpha_last", C.c_double), ("alpha_sum", C.c_double)]
+
+
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU."""
     newest = max(os.path.getmtime(f) for f in SOURCES + HEADERS)
@@ -152,8 +166,16 @@ def load_library():
     for name in ("hmcmt_jvp_block", "hmcmt_jtvp_block", "hmcmt_gn_hessvec_block"):
         getattr(lib, name).argtypes = [vp, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(Stats)]
         getattr(lib, name + "_device").argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(Stats)]
-    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS:
+    for name in JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS:
         getattr(lib, name).restype = C.c_int
+    lib.hmcmt_chain_set_dt.argtypes = [vp, C.c_double]
+    lib.hmcmt_chain_set_mass_diag.argtypes = [vp, c_double_p]
+    lib.hmcmt_chain_mass_diag.argtypes = [vp, vp, C.c_int32]
+    lib.hmcmt_default_adapt_options.argtypes = [C.POINTER(AdaptOptions)]
+    lib.hmcmt_default_adapt_options.restype = None
+    lib.hmcmt_chain_adapt_begin.argtypes = [vp, C.POINTER(AdaptOptions)]
+    lib.hmcmt_chain_adapt_info.argtypes = [vp, C.POINTER(AdaptInfo)]
+    lib.hmcmt_chain_adapt_end.argtypes = [vp]
     lib.hmcmt_chain_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.hmcmt_chain_momentum.argtypes = [vp, c_double_p, C.POINTER(C.c_double)]
@@ -214,8 +236,12 @@ ACOV_MAXLAG = 1023    # include/hmcmt.h: maxlag of hmcmt_chain_acov_begin
 # ... and the fourth one: posterior covariance and correlation between cells
 CHAIN_COV_SYMBOLS = ["hmcmt_chain_cov_begin", "hmcmt_chain_cov", "hmcmt_chain_corr"]
 COV_BATCH_MAX = 16    # include/hmcmt.h: HMCMT_COV_BATCH_MAX
+# ... and the warm-up: the chain's step size and diagonal mass between two steps, and their adaptation
+CHAIN_ADAPT_SYMBOLS = ["hmcmt_chain_set_dt", "hmcmt_chain_set_mass_diag", "hmcmt_chain_mass_diag", "hmcmt_default_adapt_options",
+                       "hmcmt_chain_adapt_begin", "hmcmt_chain_adapt_info", "hmcmt_chain_adapt_end"]
+ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -857,6 +883,51 @@ class HipContext:
         corr = np.empty(self._cov_shape)
         self._check(self.lib.hmcmt_chain_corr(self.h, corr.ctypes.data, 0))
         return corr
+
+    # -- step size and diagonal mass between two steps, and their warm-up (hmcmt_chain_set_*, hmcmt_chain_adapt_*) --
+    def chain_set_dt(self, dt):
+        """Replaces the chain's step size between two steps; everything the chain holds stays valid.  Refused while a warm-up is active."""
+        self._check(self.lib.hmcmt_chain_set_dt(self.h, float(dt)))
+
+    def chain_set_mass_diag(self, invM):
+        """Replaces the diagonal of M^-1 (every entry finite and > 0) without ending the chain.  A momentum drawn before the call is
+        dropped: draw a new one before the next step."""
+        self._check(self.lib.hmcmt_chain_set_mass_diag(self.h, _dp(self._model(invM))))
+
+    def chain_mass_diag(self, d_invM=None):
+        """The diagonal of M^-1 in force: invM[nAC] -- or into the device pointer d_invM (int), returning None."""
+        if d_invM is not None:
+            self._check(self.lib.hmcmt_chain_mass_diag(self.h, d_invM, 1))
+            return None
+        invM = np.empty(self.nAC)
+        self._check(self.lib.hmcmt_chain_mass_diag(self.h, invM.ctypes.data, 0))
+        return invM
+
+    def chain_adapt_begin(self, nwarmup, **options):
+        """Starts a warm-up over the next `nwarmup` steps: dual averaging of dt towards the acceptance `delta` and, with adapt_mass
+        (the default), Stan's windowed estimate of the diagonal of M^-1 from the chain's own samples.  options: the fields of
+        hmcmt_adapt_options (include/hmcmt.h) -- adapt_mass, init_buffer, term_buffer, base_window, delta, gamma, t0, kappa,
+        dt_min, dt_max; what is not given keeps the library's default."""
+        unknown = sorted(set(options) - set(ADAPT_OPTION_KEYS))
+        if unknown:
+            raise ValueError(f"chain_adapt_begin: unknown option(s) {unknown}; known: {list(ADAPT_OPTION_KEYS)}")
+        o = AdaptOptions()
+        self.lib.hmcmt_default_adapt_options(C.byref(o))
+        o.nwarmup = int(nwarmup)
+        for k, v in options.items():
+            setattr(o, k, type(getattr(o, k))(v))
+        self._check(self.lib.hmcmt_chain_adapt_begin(self.h, C.byref(o)))
+
+    def chain_adapt_info(self):
+        """Where the warm-up stands (hmcmt_adapt_info as a dict): step, nwarmup, window_count, next_window_end, active, windows_done,
+        dt (what the next step uses), dt_bar, mu, s_bar, alpha_last, alpha_sum."""
+        info = AdaptInfo()
+        self._check(self.lib.hmcmt_chain_adapt_info(self.h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in AdaptInfo._fields_}
+
+    def chain_adapt_end(self):
+        """Stops a warm-up now: dt = exp(x_bar) as at its regular end."""
+        self._check(self.lib.hmcmt_chain_adapt_end(self.h))
 
     # -- instrumentation ----------------------------------------------------------------------
     def profile(self, enable=True, every=1):

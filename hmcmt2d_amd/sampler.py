@@ -617,8 +617,42 @@ def mergeCov(list_of_cov):
             "corr": _corr_of(cov, var, r)}
 
 
+ADAPT_KEYS = ("nwarmup", "mass", "delta", "gamma", "t0", "kappa", "init_buffer", "term_buffer", "base_window", "dt_min", "dt_max")
+
+
+def adaptPlan(adapt, hmcprior):
+    """(nwarmup, options of HipContext.chain_adapt_begin) of runHMCSampler's adapt={...}; needs no device.  nwarmup defaults to
+    hmcprior.burninsamples and may not exceed it: the posterior moments would mix in warm-up samples.  mass defaults to True for
+    massType "diagonal".  Where none of init_buffer / term_buffer / base_window is given and Stan's 75 / 50 / 25 do not fit
+    nwarmup, Stan's fallback holds: 15 % / 10 % / the rest, and below 20 warm-up steps the step size alone is adapted."""
+    unknown = set(adapt) - set(ADAPT_KEYS)
+    if unknown:
+        raise ValueError(f"runHMCSampler: adapt has no key {sorted(unknown)} ({', '.join(ADAPT_KEYS)})")
+    diagonal = hmcprior.massType == "diagonal"
+    nwarmup = int(adapt.get("nwarmup", hmcprior.burninsamples))
+    if nwarmup < 1:
+        raise ValueError(f"runHMCSampler: adapt needs nwarmup >= 1, not {nwarmup} (default: hmcprior.burninsamples)")
+    if nwarmup > hmcprior.burninsamples:
+        raise ValueError(f"runHMCSampler: adapt nwarmup = {nwarmup} exceeds hmcprior.burninsamples = {hmcprior.burninsamples}: "
+                         "the posterior moments would mix in warm-up samples")
+    mass = bool(adapt.get("mass", diagonal))
+    if mass and not diagonal:
+        raise ValueError(f"runHMCSampler: adapt mass=True needs massType \"diagonal\", not {hmcprior.massType!r}")
+    opts = {k: adapt[k] for k in ("delta", "gamma", "t0", "kappa", "dt_min", "dt_max") if k in adapt}
+    windows = {k: int(adapt[k]) for k in ("init_buffer", "term_buffer", "base_window") if k in adapt}
+    if mass and not windows:
+        if nwarmup < 20:
+            mass = False
+        elif 75 + 50 + 25 > nwarmup:
+            init, term = int(0.15 * nwarmup), int(0.1 * nwarmup)
+            windows = {"init_buffer": init, "term_buffer": term, "base_window": nwarmup - init - term}
+    opts.update(windows)
+    opts["adapt_mass"] = int(mass)
+    return nwarmup, opts
+
+
 def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False, ess=None,
-                      cov=None):
+                      cov=None, adapt=None, invM=None):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals."""
@@ -635,7 +669,11 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     strModel = np.log(np.ones(nparam) / rhoref)
     invParam.strModel = strModel.copy()
     invParam.refModel = strModel.copy()
-    ctx.set_prior(invParam.refModel, invParam.Wm, setMassMatrix(nparam, 1.0)[0] if diagonal else np.ones(nparam))
+    if invM is not None:
+        invM = np.ascontiguousarray(invM, dtype=np.float64)
+        if invM.shape != (nparam,) or not (np.isfinite(invM).all() and (invM > 0).all()):
+            raise ValueError(f"runHMCSampler: invM must hold {nparam} finite positive entries")
+    ctx.set_prior(invParam.refModel, invParam.Wm, invM if invM is not None else (setMassMatrix(nparam, 1.0)[0] if diagonal else np.ones(nparam)))
     if not diagonal:
         ctx.set_mass(HMCMT_MASS_WM)
     lo, hi = np.log(hmcprior.sigBounds[0]), np.log(hmcprior.sigBounds[1])
@@ -658,8 +696,13 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     if cov is not None:
         cov_rows = None if cov.get("rows") is None else np.asarray(cov["rows"], dtype=np.int64)
         ctx.chain_cov_begin(cov_rows, int(cov.get("batch", 0)))
-    startK = ctx.chain_momentum(z)
     nsamples = hmcprior.totalsamples
+    if adapt is not None:                                   # (the warm-up: hmcprior.dt is its start and stays as it is)
+        nwarmup, adapt_opts = adaptPlan(adapt, hmcprior)
+        ctx.chain_adapt_begin(nwarmup, **adapt_opts)
+        info = ctx.chain_adapt_info()
+        adapt_dt, adapt_alpha, adapt_windows = np.full(nsamples, np.nan), np.zeros(nsamples), []
+    startK = ctx.chain_momentum(z)
     nkeep = nsamples if keep_samples else 0
     hmcmodel = np.zeros((nparam, nkeep))
     hmcdata = np.zeros((ndata, nkeep + 1), dtype=np.complex128)
@@ -670,6 +713,12 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
         L = int(rng.integers(hmcprior.timestep[0], hmcprior.timestep[1] + 1))
         u = rng.random()
         rec, model, pred = ctx.chain_step(L, u, outputs=keep_samples)
+        if adapt is not None:
+            before, info = info, ctx.chain_adapt_info()
+            adapt_dt[it - 1] = before["dt"]
+            adapt_alpha[it - 1] = 1.0 if rec["hdif"] > 0 else float(np.exp(rec["hdif"]))
+            if before["active"] and before["next_window_end"] == before["step"]:      # (this step was its window's last)
+                adapt_windows.append((it, before["window_count"] + 1))
         hmcprior.nfevals += rec["nfevals"]
         if rec["accepted"]:
             stats.nAccept += 1
@@ -686,6 +735,9 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
             hmcmodel[:, it - 1] = model
             hmcdata[:, it] = pred if rec["accepted"] else hmcdata[:, it - 1]      # (:164-168: a rejection repeats the column)
     stats.moments = ctx.chain_moments()
+    if adapt is not None:
+        stats.adapt = {"nwarmup": nwarmup, "dt": adapt_dt, "alpha": adapt_alpha, "dt_final": info["dt"],
+                       "invM": ctx.chain_mass_diag() if adapt_opts["adapt_mass"] else None, "windows": adapt_windows}
     if hist is not None:
         stats.hist = ctx.chain_hist() + (bins, targets.copy())
     if data_moments:
@@ -713,7 +765,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
                   checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
-                  cov=None):
+                  cov=None, adapt=None, invM=None):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -741,6 +793,14 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     per update kernel, 1 .. 16, default 8; the results do not depend on it).  hmcstats.cov is a dict: count, rows, mean[nparam],
     var[nparam], cov[nrow, nparam], corr[nrow, nparam] (biased estimator; hmcmt_chain_cov, include/hmcmt.h).  A chain that ends inside
     its burn-in gives count 0 and None for the rest.  See covOf, mergeCov, fileio.getCorrelationModel.  The draws keep their order.
+    `adapt={...}` (with device_chain): a warm-up over the first `nwarmup` samples (default hmcprior.burninsamples, and never more: the
+    moments count behind the burn-in) tunes the step size by dual averaging towards the acceptance `delta` (0.8) and, with `mass`
+    (default True for massType "diagonal"), the diagonal of M^-1 by Stan's windowed variance of the chain's own samples, on the GPU
+    (hmcmt_chain_adapt_begin, include/hmcmt.h).  Further keys, all optional: gamma, t0, kappa, init_buffer, term_buffer, base_window,
+    dt_min, dt_max; see adaptPlan for the window defaults.  hmcprior.dt is the start and is not modified.  hmcstats.adapt is a dict:
+    nwarmup, dt[nsamples] (the step size each sample's trajectory used), alpha[nsamples], dt_final, invM (the final diagonal, None
+    without mass) and windows, a list of (end_step, n).  `invM=array` (with device_chain): the diagonal of M^-1 the chain starts with
+    instead of ones, for example an earlier run's adapted mass.  The draws keep their order.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -762,6 +822,12 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
         raise ValueError("runHMCSampler: ess needs device_chain=True (the autocovariances are streamed in the device chain's commit)")
     if cov is not None and not device_chain:
         raise ValueError("runHMCSampler: cov needs device_chain=True (the cross moments are streamed in the device chain's commit)")
+    if (adapt is not None or invM is not None) and not device_chain:
+        raise ValueError("runHMCSampler: adapt and invM need device_chain=True (the warm-up runs in the device chain)")
+    if adapt is not None:
+        adaptPlan(adapt, hmcprior)                             # (its errors before the context is touched and the first number is drawn)
+    if invM is not None and hmcprior.massType != "diagonal":
+        raise ValueError(f"runHMCSampler: invM needs massType \"diagonal\", not {hmcprior.massType!r}")
     for name, given, keys in (("hist", hist, ("targets", "nbins", "lo", "hi")), ("ess", ess, ("targets", "maxlag")),
                               ("cov", cov, ("rows", "batch"))):
         unknown = set(given or ()) - set(keys)                 # (before the context is touched and the first number is drawn)
@@ -770,7 +836,8 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments, ess, cov)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments, ess, cov,
+                                 adapt, invM)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -875,7 +942,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     (hmcmt_allgather_samples, include/hmcmt.h -- what a non-Python host would call) instead of torch's; the process
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
-    `path.chain<k>` per chain; device_chain=True, keep_samples=False, hist=..., ess=..., cov=...).
+    `path.chain<k>` per chain; device_chain=True, keep_samples=False, hist=..., ess=..., cov=..., adapt=...; hmcstats.adapt stays on the chain's own rank, as ess and cov do).
     Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
     count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
     gelmanRubin).  A chain's block in the gather is, in doubles,
@@ -1025,6 +1092,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
             if c in results:                                # (ess= is not gathered: a chain's own rank keeps it, for mergeAcov)
                 hmcstats[c].ess = getattr(results[c][1], "ess", None)
                 hmcstats[c].cov = getattr(results[c][1], "cov", None)     # (nor is cov=: see mergeCov)
+                hmcstats[c].adapt = getattr(results[c][1], "adapt", None) # (nor is adapt=: each chain warms up on its own)
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

@@ -90,6 +90,7 @@ class HMCStatus:
     dataMoments: object = None    # (count, mean[ndata], m2[ndata]) of the predicted data: runHMCSampler(..., data_moments=True)
     ess: object = None            # dict count, maxlag, targets, mean, acov, tau, ess, window, misfit: runHMCSampler(..., ess=...)
     cov: object = None            # dict count, rows, mean, var, cov, corr: runHMCSampler(..., cov=...)
+    adapt: object = None          # dict nwarmup, dt, alpha, dt_final, invM, windows: runHMCSampler(..., adapt=...)
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

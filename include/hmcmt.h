@@ -355,6 +355,73 @@ extern int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* ro
 extern int hmcmt_chain_cov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* var, double* cov, int32_t on_device);
 extern int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device);
 
+/* The chain's step size and diagonal mass between two steps, and their warm-up adaptation (optional: with no call below, every
+ * record, moment and accumulator keeps its bits).
+ *   hmcmt_chain_set_dt    replaces the chain's dt (finite, > 0) between two steps.  The chain, its accumulators, a momentum already
+ *                         drawn and the gradient the last decision left on the device stay valid: none depends on dt.  HMCMT_EINVAL
+ *                         while an adaptation is active
+ *   hmcmt_chain_set_mass_diag   replaces the diagonal of M^-1 (invM[nAC], host; every entry finite and > 0, checked before anything is
+ *                         enqueued) without ending the chain.  A momentum drawn before the call is dropped -- its K0 belongs to the old
+ *                         mass -- so the next hmcmt_chain_step fails with "no momentum since the last step" until a new one is drawn;
+ *                         the stored gradient and D, M stay valid.  HMCMT_EINVAL with HMCMT_MASS_WM and while an adaptation with
+ *                         adapt_mass is active
+ *   hmcmt_chain_mass_diag reads out the diagonal in force: invM[nAC], host or with on_device = 1 a device pointer; complete on return
+ *   hmcmt_chain_adapt_begin   starts a warm-up of nwarmup steps, counted from this call; a step counts when hmcmt_chain_step succeeds.
+ *                         With c the steps adapted so far and W = nwarmup, a counted step does, behind its decision and its commit
+ *                         (both unchanged):
+ *                           1. alpha = hdif > 0 ? 1 : exp(hdif) from the record's hdif
+ *                           2. with adapt_mass and init_buffer <= c < W - term_buffer: the chain's current model -- after the decision,
+ *                              so a rejection repeats it -- is added to the window's Welford accumulator (two nAC buffers of the
+ *                              adaptation's own, not the chain's moments, which stay behind the burn-in)
+ *                           3. dual averaging of x = ln dt in double, in this order, t = updates since the last restart + 1:
+ *                                eta = 1 / (t + t0),  s_bar = (1 - eta) s_bar + eta (delta - alpha),  x = mu - s_bar sqrt(t) / gamma,
+ *                                x_eta = pow(t, -kappa),  x_bar = (1 - x_eta) x_bar + x_eta x,  dt = exp(x)
+ *                              dt clipped into [dt_min, dt_max] where set (x is held to +-700 before exp).  The begin call restarts:
+ *                              mu = ln(10 dt), s_bar = x_bar = 0
+ *                           4. if 2. ran and c is the window's last step, with n samples in the window: for n >= 2 one kernel writes
+ *                                invM[a] = (m2[a] / (n - 1)) w + f,  w = n / (n + 5),  f = 1e-3 * 5 / (n + 5)
+ *                              windows_done is incremented and the dual averaging restarts around the dt of 3.; a window of n < 2
+ *                              leaves the mass and the dual averaging alone.  Either way the window's accumulator is zeroed and the
+ *                              next window follows Stan's rule: the first ends at step init_buffer + base_window - 1; behind the
+ *                              window that ends at W - term_buffer - 1 there is none (next_window_end = -1); otherwise the size
+ *                              doubles, next = c + size, and if next != W - term_buffer - 1 and next + 2 size >= W - term_buffer the
+ *                              window runs up to W - term_buffer - 1
+ *                           5. ++c; at c == W: dt = exp(x_bar), clipped (dt stays if a restart fell on the last step), active = 0
+ *                         All of it is enqueued on the context's stream or scalar host work: the step keeps its single wait, and the
+ *                         next hmcmt_chain_momentum sees the new mass.  A step that fails touches nothing of the adaptation.  The
+ *                         adapted diagonal is the context's diagonal mass from then on: hmcmt_leapfrog* and hmcmt_mass_apply see it
+ *                         until the next hmcmt_set_prior.  On HMCMT_ENOMEM the chain goes on without adaptation.  A second call
+ *                         replaces a running adaptation
+ *   hmcmt_chain_adapt_info   during an adaptation and after one that ended in this chain.  step = c, window_count = samples in the open
+ *                         window, dt = the step size the next step uses, dt_bar = exp(x_bar) clipped (dt before the first update
+ *                         behind a restart), alpha_last / alpha_sum = the last alpha and the sum of all
+ *   hmcmt_chain_adapt_end stops now: dt = exp(x_bar) as at the regular end; the mass stays as the last closed window left it
+ * hmcmt_chain_begin (also over a running chain), hmcmt_chain_end, hmcmt_set_prior and hmcmt_set_mass end an adaptation and release its
+ * buffers.  HMCMT_EINVAL: NULL context or argument, no chain, a call between hmcmt_grad_device_async and hmcmt_wait, a non-finite
+ * value; for the begin call nwarmup < 1, delta outside (0, 1), gamma or t0 not positive, kappa outside (0.5, 1], dt_min > dt_max with
+ * both set, a negative bound, and with adapt_mass: HMCMT_MASS_WM, a negative buffer, base_window < 1 or
+ * init_buffer + base_window + term_buffer > nwarmup; for info and end: no adaptation begun in this chain.  For equal inputs the
+ * adapted dt and mass repeat bitwise. */
+typedef struct hmcmt_adapt_options {
+    int64_t nwarmup;                               /* steps to adapt over, counted from the begin call; >= 1 */
+    int32_t adapt_mass;                            /* 1: windowed estimate of diag(M^-1) (HMCMT_MASS_DIAGONAL only); 0: step size only */
+    int32_t init_buffer, term_buffer, base_window; /* defaults 75, 50, 25 */
+    double  delta, gamma, t0, kappa;               /* defaults 0.8, 0.05, 10, 0.75 */
+    double  dt_min, dt_max;                        /* clip of dt; 0 = no bound on that side */
+} hmcmt_adapt_options;
+typedef struct hmcmt_adapt_info {
+    int64_t step, nwarmup, window_count, next_window_end;
+    int32_t active, windows_done;
+    double  dt, dt_bar, mu, s_bar, alpha_last, alpha_sum;
+} hmcmt_adapt_info;
+extern int hmcmt_chain_set_dt(hmcmt_ctx* ctx, double dt);
+extern int hmcmt_chain_set_mass_diag(hmcmt_ctx* ctx, const double* invM);
+extern int hmcmt_chain_mass_diag(hmcmt_ctx* ctx, double* invM, int32_t on_device);
+extern void hmcmt_default_adapt_options(hmcmt_adapt_options* o);   /* nwarmup = 0: the caller sets it; adapt_mass = 1 */
+extern int hmcmt_chain_adapt_begin(hmcmt_ctx* ctx, const hmcmt_adapt_options* o);
+extern int hmcmt_chain_adapt_info(hmcmt_ctx* ctx, hmcmt_adapt_info* info);
+extern int hmcmt_chain_adapt_end(hmcmt_ctx* ctx);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -69,6 +69,37 @@ struct HmcmtChainRecord
     hdif::Float64
     nsamples::Int64
     nmoments::Int64
+end
+
+# hmcmt_adapt_options and hmcmt_adapt_info of include/hmcmt.h: the warm-up hmcmt_chain_adapt_begin starts and where it stands
+# (tests/test_adapt_host.py compares the fields with the ctypes mirrors)
+struct HmcmtAdaptOptions
+    nwarmup::Int64
+    adapt_mass::Int32
+    init_buffer::Int32
+    term_buffer::Int32
+    base_window::Int32
+    delta::Float64
+    gamma::Float64
+    t0::Float64
+    kappa::Float64
+    dt_min::Float64
+    dt_max::Float64
+end
+
+struct HmcmtAdaptInfo
+    step::Int64
+    nwarmup::Int64
+    window_count::Int64
+    next_window_end::Int64
+    active::Int32
+    windows_done::Int32
+    dt::Float64
+    dt_bar::Float64
+    mu::Float64
+    s_bar::Float64
+    alpha_last::Float64
+    alpha_sum::Float64
 end
 
 mutable struct HipContext
@@ -632,7 +663,47 @@ function chain_cov!(ctx::HipContext; rows::Vector{<:Integer}=Int[], batch::Integ
 end
 
 """
-    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, cov=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov])
+    chainSetDt!(ctx, dt);  chainSetMassDiag!(ctx, invM);  chainMassDiag(ctx) -> invM[nAC]
+    chainAdaptBegin!(ctx, nwarmup; adaptMass=true, initBuffer=75, termBuffer=50, baseWindow=25, delta=0.8, gamma=0.05, t0=10.0,
+                     kappa=0.75, dtMin=0.0, dtMax=0.0);  chainAdaptInfo(ctx) -> HmcmtAdaptInfo;  chainAdaptEnd!(ctx)
+
+The chain's step size and diagonal mass between two steps, and their warm-up (hmcmt_chain_set_dt, hmcmt_chain_set_mass_diag,
+hmcmt_chain_mass_diag, hmcmt_chain_adapt_*, include/hmcmt.h): dual averaging of dt towards the acceptance `delta` and, with
+`adaptMass`, Stan's windowed estimate of the diagonal of M^-1 from the chain's own samples, on the GPU.  `chainSetMassDiag!` drops a
+momentum drawn before it: draw a new one before the next step.  Call `chainAdaptBegin!` behind `chainBegin!` (which ends an
+adaptation); `run_chain!(...; adapt=(nwarmup=..., ...))` does so with the keywords above.
+"""
+chainSetDt!(ctx::HipContext, dt::Real) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_set_dt(ctx.ptr::Ptr{Cvoid}, Float64(dt)::Float64)::Cint)
+
+function chainSetMassDiag!(ctx::HipContext, invM::Vector{Float64})
+    length(invM) == ctx.nAC || error("chainSetMassDiag!: invM must hold nAC = $(ctx.nAC) entries")
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_set_mass_diag(ctx.ptr::Ptr{Cvoid}, invM::Ptr{Float64})::Cint)
+end
+
+function chainMassDiag(ctx::HipContext)
+    invM = Vector{Float64}(undef, ctx.nAC)
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_mass_diag(ctx.ptr::Ptr{Cvoid}, invM::Ptr{Float64}, Int32(0)::Int32)::Cint)
+    return invM
+end
+
+function chainAdaptBegin!(ctx::HipContext, nwarmup::Integer; adaptMass::Bool=true, initBuffer::Integer=75, termBuffer::Integer=50,
+                          baseWindow::Integer=25, delta::Real=0.8, gamma::Real=0.05, t0::Real=10.0, kappa::Real=0.75,
+                          dtMin::Real=0.0, dtMax::Real=0.0)
+    o = Ref(HmcmtAdaptOptions(Int64(nwarmup), Int32(adaptMass), Int32(initBuffer), Int32(termBuffer), Int32(baseWindow),
+                              Float64(delta), Float64(gamma), Float64(t0), Float64(kappa), Float64(dtMin), Float64(dtMax)))
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_begin(ctx.ptr::Ptr{Cvoid}, o::Ref{HmcmtAdaptOptions})::Cint)
+end
+
+function chainAdaptInfo(ctx::HipContext)
+    info = Ref(HmcmtAdaptInfo(0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0))
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_info(ctx.ptr::Ptr{Cvoid}, info::Ref{HmcmtAdaptInfo})::Cint)
+    return info[]
+end
+
+chainAdaptEnd!(ctx::HipContext) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_end(ctx.ptr::Ptr{Cvoid})::Cint)
+
+"""
+    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt])
 
 runHMCSampler (HMCSampler.jl:72-196) through the chain API, step for step what hmcmt2d_amd/sampler.py's device chain does, the
 reference's start included: the chain's state starts at the file's model invParam.strModel (:88), while start and reference model
@@ -643,9 +714,14 @@ rhoref; per sample L, u, the next momentum's normals.  `keepSamples=false`: no s
 hmcdata its first only); `moments` = (count, mean, m2) of the samples behind hmcprior.burninsamples either way.
 `cov=(rows=Int[], batch=0)` (both optional; see `chainCovBegin!`) streams the posterior covariance beside the moments and appends a fifth
 result, the named tuple (count, rows, mean, var, cov, corr) -- `nothing` for the arrays of a chain that ends inside its burn-in.
+`adapt=(nwarmup=hmcprior.burninsamples, ...)` (the keywords of `chainAdaptBegin!`, all optional) warms the chain up over its first
+`nwarmup <= hmcprior.burninsamples` samples and appends a last result, the named tuple (nwarmup, dt, alpha, dtFinal, invM): the step
+size each sample's trajectory used, each sample's acceptance probability, the adapted step size and the diagonal of M^-1 in force
+at the end.  hmcprior.dt is the start and is not modified.
 """
 function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior, hmcParam::HMCParameter; keepSamples::Bool=true,
-                    rhoref::Union{Nothing,Real}=nothing, cov::Union{Nothing,NamedTuple}=nothing)
+                    rhoref::Union{Nothing,Real}=nothing, cov::Union{Nothing,NamedTuple}=nothing,
+                    adapt::Union{Nothing,NamedTuple}=nothing)
     n, nd = ctx.nAC, ctx.nData
     nsamples = hmcprior.totalsamples
     fileModel = Vector{Float64}(invParam.strModel)
@@ -667,6 +743,12 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
         chainSetEnergy!(ctx, D, M)
     end
     covRows = cov === nothing ? Int[] : first(chain_cov!(ctx; rows=Vector{Int}(get(cov, :rows, Int[])), batch=get(cov, :batch, 0)))
+    if adapt !== nothing
+        nwarmup = get(adapt, :nwarmup, hmcprior.burninsamples)
+        nwarmup <= hmcprior.burninsamples || error("run_chain!: adapt nwarmup = $(nwarmup) exceeds hmcprior.burninsamples: the moments would mix in warm-up samples")
+        chainAdaptBegin!(ctx, nwarmup; Base.structdiff(adapt, NamedTuple{(:nwarmup,)})...)
+        adaptDt = fill(NaN, nsamples); adaptAlpha = zeros(nsamples)
+    end
     K = chainMomentum!(ctx, z)
     ncols = keepSamples ? nsamples : 0
     hmcmodel = zeros(Float64, n, ncols)
@@ -679,7 +761,9 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
     for it = 1:nsamples
         L = rand(hmcprior.timestep[1]:hmcprior.timestep[2])
         u = rand()
+        adapt === nothing || (adaptDt[it] = chainAdaptInfo(ctx).dt)
         rec = chainStep!(ctx, L, u; mOut=mOut, predOut=predOut)
+        adapt === nothing || (adaptAlpha[it] = rec.hdif > 0 ? 1.0 : exp(rec.hdif))
         hmcprior.nfevals += rec.nfevals
         if rec.accepted == 1
             hmcstats.nAccept += 1
@@ -694,14 +778,15 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
             hmcdata[:, it + 1] = rec.accepted == 1 ? predOut : hmcdata[:, it]      # (:164-168: a rejection repeats the column)
         end
     end
-    cov === nothing && return hmcmodel, hmcstats, hmcdata, chainMoments(ctx)
+    adaptStats = adapt === nothing ? () : ((nwarmup=nwarmup, dt=adaptDt, alpha=adaptAlpha, dtFinal=chainAdaptInfo(ctx).dt, invM=chainMassDiag(ctx)),)
+    cov === nothing && return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), adaptStats...)
     if nsamples > hmcprior.burninsamples
         count, cmean, cvar, cmat = chainCov(ctx, length(covRows))
         covStats = (count=count, rows=covRows, mean=cmean, var=cvar, cov=cmat, corr=chainCorr(ctx, length(covRows)))
     else
         covStats = (count=0, rows=covRows, mean=nothing, var=nothing, cov=nothing, corr=nothing)
     end
-    return hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats
+    return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats, adaptStats...)
 end
 
 hipWait(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_wait, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
