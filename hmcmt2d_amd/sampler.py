@@ -651,24 +651,171 @@ def adaptPlan(adapt, hmcprior):
     return nwarmup, opts
 
 
-def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist=None, data_moments=False, ess=None,
-                      cov=None, adapt=None, invM=None):
-    """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
-    moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
-    Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals."""
-    from .lib import HMCMT_MASS_WM
-    nparam, ndata = len(invParam.strModel), len(invParam.obsData)
-    diagonal = hmcprior.massType == "diagonal"
-    fileModel = np.asarray(invParam.strModel, dtype=np.float64).copy()    # the file's start model stays the chain's state (:88)
-    z = rng.standard_normal(nparam)                         # getMomentumVector's draw (:90)
+# ---- the optional outputs of the device chain: one entry of CHAIN_OUTPUTS each ---------------------------------------------------------
+class ChainOutput:
+    """One optional output of runHMCSampler(device_chain=True): the keyword `name` fills HMCStatus.`field`; `keys` are the keys its
+    dict accepts (a flag has none and arrives as {}) and `why` says why it needs the device chain.  `check(value, hmcprior)` refuses
+    what can be refused without a context.  `begin(ctx, value, env)` makes the library's begin call(s) -- behind the chain's second
+    chain_begin, which would end them, and in front of the first momentum -- and returns what `read(ctx, state, stats, env)`, behind
+    the last step, turns into the field's value.  env: nparam, lo, hi (ln of hmcprior.sigBounds), nsamples, hmcprior.  An output that
+    watches every step has `step(ctx, state, it, rec)`, called between the chain_step of sample `it` and the next momentum.  The
+    docstring of an entry is its paragraph of runHMCSampler's."""
+    name = field = why = None
+    keys = ()
+    step = None
+
+    def check(self, value, hmcprior):
+        unknown = set(value) - set(self.keys)
+        if unknown:
+            raise ValueError(f"runHMCSampler: {self.name} has no key {sorted(unknown)} ({', '.join(self.keys)})")
+
+
+def _cells(given, nparam=None):
+    """a keyword's list of active cells as the library takes it; None: every cell (spelled out where nparam is given)"""
+    if given is None:
+        return None if nparam is None else np.arange(nparam, dtype=np.int64)
+    return np.asarray(given, dtype=np.int64)
+
+
+class _Histograms(ChainOutput):
+    """`hist={...}` (with device_chain): per-cell histograms of ln sigma, streamed in the chain's commit like the moments, so that
+    marginal distributions and credible intervals need no sample history.  Keys, all optional: `targets` (active-cell indices, default
+    every cell; `sitePPDTargets` gives the cells under sites), `nbins` (300, the reference's npBins), `lo`, `hi` (ln of
+    hmcprior.sigBounds).  hmcstats.hist = (count, counts[ntarget, nbins], (nbins, lo, hi), targets): see histQuantiles,
+    histToLog10Rho, mergeHistograms, fileio.writeSitePPD, fileio.getPosteriorQuantileModels."""
+    name, field, keys, why = "hist", "hist", ("targets", "nbins", "lo", "hi"), "it is streamed in the device chain's commit"
+
+    def begin(self, ctx, value, env):
+        targets = _cells(value.get("targets"), env.nparam)
+        bins = (int(value.get("nbins", 300)), float(value.get("lo", env.lo)), float(value.get("hi", env.hi)))
+        ctx.chain_hist_begin(targets, *bins)
+        return bins, targets
+
+    def read(self, ctx, state, stats, env):
+        return ctx.chain_hist() + (state[0], state[1].copy())
+
+
+class _DataMoments(ChainOutput):
+    """`data_moments=True` (with device_chain): hmcstats.dataMoments = (count, mean[ndata], m2[ndata]) of the predicted data at the
+    samples the moments count -- the posterior-predictive spread.  Neither this nor `hist` changes the order of the random draws."""
+    name, field, why = "data_moments", "dataMoments", "it is streamed in the device chain's commit"
+
+    def begin(self, ctx, value, env):
+        ctx.chain_data_moments_begin()
+
+    def read(self, ctx, state, stats, env):
+        return ctx.chain_data_moments()
+
+
+class _EffectiveSampleSize(ChainOutput):
+    """`ess={...}` (with device_chain): per-cell lagged autocovariances streamed in the commit, and from them the integrated
+    autocorrelation time and the effective sample size, computed on the GPU.  Keys, both optional: `targets` (default every cell) and
+    `maxlag` (63).  hmcstats.ess is a dict: count, maxlag, targets, mean, acov[maxlag + 1, ntarget], tau, ess, window (hmcmt_chain_ess,
+    include/hmcmt.h: window < 0 means the lags ran out and tau is a lower bound), and `misfit`, the same estimator applied here to the
+    data misfit of the counted samples.  A chain that ends inside its burn-in gives count 0 and None for the rest.  See acovOf, essFromAcov, mcseOfMean, mergeAcov, fileio.getESSModel.  The draws keep their order."""
+    name, field, keys, why = "ess", "ess", ("targets", "maxlag"), "the autocovariances are streamed in the device chain's commit"
+
+    def begin(self, ctx, value, env):
+        targets, maxlag = _cells(value.get("targets")), int(value.get("maxlag", 63))
+        ctx.chain_acov_begin(targets, maxlag)
+        return targets, maxlag
+
+    def read(self, ctx, state, stats, env):
+        targets, maxlag = state
+        # (a chain that ends inside its burn-in has counted nothing: the read-outs need a commit, the rest of the result stands)
+        count = ctx.chain_acov_count()
+        (_, mean, acov), (tau, e, window) = (ctx.chain_acov(), ctx.chain_ess()) if count > 0 else ((0, None, None), (None, None, None))
+        out = {"count": count, "maxlag": maxlag, "targets": _cells(targets, env.nparam).copy(), "mean": mean, "acov": acov, "tau": tau,
+               "ess": e, "window": window, "misfit": None}
+        D = stats.hmstats[0, 1 + env.hmcprior.burninsamples:]  # the data misfit of the counted samples: the same estimator on the host
+        if len(D):
+            a = acovOf(D, maxlag)
+            t1, e1, w1 = essFromAcov(a, len(D))
+            out["misfit"] = {"count": len(D), "mean": float(D.mean()), "acov": a, "tau": t1, "ess": e1, "window": w1}
+        return out
+
+
+class _Covariance(ChainOutput):
+    """`cov={...}` (with device_chain): the posterior covariance and correlation between cells, streamed in the commit as cross moments
+    and folded in by a batched kernel, so that trade-offs between cells need no sample history.  Keys, both optional: `rows` (the
+    active-cell indices whose rows of the matrix are kept; default every cell, the full nparam x nparam matrix) and `batch` (commits
+    per update kernel, 1 .. 16, default 8; the results do not depend on it).  hmcstats.cov is a dict: count, rows, mean[nparam],
+    var[nparam], cov[nrow, nparam], corr[nrow, nparam] (biased estimator; hmcmt_chain_cov, include/hmcmt.h).  A chain that ends inside
+    its burn-in gives count 0 and None for the rest.  See covOf, mergeCov, fileio.getCorrelationModel.  The draws keep their order."""
+    name, field, keys, why = "cov", "cov", ("rows", "batch"), "the cross moments are streamed in the device chain's commit"
+
+    def begin(self, ctx, value, env):
+        rows = _cells(value.get("rows"))
+        ctx.chain_cov_begin(rows, int(value.get("batch", 0)))
+        return rows
+
+    def read(self, ctx, rows, stats, env):
+        # (as for ess: a chain that ends inside its burn-in has counted nothing)
+        count = ctx.chain_cov_count()
+        (_, mean, var, c), corr = (ctx.chain_cov(), ctx.chain_corr()) if count > 0 else ((0, None, None, None), None)
+        return {"count": count, "rows": _cells(rows, env.nparam).copy(), "mean": mean, "var": var, "cov": c, "corr": corr}
+
+
+class _WarmUp(ChainOutput):
+    """`adapt={...}` (with device_chain): a warm-up over the first `nwarmup` samples (default hmcprior.burninsamples, and never more: the
+    moments count behind the burn-in) tunes the step size by dual averaging towards the acceptance `delta` (0.8) and, with `mass`
+    (default True for massType "diagonal"), the diagonal of M^-1 by Stan's windowed variance of the chain's own samples, on the GPU
+    (hmcmt_chain_adapt_begin, include/hmcmt.h).  Further keys, all optional: gamma, t0, kappa, init_buffer, term_buffer, base_window,
+    dt_min, dt_max; see adaptPlan for the window defaults.  hmcprior.dt is the start and is not modified.  hmcstats.adapt is a dict:
+    nwarmup, dt[nsamples] (the step size each sample's trajectory used), alpha[nsamples], dt_final, invM (the final diagonal, None
+    without mass) and windows, a list of (end_step, n)."""
+    name, field, keys, why = "adapt", "adapt", ADAPT_KEYS, "the warm-up runs in the device chain"
+
+    def check(self, value, hmcprior):
+        adaptPlan(value, hmcprior)
+
+    def begin(self, ctx, value, env):                       # (the warm-up: hmcprior.dt is its start and stays as it is)
+        nwarmup, opts = adaptPlan(value, env.hmcprior)
+        ctx.chain_adapt_begin(nwarmup, **opts)
+        return {"nwarmup": nwarmup, "mass": opts["adapt_mass"], "info": ctx.chain_adapt_info(), "dt": np.full(env.nsamples, np.nan),
+                "alpha": np.zeros(env.nsamples), "windows": []}
+
+    def step(self, ctx, state, it, rec):
+        before, state["info"] = state["info"], ctx.chain_adapt_info()
+        state["dt"][it - 1] = before["dt"]
+        state["alpha"][it - 1] = 1.0 if rec["hdif"] > 0 else float(np.exp(rec["hdif"]))
+        if before["active"] and before["next_window_end"] == before["step"]:      # (this step was its window's last)
+            state["windows"].append((it, before["window_count"] + 1))
+
+    def read(self, ctx, state, stats, env):
+        return {"nwarmup": state["nwarmup"], "dt": state["dt"], "alpha": state["alpha"], "dt_final": state["info"]["dt"],
+                "invM": ctx.chain_mass_diag() if state["mass"] else None, "windows": state["windows"]}
+
+
+CHAIN_OUTPUTS = (_Histograms(), _DataMoments(), _EffectiveSampleSize(), _Covariance(), _WarmUp())
+
+
+def _homogeneous_start(invParam, rhoref, rng, verbose):
+    """The random homogeneous start / reference model (HMCSampler.jl:100-109) of both loops: draws rhoref where none is given, sets
+    invParam.strModel and invParam.refModel to it and returns (strModel, rhoref)."""
     rho0 = 1.0 / np.exp(invParam.strModel[0])
     if rhoref is None:
         rhoref = np.round(rho0 * 0.5 + (rho0 * 1.5 - rho0 * 0.5) * rng.random())
     if verbose:
         print(f"Homogeneous starting model with a resistivity of {rhoref} Ωm is used.")
-    strModel = np.log(np.ones(nparam) / rhoref)
+    strModel = np.log(np.ones(len(invParam.strModel)) / rhoref)
     invParam.strModel = strModel.copy()
     invParam.refModel = strModel.copy()
+    return strModel, rhoref
+
+
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM):
+    """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
+    moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
+    Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals.
+    `outputs`: keyword -> value of the entries of CHAIN_OUTPUTS that are on."""
+    from types import SimpleNamespace
+    from .lib import HMCMT_MASS_WM
+    nparam, ndata = len(invParam.strModel), len(invParam.obsData)
+    diagonal = hmcprior.massType == "diagonal"
+    fileModel = np.asarray(invParam.strModel, dtype=np.float64).copy()    # the file's start model stays the chain's state (:88)
+    z = rng.standard_normal(nparam)                         # getMomentumVector's draw (:90)
+    strModel, rhoref = _homogeneous_start(invParam, rhoref, rng, verbose)
     if invM is not None:
         invM = np.ascontiguousarray(invM, dtype=np.float64)
         if invM.shape != (nparam,) or not (np.isfinite(invM).all() and (invM > 0).all()):
@@ -683,25 +830,11 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     if not np.array_equal(fileModel, strModel):
         ctx.chain_begin(fileModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
         ctx.chain_set_energy(startD, startM)
-    if hist is not None:                                    # (behind the second begin: a begin ends the accumulators)
-        targets = np.arange(nparam, dtype=np.int64) if hist.get("targets") is None else np.asarray(hist["targets"], dtype=np.int64)
-        bins = (int(hist.get("nbins", 300)), float(hist.get("lo", lo)), float(hist.get("hi", hi)))     # (300: the reference's npBins)
-        ctx.chain_hist_begin(targets, *bins)
-    if data_moments:
-        ctx.chain_data_moments_begin()
-    if ess is not None:
-        ess_targets = None if ess.get("targets") is None else np.asarray(ess["targets"], dtype=np.int64)
-        maxlag = int(ess.get("maxlag", 63))
-        ctx.chain_acov_begin(ess_targets, maxlag)
-    if cov is not None:
-        cov_rows = None if cov.get("rows") is None else np.asarray(cov["rows"], dtype=np.int64)
-        ctx.chain_cov_begin(cov_rows, int(cov.get("batch", 0)))
     nsamples = hmcprior.totalsamples
-    if adapt is not None:                                   # (the warm-up: hmcprior.dt is its start and stays as it is)
-        nwarmup, adapt_opts = adaptPlan(adapt, hmcprior)
-        ctx.chain_adapt_begin(nwarmup, **adapt_opts)
-        info = ctx.chain_adapt_info()
-        adapt_dt, adapt_alpha, adapt_windows = np.full(nsamples, np.nan), np.zeros(nsamples), []
+    env = SimpleNamespace(nparam=nparam, lo=lo, hi=hi, nsamples=nsamples, hmcprior=hmcprior)
+    # (behind the second begin: a begin ends the accumulators)
+    begun = [(out, out.begin(ctx, outputs[out.name], env)) for out in CHAIN_OUTPUTS if out.name in outputs]
+    watching = [(out, state) for out, state in begun if out.step is not None]
     startK = ctx.chain_momentum(z)
     nkeep = nsamples if keep_samples else 0
     hmcmodel = np.zeros((nparam, nkeep))
@@ -713,12 +846,8 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
         L = int(rng.integers(hmcprior.timestep[0], hmcprior.timestep[1] + 1))
         u = rng.random()
         rec, model, pred = ctx.chain_step(L, u, outputs=keep_samples)
-        if adapt is not None:
-            before, info = info, ctx.chain_adapt_info()
-            adapt_dt[it - 1] = before["dt"]
-            adapt_alpha[it - 1] = 1.0 if rec["hdif"] > 0 else float(np.exp(rec["hdif"]))
-            if before["active"] and before["next_window_end"] == before["step"]:      # (this step was its window's last)
-                adapt_windows.append((it, before["window_count"] + 1))
+        for out, state in watching:
+            out.step(ctx, state, it, rec)
         hmcprior.nfevals += rec["nfevals"]
         if rec["accepted"]:
             stats.nAccept += 1
@@ -735,30 +864,8 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
             hmcmodel[:, it - 1] = model
             hmcdata[:, it] = pred if rec["accepted"] else hmcdata[:, it - 1]      # (:164-168: a rejection repeats the column)
     stats.moments = ctx.chain_moments()
-    if adapt is not None:
-        stats.adapt = {"nwarmup": nwarmup, "dt": adapt_dt, "alpha": adapt_alpha, "dt_final": info["dt"],
-                       "invM": ctx.chain_mass_diag() if adapt_opts["adapt_mass"] else None, "windows": adapt_windows}
-    if hist is not None:
-        stats.hist = ctx.chain_hist() + (bins, targets.copy())
-    if data_moments:
-        stats.dataMoments = ctx.chain_data_moments()
-    if ess is not None:
-        # (a chain that ends inside its burn-in has counted nothing: the read-outs need a commit, the rest of the result stands)
-        count = ctx.chain_acov_count()
-        (_, mean, acov), (tau, e, window) = (ctx.chain_acov(), ctx.chain_ess()) if count > 0 else ((0, None, None), (None, None, None))
-        stats.ess = {"count": count, "maxlag": maxlag, "targets": np.arange(nparam, dtype=np.int64) if ess_targets is None else ess_targets.copy(),
-                     "mean": mean, "acov": acov, "tau": tau, "ess": e, "window": window, "misfit": None}
-        D = stats.hmstats[0, 1 + hmcprior.burninsamples:]      # the data misfit of the counted samples: the same estimator on the host
-        if len(D):
-            a = acovOf(D, maxlag)
-            t1, e1, w1 = essFromAcov(a, len(D))
-            stats.ess["misfit"] = {"count": len(D), "mean": float(D.mean()), "acov": a, "tau": t1, "ess": e1, "window": w1}
-    if cov is not None:
-        # (as for ess: a chain that ends inside its burn-in has counted nothing)
-        count = ctx.chain_cov_count()
-        (_, mean, var, c), corr = (ctx.chain_cov(), ctx.chain_corr()) if count > 0 else ((0, None, None, None), None)
-        stats.cov = {"count": count, "rows": np.arange(nparam, dtype=np.int64) if cov_rows is None else cov_rows.copy(),
-                     "mean": mean, "var": var, "cov": c, "corr": corr}
+    for out, state in begun:
+        setattr(stats, out.field, out.read(ctx, state, stats, env))
     return hmcmodel, stats, hmcdata
 
 
@@ -775,32 +882,11 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     (fileio.getPosteriorModelFromMoments).  `keep_samples=False` (with device_chain): no sample comes back -- hmcmodel has zero
     columns and hmcdata its first column only; the moments are the result.  Checkpointing is not available with device_chain
     (ValueError): the warm-start history of the solves is part of a device chain's state.
-    `hist={...}` (with device_chain): per-cell histograms of ln sigma, streamed in the chain's commit like the moments, so that
-    marginal distributions and credible intervals need no sample history.  Keys, all optional: `targets` (active-cell indices, default
-    every cell; `sitePPDTargets` gives the cells under sites), `nbins` (300, the reference's npBins), `lo`, `hi` (ln of
-    hmcprior.sigBounds).  hmcstats.hist = (count, counts[ntarget, nbins], (nbins, lo, hi), targets): see histQuantiles,
-    histToLog10Rho, mergeHistograms, fileio.writeSitePPD, fileio.getPosteriorQuantileModels.  `data_moments=True` (with
-    device_chain): hmcstats.dataMoments = (count, mean[ndata], m2[ndata]) of the predicted data at the same samples -- the
-    posterior-predictive spread.  Neither changes the order of the random draws.
-    `ess={...}` (with device_chain): per-cell lagged autocovariances streamed in the commit, and from them the integrated
-    autocorrelation time and the effective sample size, computed on the GPU.  Keys, both optional: `targets` (default every cell) and
-    `maxlag` (63).  hmcstats.ess is a dict: count, maxlag, targets, mean, acov[maxlag + 1, ntarget], tau, ess, window (hmcmt_chain_ess,
-    include/hmcmt.h: window < 0 means the lags ran out and tau is a lower bound), and `misfit`, the same estimator applied here to the
-    data misfit of the counted samples.  A chain that ends inside its burn-in gives count 0 and None for the rest.  See acovOf, essFromAcov, mcseOfMean, mergeAcov, fileio.getESSModel.  The draws keep their order.
-    `cov={...}` (with device_chain): the posterior covariance and correlation between cells, streamed in the commit as cross moments
-    and folded in by a batched kernel, so that trade-offs between cells need no sample history.  Keys, both optional: `rows` (the
-    active-cell indices whose rows of the matrix are kept; default every cell, the full nparam x nparam matrix) and `batch` (commits
-    per update kernel, 1 .. 16, default 8; the results do not depend on it).  hmcstats.cov is a dict: count, rows, mean[nparam],
-    var[nparam], cov[nrow, nparam], corr[nrow, nparam] (biased estimator; hmcmt_chain_cov, include/hmcmt.h).  A chain that ends inside
-    its burn-in gives count 0 and None for the rest.  See covOf, mergeCov, fileio.getCorrelationModel.  The draws keep their order.
-    `adapt={...}` (with device_chain): a warm-up over the first `nwarmup` samples (default hmcprior.burninsamples, and never more: the
-    moments count behind the burn-in) tunes the step size by dual averaging towards the acceptance `delta` (0.8) and, with `mass`
-    (default True for massType "diagonal"), the diagonal of M^-1 by Stan's windowed variance of the chain's own samples, on the GPU
-    (hmcmt_chain_adapt_begin, include/hmcmt.h).  Further keys, all optional: gamma, t0, kappa, init_buffer, term_buffer, base_window,
-    dt_min, dt_max; see adaptPlan for the window defaults.  hmcprior.dt is the start and is not modified.  hmcstats.adapt is a dict:
-    nwarmup, dt[nsamples] (the step size each sample's trajectory used), alpha[nsamples], dt_final, invM (the final diagonal, None
-    without mass) and windows, a list of (end_step, n).  `invM=array` (with device_chain): the diagonal of M^-1 the chain starts with
-    instead of ones, for example an earlier run's adapted mass.  The draws keep their order.
+    The optional outputs of the device chain -- hist=, data_moments=, ess=, cov=, adapt= -- are one entry of CHAIN_OUTPUTS each, and
+    each entry's docstring is its paragraph here:
+    {CHAIN_OUTPUTS}
+    `invM=array` (with device_chain): the diagonal of M^-1 the chain starts with instead of ones, for example an earlier run's
+    adapted mass.  The draws keep their order.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -816,28 +902,20 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
         raise ValueError("runHMCSampler: checkpoint is not available with device_chain=True (use the host loop or device_leapfrog=True)")
     if not keep_samples and not device_chain:
         raise ValueError("runHMCSampler: keep_samples=False needs device_chain=True (only the device chain streams the posterior moments)")
-    if (hist is not None or data_moments) and not device_chain:
-        raise ValueError("runHMCSampler: hist and data_moments need device_chain=True (they are streamed in the device chain's commit)")
-    if ess is not None and not device_chain:
-        raise ValueError("runHMCSampler: ess needs device_chain=True (the autocovariances are streamed in the device chain's commit)")
-    if cov is not None and not device_chain:
-        raise ValueError("runHMCSampler: cov needs device_chain=True (the cross moments are streamed in the device chain's commit)")
-    if (adapt is not None or invM is not None) and not device_chain:
-        raise ValueError("runHMCSampler: adapt and invM need device_chain=True (the warm-up runs in the device chain)")
-    if adapt is not None:
-        adaptPlan(adapt, hmcprior)                             # (its errors before the context is touched and the first number is drawn)
+    # (every refusal before the context is touched and the first number is drawn)
+    outputs = {k: v for k, v in (("hist", hist), ("data_moments", {} if data_moments else None), ("ess", ess), ("cov", cov), ("adapt", adapt)) if v is not None}
+    on = [out for out in CHAIN_OUTPUTS if out.name in outputs]
+    needing = [(out.name, out.why) for out in on] + ([("invM", "it is the device chain's mass")] if invM is not None else [])
+    if needing and not device_chain:
+        raise ValueError("runHMCSampler: %s needs device_chain=True (%s)" % needing[0])
+    for out in on:
+        out.check(outputs[out.name], hmcprior)
     if invM is not None and hmcprior.massType != "diagonal":
         raise ValueError(f"runHMCSampler: invM needs massType \"diagonal\", not {hmcprior.massType!r}")
-    for name, given, keys in (("hist", hist, ("targets", "nbins", "lo", "hi")), ("ess", ess, ("targets", "maxlag")),
-                              ("cov", cov, ("rows", "batch"))):
-        unknown = set(given or ()) - set(keys)                 # (before the context is touched and the first number is drawn)
-        if unknown:
-            raise ValueError(f"runHMCSampler: {name} has no key {sorted(unknown)} ({', '.join(keys)})")
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, hist, data_moments, ess, cov,
-                                 adapt, invM)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -848,15 +926,7 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     cur.rhomodel = invParam.strModel.copy()               # file start model stays the chain state (:88)
     cur.momentum = getMomentumVector(nparam, cur, rng)
     prop = HMCParameter(nparam, cur.rhomodel.copy(), cur.momentum.copy(), cur.invM, cur.sqrtM)
-    # random homogeneous start / reference model (:100-109)
-    rho0 = 1.0 / np.exp(invParam.strModel[0])
-    if rhoref is None:
-        rhoref = np.round(rho0 * 0.5 + (rho0 * 1.5 - rho0 * 0.5) * rng.random())
-    if verbose:
-        print(f"Homogeneous starting model with a resistivity of {rhoref} Ωm is used.")
-    strModel = np.log(np.ones(nparam) / rhoref)
-    invParam.strModel = strModel.copy()
-    invParam.refModel = strModel.copy()
+    _homogeneous_start(invParam, rhoref, rng, verbose)     # (behind the first momentum's normals, as the reference draws)
     startD, startK, startH, startM, predData = getHamiltonian(mtData, mtMesh, invParam, hmcprior, cur, ctx,
                                                               reuse_forward)
     if device_leapfrog:
@@ -914,7 +984,23 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     return hmcmodel, stats, hmcdata
 
 
+if runHMCSampler.__doc__:                                   # (python -OO has none)
+    runHMCSampler.__doc__ = runHMCSampler.__doc__.replace("{CHAIN_OUTPUTS}", "\n    ".join(type(out).__doc__ for out in CHAIN_OUTPUTS))
+
+
 # --------------------------------------------------------------------------------------------
+def gatherBlockFields(nparam, ncols, nsamples, ndata, with_moments):
+    """One chain's block in parallelHMCSampler's all-gather: its fields in order, (name, number of doubles).  Their sum is the block."""
+    fields = [("model", nparam * ncols), ("hmstats", 4 * (nsamples + 1)), ("acceptstats", nsamples), ("data", 2 * ndata * (ncols + 1)),
+              ("secs_and_flag", 2)]
+    return fields + ([("count", 1), ("mean", nparam), ("m2", nparam)] if with_moments else [])
+
+
+def _block_views(buf, fields):
+    """name -> that field's stretch of the block `buf` (a view)"""
+    return dict(zip([name for name, _ in fields], np.split(buf, np.cumsum([size for _, size in fields])[:-1])))
+
+
 def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, outdir=None, nchains=None,
                        run_chain=None, device_id=None, context_factory=None, chains_per_gpu=1, gather="torch", **sampler_kw):
     """Independent chains, one process per GPU (parallelHMC.jl:10-49).
@@ -942,10 +1028,11 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     (hmcmt_allgather_samples, include/hmcmt.h -- what a non-Python host would call) instead of torch's; the process
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
-    `path.chain<k>` per chain; device_chain=True, keep_samples=False, hist=..., ess=..., cov=..., adapt=...; hmcstats.adapt stays on the chain's own rank, as ess and cov do).
+    `path.chain<k>` per chain; device_chain=True, keep_samples=False and the device chain's optional outputs).  What those outputs
+    fill -- every HMCStatus field of CHAIN_OUTPUTS -- is not gathered: it stays with the chain on the chain's own rank.
     Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
     count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
-    gelmanRubin).  A chain's block in the gather is, in doubles,
+    gelmanRubin).  A chain's block in the gather is, in doubles (the sum of gatherBlockFields, which packing and unpacking walk),
         nparam * ncols + 4 * (nsamples + 1) + nsamples + 2 * ndata * (ncols + 1) + 2   [+ 1 + 2 * nparam with moments],
     ncols = nsamples, or 0 with keep_samples=False: then 2 * nparam + 5 * nsamples + 2 * ndata + 7 instead of
     nparam * nsamples + ...  Without either keyword the layout is what it was.  With fewer chains than ranks, the ranks that run none
@@ -1035,22 +1122,20 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
         ncols, with_moments = int(lay[0]), bool(lay[1])
     ndata = len(invParam.obsData)
     per = (nchains + world - 1) // world                   # chain slots per rank (padded)
-    blk = nparam * ncols + 4 * (nsamples + 1) + nsamples + 2 * ndata * (ncols + 1) + 2 + ((1 + 2 * nparam) if with_moments else 0)
+    fields = gatherBlockFields(nparam, ncols, nsamples, ndata, with_moments)
+    blk = sum(size for _, size in fields)
 
     def pack(slot):
         c = rank + slot * world
         buf = np.zeros(blk)
         if c in results:
             model, stats, data, secs = results[c]
-            o = 0
-            buf[o:o + model.size] = model.reshape(-1); o += model.size
-            buf[o:o + stats.hmstats.size] = stats.hmstats.reshape(-1); o += stats.hmstats.size
-            buf[o:o + nsamples] = stats.acceptstats.astype(float); o += nsamples
-            buf[o:o + 2 * data.size] = data.reshape(-1).view(np.float64); o += 2 * data.size
-            buf[o] = secs; buf[o + 1] = 1.0; o += 2
+            part = {"model": model, "hmstats": stats.hmstats, "acceptstats": stats.acceptstats.astype(float),
+                    "data": data.reshape(-1).view(np.float64), "secs_and_flag": [secs, 1.0]}
             if with_moments:
-                count, mean, m2 = stats.moments
-                buf[o] = count; buf[o + 1:o + 1 + nparam] = mean; buf[o + 1 + nparam:o + 1 + 2 * nparam] = m2
+                part.update(zip(("count", "mean", "m2"), stats.moments))
+            for name, view in _block_views(buf, fields).items():
+                view[:] = np.reshape(part[name], -1)
         return buf
 
     local = np.concatenate([pack(s) for s in range(per)]) if per else np.zeros(0)
@@ -1077,22 +1162,17 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
             c = r + s * world
             if c >= nchains:
                 continue
-            buf = allbuf[r, s]
-            o = 0
-            model = buf[o:o + nparam * ncols].reshape(nparam, ncols).copy(); o += nparam * ncols
-            hm = buf[o:o + 4 * (nsamples + 1)].reshape(4, nsamples + 1).copy(); o += 4 * (nsamples + 1)
-            acc = buf[o:o + nsamples] > 0.5; o += nsamples
-            data = buf[o:o + 2 * ndata * (ncols + 1)].copy().view(np.complex128).reshape(ndata, ncols + 1)
-            o += 2 * ndata * (ncols + 1)
-            secs[c] = float(buf[o]); o += 2
-            hmcmodel[c], hmcdata[c] = model, data
-            hmcstats[c] = HMCStatus(int(acc.sum()), int((~acc).sum()), acc, hm)
+            part = _block_views(allbuf[r, s], fields)
+            acc = part["acceptstats"] > 0.5
+            hmcmodel[c] = part["model"].reshape(nparam, ncols).copy()
+            hmcdata[c] = part["data"].copy().view(np.complex128).reshape(ndata, ncols + 1)
+            secs[c] = float(part["secs_and_flag"][0])
+            hmcstats[c] = HMCStatus(int(acc.sum()), int((~acc).sum()), acc, part["hmstats"].reshape(4, nsamples + 1).copy())
             if with_moments:
-                hmcstats[c].moments = (int(round(buf[o])), buf[o + 1:o + 1 + nparam].copy(), buf[o + 1 + nparam:o + 1 + 2 * nparam].copy())
-            if c in results:                                # (ess= is not gathered: a chain's own rank keeps it, for mergeAcov)
-                hmcstats[c].ess = getattr(results[c][1], "ess", None)
-                hmcstats[c].cov = getattr(results[c][1], "cov", None)     # (nor is cov=: see mergeCov)
-                hmcstats[c].adapt = getattr(results[c][1], "adapt", None) # (nor is adapt=: each chain warms up on its own)
+                hmcstats[c].moments = (int(round(part["count"][0])), part["mean"].copy(), part["m2"].copy())
+            if c in results:                                # (what the optional outputs fill is not gathered: a chain's own rank keeps it)
+                for out in CHAIN_OUTPUTS:
+                    setattr(hmcstats[c], out.field, getattr(results[c][1], out.field, None))
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

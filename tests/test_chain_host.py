@@ -369,3 +369,153 @@ def test_device_chain_refuses_checkpoints_and_keep_samples_needs_it(tmp_path):
                               device_chain=True, checkpoint=str(tmp_path / "c.npz"), checkpoint_every=1)
     with pytest.raises(ValueError, match="keep_samples"):
         sampler.runHMCSampler(mesh, data, inv, prior, np.random.default_rng(1), ctx=OracleContext(mesh, data, inv), keep_samples=False)
+
+
+# ---- the optional outputs together, and through parallelHMCSampler -----------------------------------------------------------------
+HIST_KW = {"nbins": 17, "lo": -6.0, "hi": -3.5}          # (targets [3, 3, n - 1, 0]: a repeat, the last cell and the first)
+OUT_PRIOR = dict(totalsamples=7, burninsamples=2, dt=0.02, timestep=[1, 3], sigBounds=[1e-4, 1.0])
+
+
+def _combined_context():
+    """The stand-in with the histogram, data-moment and autocovariance accumulators at once: their chain_begin / chain_step overrides
+    chain through super()."""
+    from tests.test_acov_host import OracleAcovContext
+    from tests.test_hist_host import OracleHistContext
+
+    class OracleOutputsContext(OracleHistContext, OracleAcovContext):
+        pass
+
+    return OracleOutputsContext
+
+
+def _same(a, b):
+    """equality, array for array, of what fills an HMCStatus field: tuples, dicts, arrays, numbers, None"""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is None and b is None
+    return np.array_equal(np.asarray(a), np.asarray(b))
+
+
+def test_outputs_together_are_the_outputs_alone():
+    """hist, data_moments and ess in one run: the chain is the chain without them, and every output is what its keyword alone gives."""
+    mesh, data, inv, _ = make_problem("tiny")
+    n = len(inv.strModel)
+    Ctx = _combined_context()
+    kws = {"hist": dict(HIST_KW, targets=[3, 3, n - 1, 0]), "data_moments": True, "ess": {"maxlag": 3}}
+    run = lambda **kw: sampler.runHMCSampler(copy.deepcopy(mesh), data, copy.deepcopy(inv), HMCPrior(**OUT_PRIOR), np.random.default_rng(21),
+                                             ctx=Ctx(mesh, data, inv), device_chain=True, **kw)
+    hm0, st0, hd0 = run()
+    hm1, st1, hd1 = run(**kws)
+    assert set(st0.acceptstats.tolist()) == {True, False}
+    assert (st0.hist, st0.dataMoments, st0.ess, st0.cov, st0.adapt) == (None,) * 5
+    assert np.array_equal(hm1, hm0) and np.array_equal(hd1, hd0) and np.array_equal(st1.hmstats, st0.hmstats)
+    assert np.array_equal(st1.acceptstats, st0.acceptstats) and _same(st1.moments, st0.moments) and st1.moments[0] == 5
+    for key, field in (("hist", "hist"), ("data_moments", "dataMoments"), ("ess", "ess")):
+        _, alone, _ = run(**{key: kws[key]})
+        assert getattr(st1, field) is not None and _same(getattr(st1, field), getattr(alone, field)), key
+        assert [f for f in ("hist", "dataMoments", "ess") if getattr(alone, f) is not None] == [field]
+    assert st1.hist[0] == st1.dataMoments[0] == st1.ess["count"] == 5 and st1.ess["misfit"]["count"] == 5
+
+
+class _Recorded:
+    """Hands every method of a context on and logs its name."""
+
+    def __init__(self, ctx):
+        self._ctx, self.log = ctx, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._ctx, name)
+        if not callable(fn):
+            return fn
+
+        def logged(*a, **kw):
+            self.log.append(name)
+            return fn(*a, **kw)
+
+        return logged
+
+
+def test_order_of_the_library_calls_up_to_the_first_momentum():
+    """set_prior (set_mass), chain_begin at the homogeneous model, chain_state, chain_begin at the file's model and chain_set_energy,
+    the outputs' begins in the order hist, data_moments, ess, cov, adapt, chain_adapt_info, chain_momentum -- and no begin behind it.
+    The stand-in has no covariance and no warm-up: the second run gives it call-compatible stubs that compute nothing (count 0, a
+    warm-up that leaves dt alone), which is all the order needs."""
+    mesh, data, inv, _ = make_problem("tiny")
+    n = len(inv.strModel)
+    kws = {"hist": dict(HIST_KW, targets=[3, 3, n - 1, 0]), "data_moments": True, "ess": {"maxlag": 3}}
+    begins = ["chain_hist_begin", "chain_data_moments_begin", "chain_acov_begin"]
+
+    def logged(ctx, prior, **kw):
+        rec = _Recorded(ctx)
+        sampler.runHMCSampler(copy.deepcopy(mesh), data, copy.deepcopy(inv), prior, np.random.default_rng(21), ctx=rec, device_chain=True, **kw)
+        first = rec.log.index("chain_momentum")
+        assert not [c for c in rec.log[first:] if c.endswith("begin")]
+        tail = rec.log[first:]
+        assert tail.index("chain_moments") < min(i for i, c in enumerate(tail) if c in READS)     # (chain_moments: the first read-out)
+        assert tail.index("chain_moments") > max(i for i, c in enumerate(tail) if c in ("chain_step", "chain_momentum"))
+        return rec.log[:first + 1]
+
+    READS = ("chain_hist", "chain_data_moments", "chain_acov_count", "chain_acov", "chain_ess", "chain_cov_count", "chain_mass_diag")
+    Ctx = _combined_context()
+    assert logged(Ctx(mesh, data, inv), HMCPrior(**OUT_PRIOR), **kws) == \
+        ["set_prior", "chain_begin", "chain_state", "chain_begin", "chain_set_energy"] + begins + ["chain_momentum"]
+
+    class Stubbed(Ctx):
+        def set_mass(self, kind):
+            pass
+
+        def chain_cov_begin(self, rows, batch):
+            assert self.chain["p"] is None
+
+        def chain_cov_count(self):
+            return 0
+
+        def chain_adapt_begin(self, nwarmup, **opts):
+            assert self.chain["p"] is None
+
+        def chain_adapt_info(self):
+            return {"dt": self.prior.dt, "active": 0, "next_window_end": -1, "step": len(self.chain["committed"]), "window_count": 0}
+
+    prior = HMCPrior(massType="nondiagonal", **OUT_PRIOR)
+    assert logged(Stubbed(mesh, data, inv), prior, cov={"rows": [0, 3]}, adapt={"nwarmup": 2}, **kws) == \
+        ["set_prior", "set_mass", "chain_begin", "chain_state", "chain_begin", "chain_set_energy"] + begins + \
+        ["chain_cov_begin", "chain_adapt_begin", "chain_adapt_info", "chain_momentum"]
+
+
+def test_parallel_sampler_keeps_every_output_of_a_local_chain():
+    """hist and dataMoments stay with a chain that ran on this rank, as ess, cov and adapt do: the pooled histogram of two chains is
+    the histogram of their kept samples pooled."""
+    from tests import hist_ref
+    Ctx = _combined_context()
+    mesh, data, inv, _ = make_problem("tiny")
+    n = len(inv.strModel)
+    t = np.array([3, 3, n - 1, 0])
+    hm, hs, hd = sampler.parallelHMCSampler(mesh, data, inv, HMCPrior(**OUT_PRIOR), nchains=2, seed=5, device_chain=True,
+                                            hist=dict(HIST_KW, targets=t), data_moments=True, ess={"maxlag": 3},
+                                            context_factory=lambda m, d, i, dev: Ctx(m, d, i))
+    assert len(hs) == 2 and all(st.hist is not None and st.dataMoments is not None and st.ess is not None for st in hs)
+    assert all(st.cov is None and st.adapt is None for st in hs)
+    for c in range(2):
+        assert hs[c].hist[0] == 5 and hs[c].hist[2] == (17, -6.0, -3.5) and np.array_equal(hs[c].hist[3], t)
+        assert np.array_equal(hs[c].hist[1], hist_ref.counts_of(list(hm[c][:, 2:].T), t, 17, -6.0, -3.5))
+        post = hd[c][:, 3:]                                  # (column 0 is the start's)
+        assert hs[c].dataMoments[0] == 5 and np.allclose(hs[c].dataMoments[1], post.mean(axis=1), rtol=1e-13, atol=0)
+    assert not np.array_equal(hm[0], hm[1])              # (two chains, two streams)
+    total, counts, bins, targets = sampler.mergeHistograms([st.hist for st in hs])
+    pooled = list(hm[0][:, 2:].T) + list(hm[1][:, 2:].T)
+    assert total == 10 and bins == (17, -6.0, -3.5) and np.array_equal(counts, hist_ref.counts_of(pooled, t, 17, -6.0, -3.5))
+
+
+def test_gather_block_layout_sums_to_the_documented_size():
+    """the fields of a chain's block add up to the formula of parallelHMCSampler's docstring"""
+    nparam, ns, ndata = 37, 6, 10
+    for ncols, with_moments in ((ns, True), (0, True), (ns, False)):
+        fields = sampler.gatherBlockFields(nparam, ncols, ns, ndata, with_moments)
+        assert [name for name, _ in fields][:5] == ["model", "hmstats", "acceptstats", "data", "secs_and_flag"]
+        doc = nparam * ncols + 4 * (ns + 1) + ns + 2 * ndata * (ncols + 1) + 2 + ((1 + 2 * nparam) if with_moments else 0)
+        assert sum(size for _, size in fields) == doc and all(size >= 0 for _, size in fields)
+        if ncols == 0 and with_moments:
+            assert doc == 2 * nparam + 5 * ns + 2 * ndata + 7

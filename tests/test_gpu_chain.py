@@ -202,6 +202,53 @@ def test_chain_with_the_wm_mass(name):
     assert relmax(hm1, hm0) < 1e-7
 
 
+def same_bits(a, b):
+    """bit for bit, through what fills an HMCStatus field: tuples, lists, dicts, arrays, numbers, None"""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(same_bits(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def test_sampler_outputs_together_are_the_outputs_alone():
+    """runHMCSampler(device_chain=True) with hist, data_moments, ess and cov all on, none on and one at a time -- every run on a context
+    of its own, so that every chain's solves start cold -- : the chain keeps its bits whatever rides on its commit, and every
+    HMCStatus field has the bits its keyword alone gives (a begin in the wrong place would count nothing or meet an ended accumulator,
+    a read-out out of order the flush inside a batch of the covariance).  Then the same with a warm-up in front."""
+    n = len(problem("tiny")[2].strModel)
+    kws = {"hist": {"targets": [3, 3, n - 1, 0], "nbins": 17}, "data_moments": True, "ess": {"maxlag": 3}, "cov": {"rows": [0, 3], "batch": 2}}
+    fields = {"hist": "hist", "data_moments": "dataMoments", "ess": "ess", "cov": "cov", "adapt": "adapt"}
+    go = lambda **kw: run("tiny", prior_of(6, 2), device_chain=True, **kw)
+
+    def same_chain(a, b):
+        (hm0, st0, hd0, mom0, recs0), (hm1, st1, hd1, mom1, recs1) = a, b
+        return (same_bits(hm0, hm1) and same_bits(hd0, hd1) and same_bits(st0.hmstats, st1.hmstats) and same_bits(st0.acceptstats, st1.acceptstats)
+                and (st0.nAccept, st0.nReject) == (st1.nAccept, st1.nReject) and same_bits(st0.moments, st1.moments) and same_bits(mom0, mom1)
+                and [L for L, _ in recs0] == [L for L, _ in recs1] and all(r0 == r1 for (_, r0), (_, r1) in zip(recs0, recs1)))
+
+    none, allon = go(), go(**kws)
+    assert 0 < none[1].nAccept < 6 and none[1].moments[0] == 4
+    assert all(getattr(none[1], f) is None for f in fields.values())
+    assert same_chain(allon, none)
+    st = allon[1]
+    assert st.hist[0] == st.dataMoments[0] == st.ess["count"] == st.cov["count"] == 4 and st.ess["misfit"]["count"] == 4
+    assert st.hist[1].shape == (4, 17) and st.ess["acov"].shape == (4, n) and st.cov["cov"].shape == (2, n) and st.adapt is None
+    for key in kws:
+        alone = go(**{key: kws[key]})
+        assert same_chain(alone, none), key
+        assert getattr(st, fields[key]) is not None and same_bits(getattr(st, fields[key]), getattr(alone[1], fields[key])), key
+        assert [k for k in fields if getattr(alone[1], fields[k]) is not None] == [key]
+    warm, warm_all = go(adapt={"nwarmup": 2}), go(adapt={"nwarmup": 2}, **kws)
+    assert same_chain(warm_all, warm)
+    assert warm[1].adapt["nwarmup"] == 2 and warm[1].adapt["dt"].shape == (6,) and same_bits(warm_all[1].adapt, warm[1].adapt)
+    assert all(getattr(warm_all[1], fields[k]) is not None for k in fields)
+    assert all(getattr(warm_all[1], fields[k])[0 if isinstance(getattr(warm_all[1], fields[k]), tuple) else "count"] == 4 for k in kws)
+
+
 def test_an_evaluation_between_two_steps_is_noticed():
     ctx, inv, m_other = fresh()
     try:
