@@ -2,6 +2,7 @@
 //
 // One translation unit in several files:
 //   hmcmt_hip.hip     this file: the context, the host orchestration of an evaluation (evaluate / solve), the C ABI
+//   hmcmt_knobs.h     the one reader of the environment variables (Knobs, read_knobs); Config below is what creation makes of them
 //   host_jacobian.h   host code of the calls that borrow the context: explicit Jacobian, Jacobian products, block products
 //   kernels_cocg.h    Solver state, deterministic reductions (DPP wave sums), classic COCG kernels (Jacobi / plain FDM
 //                     preconditioners; the fp64 restart of a stagnating mixed-precision solve)
@@ -36,6 +37,7 @@
 #include "../../include/hmcmt_debug.h"
 #include "hmcmt_host.h"
 #include "hmcmt_items.h"
+#include "hmcmt_knobs.h"
 
 using namespace hmcmt;
 
@@ -93,7 +95,46 @@ struct ChainTimer {
 // ----------------------------------------------------------------------------------------------
 // context
 // ----------------------------------------------------------------------------------------------
+// What hmcmt_create decides once -- the knobs as read (Knobs: hmcmt_knobs.h) and everything derived from them, the mesh and the
+// device (make_config) -- and nothing changes afterwards: the context holds it as a const member, so an assignment to one of these
+// outside make_config does not compile.  The fields the kernels take by value (RT, RT2, RTS, splitT, xInFwd, twist, and stallIt /
+// w2 of Knobs) are copied into Solver / View by create_impl.
+struct Config : Knobs {
+    int device = 0;
+    int shareIdx = 0, shareCnt = 1;       // this context's share of every XCD's CUs (hmcmt_next_cu_share): index, 1 / 2 / 4 parts
+    unsigned shareMask = 0xF;             // ... as quarters
+    size_t maxLds = 64 * 1024;            // dynamic LDS the fused kernels may request
+    size_t maxLdsBack = 64 * 1024;
+    int bcCW = 0, bcSlots = 1;            // k_bc_fused: boundary columns per workgroup (0: k_bc_layers + k_bc_forward), edge slots
+    size_t bcLds = 0;
+    int bcbCW = 0, bcbSlots = 1;          // k_bc_blocked (meshes k_bc_fused's slabs do not fit): columns per workgroup (0: the two-kernel form)
+    int bcbNT = 512, bcbLBu = 14, bcbLBd = 8;   // its threads, layers per block of the two recurrences
+    size_t bcbLds = 0;
+    bool sensFusedAlways = false;         // HMCMT_SENS_FUSED=1: also where the persistent kernel leaves CUs free (launch_adjoint_side)
+    size_t sensFusedLds = 0;              // k_sens_fused: its LDS bytes (0: k_sens_layers + k_sens_profile + k_bcsens_pre; HMCMT_SENS_FUSED=0)
+    int RT = 0, RT2 = 0, RTS = 0;         // rows per tile of the stencil kernels, of k_update_fused<2>, of k_spmv_fused<2> (Solver)
+    int residThreads = 256;               // k_resid_pre
+    int upd2Threads = 256, upd2Batch = 6; // launch shape of k_update_fused<2> (launch_update2; HMCMT_UPD2)
+    int spmvThreads = 256;                // launch shape of k_spmv_fused (launch_spmv; HMCMT_SPMV)
+    int upd1Threads = 256;                // ... of k_update_fused<1> (HMCMT_UPD1)
+    // forward half of the FDM stage: slab width (in 16-mode tiles) of the fused kernel, 0 = the separate kernels -- where the fused
+    // one is asked for (fwdNtwFused: HMCMT_FUSED_FWD != 0 assumed, hmcmt_debug_fdm_fwd) and as configured
+    int fwdNtwFused = 0, fwdNtw = 0;
+    int splitT = 0, xInFwd = 0, twist = 0;   // Solver::splitT / xInFwd, Solver / View::twist
+    bool fusedBackFits = false;           // the fused back transform + post-smoother exists for this problem (pre-split operands, 16-row tile in LDS): fused_back_ok
+    // persistent solve kernel (kernels_persist.h)
+    int persistG = 0, persistCW = 0;      // workgroups per system, threads / 2 (0: the problem does not fit the kernel)
+    int persistCS = 1, persistGZ = 0;     // column parts of a row block (2: wide meshes, kernels_persist.h), row blocks per system
+    int persistMW = 32;                   // modes per slab of the persistent kernel's tridiagonal solves (32; 16 on tall meshes)
+    int persistSlots = 0;                 // system slots per XCD of the context's own problem (Inst::persistSlots)
+    size_t persistLds = 0;                // LDS bytes of psKern's kernels
+    const PsKernel* psKern[2] = {};       // the instantiations launch_persist runs for one / two sweeps (g_psKernels)
+    bool persistFillsShare = false;       // no CU of this context's share left over beside a solve (launch_adjoint_side)
+};
+
 struct hmcmt_ctx {
+    const Config cfg;
+    hmcmt_ctx(HostProblem&& problem, const hmcmt_options& o, const Config& c) : cfg(c), hp(std::move(problem)), opt(o) {}
     HostProblem hp;
     View v{};
     Solver sv{};
@@ -103,7 +144,10 @@ struct hmcmt_ctx {
     // solve, and give it back (Borrowed, host_jacobian.h): they copy this struct in front and assign it back behind, together with
     // v, sv, opt and stats, so that the context's next evaluation computes bit for bit what it would have.  A member whose value a
     // solve or an evaluation changes, and a later one reads, belongs HERE: as a plain member of hmcmt_ctx it leaves those calls
-    // changed, and nothing says so -- a chain that differs in the 12th digit after a Jacobian call.
+    // changed, and nothing says so -- a chain that differs in the 12th digit after a Jacobian call.  What creation decided cannot
+    // be such a member any more: it is `cfg`, const.  The plain members that remain are resources (streams, events, buffers and
+    // their sizes), counters and statistics, the memo, and the per-evaluation protocol flags -- solveBegun, preDone, psStart,
+    // side*, *WaitPending, specValid, lpFallback, solveFail --, which the bracket resets rather than saves.
     struct SolveState {
         long long evalCount = 0;
         unsigned profMask = 0;            // bit c: time category c with HIP events
@@ -150,7 +194,6 @@ struct hmcmt_ctx {
         bool psConstValid = false;
         bool dinvValid = true;                // Solver::dinv / dinv32 belong to the current model (ensure_dinv)
     } inst;
-    int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr;       // sigma-only sensitivity tables run beside the forward solve
     hipEvent_t evModel = nullptr, evSens = nullptr, evExtF = nullptr, evExtA = nullptr, evPiv = nullptr, evRec = nullptr;
@@ -164,17 +207,7 @@ struct hmcmt_ctx {
     u4v *d_Vbl = nullptr, *d_Vtbl = nullptr;      // ... lo parts: V = hi + lo to ~16 mantissa bits
     double *d_m = nullptr, *d_V = nullptr, *d_Vt = nullptr, *d_misfit = nullptr;
     double hostUs[4] = {0, 0, 0, 0}; long hostN = 0;      // HMCMT_TICKS: host time of the launch sequences around the solves
-    int residThreads = 256;               // k_resid_pre
     bool sensWaitPending = false, extAWaitPending = false;
-    bool noFusedStart = false, noSigmaRows = false, noCoefAll = false;     // environment knobs read at creation
-    bool wantTicks = false;               // HMCMT_TICKS: in-kernel wall-clock stamps (View::ticks), printed at destroy
-    int bcCW = 0, bcSlots = 1;            // k_bc_fused: boundary columns per workgroup (0: k_bc_layers + k_bc_forward), edge slots
-    size_t bcLds = 0;
-    bool sensFusedAlways = false;         // HMCMT_SENS_FUSED=1: also where the persistent kernel leaves CUs free (launch_adjoint_side)
-    size_t sensFusedLds = 0;              // k_sens_fused: its LDS bytes (0: k_sens_layers + k_sens_profile + k_bcsens_pre; HMCMT_SENS_FUSED=0)
-    int bcbCW = 0, bcbSlots = 1;          // k_bc_blocked (meshes k_bc_fused's slabs do not fit): columns per workgroup (0: the two-kernel form)
-    int bcbNT = 512, bcbLBu = 14, bcbLBd = 8;   // its threads, layers per block of the two recurrences
-    size_t bcbLds = 0;
     cplx* d_fieldsOut = nullptr;
     // pinned host staging
     int* h_nactive = nullptr;
@@ -187,24 +220,8 @@ struct hmcmt_ctx {
     double* d_ext[2] = {nullptr, nullptr};       // {w_0..w_{EXT_NP-1}, keep, count, ring heads, partial sums, ticket} (kernels_fused.h)
     cplx* d_guessCap[2] = {nullptr, nullptr};    // test hook hmcmt_debug_guess_capture: the initial guesses of the last evaluation [S*vstride] (allocated when first enabled)
     bool guessCapture = false;
-    double jacobiW = 0.8;                    // damping of the point-Jacobi halves (HMCMT_JACOBI_W; 0.7 in round 1: 0.8 saves 3-8 % of the iterations on structured models, costs 6-25 % on white-noise models of std >= 1)
-    int extrapNp = EXT_NP;                   // fields used by the initial-guess extrapolation (HMCMT_EXTRAP_POINTS = 2..EXT_NP)
-    bool fusedFwd = true;                    // forward transform + tridiagonal solve in one kernel (HMCMT_FUSED_FWD=0: separate)
     View sideView; const double* sideM = nullptr;   // deferred side-stream launches of the adjoint half (launch_adjoint_side)
     bool sidePending = false, sideExtrap = false, sideSens = false;
-    bool fusedBack = true;                   // back transform + post-smoother in one kernel (HMCMT_FUSED_BACK=0: separate)
-    int sweepsMode = 0;                      // HMCMT_SWEEPS: 1 / 2 damped Jacobi sweeps on each side of the FDM stage, 0 (default) = per solve
-    int sweepsUp = 12, sweepsDown = 6;       // auto: one sweep -> two above sweepsUp iterations (rounds 2-4: 30 -- a two-sweep iteration of the launch-per-phase loop cost 1.20 one-sweep
-                                             // ones; in the persistent kernel 1.15 / 1.10, and solves of 18-24 iterations near the true model gain 2-7 % from two), two -> one below sweepsDown (12: the first,
-                                             // cheap steps of every clamped burn-in trajectory switched back and the next ones up again)
-    long long* backStamps = nullptr;         // HMCMT_BACK_STAMPS: per-block s_memtime stamps of k_back_post (debug entry only)
-    size_t maxLdsBack = 64 * 1024;
-    bool twistOn = true;                     // HMCMT_TWIST=0: classic one-sided sweeps in the fused kernel as well
-    int upd2Threads = 256, upd2Batch = 6;    // launch shape of k_update_fused<2> (launch_update2; HMCMT_UPD2)
-    int spmvThreads = 256;                   // launch shape of k_spmv_fused (launch_spmv; HMCMT_SPMV)
-    int upd1Threads = 256;                   // ... of k_update_fused<1> (HMCMT_UPD1)
-    bool fusedFwdForce = false;              // HMCMT_FUSED_FWD=2: also where the heuristic prefers the separate kernels
-    size_t maxLds = 64 * 1024;               // dynamic LDS the fused kernels may request
     bool lpFallback = false;                 // this solve has switched its stragglers to the fp64 preconditioner
     // profiling
     int profEvery = 1;                // ... in every profEvery-th evaluation only (the brackets cost ~20 % if always on)
@@ -319,26 +336,14 @@ struct hmcmt_ctx {
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)
-    bool persistFillsShare = false;
-    int persistG = 0, persistCW = 0;      // workgroups per system, threads / 2 (0: the problem does not fit the kernel)
-    size_t persistLds = 0;                // LDS bytes of psKern's kernels
     unsigned long long persistTag = 0;    // ... the tag base of the next launch
     long long* d_pstamps = nullptr;       // HMCMT_STAMPS=persist
     long long persistSolves = 0, persistFallbacks = 0, persistTimeouts = 0;
-    int shareIdx = 0, shareCnt = 1;       // this context's share of every XCD's CUs (hmcmt_next_cu_share): index, 1 / 2 / 4 parts
-    unsigned shareMask = 0xF;             // ... as quarters
-    int persistCS = 1, persistGZ = 0;     // column parts of a row block (2: wide meshes, kernels_persist.h), row blocks per system
-    const PsKernel* psKern[2] = {};       // the instantiations launch_persist runs for one / two sweeps (g_psKernels; persist_setup)
     // the order in which the queues of the persistent kernel take the systems (PsLaunch::order; persist_balance): per solve kind
     int* d_psOrder = nullptr;             // [2][S]
     int* h_psOrder = nullptr;             // pinned staging of the same
-    bool psBalance = true;                // HMCMT_PERSIST_BALANCE=0: never
-    float psSmooth = 0.75f;               // weight of the older costs (HMCMT_PERSIST_BALANCE_SMOOTH; cfg5, 96-step chains: 0 -> 84.3, 0.5 -> 84.8, 0.75 -> 85.0 steps/s, index order 83.4)
-    unsigned persistSpin = PS_SPIN_LIMIT; // HMCMT_PS_SPIN: polls before a wait of the kernel gives up (tests shorten it)
     struct PsStart { int resid = 0, begin = 0; };      // the solve's start inside the persistent kernel (PsLaunch::resid / begin): set by evaluate_once for the NEXT solve
     PsStart psStart{};
-    bool lazyDinv = true;                 // HMCMT_LAZY_DINV=0: k_coef_all writes every system's Jacobi diagonal in every evaluation, as until round 6 (A/B)
-    bool psInKernelStart = true;          // HMCMT_PS_START=0: k_resid0 / k_solve_begin in launches of their own, as until round 5 (A/B)
     bool persistTimedOut = false;         // a wait of the last persistent launch timed out: evaluate() redoes the evaluation with the launch-per-phase loop
     int dbgPlace = 0;                     // test hook (hmcmt_debug_flags bit 2): 1 + index of the group of the next persistent launch that fails its placement check
     bool dbgPlaceAdj = false;             // ... (bit 4) not the next launch but the next ADJOINT one: forward launches pass it by
@@ -349,14 +354,11 @@ struct hmcmt_ctx {
     // solves is formed (two vector passes and a read-back: ~0.1 ms once in guardEvery evaluations) -- hmcmt_guard
     long long guardChecks = 0;
     double guardWorst = 0.0, guardLast = 0.0;
-    double guardLimit = 1e-6;             // HMCMT_GUARD_LIMIT: a checked residual above it is a "trip" (warning, next evaluation starts cold)
     long long guardTrips = 0;
     // kernels queued behind a persistent solve before the host knows its outcome (View::gate; evaluate(), solve())
-    int persistMW = 32;                   // modes per slab of the persistent kernel's tridiagonal solves (32; 16 on tall meshes)
     int* d_gate = nullptr;                // [2] device words written by the persistent kernel's last workgroup, per solve kind
     int gateGen = 0;                      // serial number of the persistent launches
     bool specValid = false;               // the last solve's speculative followers ran (the solve ended clean)
-    bool specOn = true;                   // HMCMT_SPEC=0: followers are queued after the host has seen the solve's outcome
     bool guardNow = false;                // the evaluation at hand is a guarded one
     // results of the last two host-API evaluations, keyed by the model: a sampler re-evaluates the model it has
     // just evaluated (getHamiltonian at the proposal, HMCSampler.jl:364; the first gradient of the next trajectory,
@@ -423,6 +425,15 @@ static thread_local std::string g_createError;      // (per thread: contexts of 
     } while (0)
 
 namespace {
+
+// scope guard: f runs on every way out
+template <class F>
+struct AtExit {
+    F f;
+    explicit AtExit(F g) : f(g) {}
+    AtExit(const AtExit&) = delete;
+    ~AtExit() { f(); }
+};
 
 template <class T>
 int dalloc(hmcmt_ctx* ctx, T** p, size_t n, bool zero = true) {
@@ -522,11 +533,14 @@ int launch_transform_lp(hmcmt_ctx* ctx, const float2* A, bool transposed, void* 
     return 0;
 }
 
-// the fused back transform + post-smoother is available for this problem (pre-split operands, 16-row tile in LDS)
-bool fused_back_ok(const hmcmt_ctx* ctx) {
-    const Solver& k = ctx->sv;
-    const size_t lds = (size_t)16 * k.NYP * sizeof(cplx) + (size_t)2 * ((k.NYP + 31) / 32) * 2 * 64 * 16;
-    return k.splitT && ctx->fusedBack && lds <= ctx->maxLdsBack && k.NYP <= 256;
+// Which of the two forms of a half of the FDM stage a launch takes: the hot path passes nothing (as configured); the debug entry
+// points, which compare the two, ask for one
+enum class FdmPath { Configured, Fused, Separate };
+// LDS of k_back_post: z tile + staged A fragments
+size_t back_post_lds(int NYP) { return (size_t)16 * NYP * sizeof(cplx) + (size_t)2 * ((NYP + 31) / 32) * 2 * 64 * 16; }
+// the fused back transform + post-smoother runs (it exists for this problem: Config::fusedBackFits; HMCMT_FUSED_BACK, or the caller's path)
+bool fused_back_ok(const hmcmt_ctx* ctx, FdmPath path = FdmPath::Configured) {
+    return ctx->cfg.fusedBackFits && (path == FdmPath::Configured ? ctx->cfg.fusedBack : path == FdmPath::Fused);
 }
 // grid of the fused stencil kernels for `ntiles` row tiles per system (tile_map, kernels_fused.h)
 dim3 tile_grid(const Solver& k, int ntiles) {
@@ -544,7 +558,7 @@ void launch_update2(hmcmt_ctx* ctx, const float2* pcur, const cplx* rin, cplx* r
     const dim3 grid = tile_grid(k, update2_tiles(k));
     const size_t lds = update2_lds(k);
 #define UPD2(NT, UB) hipLaunchKernelGGL((k_update_fused<2, NT, UB>), grid, dim3(NT), lds, ctx->stream, k, pcur, rin, rout, it, startOnly)
-    const int nt = ctx->upd2Threads, ub = ctx->upd2Batch;
+    const int nt = ctx->cfg.upd2Threads, ub = ctx->cfg.upd2Batch;
     if (nt == 1024) UPD2(1024, 4);
     else if (nt == 512 && ub <= 4) UPD2(512, 4);
     else if (nt == 512 && ub <= 6) UPD2(512, 6);
@@ -556,8 +570,8 @@ template <int SW>
 void launch_spmv(hmcmt_ctx* ctx, size_t lds, const float2* pin, float2* pout, int it) {
     const Solver& k = ctx->sv;
     const dim3 grid = tile_grid(k, SW == 2 ? (k.nz - 1 + k.RTS - 1) / k.RTS : k.NTR);
-    if (ctx->spmvThreads == 512) hipLaunchKernelGGL((k_spmv_fused<SW, 512>), grid, dim3(512), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
-    else if (ctx->spmvThreads == 1024) hipLaunchKernelGGL((k_spmv_fused<SW, 1024>), grid, dim3(1024), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
+    if (ctx->cfg.spmvThreads == 512) hipLaunchKernelGGL((k_spmv_fused<SW, 512>), grid, dim3(512), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
+    else if (ctx->cfg.spmvThreads == 1024) hipLaunchKernelGGL((k_spmv_fused<SW, 1024>), grid, dim3(1024), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
     else hipLaunchKernelGGL((k_spmv_fused<SW, 256>), grid, dim3(256), lds, ctx->stream, k, ctx->inst.d_partZZ, pin, pout, it, ctx->opt.maxit);
 }
 // two sweeps per side exist on the fused mixed-precision path (and on the fp64 path of the restarts)
@@ -571,17 +585,18 @@ bool sweeps2_ok(const hmcmt_ctx* ctx) {
 
 // forward half of the mixed-precision FDM stage: y32 = tridiag^-1 (t32 V); fused kernel when its LDS slabs fit
 // back half of the FDM stage + post-smoother: fused kernel on the pre-split path when its 16-row tile fits LDS
-int launch_back_post(hmcmt_ctx* ctx) {
+// stamps: per-block s_memtime stamps of k_back_post (HMCMT_BACK_STAMPS, debug entry only)
+int launch_back_post(hmcmt_ctx* ctx, FdmPath path = FdmPath::Configured, long long* stamps = nullptr) {
     Solver& k = ctx->sv;
     const int NT = k.NYP / 16, NW = std::min(8, (NT + LP_NTW - 1) / LP_NTW);
-    const size_t lds = (size_t)16 * k.NYP * sizeof(cplx) + (size_t)2 * ((k.NYP + 31) / 32) * 2 * 64 * 16;   // z tile + staged A fragments
+    const size_t lds = back_post_lds(k.NYP);
     dim3 vg(k.NB, k.S), vb(VBLOCK);
-    if (k.splitT && ctx->fusedBack && lds <= ctx->maxLdsBack && k.NYP <= 256) {      // the kernel holds all of a wave's V fragments: 8 k-groups, 2 tiles
+    if (fused_back_ok(ctx, path)) {      // the kernel holds all of a wave's V fragments: 8 k-groups, 2 tiles
         const int nwg = (k.nz - 1 + BP_OWN - 1) / BP_OWN;
         if (k.sweeps == 2) {
             { ProfScope ps(ctx, 0, true);
               hipLaunchKernelGGL((k_back_post<1, 2>), dim3(nwg, k.S), dim3(64 * NW), lds, ctx->stream, k, k.y32, ctx->d_Vtb, ctx->d_Vtbl,
-                                 ctx->inst.d_partZZ, NW, ctx->backStamps); }
+                                 ctx->inst.d_partZZ, NW, stamps); }
             if (k.merged2) return 0;                  // (the second post-sweep runs inside k_spmv_fused<2>)
             ProfScope ps(ctx, 7, true);
             hipLaunchKernelGGL(k_post2, dim3(k.NTR, k.S), vb, (size_t)(k.RT + 2) * k.NYP * sizeof(float2), ctx->stream, k, ctx->inst.d_partZZ);
@@ -589,7 +604,7 @@ int launch_back_post(hmcmt_ctx* ctx) {
         }
         ProfScope ps(ctx, 0, true);
         hipLaunchKernelGGL((k_back_post<1, 1>), dim3(nwg, k.S), dim3(64 * NW), lds, ctx->stream, k, k.y32, ctx->d_Vtb, ctx->d_Vtbl,
-                           ctx->inst.d_partZZ, NW, ctx->backStamps);
+                           ctx->inst.d_partZZ, NW, stamps);
         return 0;
     }
     int rc;
@@ -610,23 +625,24 @@ size_t fdm_fwd_lds(const Solver& k, int ntw, int twist) {
     const size_t rl = (size_t)(twist ? mid + 1 : k.NZP) + 4 * FW_TB, nreg = twist ? 2 : 1, sw = 16 * (size_t)ntw;
     return (((size_t)k.NZP * sizeof(float) + 127) & ~(size_t)127) + (sw + 2 * FW_TB * sw + 3 * nreg * rl * sw + 2 * FW_TB * sw) * sizeof(c32) + 64;   // (+ 8 per-wave sums of the x update)
 }
-int fdm_fwd_ntw(const hmcmt_ctx* ctx) {
-    const Solver& k = ctx->sv;
+// fusedFwd: the fused kernel is wanted (HMCMT_FUSED_FWD != 0), force: also where the heuristic prefers the separate kernels (= 2)
+int fdm_fwd_ntw(const Solver& k, bool fusedFwd, bool force, bool twistOn, size_t maxLds) {
     // The fused kernel pays off while every slab workgroup of a launch is resident at once and re-reading a
     // system's rows per slab is cheap: 32-mode slabs that fit LDS on meshes up to 256 nodes wide (measured:
     // 21 vs 29 us at 200x100 cells; at 400x200 the separate kernels win, 146 vs 219 us).  HMCMT_FUSED_FWD=2
     // forces it (16-mode slabs if need be), =0 disables it.
-    if (!ctx->fusedFwd) return 0;
-    const int tw = ctx->twistOn ? 1 : 0;
-    if (fdm_fwd_lds(k, FW_NTW, tw) <= ctx->maxLds && (k.NYP <= 256 || ctx->fusedFwdForce)) return FW_NTW;
-    if (ctx->fusedFwdForce && fdm_fwd_lds(k, 1, tw) <= ctx->maxLds) return 1;
+    if (!fusedFwd) return 0;
+    const int tw = twistOn ? 1 : 0;
+    if (fdm_fwd_lds(k, FW_NTW, tw) <= maxLds && (k.NYP <= 256 || force)) return FW_NTW;
+    if (force && fdm_fwd_lds(k, 1, tw) <= maxLds) return 1;
     return 0;
 }
 
-int launch_fdm_fwd(hmcmt_ctx* ctx, const float2* pX = nullptr) {        // pX: this iteration's direction -> the kernel's idle waves do x += alpha p
+int launch_fdm_fwd(hmcmt_ctx* ctx, const float2* pX = nullptr, FdmPath path = FdmPath::Configured) {        // pX: this iteration's direction -> the kernel's idle waves do x += alpha p
     Solver& k = ctx->sv;
     auto ldsFor = [&](int ntw) { return fdm_fwd_lds(k, ntw, k.twist); };
-    const int ntw = k.splitT ? fdm_fwd_ntw(ctx) : 0;       // (k.splitT is set from fdm_fwd_ntw: the operand format goes with the path)
+    // (k.splitT is set from the same width: the operand format goes with the path)
+    const int ntw = !k.splitT ? 0 : path == FdmPath::Configured ? ctx->cfg.fwdNtw : path == FdmPath::Fused ? ctx->cfg.fwdNtwFused : 0;
     if (ntw) {
         const int G = (k.NZP + 7) / 8, per = (G + 7) / 8, nw = (G + per - 1) / per;
         const dim3 grid(((k.NYP / 16 + ntw - 1) / ntw) * k.S), block(64 * nw);
@@ -735,21 +751,20 @@ static bool devlock_try(DevLock& L) {
     L.held = flock(L.fd, LOCK_EX | LOCK_NB) == 0;
     return L.held;
 }
-static void devlock_ref(int dev) {
+static void devlock_ref(const Config& cfg) {      // (HMCMT_PERSIST_LOCK, HMCMT_LOCK_DIR: those of the first context that takes the device's lock)
+    const int dev = cfg.device;
     if (dev < 0 || dev >= MAXDEV) return;
     std::lock_guard<std::mutex> g(g_lockMu);
     DevLock& L = g_devLock[dev];
     if (L.refs++ > 0) return;
-    const char* off = getenv("HMCMT_PERSIST_LOCK");
-    if (off && off[0] == '0') { L.held = true; return; }
+    if (!cfg.persistLock) { L.held = true; return; }
     char bus[64] = "unknown";
     if (hipDeviceGetPCIBusId(bus, sizeof bus, dev) != hipSuccess) { (void)hipGetLastError(); snprintf(bus, sizeof bus, "dev%d", dev); }
     for (char* c = bus; *c; ++c) if (*c == ':' || *c == '/') *c = '_';
     // $HMCMT_LOCK_DIR, else /tmp: the one directory every user's processes on a machine share (a per-user runtime directory would
     // not coordinate two users' processes on one GPU).  The name is predictable, so the open follows no symlink (a planted link
     // could make it create or open a file elsewhere with this process's rights) and the file carries no data.
-    const char* dir = getenv("HMCMT_LOCK_DIR");
-    const std::string path = std::string(dir && dir[0] ? dir : "/tmp") + "/hmcmt_persist_" + bus + ".lock";
+    const std::string path = cfg.lockDir + "/hmcmt_persist_" + bus + ".lock";
     L.fd = open(path.c_str(), O_CREAT | O_RDWR | O_CLOEXEC | O_NOFOLLOW, 0666);
     if (L.fd < 0) L.fd = open(path.c_str(), O_RDONLY | O_CLOEXEC | O_NOFOLLOW);      // (another user's file: a shared lock needs no write access)
     if (L.fd < 0) { L.held = true; return; }           // (no lock directory: nothing to coordinate through)
@@ -776,18 +791,20 @@ static bool devlock_held(int dev) {
 // the persistent solve kernel applies to the solve at hand (default path, a mesh its tiles fit, alone on the device)
 // (this context is alone on its device in the process, and the process holds the device's lock)
 bool persist_alone(const hmcmt_ctx* ctx) {
-    if (ctx->device < 0 || ctx->device >= MAXDEV) return false;
+    if (ctx->cfg.device < 0 || ctx->cfg.device >= MAXDEV) return false;
     for (int q = 0; q < 4; ++q)
-        if (((ctx->shareMask >> q) & 1u) && g_quarterUse[ctx->device][q].load() != 1) return false;
-    return devlock_held(ctx->device);
+        if (((ctx->cfg.shareMask >> q) & 1u) && g_quarterUse[ctx->cfg.device][q].load() != 1) return false;
+    return devlock_held(ctx->cfg.device);
 }
+// the problem fits the kernel and the solver instance at hand has its words (a block call's instance may not: blk_enter)
+bool persist_fits(const hmcmt_ctx* ctx) { return ctx->cfg.persistCW > 0 && ctx->inst.d_psync; }
 bool persist_ok(const hmcmt_ctx* ctx) {
-    return ctx->ss.persistOn && ctx->persistCW > 0 && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && persist_alone(ctx);
+    return ctx->ss.persistOn && persist_fits(ctx) && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && persist_alone(ctx);
 }
 // a word of the mapped host block (HostWord)
 volatile int& host_word(const hmcmt_ctx* ctx, HostWord w) { return reinterpret_cast<volatile int*>(ctx->h_stall)[w]; }
 
-// Every instantiation of the persistent solve kernel: persist_setup raises their LDS limit and picks the pair (one / two sweeps)
+// Every instantiation of the persistent solve kernel: persist_config raises their LDS limit and picks the pair (one / two sweeps)
 // of this context (ps_pick), launch_persist launches it.  HMCMT_STAMPS=persist: the phase stamps compiled in, on the 512-thread
 // shapes the phase tables are made on; nyk: width-specialised (PS_WIDTHS: the row width is a compile-time constant).
 template <int CW, int SW, int MW, int CS, int NYK = 0, bool ST = false>
@@ -826,11 +843,11 @@ int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, in
     PsConst c{};
     c.S = k.S; c.nFreq = k.nFreq; c.NYP = k.NYP; c.NZP = k.NZP; c.ny = k.ny; c.nz = k.nz; c.twist = k.twist; c.stallIt = k.stallIt;
     c.vstride = k.vstride;
-    c.G = ctx->persistG; c.GZ = ctx->persistGZ; c.slots = ctx->inst.persistSlots;
-    c.C0 = ctx->persistCS > 1 ? ps_split_col(k.NYP) : k.NYP; c.TW = ps_tile_width(k.NYP, ctx->persistCS); c.PLW = ctx->persistCS > 1 ? ps_plane_width(k.NYP) : k.NYP;
+    c.G = ctx->cfg.persistG; c.GZ = ctx->cfg.persistGZ; c.slots = ctx->inst.persistSlots;
+    c.C0 = ctx->cfg.persistCS > 1 ? ps_split_col(k.NYP) : k.NYP; c.TW = ps_tile_width(k.NYP, ctx->cfg.persistCS); c.PLW = ctx->cfg.persistCS > 1 ? ps_plane_width(k.NYP) : k.NYP;
     c.syncWords = (int)(ctx->inst.psyncBytes / sizeof(unsigned));      // (zero at create; every launch's last workgroup leaves them zero)
-    c.spinLimit = ctx->persistSpin;
-    c.wJ = (float)ctx->jacobiW;
+    c.spinLimit = ctx->cfg.persistSpin;
+    c.wJ = (float)ctx->cfg.jacobiW;
     c.omega = k.omega; c.ofz = k.ofz; c.dM = k.dM; c.cY = k.cY; c.cZ = k.cZ; c.cf32 = k.cf32;
     c.active = k.active; c.iters = k.iters; c.status = k.status; c.nactive = k.nactive; c.nactHost = k.nactHost;
     c.failHost = k.failHost; c.stallHost = k.stallHost; c.progHost = k.progHost; c.errEst = k.errEst; c.ticks = k.ticks;
@@ -866,9 +883,9 @@ int launch_persist(hmcmt_ctx* ctx, int sweeps, int precondOnly, float2* zout, in
     a.placedCnt = precondOnly ? nullptr : ctx->inst.d_psync + 32 * groups + 5; a.nGroups = groups;
     if (start.begin) *(volatile int*)ctx->h_nactive = ctx->ss.nSysOn;      // (mapped: "not all done yet" until the kernel's last converged system says otherwise)
     if (ctx->d_pstamps) HIPCHK(hipMemsetAsync(ctx->d_pstamps, 0, sizeof(long long) * 16 * 256, ctx->stream));
-    const PsKernel& e = *ctx->psKern[sweeps == 2 ? 1 : 0];
+    const PsKernel& e = *ctx->cfg.psKern[sweeps == 2 ? 1 : 0];
     void* args[] = {&a};
-    (void)hipLaunchKernel(e.fn, dim3(groups * ctx->persistG), dim3(e.strips * e.cw), args, ctx->persistLds, ctx->stream);
+    (void)hipLaunchKernel(e.fn, dim3(groups * ctx->cfg.persistG), dim3(e.strips * e.cw), args, ctx->cfg.persistLds, ctx->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -900,8 +917,8 @@ constexpr int SWEEPS_PROBE_EVERY = 40;      // in two-sweep mode: every so many 
 // sweepsDown, and -- since the gain depends on the model, not on the count -- tries one sweep once every
 // SWEEPS_PROBE_EVERY solves and keeps whichever is cheaper (parse_stats).
 int pick_sweeps(const hmcmt_ctx* ctx, int kind) {
-    if (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) return 1;
-    return ctx->sweepsMode == 2 ? 2 : ctx->ss.sweepsKind[kind];
+    if (ctx->cfg.sweepsMode == 1 || !sweeps2_ok(ctx)) return 1;
+    return ctx->cfg.sweepsMode == 2 ? 2 : ctx->ss.sweepsKind[kind];
 }
 
 // Solves A x = r for all systems (x zero on interior on entry; r destroyed).  kind 0 forward, 1 adjoint.
@@ -924,7 +941,7 @@ using SpecFn = std::function<void(const int* gate, int gen)>;
 // was to run in the persistent kernel: a placement fallback, a stagnated system's fp64 restart, a second context on the device).
 void ensure_dinv(hmcmt_ctx* ctx) {
     if (ctx->inst.dinvValid) return;
-    hipLaunchKernelGGL(k_dinv, dim3(ctx->sv.NB, ctx->sv.S), dim3(VBLOCK), 0, ctx->stream, ctx->sv, ctx->jacobiW);
+    hipLaunchKernelGGL(k_dinv, dim3(ctx->sv.NB, ctx->sv.S), dim3(VBLOCK), 0, ctx->stream, ctx->sv, ctx->cfg.jacobiW);
     ctx->inst.dinvValid = true;
 }
 // What the persistent attempt of a solve came to (solve_persist)
@@ -960,7 +977,7 @@ int solve_persist(hmcmt_ctx* ctx, int kind, hmcmt_ctx::PsStart start, const Spec
         }
         launch_adjoint_side(ctx);
     }
-    if (spec && ctx->specOn) (*spec)(ctx->d_gate + kind, ctx->gateGen);
+    if (spec && ctx->cfg.specOn) (*spec)(ctx->d_gate + kind, ctx->gateGen);
     { int prc = spin_until(ctx, [ctx] { return *(volatile int*)ctx->h_prog == PS_DONE; }); if (prc) return prc; }
     if (host_word(ctx, HW_TIMEOUT)) {
         // a wait inside the kernel timed out (a word of its own: a healthy group's system that ends with a status afterwards
@@ -1024,8 +1041,7 @@ int solve_fused(hmcmt_ctx* ctx, int kind, int nextCheck, bool& done, int& it) {
     *(volatile int*)ctx->h_prog = 0;
     bool stalled = false;
     // (HMCMT_SIDE_IT = n > 0: at iteration n; default: half-way through the expected solve, between 2 and 12)
-    static const int sideItEnv = getenv("HMCMT_SIDE_IT") ? atoi(getenv("HMCMT_SIDE_IT")) : 0;
-    const int sideIt = sideItEnv > 0 ? sideItEnv : std::max(2, std::min(12, nextCheck / 2));
+    const int sideIt = ctx->cfg.sideIt > 0 ? ctx->cfg.sideIt : std::max(2, std::min(12, nextCheck / 2));
     while (!done && !stalled && it < ctx->opt.maxit + 1) {
         ++it;
         // decide convergence of the state after iteration it-1, p = z + beta p, q = A p
@@ -1034,7 +1050,7 @@ int solve_fused(hmcmt_ctx* ctx, int kind, int nextCheck, bool& done, int& it) {
             launch_spmv<2>(ctx, (size_t)(k.RTS + 2) * k.NYP * sizeof(cplx) + (size_t)(k.RTS + 4) * k.NYP * sizeof(float2), pb[(it - 1) & 1], pb[it & 1], it);
         } else { ProfScope ps(ctx, 2, true); launch_spmv<1>(ctx, (size_t)(k.RT + 2) * k.NYP * sizeof(cplx), pb[(it - 1) & 1], pb[it & 1], it); }
         if (k.sweeps == 2) { ProfScope ps(ctx, 3, true); launch_update2(ctx, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0); }
-        else { ProfScope ps(ctx, 3, true); if (ctx->upd1Threads == 512) hipLaunchKernelGGL((k_update_fused<1, 512, 6>), tile_grid(k, k.NTR), dim3(512), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0);
+        else { ProfScope ps(ctx, 3, true); if (ctx->cfg.upd1Threads == 512) hipLaunchKernelGGL((k_update_fused<1, 512, 6>), tile_grid(k, k.NTR), dim3(512), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0);
                else hipLaunchKernelGGL((k_update_fused<1, 256, 6>), tile_grid(k, k.NTR), dim3(256), (size_t)(2 * k.RT + 2) * k.NYP * sizeof(cplx), ctx->stream, k, pb[it & 1], rb[rcur], rb[rcur ^ 1], it, 0); }
         rcur ^= 1;
         k.r = rb[rcur];
@@ -1128,12 +1144,12 @@ int solve_epilogue(hmcmt_ctx* ctx, int kind, const cplx* x, bool done, bool defe
         }
         if (guard) {
             ++ctx->guardChecks; ctx->guardLast = ctx->stats.true_res_max; ctx->guardWorst = std::max(ctx->guardWorst, ctx->guardLast);
-            if (!(ctx->guardLast <= ctx->guardLimit)) {
+            if (!(ctx->guardLast <= ctx->cfg.guardLimit)) {
                 // the estimate ||z|| <= tol ||x|| stopped a solve whose residual is not small: say so, and do not warm-start from it
                 ++ctx->guardTrips;
                 ctx->ss.guardDropWarm = true;
                 fprintf(stderr, "hmcmt: stopping-rule guard: evaluation %lld, %s solve: true residual %.3e > %.1e (tol %.1e)\n",
-                        ctx->ss.evalCount, kind == 0 ? "forward" : "adjoint", ctx->guardLast, ctx->guardLimit, ctx->opt.tol);
+                        ctx->ss.evalCount, kind == 0 ? "forward" : "adjoint", ctx->guardLast, ctx->cfg.guardLimit, ctx->opt.tol);
             }
         }
     }
@@ -1196,7 +1212,7 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
     guess = it;        // (launched iterations; collect_stats replaces it with the iterations actually needed)
 
     ctx->ss.solveDone[kind] = done;
-    ctx->specValid = spec && ctx->specOn && outcome == PsOutcome::Done && done;       // (the device decided the same from the same words: k_cocg_persist's exit)
+    ctx->specValid = spec && ctx->cfg.specOn && outcome == PsOutcome::Done && done;       // (the device decided the same from the same words: k_cocg_persist's exit)
     return solve_epilogue(ctx, kind, x, done, deferEnd, guard);
 }
 
@@ -1205,15 +1221,15 @@ int solve(hmcmt_ctx* ctx, cplx* x, int kind, bool deferEnd = false, const SpecFn
 void launch_resid_pre(hmcmt_ctx* ctx, size_t lds, const cplx* x, int zero_r) {
     const Solver& k = ctx->sv;
     const dim3 grid(k.NTR, k.S);
-    if (ctx->residThreads == 1024) hipLaunchKernelGGL(k_resid_pre<1024>, grid, dim3(1024), lds, ctx->stream, k, x, k.r, k.r2, zero_r, ctx->v.sysOn);
-    else if (ctx->residThreads == 512) hipLaunchKernelGGL(k_resid_pre<512>, grid, dim3(512), lds, ctx->stream, k, x, k.r, k.r2, zero_r, ctx->v.sysOn);
+    if (ctx->cfg.residThreads == 1024) hipLaunchKernelGGL(k_resid_pre<1024>, grid, dim3(1024), lds, ctx->stream, k, x, k.r, k.r2, zero_r, ctx->v.sysOn);
+    else if (ctx->cfg.residThreads == 512) hipLaunchKernelGGL(k_resid_pre<512>, grid, dim3(512), lds, ctx->stream, k, x, k.r, k.r2, zero_r, ctx->v.sysOn);
     else hipLaunchKernelGGL(k_resid_pre<256>, grid, dim3(256), lds, ctx->stream, k, x, k.r, k.r2, zero_r, ctx->v.sysOn);
 }
 
 // weights of the initial-guess extrapolation for solve kind kd (side stream): partial sums, weights, history shift
 void launch_extrap_weights(hmcmt_ctx* ctx, const double* d_m, int kd, hipStream_t sp) {
     hipLaunchKernelGGL(k_extrap_prepare, dim3(EXT_NBLK), dim3(256), 0, sp, d_m, ctx->d_mHist[kd], ctx->v.nAC, ctx->d_ext[kd],
-                       ctx->extrapNp, kd == 1 ? 1 : 0, ctx->v.ticks);
+                       ctx->cfg.extrapNp, kd == 1 ? 1 : 0, ctx->v.ticks);
 }
 
 // side stream, beside the forward solve: the adjoint initial guess and the sigma-only sensitivity tables (joined
@@ -1239,8 +1255,8 @@ void launch_adjoint_side(hmcmt_ctx* ctx) {
         // beside a solve there: the adjoint guess in front takes the whole forward solve, ANY kernel behind it starts at the adjoint
         // solve's own start, and the fused one's workgroups (LDS, 256 threads) then sit on CUs that solve's workgroups need (measured:
         // 84.2 against 85.0 steps/s; the tables in front of the guess: 83.5, the guess then delays the adjoint solve).
-        if (ctx->sensFusedLds > 0 && (ctx->sensFusedAlways || !persist_ok(ctx) || ctx->persistFillsShare)) {
-            hipLaunchKernelGGL(k_sens_fused, dim3(3, S), dim3(std::min(256, (v.nz + 1 + 63) / 64 * 64)), ctx->sensFusedLds, ctx->side, v);
+        if (ctx->cfg.sensFusedLds > 0 && (ctx->cfg.sensFusedAlways || !persist_ok(ctx) || ctx->cfg.persistFillsShare)) {
+            hipLaunchKernelGGL(k_sens_fused, dim3(3, S), dim3(std::min(256, (v.nz + 1 + 63) / 64 * 64)), ctx->cfg.sensFusedLds, ctx->side, v);
         } else {
             hipLaunchKernelGGL(k_sens_layers, dim3((v.nz + 1 + 63) / 64, 3, S), dim3(64), 0, ctx->side, v);
             hipLaunchKernelGGL(k_sens_profile, dim3((3 * S + 63) / 64), dim3(64), 0, ctx->side, v);
@@ -1305,18 +1321,18 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
     // start of a solve on the default path: residual and first pre-smoothing pass in one launch (k_resid_pre)
     const size_t startLds = (size_t)(2 * ctx->sv.RT + 6) * v.NYP * sizeof(cplx);
     const bool fusedStartOk = ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && !ctx->opt.verify &&
-                              startLds <= (size_t)150 * 1024 && !ctx->noFusedStart;
+                              startLds <= (size_t)150 * 1024 && !ctx->cfg.noFusedStart;
     const int sweepsF = pick_sweeps(ctx, 0), sweepsA = pick_sweeps(ctx, 1);
     bool fusedStart = fusedStartOk && sweepsF == 1;      // (k_resid_pre does ONE pre-sweep; two go through k_resid0 + the solve's own start)
     // the solves' start -- initial residual, bookkeeping -- inside the persistent kernel (kernels_persist.h, PsLaunch::resid / begin)
-    const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && !ctx->opt.verify && persist_ok(ctx);
+    const bool inKernelStart = ctx->cfg.psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 && !ctx->opt.verify && persist_ok(ctx);
     ctx->sv.sweeps = sweepsF;
     ctx->stats.smoother_sweeps = 10 * sweepsF + (wantGrad ? sweepsA : 0);
     ctx->ss.sweepsUsed[0] = sweepsF; if (wantGrad) ctx->ss.sweepsUsed[1] = sweepsA;
     {
         ProfScope ps(ctx, 4);
         // conductivities and their lateral means, one wave per cell row (meshes of whole rows: always; k_sigma + k_rowmean otherwise)
-        const bool rows = v.nCell == v.ny * v.nz && !ctx->noSigmaRows;
+        const bool rows = v.nCell == v.ny * v.nz && !ctx->cfg.noSigmaRows;
         const auto hostT0 = std::chrono::steady_clock::now();
         if (v.ticks) {                                   // HMCMT_TICKS: earliest starts <- max, latest ends <- 0
             HIPCHK(hipMemsetAsync(v.ticks, 0xff, 32 * sizeof(long long), st));
@@ -1355,10 +1371,10 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
         // queue reaches them, not by the kernels: the order of the calls is the schedule, and every call
         // that could be dropped or moved to where the host runs ahead of the device has been.
         if (!freezeBC) {
-            if (ctx->bcCW > 0) {
-                hipLaunchKernelGGL(k_bc_fused, dim3((v.ny + ctx->bcCW) / ctx->bcCW, v.nFreq), dim3(256), ctx->bcLds, st, v, ctx->bcCW, ctx->bcSlots);
-            } else if (ctx->bcbCW > 0) {
-                hipLaunchKernelGGL(k_bc_blocked, dim3((v.ny + ctx->bcbCW) / ctx->bcbCW, v.nFreq), dim3(ctx->bcbNT), ctx->bcbLds, st, v, ctx->bcbCW, ctx->bcbSlots, ctx->bcbLBu, ctx->bcbLBd);
+            if (ctx->cfg.bcCW > 0) {
+                hipLaunchKernelGGL(k_bc_fused, dim3((v.ny + ctx->cfg.bcCW) / ctx->cfg.bcCW, v.nFreq), dim3(256), ctx->cfg.bcLds, st, v, ctx->cfg.bcCW, ctx->cfg.bcSlots);
+            } else if (ctx->cfg.bcbCW > 0) {
+                hipLaunchKernelGGL(k_bc_blocked, dim3((v.ny + ctx->cfg.bcbCW) / ctx->cfg.bcbCW, v.nFreq), dim3(ctx->cfg.bcbNT), ctx->cfg.bcbLds, st, v, ctx->cfg.bcbCW, ctx->cfg.bcbSlots, ctx->cfg.bcbLBu, ctx->cfg.bcbLBd);
             } else {
                 hipLaunchKernelGGL(k_bc_layers, dim3((v.ny + 1 + 63) / 64, v.nz, v.nFreq), dim3(64), 0, st, v);
                 hipLaunchKernelGGL(k_bc_forward, dim3((v.ny + 1 + 63) / 64, v.nFreq), dim3(64), 4 * (size_t)v.nz * sizeof(cplx), st, v);
@@ -1385,16 +1401,16 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             HIPCHK(hipEventRecord(ctx->evExtF, sA));
         }
         HIPCHK(issue_pivot(sA));
-        if (ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && !ctx->noCoefAll) {
+        if (ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && !ctx->cfg.noCoefAll) {
             // (the per-system Jacobi diagonals only where something will read them: not the persistent kernel -- ensure_dinv)
-            const bool lazy = ctx->lazyDinv && inKernelStart;
-            hipLaunchKernelGGL(k_coef_all, dim3(lazy ? std::max(ctx->sv.NB, (int)std::min<long>(512, (v.vstride + VBLOCK - 1) / VBLOCK)) : ctx->sv.NB, lazy ? 2 : S), dim3(VBLOCK), 0, sB, v, ctx->sv, ctx->jacobiW, const_cast<float4*>(ctx->sv.cf32),
+            const bool lazy = ctx->cfg.lazyDinv && inKernelStart;
+            hipLaunchKernelGGL(k_coef_all, dim3(lazy ? std::max(ctx->sv.NB, (int)std::min<long>(512, (v.vstride + VBLOCK - 1) / VBLOCK)) : ctx->sv.NB, lazy ? 2 : S), dim3(VBLOCK), 0, sB, v, ctx->sv, ctx->cfg.jacobiW, const_cast<float4*>(ctx->sv.cf32),
                                lazy ? v.nFreq : 1);
             ctx->inst.dinvValid = !lazy;
         } else {
             hipLaunchKernelGGL(k_coef, grid1(nodes, 256), dim3(256), 0, sB, v, 0, 1, 1, 0);
             if (ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI) {
-                hipLaunchKernelGGL(k_dinv, dim3(ctx->sv.NB, S), dim3(VBLOCK), 0, sB, ctx->sv, ctx->jacobiW);
+                hipLaunchKernelGGL(k_dinv, dim3(ctx->sv.NB, S), dim3(VBLOCK), 0, sB, ctx->sv, ctx->cfg.jacobiW);
                 hipLaunchKernelGGL(k_coef32, dim3(ctx->sv.NB, 2), dim3(VBLOCK), 0, sB, ctx->sv, const_cast<float4*>(ctx->sv.cf32));
             }
         }
@@ -1414,7 +1430,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             hipLaunchKernelGGL(k_resid0, dim3(ctx->sv.NB, S), dim3(VBLOCK), 0, st, ctx->sv, v.X, 1, ctx->opt.verify ? nullptr : ctx->v.sysOn, 0);
             ctx->solveBegun = !ctx->opt.verify;
         }
-        if (ctx->wantTicks) { ctx->hostUs[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT0).count(); ++ctx->hostN; }
+        if (ctx->cfg.wantTicks) { ctx->hostUs[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT0).count(); ++ctx->hostN; }
         HIPCHK(hipStreamWaitEvent(st, ctx->evPiv, 0));
         // (the adjoint half's side-stream work -- its initial guess, the sigma-only sensitivity tables -- is launched
         // from inside the forward solve, once the main queue holds two iterations: launch_adjoint_side)
@@ -1497,7 +1513,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             }
         }
         ctx->sensWaitPending = true;     // (the wait for the side stream's sensitivity tables is issued from inside the adjoint solve)
-        if (ctx->wantTicks) ctx->hostUs[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT1).count();
+        if (ctx->cfg.wantTicks) ctx->hostUs[1] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT1).count();
         const SpecFn specA = [&](const int* gate, int gen) {
             View vg = v; vg.gate = gate; vg.gateGen = gen;
             if (ctx->sensWaitPending) { ctx->sensWaitPending = false; hipStreamWaitEvent(st, ctx->evSens, 0); }
@@ -1529,7 +1545,7 @@ int evaluate_once(hmcmt_ctx* ctx, const double* d_m, bool wantGrad, double* d_pr
             hipLaunchKernelGGL(k_bcsens_contract, dim3((BCC_L * v.nz + 127) / 128, 2, S), dim3(128), 0, st, v, ctx->ss.lfMom.on ? ctx->ss.lfMom.L.part : (double*)nullptr);
             hipLaunchKernelGGL(k_gradfinal, grid1(GF_L * v.nAC, 128), dim3(128), 0, st, v, ctx->ss.lfMom);
         }
-        if (ctx->wantTicks) ctx->hostUs[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT2).count();
+        if (ctx->cfg.wantTicks) ctx->hostUs[2] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT2).count();
     }
     HIPCHK(hipGetLastError());
     ctx->ss.haveModel = true;
@@ -1567,13 +1583,13 @@ static void pack_queues(const float* cost, int S, int NQ, int* tab) {
 }
 void persist_balance(hmcmt_ctx* ctx, int kind) {
     const int S = ctx->sv.S, NQ = 8 * ctx->inst.persistSlots;
-    if (!ctx->psBalance || !ctx->d_psOrder || NQ <= 0 || S <= NQ) return;
+    if (!ctx->cfg.psBalance || !ctx->d_psOrder || NQ <= 0 || S <= NQ) return;
     // (costs: the mean of the last solve's counts and the costs before it -- the counts of one system wander by one or two from
     //  step to step, and a table made from one solve's noise is a worse guess for the next than one made from several)
     std::vector<float>& cost = ctx->ss.psCost[kind];
     const int* last = ctx->ss.itersLast.data() + (size_t)kind * S;
     if (cost.empty()) cost.assign(last, last + S);
-    else for (int i = 0; i < S; ++i) cost[i] = ctx->psSmooth * cost[i] + (1.f - ctx->psSmooth) * (float)last[i];
+    else for (int i = 0; i < S; ++i) cost[i] = ctx->cfg.psSmooth * cost[i] + (1.f - ctx->cfg.psSmooth) * (float)last[i];
     std::vector<int> tab(S);
     pack_queues(cost.data(), S, NQ, tab.data());
     std::vector<int>& cur = ctx->ss.psOrder[kind];
@@ -1610,20 +1626,20 @@ void parse_stats(hmcmt_ctx* ctx, bool withAdjoint) {
         // first convergence poll of the next evaluation: where this one actually finished (the loop itself only
         // knows how many iterations it launched, which includes the empty ones behind the last poll)
         if (ctx->ss.solveDone[kind] && mx > 0) (kind == 0 ? ctx->ss.lastItFwd : ctx->ss.lastItAdj) = mx;
-        if (ctx->ss.solveDone[kind] && mx > 0 && ctx->stats.status == 0 && ctx->persistCW && ctx->ss.persistOn) persist_balance(ctx, kind);
+        if (ctx->ss.solveDone[kind] && mx > 0 && ctx->stats.status == 0 && persist_fits(ctx) && ctx->ss.persistOn) persist_balance(ctx, kind);
         // ... and the smoother of the next solve of this kind (pick_sweeps): two sweeps per side when this one was long
-        if (ctx->sweepsMode == 0 && ctx->ss.solveDone[kind] && mx > 0) {
+        if (ctx->cfg.sweepsMode == 0 && ctx->ss.solveDone[kind] && mx > 0) {
             int& next = ctx->ss.sweepsKind[kind];
             if (ctx->ss.sweepsUsed[kind] == 1) {
                 if (ctx->ss.sweepsProbe[kind]) {                 // a probe with one sweep: keep it if it is the cheaper one
                     ctx->ss.sweepsProbe[kind] = false;
-                    const double cost2 = (ctx->persistCW && ctx->ss.persistOn) ? (ctx->persistCS > 1 ? SWEEPS2_COST_PERSIST_CS2 : SWEEPS2_COST_PERSIST) : SWEEPS2_COST;
+                    const double cost2 = (persist_fits(ctx) && ctx->ss.persistOn) ? (ctx->cfg.persistCS > 1 ? SWEEPS2_COST_PERSIST_CS2 : SWEEPS2_COST_PERSIST) : SWEEPS2_COST;
                     next = (double)mx <= cost2 * ctx->ss.sweepsCount2[kind] ? 1 : 2;
-                } else if (mx > ctx->sweepsUp) next = 2;
+                } else if (mx > ctx->cfg.sweepsUp) next = 2;
             } else {
                 ctx->ss.sweepsCount2[kind] = mx;
-                if (mx < ctx->sweepsDown) next = 1;
-                else if (++ctx->ss.sweepsSince[kind] >= SWEEPS_PROBE_EVERY && mx < ctx->sweepsUp) {
+                if (mx < ctx->cfg.sweepsDown) next = 1;
+                else if (++ctx->ss.sweepsSince[kind] >= SWEEPS_PROBE_EVERY && mx < ctx->cfg.sweepsUp) {
                     ctx->ss.sweepsSince[kind] = 0; ctx->ss.sweepsProbe[kind] = true; next = 1;
                 }
             }
@@ -1656,7 +1672,7 @@ int collect_pending(hmcmt_ctx* ctx) {
     if (!ctx->statsPending) return 0;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipEventSynchronize(ctx->evRec));
-    if (ctx->wantTicks) ctx->hostUs[3] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    if (ctx->cfg.wantTicks) ctx->hostUs[3] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     parse_stats(ctx, ctx->pendingAdj);
     ctx->statsPending = false;
     return finish_status(ctx);
@@ -1703,12 +1719,12 @@ const char* hmcmt_last_error(const hmcmt_ctx* ctx) { return ctx ? ctx->err.c_str
 int hmcmt_destroy(hmcmt_ctx* ctx) {
     if (!ctx) return HMCMT_EINVAL;
     if (ctx->counted) {
-        if (ctx->device >= 0 && ctx->device < MAXDEV) {
-            for (int q = 0; q < 4; ++q) if ((ctx->shareMask >> q) & 1u) g_quarterUse[ctx->device][q].fetch_sub(1);
+        if (ctx->cfg.device >= 0 && ctx->cfg.device < MAXDEV) {
+            for (int q = 0; q < 4; ++q) if ((ctx->cfg.shareMask >> q) & 1u) g_quarterUse[ctx->cfg.device][q].fetch_sub(1);
         }
-        devlock_unref(ctx->device); ctx->counted = false;
+        devlock_unref(ctx->cfg.device); ctx->counted = false;
     }
-    hipSetDevice(ctx->device);
+    hipSetDevice(ctx->cfg.device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
     if (ctx->side) hipStreamSynchronize(ctx->side);      // (side-stream work of an evaluation nobody waited for)
     if (ctx->v.ticks) {
@@ -1719,7 +1735,7 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
         std::vector<long long> traw(32 + 64 * TK_N);
         long long t[64] = {0};
         int rate = 100000;                                // kHz
-        hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, ctx->device);
+        hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, ctx->cfg.device);
         if (hipMemcpy(traw.data(), ctx->v.ticks, traw.size() * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess) {
             for (int i = 0; i < TK_N; ++i) {
                 t[i] = traw[i];
@@ -1762,7 +1778,7 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
 #endif
         if (n) {
             int rate = 100000;                                // kHz
-            hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, ctx->device);
+            hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, ctx->cfg.device);
             const double us = 1e3 / rate / n;
             double tot = 0; for (int i = 1; i < 12; ++i) tot += acc[i];
             fprintf(stderr, "HMCMT_STAMPS persist: %ld workgroups, third iteration of the last solve, mean us: pre-smooth %.2f fwd-transform %.2f wait-T1 %.2f slabs %.2f wait-T2 %.2f back-transform %.2f "
@@ -1821,10 +1837,6 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
 // CS = 1 where the whole row fits one tile (its LDS); CS = 2 (two column parts per row block) on wider meshes -- the stress size.
 // does the mesh fit the kernel (its LDS, a system's workgroups on one XCD)?  twist: the factorisation the solves will use
 struct ShapeDims { int NYP, NZP, nz; };
-static bool persist_shape_dims(const ShapeDims& k, int twist, int cs, int cuPerXcd, int& G, int& cw, int& mw, size_t& lds);
-static bool persist_shape_cs(const hmcmt_ctx* ctx, int twist, int cs, int cuPerXcd, int& G, int& cw, int& mw, size_t& lds) {
-    return persist_shape_dims(ShapeDims{ctx->sv.NYP, ctx->sv.NZP, ctx->sv.nz}, twist, cs, cuPerXcd, G, cw, mw, lds);
-}
 // (pure arithmetic on the mesh sizes: also behind hmcmt_persist_envelope, which needs no device)
 static bool persist_shape_dims(const ShapeDims& k, int twist, int cs, int cuPerXcd, int& G, int& cw, int& mw, size_t& lds) {
     const int GZ = (k.nz - 1 + PS_OWN - 1) / PS_OWN;
@@ -1850,130 +1862,210 @@ static bool persist_shape_dims(const ShapeDims& k, int twist, int cs, int cuPerX
     }
     return false;
 }
-static bool persist_shape(const hmcmt_ctx* ctx, int twist, int& cuPerXcd, int& G, int& cw, int& mw, size_t& lds, int* csOut = nullptr) {
+static bool persist_shape(const Config& c, const ShapeDims& dims, int twist, int& cuPerXcd, int& G, int& cw, int& mw, size_t& lds, int* csOut = nullptr) {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) { (void)hipGetLastError(); return false; }
-    cuPerXcd = prop.multiProcessorCount / 8 / std::max(ctx->shareCnt, 1);        // (this context's share of an XCD's CUs)
-    if (cuPerXcd < 1 || !ctx->d_Vb || !ctx->d_Vtb) return false;
+    if (hipGetDeviceProperties(&prop, c.device) != hipSuccess) { (void)hipGetLastError(); return false; }
+    cuPerXcd = prop.multiProcessorCount / 8 / std::max(c.shareCnt, 1);        // (this context's share of an XCD's CUs)
+    if (cuPerXcd < 1) return false;
     // HMCMT_PERSIST_CS = 1 | 2 forces the column parts (tests: the two-part kernel on meshes one tile would hold)
-    const char* e = getenv("HMCMT_PERSIST_CS");
-    const int force = e ? atoi(e) : 0;
     for (int cs = 1; cs <= 2; ++cs) {
-        if (force && cs != force) continue;
-        if (persist_shape_cs(ctx, twist, cs, cuPerXcd, G, cw, mw, lds)) { if (csOut) *csOut = cs; return true; }
+        if (c.persistCsForce && cs != c.persistCsForce) continue;
+        if (persist_shape_dims(dims, twist, cs, cuPerXcd, G, cw, mw, lds)) { if (csOut) *csOut = cs; return true; }
     }
     return false;
 }
-static int persist_setup(hmcmt_ctx* ctx) {
-    const Solver& k = ctx->sv;
-    if (const char* e = getenv("HMCMT_PERSIST")) ctx->ss.persistOn = e[0] != '0';
-    if (const char* e = getenv("HMCMT_PS_START")) ctx->psInKernelStart = e[0] != '0';
-    if (const char* e = getenv("HMCMT_PS_SPIN")) ctx->persistSpin = (unsigned)std::max(1024l, atol(e));
-    ctx->persistCW = 0;
+// the persistent kernel's part of make_config: does it apply to this problem, and in which shape (persistCW = 0: it does not)
+static int persist_config(const HostProblem& h, Config& c, std::string& err) {
     int cuPerXcd = 0, G = 0, cw = 0, mw = 32, cs = 1;
     size_t lds = 0;
-    if (!persist_shape(ctx, k.twist, cuPerXcd, G, cw, mw, lds, &cs)) return 0;
-    if ((size_t)k.S * (size_t)k.vstride >= ((size_t)1 << 27)) return 0;      // (the kernel's 32-bit lane offsets carry the system's element offset: kernels_persist.h, so32)
-    ctx->persistMW = mw;
+    if (!persist_shape(c, ShapeDims{h.NYP, h.NZP, h.nz}, c.twist, cuPerXcd, G, cw, mw, lds, &cs)) return 0;
+    if ((size_t)h.S * (size_t)h.NZP * (size_t)h.NYP >= ((size_t)1 << 27)) return 0;      // (the kernel's 32-bit lane offsets carry the system's element offset: kernels_persist.h, so32)
     for (const PsKernel& e : g_psKernels)
         if (e.strips == 2 && hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); return 0; }
-
-    ctx->persistG = G;
-    ctx->persistCS = cs;
-    ctx->persistGZ = G / cs;
+    c.persistMW = mw;
+    c.persistG = G;
+    c.persistCS = cs;
+    c.persistGZ = G / cs;
     // the width-specialised instantiations where the table has one for the mesh's padded row width (ps_pick); HMCMT_PERSIST_WIDTHK=0
     // keeps the generic kernels (A/B runs, tests)
-    int wk = k.NYP;
-    if (const char* e = getenv("HMCMT_PERSIST_WIDTHK")) if (e[0] == '0') wk = 0;
-    ctx->inst.persistSlots = std::max(1, std::min((k.S + 7) / 8, cuPerXcd / G));
-    ctx->persistFillsShare = ctx->inst.persistSlots * G >= cuPerXcd;       // (no CU of this context's share left over beside a solve: launch_adjoint_side)
-    ctx->persistLds = lds;
-    ctx->inst.psyncBytes = ((size_t)(32 * 8 * ctx->inst.persistSlots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, ctx->inst.psyncBytes));
-    HIPCHK(hipMemset(q, 0, ctx->inst.psyncBytes));
-    {
-        void* gq = nullptr;
-        HIPCHK(hipMalloc(&gq, 2 * sizeof(int)));
-        HIPCHK(hipMemset(gq, 0, 2 * sizeof(int)));
-        ctx->allocs.push_back(gq);
-        ctx->d_gate = reinterpret_cast<int*>(gq);
-    }
-    ctx->allocs.push_back(q);
-    ctx->inst.d_psync = reinterpret_cast<unsigned*>(q);
-    {
-        const size_t recBytes = (size_t)k.S * MAXNB * 2 * 8 * 16;
-        void* r = nullptr;
-        HIPCHK(hipMalloc(&r, recBytes));
-        HIPCHK(hipMemset(r, 0, recBytes));
-        ctx->allocs.push_back(r);
-        ctx->inst.d_prec = reinterpret_cast<u4v*>(r);
-    }
-    {
-        void* pc = nullptr;
-        HIPCHK(hipMalloc(&pc, sizeof(PsConst)));
-        ctx->allocs.push_back(pc);
-        ctx->inst.d_psConst = reinterpret_cast<PsConst*>(pc);
-        ctx->inst.psConstValid = false;
-    }
-    if (k.S > 8 * ctx->inst.persistSlots) {          // (more than one round of systems: persist_balance)
-        void* po = nullptr;
-        HIPCHK(hipMalloc(&po, 2 * sizeof(int) * (size_t)k.S));
-        ctx->allocs.push_back(po);
-        ctx->d_psOrder = reinterpret_cast<int*>(po);
-        HIPCHK(hipHostMalloc((void**)&ctx->h_psOrder, 2 * sizeof(int) * (size_t)k.S, hipHostMallocDefault));
-        if (const char* e = getenv("HMCMT_PERSIST_BALANCE")) ctx->psBalance = e[0] != '0';
-        if (const char* e = getenv("HMCMT_PERSIST_BALANCE_SMOOTH")) ctx->psSmooth = (float)std::min(0.95, std::max(0.0, atof(e)));
-    }
-    if (cs > 1) {
-        void* y2 = nullptr;
-        const size_t nb = (size_t)k.S * k.vstride * sizeof(float2);
-        HIPCHK(hipMalloc(&y2, nb));
-        HIPCHK(hipMemset(y2, 0, nb));
-        ctx->allocs.push_back(y2);
-        ctx->inst.d_yhat2 = reinterpret_cast<float2*>(y2);
-    }
+    const int wk = c.persistWidthK ? h.NYP : 0;
+    c.persistSlots = std::max(1, std::min((h.S + 7) / 8, cuPerXcd / G));
+    c.persistFillsShare = c.persistSlots * G >= cuPerXcd;       // (no CU of this context's share left over beside a solve: launch_adjoint_side)
+    c.persistLds = lds;
     // the four-strip kernel where it applies: one column part, 32-mode slabs, a column tile of the transforms per wave, the slab
     // sweeps' chunks of four rows covering half the rows; HMCMT_PERSIST_STRIPS=2 keeps the two-half kernel (A/B)
+    // (round 6: the four-strip kernel is opt-in -- it measured 530 against 600 steps/s at the headline size)
     int strips = 2;
-    {
-        const char* e = getenv("HMCMT_PERSIST_STRIPS");
-        const int want = e ? atoi(e) : 2;      // (round 6: the four-strip kernel is opt-in -- it measured 530 against 600 steps/s at the headline size)
-        const size_t lds4 = ps4_lds_bytes(k.NYP, k.NZP, k.nz, 32, 4 * cw);
-        if (want == 4 && cs == 1 && mw == 32 && 4 * cw <= 1024 && k.NYP / 16 <= 4 * cw / 64 && ps4_slab_rc(k.nz, 32, 4 * cw) == 4 && lds4 <= (size_t)160 * 1024) {
-            bool ok4 = true;
-            for (const PsKernel& e4 : g_psKernels)
-                if (e4.strips == 4 && hipFuncSetAttribute(e4.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); ok4 = false; }
-            if (ok4) { strips = 4; ctx->persistLds = lds4; }
-        }
-    }
-    if (const char* es = getenv("HMCMT_STAMPS")) if (!strcmp(es, "persist")) {
-        HIPCHK(hipMalloc((void**)&ctx->d_pstamps, sizeof(long long) * 16 * 256));
-        HIPCHK(hipMemset(ctx->d_pstamps, 0, sizeof(long long) * 16 * 256));
-        ctx->allocs.push_back(ctx->d_pstamps);
+    const size_t lds4 = ps4_lds_bytes(h.NYP, h.NZP, h.nz, 32, 4 * cw);
+    if (c.persistStrips == 4 && cs == 1 && mw == 32 && 4 * cw <= 1024 && h.NYP / 16 <= 4 * cw / 64 && ps4_slab_rc(h.nz, 32, 4 * cw) == 4 && lds4 <= (size_t)160 * 1024) {
+        bool ok4 = true;
+        for (const PsKernel& e4 : g_psKernels)
+            if (e4.strips == 4 && hipFuncSetAttribute(e4.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); ok4 = false; }
+        if (ok4) { strips = 4; c.persistLds = lds4; }
     }
     for (int sw = 1; sw <= 2; ++sw)
-        if (!(ctx->psKern[sw - 1] = ps_pick(strips, cw, mw, cs, wk, ctx->d_pstamps != nullptr, sw))) {
-            ctx->err = "no instantiation of the persistent solve kernel for this shape (g_psKernels)"; return HMCMT_EINVAL;
+        if (!(c.psKern[sw - 1] = ps_pick(strips, cw, mw, cs, wk, c.stamps == STAMPS_PERSIST, sw))) {
+            err = "no instantiation of the persistent solve kernel for this shape (g_psKernels)"; return HMCMT_EINVAL;
         }
-    ctx->persistCW = cw;
+    c.persistCW = cw;
+    return 0;
+}
+// the persistent kernel's words, records and tables (Config::persistCW > 0)
+static int persist_alloc(hmcmt_ctx* ctx) {
+    const Solver& k = ctx->sv;
+    const Config& c = ctx->cfg;
+    if (!c.persistCW) return 0;
+    int rc = 0;
+    ctx->inst.persistSlots = c.persistSlots;
+    ctx->inst.psyncBytes = ((size_t)(32 * 8 * c.persistSlots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
+    if ((rc = dalloc(ctx, &ctx->inst.d_psync, ctx->inst.psyncBytes / sizeof(unsigned)))) return rc;
+    if ((rc = dalloc(ctx, &ctx->d_gate, 2))) return rc;
+    static_assert(sizeof(u4v) == 16, "a record of the kernel's reductions");
+    if ((rc = dalloc(ctx, &ctx->inst.d_prec, (size_t)k.S * MAXNB * 2 * 8))) return rc;
+    if ((rc = dalloc(ctx, &ctx->inst.d_psConst, 1, false))) return rc;      // (never cleared: launch_persist writes it whole)
+    ctx->inst.psConstValid = false;
+    if (k.S > 8 * c.persistSlots) {          // (more than one round of systems: persist_balance)
+        if ((rc = dalloc(ctx, &ctx->d_psOrder, 2 * (size_t)k.S, false))) return rc;
+        HIPCHK(hipHostMalloc((void**)&ctx->h_psOrder, 2 * sizeof(int) * (size_t)k.S, hipHostMallocDefault));
+    }
+    if (c.persistCS > 1 && (rc = dalloc(ctx, &ctx->inst.d_yhat2, (size_t)k.S * k.vstride))) return rc;
+    if (c.stamps == STAMPS_PERSIST && (rc = dalloc(ctx, &ctx->d_pstamps, 16 * 256))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
-static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
+// What creation decides: the knobs resolved against the mesh and the device.  The device is checked and made current here (the
+// kernels' LDS limits are raised on it); the context and its buffers come afterwards (create_impl, persist_alloc).
+static int make_config(const HostProblem& h, const hmcmt_options& opt, const Knobs& kn, int32_t device_id, int shareIdx, int shareCnt, Config& c, std::string& err) {
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ctx->err = "no HIP device available (this library has no host compute path)"; return HMCMT_ENODEV; }
-    if (device_id < 0 || device_id >= ndev) { ctx->err = "device_id out of range"; return HMCMT_ENODEV; }
-    ctx->device = device_id;
-    if (ctx->hp.NZP > MAXNZP) { ctx->err = "nz too large for the tridiagonal kernel (nz+1 > 1024)"; return HMCMT_EINVAL; }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { err = "no HIP device available (this library has no host compute path)"; return HMCMT_ENODEV; }
+    if (device_id < 0 || device_id >= ndev) { err = "device_id out of range"; return HMCMT_ENODEV; }
+    if (h.NZP > MAXNZP) { err = "nz too large for the tridiagonal kernel (nz+1 > 1024)"; return HMCMT_EINVAL; }
     // the fp64 eigen-transform kernel (fdm_precision = 1, and the restart of a stagnating mixed-precision solve) holds at most
     // 28 column tiles of 16 nodes.  A wider mesh runs the default mixed-precision path (the reference takes any mesh,
     // readEMModel2D.jl:11-154); it is refused here only where fp64 is ASKED for, and a restart that needs the kernel fails that
     // evaluation with HMCMT_ENOCONV (solve()) -- the safety net is what such a mesh goes without, not the solver.
-    if (ctx->hp.NYP / 16 > 28 && ctx->opt.fdm_precision == 1) { ctx->err = "fdm_precision = 1 on a mesh wider than 447 cells: the fp64 eigen-transform holds ny + 1 <= 448 nodes (include/hmcmt.h, hmcmt_create)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(device_id));
-    ctx->shareMask = quarter_mask(ctx->shareIdx, ctx->shareCnt);      // (hmcmt_next_cu_share, taken over by hmcmt_create)
-    if (ctx->shareCnt > 1) {
+    if (h.NYP / 16 > 28 && opt.fdm_precision == 1) { err = "fdm_precision = 1 on a mesh wider than 447 cells: the fp64 eigen-transform holds ny + 1 <= 448 nodes (include/hmcmt.h, hmcmt_create)"; return HMCMT_EINVAL; }
+    if (const hipError_t e = hipSetDevice(device_id)) { err = std::string("hipSetDevice(device_id): ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? HMCMT_ENOMEM : HMCMT_EHIP; }
+    static_cast<Knobs&>(c) = kn;
+    c.device = device_id;
+    c.shareIdx = shareIdx; c.shareCnt = shareCnt;
+    c.shareMask = quarter_mask(shareIdx, shareCnt);      // (hmcmt_next_cu_share, taken over by hmcmt_create)
+    auto raise_lds = [](const void* f, int bytes) { if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) return true; (void)hipGetLastError(); return false; };
+#define KFN(...) reinterpret_cast<const void*>(__VA_ARGS__)
+    // (this kernel also has a few hundred bytes of static LDS: ask for less than the full 160 KB)
+    if (raise_lds(KFN(k_back_post<1, 1>), 152 * 1024)) c.maxLdsBack = 152 * 1024;
+    {
+        // boundary columns per workgroup of k_bc_fused: all workgroups resident at once (two per CU: registers), else the
+        // two-kernel form (HMCMT_BC_FUSED = 0: never, n: n columns per workgroup)
+        const int cols = h.ny + 1, nz = h.nz;
+        const int cw = kn.bcFusedGiven ? kn.bcFused : std::max(1, (cols * h.nFreq + 511) / 512);
+        const int slots = cols <= cw ? 2 : 1;
+        const size_t lds = ((size_t)5 * nz * cw + (size_t)slots * 2 * nz) * sizeof(cplx);
+        if (cw > 0 && cw <= 256 && lds <= (size_t)80 * 1024 && raise_lds(KFN(k_bc_fused), 80 * 1024)) {
+            c.bcCW = cw; c.bcSlots = slots; c.bcLds = lds;
+        }
+        // otherwise the layer-blocked form (HMCMT_BC_BLOCKED = 0: the two-kernel form; "columns[,threads[,up layers[,down layers]]]"
+        // per workgroup and block)
+        // default: 1 024 threads (15 producer waves beside the chain wave: the transcendental work needs the occupancy), columns
+        // such that the workgroups of a frequency divide its columns evenly and fill the chip at the stress size (401 columns, 32
+        // frequencies: 8 x 51 -> 256 workgroups, one per CU), as many layers per bottom -> top block as the producers have threads
+        int nt = 1024, cb = 64, lbu = 0, lbd = 8;
+        { const int g = (cols + 63) / 64; int per = 256 / std::max(1, h.nFreq); per = std::max(g, std::min(per, (cols + 15) / 16)); cb = (cols + per - 1) / per; }
+        int* const field[4] = {&cb, &nt, &lbu, &lbd};
+        for (int i = 0; i < kn.bcBlockedN; ++i) *field[i] = kn.bcBlocked[i];
+        const bool blockedOff = cb <= 0;
+        cb = std::max(1, std::min(cb, 64)); nt = std::max(128, std::min(1024, nt / 64 * 64));
+        if (lbu <= 0) lbu = (nt - 64) / cb;
+        lbu = std::max(1, std::min(std::min(lbu, nz), (nt - 64) / cb));
+        lbd = std::max(1, std::min(std::min(lbd, nz), (nt - 64) / cb));
+        const int bslots = cols <= cb ? 2 : 1;
+        const size_t blds = ((size_t)2 * std::max(3 * lbu, 5 * lbd) * cb + (size_t)bslots * 2 * nz) * sizeof(cplx);
+        if (c.bcCW == 0 && !blockedOff && blds <= (size_t)150 * 1024 && raise_lds(KFN(k_bc_blocked), 150 * 1024)) {
+            c.bcbCW = cb; c.bcbSlots = bslots; c.bcbLds = blds; c.bcbNT = nt; c.bcbLBu = lbu; c.bcbLBd = lbd;
+        }
+    }
+    {
+        const size_t sl = (size_t)12 * (h.nz + 1) * sizeof(cplx) + (size_t)h.nz * sizeof(double);
+        c.sensFusedAlways = kn.sensFusedMode == 1;
+        if (kn.sensFusedMode != 0 && sl <= (size_t)150 * 1024 && raise_lds(KFN(k_sens_fused), 150 * 1024)) c.sensFusedLds = sl;
+    }
+    if (raise_lds(KFN(k_fdm_fwd<FW_NTW>), 160 * 1024) && raise_lds(KFN(k_fdm_fwd<1>), 160 * 1024)) c.maxLds = 160 * 1024;
+    // (the separate transform kernel stages LP_NRG row groups: beyond 64 KB on wide meshes with LP_NRG > 2); the stencil kernels'
+    // tiles can pass 64 KB on wide meshes
+    for (const void* f : {KFN(k_transform_lp<0, 0>), KFN(k_transform_lp<0, 1>), KFN(k_transform_lp<1, 0>), KFN(k_transform_lp<1, 1>),
+                          KFN(k_transform_lp<2, 0>), KFN(k_transform_lp<2, 1>),
+                          KFN(k_update_fused<1, 256, 6>), KFN(k_update_fused<1, 512, 6>), KFN(k_update_fused<2, 256, 6>), KFN(k_update_fused<2, 512, 4>),
+                          KFN(k_update_fused<2, 512, 6>), KFN(k_update_fused<2, 512, 8>), KFN(k_update_fused<2, 1024, 4>),
+                          KFN(k_post2), KFN(k_back_post<1, 2>),
+                          KFN(k_spmv_fused<1, 256>), KFN(k_spmv_fused<1, 512>), KFN(k_spmv_fused<1, 1024>),
+                          KFN(k_spmv_fused<2, 256>), KFN(k_spmv_fused<2, 512>), KFN(k_spmv_fused<2, 1024>),
+                          KFN(k_resid_pre<256>), KFN(k_resid_pre<512>), KFN(k_resid_pre<1024>)})
+        raise_lds(f, 152 * 1024);
+#undef KFN
+    // rows per tile of the stencil kernels: about 512 workgroups per launch, at most 8 rows (measured at cfg3:
+    // 4 rows 484, 6 rows 489, 8 rows 492, 12 rows 456 steps/s), at least what MAXNB partial sums per system allow
+    {
+        // ... and few enough that two workgroups of k_update_fused fit a CU's LDS ((2 RT + 2) rows of NYP complex128)
+        const int ldsRows = std::max(1, (int)((80 * 1024 / ((size_t)h.NYP * sizeof(cplx)) - 2) / 2));
+        const int want = std::min(std::min(8, ldsRows), std::max(2, (int)(((long)(h.nz - 1) * h.S + 511) / 512)));
+        c.RT = std::max(kn.rtGiven ? kn.rt : want, (h.nz - 1 + MAXNB - 1) / MAXNB);
+    }
+    c.RTS = c.RT;      // rows per tile of k_spmv_fused<2> (HMCMT_RTS; headline mesh, steps/s: 7 rows 328, 10 rows 311, 14 rows 325 -- it stays on the short tiles)
+    c.RT2 = c.RT;      // rows per tile of k_update_fused<2> (>= RT: its partial sums fill the first slots of the k.NTR the consumers read); set with the launch shapes below
+    // launch shapes of the two stencil kernels (launch_update2, launch_spmv).  Measured at the headline size, bench.py, steps/s
+    // (round 3, profiles/r03_launch_shapes.md): k_spmv_fused 256 / 512 / 1024 threads 290 / 294 / 275; k_update_fused<2>
+    // threads,batch,rows 256,6,7 (round 2) 294 | 512,8,14 304 | 512,6,14 301 | 512,4,14 297 | 1024,4,14 305 | 512,8,18 298 |
+    // 512,8,21 279 | 512,8,12 281 | 256,6,14 277: twice the rows with twice the threads -- the same work per thread, 4 halo
+    // rows per 14 instead of per 7.
+    // ... all of which is for tiles with enough nodes per thread: on the reference's dprism3d example (96x49 cells, 22
+    // systems, tiles of 3 rows x 112 nodes) the wide shapes lose 7 % (392 vs 419 evaluations/s, scripts/gpu_example_ab.sh),
+    // so small tiles keep the round-2 shapes.
+    const int tileNodes = (c.RT + 2) * h.NYP, tile2Nodes = (2 * c.RT + 4) * h.NYP;
+    c.spmvThreads = c.upd1Threads = tileNodes >= 1280 ? 512 : 256;     // (cfg3 1872, cfg5 2912 | dprism3d 560, cfg2 256)
+    c.residThreads = tileNodes >= 1280 ? 512 : 256;        // (k_resid_pre at the headline size: 16.9 / 13.8 / 18.6 us with 256 / 512 / 1024)
+    if (kn.resid) c.residThreads = kn.resid;
+    c.upd2Threads = 256; c.upd2Batch = 6;
+    if (tile2Nodes >= 2560 && h.NYP <= 256 &&                               // (cfg3 3744 | dprism3d 1120; cfg5: 52.7 vs 51.8 steps/s with the taller tiles)
+        (size_t)(3 * 2 * c.RT + 8) * h.NYP * sizeof(float2) <= (size_t)150 * 1024) { c.upd2Threads = 512; c.upd2Batch = 8; c.RT2 = 2 * c.RT; }
+    if (kn.rt2Given) c.RT2 = std::max(c.RT, kn.rt2);
+    if (kn.rtsGiven) c.RTS = std::max(c.RT, std::min(kn.rts, 64));
+    {   // HMCMT_UPD2 = "threads,batch,rows"
+        const int a = kn.upd2[0], b = kn.upd2[1], r = kn.upd2[2];
+        if (kn.upd2N >= 1 && (a == 256 || a == 512 || a == 1024)) c.upd2Threads = a;
+        if (kn.upd2N >= 2 && b > 0) c.upd2Batch = b;
+        if (kn.upd2N >= 3 && r >= c.RT) c.RT2 = r;
+    }
+    if (kn.upd1) c.upd1Threads = kn.upd1;
+    if (kn.spmv) c.spmvThreads = kn.spmv;
+    // forward half of the FDM stage: the fused kernel where its LDS slabs fit (fdm_fwd_ntw); the operand format goes with the path
+    Solver dims{};
+    dims.NYP = h.NYP; dims.NZP = h.NZP; dims.nz = h.nz;
+    c.fwdNtwFused = fdm_fwd_ntw(dims, true, kn.fusedFwdMode == 2, kn.twistOn, c.maxLds);
+    c.fwdNtw = kn.fusedFwdMode ? c.fwdNtwFused : 0;
+    c.splitT = c.fwdNtw > 0;
+    c.fusedBackFits = c.splitT && back_post_lds(h.NYP) <= c.maxLdsBack && h.NYP <= 256;
+    // x += alpha p rides along in k_fdm_fwd where the update kernel's burst is long enough to notice (headline size: +2.4 .. 3.5 %;
+    // on dprism3d's 6 160 interior nodes per system it costs 1 %); HMCMT_XFWD=0 / 1 forces it off / on
+    c.xInFwd = c.splitT && (kn.xfwd < 0 ? (long)(h.nz - 1) * h.NYP >= 12000 : kn.xfwd != 0);
+    {   // the x update is done by the fused kernel's waves 1.. and its per-slab sums fill MAXNB slots: not with one wave, not with more slabs
+        const int Gq = (h.NZP + 7) / 8, per = (Gq + 7) / 8, nw = (Gq + per - 1) / per, nslab = ((h.NYP >> 4) + FW_NTW - 1) / FW_NTW;
+        if (nw < 2 || nslab > MAXNB) c.xInFwd = 0;
+    }
+    {   // the twisted factorisation goes with the kernels that sweep both ways at once: the fused forward kernel of the launch-per-phase
+        // path, and the persistent kernel (which does not need the fused one to fit: tall meshes)
+        int a1, a2, a3, a4; size_t a5;
+        const bool pshape = persist_shape(c, ShapeDims{h.NYP, h.NZP, h.nz}, kn.twistOn ? 1 : 0, a1, a2, a3, a4, a5);
+        c.twist = (c.splitT || pshape) && kn.twistOn;
+    }
+    return persist_config(h, c, err);
+}
+
+// the context's streams, events and buffers, for the problem and the configuration it was constructed with (the device is current)
+static int create_impl(hmcmt_ctx* ctx) {
+    const int device_id = ctx->cfg.device;
+    ctx->ss.persistOn = ctx->cfg.persist; ctx->ss.guardEvery = ctx->cfg.guardEvery; ctx->ss.dbgFlags = ctx->cfg.debugFlags;      // (their initial values: they change at run time)
+    if (ctx->cfg.shareCnt > 1) {
         // a share of EVERY XCD's CUs: mask bit n is CU n / nXCD of XCD n % nXCD (measured, scripts/probe/cumask.hip: a mask that
         // leaves an XCD without a bit leaves that XCD unrestricted), so share i of c takes the CU indices [i, i + 1) * cuPerXcd / c
         hipDeviceProp_t prop;
@@ -1982,7 +2074,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
         std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
         for (int n = 0; n < ncu; ++n) {
             const int cu = n / nxcd;
-            if (cu * ctx->shareCnt / per == ctx->shareIdx) mask[n / 32] |= 1u << (n % 32);
+            if (cu * ctx->cfg.shareCnt / per == ctx->cfg.shareIdx) mask[n / 32] |= 1u << (n % 32);
         }
         HIPCHK(hipExtStreamCreateWithCUMask(&ctx->stream, (uint32_t)mask.size(), mask.data()));
         HIPCHK(hipExtStreamCreateWithCUMask(&ctx->side, (uint32_t)mask.size(), mask.data()));
@@ -1993,108 +2085,20 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
         // solves instead of beside them (round 6: bench.py under a process group 519-531 steps/s against 606-625 without; with
         // GPU_MAX_HW_QUEUES=8 626).  Another priority is another set of queues.  HMCMT_STREAM_PRIORITY=0: both streams at the default one.
         int prLeast = 0, prGreatest = 0;
-        const char* ep = getenv("HMCMT_STREAM_PRIORITY");
-        const bool hiPr = !(ep && ep[0] == '0') && hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest) == hipSuccess && prGreatest != prLeast;
+        const bool hiPr = ctx->cfg.streamPriority && hipDeviceGetStreamPriorityRange(&prLeast, &prGreatest) == hipSuccess && prGreatest != prLeast;
         if (hiPr) HIPCHK(hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prGreatest));
         else { (void)hipGetLastError(); HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)); }
         HIPCHK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
     }
     // events between the library's own streams: no system-scope fence at the record (HMCMT_EVENT_FLAGS: 0 the default
     // system-scope release, 1 hipEventDisableSystemFence, 2 hipEventReleaseToDevice); evRec is waited for by the host
-    const int evMode = getenv("HMCMT_EVENT_FLAGS") ? atoi(getenv("HMCMT_EVENT_FLAGS")) : 1;
+    const int evMode = ctx->cfg.eventFlags;
     const unsigned evDev = hipEventDisableTiming | (evMode == 1 ? hipEventDisableSystemFence : evMode == 2 ? hipEventReleaseToDevice : 0u);
     HIPCHK(hipEventCreateWithFlags(&ctx->evModel, evDev));
     HIPCHK(hipEventCreateWithFlags(&ctx->evSens, evDev));
     HIPCHK(hipEventCreateWithFlags(&ctx->evExtF, evDev));
     HIPCHK(hipEventCreateWithFlags(&ctx->evPiv, evDev));
     HIPCHK(hipEventCreateWithFlags(&ctx->evRec, hipEventDisableTiming));
-    {
-        const char* e = getenv("HMCMT_FUSED_FWD");
-        ctx->fusedFwd = !(e && e[0] == '0');
-        ctx->fusedFwdForce = e && e[0] == '2';
-
-        if (const char* et = getenv("HMCMT_TWIST")) ctx->twistOn = et[0] != '0';
-        if (const char* eb = getenv("HMCMT_FUSED_BACK")) ctx->fusedBack = eb[0] != '0';
-        // (this kernel also has a few hundred bytes of static LDS: ask for less than the full 160 KB)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_back_post<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) == hipSuccess)
-            ctx->maxLdsBack = 152 * 1024;
-        else (void)hipGetLastError();
-        if (const char* ew = getenv("HMCMT_JACOBI_W")) ctx->jacobiW = std::min(1.2, std::max(0.1, atof(ew)));
-        if (const char* es = getenv("HMCMT_SWEEPS")) ctx->sweepsMode = std::max(0, std::min(2, atoi(es)));     // 0 / "auto": per solve
-        if (const char* eg = getenv("HMCMT_GUARD_EVERY")) ctx->ss.guardEvery = std::max(0, atoi(eg));
-        if (const char* eg = getenv("HMCMT_SPEC")) ctx->specOn = eg[0] != '0';
-        if (const char* eg = getenv("HMCMT_GUARD_LIMIT")) ctx->guardLimit = atof(eg);
-        if (const char* es = getenv("HMCMT_SWEEPS_UP")) ctx->sweepsUp = std::max(1, atoi(es));
-        if (const char* es = getenv("HMCMT_SWEEPS_DOWN")) ctx->sweepsDown = std::max(0, atoi(es));
-        if (const char* ep = getenv("HMCMT_EXTRAP_POINTS")) ctx->extrapNp = std::max(2, std::min(EXT_NP, atoi(ep)));
-        {
-            // boundary columns per workgroup of k_bc_fused: all workgroups resident at once (two per CU: registers), else the
-            // two-kernel form (HMCMT_BC_FUSED = 0: never, n: n columns per workgroup)
-            const int cols = ctx->hp.ny + 1, nz = ctx->hp.nz;
-            int cw = std::max(1, (cols * ctx->hp.nFreq + 511) / 512);
-            if (const char* eb = getenv("HMCMT_BC_FUSED")) cw = atoi(eb);
-            const int slots = cols <= cw ? 2 : 1;
-            const size_t lds = ((size_t)5 * nz * cw + (size_t)slots * 2 * nz) * sizeof(cplx);
-            if (cw > 0 && cw <= 256 && lds <= (size_t)80 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_bc_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess) {
-                ctx->bcCW = cw; ctx->bcSlots = slots; ctx->bcLds = lds;
-            }
-            // otherwise the layer-blocked form (HMCMT_BC_BLOCKED = 0: the two-kernel form; "columns[,threads[,up layers[,down layers]]]"
-            // per workgroup and block)
-            // default: 1 024 threads (15 producer waves beside the chain wave: the transcendental work needs the occupancy), columns
-            // such that the workgroups of a frequency divide its columns evenly and fill the chip at the stress size (401 columns, 32
-            // frequencies: 8 x 51 -> 256 workgroups, one per CU), as many layers per bottom -> top block as the producers have threads
-            int nt = 1024, cb = 64, lbu = 0, lbd = 8;
-            { const int g = (cols + 63) / 64; int per = 256 / std::max(1, ctx->hp.nFreq); per = std::max(g, std::min(per, (cols + 15) / 16)); cb = (cols + per - 1) / per; }
-            if (const char* eb = getenv("HMCMT_BC_BLOCKED")) sscanf(eb, "%d,%d,%d,%d", &cb, &nt, &lbu, &lbd);
-            const bool blockedOff = cb <= 0;
-            cb = std::max(1, std::min(cb, 64)); nt = std::max(128, std::min(1024, nt / 64 * 64));
-            if (lbu <= 0) lbu = (nt - 64) / cb;
-            lbu = std::max(1, std::min(std::min(lbu, nz), (nt - 64) / cb));
-            lbd = std::max(1, std::min(std::min(lbd, nz), (nt - 64) / cb));
-            const int bslots = cols <= cb ? 2 : 1;
-            const size_t blds = ((size_t)2 * std::max(3 * lbu, 5 * lbd) * cb + (size_t)bslots * 2 * nz) * sizeof(cplx);
-            if (ctx->bcCW == 0 && !blockedOff && blds <= (size_t)150 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_bc_blocked), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess) {
-                ctx->bcbCW = cb; ctx->bcbSlots = bslots; ctx->bcbLds = blds; ctx->bcbNT = nt; ctx->bcbLBu = lbu; ctx->bcbLBd = lbd;
-            }
-        }
-        {
-            const size_t sl = (size_t)12 * (ctx->hp.nz + 1) * sizeof(cplx) + (size_t)ctx->hp.nz * sizeof(double);
-            const char* es = getenv("HMCMT_SENS_FUSED");
-            ctx->sensFusedAlways = es && es[0] == '1';
-            if (!(es && es[0] == '0') && sl <= (size_t)150 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(k_sens_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess)
-                ctx->sensFusedLds = sl;
-        }
-        ctx->wantTicks = getenv("HMCMT_TICKS") != nullptr;
-        ctx->noFusedStart = getenv("HMCMT_NO_FUSED_START") != nullptr;
-        ctx->noSigmaRows = getenv("HMCMT_NO_SIGMA_ROWS") != nullptr;
-        ctx->noCoefAll = getenv("HMCMT_NO_COEF_ALL") != nullptr;
-        if (const char* el = getenv("HMCMT_LAZY_DINV")) ctx->lazyDinv = el[0] != '0';
-        if (const char* ed = getenv("HMCMT_DEBUG_FLAGS")) ctx->ss.dbgFlags = atoi(ed);                  // (measurement only: hmcmt_debug_flags)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fdm_fwd<FW_NTW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_fdm_fwd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess)
-            ctx->maxLds = 160 * 1024;
-        else (void)hipGetLastError();
-        // (the separate transform kernel stages LP_NRG row groups: beyond 64 KB on wide meshes with LP_NRG > 2)
-        for (const void* f : {reinterpret_cast<const void*>(k_transform_lp<0, 0>), reinterpret_cast<const void*>(k_transform_lp<0, 1>),
-                              reinterpret_cast<const void*>(k_transform_lp<1, 0>), reinterpret_cast<const void*>(k_transform_lp<1, 1>),
-                              reinterpret_cast<const void*>(k_transform_lp<2, 0>), reinterpret_cast<const void*>(k_transform_lp<2, 1>)})
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) (void)hipGetLastError();
-        // the stencil kernels' tiles can pass 64 KB on wide meshes
-        for (const void* f : {reinterpret_cast<const void*>(k_update_fused<1, 256, 6>), reinterpret_cast<const void*>(k_update_fused<1, 512, 6>), reinterpret_cast<const void*>(k_update_fused<2, 256, 6>),
-                              reinterpret_cast<const void*>(k_update_fused<2, 512, 4>), reinterpret_cast<const void*>(k_update_fused<2, 512, 6>),
-                              reinterpret_cast<const void*>(k_update_fused<2, 512, 8>), reinterpret_cast<const void*>(k_update_fused<2, 1024, 4>)})
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_post2), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) (void)hipGetLastError();
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_back_post<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) (void)hipGetLastError();
-        for (const void* f : {reinterpret_cast<const void*>(k_spmv_fused<1, 256>), reinterpret_cast<const void*>(k_spmv_fused<1, 512>), reinterpret_cast<const void*>(k_spmv_fused<1, 1024>),
-                              reinterpret_cast<const void*>(k_spmv_fused<2, 256>), reinterpret_cast<const void*>(k_spmv_fused<2, 512>), reinterpret_cast<const void*>(k_spmv_fused<2, 1024>)})
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) (void)hipGetLastError();
-        for (const void* f : {reinterpret_cast<const void*>(k_resid_pre<256>), reinterpret_cast<const void*>(k_resid_pre<512>), reinterpret_cast<const void*>(k_resid_pre<1024>)})
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) (void)hipGetLastError();
-    }
     HIPCHK(hipEventCreateWithFlags(&ctx->evExtA, evDev));
     const HostProblem& h = ctx->hp;
     View& v = ctx->v;
@@ -2180,57 +2184,22 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     k.S = h.S; k.NYP = h.NYP; k.NZP = h.NZP; k.ny = h.ny; k.nz = h.nz; k.nFreq = h.nFreq; k.vstride = v.vstride;
     k.NB = std::max(1, std::min(32, (1024 + h.S - 1) / h.S));
     k.chunk = (v.vstride + k.NB - 1) / k.NB;
-    // rows per tile of the stencil kernels: about 512 workgroups per launch, at most 8 rows (measured at cfg3:
-    // 4 rows 484, 6 rows 489, 8 rows 492, 12 rows 456 steps/s), at least what MAXNB partial sums per system allow
-    {
-        // ... and few enough that two workgroups of k_update_fused fit a CU's LDS ((2 RT + 2) rows of NYP complex128)
-        const int ldsRows = std::max(1, (int)((80 * 1024 / ((size_t)h.NYP * sizeof(cplx)) - 2) / 2));
-        const int want = std::min(std::min(8, ldsRows), std::max(2, (int)(((long)(h.nz - 1) * h.S + 511) / 512)));
-        const char* e = getenv("HMCMT_RT");
-        k.RT = std::max(e ? atoi(e) : want, (h.nz - 1 + MAXNB - 1) / MAXNB);
-    }
+    // the launch shapes and paths make_config chose, where the kernels take them by value
+    k.RT = ctx->cfg.RT; k.RT2 = ctx->cfg.RT2; k.RTS = ctx->cfg.RTS;
     k.NTR = (h.nz - 1 + k.RT - 1) / k.RT;
     k.sweeps = 1;
-    k.RTS = k.RT;      // rows per tile of k_spmv_fused<2> (HMCMT_RTS; headline mesh, steps/s: 7 rows 328, 10 rows 311, 14 rows 325 -- it stays on the short tiles)
-    k.RT2 = k.RT;      // rows per tile of k_update_fused<2> (>= RT: its partial sums fill the first slots of the k.NTR the consumers read); set with the launch shapes below
-    // launch shapes of the two stencil kernels (launch_update2, launch_spmv).  Measured at the headline size, bench.py, steps/s
-    // (round 3, profiles/r03_launch_shapes.md): k_spmv_fused 256 / 512 / 1024 threads 290 / 294 / 275; k_update_fused<2>
-    // threads,batch,rows 256,6,7 (round 2) 294 | 512,8,14 304 | 512,6,14 301 | 512,4,14 297 | 1024,4,14 305 | 512,8,18 298 |
-    // 512,8,21 279 | 512,8,12 281 | 256,6,14 277: twice the rows with twice the threads -- the same work per thread, 4 halo
-    // rows per 14 instead of per 7.
-    // ... all of which is for tiles with enough nodes per thread: on the reference's dprism3d example (96x49 cells, 22
-    // systems, tiles of 3 rows x 112 nodes) the wide shapes lose 7 % (392 vs 419 evaluations/s, scripts/gpu_example_ab.sh),
-    // so small tiles keep the round-2 shapes.
-    const int tileNodes = (k.RT + 2) * k.NYP, tile2Nodes = (2 * k.RT + 4) * k.NYP;
-    ctx->spmvThreads = ctx->upd1Threads = tileNodes >= 1280 ? 512 : 256;     // (cfg3 1872, cfg5 2912 | dprism3d 560, cfg2 256)
-    ctx->residThreads = tileNodes >= 1280 ? 512 : 256;        // (k_resid_pre at the headline size: 16.9 / 13.8 / 18.6 us with 256 / 512 / 1024)
-    if (const char* er = getenv("HMCMT_RESID")) { const int t = atoi(er); if (t == 256 || t == 512 || t == 1024) ctx->residThreads = t; }
-    ctx->upd2Threads = 256; ctx->upd2Batch = 6;
-    if (tile2Nodes >= 2560 && k.NYP <= 256 &&                               // (cfg3 3744 | dprism3d 1120; cfg5: 52.7 vs 51.8 steps/s with the taller tiles)
-        (size_t)(3 * 2 * k.RT + 8) * k.NYP * sizeof(float2) <= (size_t)150 * 1024) { ctx->upd2Threads = 512; ctx->upd2Batch = 8; k.RT2 = 2 * k.RT; }
-    if (const char* e2 = getenv("HMCMT_RT2")) k.RT2 = std::max(k.RT, atoi(e2));
-    if (const char* e2 = getenv("HMCMT_RTS")) k.RTS = std::max(k.RT, std::min(atoi(e2), 64));
-    if (const char* eu = getenv("HMCMT_UPD2")) {              // "threads,batch,rows"
-        int a = 0, b = 0, c = 0;
-        const int n = sscanf(eu, "%d,%d,%d", &a, &b, &c);
-        if (n >= 1 && (a == 256 || a == 512 || a == 1024)) ctx->upd2Threads = a;
-        if (n >= 2 && b > 0) ctx->upd2Batch = b;
-        if (n >= 3 && c >= k.RT) k.RT2 = c;
-    }
-    if (const char* eu = getenv("HMCMT_UPD1")) { const int a = atoi(eu); if (a == 256 || a == 512) ctx->upd1Threads = a; }
-    if (const char* eu = getenv("HMCMT_SPMV")) { const int a = atoi(eu); if (a == 256 || a == 512 || a == 1024) ctx->spmvThreads = a; }
-    k.xInFwd = 0;       // set with k.splitT (the fused forward kernel is the one that can take the x update along)
+    k.splitT = ctx->cfg.splitT; k.xInFwd = ctx->cfg.xInFwd; k.twist = v.twist = ctx->cfg.twist;
     k.stamps = nullptr; k.stampKernel = 0;
     k.ticks = nullptr; k.xTickF = v.X;
-    if (ctx->wantTicks && hipMalloc(&ctx->v.ticks, (32 + 64 * TK_N) * sizeof(long long)) == hipSuccess) {
+    if (ctx->cfg.wantTicks && hipMalloc(&ctx->v.ticks, (32 + 64 * TK_N) * sizeof(long long)) == hipSuccess) {
         hipMemset(ctx->v.ticks, 0, (32 + 64 * TK_N) * sizeof(long long));
         k.ticks = ctx->v.ticks;
     }
-    if (const char* es = getenv("HMCMT_STAMPS")) {
-        k.stampKernel = !strcmp(es, "upd") ? 1 : (!strcmp(es, "spmv") ? 2 : 0);
-        if (k.stampKernel) { HIPCHK(hipMalloc((void**)&k.stamps, sizeof(long long) * 8 * 4096)); HIPCHK(hipMemset(k.stamps, 0, sizeof(long long) * 8 * 4096)); }
+    if (ctx->cfg.stamps == STAMPS_UPD || ctx->cfg.stamps == STAMPS_SPMV) {
+        k.stampKernel = ctx->cfg.stamps;
+        HIPCHK(hipMalloc((void**)&k.stamps, sizeof(long long) * 8 * 4096)); HIPCHK(hipMemset(k.stamps, 0, sizeof(long long) * 8 * 4096));
     }
-    k.w2 = getenv("HMCMT_JACOBI_W2") ? (float)atof(getenv("HMCMT_JACOBI_W2")) : 1.0f;
+    k.w2 = ctx->cfg.w2;
     k.merged2 = 1;
     k.omega = v.omega; k.cY = v.cY; k.cZ = v.cZ; k.dK = v.dK; k.dM = v.dM; k.ofz = v.ofz; k.invp = v.invp;
     { float4* cf = nullptr; if ((rc = dalloc(ctx, &cf, 2 * 2 * VS))) return rc; k.cf32 = cf; }
@@ -2252,8 +2221,7 @@ static int create_impl(hmcmt_ctx* ctx, int32_t device_id) {
     for (int w = 0; w < HW_WORDS; ++w) ctx->h_stall[w] = 0;
     HIPCHK(hipHostGetDevicePointer((void**)&k.stallHost, ctx->h_stall, 0));
     k.failHost = k.stallHost + HW_FAIL;
-    k.stallIt = STALL_IT;
-    if (const char* es = getenv("HMCMT_STALL_IT")) k.stallIt = std::max(1, atoi(es));   // (tests force the fp64 restart with a short window)
+    k.stallIt = ctx->cfg.stallIt;       // (HMCMT_STALL_IT: tests force the fp64 restart with a short window)
     HIPCHK(hipHostMalloc((void**)&ctx->h_prog, sizeof(int), hipHostMallocMapped));
     *ctx->h_prog = 0;
     HIPCHK(hipHostGetDevicePointer((void**)&k.progHost, ctx->h_prog, 0));
@@ -2294,43 +2262,26 @@ int hmcmt_create(hmcmt_ctx** out, int32_t device_id, int64_t ny, int64_t nz, con
         g_createError = "null input array"; return HMCMT_EINVAL;
     }
     if (opts) if (const char* e = options_error(opts)) { g_createError = e; return HMCMT_EINVAL; }
-    hmcmt_ctx* ctx = new hmcmt_ctx();
-    hmcmt_default_options(&ctx->opt);
-    if (opts) ctx->opt = *opts;
-    if (!ctx->hp.build(ny, nz, yLen, zLen, origin, nFreq, freqs, nRx, rxY, rxZ, nComp, compMode, nData, freqID,
-                       rxID, dtID, dataID, obs, dataW, nAC, activeIdx, bgModel)) {
-        g_createError = ctx->hp.error;
-        delete ctx;
+    HostProblem hp;
+    if (!hp.build(ny, nz, yLen, zLen, origin, nFreq, freqs, nRx, rxY, rxZ, nComp, compMode, nData, freqID,
+                  rxID, dtID, dataID, obs, dataW, nAC, activeIdx, bgModel)) {
+        g_createError = hp.error;
         return HMCMT_EINVAL;
     }
-    ctx->shareIdx = shareIdx; ctx->shareCnt = shareCnt;
-    int rc = create_impl(ctx, device_id);
-    if (rc) {
-        g_createError = ctx->err;
-        hmcmt_destroy(ctx);
-        return rc;
+    hmcmt_options opt;
+    hmcmt_default_options(&opt);
+    if (opts) opt = *opts;
+    // the configuration first -- knobs, then what they, the mesh and the device decide --, then the context around it: const from here on
+    struct { const char* operator()(const char* name) const { return getenv(name); } } env;     // (the library's one look at the environment)
+    Config cfg;
+    int rc = make_config(hp, opt, read_knobs(env, KnobLimits{EXT_NP, STALL_IT, PS_SPIN_LIMIT}), device_id, shareIdx, shareCnt, cfg, g_createError);
+    if (rc) return rc;
+    hmcmt_ctx* ctx = new hmcmt_ctx(std::move(hp), opt, cfg);
+    if ((rc = create_impl(ctx)) || (rc = persist_alloc(ctx))) { g_createError = ctx->err; hmcmt_destroy(ctx); return rc; }
+    if (ctx->cfg.device >= 0 && ctx->cfg.device < MAXDEV) {
+        for (int q = 0; q < 4; ++q) if ((ctx->cfg.shareMask >> q) & 1u) g_quarterUse[ctx->cfg.device][q].fetch_add(1);
     }
-    ctx->sv.splitT = fdm_fwd_ntw(ctx) > 0;
-    // x += alpha p rides along in k_fdm_fwd where the update kernel's burst is long enough to notice (headline size: +2.4 .. 3.5 %;
-    // on dprism3d's 6 160 interior nodes per system it costs 1 %); HMCMT_XFWD=0 / 1 forces it off / on
-    ctx->sv.xInFwd = ctx->sv.splitT && (long)(ctx->sv.nz - 1) * ctx->sv.NYP >= 12000;
-    if (const char* ex = getenv("HMCMT_XFWD")) ctx->sv.xInFwd = ctx->sv.splitT && ex[0] != '0';
-    {   // the x update is done by the fused kernel's waves 1.. and its per-slab sums fill MAXNB slots: not with one wave, not with more slabs
-        const Solver& kk = ctx->sv;
-        const int Gq = (kk.NZP + 7) / 8, per = (Gq + 7) / 8, nw = (Gq + per - 1) / per, nslab = ((kk.NYP >> 4) + FW_NTW - 1) / FW_NTW;
-        if (nw < 2 || nslab > MAXNB) ctx->sv.xInFwd = 0;
-    }
-    {   // the twisted factorisation goes with the kernels that sweep both ways at once: the fused forward kernel of the launch-per-phase
-        // path, and the persistent kernel (which does not need the fused one to fit: tall meshes)
-        int a1, a2, a3, a4; size_t a5;
-        const bool pshape = persist_shape(ctx, ctx->twistOn ? 1 : 0, a1, a2, a3, a4, a5);
-        ctx->sv.twist = ctx->v.twist = (ctx->sv.splitT || pshape) && ctx->twistOn;
-    }
-    if ((rc = persist_setup(ctx))) { g_createError = ctx->err; hmcmt_destroy(ctx); return rc; }
-    if (ctx->device >= 0 && ctx->device < MAXDEV) {
-        for (int q = 0; q < 4; ++q) if ((ctx->shareMask >> q) & 1u) g_quarterUse[ctx->device][q].fetch_add(1);
-    }
-    devlock_ref(ctx->device);
+    devlock_ref(ctx->cfg);
     ctx->counted = true;
     *out = ctx;
     return 0;
@@ -2364,7 +2315,7 @@ int hmcmt_get_iters(const hmcmt_ctx* ctx, int32_t* iters) {
 
 int hmcmt_profile_counters(hmcmt_ctx* ctx, int64_t* out) {
     if (!ctx || !out) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     prof_collect(ctx);
     unsigned long long c = 0;
     HIPCHK(hipMemcpy(&c, ctx->d_cnt, sizeof c, hipMemcpyDeviceToHost));
@@ -2381,7 +2332,7 @@ int hmcmt_dims(const hmcmt_ctx* ctx, int32_t* o) {
 
 int hmcmt_grad_device(hmcmt_ctx* ctx, const double* d_m, double* d_pred, double* d_misfit, double* d_grad) {
     if (!ctx || !d_m || !d_grad) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     int rc = evaluate(ctx, d_m, true, d_pred, d_misfit, d_grad);
     if (rc) return rc;
     if ((rc = collect_stats(ctx, true))) return rc;      // includes the stream synchronisation
@@ -2391,7 +2342,7 @@ int hmcmt_grad_device(hmcmt_ctx* ctx, const double* d_m, double* d_pred, double*
 
 int hmcmt_grad_device_async(hmcmt_ctx* ctx, const double* d_m, double* d_pred, double* d_misfit, double* d_grad) {
     if (!ctx || !d_m || !d_grad) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     int rc = evaluate(ctx, d_m, true, d_pred, d_misfit, d_grad);
     if (rc) return rc;
     ctx->statsPending = true;
@@ -2403,7 +2354,7 @@ static int leapfrog_flag(hmcmt_ctx* ctx);
 
 int hmcmt_wait(hmcmt_ctx* ctx) {
     if (!ctx) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const int rc = collect_pending(ctx);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     prof_collect(ctx);
@@ -2413,7 +2364,7 @@ int hmcmt_wait(hmcmt_ctx* ctx) {
 
 int hmcmt_forward_device(hmcmt_ctx* ctx, const double* d_m, double* d_pred, double* d_misfit) {
     if (!ctx || !d_m) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     int rc = evaluate(ctx, d_m, false, d_pred, d_misfit, nullptr);
     if (rc) return rc;
     if ((rc = collect_stats(ctx, false))) return rc;
@@ -2443,7 +2394,7 @@ static void memo_store(hmcmt_ctx* ctx, const double* m, const double* pred, doub
 
 static int host_eval(hmcmt_ctx* ctx, const double* m, double* pred, double* misfit, double* grad, bool wantGrad) {
     if (!ctx || !m || (wantGrad && !grad)) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const int nAC = ctx->v.nAC, nData = ctx->v.nData;
     for (int i = 0; i < nAC; ++i)
         if (!std::isfinite(m[i])) { ctx->err = "non-finite model value"; return HMCMT_EBREAKDOWN; }
@@ -2486,7 +2437,7 @@ int hmcmt_forward(hmcmt_ctx* ctx, const double* m, double* pred, double* misfit)
 int hmcmt_get_fields(hmcmt_ctx* ctx, int32_t adjoint, double* exTE, double* hxTM) {
     if (!ctx) return HMCMT_EINVAL;
     if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const View& v = ctx->v;
     const int nn = (v.ny + 1) * (v.nz + 1);
     const cplx* src = adjoint ? v.Lam : v.X;
@@ -2516,9 +2467,9 @@ int hmcmt_profile(hmcmt_ctx* ctx, int32_t enable) {
         // out at 2.57 us run after run.  (Rounds 1-2 calibrated with an EMPTY kernel, whose period is the HOST's launch
         // rate, times a fitted factor: the subtracted value followed the host's speed, 0.3 .. 3.8 us from run to run.
         // A 512-workgroup spin kernel is no better a yardstick: its workgroups start over 6 us.)
-        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipSetDevice(ctx->cfg.device));
         int wallKHz = 100000;
-        if (hipDeviceGetAttribute(&wallKHz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || wallKHz <= 0) wallKHz = 100000;
+        if (hipDeviceGetAttribute(&wallKHz, hipDeviceAttributeWallClockRate, ctx->cfg.device) != hipSuccess || wallKHz <= 0) wallKHz = 100000;
         constexpr double SPIN_US = 12.0, SPIN_EDGE_US = 0.39;
         const long long ticks = (long long)(SPIN_US * 1e-3 * wallKHz);
         const int N = 48;
@@ -2584,7 +2535,7 @@ static int set_all_active(hmcmt_ctx* ctx) {
 
 int hmcmt_debug_transform(hmcmt_ctx* ctx, int32_t which, const double* A, double* C) {
     if (!ctx || !A || !C) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const size_t bytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     HIPCHK(hipMemcpy(ctx->sv.p, A, bytes, hipMemcpyHostToDevice));
     if (which >= 2) {
@@ -2618,7 +2569,7 @@ int hmcmt_debug_flags(hmcmt_ctx* ctx, int32_t flags) {
 int hmcmt_debug_spmv(hmcmt_ctx* ctx, const double* p, double* q) {
     if (!ctx || !p || !q) return HMCMT_EINVAL;
     if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const size_t bytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     HIPCHK(hipMemcpy(ctx->sv.p, p, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(ctx->sv.q, 0, bytes));
@@ -2633,7 +2584,7 @@ int hmcmt_debug_spmv(hmcmt_ctx* ctx, const double* p, double* q) {
 // the extrapolation state of solve kind `kind` as the last evaluation left it: {w_0..w_5, keep, count, field-ring head, model-ring head}
 int hmcmt_debug_extrap(hmcmt_ctx* ctx, int32_t kind, double* out) {
     if (!ctx || !out || kind < 0 || kind > 1) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->side));
     HIPCHK(hipMemcpy(out, ctx->d_ext[kind], EXT_PART * sizeof(double), hipMemcpyDeviceToHost));
@@ -2643,7 +2594,7 @@ int hmcmt_debug_extrap(hmcmt_ctx* ctx, int32_t kind, double* out) {
 // capture of the initial guesses on / off: while on, every evaluation that extrapolates copies X (Lam) behind k_extrap, on its stream
 int hmcmt_debug_guess_capture(hmcmt_ctx* ctx, int32_t enable) {
     if (!ctx) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->side));
     if (enable && !ctx->d_guessCap[0]) {
@@ -2660,7 +2611,7 @@ int hmcmt_debug_guess_capture(hmcmt_ctx* ctx, int32_t enable) {
 int hmcmt_debug_guess(hmcmt_ctx* ctx, int32_t kind, double* out) {
     if (!ctx || !out || kind < 0 || kind > 1) return HMCMT_EINVAL;
     if (!ctx->guessCapture || !ctx->d_guessCap[kind]) { ctx->err = "hmcmt_debug_guess: the capture is off (hmcmt_debug_guess_capture)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->side));
     HIPCHK(hipMemcpy(out, ctx->d_guessCap[kind], (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx), hipMemcpyDeviceToHost));
@@ -2670,16 +2621,18 @@ int hmcmt_debug_guess(hmcmt_ctx* ctx, int32_t kind, double* out) {
 int hmcmt_debug_precond(hmcmt_ctx* ctx, const double* r, double* z) {
     if (!ctx || !r || !z) return HMCMT_EINVAL;
     if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const size_t bytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     HIPCHK(hipMemcpy(ctx->sv.r, r, bytes, hipMemcpyHostToDevice));
     int rc = set_all_active(ctx);
     if (rc) return rc;
-    const int merged = ctx->sv.merged2;
-    ctx->sv.merged2 = 0;                 // (two sweeps: the last one as a launch of its own, so that z exists in memory)
-    ensure_dinv(ctx);
-    apply_precond(ctx);
-    ctx->sv.merged2 = merged;
+    {
+        const int merged = ctx->sv.merged2;
+        AtExit mergedBack([&] { ctx->sv.merged2 = merged; });
+        ctx->sv.merged2 = 0;                 // (two sweeps: the last one as a launch of its own, so that z exists in memory)
+        ensure_dinv(ctx);
+        apply_precond(ctx);
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0) {
         // the default path leaves its result as complex64 (Solver::z32): widen it for the caller
@@ -2709,14 +2662,14 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
     if (!ctx || !out || nout < 0) return HMCMT_EINVAL;
     // (the caller says how many slots it has: fields are only ever appended, a caller built against an older header gets the ones it knows)
     const int64_t v[HMCMT_PERSIST_INFO_FIELDS] = {
-        ctx->persistCW, ctx->persistG, ctx->inst.persistSlots, ctx->ss.persistOn ? 1 : 0,
+        ctx->cfg.persistCW, ctx->cfg.persistG, ctx->inst.persistSlots, ctx->ss.persistOn ? 1 : 0,
         ctx->persistSolves, ctx->persistFallbacks,
         persist_ok(ctx) ? 1 : 0,              // would the next default-path solve use it (alone on the device, device lock held)
-        ctx->persistCW ? ctx->persistMW : 0,  // modes per slab
-        ctx->persistCW ? ctx->persistCS : 0,  // column parts per row block (2: wide meshes)
+        ctx->cfg.persistCW ? ctx->cfg.persistMW : 0,  // modes per slab
+        ctx->cfg.persistCW ? ctx->cfg.persistCS : 0,  // column parts per row block (2: wide meshes)
         ctx->persistTimeouts,                 // timed-out waits (the evaluation was redone with the launch-per-phase loop)
-        ctx->shareIdx, ctx->shareCnt,         // this context's share of every XCD's CUs (hmcmt_next_cu_share)
-        ctx->persistCW ? ctx->psKern[0]->strips : 0,   // strips of tile rows per column: 2 (k_cocg_persist) or 4 (k_cocg_persist4: threads = strips x threads_half)
+        ctx->cfg.shareIdx, ctx->cfg.shareCnt,         // this context's share of every XCD's CUs (hmcmt_next_cu_share)
+        ctx->cfg.persistCW ? ctx->cfg.psKern[0]->strips : 0,   // strips of tile rows per column: 2 (k_cocg_persist) or 4 (k_cocg_persist4: threads = strips x threads_half)
         ctx->ss.persistWhyOff,                   // why the kernel is off: 0 it is not / HMCMT_PERSIST=0, 1 placement (for good), 2 a timed-out wait (tried again after the backoff)
         ctx->fbKind, ctx->fbStalled};         // the last placement fallback: kind of its launch, systems it found started and still active (stalled)
     for (int i = 0; i < nout && i < HMCMT_PERSIST_INFO_FIELDS; ++i) out[i] = v[i];
@@ -2727,7 +2680,7 @@ int hmcmt_persist_info(const hmcmt_ctx* ctx, int64_t* out, int32_t nout) {
 // row: kernels_persist.h, NYK), 0 = the generic kernel (or no persistent kernel at all).
 int hmcmt_persist_width(const hmcmt_ctx* ctx, int32_t* width) {
     if (!ctx || !width) return HMCMT_EINVAL;
-    *width = ctx->persistCW ? ctx->psKern[0]->nyk : 0;
+    *width = ctx->cfg.persistCW ? ctx->cfg.psKern[0]->nyk : 0;
     return 0;
 }
 
@@ -2794,22 +2747,22 @@ int hmcmt_next_cu_share(int32_t index, int32_t count) {
 // own -- returns once they are resident (or after 2 s).  What another application on the device does to the persistent kernel's co-residency (tests/test_gpu_persist.py).
 int hmcmt_debug_hog(hmcmt_ctx* ctx, int32_t nblocks, int32_t ms) {
     if (!ctx || nblocks < 1 || nblocks > 4096 || ms < 0 || ms > 10000) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     static hipStream_t hogStreams[MAXDEV] = {};                   // (one per device, kept: the kernel outlives this call)
-    if (ctx->device < 0 || ctx->device >= MAXDEV) return HMCMT_EINVAL;
-    hipStream_t& hogStream = hogStreams[ctx->device];
+    if (ctx->cfg.device < 0 || ctx->cfg.device >= MAXDEV) return HMCMT_EINVAL;
+    hipStream_t& hogStream = hogStreams[ctx->cfg.device];
     if (!hogStream) HIPCHK(hipStreamCreateWithFlags(&hogStream, hipStreamNonBlocking));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hog), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // (returns when the hog is RESIDENT -- min(nblocks, the device's CUs) of its workgroups have started, counted in a mapped host
     //  word; a fresh process loads the code object at this first launch, which a fixed sleep in the test did not cover -- or after 2 s)
     static int* hogStarted[MAXDEV] = {};
-    int*& started = hogStarted[ctx->device];
+    int*& started = hogStarted[ctx->cfg.device];
     if (!started) HIPCHK(hipHostMalloc((void**)&started, sizeof(int), hipHostMallocMapped));
     *(volatile int*)started = 0;
     hipLaunchKernelGGL(k_hog, dim3(nblocks), dim3(64), 160 * 1024, hogStream, (long long)ms * 100000ll, started);   // (wall_clock64: 100 MHz)
     HIPCHK(hipGetLastError());
     int ncu = 0;
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->cfg.device));
     const int want = std::min(nblocks, ncu > 0 ? ncu : 256);
     const auto t0 = std::chrono::steady_clock::now();
     while (*(volatile int*)started < want && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < 2.0) __builtin_ia32_pause();
@@ -2821,9 +2774,9 @@ int hmcmt_debug_hog(hmcmt_ctx* ctx, int32_t nblocks, int32_t ms) {
 int hmcmt_debug_persist_precond(hmcmt_ctx* ctx, int32_t sweeps, const double* r, double* z) {
     if (!ctx || !r || !z || (sweeps != 1 && sweeps != 2)) return HMCMT_EINVAL;
     if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
-    if (!ctx->persistCW) { ctx->err = "the persistent solve kernel does not apply to this problem"; return HMCMT_EINVAL; }
+    if (!ctx->cfg.persistCW) { ctx->err = "the persistent solve kernel does not apply to this problem"; return HMCMT_EINVAL; }
     if (!persist_alone(ctx)) { ctx->err = "the persistent solve kernel may not run now (another context or process holds the device)"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t)ctx->v.S * ctx->v.vstride;
     HIPCHK(hipMemcpy(ctx->sv.r, r, n * sizeof(cplx), hipMemcpyHostToDevice));
     int rc = set_all_active(ctx);
@@ -2847,14 +2800,14 @@ int hmcmt_debug_persist_precond(hmcmt_ctx* ctx, int32_t sweeps, const double* r,
 int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out) {
     if (!ctx || !t || !out) return HMCMT_EINVAL;
     if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     Solver& k = ctx->sv;
     const size_t n = (size_t)ctx->v.S * ctx->v.vstride;
     HIPCHK(hipMemcpy(k.r, t, n * sizeof(cplx), hipMemcpyHostToDevice));
     int rc = set_all_active(ctx);
     if (rc) return rc;
     std::vector<float2> h(n);
-    if (getenv("HMCMT_FWD_STAMPS")) {
+    if (ctx->cfg.fwdStamps) {
         const int gx = (k.NYP / 16 + FW_NTW - 1) / FW_NTW, nb = gx * k.S;
         long long* d_st = nullptr;
         HIPCHK(hipMalloc((void**)&d_st, sizeof(long long) * 8 * nb));
@@ -2878,21 +2831,18 @@ int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out) {
         fprintf(stderr, "k_fdm_fwd stamps (s_memtime ticks, mean over %d blocks): transform %.0f premul %.0f chain %.0f write %.0f | first start -> last end %lld\n",
                 nb, d[0], d[1], d[2], d[3], tmax - tmin);
     }
-    const bool keep = ctx->fusedFwd;
     const int keepSplit = k.splitT;
+    AtExit splitBack([&] { k.splitT = keepSplit; });
     for (int pass = 0; pass < 2; ++pass) {
-        ctx->fusedFwd = pass == 0;
-        k.splitT = pass == 0 && fdm_fwd_ntw(ctx) > 0;      // the operand format goes with the path
+        k.splitT = pass == 0 && ctx->cfg.fwdNtwFused > 0;      // the operand format goes with the path
         hipLaunchKernelGGL(k_to_c64, dim3(k.NB, k.S), dim3(VBLOCK), 0, ctx->stream, k, k.r);
         HIPCHK(hipMemsetAsync(k.y32, 0xff, n * sizeof(float2), ctx->stream));
-        rc = launch_fdm_fwd(ctx);
+        rc = launch_fdm_fwd(ctx, nullptr, pass == 0 ? FdmPath::Fused : FdmPath::Separate);
         const float2* res = k.y32;
         if (!rc && k.splitT) {                              // pre-split result -> complex64 (hi + lo), into t32
             hipLaunchKernelGGL(k_unsplit, dim3(512), dim3(256), 0, ctx->stream, k, k.y32, k.t32);
             res = k.t32;
         }
-        ctx->fusedFwd = keep;
-        k.splitT = keepSplit;
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(h.data(), res, n * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2907,12 +2857,11 @@ int hmcmt_debug_fdm_fwd(hmcmt_ctx* ctx, const double* t, double* out) {
 int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, double* out, double* sums) {
     if (!ctx || !y || !r || !out || !sums) return HMCMT_EINVAL;
     if (!ctx->ss.haveModel) { ctx->err = "no evaluation has been run yet"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     Solver& k = ctx->sv;
     const size_t n = (size_t)ctx->v.S * ctx->v.vstride;
     int rc = set_all_active(ctx);
     if (rc) return rc;
-    const bool keep = ctx->fusedBack;
     ensure_dinv(ctx);
     std::vector<cplx> pa((size_t)k.S * MAXNB);
     std::vector<double> pz((size_t)k.S * MAXNB);
@@ -2923,16 +2872,14 @@ int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, doub
         HIPCHK(hipMemcpyAsync(k.y32, k.t32, n * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(k.r, r, n * sizeof(cplx), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemsetAsync(k.z32, 0xff, n * sizeof(float2), ctx->stream));
-        ctx->fusedBack = pass == 0;
-        rc = launch_back_post(ctx);
-        if (!rc && pass == 0 && getenv("HMCMT_BACK_STAMPS")) {
+        const FdmPath path = pass == 0 ? FdmPath::Fused : FdmPath::Separate;
+        rc = launch_back_post(ctx, path);
+        if (!rc && pass == 0 && ctx->cfg.backStamps) {
             const int nb = ((k.nz - 1 + BP_OWN - 1) / BP_OWN) * k.S;
             long long* d_st = nullptr;
             HIPCHK(hipMalloc((void**)&d_st, sizeof(long long) * 8 * nb));
             HIPCHK(hipMemset(d_st, 0, sizeof(long long) * 8 * nb));
-            ctx->backStamps = d_st;
-            for (int rep = 0; rep < 3 && !rc; ++rep) rc = launch_back_post(ctx);
-            ctx->backStamps = nullptr;
+            for (int rep = 0; rep < 3 && !rc; ++rep) rc = launch_back_post(ctx, path, d_st);
             HIPCHK(hipStreamSynchronize(ctx->stream));
             std::vector<long long> st(8 * (size_t)nb);
             HIPCHK(hipMemcpy(st.data(), d_st, sizeof(long long) * 8 * nb, hipMemcpyDeviceToHost));
@@ -2947,7 +2894,6 @@ int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, doub
             fprintf(stderr, "k_back_post stamps (s_memtime ticks, mean over %d blocks): stage %.0f mfma(first pair) %.0f epilogue+rest %.0f barrier %.0f stencil %.0f reduce %.0f | start -> loads issued %.0f | first start -> last end %lld\n",
                     nb, d[0], d[1], d[2], d[3], d[4], d[5], d[6], tmax - tmin);
         }
-        ctx->fusedBack = keep;
         if (rc) return rc;
         std::vector<float2> hz(n);                              // both paths leave the result as complex64 in z32
         HIPCHK(hipMemcpyAsync(hz.data(), k.z32, n * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
@@ -3207,7 +3153,7 @@ static int mass_apply_dev(hmcmt_ctx* ctx, int op, const double* x, double* y) {
 int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, const int64_t* colind,
                     const double* val, const double* invM) {
     if (!ctx || !mref || !rowptr || !colind || !val || !invM) return HMCMT_EINVAL;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const int n = ctx->v.nAC;
     const int64_t nnz = rowptr[n];
     if (rowptr[0] != 0 || nnz < 0) { ctx->err = "Wm row pointer must be 0-based CSR"; return HMCMT_EINVAL; }
@@ -3256,7 +3202,7 @@ int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
     if (!ctx) return HMCMT_EINVAL;
     if (!ctx->havePrior) { ctx->err = "hmcmt_set_mass: hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
     if (kind != HMCMT_MASS_DIAGONAL && kind != HMCMT_MASS_WM) { ctx->err = "hmcmt_set_mass: kind must be HMCMT_MASS_DIAGONAL or HMCMT_MASS_WM"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the mass buffers)
     chain_release(ctx);                                     // (... and to the mass)
     ctx->mass.kind = HMCMT_MASS_DIAGONAL;
@@ -3274,7 +3220,7 @@ int hmcmt_mass_apply(hmcmt_ctx* ctx, int32_t op, const double* x, double* y, int
     if (!ctx || !x || !y) return HMCMT_EINVAL;
     if (!ctx->havePrior) { ctx->err = "hmcmt_mass_apply: hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
     if (op != HMCMT_MASS_OP_INV && op != HMCMT_MASS_OP_SQRT) { ctx->err = "hmcmt_mass_apply: op must be HMCMT_MASS_OP_INV or HMCMT_MASS_OP_SQRT"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const int n = ctx->v.nAC;
     int rc;
     if (ctx->mass.kind == HMCMT_MASS_DIAGONAL && !ctx->mass.d_in) {
@@ -3396,7 +3342,7 @@ int hmcmt_leapfrog_device(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, i
     if (L < 1 || !(dt > 0) || !(lnSigMax > lnSigMin)) { ctx->err = "need L >= 1, dt > 0, lnSigMax > lnSigMin"; return HMCMT_EINVAL; }
     if (start_grad < 0 || start_grad > 2) { ctx->err = "start_grad must be 0, 1 or 2"; return HMCMT_EINVAL; }
     if (start_grad != 0 && !ctx->lfHaveGrad) { ctx->err = "start_grad != 0 needs a previous trajectory on this context"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     int evals = 0;
     ctx->lfHaveGrad = false;
     int rc = leapfrog_core(ctx, d_m, d_p, dt, L, regParam, lnSigMin, lnSigMax, start_grad, d_pred, d_misfit, &evals);
@@ -3414,7 +3360,7 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
     if (!ctx || !m0 || !p0 || !m1 || !p1) return HMCMT_EINVAL;
     if (!ctx->havePrior) { ctx->err = "hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
     if (L < 1 || !(dt > 0) || !(lnSigMax > lnSigMin)) { ctx->err = "need L >= 1, dt > 0, lnSigMax > lnSigMin"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(m0[i]) || !std::isfinite(p0[i])) { ctx->err = "non-finite model or momentum"; return HMCMT_EBREAKDOWN; }

@@ -204,10 +204,10 @@ static void chain_cov_flush(hmcmt_ctx* ctx) {
 // ends the commit's optional accumulators (histogram, data moments, autocovariances, cross moments) and frees their buffers
 static void chain_acc_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
-    C.acov.timer.free(ctx->device, ctx->stream);
-    C.cov.timer.free(ctx->device, ctx->stream);
+    C.acov.timer.free(ctx->cfg.device, ctx->stream);
+    C.cov.timer.free(ctx->cfg.device, ctx->stream);
     if (!C.hist.allocs.empty() || !C.dmom.allocs.empty() || !C.acov.allocs.empty() || !C.cov.allocs.empty() || !C.adapt.allocs.empty()) {
-        hipSetDevice(ctx->device);
+        hipSetDevice(ctx->cfg.device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be counting)
     }
     chain_acc_free(C.hist.allocs); C.hist = {};
@@ -221,7 +221,7 @@ static void chain_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     chain_acc_release(ctx);
     if (!C.allocs.empty() || C.h_rec) {
-        hipSetDevice(ctx->device);
+        hipSetDevice(ctx->cfg.device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be running on the buffers)
         for (void* p : C.allocs) hipFree(p);
         if (C.h_rec) hipHostFree(C.h_rec);
@@ -308,7 +308,7 @@ int hmcmt_chain_begin(hmcmt_ctx* ctx, const double* m_start, double dt, double r
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(m_start[i])) { ctx->err = "hmcmt_chain_begin: non-finite start model"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& C = ctx->chain;
     // a begin on a context that holds a chain keeps that chain's buffers (their sizes belong to the context) and zeroes them
     const bool reuse = C.h_rec != nullptr;
@@ -373,7 +373,7 @@ int hmcmt_chain_momentum(hmcmt_ctx* ctx, const double* z, double* K) {
     const int n = ctx->v.nAC;
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(z[i])) { ctx->err = "hmcmt_chain_momentum: non-finite normal"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     hipStream_t st = ctx->stream;
     C.haveMomentum = false;
     std::memcpy(ctx->h_stage, z, sizeof(double) * n);
@@ -406,7 +406,7 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
     auto& C = ctx->chain;
     if (!C.haveMomentum) { ctx->err = "hmcmt_chain_step: no momentum since the last step (hmcmt_chain_momentum first)"; return HMCMT_EINVAL; }
     if (L < 1 || !std::isfinite(u)) { ctx->err = "hmcmt_chain_step: need L >= 1 and a finite u"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     hipStream_t st = ctx->stream;
     const int cur = C.cur, prop = cur ^ 1;
@@ -501,7 +501,7 @@ int hmcmt_chain_state(hmcmt_ctx* ctx, double* m_cur, double* p_cur, double* pred
     if (!ctx) return HMCMT_EINVAL;
     const int rc = chain_ready(ctx, "hmcmt_chain_state", true);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& C = ctx->chain;
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     hipStream_t st = ctx->stream;
@@ -516,7 +516,7 @@ int hmcmt_chain_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2
     if (!ctx) return HMCMT_EINVAL;
     int rc = chain_ready(ctx, "hmcmt_chain_moments", true);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& C = ctx->chain;
     if ((rc = chain_welford_out(ctx, sizeof(double) * ctx->v.nAC, C.d_mean, C.d_m2, mean, m2, on_device))) return rc;
     if (count) *count = C.nmoments;
@@ -533,7 +533,7 @@ int hmcmt_chain_hist_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* targe
     long long nt = 0;
     if ((rc = chain_cell_list(ctx, fn, "target", ntarget, target, false, restOk, "target, ntarget >= 1, 1 <= nbins <= 4096 and finite lo < hi", &nt)))
         return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& H = ctx->chain.hist;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be counting into the histogram this one replaces)
@@ -563,7 +563,7 @@ int hmcmt_chain_hist(hmcmt_ctx* ctx, int64_t* count, uint32_t* counts, int32_t o
     auto& H = ctx->chain.hist;
     const int rc = chain_acc_ready(ctx, "hmcmt_chain_hist", H.on, H.count, false, CHAIN_HIST);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     hipStream_t st = ctx->stream;
     const long long total = H.ntarget * H.nbins;
     if (counts && on_device) {
@@ -598,7 +598,7 @@ int hmcmt_chain_hist_quantiles(hmcmt_ctx* ctx, int32_t nq, const double* q, doub
     for (int i = 0; i < nq; ++i)
         if (!(q[i] >= 0.0 && q[i] <= 1.0)) { ctx->err = "hmcmt_chain_hist_quantiles: every q must lie in [0, 1]"; return HMCMT_EINVAL; }
     if ((rc = chain_acc_ready(ctx, fn, H.on, H.count, true, CHAIN_HIST))) return rc;      // (empty: reported behind the arguments)
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     hipStream_t st = ctx->stream;
     std::vector<double> x((size_t)nq);
     for (int i = 0; i < nq; ++i) x[i] = q[i] * (double)H.count;       // (one product: what a host restatement forms)
@@ -620,7 +620,7 @@ int hmcmt_chain_data_moments_begin(hmcmt_ctx* ctx) {
     if (!ctx) return HMCMT_EINVAL;
     int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& M = ctx->chain.dmom;
     hipStream_t st = ctx->stream;
     const size_t bytes = sizeof(double) * std::max<size_t>((size_t)2 * ctx->v.nData, 1);
@@ -640,7 +640,7 @@ int hmcmt_chain_data_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, doubl
     auto& M = ctx->chain.dmom;
     int rc = chain_acc_ready(ctx, "hmcmt_chain_data_moments", M.on, M.count, false, CHAIN_DMOM);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     if ((rc = chain_welford_out(ctx, sizeof(double) * 2 * ctx->v.nData, M.d_mean, M.d_m2, mean, m2, on_device))) return rc;
     if (count) *count = M.count;
     return 0;
@@ -656,11 +656,11 @@ int hmcmt_chain_acov_begin(hmcmt_ctx* ctx, int64_t ntarget, const int64_t* targe
     if ((rc = chain_cell_list(ctx, fn, "target", ntarget, target, true, maxlag >= 1 && maxlag <= CHAIN_ACOV_MAXLAG,
                               "target and ntarget >= 1 (or NULL and 0: every active cell) and 1 <= maxlag <= 1023", &nt)))
         return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& A = ctx->chain.acov;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be adding to the accumulator this one replaces)
-    A.timer.free(ctx->device, st);
+    A.timer.free(ctx->cfg.device, st);
     chain_acc_free(A.allocs); A = {};
     const size_t vb = (size_t)nt * sizeof(double), lb = vb * (size_t)(maxlag + 1);
     auto build = [&]() -> int {
@@ -696,7 +696,7 @@ int hmcmt_chain_acov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* acov,
     int rc = chain_acc_ready(ctx, fn, A.on, A.count, mean || acov, CHAIN_ACOV);
     if (rc) return rc;
     if (mean || acov) {
-        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipSetDevice(ctx->cfg.device));
         const size_t mb = sizeof(double) * (size_t)A.ntarget;
         ChainReadout R(ctx, fn, on_device);
         double *d_mean = (double*)R.out(mean, mb), *d_acov = (double*)R.out(acov, mb * (size_t)(A.K + 1));
@@ -715,7 +715,7 @@ int hmcmt_chain_ess(hmcmt_ctx* ctx, double* tau, double* ess, int32_t* window, i
     const int rc = chain_acc_ready(ctx, fn, A.on, A.count, true, CHAIN_ACOV);
     if (rc) return rc;
     if (!tau && !ess && !window) return 0;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const size_t mb = sizeof(double) * (size_t)A.ntarget;
     const double lg = std::max(1.0, std::log10((double)A.count));
     static_assert(sizeof(int) == sizeof(int32_t), "window is written as int");
@@ -735,7 +735,7 @@ static int chain_timer_report(hmcmt_ctx* ctx, const char* fn, bool on, const Cha
                               int64_t* launches) {
     const int rc = chain_acc_ready(ctx, fn, on, 0, false, name);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     T.report(ctx->stream, enable, ms, launches);
     return 0;
 }
@@ -755,11 +755,11 @@ int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* row, int3
     if ((rc = chain_cell_list(ctx, fn, "row", nrow, row, true, batch >= 0 && batch <= CHAIN_COV_BATCH_MAX,
                               "row and nrow >= 1 (or NULL and 0: every active cell) and 1 <= batch <= 16 (0: the default, 8)", &nr)))
         return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& V = ctx->chain.cov;
     hipStream_t st = ctx->stream;
     HIPCHK(hipStreamSynchronize(st));                        // (a commit may still be adding to the accumulator this one replaces)
-    V.timer.free(ctx->device, st);
+    V.timer.free(ctx->cfg.device, st);
     chain_acc_free(V.allocs); V = {};
     const int B = batch == 0 ? CHAIN_COV_BATCH_DEFAULT : batch;
     const size_t vb = (size_t)ctx->v.nAC * sizeof(double);
@@ -793,7 +793,7 @@ int hmcmt_chain_cov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* var, d
     int rc = chain_acc_ready(ctx, fn, V.on, V.count, mean || var || cov, CHAIN_COV);
     if (rc) return rc;
     if (mean || var || cov) {
-        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipSetDevice(ctx->cfg.device));
         const long long n = ctx->v.nAC;
         const size_t mb = sizeof(double) * (size_t)n;
         ChainReadout R(ctx, fn, on_device);
@@ -816,7 +816,7 @@ int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device) {
     const int rc = chain_acc_ready(ctx, fn, V.on, V.count, true, CHAIN_COV);
     if (rc) return rc;
     if (!corr) return 0;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     const long long n = ctx->v.nAC;
     ChainReadout R(ctx, fn, on_device);
     double* d_corr = (double*)R.out(corr, sizeof(double) * (size_t)n * (size_t)V.nrow);
@@ -859,7 +859,7 @@ int hmcmt_chain_set_mass_diag(hmcmt_ctx* ctx, const double* invM) {
     const int n = ctx->v.nAC;
     for (int i = 0; i < n; ++i)
         if (!(invM[i] > 0) || !std::isfinite(invM[i])) { ctx->err = std::string(fn) + ": every entry must be finite and > 0"; return HMCMT_EINVAL; }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     C.haveMomentum = false;                                  // (its K0 belongs to the old mass)
     std::memcpy(ctx->h_stage, invM, sizeof(double) * n);
     HIPCHK(hipMemcpyAsync(ctx->d_invM, ctx->h_stage, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -873,7 +873,7 @@ int hmcmt_chain_mass_diag(hmcmt_ctx* ctx, double* invM, int32_t on_device) {
     if (!invM) { ctx->err = std::string(fn) + ": invM is NULL"; return HMCMT_EINVAL; }
     const int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipMemcpyAsync(invM, ctx->d_invM, sizeof(double) * ctx->v.nAC, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -908,7 +908,7 @@ int hmcmt_chain_adapt_begin(hmcmt_ctx* ctx, const hmcmt_adapt_options* o) {
             return HMCMT_EINVAL;
         }
     }
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     auto& C = ctx->chain;
     auto& A = C.adapt;
     hipStream_t st = ctx->stream;

@@ -7,17 +7,12 @@
 // ----------------------------------------------------------------------------------------------
 // what the family shares
 // ----------------------------------------------------------------------------------------------
-template <class F>
-struct AtExit {
-    F f;
-    explicit AtExit(F g) : f(g) {}
-    AtExit(const AtExit&) = delete;
-    ~AtExit() { f(); }
-};
-
 // The bracket of a call that borrows the context.  Everything the call's evaluation and solves move in the host solve state --
 // hmcmt_ctx::SolveState, and View, Solver, options and statistics whole -- is saved in front and put back behind, on every way
-// out, so the context's next evaluation computes what it would have.  `st` collects the call's own statistics for the caller.
+// out, so the context's next evaluation computes what it would have.  The configuration needs no saving: hmcmt_ctx::cfg is const (a
+// block call's instance without sync words is seen by persist_fits, not written into it).  What remains loose in the context --
+// resources, counters, the per-evaluation protocol flags -- is left alone or reset below.  `st` collects the call's own
+// statistics for the caller.
 struct Borrowed {
     hmcmt_ctx* const ctx;
     hmcmt_stats* const stOut;
@@ -85,7 +80,7 @@ static void launch_post_forward(hmcmt_ctx* ctx, const View& vj) {
 }
 
 // sweeps per side of the family's solves (cold: well above the two-sweep threshold)
-static int cold_sweeps(const hmcmt_ctx* ctx) { return (ctx->sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2; }
+static int cold_sweeps(const hmcmt_ctx* ctx) { return (ctx->cfg.sweepsMode == 1 || !sweeps2_ok(ctx)) ? 1 : 2; }
 
 static int model_finite(hmcmt_ctx* ctx, const double* m) {
     for (int i = 0; i < ctx->v.nAC; ++i)
@@ -130,7 +125,7 @@ static int borrowed_solve(hmcmt_ctx* ctx, cplx* x, int kind, int sweeps, int spa
     const size_t vecBytes = (size_t)ctx->v.S * ctx->v.vstride * sizeof(cplx);
     for (int attempt = 0;; ++attempt) {
         HIPCHK(hipMemsetAsync(x, 0, vecBytes, strm));
-        const bool inKernelStart = ctx->psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 &&
+        const bool inKernelStart = ctx->cfg.psInKernelStart && ctx->opt.precond == HMCMT_PRECOND_FDM_JACOBI && ctx->opt.fdm_precision == 0 &&
                                    !ctx->opt.verify && persist_ok(ctx);
         fill(inKernelStart);
         ctx->sv.sweeps = sweeps;
@@ -306,7 +301,7 @@ extern "C" {
 int hmcmt_jacobian_device(hmcmt_ctx* ctx, const double* d_m, int64_t row0, int64_t nrows, int32_t wrt, double* d_J, hmcmt_stats* st) {
     if (!ctx) return HMCMT_EINVAL;
     if (int rc = jac_check(ctx, d_m, row0, nrows, wrt, d_J)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     if (int rc = jac_alloc(ctx)) return rc;
     return jac_run(ctx, d_m, row0, nrows, wrt, d_J, false, false, st);
 }
@@ -315,7 +310,7 @@ int hmcmt_jacobian(hmcmt_ctx* ctx, const double* m, int64_t row0, int64_t nrows,
     if (!ctx) return HMCMT_EINVAL;
     if (int rc = jac_check(ctx, m, row0, nrows, wrt, J)) return rc;
     if (int rc = model_finite(ctx, m)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     if (int rc = jac_alloc(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(ctx->jac.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
     return jac_run(ctx, ctx->jac.m, row0, nrows, wrt, J, true, false, st);
@@ -325,7 +320,7 @@ int hmcmt_sensitivity(hmcmt_ctx* ctx, const double* m, int32_t wrt, double* sens
     if (!ctx) return HMCMT_EINVAL;
     if (int rc = jac_check(ctx, m, 0, ctx->v.nData, wrt, sens)) return rc;
     if (int rc = model_finite(ctx, m)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     if (int rc = jac_alloc(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(ctx->jac.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
     int rc = jac_run(ctx, ctx->jac.m, 0, ctx->v.nData, wrt, nullptr, false, true, st);
@@ -409,7 +404,7 @@ int hmcmt_linearize(hmcmt_ctx* ctx, const double* m) {
     if (!ctx) return HMCMT_EINVAL;
     if (int rc = linearize_check(ctx, m)) return rc;
     if (int rc = model_finite(ctx, m)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     if (int rc = jvp_alloc(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(ctx->jvp.m, m, sizeof(double) * ctx->v.nAC, hipMemcpyHostToDevice, ctx->stream));
     return linearize_run(ctx);
@@ -417,7 +412,7 @@ int hmcmt_linearize(hmcmt_ctx* ctx, const double* m) {
 int hmcmt_linearize_device(hmcmt_ctx* ctx, const double* d_m) {
     if (!ctx) return HMCMT_EINVAL;
     if (int rc = linearize_check(ctx, d_m)) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     if (int rc = jvp_alloc(ctx)) return rc;
     HIPCHK(hipMemcpyAsync(ctx->jvp.m, d_m, sizeof(double) * ctx->v.nAC, hipMemcpyDeviceToDevice, ctx->stream));
     return linearize_run(ctx);
@@ -464,18 +459,18 @@ static int blk_alloc_impl(hmcmt_ctx* ctx, int nvec) {
     BA(B.dbcL, SV * v.nz) BA(B.dbcR, SV * v.nz) BA(B.dbcB, SV * (v.ny + 1)) BA(B.jv, K * v.nData) BA(B.u, K * v.nData) BA(B.vbar, K * v.nData) BA(B.rxCoef, SV * v.nRx)
     BA(B.srcB, SV * 4) BA(B.wL, SV * v.nz) BA(B.wR, SV * v.nz) BA(B.colw, SV * v.ny) BA(B.gL, SV * v.nz) BA(B.gR, SV * v.nz)
     k.omega = B.omega; k.invp = B.invp; k.invp32 = B.inst.d_invp32;
-    // the persistent kernel's own words for this instance (persist_setup): more system slots where the share has the CUs for them;
+    // the persistent kernel's own words for this instance (persist_alloc): more system slots where the share has the CUs for them;
     // its 32-bit lane offsets carry the system's element offset, so a block beyond 2^27 elements runs the launch-per-phase loop
-    if (ctx->persistCW > 0 && SV * VS < ((size_t)1 << 27)) {
+    if (ctx->cfg.persistCW > 0 && SV * VS < ((size_t)1 << 27)) {
         hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
-        const int cuPerXcd = prop.multiProcessorCount / 8 / std::max(ctx->shareCnt, 1);
-        B.slots = std::max(1, std::min((int)((SV + 7) / 8), cuPerXcd / std::max(ctx->persistG, 1)));
+        HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
+        const int cuPerXcd = prop.multiProcessorCount / 8 / std::max(ctx->cfg.shareCnt, 1);
+        B.slots = std::max(1, std::min((int)((SV + 7) / 8), cuPerXcd / std::max(ctx->cfg.persistG, 1)));
         B.inst.psyncBytes = ((size_t)(32 * 8 * B.slots + 16) * sizeof(unsigned) + 15) & ~(size_t)15;
         unsigned char* ps = nullptr; BA(ps, B.inst.psyncBytes) B.inst.d_psync = reinterpret_cast<unsigned*>(ps);
         unsigned char* pr = nullptr; BA(pr, SV * MAXNB * 2 * 8 * 16) B.inst.d_prec = reinterpret_cast<u4v*>(pr);
         unsigned char* pc = nullptr; BA(pc, sizeof(PsConst)) B.inst.d_psConst = reinterpret_cast<PsConst*>(pc);
-        if (ctx->persistCS > 1) BA(B.inst.d_yhat2, SV * VS)
+        if (ctx->cfg.persistCS > 1) BA(B.inst.d_yhat2, SV * VS)
     }
 #undef BA
     HIPCHK(hipHostMalloc((void**)&B.inst.h_rec, sizeof(double) * 4 * SV, hipHostMallocMapped));
@@ -533,8 +528,8 @@ static int blk_pivots(hmcmt_ctx* ctx, int nvec) {
 static void blk_enter(hmcmt_ctx* ctx, int nvec) {
     hmcmt_ctx::Blk& B = ctx->blk;
     std::swap(ctx->inst, B.inst);                        // (its psShadow / psConstValid come along, and go back with it: they survive between calls)
-    if (!ctx->inst.d_psync) ctx->persistCW = 0;          // (no sync words, no persistent kernel for this block: persist_ok)
-    else ctx->inst.persistSlots = std::max(1, std::min(B.slots, (nvec * ctx->v.S + 7) / 8));   // (words of the largest block seen, this call's count of systems)
+    // (no sync words: no persistent kernel for this block -- persist_fits)
+    if (ctx->inst.d_psync) ctx->inst.persistSlots = std::max(1, std::min(B.slots, (nvec * ctx->v.S + 7) / 8));   // (words of the largest block seen, this call's count of systems)
     ctx->inst.dinvValid = false;                         // (the instance's Jacobi diagonals: written where a launch-per-phase kernel needs them)
     ctx->ss.psOrder[0].clear(); ctx->ss.psOrder[1].clear();    // (the queue tables are the context's problem's: the kernel's own order here)
     ctx->sv = B.sv;
@@ -542,10 +537,7 @@ static void blk_enter(hmcmt_ctx* ctx, int nvec) {
     ctx->v.Lam = B.lam; ctx->v.R = B.sv.r;
     ctx->sv.S = ctx->v.S; ctx->sv.nFreq = ctx->v.nFreq;  // (arrays of the largest block seen, this call's count of systems)
 }
-static void blk_leave(hmcmt_ctx* ctx, int ownCW) {
-    std::swap(ctx->inst, ctx->blk.inst);
-    ctx->persistCW = ownCW;
-}
+static void blk_leave(hmcmt_ctx* ctx) { std::swap(ctx->inst, ctx->blk.inst); }
 
 // the directions k_dir_norm found not identically zero -> the system flags by direction and by virtual system, made on the device
 // (k_blk_flags); the host reads the flags by virtual system from mapped memory.  One synchronisation, no copy.
@@ -647,8 +639,7 @@ static int prod_run(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int 
     int nOn = ctx->ss.nSysOn;                            // (one direction: the systems that carry data)
     st.nsystems = !blockStats ? vr.S : nvec == 1 ? nOn : 0;
     // ... and for solve(): the context itself for one direction -- no second solver instance --, the block instance in its place
-    const int ownCW = ctx->persistCW;
-    AtExit instanceBack([&] { if (nvec > 1) blk_leave(ctx, ownCW); });
+    AtExit instanceBack([&] { if (nvec > 1) blk_leave(ctx); });
     if (nvec > 1) { blk_enter(ctx, nvec); vr.sysOn = B.sysOnDir; }
     if (nvec > 1) adjoint_arrays(vr, B, ctx->sv.r);
     else adjoint_arrays(vr, ctx->jac, ctx->sv.r);        // (one direction: the explicit Jacobian's arrays)
@@ -671,7 +662,7 @@ static int prod_run(hmcmt_ctx* ctx, int what, const double* d_in, int nvec, int 
 
 // (one direction allocates nothing: a context that only ever makes single products has no block arrays)
 static int prod_ready(hmcmt_ctx* ctx, int nvec) {
-    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->cfg.device));
     return nvec > 1 ? blk_alloc(ctx, nvec) : 0;
 }
 // host pointers: stage the input, run on the device buffers, bring the result back
