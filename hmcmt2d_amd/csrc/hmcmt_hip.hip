@@ -265,6 +265,11 @@ struct hmcmt_ctx {
         double *d_in = nullptr, *d_out = nullptr;         // [nAC] staging of hmcmt_mass_apply / PCG solution
         double *d_r = nullptr, *d_z = nullptr, *d_pp = nullptr, *d_q = nullptr, *d_s = nullptr;   // PCG vectors, scalars [8]
         int* d_map = nullptr;                             // [nzb*nyb] active index of each box cell, -1 frozen
+        // HMCMT_MASS_LOWRANK (hmcmt_set_mass_lowrank): buffers of their own, released by mass_lr_release; d_x, d_in, d_out are shared
+        int lrRank = 0;
+        double *d_lrS = nullptr, *d_lrU = nullptr;        // [nAC] s = sqrt(invM), [rank][nAC]
+        double *d_lrC = nullptr;                          // [2][rank] lambda - 1, lambda^-1/2 - 1
+        double *d_lrPart = nullptr;                       // [rank][LFNB] partial sums of the projection
     } mass;
     // the device-resident HMC chain (hmcmt_chain_*, host_chain.h, kernels_chain.h)
     long long stateGen = 0;               // counts the evaluations and option changes of the context: a chain compares it with the value it left
@@ -2913,8 +2918,25 @@ int hmcmt_debug_back_post(hmcmt_ctx* ctx, const double* y, const double* r, doub
 constexpr int MASS_PCG_MAXIT = 1000;
 constexpr double MASS_PCG_TOL = 1e-13;
 
+// the buffers of the low-rank mass alone (a Wm factor stays)
+static void mass_lr_free(hmcmt_ctx* ctx, std::initializer_list<void*> bufs) {
+    for (void* old : bufs) {
+        if (!old) continue;
+        auto it = std::find(ctx->allocs.begin(), ctx->allocs.end(), old);
+        if (it != ctx->allocs.end()) ctx->allocs.erase(it);
+        hipFree(old);
+    }
+}
+static void mass_lr_release(hmcmt_ctx* ctx) {
+    auto& M = ctx->mass;
+    mass_lr_free(ctx, {M.d_lrS, M.d_lrU, M.d_lrC, M.d_lrPart});
+    M.d_lrS = M.d_lrU = M.d_lrC = M.d_lrPart = nullptr;
+    M.lrRank = 0;
+}
+
 static void mass_release(hmcmt_ctx* ctx) {
     auto& M = ctx->mass;
+    mass_lr_release(ctx);
     for (void* old : {(void*)M.d_L, (void*)M.d_Qz, (void*)M.d_QzT, (void*)M.d_Qy, (void*)M.d_QyT, (void*)M.d_lz, (void*)M.d_ly,
                       (void*)M.d_T1, (void*)M.d_T2, (void*)M.d_x, (void*)M.d_in, (void*)M.d_out, (void*)M.d_r, (void*)M.d_z,
                       (void*)M.d_pp, (void*)M.d_q, (void*)M.d_s, (void*)M.d_map}) {
@@ -3140,6 +3162,12 @@ static int mass_apply_dev(hmcmt_ctx* ctx, int op, const double* x, double* y) {
         hipLaunchKernelGGL(k_mass_diag, dim3((n + 255) / 256), dim3(256), 0, st, n, ctx->d_invM, x, y, op);
         return 0;
     }
+    if (M.kind == HMCMT_MASS_LOWRANK) {
+        const MassLr m{n, M.lrRank, op, M.d_lrS, M.d_lrU, M.d_lrC + (op == HMCMT_MASS_OP_INV ? 0 : M.lrRank), M.d_lrPart};
+        hipLaunchKernelGGL(k_mass_lr_project, dim3(LFNB), dim3(256), 0, st, m, x);
+        hipLaunchKernelGGL(k_mass_lr_expand, dim3(LFNB), dim3(256), 0, st, m, x, y);
+        return 0;
+    }
     if (op == HMCMT_MASS_OP_SQRT) {
         double* out = (x == y) ? M.d_out : y;
         hipLaunchKernelGGL(k_mass_lmul, dim3((n + 3) / 4), dim3(256), 0, st, n, M.bw, M.d_L, x, out);
@@ -3164,6 +3192,8 @@ int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, c
     int rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the previous prior)
     chain_release(ctx);                                     // (a chain belongs to the prior it began with)
+    mass_lr_release(ctx);                                   // (... and so does a low-rank mass: its scales default to this prior's invM)
+    if (ctx->mass.kind == HMCMT_MASS_LOWRANK) ctx->mass.kind = HMCMT_MASS_DIAGONAL;
     // a repeated call replaces the previous prior: its buffers are released, not kept until hmcmt_destroy
     for (void* old : {(void*)ctx->d_mref, (void*)ctx->d_invM, (void*)ctx->d_wmVal, (void*)ctx->d_wmRow, (void*)ctx->d_wmCol}) {
         if (!old) continue;
@@ -3201,11 +3231,16 @@ int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, c
 int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
     if (!ctx) return HMCMT_EINVAL;
     if (!ctx->havePrior) { ctx->err = "hmcmt_set_mass: hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
-    if (kind != HMCMT_MASS_DIAGONAL && kind != HMCMT_MASS_WM) { ctx->err = "hmcmt_set_mass: kind must be HMCMT_MASS_DIAGONAL or HMCMT_MASS_WM"; return HMCMT_EINVAL; }
+    if (kind != HMCMT_MASS_DIAGONAL && kind != HMCMT_MASS_WM) {
+        ctx->err = kind == HMCMT_MASS_LOWRANK ? "hmcmt_set_mass: HMCMT_MASS_LOWRANK is set by hmcmt_set_mass_lowrank, which takes its scales and directions"
+                                              : "hmcmt_set_mass: kind must be HMCMT_MASS_DIAGONAL or HMCMT_MASS_WM";
+        return HMCMT_EINVAL;
+    }
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the mass buffers)
     chain_release(ctx);                                     // (... and to the mass)
     ctx->mass.kind = HMCMT_MASS_DIAGONAL;
+    mass_lr_release(ctx);
     if (kind == HMCMT_MASS_DIAGONAL) return 0;
     auto& M = ctx->mass;
     if (!(M.ready && M.keyRow == ctx->wmRowH && M.keyCol == ctx->wmColH && M.keyVal == ctx->wmValH)) {
@@ -3213,6 +3248,99 @@ int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
         if (rc) { mass_release(ctx); return rc; }
     }
     M.kind = HMCMT_MASS_WM;
+    return 0;
+}
+
+// uploads s, U, the two coefficient rows and checks U'U = I with the projection kernel: row j of U projected onto every row
+static int mass_lr_build(hmcmt_ctx* ctx, int rank, const std::vector<double>& s, const double* U, const std::vector<double>& c,
+                         double** d_s, double** d_U, double** d_c, double** d_part, double* defect) {
+    const int n = ctx->v.nAC;
+    hipStream_t st = ctx->stream;
+    int rc;
+    if ((rc = dupload(ctx, d_s, s))) return rc;
+    if ((rc = dalloc(ctx, d_U, (size_t)rank * n, false))) return rc;
+    HIPCHK(hipMemcpy(*d_U, U, sizeof(double) * rank * n, hipMemcpyHostToDevice));
+    if ((rc = dupload(ctx, d_c, c))) return rc;
+    if ((rc = dalloc(ctx, d_part, (size_t)rank * LFNB))) return rc;
+    for (double** p : {&ctx->mass.d_x, &ctx->mass.d_in, &ctx->mass.d_out})
+        if (!*p && (rc = dalloc(ctx, p, (size_t)n))) return rc;
+    std::vector<double> part((size_t)rank * rank * LFNB);
+    const MassLr m{n, rank, HMCMT_MASS_OP_SQRT, *d_s, *d_U, *d_c, *d_part};
+    for (int j = 0; j < rank; ++j) {
+        hipLaunchKernelGGL(k_mass_lr_project, dim3(LFNB), dim3(256), 0, st, m, *d_U + (size_t)j * n);
+        HIPCHK(hipMemcpyAsync(&part[(size_t)j * rank * LFNB], *d_part, sizeof(double) * rank * LFNB, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    double worst = 0.0;
+    for (int j = 0; j < rank; ++j)
+        for (int k = 0; k < rank; ++k) {
+            const double g = item_chain_total(&part[((size_t)j * rank + k) * LFNB]) - (j == k ? 1.0 : 0.0);
+            worst = std::isfinite(g) ? std::max(worst, std::fabs(g)) : INFINITY;
+        }
+    *defect = worst;
+    return 0;
+}
+
+int hmcmt_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, const double* U, const double* lambda) {
+    const char* fn = "hmcmt_set_mass_lowrank";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!ctx->havePrior) { ctx->err = std::string(fn) + ": hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
+    if (!U || !lambda) { ctx->err = std::string(fn) + (!U ? ": U is NULL" : ": lambda is NULL"); return HMCMT_EINVAL; }
+    if (rank < 1 || rank > HMCMT_MASS_RANK_MAX) {
+        ctx->err = std::string(fn) + ": rank " + std::to_string(rank) + " is outside 1 .. HMCMT_MASS_RANK_MAX = " + std::to_string(HMCMT_MASS_RANK_MAX);
+        return HMCMT_EINVAL;
+    }
+    const int n = ctx->v.nAC;
+    std::vector<double> s((size_t)n), c((size_t)2 * rank);
+    for (int k = 0; k < rank; ++k) {
+        if (!std::isfinite(lambda[k]) || !(lambda[k] > 0.0)) {
+            ctx->err = std::string(fn) + ": lambda[" + std::to_string(k) + "] is not finite and positive";
+            return HMCMT_EINVAL;
+        }
+        c[k] = lambda[k] - 1.0;
+        c[rank + k] = 1.0 / std::sqrt(lambda[k]) - 1.0;
+    }
+    for (size_t i = 0; i < (size_t)rank * n; ++i)
+        if (!std::isfinite(U[i])) {
+            ctx->err = std::string(fn) + ": U[" + std::to_string(i / n) + "][" + std::to_string(i % n) + "] is not finite";
+            return HMCMT_EINVAL;
+        }
+    if (invM)
+        for (int a = 0; a < n; ++a) s[a] = invM[a];
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the mass buffers)
+    if (!invM) HIPCHK(hipMemcpy(s.data(), ctx->d_invM, sizeof(double) * n, hipMemcpyDeviceToHost));   // (the diagonal in force)
+    for (int a = 0; a < n; ++a) {
+        if (!std::isfinite(s[a]) || !(s[a] > 0.0)) {
+            ctx->err = std::string(fn) + ": invM[" + std::to_string(a) + "] is not finite and positive";
+            return HMCMT_EINVAL;
+        }
+        s[a] = std::sqrt(s[a]);
+    }
+    auto& M = ctx->mass;
+    double *d_s = nullptr, *d_U = nullptr, *d_c = nullptr, *d_part = nullptr, defect = 0.0;
+    const int rc = mass_lr_build(ctx, rank, s, U, c, &d_s, &d_U, &d_c, &d_part, &defect);
+    if (rc || !(defect <= 1e-8)) {
+        const std::string e = ctx->err;
+        mass_lr_free(ctx, {d_s, d_U, d_c, d_part});
+        if (rc) {                                           // (out of memory: the context is left on the diagonal mass)
+            chain_release(ctx);
+            mass_lr_release(ctx);
+            M.kind = HMCMT_MASS_DIAGONAL;
+            ctx->err = e;
+            return rc;
+        }
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%.3e", defect);
+        ctx->err = std::string(fn) + ": the rows of U are not orthonormal (max |U'U - I| = " + buf + " > 1e-8)";
+        return HMCMT_EINVAL;                                // (nothing has changed: the mass and a running chain stay)
+    }
+    chain_release(ctx);                                     // (a chain belongs to the mass it began with)
+    mass_lr_release(ctx);
+    M.d_lrS = d_s; M.d_lrU = d_U; M.d_lrC = d_c; M.d_lrPart = d_part;
+    M.lrRank = rank;
+    M.kind = HMCMT_MASS_LOWRANK;
     return 0;
 }
 
@@ -3246,7 +3374,8 @@ int hmcmt_mass_info(const hmcmt_ctx* ctx, double* out) {
     const auto& M = ctx->mass;
     const double v[HMCMT_MASS_INFO_FIELDS] = {(double)M.kind, M.factorSec, (double)M.bw, (double)M.separable, (double)M.pcgIters,
                                               (double)M.nzb, (double)M.nyb};
-    for (int i = 0; i < HMCMT_MASS_INFO_FIELDS; ++i) out[i] = v[i];
+    // (the fields behind the kind describe the Wm factor: 0 under HMCMT_MASS_LOWRANK, also while a factor is kept)
+    for (int i = 0; i < HMCMT_MASS_INFO_FIELDS; ++i) out[i] = (i > 0 && M.kind == HMCMT_MASS_LOWRANK) ? 0.0 : v[i];
     return 0;
 }
 
@@ -3279,9 +3408,10 @@ static int leapfrog_core(hmcmt_ctx* ctx, double* d_m, double* d_p, double dt, in
     // M = Wm (hmcmt_set_mass): x = Wm^-1 p after every momentum update, the step bound and the position update read x.  The
     // position and momentum updates are then launches of their own (k_mass_step in front of the evaluation, k_lf_momentum_max
     // behind it); the fused forms of the diagonal mass stay as they are.
-    const bool wm = ctx->mass.kind == HMCMT_MASS_WM;
+    // The low-rank mass (hmcmt_set_mass_lowrank) takes the same route with x = M^-1 p from its two kernels, everything enqueued.
+    const bool wm = ctx->mass.kind != HMCMT_MASS_DIAGONAL;
     auto mass_x_bound = [&]() -> int {
-        if (!ctx->mass.separable) {            // (PCG synchronises: the records of the evaluation in flight are read first)
+        if (ctx->mass.kind == HMCMT_MASS_WM && !ctx->mass.separable) {   // (PCG synchronises: the records of the evaluation in flight are read first)
             const int r = collect_pending(ctx);
             if (r) return r;
         }

@@ -1104,6 +1104,34 @@ HD void item_chain_corr(const double* tot, const double* q, const double* S, con
     corr[r * n + a] = c;
 }
 
+// ----------------------------------------------------------------------------------------------
+// the low-rank-plus-diagonal mass (hmcmt_set_mass_lowrank, kernels_mass.h: k_mass_lr_project, k_mass_lr_expand)
+// ----------------------------------------------------------------------------------------------
+// M^-1 = S (I + U (Lambda - I) U') S,  M = F F',  F = S^-1 (I + U (Lambda^-1/2 - I) U');  S = diag(s), U [rank][n] direction-contiguous.
+// One application is y = post .* (x' + U' (c .* (U x'))): x' = s .* x, post = s, c = lambda - 1 for M^-1 x; x' = x, post = 1 / s,
+// c = lambda^-1/2 - 1 for F x.  The projection t = U x' is reduced in a fixed order: a thread walks its cells upwards with fma, the
+// 64 lanes of a wave add up in wave_sum's tree, the four waves as item_mass_lr_block, the CHAIN_NB workgroups in index order.
+constexpr int MASS_LR_RANK_MAX = 32;
+constexpr int MASS_LR_CHUNK = 8;       // directions a thread accumulates side by side (registers, indexed at compile time)
+// x'[a]: op 0 (M^-1 x) scales by s, op 1 (F x) does not
+HD double item_mass_lr_pre(const double* s, const double* x, int op, long long a) { return op == 0 ? s[a] * x[a] : x[a]; }
+// cell a's terms of the projections k0 .. k0 + nk - 1 (nk <= MASS_LR_CHUNK) onto acc[0 .. MASS_LR_CHUNK)
+HD void item_mass_lr_acc(const double* U, long long n, int k0, int nk, double xp, long long a, double (&acc)[MASS_LR_CHUNK]) {
+#pragma unroll
+    for (int q = 0; q < MASS_LR_CHUNK; ++q)
+        if (q < nk) acc[q] = fma(U[(long long)(k0 + q) * n + a], xp, acc[q]);
+}
+// a workgroup's partial sum from its four waves' sums
+HD double item_mass_lr_block(double w0, double w1, double w2, double w3) { return (w0 + w1) + (w2 + w3); }
+// w_k = c_k t_k, t_k the workgroups' partial sums in index order
+HD double item_mass_lr_weight(const double* part, const double* c, int k) { return c[k] * item_chain_total(part + (long long)k * CHAIN_NB); }
+// y[a] = post[a] (x'[a] + sum_k U[k][a] w_k), k upwards
+HD double item_mass_lr_expand(const double* s, const double* x, const double* U, const double* w, long long n, int rank, int op, long long a) {
+    double acc = item_mass_lr_pre(s, x, op, a);
+    for (int k = 0; k < rank; ++k) acc = fma(U[(long long)k * n + a], w[k], acc);
+    return op == 0 ? s[a] * acc : acc / s[a];
+}
+
 
 // ---- initial guess extrapolated along the model path (kernels_fused.h: k_extrap_prepare, k_extrap) ----
 #if !defined(__HIPCC__)

@@ -378,8 +378,8 @@ int hmcmt_chain_momentum(hmcmt_ctx* ctx, const double* z, double* K) {
     C.haveMomentum = false;
     std::memcpy(ctx->h_stage, z, sizeof(double) * n);
     HIPCHK(hipMemcpyAsync(C.d_z, ctx->h_stage, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    if (ctx->mass.kind == HMCMT_MASS_WM) {
-        // p = L clip(z), x = Wm^-1 p, K = 0.5 p'x
+    if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) {
+        // p = L clip(z), x = Wm^-1 p, K = 0.5 p'x (HMCMT_MASS_LOWRANK: p = F clip(z), x = M^-1 p)
         hipLaunchKernelGGL(k_chain_clip, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_z, C.d_p);
         if ((rc = mass_apply_dev(ctx, HMCMT_MASS_OP_SQRT, C.d_p, C.d_p))) return rc;
         if ((rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, C.d_p, ctx->mass.d_x))) return rc;
@@ -419,7 +419,7 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
     int evals = 0;
     rc = leapfrog_core(ctx, C.d_m[prop], C.d_p, C.dt, L, C.regParam, C.lo, C.hi, startGrad, C.d_pred[prop], C.d_scal + CH_D1, &evals);
     if (rc) return chain_fail(ctx, rc);
-    const bool wm = ctx->mass.kind == HMCMT_MASS_WM;
+    const bool wm = ctx->mass.kind != HMCMT_MASS_DIAGONAL;
     if (wm && (rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, C.d_p, ctx->mass.d_x))) return chain_fail(ctx, rc);
     hipLaunchKernelGGL(k_chain_kinetic, dim3(LFNB), dim3(256), 0, st, n, C.d_p, wm ? ctx->mass.d_x : nullptr, ctx->d_invM, C.d_part + LFNB);
     hipLaunchKernelGGL(k_chain_final, dim3(1), dim3(1), 0, st, C.d_part, C.d_part + LFNB, ctx->d_lfScal, ctx->d_lfFlag, C.d_scal);
@@ -851,7 +851,10 @@ int hmcmt_chain_set_mass_diag(hmcmt_ctx* ctx, const double* invM) {
     const int rc = chain_ready(ctx, fn, true);
     if (rc) return rc;
     auto& C = ctx->chain;
-    if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) { ctx->err = std::string(fn) + ": the mass is HMCMT_MASS_WM, which has no diagonal to set"; return HMCMT_EINVAL; }
+    if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) { 
+        ctx->err = std::string(fn) + ": the mass is " + (ctx->mass.kind == HMCMT_MASS_WM ? "HMCMT_MASS_WM" : "HMCMT_MASS_LOWRANK") + ", which has no diagonal to set";
+        return HMCMT_EINVAL;
+    }
     if (C.adapt.active && C.adapt.opt.adapt_mass) {
         ctx->err = std::string(fn) + ": an adaptation of the mass is active (hmcmt_chain_adapt_end first)";
         return HMCMT_EINVAL;

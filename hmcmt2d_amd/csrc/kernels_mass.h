@@ -165,3 +165,50 @@ __global__ void k_mass_diag(int n, const double* __restrict__ invM, const double
     if (a >= n) return;
     y[a] = op == 0 ? invM[a] * x[a] : x[a] / sqrt(invM[a]);
 }
+
+// ---- the low-rank-plus-diagonal mass (hmcmt_set_mass_lowrank): M^-1 = S (I + U (Lambda - I) U') S, M = F F' with
+// F = S^-1 (I + U (Lambda^-1/2 - I) U'); arithmetic and its order in hmcmt_items.h (item_mass_lr_*).  Two launches per application,
+// no atomics: every partial sum and every output has one owner, so the bits repeat.  x and y may be the same vector (thread a reads
+// x[a] before it writes y[a], and the projection is complete before the expansion starts) -- hence no __restrict__ on them.
+struct MassLr {
+    int n, rank, op;               // op: HMCMT_MASS_OP_INV (x' = s x, post = s) or HMCMT_MASS_OP_SQRT (x' = x, post = 1 / s)
+    const double* s;               // [n]
+    const double* U;               // [rank][n]
+    const double* c;               // [rank] lambda - 1 (INV) or lambda^-1/2 - 1 (SQRT)
+    double* part;                  // [rank][LFNB] partial sums of U x'
+};
+static_assert(MASS_LR_RANK_MAX == HMCMT_MASS_RANK_MAX && MASS_LR_RANK_MAX % MASS_LR_CHUNK == 0 && MASS_LR_RANK_MAX <= 256,
+              "the projection walks the directions in whole chunks; one thread per direction forms the weights");
+// part[k][block] = this workgroup's share of sum_a U[k][a] x'[a]: lanes walk a (U[k][.] is contiguous), MASS_LR_CHUNK directions per
+// pass over the cells so that the accumulators stay in registers
+__global__ __launch_bounds__(256) void k_mass_lr_project(MassLr m, const double* x) {
+    __shared__ double sh[4][MASS_LR_RANK_MAX];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k0 = 0; k0 < m.rank; k0 += MASS_LR_CHUNK) {
+        const int nk = min(MASS_LR_CHUNK, m.rank - k0);
+        double acc[MASS_LR_CHUNK];
+#pragma unroll
+        for (int q = 0; q < MASS_LR_CHUNK; ++q) acc[q] = 0.0;
+        for (int a = blockIdx.x * 256 + threadIdx.x; a < m.n; a += 256 * LFNB)
+            item_mass_lr_acc(m.U, m.n, k0, nk, item_mass_lr_pre(m.s, x, m.op, a), a, acc);
+#pragma unroll
+        for (int q = 0; q < MASS_LR_CHUNK; ++q) {
+            const double t = wave_sum(acc[q]);
+            if (lane == 0) sh[wave][k0 + q] = t;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < m.rank) {
+        const int k = threadIdx.x;
+        m.part[k * LFNB + blockIdx.x] = item_mass_lr_block(sh[0][k], sh[1][k], sh[2][k], sh[3][k]);
+    }
+}
+// y[a] = post[a] (x'[a] + sum_k U[k][a] w_k), w_k = c_k sum_b part[k][b]: every workgroup forms the rank weights itself (rank * LFNB
+// loads, the sums in index order), then walks its cells
+__global__ __launch_bounds__(256) void k_mass_lr_expand(MassLr m, const double* x, double* y) {
+    __shared__ double w[MASS_LR_RANK_MAX];
+    if (threadIdx.x < m.rank) w[threadIdx.x] = item_mass_lr_weight(m.part, m.c, threadIdx.x);
+    __syncthreads();
+    for (int a = blockIdx.x * 256 + threadIdx.x; a < m.n; a += 256 * LFNB)
+        y[a] = item_mass_lr_expand(m.s, x, m.U, w, m.n, m.rank, m.op, a);
+}

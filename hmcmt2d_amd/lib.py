@@ -30,7 +30,8 @@ def _warm_start_code(v):
         return 2 if v else 0
     return {"cold": 0, "previous": 1, "extrapolate": 2, 0: 0, 1: 1, 2: 2}[v]
 # include/hmcmt.h: hmcmt_set_mass kinds and hmcmt_mass_apply operations
-HMCMT_MASS_DIAGONAL, HMCMT_MASS_WM = 0, 1
+HMCMT_MASS_DIAGONAL, HMCMT_MASS_WM, HMCMT_MASS_LOWRANK = 0, 1, 2
+HMCMT_MASS_RANK_MAX = 32   # directions of hmcmt_set_mass_lowrank
 HMCMT_MASS_OP_INV, HMCMT_MASS_OP_SQRT = 0, 1
 ERRORS = {-1: "EINVAL", -2: "ENODEV", -3: "EHIP", -10: "ENOCONV", -11: "EBREAKDOWN", -13: "ENOMEM"}
 
@@ -126,6 +127,7 @@ def load_library():
                                           vp, vp, vp, C.POINTER(C.c_int32)]
     lib.hmcmt_get_fields.argtypes = [vp, C.c_int32, c_double_p, c_double_p]
     lib.hmcmt_set_mass.argtypes = [vp, C.c_int32]
+    lib.hmcmt_set_mass_lowrank.argtypes = [vp, c_double_p, C.c_int32, c_double_p, c_double_p]
     lib.hmcmt_mass_apply.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
     lib.hmcmt_mass_info.argtypes = [vp, c_double_p]
     lib.hmcmt_profile.argtypes = [vp, C.c_int32]
@@ -208,7 +210,7 @@ def load_library():
         getattr(lib, name).restype = C.c_int
     for name in ("hmcmt_create", "hmcmt_destroy", "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters",
                  "hmcmt_grad", "hmcmt_forward", "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async",
-                 "hmcmt_wait", "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_mass_info", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead",
+                 "hmcmt_wait", "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_mass_info", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields", "hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "hmcmt_profile_counters", "hmcmt_profile_overhead",
                  "hmcmt_dims", "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond",
                  "hmcmt_debug_fdm_fwd", "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_guard", "hmcmt_debug_hog", "hmcmt_next_cu_share", "hmcmt_persist_envelope", "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack",
                  "hmcmt_jacobian", "hmcmt_jacobian_device", "hmcmt_sensitivity"):
@@ -244,7 +246,7 @@ ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", 
 PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
-                   "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
+                   "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
                    "hmcmt_guard", "hmcmt_next_cu_share", "hmcmt_jacobian", "hmcmt_jacobian_device", "hmcmt_sensitivity",
                    "hmcmt_comm_id", "hmcmt_comm_create", "hmcmt_allgather_samples", "hmcmt_comm_destroy", "hmcmt_comm_last_error"]
 # include/hmcmt_debug.h: instrumentation, introspection of the persistent kernel, test hooks
@@ -258,6 +260,22 @@ EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 def _dp(a):
     return a.ctypes.data_as(c_double_p)
+
+
+def lowrank_mass_arrays(nAC, invM, U, lam):
+    """The arguments of HipContext.set_mass_lowrank as contiguous float64 arrays; ValueError for a wrong shape (the values are the
+    library's to judge, a rank outside 1 .. HMCMT_MASS_RANK_MAX included)."""
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    if U.ndim != 2 or U.shape[1] != nAC:
+        raise ValueError(f"U must be [rank, nAC = {nAC}], C-ordered; got shape {U.shape}")
+    if lam.shape != (U.shape[0],):
+        raise ValueError(f"lam must have one entry per row of U ({U.shape[0]}); got shape {lam.shape}")
+    if invM is not None:
+        invM = np.ascontiguousarray(invM, dtype=np.float64)
+        if invM.shape != (nAC,):
+            raise ValueError(f"invM must have nAC = {nAC} entries; got shape {invM.shape}")
+    return invM, U, lam
 
 
 class SampleComm:
@@ -619,8 +637,16 @@ class HipContext:
         after set_prior, which returns to the diagonal kind."""
         self._check(self.lib.hmcmt_set_mass(self.h, int(kind)))
 
+    def set_mass_lowrank(self, invM, U, lam):
+        """hmcmt_set_mass_lowrank: M^-1 = S (I + U' (diag(lam) - I) U) S with S = diag(sqrt(invM)).  invM [nAC] or None (the
+        diagonal in force), U [rank, nAC] C-ordered with orthonormal rows, lam [rank] > 0; 1 <= rank <= HMCMT_MASS_RANK_MAX.
+        Ends a running chain, as set_mass does."""
+        invM, U, lam = lowrank_mass_arrays(self.nAC, invM, U, lam)
+        self._check(self.lib.hmcmt_set_mass_lowrank(self.h, None if invM is None else _dp(invM), int(U.shape[0]), _dp(U), _dp(lam)))
+
     def mass_apply(self, op, x):
-        """hmcmt_mass_apply on a host vector: M^-1 x (HMCMT_MASS_OP_INV) or L x (HMCMT_MASS_OP_SQRT)."""
+        """hmcmt_mass_apply on a host vector: M^-1 x (HMCMT_MASS_OP_INV) or L x (HMCMT_MASS_OP_SQRT; F x under
+        HMCMT_MASS_LOWRANK)."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.shape != (self.nAC,):
             raise ValueError("vector has the wrong length")

@@ -620,6 +620,38 @@ def mergeCov(list_of_cov):
 ADAPT_KEYS = ("nwarmup", "mass", "delta", "gamma", "t0", "kappa", "init_buffer", "term_buffer", "base_window", "dt_min", "dt_max")
 
 
+def lowRankMassFromSamples(samples, rank=8, cutoff=2.0, invM=None):
+    """(invM[nparam], U[r, nparam], lam[r]) of the low-rank-plus-diagonal mass M^-1 = S (I + U' (diag(lam) - I) U) S, S = diag(sqrt(invM)),
+    estimated from samples[nparam, N] (columns = models, N >= 2) -- the arguments of HipContext.set_mass_lowrank and of
+    runHMCSampler(mass_lowrank=...), U with one direction per ROW.  The scales are `invM` where given, else the library's own window
+    rule (hmcmt_chain_adapt_begin, step 4): var N / (N + 5) + 1e-3 * 5 / (N + 5) with the unbiased sample variance.  The directions
+    are the principal ones of the scaled, centred samples Z = (samples - mean) / s / sqrt(N - 1): the eigenpairs of the N x N matrix
+    Z'Z lifted to U = Z v / sigma, lam = sigma^2 the variance along the direction in units of the scales.  At most `rank` pairs with
+    lam > cutoff are kept, largest first -- r may be 0; each direction's entry of largest magnitude is positive.  Needs no device."""
+    X = np.asarray(samples, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] < 2:
+        raise ValueError("lowRankMassFromSamples: samples must be [nparam, N] with N >= 2")
+    if int(rank) < 0:
+        raise ValueError("lowRankMassFromSamples: rank must not be negative")
+    nparam, N = X.shape
+    mean = X.mean(axis=1)
+    if invM is None:
+        s2 = X.var(axis=1, ddof=1) * (N / (N + 5.0)) + 1e-3 * 5.0 / (N + 5.0)
+    else:
+        s2 = np.array(invM, dtype=np.float64)
+        if s2.shape != (nparam,) or not (np.isfinite(s2).all() and (s2 > 0).all()):
+            raise ValueError(f"lowRankMassFromSamples: invM must hold {nparam} finite positive entries")
+    Z = (X - mean[:, None]) / np.sqrt(s2)[:, None] / np.sqrt(N - 1.0)
+    w, v = np.linalg.eigh(Z.T @ Z)                          # (ascending)
+    keep = [i for i in np.argsort(w)[::-1] if w[i] > cutoff][:int(rank)]
+    lam = w[keep]
+    U = np.ascontiguousarray(((Z @ v[:, keep]) / np.sqrt(lam)).T)
+    for k in range(len(keep)):
+        if U[k, np.argmax(np.abs(U[k]))] < 0:
+            U[k] = -U[k]
+    return s2, U, lam
+
+
 def adaptPlan(adapt, hmcprior):
     """(nwarmup, options of HipContext.chain_adapt_begin) of runHMCSampler's adapt={...}; needs no device.  nwarmup defaults to
     hmcprior.burninsamples and may not exceed it: the posterior moments would mix in warm-up samples.  mass defaults to True for
@@ -790,6 +822,24 @@ class _WarmUp(ChainOutput):
 CHAIN_OUTPUTS = (_Histograms(), _DataMoments(), _EffectiveSampleSize(), _Covariance(), _WarmUp())
 
 
+def _check_mass_lowrank(mass_lowrank, nparam):
+    """runHMCSampler's mass_lowrank=(invM, U, lam) -> (invM, (invM, U, lam) or None when U has no row): shapes and values checked
+    here, before the context is touched"""
+    from .lib import HMCMT_MASS_RANK_MAX, lowrank_mass_arrays
+    try:
+        invM, U, lam = mass_lowrank
+    except (TypeError, ValueError):
+        raise ValueError("runHMCSampler: mass_lowrank must be (invM, U, lam)") from None
+    if invM is None:
+        raise ValueError("runHMCSampler: mass_lowrank needs its invM (the scales)")
+    invM, U, lam = lowrank_mass_arrays(nparam, invM, U, lam)
+    if U.shape[0] > HMCMT_MASS_RANK_MAX:
+        raise ValueError(f"runHMCSampler: mass_lowrank has {U.shape[0]} directions, more than HMCMT_MASS_RANK_MAX = {HMCMT_MASS_RANK_MAX}")
+    if not (np.isfinite(invM).all() and (invM > 0).all() and np.isfinite(lam).all() and (lam > 0).all() and np.isfinite(U).all()):
+        raise ValueError("runHMCSampler: mass_lowrank needs finite positive invM and lam and a finite U")
+    return invM, ((invM, U, lam) if U.shape[0] else None)
+
+
 def _homogeneous_start(invParam, rhoref, rng, verbose):
     """The random homogeneous start / reference model (HMCSampler.jl:100-109) of both loops: draws rhoref where none is given, sets
     invParam.strModel and invParam.refModel to it and returns (strModel, rhoref)."""
@@ -804,11 +854,12 @@ def _homogeneous_start(invParam, rhoref, rng, verbose):
     return strModel, rhoref
 
 
-def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM):
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank=None):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals.
-    `outputs`: keyword -> value of the entries of CHAIN_OUTPUTS that are on."""
+    `outputs`: keyword -> value of the entries of CHAIN_OUTPUTS that are on.  `mass_lowrank`: checked (invM, U, lam) with at least one
+    direction, set behind the prior."""
     from types import SimpleNamespace
     from .lib import HMCMT_MASS_WM
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
@@ -823,6 +874,8 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     ctx.set_prior(invParam.refModel, invParam.Wm, invM if invM is not None else (setMassMatrix(nparam, 1.0)[0] if diagonal else np.ones(nparam)))
     if not diagonal:
         ctx.set_mass(HMCMT_MASS_WM)
+    if mass_lowrank is not None:
+        ctx.set_mass_lowrank(None, mass_lowrank[1], mass_lowrank[2])      # (the scales: the prior's invM, set just above)
     lo, hi = np.log(hmcprior.sigBounds[0]), np.log(hmcprior.sigBounds[1])
     # the reference takes its first Hamiltonian at the homogeneous model (:100-112) and its first trajectory from the file's
     startD, startM = ctx.chain_begin(strModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
@@ -872,7 +925,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
                   checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
-                  cov=None, adapt=None, invM=None):
+                  cov=None, adapt=None, invM=None, mass_lowrank=None):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -887,6 +940,10 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     {CHAIN_OUTPUTS}
     `invM=array` (with device_chain): the diagonal of M^-1 the chain starts with instead of ones, for example an earlier run's
     adapted mass.  The draws keep their order.
+    `mass_lowrank=(invM, U, lam)` (with device_chain and massType "diagonal"): the low-rank-plus-diagonal mass of
+    HipContext.set_mass_lowrank, for example lowRankMassFromSamples of a pilot run -- invM[nparam] the scales, U[r, nparam] the
+    directions, lam[r].  The draws keep their order.  With r = 0 it is `invM=invM`.  Not together with invM= or adapt={"mass": True};
+    an adapt without "mass" adapts the step size alone.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -905,17 +962,29 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     # (every refusal before the context is touched and the first number is drawn)
     outputs = {k: v for k, v in (("hist", hist), ("data_moments", {} if data_moments else None), ("ess", ess), ("cov", cov), ("adapt", adapt)) if v is not None}
     on = [out for out in CHAIN_OUTPUTS if out.name in outputs]
-    needing = [(out.name, out.why) for out in on] + ([("invM", "it is the device chain's mass")] if invM is not None else [])
+    needing = [(out.name, out.why) for out in on] + [(k, "it is the device chain's mass") for k, v in (("invM", invM), ("mass_lowrank", mass_lowrank))
+                                                     if v is not None]
     if needing and not device_chain:
         raise ValueError("runHMCSampler: %s needs device_chain=True (%s)" % needing[0])
+    if mass_lowrank is not None:
+        if hmcprior.massType != "diagonal":
+            raise ValueError(f"runHMCSampler: mass_lowrank needs massType \"diagonal\", not {hmcprior.massType!r}")
+        if invM is not None:
+            raise ValueError("runHMCSampler: mass_lowrank carries its own invM; not together with invM=")
+        if adapt is not None:
+            if adapt.get("mass"):
+                raise ValueError("runHMCSampler: adapt mass=True adapts a diagonal mass; not together with mass_lowrank")
+            outputs["adapt"] = {**adapt, "mass": False}
     for out in on:
         out.check(outputs[out.name], hmcprior)
     if invM is not None and hmcprior.massType != "diagonal":
         raise ValueError(f"runHMCSampler: invM needs massType \"diagonal\", not {hmcprior.massType!r}")
+    if mass_lowrank is not None:
+        invM, mass_lowrank = _check_mass_lowrank(mass_lowrank, len(invParam.strModel))
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)

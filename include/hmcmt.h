@@ -176,14 +176,34 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
  *                        hmcmt_set_prior with the same Wm): HMCMT_EINVAL if Wm is not positive definite.  Wm^-1 is a fast
  *                        diagonalisation in fp64 when the active cells fill a box below the air (Wm then separates,
  *                        kernels_mass.h), fp64 PCG on Wm otherwise (relative residual 1e-13, HMCMT_ENOCONV at its cap).
- * hmcmt_mass_apply: y = M^-1 x (HMCMT_MASS_OP_INV) or y = L x (HMCMT_MASS_OP_SQRT) for the mass matrix that was set (for
+ *   HMCMT_MASS_LOWRANK   a diagonal plus a low-rank correction, set by hmcmt_set_mass_lowrank (hmcmt_set_mass refuses the kind):
+ *                          M^-1 = S (I + U (Lambda - I) U') S,   M = F F',   F = S^-1 (I + U (Lambda^-1/2 - I) U')
+ *                        with S = diag(sqrt(invM)), U nAC x rank with orthonormal columns and Lambda = diag(lambda) > 0 -- the
+ *                        metric for a posterior whose covariance is about M^-1: a few strongly correlated directions (U, with
+ *                        variances lambda in units of the scales) over per-cell scales.  Momentum p = F z, position step
+ *                        dm = dt M^-1 p, kinetic energy 0.5 p'M^-1 p, on the route of HMCMT_MASS_WM; hmcmt_mass_apply gives
+ *                        M^-1 x and F x.  One application is two fp64 kernels (kernels_mass.h), nothing waits.
+ * hmcmt_mass_apply: y = M^-1 x (HMCMT_MASS_OP_INV) or y = L x (HMCMT_MASS_OP_SQRT; F x under HMCMT_MASS_LOWRANK) for the mass matrix that was set (for
  *   HMCMT_MASS_DIAGONAL: invM .* x and x ./ sqrt(invM)); x, y [nAC], host (on_device = 0, synchronous) or device pointers
- *   (on_device = 1, enqueued on the context's stream, complete on return). */
+ *   (on_device = 1, enqueued on the context's stream, complete on return).
+ * hmcmt_set_mass_lowrank: invM [nAC] = s^2 (NULL: the diagonal in force, the invM of hmcmt_set_prior unless the chain replaced it),
+ *   1 <= rank <= HMCMT_MASS_RANK_MAX, U [rank][nAC] (direction k contiguous), lambda [rank]; all host.  Like hmcmt_set_mass it needs
+ *   a prior, waits for the stream and ENDS a running chain with its accumulators and adaptation.  HMCMT_EINVAL, with nothing
+ *   changed, for a NULL U or lambda, a rank outside the range, a non-finite or non-positive invM or lambda entry, a non-finite U entry
+ *   (all checked before anything is enqueued) and for max |U'U - I| > 1e-8 (checked on the device; a U from a QR or SVD sits near
+ *   1e-12).  HMCMT_ENOMEM leaves the context on HMCMT_MASS_DIAGONAL.  The call keeps buffers of its own and never writes the prior's
+ *   invM: hmcmt_set_mass(HMCMT_MASS_DIAGONAL) afterwards is the diagonal mass as it was, bit for bit; hmcmt_set_prior and
+ *   hmcmt_set_mass release the buffers, a kept factor of Wm stays.  hmcmt_chain_set_mass_diag and an adaptation with adapt_mass are
+ *   HMCMT_EINVAL under this mass, hmcmt_chain_set_dt and a step-size-only adaptation work.  hmcmt_mass_info reports the kind and 0 in
+ *   its other fields. */
 #define HMCMT_MASS_DIAGONAL 0
 #define HMCMT_MASS_WM       1
+#define HMCMT_MASS_LOWRANK  2
+#define HMCMT_MASS_RANK_MAX 32
 #define HMCMT_MASS_OP_INV   0
 #define HMCMT_MASS_OP_SQRT  1
 int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind);
+int hmcmt_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, const double* U, const double* lambda);
 int hmcmt_mass_apply(hmcmt_ctx* ctx, int32_t op, const double* x, double* y, int32_t on_device);
 
 /* The same trajectory on DEVICE vectors: d_m, d_p [nAC] are updated in place (start model / momentum -> proposal), nothing

@@ -26,7 +26,7 @@ using SparseArrays
 using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
-export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, proposeLeapfrog, proposeLeapfrogDevice!,
+export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, proposeLeapfrog, proposeLeapfrogDevice!,
        hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
@@ -406,6 +406,26 @@ function setPrior!(ctx::HipContext, invParam::InvDataModel, hmcParam::HMCParamet
         rc = ccall((:hmcmt_set_mass, libhmcmt), Cint, (Ptr{Cvoid}, Int32), ctx.ptr, HMCMT_MASS_WM)
         checkerr(ctx.ptr, rc)
     end
+    return ctx
+end
+
+"""
+    set_mass_lowrank!(ctx, invM, U, lam)
+
+The low-rank-plus-diagonal mass M^-1 = S (I + U (Λ - I) U') S, S = diag(sqrt.(invM)) (hmcmt_set_mass_lowrank, include/hmcmt.h): `invM`
+the nAC scales squared, or `nothing` for the diagonal in force; `U` nAC × r with orthonormal columns -- Julia's column-major matrix is
+the C layout, one direction after the other --, `lam` its r variances in units of the scales, 1 ≤ r ≤ HMCMT_MASS_RANK_MAX.  Call it
+behind `setPrior!`; like it, it ends a running chain.
+"""
+const HMCMT_MASS_LOWRANK = Int32(2)
+const HMCMT_MASS_RANK_MAX = 32
+function set_mass_lowrank!(ctx::HipContext, invM::Union{Nothing,Vector{Float64}}, U::Matrix{Float64}, lam::Vector{Float64})
+    size(U, 1) == ctx.nAC || error("set_mass_lowrank!: U must be nAC = $(ctx.nAC) × r")
+    length(lam) == size(U, 2) || error("set_mass_lowrank!: lam must hold one entry per column of U")
+    invM === nothing || length(invM) == ctx.nAC || error("set_mass_lowrank!: invM must hold nAC = $(ctx.nAC) entries")
+    rc = ccall((:hmcmt_set_mass_lowrank, libhmcmt), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+               ctx.ptr, invM === nothing ? C_NULL : invM, Int32(size(U, 2)), U, lam)
+    checkerr(ctx.ptr, rc)
     return ctx
 end
 
