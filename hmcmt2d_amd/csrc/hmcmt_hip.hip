@@ -287,6 +287,10 @@ struct hmcmt_ctx {
         long long burnin = 0, nsamples = 0, nmoments = 0;
         int nextStart = 0;                // start_grad of the next step: 0 evaluate, 1 accepted, 2 rejected
         long long gen = 0;                // stateGen when the chain last left the context
+        // the chain's own generator (hmcmt_chain_seed; hmcmt_items.h: item_rng_*): the state is these three integers, t the next draw
+        bool seeded = false;
+        uint64_t seed = 0, t = 0;
+        uint32_t stream = 0;
         std::vector<void*> allocs;
         // the optional accumulators of the commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*, hmcmt_chain_acov_*, hmcmt_chain_cov_*):
         // each owns its buffers through `allocs` (chain_acc_alloc / chain_acc_free; the d_ pointers only name them), released with the

@@ -11,6 +11,7 @@
 // padded row stride, so the interior/boundary split of getBoundaryIndex (:227-248) is implicit.
 #pragma once
 #include "hmcmt_math.h"
+#include <stdint.h>
 #if !defined(__HIPCC__)
 #include <algorithm>
 #endif
@@ -848,17 +849,15 @@ constexpr int CHAIN_NT = 256;
 constexpr double CHAIN_ZCLIP = 2.5;   // getMomentumVector clips the normals at +-2.5 (HMCSampler.jl:444-447)
 HD int chain_part_of(int a) { return (a / CHAIN_NT) % CHAIN_NB; }
 // momentum of parameter a for the diagonal mass: p = sqrtM * clip(z) = clip(z) / sqrt(invM); returns its term of p' M^-1 p
-HD double item_chain_momentum(const double* z, const double* invM, double* p, int a) {
-    double zc = z[a];
-    zc = zc > CHAIN_ZCLIP ? CHAIN_ZCLIP : (zc < -CHAIN_ZCLIP ? -CHAIN_ZCLIP : zc);
+HD double chain_clip(double zc) { return zc > CHAIN_ZCLIP ? CHAIN_ZCLIP : (zc < -CHAIN_ZCLIP ? -CHAIN_ZCLIP : zc); }
+// ... from the clipped normal zc (shared with the seeded draw, item_chain_draw_momentum: the same operations, so the same bits)
+HD double chain_momentum_of(double zc, const double* invM, double* p, int a) {
     const double pa = zc / sqrt(invM[a]);
     p[a] = pa;
     return pa * (invM[a] * pa);
 }
-HD double item_chain_clip(const double* z, int a) {
-    const double zc = z[a];
-    return zc > CHAIN_ZCLIP ? CHAIN_ZCLIP : (zc < -CHAIN_ZCLIP ? -CHAIN_ZCLIP : zc);
-}
+HD double item_chain_momentum(const double* z, const double* invM, double* p, int a) { return chain_momentum_of(chain_clip(z[a]), invM, p, a); }
+HD double item_chain_clip(const double* z, int a) { return chain_clip(z[a]); }
 // parameter a's term of p' M^-1 p: x = M^-1 p given (M = Wm, from the mass solve), or the diagonal invM
 HD double item_chain_kinetic(const double* p, const double* x, const double* invM, int a) {
     return x ? p[a] * x[a] : p[a] * (invM[a] * p[a]);
@@ -868,6 +867,58 @@ HD double item_chain_total(const double* part) {
     double acc = 0.0;
     for (int b = 0; b < CHAIN_NB; ++b) acc += part[b];
     return acc;
+}
+// The chain's own random numbers (hmcmt_chain_seed, hmcmt_chain_sample; hmcmt_rng_* are these functions on the host): Philox4x32-10
+// (Salmon, Moraes, Dror, Shaw, SC'11), a counter-based generator -- a draw is a pure function of (seed, stream, t, c0), so a chain's
+// generator state is three integers and any host reproduces it.
+//   key     = (seed & 0xffffffff, seed >> 32)
+//   counter = (c0, stream, t & 0xffffffff, t >> 32)   t: the draw's index, one per sample from 0; stream: the chain's number
+//   c0      = the active-cell index a for the momentum's normal of cell a; RNG_C0_SCALARS for the sample's L and u.  nAC is an int32,
+//             so a cell index never reaches 0xFFFFFFFF and the two kinds of block never meet.
+constexpr uint32_t RNG_C0_SCALARS = 0xFFFFFFFFu;
+// one block: ten rounds of two plain 32 x 32 -> 64 products, the key stepped by the Weyl constants behind each round
+HD void item_philox4x32(const uint32_t* c, const uint32_t* k, uint32_t* out) {
+    uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], k0 = k[0], k1 = k[1];
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0;
+        c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+HD void item_rng_block(uint64_t seed, uint32_t stream, uint64_t t, uint32_t c0, uint32_t* out) {
+    const uint32_t c[4] = {c0, stream, (uint32_t)t, (uint32_t)(t >> 32)}, k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    item_philox4x32(c, k, out);
+}
+// a uniform from the upper 26 bits of two words: U = (2 k + 1) 2^-53 with the 52-bit k -- exact in fp64 and strictly inside (0, 1),
+// so that log never sees 0
+HD double item_rng_u52(uint32_t hi, uint32_t lo) {
+    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
+    return (double)(2 * k + 1) * 0x1p-53;
+}
+// the standard normal of cell a in draw t: ONE block per cell and the cosine branch of Box-Muller (the sine is discarded on purpose:
+// a thread owns a cell as in k_chain_momentum, so the partial sums of K0 keep their order); |z| <= sqrt(2 * 53 ln 2) = 8.57
+HD double item_rng_normal(uint64_t seed, uint32_t stream, uint64_t t, int a) {
+    uint32_t x[4];
+    item_rng_block(seed, stream, t, (uint32_t)a, x);
+    const double u1 = item_rng_u52(x[0], x[1]), u2 = item_rng_u52(x[2], x[3]);
+    const double r = sqrt(-2.0 * log(u1)), c = cos(TWO_PI * u2);
+    return r * c;
+}
+// the scalars of draw t: the accept test's uniform u and the trajectory length L in Lmin .. Lmax by multiply-shift of one word --
+// value v has probability floor or ceil of 2^32 / span over 2^32 with span = Lmax - Lmin + 1, a bias of at most span / 2^32
+HD void item_rng_scalars(uint64_t seed, uint32_t stream, uint64_t t, int Lmin, int Lmax, int* L, double* u) {
+    uint32_t x[4];
+    item_rng_block(seed, stream, t, RNG_C0_SCALARS, x);
+    *u = item_rng_u52(x[0], x[1]);
+    *L = Lmin + (int)(((uint64_t)x[2] * (uint64_t)((int64_t)Lmax - (int64_t)Lmin + 1)) >> 32);
+}
+// the seeded draw of cell a: the clipped normal, and for the diagonal mass item_chain_momentum behind it
+HD double item_chain_draw_clip(uint64_t seed, uint32_t stream, uint64_t t, int a) { return chain_clip(item_rng_normal(seed, stream, t, a)); }
+HD double item_chain_draw_momentum(uint64_t seed, uint32_t stream, uint64_t t, const double* invM, double* p, int a) {
+    return chain_momentum_of(item_chain_draw_clip(seed, stream, t, a), invM, p, a);
 }
 // Welford's update of the running mean and the sum of squared deviations with sample m; count includes this sample.
 // A cell that holds the same value in every sample keeps m2 == 0 exactly (d == 0 from the second sample on; the first

@@ -2,7 +2,8 @@
 // unit, included at the end of its extern "C" block (behind leapfrog_core and mass_apply_dev); kernels in kernels_chain.h.
 //
 // One sample = hmcmt_chain_momentum + hmcmt_chain_step.  What crosses PCIe per sample: nAC normals up, LFNB partial sums and
-// CHAIN_REC scalars down; with outputs, nAC + 2 nData doubles more.  Launches per sample beyond leapfrog_core's (diagonal mass):
+// CHAIN_REC scalars down; with outputs, nAC + 2 nData doubles more.  A seeded chain (hmcmt_chain_seed) draws its numbers itself:
+// one sample = hmcmt_chain_sample, k_chain_draw_momentum in k_chain_momentum's place, nothing up, CHAIN_REC scalars down, one wait.  Launches per sample beyond leapfrog_core's (diagonal mass):
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
 // k_chain_hist, a second k_chain_welford (the predicted data), k_chain_acov (lagged autocovariances) and k_chain_cov_commit (cross
 // moments; every `batch` commits k_chain_cov_flush) behind them.  During a warm-up (hmcmt_chain_adapt_*) a k_chain_welford on the
@@ -358,11 +359,63 @@ int hmcmt_chain_begin(hmcmt_ctx* ctx, const double* m_start, double dt, double r
     C.burnin = burnin; C.nsamples = C.nmoments = 0;
     C.cur = 0; C.nextStart = 0; C.haveMomentum = false;
     C.gen = ctx->stateGen;
+    C.seeded = false; C.seed = C.t = 0; C.stream = 0;        // (a begin forgets the seed)
     C.active = true;
     if (D0) *D0 = C.D;
     if (M0) *M0 = C.M;
     return 0;
 }
+
+// ---- one sample in parts: hmcmt_chain_momentum + hmcmt_chain_step wait twice with the host's numbers, hmcmt_chain_sample once with
+// the chain's own (Chain::seed, stream, t) -----------------------------------------------------------------------------------------
+// The momentum's launches, enqueued: p = sqrtM clip(z) into d_p and the partial sums of p' M^-1 p into d_part[0 .. LFNB).  draw ==
+// nullptr: z is what the caller left in d_z; else *draw is the index of the chain's own draw and nothing is read from d_z.
+static int chain_momentum_enqueue(hmcmt_ctx* ctx, const uint64_t* draw) {
+    auto& C = ctx->chain;
+    const int n = ctx->v.nAC;
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) {
+        // p = L clip(z), x = Wm^-1 p, K = 0.5 p'x (HMCMT_MASS_LOWRANK: p = F clip(z), x = M^-1 p)
+        if (draw) hipLaunchKernelGGL(k_chain_draw_clip, dim3((n + 255) / 256), dim3(256), 0, st, n, C.seed, C.stream, *draw, C.d_p);
+        else hipLaunchKernelGGL(k_chain_clip, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_z, C.d_p);
+        if ((rc = mass_apply_dev(ctx, HMCMT_MASS_OP_SQRT, C.d_p, C.d_p))) return rc;
+        if ((rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, C.d_p, ctx->mass.d_x))) return rc;
+        hipLaunchKernelGGL(k_chain_kinetic, dim3(LFNB), dim3(256), 0, st, n, C.d_p, ctx->mass.d_x, ctx->d_invM, C.d_part);
+    } else if (draw) {
+        hipLaunchKernelGGL(k_chain_draw_momentum, dim3(LFNB), dim3(256), 0, st, n, C.seed, C.stream, *draw, ctx->d_invM, C.d_p, C.d_part);
+    } else {
+        hipLaunchKernelGGL(k_chain_momentum, dim3(LFNB), dim3(256), 0, st, n, C.d_z, ctx->d_invM, C.d_p, C.d_part);
+    }
+    return 0;
+}
+
+// what a step carries from its enqueue part to its decide part
+struct ChainStepState { int startGrad = 0, evals = 0; };
+
+// The step's launches behind a momentum in d_p and its partial sums in d_part: the trajectory of L steps in the proposal buffer, K1,
+// k_chain_final and the record's copy to h_rec -- enqueued, the caller waits.  A failure has gone through chain_fail.
+static int chain_step_enqueue(hmcmt_ctx* ctx, int32_t L, ChainStepState* S) {
+    auto& C = ctx->chain;
+    const int n = ctx->v.nAC;
+    hipStream_t st = ctx->stream;
+    const int cur = C.cur, prop = cur ^ 1;
+    C.haveMomentum = false;                                  // consumed, whatever happens
+    // the gradient the last decision left on the device is the start gradient only if nothing has evaluated on the context since
+    S->startGrad = (C.gen == ctx->stateGen && ctx->lfHaveGrad) ? C.nextStart : 0;
+    C.nextStart = 0;
+    HIPCHK(hipMemcpyAsync(C.d_m[prop], C.d_m[cur], sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    ctx->lfHaveGrad = false;
+    int rc = leapfrog_core(ctx, C.d_m[prop], C.d_p, C.dt, L, C.regParam, C.lo, C.hi, S->startGrad, C.d_pred[prop], C.d_scal + CH_D1, &S->evals);
+    if (rc) return chain_fail(ctx, rc);
+    const bool wm = ctx->mass.kind != HMCMT_MASS_DIAGONAL;
+    if (wm && (rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, C.d_p, ctx->mass.d_x))) return chain_fail(ctx, rc);
+    hipLaunchKernelGGL(k_chain_kinetic, dim3(LFNB), dim3(256), 0, st, n, C.d_p, wm ? ctx->mass.d_x : nullptr, ctx->d_invM, C.d_part + LFNB);
+    hipLaunchKernelGGL(k_chain_final, dim3(1), dim3(1), 0, st, C.d_part, C.d_part + LFNB, ctx->d_lfScal, ctx->d_lfFlag, C.d_scal);
+    HIPCHK(hipMemcpyAsync(C.h_rec, C.d_scal, sizeof(double) * CHAIN_REC, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, hmcmt_chain_record* rec, double* m_out, double* pred_out);
 
 int hmcmt_chain_momentum(hmcmt_ctx* ctx, const double* z, double* K) {
     if (!ctx) return HMCMT_EINVAL;
@@ -378,15 +431,7 @@ int hmcmt_chain_momentum(hmcmt_ctx* ctx, const double* z, double* K) {
     C.haveMomentum = false;
     std::memcpy(ctx->h_stage, z, sizeof(double) * n);
     HIPCHK(hipMemcpyAsync(C.d_z, ctx->h_stage, sizeof(double) * n, hipMemcpyHostToDevice, st));
-    if (ctx->mass.kind != HMCMT_MASS_DIAGONAL) {
-        // p = L clip(z), x = Wm^-1 p, K = 0.5 p'x (HMCMT_MASS_LOWRANK: p = F clip(z), x = M^-1 p)
-        hipLaunchKernelGGL(k_chain_clip, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_z, C.d_p);
-        if ((rc = mass_apply_dev(ctx, HMCMT_MASS_OP_SQRT, C.d_p, C.d_p))) return rc;
-        if ((rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, C.d_p, ctx->mass.d_x))) return rc;
-        hipLaunchKernelGGL(k_chain_kinetic, dim3(LFNB), dim3(256), 0, st, n, C.d_p, ctx->mass.d_x, ctx->d_invM, C.d_part);
-    } else {
-        hipLaunchKernelGGL(k_chain_momentum, dim3(LFNB), dim3(256), 0, st, n, C.d_z, ctx->d_invM, C.d_p, C.d_part);
-    }
+    if ((rc = chain_momentum_enqueue(ctx, nullptr))) return rc;
     // (the partial sums come over and are added here in k_chain_final's order: the same bits as the record's K0, one launch less)
     HIPCHK(hipMemcpyAsync(C.h_rec + CHAIN_REC, C.d_part, sizeof(double) * LFNB, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -407,28 +452,28 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
     if (!C.haveMomentum) { ctx->err = "hmcmt_chain_step: no momentum since the last step (hmcmt_chain_momentum first)"; return HMCMT_EINVAL; }
     if (L < 1 || !std::isfinite(u)) { ctx->err = "hmcmt_chain_step: need L >= 1 and a finite u"; return HMCMT_EINVAL; }
     HIPCHK(hipSetDevice(ctx->cfg.device));
+    ChainStepState S;
+    if ((rc = chain_step_enqueue(ctx, L, &S))) return rc;
+    return chain_step_decide(ctx, u, S, rec, m_out, pred_out);
+}
+
+// The step behind its launches: the sample's one wait, the record's checks, the accept test with u, the commit (enqueued), the outputs.
+// K0 is the record's: what hmcmt_chain_momentum returned, bit for bit, and the only place hmcmt_chain_sample reads it.
+static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, hmcmt_chain_record* rec, double* m_out, double* pred_out) {
+    auto& C = ctx->chain;
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     hipStream_t st = ctx->stream;
-    const int cur = C.cur, prop = cur ^ 1;
-    C.haveMomentum = false;                                  // consumed, whatever happens
-    // the gradient the last decision left on the device is the start gradient only if nothing has evaluated on the context since
-    const int startGrad = (C.gen == ctx->stateGen && ctx->lfHaveGrad) ? C.nextStart : 0;
-    C.nextStart = 0;
-    HIPCHK(hipMemcpyAsync(C.d_m[prop], C.d_m[cur], sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    ctx->lfHaveGrad = false;
-    int evals = 0;
-    rc = leapfrog_core(ctx, C.d_m[prop], C.d_p, C.dt, L, C.regParam, C.lo, C.hi, startGrad, C.d_pred[prop], C.d_scal + CH_D1, &evals);
-    if (rc) return chain_fail(ctx, rc);
-    const bool wm = ctx->mass.kind != HMCMT_MASS_DIAGONAL;
-    if (wm && (rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, C.d_p, ctx->mass.d_x))) return chain_fail(ctx, rc);
-    hipLaunchKernelGGL(k_chain_kinetic, dim3(LFNB), dim3(256), 0, st, n, C.d_p, wm ? ctx->mass.d_x : nullptr, ctx->d_invM, C.d_part + LFNB);
-    hipLaunchKernelGGL(k_chain_final, dim3(1), dim3(1), 0, st, C.d_part, C.d_part + LFNB, ctx->d_lfScal, ctx->d_lfFlag, C.d_scal);
-    HIPCHK(hipMemcpyAsync(C.h_rec, C.d_scal, sizeof(double) * CHAIN_REC, hipMemcpyDeviceToHost, st));
+    const int prop = C.cur ^ 1, startGrad = S.startGrad, evals = S.evals;
+    int rc;
     HIPCHK(hipStreamSynchronize(st));                        // the step's one wait
     HIPCHK(hipGetLastError());
     prof_collect(ctx);
     if ((rc = leapfrog_flag(ctx))) return chain_fail(ctx, rc);
     const double K0 = C.h_rec[CH_K0], K1 = C.h_rec[CH_K1], D1 = C.h_rec[CH_D1], M1 = C.h_rec[CH_M1];
+    if (!std::isfinite(K0)) {                                // (a host-fed momentum has failed in hmcmt_chain_momentum already)
+        ctx->err = "non-finite kinetic energy of the drawn momentum (the diagonal of M^-1 must be positive)";
+        return chain_fail(ctx, HMCMT_EBREAKDOWN);
+    }
     if (C.h_rec[CH_FLAG] != 0.0 || !std::isfinite(K1) || !std::isfinite(D1) || !std::isfinite(M1)) {
         ctx->err = "non-finite model value or Hamiltonian term at the proposal";
         return chain_fail(ctx, HMCMT_EBREAKDOWN);
@@ -520,6 +565,126 @@ int hmcmt_chain_moments(hmcmt_ctx* ctx, int64_t* count, double* mean, double* m2
     auto& C = ctx->chain;
     if ((rc = chain_welford_out(ctx, sizeof(double) * ctx->v.nAC, C.d_mean, C.d_m2, mean, m2, on_device))) return rc;
     if (count) *count = C.nmoments;
+    return 0;
+}
+
+// ---- the chain's own random numbers: Philox4x32-10 by counter (hmcmt_items.h: item_rng_*), one wait per sample -----------------------
+// the two generator calls that need neither a context nor a device: the item functions on the host
+int hmcmt_rng_draw(uint64_t seed, uint32_t stream, uint64_t t, int32_t Lmin, int32_t Lmax, int32_t* L, double* u) {
+    if (Lmin < 1 || Lmax < Lmin) return HMCMT_EINVAL;
+    int l = 0;
+    double uu = 0.0;
+    item_rng_scalars(seed, stream, t, Lmin, Lmax, &l, &uu);
+    if (L) *L = l;
+    if (u) *u = uu;
+    return 0;
+}
+int hmcmt_rng_normals(uint64_t seed, uint32_t stream, uint64_t t, int64_t a0, int64_t n, double* z) {
+    if (a0 < 0 || n < 0 || a0 > (int64_t)INT32_MAX || n > (int64_t)INT32_MAX + 1 - a0 || (n > 0 && !z)) return HMCMT_EINVAL;
+    for (int64_t i = 0; i < n; ++i) z[i] = item_rng_normal(seed, stream, t, (int)(a0 + i));
+    return 0;
+}
+
+// what the calls on a seeded chain check first
+static int chain_rng_ready(hmcmt_ctx* ctx, const char* fn) {
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    if (!ctx->chain.seeded) { ctx->err = std::string(fn) + ": the chain has no seed (hmcmt_chain_seed first; hmcmt_chain_begin forgets it)"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+int hmcmt_chain_seed(hmcmt_ctx* ctx, uint64_t seed, uint32_t stream) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, "hmcmt_chain_seed", true);
+    if (rc) return rc;
+    auto& C = ctx->chain;
+    C.seed = seed; C.stream = stream; C.t = 0;
+    C.seeded = true;
+    return 0;
+}
+
+int hmcmt_chain_rng_state(hmcmt_ctx* ctx, uint64_t* seed, uint32_t* stream, uint64_t* t) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_rng_ready(ctx, "hmcmt_chain_rng_state");
+    if (rc) return rc;
+    const auto& C = ctx->chain;
+    if (seed) *seed = C.seed;
+    if (stream) *stream = C.stream;
+    if (t) *t = C.t;
+    return 0;
+}
+
+int hmcmt_chain_rng_seek(hmcmt_ctx* ctx, uint64_t t) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_rng_ready(ctx, "hmcmt_chain_rng_seek");
+    if (rc) return rc;
+    ctx->chain.t = t;
+    return 0;
+}
+
+int hmcmt_chain_normals(hmcmt_ctx* ctx, uint64_t t, double* z, int32_t on_device) {
+    const char* fn = "hmcmt_chain_normals";
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_rng_ready(ctx, fn);
+    if (rc) return rc;
+    if (!z) { ctx->err = std::string(fn) + ": z is NULL"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    const auto& C = ctx->chain;
+    const int n = ctx->v.nAC;
+    ChainReadout R(ctx, fn, on_device);
+    double* dst = (double*)R.out(z, sizeof(double) * (size_t)n);
+    if (R.rc) return R.rc;
+    hipLaunchKernelGGL(k_chain_draw_clip, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, C.seed, C.stream, t, dst);
+    return R.finish();
+}
+
+// one sample with the chain's own numbers; fn: the entry point the messages name
+static int chain_sample(hmcmt_ctx* ctx, const char* fn, int32_t Lmin, int32_t Lmax, hmcmt_chain_record* rec, double* m_out, double* pred_out) {
+    auto& C = ctx->chain;
+    int L = 0;
+    double u = 0.0;
+    item_rng_scalars(C.seed, C.stream, C.t, Lmin, Lmax, &L, &u);
+    const uint64_t t = C.t++;                                // the draw is consumed, whatever happens
+    C.haveMomentum = false;
+    int rc = chain_momentum_enqueue(ctx, &t);
+    if (rc) { ctx->err = std::string(fn) + ": " + ctx->err; return chain_fail(ctx, rc); }
+    ChainStepState S;
+    if ((rc = chain_step_enqueue(ctx, L, &S))) return rc;
+    return chain_step_decide(ctx, u, S, rec, m_out, pred_out);
+}
+
+static int chain_sample_ready(hmcmt_ctx* ctx, const char* fn, int32_t Lmin, int32_t Lmax) {
+    const int rc = chain_rng_ready(ctx, fn);
+    if (rc) return rc;
+    if (Lmin < 1 || Lmax < Lmin) { ctx->err = std::string(fn) + ": need 1 <= Lmin <= Lmax"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+int hmcmt_chain_sample(hmcmt_ctx* ctx, int32_t Lmin, int32_t Lmax, hmcmt_chain_record* rec, double* m_out, double* pred_out) {
+    const char* fn = "hmcmt_chain_sample";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!rec) { ctx->err = std::string(fn) + ": rec is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_sample_ready(ctx, fn, Lmin, Lmax);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    return chain_sample(ctx, fn, Lmin, Lmax, rec, m_out, pred_out);
+}
+
+int hmcmt_chain_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t Lmin, int32_t Lmax, hmcmt_chain_record* recs, double* models, double* preds,
+                    int64_t* done) {
+    const char* fn = "hmcmt_chain_run";
+    if (!ctx) return HMCMT_EINVAL;
+    if (done) *done = 0;
+    if (!recs || nsamples < 0) { ctx->err = std::string(fn) + ": need recs[nsamples] and nsamples >= 0"; return HMCMT_EINVAL; }
+    int rc = chain_sample_ready(ctx, fn, Lmin, Lmax);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    const size_t n = (size_t)ctx->v.nAC, nd = (size_t)2 * ctx->v.nData;
+    for (int64_t i = 0; i < nsamples; ++i) {
+        if ((rc = chain_sample(ctx, fn, Lmin, Lmax, recs + i, models ? models + (size_t)i * n : nullptr, preds ? preds + (size_t)i * nd : nullptr)))
+            return rc;
+        if (done) *done = i + 1;
+    }
     return 0;
 }
 

@@ -25,6 +25,24 @@ __global__ void k_chain_clip(int n, const double* __restrict__ z, double* __rest
     const int a = TID1;
     if (a < n) out[a] = item_chain_clip(z, a);
 }
+// The seeded chain's momentum (hmcmt_chain_sample): k_chain_momentum with the normal of cell a drawn in the thread that owns the cell
+// (item_rng_normal: one Philox block, a log, a sqrt and a cos) -- nothing is read from d_z, and the thread-to-cell mapping and with
+// it the order of the partial sums are k_chain_momentum's
+__global__ __launch_bounds__(256) void k_chain_draw_momentum(int n, unsigned long long seed, unsigned int stream, unsigned long long t,
+                                                             const double* __restrict__ invM, double* __restrict__ p,
+                                                             double* __restrict__ part) {
+    __shared__ double sh[32];
+    double acc = 0.0, dummy = 0.0;
+    for (int a = blockIdx.x * 256 + threadIdx.x; a < n; a += 256 * LFNB) acc += item_chain_draw_momentum(seed, stream, t, invM, p, a);
+    block_sum2(acc, dummy, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+// ... and k_chain_clip with the drawn normal: in front of mass_apply_dev for the non-diagonal masses, and hmcmt_chain_normals' read-out
+__global__ __launch_bounds__(256) void k_chain_draw_clip(int n, unsigned long long seed, unsigned int stream, unsigned long long t,
+                                                         double* __restrict__ out) {
+    const int a = TID1;
+    if (a < n) out[a] = item_chain_draw_clip(seed, stream, t, a);
+}
 // partial sums of p' M^-1 p: x = M^-1 p from the mass solve (M = Wm), or x == nullptr and the diagonal invM
 __global__ __launch_bounds__(256) void k_chain_kinetic(int n, const double* __restrict__ p, const double* __restrict__ x,
                                                        const double* __restrict__ invM, double* __restrict__ part) {

@@ -201,6 +201,16 @@ def load_library():
     lib.hmcmt_chain_corr.argtypes = [vp, vp, C.c_int32]
     lib.hmcmt_debug_chain_cov_time.argtypes = [vp, C.c_int32, c_double_p, c_int64_p]
     lib.hmcmt_debug_chain_cov_time.restype = C.c_int
+    lib.hmcmt_rng_draw.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    lib.hmcmt_rng_normals.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, C.c_int64, c_double_p]
+    lib.hmcmt_chain_seed.argtypes = [vp, C.c_uint64, C.c_uint32]
+    lib.hmcmt_chain_rng_state.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.hmcmt_chain_rng_seek.argtypes = [vp, C.c_uint64]
+    lib.hmcmt_chain_normals.argtypes = [vp, C.c_uint64, vp, C.c_int32]
+    lib.hmcmt_chain_sample.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(ChainRecord), c_double_p, c_double_p]
+    lib.hmcmt_chain_run.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ChainRecord), c_double_p, c_double_p, c_int64_p]
+    for name in CHAIN_RNG_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     lib.hmcmt_debug_extrap.argtypes = [vp, C.c_int32, c_double_p]
@@ -241,9 +251,12 @@ COV_BATCH_MAX = 16    # include/hmcmt.h: HMCMT_COV_BATCH_MAX
 # ... and the warm-up: the chain's step size and diagonal mass between two steps, and their adaptation
 CHAIN_ADAPT_SYMBOLS = ["hmcmt_chain_set_dt", "hmcmt_chain_set_mass_diag", "hmcmt_chain_mass_diag", "hmcmt_default_adapt_options",
                        "hmcmt_chain_adapt_begin", "hmcmt_chain_adapt_info", "hmcmt_chain_adapt_end"]
+# ... and the chain's own random numbers: Philox4x32-10 by counter, one call and one wait per sample, one call per run
+CHAIN_RNG_SYMBOLS = ["hmcmt_rng_draw", "hmcmt_rng_normals", "hmcmt_chain_seed", "hmcmt_chain_rng_state", "hmcmt_chain_rng_seek",
+                     "hmcmt_chain_normals", "hmcmt_chain_sample", "hmcmt_chain_run"]
 ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_RNG_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -260,6 +273,34 @@ EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 def _dp(a):
     return a.ctypes.data_as(c_double_p)
+
+
+def _rng_ints(seed, stream, t=0):
+    seed, stream, t = int(seed), int(stream), int(t)
+    if not (0 <= seed < 2 ** 64 and 0 <= stream < 2 ** 32 and 0 <= t < 2 ** 64):
+        raise ValueError(f"seed and t are uint64 and stream is uint32; got seed {seed}, stream {stream}, t {t}")
+    return seed, stream, t
+
+
+def rng_draw(seed, stream, t, Lmin, Lmax):
+    """(L, u) of draw t of the chain (seed, stream): hmcmt_rng_draw, pure arithmetic on the host, no GPU needed."""
+    lib = load_library()
+    L, u = C.c_int32(), C.c_double()
+    rc = lib.hmcmt_rng_draw(*_rng_ints(seed, stream, t), int(Lmin), int(Lmax), C.byref(L), C.byref(u))
+    if rc != 0:
+        raise HmcmtError(rc, "hmcmt_rng_draw: need 1 <= Lmin <= Lmax")
+    return int(L.value), float(u.value)
+
+
+def rng_normals(seed, stream, t, n, a0=0):
+    """The unclipped standard normals of the cells a0 .. a0 + n - 1 in draw t of the chain (seed, stream): hmcmt_rng_normals, the
+    device's numbers to libm accuracy, computed on the host, no GPU needed."""
+    lib = load_library()
+    z = np.empty(max(int(n), 0))                             # (a negative n is the library's to refuse)
+    rc = lib.hmcmt_rng_normals(*_rng_ints(seed, stream, t), int(a0), int(n), _dp(z))
+    if rc != 0:
+        raise HmcmtError(rc, "hmcmt_rng_normals: need a0 >= 0, n >= 0 and a0 + n <= 2^31")
+    return z
 
 
 def lowrank_mass_arrays(nAC, invM, U, lam):
@@ -738,6 +779,64 @@ class HipContext:
 
     def chain_end(self):
         self._check(self.lib.hmcmt_chain_end(self.h))
+
+    # -- the chain's own random numbers (hmcmt_chain_seed, hmcmt_chain_sample, hmcmt_chain_run) ----
+    def chain_seed(self, seed, stream=0):
+        """The chain draws its own numbers from here on: Philox4x32-10 keyed by seed, counter (cell, stream, t), t = 0."""
+        seed, stream, _ = _rng_ints(seed, stream)
+        self._check(self.lib.hmcmt_chain_seed(self.h, seed, stream))
+
+    def chain_rng_state(self):
+        """(seed, stream, t): all a checkpoint of the chain's generator needs; t is the index of the next draw."""
+        seed, stream, t = C.c_uint64(), C.c_uint32(), C.c_uint64()
+        self._check(self.lib.hmcmt_chain_rng_state(self.h, C.byref(seed), C.byref(stream), C.byref(t)))
+        return int(seed.value), int(stream.value), int(t.value)
+
+    def chain_rng_seek(self, t):
+        self._check(self.lib.hmcmt_chain_rng_seek(self.h, _rng_ints(0, 0, t)[2]))
+
+    def chain_normals(self, t, d_z=None):
+        """The device's clipped normals of draw t, [nAC]; with d_z (a device pointer as int) they stay on the device."""
+        t = _rng_ints(0, 0, t)[2]
+        if d_z is not None:
+            self._check(self.lib.hmcmt_chain_normals(self.h, t, d_z, 1))
+            return None
+        z = np.empty(self.nAC)
+        self._check(self.lib.hmcmt_chain_normals(self.h, t, z.ctypes.data, 0))
+        return z
+
+    def chain_sample(self, Lmin, Lmax, outputs=True):
+        """One sample of a seeded chain: momentum, L in Lmin .. Lmax and u are draw t's; returns what chain_step returns."""
+        rec = ChainRecord()
+        m = np.empty(self.nAC) if outputs else None
+        pred = np.empty(self.nData, dtype=np.complex128) if outputs else None
+        self._check(self.lib.hmcmt_chain_sample(self.h, int(Lmin), int(Lmax), C.byref(rec), _dp(m) if outputs else None,
+                                                _dp(pred) if outputs else None))
+        if outputs and self.args.real_data:
+            pred = pred.real.copy()
+        return rec.as_dict(), m, pred
+
+    def chain_run(self, nsamples, Lmin, Lmax, outputs=True, check=True):
+        """nsamples samples of a seeded chain in one call.  Returns (records, models [nsamples, nAC], preds [nsamples, nData]) -- None
+        for both arrays with outputs=False.  A failing sample raises; with check=False the call returns (records, models, preds, rc)
+        cut to the samples that were completed."""
+        nsamples = int(nsamples)
+        rows = max(nsamples, 0)                              # (a negative nsamples is the library's to refuse)
+        recs = (ChainRecord * max(rows, 1))()
+        models = np.empty((rows, self.nAC)) if outputs else None
+        preds = np.empty((rows, self.nData), dtype=np.complex128) if outputs else None
+        done = C.c_int64()
+        rc = self.lib.hmcmt_chain_run(self.h, nsamples, int(Lmin), int(Lmax), recs, _dp(models) if outputs else None,
+                                      _dp(preds) if outputs else None, C.byref(done))
+        if check:
+            self._check(rc)
+        k = int(done.value)
+        out = [recs[i].as_dict() for i in range(k)]
+        if outputs:
+            models, preds = models[:k], preds[:k]
+            if self.args.real_data:
+                preds = preds.real.copy()
+        return (out, models, preds) if check else (out, models, preds, rc)
 
     # -- marginal posteriors from the chain's commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*) --
     def chain_hist_begin(self, targets, nbins, lo, hi):

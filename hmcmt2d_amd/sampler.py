@@ -854,7 +854,65 @@ def _homogeneous_start(invParam, rhoref, rng, verbose):
     return strModel, rhoref
 
 
-def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank=None):
+def _check_library_rng(library_rng):
+    """runHMCSampler's library_rng=(seed, stream) as two ints in the library's ranges (uint64, uint32); ValueError otherwise"""
+    try:
+        seed, stream = (int(v) for v in library_rng)
+    except (TypeError, ValueError):
+        raise ValueError("runHMCSampler: library_rng must be (seed, stream)") from None
+    if not (0 <= seed < 2 ** 64 and 0 <= stream < 2 ** 32):
+        raise ValueError(f"runHMCSampler: library_rng needs 0 <= seed < 2^64 and 0 <= stream < 2^32; got {(seed, stream)}")
+    return seed, stream
+
+
+def _sample_line(it, rec):
+    return (f"iterNo={it:6d} dtMisfit={rec['D1']:8.3e} mNorm={rec['M1']:8.3e} KEnergy={rec['K1']:8.3e} "
+            f"HEnergy={rec['D1'] + rec['K1'] + rec['M1']:8.3e} {'accepted' if rec['accepted'] else 'rejected'} "
+            f"p={min(1.0, float(np.exp(min(rec['hdif'], 0.0)))):.3f}")
+
+
+LIBRARY_RNG_BLOCK = 16      # samples per chain_run call where a progress line is wanted
+
+
+def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, start):
+    """The loop of _run_device_chain with the library's own random numbers (library_rng = (seed, stream)): chain_seed, then the samples
+    through chain_run -- one call for the whole run, blocks of LIBRARY_RNG_BLOCK with verbose (the lines of a block are printed behind
+    it), single samples where an output watches every step.  Column `it` of hmstats takes its K from the record of sample it + 1 (K0
+    is the kinetic energy of the momentum that sample drew); the last column's is the next draw's, read back through chain_normals and
+    chain_momentum, which leaves the generator where it is."""
+    ctx.chain_seed(*library_rng)
+    nsamples = hmcprior.totalsamples
+    Lmin, Lmax = int(hmcprior.timestep[0]), int(hmcprior.timestep[1])
+    block = 1 if watching else (LIBRARY_RNG_BLOCK if verbose else max(nsamples, 1))
+    D, M = start
+    it = 0
+    while it < nsamples:
+        recs, models, preds = ctx.chain_run(min(block, nsamples - it), Lmin, Lmax, outputs=keep_samples)
+        for k, rec in enumerate(recs):
+            stats.hmstats[:, it] = [D, M, rec["K0"], D + M + rec["K0"]]
+            it += 1
+            for out, state in watching:
+                out.step(ctx, state, it, rec)
+            hmcprior.nfevals += rec["nfevals"]
+            if rec["accepted"]:
+                stats.nAccept += 1
+                stats.acceptstats[it - 1] = True
+            else:
+                stats.nReject += 1
+            if verbose:
+                print(_sample_line(it, rec))
+            D, M = rec["D"], rec["M"]
+            if keep_samples:
+                hmcmodel[:, it - 1] = models[k]
+                hmcdata[:, it] = preds[k] if rec["accepted"] else hmcdata[:, it - 1]
+    seed, stream, t = ctx.chain_rng_state()
+    K = ctx.chain_momentum(ctx.chain_normals(t))             # (host-fed: t stays)
+    stats.hmstats[:, nsamples] = [D, M, K, D + M + K]
+    stats.rng = (seed, stream, t)
+
+
+def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank=None,
+                      library_rng=None):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals.
@@ -888,12 +946,19 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     # (behind the second begin: a begin ends the accumulators)
     begun = [(out, out.begin(ctx, outputs[out.name], env)) for out in CHAIN_OUTPUTS if out.name in outputs]
     watching = [(out, state) for out, state in begun if out.step is not None]
-    startK = ctx.chain_momentum(z)
     nkeep = nsamples if keep_samples else 0
     hmcmodel = np.zeros((nparam, nkeep))
     hmcdata = np.zeros((ndata, nkeep + 1), dtype=np.complex128)
     hmcdata[:, 0] = predStart
     stats: HMCStatus = initHMCStatus(nsamples)
+    if library_rng is not None:
+        # (z, drawn above so that rhoref is the draw it is without the keyword, is not used: every momentum is the library's)
+        _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, (startD, startM))
+        stats.moments = ctx.chain_moments()
+        for out, state in begun:
+            setattr(stats, out.field, out.read(ctx, state, stats, env))
+        return hmcmodel, stats, hmcdata
+    startK = ctx.chain_momentum(z)
     stats.hmstats[:, 0] = [startD, startM, startK, startD + startM + startK]
     for it in range(1, nsamples + 1):
         L = int(rng.integers(hmcprior.timestep[0], hmcprior.timestep[1] + 1))
@@ -908,9 +973,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
         else:
             stats.nReject += 1
         if verbose:
-            print(f"iterNo={it:6d} dtMisfit={rec['D1']:8.3e} mNorm={rec['M1']:8.3e} KEnergy={rec['K1']:8.3e} "
-                  f"HEnergy={rec['D1'] + rec['K1'] + rec['M1']:8.3e} {'accepted' if rec['accepted'] else 'rejected'} "
-                  f"p={min(1.0, float(np.exp(min(rec['hdif'], 0.0)))):.3f}")
+            print(_sample_line(it, rec))
         startK = ctx.chain_momentum(rng.standard_normal(nparam))
         stats.hmstats[:, it] = [rec["D"], rec["M"], startK, rec["D"] + rec["M"] + startK]
         if keep_samples:
@@ -925,7 +988,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
                   checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
-                  cov=None, adapt=None, invM=None, mass_lowrank=None):
+                  cov=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -944,6 +1007,13 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     HipContext.set_mass_lowrank, for example lowRankMassFromSamples of a pilot run -- invM[nparam] the scales, U[r, nparam] the
     directions, lam[r].  The draws keep their order.  With r = 0 it is `invM=invM`.  Not together with invM= or adapt={"mass": True};
     an adapt without "mass" adapts the step size alone.
+
+    `library_rng=(seed, stream)` (with device_chain): the chain draws its own random numbers in the library -- Philox4x32-10 by
+    counter (hmcmt_chain_seed, include/hmcmt.h): the momenta on the GPU, L and u on the host side of the library -- and runs through
+    hmcmt_chain_run: one call for the run (blocks of 16 samples with verbose, single samples with adapt=), one wait and no upload per
+    sample.  The chain is a function of (seed, stream) and the problem alone, the same from Python and from julia/HMCMTHip.jl;
+    hmcstats.rng = (seed, stream, t) is the generator's whole state behind the run, t the index of the next draw.  `rng` still draws
+    rhoref, and nothing else.  Every other keyword works unchanged.
 
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
@@ -964,8 +1034,12 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     on = [out for out in CHAIN_OUTPUTS if out.name in outputs]
     needing = [(out.name, out.why) for out in on] + [(k, "it is the device chain's mass") for k, v in (("invM", invM), ("mass_lowrank", mass_lowrank))
                                                      if v is not None]
+    if library_rng is not None:
+        needing.append(("library_rng", "the library's generator feeds the device chain"))
     if needing and not device_chain:
         raise ValueError("runHMCSampler: %s needs device_chain=True (%s)" % needing[0])
+    if library_rng is not None:
+        library_rng = _check_library_rng(library_rng)
     if mass_lowrank is not None:
         if hmcprior.massType != "diagonal":
             raise ValueError(f"runHMCSampler: mass_lowrank needs massType \"diagonal\", not {hmcprior.massType!r}")
@@ -984,7 +1058,8 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     rng = rng or np.random.default_rng()
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
-        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank)
+        return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank,
+                                 library_rng)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -1099,6 +1174,8 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
     `path.chain<k>` per chain; device_chain=True, keep_samples=False and the device chain's optional outputs).  What those outputs
     fill -- every HMCStatus field of CHAIN_OUTPUTS -- is not gathered: it stays with the chain on the chain's own rank.
+    `library_rng=True` (with device_chain=True): chain c draws its numbers in the library as stream c of `seed`,
+    runHMCSampler(library_rng=(seed, c)); its hmcstats.rng stays on the chain's own rank like the optional outputs.
     Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
     count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
     gelmanRubin).  A chain's block in the gather is, in doubles (the sum of gatherBlockFields, which packing and unpacking walk),
@@ -1154,6 +1231,8 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                 kw = dict(sampler_kw)
                 if kw.get("checkpoint"):                        # one checkpoint file per chain
                     kw["checkpoint"] = f"{kw['checkpoint']}.chain{c + 1}"
+                if kw.get("library_rng") is True:               # the library's generator: chain c is stream c of the run's seed
+                    kw["library_rng"] = (int(seed), c)
                 model, stats, data = runHMCSampler(mesh_c, mtData, inv_c, prior_c, rng, ctx=ctx_c, **kw)
             finally:
                 release_context(inv_c)
@@ -1242,6 +1321,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
             if c in results:                                # (what the optional outputs fill is not gathered: a chain's own rank keeps it)
                 for out in CHAIN_OUTPUTS:
                     setattr(hmcstats[c], out.field, getattr(results[c][1], out.field, None))
+                hmcstats[c].rng = getattr(results[c][1], "rng", None)
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

@@ -91,6 +91,7 @@ class HMCStatus:
     ess: object = None            # dict count, maxlag, targets, mean, acov, tau, ess, window, misfit: runHMCSampler(..., ess=...)
     cov: object = None            # dict count, rows, mean, var, cov, corr: runHMCSampler(..., cov=...)
     adapt: object = None          # dict nwarmup, dt, alpha, dt_final, invM, windows: runHMCSampler(..., adapt=...)
+    rng: object = None            # (seed, stream, t) of the library's generator behind the run: runHMCSampler(..., library_rng=(seed, stream))
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

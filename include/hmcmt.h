@@ -442,6 +442,54 @@ extern int hmcmt_chain_adapt_begin(hmcmt_ctx* ctx, const hmcmt_adapt_options* o)
 extern int hmcmt_chain_adapt_info(hmcmt_ctx* ctx, hmcmt_adapt_info* info);
 extern int hmcmt_chain_adapt_end(hmcmt_ctx* ctx);
 
+/* The chain's own random numbers: a seeded chain draws its momenta on the device and its L and u in the library, and waits once per
+ * sample.  The generator is Philox4x32-10 (Salmon et al., SC'11: multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ * 0xBB67AE85, ten rounds), used by counter: a draw is a pure function of four integers and no state is carried.
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (c0, stream, t & 0xffffffff, t >> 32); t = the draw's index, one per sample, from 0; stream = the chain's number in a
+ *             multi-chain run; c0 = the active-cell index a (0-based) for the momentum's normal of cell a, 0xFFFFFFFF for the sample's
+ *             scalars (nAC is an int32: the two never meet).  The block's four words are x0 .. x3.
+ *   uniform   U(hi, lo) = (2 k + 1) 2^-53 with k = ((uint64)(hi >> 6) << 26) | (lo >> 6): exact in fp64, strictly inside (0, 1)
+ *   normal    of cell a: z = sqrt(-2 ln U(x0, x1)) * cos(2 pi U(x2, x3)) in fp64 from the block at c0 = a (one block per cell; the
+ *             sine is not used).  The chain clips it at +-2.5 like a host normal.  |z| <= 8.57
+ *   scalars   from the block at c0 = 0xFFFFFFFF: u = U(x0, x1); L = Lmin + (int)((x2 * (Lmax - Lmin + 1)) >> 32) in 64-bit arithmetic,
+ *             whose bias is at most (Lmax - Lmin + 1) / 2^32 per value
+ * So a chain's generator state is (seed, stream, t): three integers are what a checkpoint carries.
+ *   hmcmt_rng_draw        L and u of draw t on the host (each may be NULL): no context, no device.  HMCMT_EINVAL for Lmin < 1 or
+ *                         Lmax < Lmin.  u is the chain's bit for bit, L exactly
+ *   hmcmt_rng_normals     the UNCLIPPED normals of the cells a0 .. a0 + n - 1 of draw t on the host, z[n]: no context, no device.  The
+ *                         uniforms under them are the device's bit for bit; log, sqrt and cos are the host's libm, so z agrees with
+ *                         the device's to a few ulp of 8.57 (4e-14 absolute holds both against a long-double evaluation).
+ *                         HMCMT_EINVAL for a0 < 0, n < 0, a0 + n > 2^31 or a NULL z with n > 0
+ *   hmcmt_chain_seed      on a live chain, at any point between two steps: sets (seed, stream) and t = 0.  hmcmt_chain_begin forgets
+ *                         the seed
+ *   hmcmt_chain_rng_state / hmcmt_chain_rng_seek   read (seed, stream, t; each may be NULL) / set t, the index of the next draw
+ *   hmcmt_chain_normals   the device's clipped normals of draw t of this chain's (seed, stream), z[nAC] (host, or a device pointer with
+ *                         on_device = 1); complete on return.  Moves neither t nor anything else of the chain
+ *   hmcmt_chain_sample    one sample with draw t: the momentum on the device (k_chain_draw_momentum; for HMCMT_MASS_WM and
+ *                         HMCMT_MASS_LOWRANK the clipped normals through the mass's own route), L in Lmin .. Lmax and u as
+ *                         hmcmt_rng_draw gives them, then exactly hmcmt_chain_step: trajectory, accept test, commit, record, outputs
+ *                         (m_out[nAC], pred_out complex [nData], host, each may be NULL).  t advances by one whether the sample succeeds
+ *                         or fails: a failed sample consumes its draw as a failed step consumes its momentum, and leaves the chain
+ *                         where it was.  The host waits once (plus once for the outputs when asked for); K0 comes from the record, and a
+ *                         non-finite K0 is HMCMT_EBREAKDOWN.  The sample equals, bit for bit, hmcmt_chain_momentum with the normals
+ *                         hmcmt_chain_normals(t) returns followed by hmcmt_chain_step with hmcmt_rng_draw(t)'s L and u
+ *   hmcmt_chain_run       nsamples times hmcmt_chain_sample in one call: recs[nsamples] (required), models[nsamples][nAC] and preds
+ *                         complex [nsamples][nData] (host, each may be NULL; row i filled behind sample i's decision).  Stops at the
+ *                         first failing sample and returns its code; *done (may be NULL) = the number of valid records
+ * hmcmt_chain_momentum and hmcmt_chain_step keep working on a seeded chain with the host's numbers and do not move t.  Warm-up
+ * adaptation and the accumulators work unchanged: they live in the step's commit.  HMCMT_EINVAL: NULL context, rec, recs or z, no chain,
+ * no seed, Lmin < 1, Lmax < Lmin, nsamples < 0, a call between hmcmt_grad_device_async and hmcmt_wait. */
+extern int hmcmt_rng_draw(uint64_t seed, uint32_t stream, uint64_t t, int32_t Lmin, int32_t Lmax, int32_t* L, double* u);
+extern int hmcmt_rng_normals(uint64_t seed, uint32_t stream, uint64_t t, int64_t a0, int64_t n, double* z);
+extern int hmcmt_chain_seed(hmcmt_ctx* ctx, uint64_t seed, uint32_t stream);
+extern int hmcmt_chain_rng_state(hmcmt_ctx* ctx, uint64_t* seed, uint32_t* stream, uint64_t* t);
+extern int hmcmt_chain_rng_seek(hmcmt_ctx* ctx, uint64_t t);
+extern int hmcmt_chain_normals(hmcmt_ctx* ctx, uint64_t t, double* z, int32_t on_device);
+extern int hmcmt_chain_sample(hmcmt_ctx* ctx, int32_t Lmin, int32_t Lmax, hmcmt_chain_record* rec, double* m_out, double* pred_out);
+extern int hmcmt_chain_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t Lmin, int32_t Lmax, hmcmt_chain_record* recs, double* models,
+                           double* preds, int64_t* done);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -544,6 +544,57 @@ chainSetEnergy!(ctx::HipContext, D::Real, M::Real) =
 chainEnd!(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_chain_end, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
 
 """
+    chain_seed!(ctx, seed, stream=0);  chain_rng_state(ctx) -> (seed, stream, t)
+    chain_sample!(ctx, Lmin, Lmax; mOut=nothing, predOut=nothing) -> HmcmtChainRecord
+    chain_run!(ctx, nsamples, Lmin, Lmax; keepSamples=true) -> (recs, models[nAC, done], preds[nData, done])
+
+The chain's own random numbers (hmcmt_chain_seed, hmcmt_chain_sample, hmcmt_chain_run, include/hmcmt.h): Philox4x32-10 by counter --
+key = seed, counter = (cell or 0xFFFFFFFF, stream, t) -- with the momenta drawn on the GPU and L, u in the library, so that a chain is a
+function of (seed, stream) and the problem alone: the same chain as hmcmt2d_amd/sampler.py's runHMCSampler(library_rng=(seed, stream)),
+sample by sample.  `chain_seed!` comes behind `chainBegin!` (a begin forgets the seed); (seed, stream, t) is all a checkpoint of the
+generator needs.  `chain_run!` is the whole loop in one C call: it stops at the first failing sample, and then throws after cutting
+its results to the `done` valid ones.  `run_chain!(...; seed=(s, c))` runs the sampler this way.
+"""
+chain_seed!(ctx::HipContext, seed::Integer, stream::Integer=0) =
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_seed(ctx.ptr::Ptr{Cvoid}, UInt64(seed)::UInt64, UInt32(stream)::UInt32)::Cint)
+
+function chain_rng_state(ctx::HipContext)
+    seed = Ref{UInt64}(0); stream = Ref{UInt32}(0); t = Ref{UInt64}(0)
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_rng_state(ctx.ptr::Ptr{Cvoid}, seed::Ref{UInt64}, stream::Ref{UInt32}, t::Ref{UInt64})::Cint)
+    return seed[], stream[], t[]
+end
+
+function chain_sample!(ctx::HipContext, Lmin::Integer, Lmax::Integer; mOut::Union{Nothing,Vector{Float64}}=nothing,
+                       predOut::Union{Nothing,Vector{ComplexF64}}=nothing)
+    rec = Ref(HmcmtChainRecord(0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0))
+    pm = mOut === nothing ? Ptr{Float64}(C_NULL) : pointer(mOut)
+    pp = predOut === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(predOut)
+    rc = GC.@preserve mOut predOut @ccall libhmcmt.hmcmt_chain_sample(ctx.ptr::Ptr{Cvoid}, Int32(Lmin)::Int32, Int32(Lmax)::Int32,
+                                                                     rec::Ref{HmcmtChainRecord}, pm::Ptr{Float64}, pp::Ptr{ComplexF64})::Cint
+    checkerr(ctx.ptr, rc)
+    return rec[]
+end
+
+function chain_run!(ctx::HipContext, nsamples::Integer, Lmin::Integer, Lmax::Integer; keepSamples::Bool=true)
+    recs = Vector{HmcmtChainRecord}(undef, nsamples)
+    models = keepSamples ? Matrix{Float64}(undef, ctx.nAC, nsamples) : nothing
+    preds = keepSamples ? Matrix{ComplexF64}(undef, ctx.nData, nsamples) : nothing
+    pm = keepSamples ? pointer(models) : Ptr{Float64}(C_NULL)
+    pp = keepSamples ? pointer(preds) : Ptr{ComplexF64}(C_NULL)
+    done = Ref{Int64}(0)
+    rc = GC.@preserve recs models preds @ccall libhmcmt.hmcmt_chain_run(ctx.ptr::Ptr{Cvoid}, Int64(nsamples)::Int64, Int32(Lmin)::Int32,
+                                                                       Int32(Lmax)::Int32, pointer(recs)::Ptr{HmcmtChainRecord},
+                                                                       pm::Ptr{Float64}, pp::Ptr{ComplexF64}, done::Ref{Int64})::Cint
+    k = Int(done[])
+    resize!(recs, k)
+    if keepSamples
+        models = models[:, 1:k]; preds = preds[:, 1:k]
+    end
+    checkerr(ctx.ptr, rc)
+    return recs, models, preds
+end
+
+"""
     chainHistBegin!(ctx, targets, nbins, lo, hi);  chainHist(ctx, ntarget, nbins) -> (count, counts[nbins, ntarget])
     chainQuantiles(ctx, q, ntarget) -> values[ntarget, nq];  chainDataMomentsBegin!(ctx);  chainDataMoments(ctx) -> (count, mean, m2)
     chain_hist!(ctx, invParam, hmcprior; targets=all cells, nbins=300) -> (targets, nbins, lo, hi)
@@ -723,7 +774,7 @@ end
 chainAdaptEnd!(ctx::HipContext) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_end(ctx.ptr::Ptr{Cvoid})::Cint)
 
 """
-    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt])
+    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, seed=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt])
 
 runHMCSampler (HMCSampler.jl:72-196) through the chain API, step for step what hmcmt2d_amd/sampler.py's device chain does, the
 reference's start included: the chain's state starts at the file's model invParam.strModel (:88), while start and reference model
@@ -738,10 +789,14 @@ result, the named tuple (count, rows, mean, var, cov, corr) -- `nothing` for the
 `nwarmup <= hmcprior.burninsamples` samples and appends a last result, the named tuple (nwarmup, dt, alpha, dtFinal, invM): the step
 size each sample's trajectory used, each sample's acceptance probability, the adapted step size and the diagonal of M^-1 in force
 at the end.  hmcprior.dt is the start and is not modified.
+`seed=(s, c)`: the chain draws its own numbers in the library (`chain_seed!(ctx, s, c)`) and runs through `chain_run!` -- single
+samples with `adapt`, whose trace watches every step.  Julia's generator then draws `rhoref` alone, and the chain is sample by sample
+the one runHMCSampler(device_chain=True, library_rng=(s, c)) gives for the same rhoref.  Column it + 1 of hmstats takes its K from
+sample it + 1's record; the last column's K is NaN (that momentum is never drawn).
 """
 function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior, hmcParam::HMCParameter; keepSamples::Bool=true,
-                    rhoref::Union{Nothing,Real}=nothing, cov::Union{Nothing,NamedTuple}=nothing,
-                    adapt::Union{Nothing,NamedTuple}=nothing)
+                    rhoref::Union{Nothing,Real}=nothing, seed::Union{Nothing,Tuple{<:Integer,<:Integer}}=nothing,
+                    cov::Union{Nothing,NamedTuple}=nothing, adapt::Union{Nothing,NamedTuple}=nothing)
     n, nd = ctx.nAC, ctx.nData
     nsamples = hmcprior.totalsamples
     fileModel = Vector{Float64}(invParam.strModel)
@@ -769,20 +824,36 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
         chainAdaptBegin!(ctx, nwarmup; Base.structdiff(adapt, NamedTuple{(:nwarmup,)})...)
         adaptDt = fill(NaN, nsamples); adaptAlpha = zeros(nsamples)
     end
-    K = chainMomentum!(ctx, z)
     ncols = keepSamples ? nsamples : 0
     hmcmodel = zeros(Float64, n, ncols)
     hmcdata = zeros(ComplexF64, nd, ncols + 1)
     hmcdata[:, 1] = predStart
     hmcstats = initHMCStatus(nsamples)
-    hmcstats.hmstats[:, 1] = [D, M, K, D + M + K]
+    if seed === nothing
+        K = chainMomentum!(ctx, z)
+        hmcstats.hmstats[:, 1] = [D, M, K, D + M + K]
+    else
+        chain_seed!(ctx, seed[1], seed[2])                   # (behind the begins: a begin forgets the seed; z is not used)
+    end
     mOut = keepSamples ? Vector{Float64}(undef, n) : nothing
     predOut = keepSamples ? Vector{ComplexF64}(undef, nd) : nothing
+    Lmin, Lmax = hmcprior.timestep[1], hmcprior.timestep[2]
+    # the library's numbers: the whole run in one call, or sample by sample where the warm-up's trace watches every step
+    seededRecs = (seed === nothing || adapt !== nothing) ? nothing : chain_run!(ctx, nsamples, Lmin, Lmax; keepSamples=keepSamples)
     for it = 1:nsamples
-        L = rand(hmcprior.timestep[1]:hmcprior.timestep[2])
-        u = rand()
         adapt === nothing || (adaptDt[it] = chainAdaptInfo(ctx).dt)
-        rec = chainStep!(ctx, L, u; mOut=mOut, predOut=predOut)
+        if seed === nothing
+            L = rand(Lmin:Lmax)
+            u = rand()
+            rec = chainStep!(ctx, L, u; mOut=mOut, predOut=predOut)
+        elseif seededRecs === nothing
+            rec = chain_sample!(ctx, Lmin, Lmax; mOut=mOut, predOut=predOut)
+        else
+            rec = seededRecs[1][it]
+            if keepSamples
+                mOut = seededRecs[2][:, it]; predOut = seededRecs[3][:, it]
+            end
+        end
         adapt === nothing || (adaptAlpha[it] = rec.hdif > 0 ? 1.0 : exp(rec.hdif))
         hmcprior.nfevals += rec.nfevals
         if rec.accepted == 1
@@ -791,8 +862,14 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
         else
             hmcstats.nReject += 1
         end
-        K = chainMomentum!(ctx, randn(n))
-        hmcstats.hmstats[:, it + 1] = [rec.D, rec.M, K, rec.D + rec.M + K]
+        if seed === nothing
+            K = chainMomentum!(ctx, randn(n))
+            hmcstats.hmstats[:, it + 1] = [rec.D, rec.M, K, rec.D + rec.M + K]
+        else
+            hmcstats.hmstats[3:4, it] = [rec.K0, hmcstats.hmstats[1, it] + hmcstats.hmstats[2, it] + rec.K0]
+            hmcstats.hmstats[:, it + 1] = [rec.D, rec.M, NaN, NaN]
+            it == 1 && (hmcstats.hmstats[:, 1] = [D, M, rec.K0, D + M + rec.K0])
+        end
         if keepSamples
             hmcmodel[:, it] = mOut
             hmcdata[:, it + 1] = rec.accepted == 1 ? predOut : hmcdata[:, it]      # (:164-168: a rejection repeats the column)
