@@ -64,6 +64,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_path.h"
 #include "kernels_mass.h"
 #include "kernels_chain.h"
+#include "kernels_nuts.h"
 #include "kernels_jac.h"
 #include "kernels_jvp.h"
 
@@ -342,6 +343,21 @@ struct hmcmt_ctx {
             double *d_mean = nullptr, *d_m2 = nullptr;   // [nAC] each: the window's Welford accumulator (adapt_mass)
             std::vector<void*> allocs;
         } adapt;
+        struct Nuts {                                 // hmcmt_chain_nuts_*: the tree's buffers, allocated at the first NUTS sample, released with the chain
+            bool ready = false;
+            double *d_m[2] = {nullptr, nullptr}, *d_p[2] = {nullptr, nullptr};   // [nAC] the ends, [0] backward (momentum stored negated), [1] forward
+            double *d_x[2] = {nullptr, nullptr}, *d_g[2] = {nullptr, nullptr};   // [nAC] M^-1 p of an end (non-diagonal mass), its data gradient
+            double *d_g0 = nullptr;                   // [nAC] the start state's gradient
+            double *d_rho[2] = {nullptr, nullptr}, *d_rhoS = nullptr;            // [nAC] the tree's momentum sum and its successor, the subtree's
+            double *d_ck[NUTS_CK_MAX][3] = {};        // [nAC] each: the checkpoints' p, x, rhoS
+            double *d_selM[2] = {nullptr, nullptr}, *d_selG[2] = {nullptr, nullptr}, *d_selPred[2] = {nullptr, nullptr};   // captures: tree / subtree
+            double *d_pred = nullptr;                 // [2 nData] the leaf's predicted data
+            double *d_part = nullptr, *d_scal = nullptr;   // [NUTS_NQ][LFNB], [NUTS_SCAL]
+            double *h_scal = nullptr;                 // pinned [NUTS_SCAL]
+            long long its[2] = {0, 0}, solves[2] = {0, 0};   // measurement (hmcmt_debug_nuts_iters): solver iterations and solves of the leaves
+                                                      //   [1] that follow a change of direction, [0] of the others
+            std::vector<void*> allocs;
+        } nuts;
     } chain;
     int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)

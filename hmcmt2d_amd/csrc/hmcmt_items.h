@@ -1183,6 +1183,158 @@ HD double item_mass_lr_expand(const double* s, const double* x, const double* U,
     return op == 0 ? s[a] * acc : acc / s[a];
 }
 
+// ----------------------------------------------------------------------------------------------
+// the No-U-turn sampler of the device chain (hmcmt_chain_nuts_*, kernels_nuts.h: k_nuts_leaf, k_nuts_final; include/hmcmt.h has the
+// algorithm): the draws, one cell's share of a leaf's sums, and the scalar state machine of the host
+// ----------------------------------------------------------------------------------------------
+constexpr int NUTS_DEPTH_MAX = 10;     // == HMCMT_NUTS_DEPTH_MAX
+constexpr int NUTS_CK_MAX = 9;         // checkpoint slots: popcount(i >> 1) of an even leaf i < 2^(NUTS_DEPTH_MAX - 1) is at most 8
+constexpr int NUTS_GROUP = 4;          // due checkpoints a thread takes per pass over the cells (registers, indexed at compile time)
+constexpr int NUTS_NACC = 3 + 2 * NUTS_GROUP;       // accumulators of a pass: p.x, the merged tree's pair, two per checkpoint
+constexpr int NUTS_NQ = 3 + 2 * NUTS_CK_MAX;        // sums of a leaf: q = 0 p.x; 1, 2 x.rho' and x_other.rho' of the merged tree;
+                                                    //   3 + 2c, 4 + 2c x_ck.span and x.span of the c-th due checkpoint
+// scalars of one leaf, device side: what the evaluation left, the sample's K0, then the NUTS_NQ sums
+enum { NS_D1 = 0, NS_M1 = 1, NS_FLAG = 2, NS_K0 = 3, NS_SUM = 4, NUTS_SCAL = NS_SUM + NUTS_NQ };
+constexpr uint32_t RNG_C0_NUTS_LEAF = 0x80000000u, RNG_C0_NUTS_DIR = 0xC0000000u;
+// the sample's draws beside the momentum: kind 0, doubling j -- its direction and the uniform of its merge; kind 1, the sample's l-th
+// leaf -- the uniform of its selection inside the subtree
+HD void item_rng_nuts(uint64_t seed, uint32_t stream, uint64_t t, int kind, uint32_t index, int* forward, double* u) {
+    uint32_t x[4];
+    item_rng_block(seed, stream, t, (kind == 0 ? RNG_C0_NUTS_DIR : RNG_C0_NUTS_LEAF) + index, x);
+    *u = item_rng_u52(x[0], x[1]);
+    *forward = kind == 0 ? (int)(x[2] >> 31) : 0;
+}
+
+// One leaf's pass over the cells.  Momenta and x = M^-1 p are in the forward-time sign: the moving end stores sign * p (the backward
+// end integrates the same map on -p), and so does the other end with signOther.
+struct NutsLeaf {
+    int n;
+    int first;                     // leaf 0 of its subtree: rhoS = p, else rhoS += p
+    int merged;                    // the subtree's last leaf: rhoNext = rho + rhoS and the two products of the merged tree
+    int ndue;                      // due checkpoints of this pass (<= NUTS_GROUP), the first of them is the leaf's q0-th
+    int q0;
+    double sign, signOther;
+    const double* p;               // [n] the moving end's stored momentum
+    const double* x;               // [n] M^-1 of it, or nullptr: the diagonal invM
+    const double* invM;            // [n]
+    double* rhoS;                  // [n] the subtree's momentum sum
+    double *ckP, *ckX, *ckR;       // an even leaf's checkpoint (p, x, rhoS), nullptr on an odd leaf
+    const double *dueP[NUTS_GROUP], *dueX[NUTS_GROUP], *dueR[NUTS_GROUP];
+    const double* rho;             // [n] the tree's momentum sum
+    double* rhoNext;               // [n]
+    const double *pOther, *xOther; // the end that stands still (xOther nullptr: the diagonal invM)
+    double* part;                  // [NUTS_NQ][CHAIN_NB]
+};
+// cell a of a leaf's pass.  FIRST: the pass that updates rhoS, writes the checkpoint and forms p.x and the merged tree's pair; the
+// further passes of a leaf with more than NUTS_GROUP due checkpoints only read.  acc[0 .. 3) belong to FIRST, acc[3 + 2c], acc[4 + 2c]
+// to the pass's c-th checkpoint; every term enters by one fma.
+template <int NCK, bool FIRST>
+HD void item_nuts_cell(const NutsLeaf& L, int a, double (&acc)[NUTS_NACC]) {
+    const double ps = L.p[a];
+    const double p = L.sign * ps, x = L.sign * (L.x ? L.x[a] : L.invM[a] * ps);
+    double rs;
+    if (FIRST) {
+        rs = L.first ? p : L.rhoS[a] + p;
+        L.rhoS[a] = rs;
+        if (L.ckP) { L.ckP[a] = p; L.ckX[a] = x; L.ckR[a] = rs; }
+        acc[0] = fma(p, x, acc[0]);
+        if (L.merged) {
+            const double po = L.pOther[a];
+            const double xo = L.signOther * (L.xOther ? L.xOther[a] : L.invM[a] * po);
+            const double rn = L.rho[a] + rs;
+            L.rhoNext[a] = rn;
+            acc[1] = fma(x, rn, acc[1]);
+            acc[2] = fma(xo, rn, acc[2]);
+        }
+    } else {
+        rs = L.rhoS[a];
+    }
+#pragma unroll
+    for (int c = 0; c < NCK; ++c) {
+        const double span = (rs - L.dueR[c][a]) + L.dueP[c][a];
+        acc[3 + 2 * c] = fma(L.dueX[c][a], span, acc[3 + 2 * c]);
+        acc[4 + 2 * c] = fma(x, span, acc[4 + 2 * c]);
+    }
+}
+// row of `part` that accumulator q of a pass lands in
+HD int item_nuts_row(const NutsLeaf& L, int q) { return q < 3 ? q : q + 2 * L.q0; }
+
+// The checkpoints of leaf i of a subtree: an even leaf stores slot popcount(i >> 1); an odd leaf checks *ndue = (trailing ones of i)
+// slots, from *slot = popcount(i >> 1) downwards -- the spans [i + 1 - 2^s, i], s = 1 .. ndue, each once.
+HD void item_nuts_checkpoints(int i, int* slot, int* ndue) {
+    int k = 0;
+    for (int v = i >> 1; v; v >>= 1) k += v & 1;
+    int t = 0;
+    for (int v = i; v & 1; v >>= 1) ++t;
+    *slot = k;
+    *ndue = t;
+}
+
+HD double item_nuts_logaddexp(double a, double b) {
+    if (a == -INFINITY) return b;
+    if (b == -INFINITY) return a;
+    return a > b ? a + log1p(exp(b - a)) : b + log1p(exp(a - b));
+}
+// The tree of one sample, host scalars.  Times are signed leapfrog steps from the start state.
+struct NutsTree {
+    int maxDepth = 0;
+    double H0 = 0;
+    int depth = 0, nleaves = 0, stop = -1;         // stop < 0: growing
+    uint32_t dirs = 0;
+    long long selected = 0, tMinus = 0, tPlus = 0;
+    double logW = 0, alphaSum = 0;
+    // the doubling at hand
+    int forward = 0, i = 0;                        // i: the next leaf of the subtree
+    long long selS = 0;
+    double logWs = -INFINITY;
+};
+HD void item_nuts_begin(NutsTree& T, int maxDepth, double H0) {
+    T = NutsTree{};
+    T.maxDepth = maxDepth;
+    T.H0 = H0;
+}
+HD void item_nuts_doubling(NutsTree& T, int forward) {
+    T.forward = forward;
+    if (forward) T.dirs |= 1u << T.depth;
+    T.i = 0;
+    T.logWs = -INFINITY;
+}
+// Leaf T.i of the doubling with energy H, its uniform u and its sums (NUTS_NQ, rows as in NutsLeaf).  Returns 0 the subtree goes on,
+// 1 it is complete (item_nuts_merge follows), -1 the sample has stopped (T.stop); *take: the leaf is the subtree's selection.
+HD int item_nuts_leaf(NutsTree& T, double H, double u, const double* sums, bool* take) {
+    const double delta = T.H0 - H;
+    const int i = T.i;
+    *take = false;
+    ++T.nleaves;
+    if (!std::isfinite(delta) || -delta > 1000.0) { T.stop = 3; return -1; }
+    T.alphaSum += delta > 0 ? 1.0 : exp(delta);
+    T.logWs = item_nuts_logaddexp(T.logWs, delta);
+    if (i == 0 || u < exp(delta - T.logWs)) {
+        *take = true;
+        T.selS = T.forward ? T.tPlus + i + 1 : T.tMinus - i - 1;
+    }
+    int slot, ndue;
+    item_nuts_checkpoints(i, &slot, &ndue);
+    if (i & 1)
+        for (int c = 0; c < ndue; ++c)
+            if (!(sums[3 + 2 * c] > 0.0) || !(sums[4 + 2 * c] > 0.0)) { T.stop = 1; return -1; }
+    T.i = i + 1;
+    return T.i == (1 << T.depth) ? 1 : 0;
+}
+// The completed subtree joins the tree: u is the doubling's uniform, sums the last leaf's.  *take: the subtree's selection becomes the
+// tree's.  Returns 0 the tree doubles again, -1 the sample has stopped.
+HD int item_nuts_merge(NutsTree& T, double u, const double* sums, bool* take) {
+    const double d = T.logWs - T.logW;
+    *take = u < exp(d < 0 ? d : 0.0);
+    if (*take) T.selected = T.selS;
+    T.logW = item_nuts_logaddexp(T.logW, T.logWs);
+    if (T.forward) T.tPlus += 1LL << T.depth; else T.tMinus -= 1LL << T.depth;
+    ++T.depth;
+    if (!(sums[1] > 0.0) || !(sums[2] > 0.0)) { T.stop = 2; return -1; }
+    if (T.depth == T.maxDepth) { T.stop = 0; return -1; }
+    return 0;
+}
+
 
 // ---- initial guess extrapolated along the model path (kernels_fused.h: k_extrap_prepare, k_extrap) ----
 #if !defined(__HIPCC__)

@@ -7,7 +7,9 @@
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
 // k_chain_hist, a second k_chain_welford (the predicted data), k_chain_acov (lagged autocovariances) and k_chain_cov_commit (cross
 // moments; every `batch` commits k_chain_cov_flush) behind them.  During a warm-up (hmcmt_chain_adapt_*) a k_chain_welford on the
-// window's buffers inside a window and k_chain_adapt_mass at a window's end follow the commit.
+// window's buffers inside a window and k_chain_adapt_mass at a window's end follow the commit.  A NUTS sample (hmcmt_chain_nuts_sample,
+// kernels_nuts.h) chooses its trajectory length: per leaf leapfrog_core(L = 1) with its wait for the solver records, k_nuts_leaf, k_nuts_final,
+// NUTS_SCAL scalars down and one wait more; it ends in the same commit.
 //
 // The four accumulators share their host scaffolding, which stands in front of them: ChainTimer (the event pairs of the measurement
 // hooks), chain_acc_alloc / chain_acc_free (each accumulator's struct owns its buffers through `allocs`), chain_acc_ready (the
@@ -221,11 +223,13 @@ static void chain_acc_release(hmcmt_ctx* ctx) {
 static void chain_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     chain_acc_release(ctx);
-    if (!C.allocs.empty() || C.h_rec) {
+    if (!C.allocs.empty() || C.h_rec || !C.nuts.allocs.empty() || C.nuts.h_scal) {
         hipSetDevice(ctx->cfg.device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be running on the buffers)
         for (void* p : C.allocs) hipFree(p);
         if (C.h_rec) hipHostFree(C.h_rec);
+        chain_acc_free(C.nuts.allocs);
+        if (C.nuts.h_scal) hipHostFree(C.nuts.h_scal);
     }
     C = hmcmt_ctx::Chain{};
 }
@@ -260,14 +264,14 @@ static int chain_fail(hmcmt_ctx* ctx, int rc) {
 }
 
 // One counted step of the warm-up (hmcmt.h: 1. to 5.), behind the decision and the commit: launches on the context's stream and scalar
-// host work, no wait.  The mass kernel runs behind the commit, in front of the next k_chain_momentum.
-static void chain_adapt_step(hmcmt_ctx* ctx, double hdif) {
+// host work, no wait.  alpha: the step's acceptance probability min(1, exp(hdif)), a NUTS sample's mean over its leaves.  The mass
+// kernel runs behind the commit, in front of the next k_chain_momentum.
+static void chain_adapt_step(hmcmt_ctx* ctx, double alpha) {
     auto& C = ctx->chain;
     auto& A = C.adapt;
     const hmcmt_adapt_options& o = A.opt;
     const int n = ctx->v.nAC;
     hipStream_t st = ctx->stream;
-    const double alpha = hdif > 0 ? 1.0 : std::exp(hdif);
     A.alphaLast = alpha;
     A.alphaSum += alpha;
     const bool inWindow = o.adapt_mass && A.c >= o.init_buffer && A.c < o.nwarmup - o.term_buffer;
@@ -457,33 +461,12 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
     return chain_step_decide(ctx, u, S, rec, m_out, pred_out);
 }
 
-// The step behind its launches: the sample's one wait, the record's checks, the accept test with u, the commit (enqueued), the outputs.
-// K0 is the record's: what hmcmt_chain_momentum returned, bit for bit, and the only place hmcmt_chain_sample reads it.
-static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, hmcmt_chain_record* rec, double* m_out, double* pred_out) {
+// The commit of a sample behind its decision, shared by hmcmt_chain_step and the NUTS sample: the counters, the moments and the
+// optional accumulators with the chain's current model -- enqueued, not waited for.
+static void chain_commit(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     hipStream_t st = ctx->stream;
-    const int prop = C.cur ^ 1, startGrad = S.startGrad, evals = S.evals;
-    int rc;
-    HIPCHK(hipStreamSynchronize(st));                        // the step's one wait
-    HIPCHK(hipGetLastError());
-    prof_collect(ctx);
-    if ((rc = leapfrog_flag(ctx))) return chain_fail(ctx, rc);
-    const double K0 = C.h_rec[CH_K0], K1 = C.h_rec[CH_K1], D1 = C.h_rec[CH_D1], M1 = C.h_rec[CH_M1];
-    if (!std::isfinite(K0)) {                                // (a host-fed momentum has failed in hmcmt_chain_momentum already)
-        ctx->err = "non-finite kinetic energy of the drawn momentum (the diagonal of M^-1 must be positive)";
-        return chain_fail(ctx, HMCMT_EBREAKDOWN);
-    }
-    if (C.h_rec[CH_FLAG] != 0.0 || !std::isfinite(K1) || !std::isfinite(D1) || !std::isfinite(M1)) {
-        ctx->err = "non-finite model value or Hamiltonian term at the proposal";
-        return chain_fail(ctx, HMCMT_EBREAKDOWN);
-    }
-    ctx->lfHaveGrad = true;
-    const double hdif = (C.D + C.M + K0) - (D1 + K1 + M1);
-    const bool accepted = hdif > 0 || u < std::exp(hdif);
-    if (accepted) { C.cur = prop; C.D = D1; C.M = M1; }
-    C.nextStart = accepted ? 1 : 2;
-    // the commit: enqueued, not waited for
     ++C.nsamples;
     if (C.nsamples > C.burnin) {
         ++C.nmoments;
@@ -516,7 +499,36 @@ static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, 
             if (++V.npend == V.B) chain_cov_flush(ctx);
         }
     }
-    if (C.adapt.active) chain_adapt_step(ctx, hdif);
+}
+
+// The step behind its launches: the sample's one wait, the record's checks, the accept test with u, the commit (enqueued), the outputs.
+// K0 is the record's: what hmcmt_chain_momentum returned, bit for bit, and the only place hmcmt_chain_sample reads it.
+static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, hmcmt_chain_record* rec, double* m_out, double* pred_out) {
+    auto& C = ctx->chain;
+    const int n = ctx->v.nAC, nData = ctx->v.nData;
+    hipStream_t st = ctx->stream;
+    const int prop = C.cur ^ 1, startGrad = S.startGrad, evals = S.evals;
+    int rc;
+    HIPCHK(hipStreamSynchronize(st));                        // the step's one wait
+    HIPCHK(hipGetLastError());
+    prof_collect(ctx);
+    if ((rc = leapfrog_flag(ctx))) return chain_fail(ctx, rc);
+    const double K0 = C.h_rec[CH_K0], K1 = C.h_rec[CH_K1], D1 = C.h_rec[CH_D1], M1 = C.h_rec[CH_M1];
+    if (!std::isfinite(K0)) {                                // (a host-fed momentum has failed in hmcmt_chain_momentum already)
+        ctx->err = "non-finite kinetic energy of the drawn momentum (the diagonal of M^-1 must be positive)";
+        return chain_fail(ctx, HMCMT_EBREAKDOWN);
+    }
+    if (C.h_rec[CH_FLAG] != 0.0 || !std::isfinite(K1) || !std::isfinite(D1) || !std::isfinite(M1)) {
+        ctx->err = "non-finite model value or Hamiltonian term at the proposal";
+        return chain_fail(ctx, HMCMT_EBREAKDOWN);
+    }
+    ctx->lfHaveGrad = true;
+    const double hdif = (C.D + C.M + K0) - (D1 + K1 + M1);
+    const bool accepted = hdif > 0 || u < std::exp(hdif);
+    if (accepted) { C.cur = prop; C.D = D1; C.M = M1; }
+    C.nextStart = accepted ? 1 : 2;
+    chain_commit(ctx);
+    if (C.adapt.active) chain_adapt_step(ctx, hdif > 0 ? 1.0 : std::exp(hdif));
     C.gen = ctx->stateGen;
     rec->accepted = accepted ? 1 : 0;
     rec->nfevals = evals - (startGrad != 0 ? 1 : 0);
@@ -685,6 +697,319 @@ int hmcmt_chain_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t Lmin, int32_t Lmax
             return rc;
         if (done) *done = i + 1;
     }
+    return 0;
+}
+
+// ---- the No-U-turn sampler (hmcmt.h has the algorithm; kernels_nuts.h; hmcmt_items.h: item_nuts_*) ---------------------------------------
+// A sample = the momentum of draw t, then leaf by leaf: leapfrog_core(L = 1) on the moving end's own (m, p) with the gradient kept in
+// ctx->d_g (it ends in collect_pending's wait for the evaluation's solver records, as every trajectory does -- once per leaf here, once
+// per L steps there), the mass application, k_nuts_leaf, k_nuts_final, one copy of NUTS_SCAL scalars, the leaf's own wait, and the host's decision
+// (item_nuts_leaf / item_nuts_merge).  Captures (model, predicted data, gradient) are enqueued behind the decision, in front of the next
+// leaf.  The sample ends in chain_commit.
+int hmcmt_rng_nuts(uint64_t seed, uint32_t stream, uint64_t t, int32_t kind, uint32_t index, int32_t* forward, double* u) {
+    if ((kind != 0 && kind != 1) || (kind == 0 && index >= 32u) || (kind == 1 && index >= 0x40000000u)) return HMCMT_EINVAL;
+    int f = 0;
+    double uu = 0.0;
+    item_rng_nuts(seed, stream, t, kind, index, &f, &uu);
+    if (forward) *forward = f;
+    if (u) *u = uu;
+    return 0;
+}
+
+// the tree's buffers, through the chain's allocator; a failure frees what it got and leaves the chain as it was
+static int chain_nuts_alloc(hmcmt_ctx* ctx, const char* fn) {
+    auto& N = ctx->chain.nuts;
+    if (N.ready) return 0;
+    const size_t vb = sizeof(double) * std::max<size_t>((size_t)ctx->v.nAC, 1), pb = sizeof(double) * std::max<size_t>((size_t)2 * ctx->v.nData, 1);
+    std::vector<std::pair<double**, size_t>> bufs = {{&N.d_g0, vb}, {&N.d_rhoS, vb}, {&N.d_pred, pb},
+                                                     {&N.d_part, sizeof(double) * NUTS_NQ * LFNB}, {&N.d_scal, sizeof(double) * NUTS_SCAL}};
+    for (int e = 0; e < 2; ++e) {
+        for (double** q : {&N.d_m[e], &N.d_p[e], &N.d_x[e], &N.d_g[e], &N.d_rho[e], &N.d_selM[e], &N.d_selG[e]}) bufs.push_back({q, vb});
+        bufs.push_back({&N.d_selPred[e], pb});
+    }
+    for (int k = 0; k < NUTS_CK_MAX; ++k)
+        for (int v = 0; v < 3; ++v) bufs.push_back({&N.d_ck[k][v], vb});
+    int rc = 0;
+    for (const auto& b : bufs)
+        if ((rc = chain_acc_zeroed(ctx, fn, N.allocs, (void**)b.first, b.second))) break;
+    if (!rc && hipHostMalloc((void**)&N.h_scal, sizeof(double) * NUTS_SCAL, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        N.h_scal = nullptr;
+        ctx->err = std::string(fn) + ": pinned allocation failed";
+        rc = HMCMT_ENOMEM;
+    }
+    if (rc) {
+        const std::string e = ctx->err;
+        (void)hipStreamSynchronize(ctx->stream);
+        chain_acc_free(N.allocs);
+        N = {};
+        ctx->err = e;
+        return rc;
+    }
+    N.ready = true;
+    return 0;
+}
+
+// the launches of one leaf's sums behind its step: the passes of k_nuts_leaf (NUTS_GROUP due checkpoints each), k_nuts_final
+static void nuts_leaf_launch(hipStream_t st, NutsLeaf L, int ndue, const double* const (*due)[3], const double* partK0, const double* misfit,
+                             const double* mnorm, const int* flag, double* scal) {
+    for (int c0 = 0; c0 == 0 || c0 < ndue; c0 += NUTS_GROUP) {
+        const int nc = std::max(0, std::min(NUTS_GROUP, ndue - c0));
+        L.ndue = nc;
+        L.q0 = c0;
+        for (int c = 0; c < NUTS_GROUP; ++c) {
+            L.dueP[c] = c < nc ? due[c0 + c][0] : nullptr;
+            L.dueX[c] = c < nc ? due[c0 + c][1] : nullptr;
+            L.dueR[c] = c < nc ? due[c0 + c][2] : nullptr;
+        }
+        static_assert(NUTS_GROUP == 4, "one instantiation of k_nuts_leaf per number of checkpoints in a pass below");
+        switch (nc + (c0 == 0 ? 0 : 8)) {
+#define HMCMT_NUTS_LEAF(NC, FIRST, CASE) \
+    case CASE: hipLaunchKernelGGL((k_nuts_leaf<NC, FIRST>), dim3(LFNB), dim3(256), 0, st, L); break;
+            HMCMT_NUTS_LEAF(0, true, 0) HMCMT_NUTS_LEAF(1, true, 1) HMCMT_NUTS_LEAF(2, true, 2) HMCMT_NUTS_LEAF(3, true, 3) HMCMT_NUTS_LEAF(4, true, 4)
+            HMCMT_NUTS_LEAF(1, false, 9) HMCMT_NUTS_LEAF(2, false, 10) HMCMT_NUTS_LEAF(3, false, 11) HMCMT_NUTS_LEAF(4, false, 12)
+#undef HMCMT_NUTS_LEAF
+        }
+    }
+    hipLaunchKernelGGL(k_nuts_final, dim3(1), dim3(64), 0, st, 3 + 2 * ndue, L.part, partK0, misfit, mnorm, flag, scal);
+}
+
+// one NUTS sample with the chain's own numbers; fn: the entry point the messages name
+static int chain_nuts_sample(hmcmt_ctx* ctx, const char* fn, int32_t maxDepth, hmcmt_nuts_record* rec, double* m_out, double* pred_out) {
+    auto& C = ctx->chain;
+    auto& N = C.nuts;
+    const int n = ctx->v.nAC, nData = ctx->v.nData;
+    hipStream_t st = ctx->stream;
+    const size_t vb = sizeof(double) * (size_t)n, pb = sizeof(double) * 2 * (size_t)nData;
+    const uint64_t t = C.t++;                                // the draw is consumed, whatever happens
+    C.haveMomentum = false;
+    int rc = chain_nuts_alloc(ctx, fn);
+    if (rc) return rc;                                       // (nothing is in flight: the chain stays usable)
+    if ((rc = chain_momentum_enqueue(ctx, &t))) { ctx->err = std::string(fn) + ": " + ctx->err; return chain_fail(ctx, rc); }
+    // the start gradient into ctx->d_g: what the last decision left on the device, or one evaluation
+    const int startGrad = (C.gen == ctx->stateGen && ctx->lfHaveGrad) ? C.nextStart : 0;
+    C.nextStart = 0;
+    ctx->lfHaveGrad = false;
+    int evals = 0;
+    if (startGrad == 0) {
+        if ((rc = evaluate(ctx, C.d_m[C.cur], true, nullptr, nullptr, ctx->d_g)) || (rc = collect_stats(ctx, true)) || (rc = finish_status(ctx)))
+            return chain_fail(ctx, rc);
+        ++evals;
+    } else if (startGrad == 2) {
+        HIPCHK(hipMemcpyAsync(ctx->d_g, ctx->d_gStart, vb, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(N.d_g0, ctx->d_g, vb, hipMemcpyDeviceToDevice, st));
+    const bool diag = ctx->mass.kind == HMCMT_MASS_DIAGONAL;
+    hipLaunchKernelGGL(k_nuts_begin, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_m[C.cur], C.d_p, diag ? nullptr : ctx->mass.d_x, N.d_m[0], N.d_m[1],
+                       N.d_p[0], N.d_p[1], N.d_x[0], N.d_x[1], N.d_rho[0]);
+    int rho = 0;                                             // d_rho[rho]: the tree's momentum sum
+    int selTree = 0;                                         // d_sel*[selTree]: the tree's selection once it has left the start, [selTree ^ 1]: the subtree's
+    int gOwner = -1;                                         // the end whose gradient ctx->d_g holds (-1: the start's, both ends')
+    bool moved[2] = {false, false};                          // the end has left the start: its gradient is in d_g or saved in N.d_g[end]
+    NutsTree T;
+    item_nuts_begin(T, maxDepth, 0.0);                       // (H0 follows with the first leaf's scalars, which bring K0)
+    double K0 = 0, selS[3] = {0, 0, 0}, sel[3] = {0, 0, 0};  // K, D, M at the subtree's / the tree's selection
+    uint32_t leaf = 0;
+    int unused = 0;                                          // (a leaf's draw has no direction)
+    bool first = true;
+    while (true) {
+        int forward = 0;
+        double uj = 0, ul = 0;
+        item_rng_nuts(C.seed, C.stream, t, 0, (uint32_t)T.depth, &forward, &uj);
+        item_nuts_doubling(T, forward);
+        const int d = forward, nl = 1 << T.depth;
+        int status = 0;
+        for (int i = 0; i < nl; ++i) {
+            const int changed = gOwner >= 0 && gOwner != d;
+            if (gOwner != d) {                               // the gradient's hand-over where the direction changes
+                if (gOwner >= 0) HIPCHK(hipMemcpyAsync(N.d_g[gOwner], ctx->d_g, vb, hipMemcpyDeviceToDevice, st));
+                if (gOwner >= 0) HIPCHK(hipMemcpyAsync(ctx->d_g, moved[d] ? N.d_g[d] : N.d_g0, vb, hipMemcpyDeviceToDevice, st));
+                gOwner = d;
+            }
+            int le = 0;
+            if ((rc = leapfrog_core(ctx, N.d_m[d], N.d_p[d], C.dt, 1, C.regParam, C.lo, C.hi, 1, N.d_pred, C.d_scal + CH_D1, &le))) return chain_fail(ctx, rc);
+            moved[d] = true;
+            ++evals;                                         // (le counts the kept start gradient too)
+            N.its[changed] += (long long)ctx->stats.iters_fwd_sum + ctx->stats.iters_adj_sum;
+            N.solves[changed] += 2LL * ctx->stats.nsystems;
+            if (!diag && (rc = mass_apply_dev(ctx, HMCMT_MASS_OP_INV, N.d_p[d], N.d_x[d]))) return chain_fail(ctx, rc);
+            int slot = 0, ndue = 0;
+            item_nuts_checkpoints(i, &slot, &ndue);
+            NutsLeaf L{};
+            L.n = n; L.first = i == 0; L.merged = i == nl - 1;
+            L.sign = d ? 1.0 : -1.0; L.signOther = d ? -1.0 : 1.0;
+            L.p = N.d_p[d]; L.x = diag ? nullptr : N.d_x[d]; L.invM = ctx->d_invM;
+            L.rhoS = N.d_rhoS;
+            const double* due[NUTS_CK_MAX][3] = {};
+            if (i & 1) {
+                for (int c = 0; c < ndue; ++c)
+                    for (int v = 0; v < 3; ++v) due[c][v] = N.d_ck[slot - c][v];
+            } else {
+                L.ckP = N.d_ck[slot][0]; L.ckX = N.d_ck[slot][1]; L.ckR = N.d_ck[slot][2];
+                ndue = 0;
+            }
+            L.rho = N.d_rho[rho]; L.rhoNext = N.d_rho[rho ^ 1];
+            L.pOther = N.d_p[d ^ 1]; L.xOther = diag ? nullptr : N.d_x[d ^ 1];
+            L.part = N.d_part;
+            nuts_leaf_launch(st, L, ndue, due, C.d_part, C.d_scal + CH_D1, ctx->d_lfScal, ctx->d_lfFlag, N.d_scal);
+            HIPCHK(hipMemcpyAsync(N.h_scal, N.d_scal, sizeof(double) * NUTS_SCAL, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));                // the leaf's one wait
+            HIPCHK(hipGetLastError());
+            prof_collect(ctx);
+            if ((rc = leapfrog_flag(ctx))) return chain_fail(ctx, rc);
+            const double* h = N.h_scal;
+            if (first) {
+                K0 = h[NS_K0];
+                if (!std::isfinite(K0)) {
+                    ctx->err = "non-finite kinetic energy of the drawn momentum (the diagonal of M^-1 must be positive)";
+                    return chain_fail(ctx, HMCMT_EBREAKDOWN);
+                }
+                T.H0 = C.D + C.M + K0;
+                first = false;
+            }
+            const double K1 = 0.5 * h[NS_SUM], D1 = h[NS_D1], M1 = h[NS_M1];
+            const double H = h[NS_FLAG] != 0.0 ? NAN : D1 + K1 + M1;
+            item_rng_nuts(C.seed, C.stream, t, 1, leaf++, &unused, &ul);
+            bool take = false;
+            status = item_nuts_leaf(T, H, ul, h + NS_SUM, &take);
+            if (status < 0) break;
+            if (take) {                                      // the capture: the leaf is the subtree's selection
+                const int s = selTree ^ 1;
+                HIPCHK(hipMemcpyAsync(N.d_selM[s], N.d_m[d], vb, hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(N.d_selPred[s], N.d_pred, pb, hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(N.d_selG[s], ctx->d_g, vb, hipMemcpyDeviceToDevice, st));
+                selS[0] = K1; selS[1] = D1; selS[2] = M1;
+            }
+        }
+        if (status < 0) break;
+        bool take = false;
+        status = item_nuts_merge(T, uj, N.h_scal + NS_SUM, &take);
+        if (take) { selTree ^= 1; sel[0] = selS[0]; sel[1] = selS[1]; sel[2] = selS[2]; }
+        rho ^= 1;
+        if (status < 0) break;
+    }
+    // the decision: the selected state becomes the chain's, and its gradient the next sample's start gradient
+    const bool movedOn = T.selected != 0;
+    const int prop = C.cur ^ 1;
+    if (movedOn) {
+        HIPCHK(hipMemcpyAsync(C.d_m[prop], N.d_selM[selTree], vb, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(C.d_pred[prop], N.d_selPred[selTree], pb, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(ctx->d_g, N.d_selG[selTree], vb, hipMemcpyDeviceToDevice, st));
+    } else {
+        HIPCHK(hipMemcpyAsync(ctx->d_g, N.d_g0, vb, hipMemcpyDeviceToDevice, st));
+    }
+    ctx->lfHaveGrad = true;
+    C.nextStart = 1;
+    const double D0 = C.D, M0 = C.M;
+    if (movedOn) { C.cur = prop; C.D = sel[1]; C.M = sel[2]; }
+    const double alpha = T.alphaSum / (double)T.nleaves;
+    chain_commit(ctx);
+    if (C.adapt.active) chain_adapt_step(ctx, alpha);
+    C.gen = ctx->stateGen;
+    std::memset(rec, 0, sizeof *rec);
+    rec->rec.accepted = movedOn ? 1 : 0;
+    rec->rec.nfevals = evals;
+    rec->rec.K0 = K0;
+    rec->rec.K1 = movedOn ? sel[0] : K0; rec->rec.D1 = movedOn ? sel[1] : D0; rec->rec.M1 = movedOn ? sel[2] : M0;
+    rec->rec.D = C.D; rec->rec.M = C.M;
+    rec->rec.hdif = movedOn ? (D0 + M0 + K0) - (sel[1] + sel[0] + sel[2]) : 0.0;
+    rec->rec.nsamples = C.nsamples; rec->rec.nmoments = C.nmoments;
+    rec->depth = T.depth; rec->nleaves = T.nleaves; rec->stop = T.stop; rec->dirs = T.dirs;
+    rec->selected = T.selected; rec->alpha = alpha;
+    if (m_out || pred_out) {
+        if (m_out) HIPCHK(hipMemcpyAsync(m_out, C.d_m[C.cur], vb, hipMemcpyDeviceToHost, st));
+        if (pred_out) HIPCHK(hipMemcpyAsync(pred_out, C.d_pred[C.cur], pb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int chain_nuts_ready(hmcmt_ctx* ctx, const char* fn, int32_t maxDepth) {
+    const int rc = chain_rng_ready(ctx, fn);
+    if (rc) return rc;
+    if (maxDepth < 1 || maxDepth > HMCMT_NUTS_DEPTH_MAX) {
+        ctx->err = std::string(fn) + ": need 1 <= max_depth <= HMCMT_NUTS_DEPTH_MAX = " + std::to_string(HMCMT_NUTS_DEPTH_MAX);
+        return HMCMT_EINVAL;
+    }
+    if (ctx->mass.kind == HMCMT_MASS_WM) {
+        ctx->err = std::string(fn) + ": HMCMT_MASS_WM is not supported (its mass solve synchronises); use the diagonal or the low-rank mass";
+        return HMCMT_EINVAL;
+    }
+    return 0;
+}
+
+int hmcmt_chain_nuts_sample(hmcmt_ctx* ctx, int32_t max_depth, hmcmt_nuts_record* rec, double* m_out, double* pred_out) {
+    const char* fn = "hmcmt_chain_nuts_sample";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!rec) { ctx->err = std::string(fn) + ": rec is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_nuts_ready(ctx, fn, max_depth);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    return chain_nuts_sample(ctx, fn, max_depth, rec, m_out, pred_out);
+}
+
+int hmcmt_chain_nuts_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t max_depth, hmcmt_nuts_record* recs, double* models, double* preds,
+                         int64_t* done) {
+    const char* fn = "hmcmt_chain_nuts_run";
+    if (!ctx) return HMCMT_EINVAL;
+    if (done) *done = 0;
+    if (!recs || nsamples < 0) { ctx->err = std::string(fn) + ": need recs[nsamples] and nsamples >= 0"; return HMCMT_EINVAL; }
+    int rc = chain_nuts_ready(ctx, fn, max_depth);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    const size_t n = (size_t)ctx->v.nAC, nd = (size_t)2 * ctx->v.nData;
+    for (int64_t i = 0; i < nsamples; ++i) {
+        if ((rc = chain_nuts_sample(ctx, fn, max_depth, recs + i, models ? models + i * n : nullptr, preds ? preds + i * nd : nullptr))) return rc;
+        if (done) *done = i + 1;
+    }
+    return 0;
+}
+
+// measurement: the solver's work per leaf by whether the leaf follows a change of direction (hmcmt_debug.h)
+int hmcmt_debug_nuts_iters(hmcmt_ctx* ctx, int64_t* out, int32_t reset) {
+    if (!ctx) return HMCMT_EINVAL;
+    const int rc = chain_ready(ctx, "hmcmt_debug_nuts_iters", true);
+    if (rc) return rc;
+    auto& N = ctx->chain.nuts;
+    if (out) { out[0] = N.its[1]; out[1] = N.solves[1]; out[2] = N.its[0]; out[3] = N.solves[0]; }
+    if (reset) N.its[0] = N.its[1] = N.solves[0] = N.solves[1] = 0;
+    return 0;
+}
+
+// the two kernels on the caller's device vectors (hmcmt_debug.h)
+int hmcmt_debug_nuts_leaf(hmcmt_ctx* ctx, const hmcmt_debug_nuts_args* a, double* sums) {
+    const char* fn = "hmcmt_debug_nuts_leaf";
+    if (!ctx) return HMCMT_EINVAL;
+    static_assert(HMCMT_NUTS_CK_MAX == NUTS_CK_MAX && HMCMT_NUTS_SUMS == NUTS_NQ, "the hook's header mirrors hmcmt_items.h");
+    const bool ok = a && sums && a->n >= 1 && a->n <= (int64_t)HMCMT_NUTS_HOOK_NMAX && a->ndue >= 0 && a->ndue <= NUTS_CK_MAX && a->p && a->rho_s &&
+                    (a->x || a->inv_m) && (!a->merged || (a->rho && a->rho_next && a->p_other && (a->x_other || a->inv_m)));
+    if (!ok) { ctx->err = std::string(fn) + ": need args, sums, 1 <= n <= HMCMT_NUTS_HOOK_NMAX, 0 <= ndue <= HMCMT_NUTS_CK_MAX and the vectors the leaf reads"; return HMCMT_EINVAL; }
+    for (int c = 0; c < a->ndue; ++c)
+        if (!a->ck_due[c][0] || !a->ck_due[c][1] || !a->ck_due[c][2]) { ctx->err = std::string(fn) + ": a due checkpoint is NULL"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    hipStream_t st = ctx->stream;
+    ChainReadout R(ctx, fn, false);
+    double* part = (double*)R.scratch(sizeof(double) * NUTS_NQ * LFNB);
+    double* aux = (double*)R.scratch(sizeof(double) * (LFNB + 4));       // zeros: the K0 partial sums, misfit, mnorm, flag
+    double scal[NUTS_SCAL];
+    double* d_scal = (double*)R.out(scal, sizeof scal);
+    if (R.rc) return R.rc;
+    HIPCHK(hipMemsetAsync(part, 0, sizeof(double) * NUTS_NQ * LFNB, st));
+    HIPCHK(hipMemsetAsync(aux, 0, sizeof(double) * (LFNB + 4), st));
+    HIPCHK(hipMemsetAsync(d_scal, 0, sizeof scal, st));
+    NutsLeaf L{};
+    L.n = (int)a->n; L.first = a->first != 0; L.merged = a->merged != 0;
+    L.sign = a->backward ? -1.0 : 1.0; L.signOther = a->other_backward ? -1.0 : 1.0;
+    L.p = a->p; L.x = a->x; L.invM = a->inv_m; L.rhoS = a->rho_s;
+    L.ckP = a->ck_write[0]; L.ckX = a->ck_write[1]; L.ckR = a->ck_write[2];
+    if (!L.ckP || !L.ckX || !L.ckR) L.ckP = L.ckX = L.ckR = nullptr;
+    L.rho = a->rho; L.rhoNext = a->rho_next; L.pOther = a->p_other; L.xOther = a->x_other;
+    L.part = part;
+    nuts_leaf_launch(st, L, a->ndue, a->ck_due, aux, aux + LFNB, aux + LFNB + 1, (const int*)(aux + LFNB + 2), d_scal);
+    const int rc = R.finish();
+    if (rc) return rc;
+    for (int q = 0; q < NUTS_NQ; ++q) sums[q] = q < 3 + 2 * a->ndue ? scal[NS_SUM + q] : 0.0;
     return 0;
 }
 

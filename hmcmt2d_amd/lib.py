@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_chain.h", "kernels_jac.h", "kernels_jvp.h", "host_jacobian.h", "host_chain.h", "hmcmt_knobs.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_chain.h", "kernels_nuts.h", "kernels_jac.h", "kernels_jvp.h", "host_jacobian.h", "host_chain.h", "hmcmt_knobs.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -63,6 +63,25 @@ class ChainRecord(C.Structure):
 
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class NutsRecord(C.Structure):
+    """hmcmt_nuts_record (include/hmcmt.h): what hmcmt_chain_nuts_sample reports of one sample."""
+    _fields_ = [("rec", ChainRecord), ("depth", C.c_int32), ("nleaves", C.c_int32), ("stop", C.c_int32), ("dirs", C.c_uint32),
+                ("selected", C.c_int64), ("alpha", C.c_double)]
+
+    def as_dict(self):
+        d = self.rec.as_dict()
+        d.update({f: getattr(self, f) for f, _ in self._fields_[1:]})
+        return d
+
+
+class DebugNutsArgs(C.Structure):
+    """hmcmt_debug_nuts_args (include/hmcmt_debug.h): the device vectors of one leaf's pass."""
+    _fields_ = [("n", C.c_int64), ("backward", C.c_int32), ("other_backward", C.c_int32), ("first", C.c_int32), ("merged", C.c_int32),
+                ("ndue", C.c_int32), ("reserved_", C.c_int32), ("p", C.c_void_p), ("x", C.c_void_p), ("inv_m", C.c_void_p),
+                ("rho_s", C.c_void_p), ("ck_write", C.c_void_p * 3), ("ck_due", (C.c_void_p * 3) * 9), ("rho", C.c_void_p),
+                ("rho_next", C.c_void_p), ("p_other", C.c_void_p), ("x_other", C.c_void_p)]
 
 
 class AdaptOptions(C.Structure):
@@ -209,7 +228,14 @@ def load_library():
     lib.hmcmt_chain_normals.argtypes = [vp, C.c_uint64, vp, C.c_int32]
     lib.hmcmt_chain_sample.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(ChainRecord), c_double_p, c_double_p]
     lib.hmcmt_chain_run.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(ChainRecord), c_double_p, c_double_p, c_int64_p]
-    for name in CHAIN_RNG_SYMBOLS:
+    lib.hmcmt_chain_nuts_sample.argtypes = [vp, C.c_int32, C.POINTER(NutsRecord), c_double_p, c_double_p]
+    lib.hmcmt_chain_nuts_run.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(NutsRecord), c_double_p, c_double_p, c_int64_p]
+    lib.hmcmt_rng_nuts.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    lib.hmcmt_debug_nuts_leaf.argtypes = [vp, C.POINTER(DebugNutsArgs), c_double_p]
+    lib.hmcmt_debug_nuts_leaf.restype = C.c_int
+    lib.hmcmt_debug_nuts_iters.argtypes = [vp, c_int64_p, C.c_int32]
+    lib.hmcmt_debug_nuts_iters.restype = C.c_int
+    for name in CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
@@ -254,9 +280,13 @@ CHAIN_ADAPT_SYMBOLS = ["hmcmt_chain_set_dt", "hmcmt_chain_set_mass_diag", "hmcmt
 # ... and the chain's own random numbers: Philox4x32-10 by counter, one call and one wait per sample, one call per run
 CHAIN_RNG_SYMBOLS = ["hmcmt_rng_draw", "hmcmt_rng_normals", "hmcmt_chain_seed", "hmcmt_chain_rng_state", "hmcmt_chain_rng_seek",
                      "hmcmt_chain_normals", "hmcmt_chain_sample", "hmcmt_chain_run"]
+# ... and the No-U-turn sampler on a seeded chain: the trajectory length chosen per sample
+CHAIN_NUTS_SYMBOLS = ["hmcmt_chain_nuts_sample", "hmcmt_chain_nuts_run", "hmcmt_rng_nuts"]
+NUTS_DEPTH_MAX = 10   # include/hmcmt.h: HMCMT_NUTS_DEPTH_MAX
+NUTS_CK_MAX, NUTS_SUMS = 9, 21   # include/hmcmt_debug.h: HMCMT_NUTS_CK_MAX, HMCMT_NUTS_SUMS
 ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_RNG_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -267,7 +297,8 @@ DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "
                  "hmcmt_debug_transform", "hmcmt_debug_flags", "hmcmt_debug_spmv", "hmcmt_debug_precond", "hmcmt_debug_fdm_fwd",
                  "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_debug_hog", "hmcmt_persist_envelope",
                  "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time",
-                 "hmcmt_debug_chain_cov_time", "hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess"]
+                 "hmcmt_debug_chain_cov_time", "hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess", "hmcmt_debug_nuts_leaf",
+                 "hmcmt_debug_nuts_iters"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -290,6 +321,20 @@ def rng_draw(seed, stream, t, Lmin, Lmax):
     if rc != 0:
         raise HmcmtError(rc, "hmcmt_rng_draw: need 1 <= Lmin <= Lmax")
     return int(L.value), float(u.value)
+
+
+def rng_nuts(seed, stream, t, kind, index):
+    """(forward, u) of a NUTS sample's draws beside the momentum: kind 0, doubling `index` -- its direction and the uniform of its
+    merge; kind 1, the sample's index-th leaf -- the uniform of its selection (forward is 0).  hmcmt_rng_nuts, on the host."""
+    lib = load_library()
+    f, u = C.c_int32(), C.c_double()
+    index = int(index)
+    if not 0 <= index < 2 ** 32:
+        raise ValueError(f"index is uint32; got {index}")
+    rc = lib.hmcmt_rng_nuts(*_rng_ints(seed, stream, t), int(kind), index, C.byref(f), C.byref(u))
+    if rc != 0:
+        raise HmcmtError(rc, "hmcmt_rng_nuts: need kind 0 (index < 32) or 1 (index < 2^30)")
+    return int(f.value), float(u.value)
 
 
 def rng_normals(seed, stream, t, n, a0=0):
@@ -837,6 +882,66 @@ class HipContext:
             if self.args.real_data:
                 preds = preds.real.copy()
         return (out, models, preds) if check else (out, models, preds, rc)
+
+    # -- the No-U-turn sampler on a seeded chain (hmcmt_chain_nuts_sample, hmcmt_chain_nuts_run) ----
+    def chain_nuts_sample(self, max_depth, outputs=True):
+        """One NUTS sample of a seeded chain: the tree doubles up to max_depth times.  Returns (record, m, pred): the record is
+        chain_step's (at the selected state) with depth, nleaves, stop, dirs, selected and alpha added."""
+        rec = NutsRecord()
+        m = np.empty(self.nAC) if outputs else None
+        pred = np.empty(self.nData, dtype=np.complex128) if outputs else None
+        self._check(self.lib.hmcmt_chain_nuts_sample(self.h, int(max_depth), C.byref(rec), _dp(m) if outputs else None,
+                                                     _dp(pred) if outputs else None))
+        if outputs and self.args.real_data:
+            pred = pred.real.copy()
+        return rec.as_dict(), m, pred
+
+    def chain_nuts_run(self, nsamples, max_depth, outputs=True, check=True):
+        """nsamples NUTS samples in one call, in chain_run's conventions."""
+        nsamples = int(nsamples)
+        rows = max(nsamples, 0)                              # (a negative nsamples is the library's to refuse)
+        recs = (NutsRecord * max(rows, 1))()
+        models = np.empty((rows, self.nAC)) if outputs else None
+        preds = np.empty((rows, self.nData), dtype=np.complex128) if outputs else None
+        done = C.c_int64()
+        rc = self.lib.hmcmt_chain_nuts_run(self.h, nsamples, int(max_depth), recs, _dp(models) if outputs else None,
+                                           _dp(preds) if outputs else None, C.byref(done))
+        if check:
+            self._check(rc)
+        k = int(done.value)
+        out = [recs[i].as_dict() for i in range(k)]
+        if outputs:
+            models, preds = models[:k], preds[:k]
+            if self.args.real_data:
+                preds = preds.real.copy()
+        return (out, models, preds) if check else (out, models, preds, rc)
+
+    def debug_nuts_leaf(self, n, p, rho_s, x=None, inv_m=None, backward=False, first=False, ck_write=None, ck_due=(), merged=None):
+        """k_nuts_leaf + k_nuts_final on device vectors given as pointers (ints): hmcmt_debug_nuts_leaf.  ck_write: (p, x, rho_s) to
+        store; ck_due: a list of such triples to check; merged: dict(rho=, rho_next=, p_other=, x_other=None, other_backward=).
+        Returns the NUTS_SUMS sums."""
+        a = DebugNutsArgs()
+        a.n, a.backward, a.first, a.ndue = int(n), int(bool(backward)), int(bool(first)), len(ck_due)
+        a.p, a.x, a.inv_m, a.rho_s = p, x, inv_m, rho_s
+        if ck_write is not None:
+            for v in range(3):
+                a.ck_write[v] = ck_write[v]
+        for c, trip in enumerate(ck_due[:NUTS_CK_MAX]):
+            for v in range(3):
+                a.ck_due[c][v] = trip[v]
+        if merged is not None:
+            a.merged = 1
+            a.rho, a.rho_next, a.p_other, a.x_other = merged["rho"], merged["rho_next"], merged["p_other"], merged.get("x_other")
+            a.other_backward = int(bool(merged.get("other_backward", False)))
+        sums = np.zeros(NUTS_SUMS)
+        self._check(self.lib.hmcmt_debug_nuts_leaf(self.h, C.byref(a), _dp(sums)))
+        return sums
+
+    def debug_nuts_iters(self, reset=False):
+        """{after_change: (iterations, solves), other: (iterations, solves)} of the NUTS leaves since the last reset (measurement)."""
+        o = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.hmcmt_debug_nuts_iters(self.h, o.ctypes.data_as(c_int64_p), int(bool(reset))))
+        return {"after_change": (int(o[0]), int(o[1])), "other": (int(o[2]), int(o[3]))}
 
     # -- marginal posteriors from the chain's commit (hmcmt_chain_hist_*, hmcmt_chain_data_moments*) --
     def chain_hist_begin(self, targets, nbins, lo, hi):

@@ -810,7 +810,8 @@ class _WarmUp(ChainOutput):
     def step(self, ctx, state, it, rec):
         before, state["info"] = state["info"], ctx.chain_adapt_info()
         state["dt"][it - 1] = before["dt"]
-        state["alpha"][it - 1] = 1.0 if rec["hdif"] > 0 else float(np.exp(rec["hdif"]))
+        # (a NUTS sample's record carries the alpha the warm-up was fed: the mean over the tree's leaves)
+        state["alpha"][it - 1] = rec["alpha"] if "alpha" in rec else (1.0 if rec["hdif"] > 0 else float(np.exp(rec["hdif"])))
         if before["active"] and before["next_window_end"] == before["step"]:      # (this step was its window's last)
             state["windows"].append((it, before["window_count"] + 1))
 
@@ -871,24 +872,59 @@ def _sample_line(it, rec):
             f"p={min(1.0, float(np.exp(min(rec['hdif'], 0.0)))):.3f}")
 
 
+def _nuts_line(it, rec):
+    return (f"iterNo={it:6d} dtMisfit={rec['D']:8.3e} mNorm={rec['M']:8.3e} depth={rec['depth']} leaves={rec['nleaves']:4d} "
+            f"stop={rec['stop']} selected={rec['selected']:5d} alpha={rec['alpha']:.3f}")
+
+
 LIBRARY_RNG_BLOCK = 16      # samples per chain_run call where a progress line is wanted
+NUTS_KEYS = ("max_depth",)
+NUTS_FIELDS = (("depth", np.int32), ("nleaves", np.int32), ("stop", np.int32), ("dirs", np.uint32), ("selected", np.int64), ("alpha", np.float64))
 
 
-def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, start):
+def _check_nuts(nuts, hmcprior, library_rng):
+    """runHMCSampler's nuts={"max_depth": d} -> d, refused before the context is touched: it is a sampling mode of the seeded device
+    chain (hmcmt_chain_nuts_run), which draws the tree's numbers itself"""
+    from .lib import NUTS_DEPTH_MAX
+    if not isinstance(nuts, dict) or set(nuts) - set(NUTS_KEYS):
+        raise ValueError(f"runHMCSampler: nuts must be a dict with the keys {NUTS_KEYS}")
+    if library_rng is None:
+        raise ValueError("runHMCSampler: nuts needs library_rng=(seed, stream) (the tree's draws are the library's)")
+    try:
+        depth = int(nuts.get("max_depth", NUTS_DEPTH_MAX))
+    except (TypeError, ValueError):
+        raise ValueError("runHMCSampler: nuts max_depth must be an integer") from None
+    if not 1 <= depth <= NUTS_DEPTH_MAX:
+        raise ValueError(f"runHMCSampler: nuts needs 1 <= max_depth <= {NUTS_DEPTH_MAX}, not {depth}")
+    if hmcprior.massType != "diagonal":
+        raise ValueError(f"runHMCSampler: nuts needs massType \"diagonal\" (optionally with mass_lowrank), not {hmcprior.massType!r}")
+    return depth
+
+
+def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, start, nuts=None):
     """The loop of _run_device_chain with the library's own random numbers (library_rng = (seed, stream)): chain_seed, then the samples
     through chain_run -- one call for the whole run, blocks of LIBRARY_RNG_BLOCK with verbose (the lines of a block are printed behind
     it), single samples where an output watches every step.  Column `it` of hmstats takes its K from the record of sample it + 1 (K0
     is the kinetic energy of the momentum that sample drew); the last column's is the next draw's, read back through chain_normals and
-    chain_momentum, which leaves the generator where it is."""
+    chain_momentum, which leaves the generator where it is.  nuts (a max_depth): the samples are NUTS samples through chain_nuts_run
+    -- hmcprior.timestep is not used --, and stats.nuts takes their tree records."""
     ctx.chain_seed(*library_rng)
+    if nuts is not None:
+        stats.nuts = {"max_depth": nuts, **{f: np.zeros(hmcprior.totalsamples, dtype=t) for f, t in NUTS_FIELDS}}
     nsamples = hmcprior.totalsamples
     Lmin, Lmax = int(hmcprior.timestep[0]), int(hmcprior.timestep[1])
     block = 1 if watching else (LIBRARY_RNG_BLOCK if verbose else max(nsamples, 1))
     D, M = start
     it = 0
     while it < nsamples:
-        recs, models, preds = ctx.chain_run(min(block, nsamples - it), Lmin, Lmax, outputs=keep_samples)
+        if nuts is not None:
+            recs, models, preds = ctx.chain_nuts_run(min(block, nsamples - it), nuts, outputs=keep_samples)
+        else:
+            recs, models, preds = ctx.chain_run(min(block, nsamples - it), Lmin, Lmax, outputs=keep_samples)
         for k, rec in enumerate(recs):
+            if nuts is not None:
+                for f, _ in NUTS_FIELDS:
+                    stats.nuts[f][it] = rec[f]
             stats.hmstats[:, it] = [D, M, rec["K0"], D + M + rec["K0"]]
             it += 1
             for out, state in watching:
@@ -900,7 +936,7 @@ def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watchin
             else:
                 stats.nReject += 1
             if verbose:
-                print(_sample_line(it, rec))
+                print(_sample_line(it, rec) if nuts is None else _nuts_line(it, rec))
             D, M = rec["D"], rec["M"]
             if keep_samples:
                 hmcmodel[:, it - 1] = models[k]
@@ -912,7 +948,7 @@ def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watchin
 
 
 def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank=None,
-                      library_rng=None):
+                      library_rng=None, nuts=None):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals.
@@ -953,7 +989,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     stats: HMCStatus = initHMCStatus(nsamples)
     if library_rng is not None:
         # (z, drawn above so that rhoref is the draw it is without the keyword, is not used: every momentum is the library's)
-        _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, (startD, startM))
+        _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, (startD, startM), nuts)
         stats.moments = ctx.chain_moments()
         for out, state in begun:
             setattr(stats, out.field, out.read(ctx, state, stats, env))
@@ -988,7 +1024,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
                   checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
-                  cov=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None):
+                  cov=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None, nuts=None):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -1015,6 +1051,13 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     hmcstats.rng = (seed, stream, t) is the generator's whole state behind the run, t the index of the next draw.  `rng` still draws
     rhoref, and nothing else.  Every other keyword works unchanged.
 
+    `nuts={"max_depth": d}` (with device_chain and library_rng; massType "diagonal", with or without invM= / mass_lowrank=): the
+    No-U-turn sampler of the library (hmcmt_chain_nuts_run, include/hmcmt.h) chooses every sample's trajectory length; d in 1 .. 10
+    bounds the tree at 2^d - 1 leapfrog steps and hmcprior.timestep is not used.  It is a sampling mode, not an output: the commit,
+    the optional outputs and adapt= (fed the tree's mean acceptance) work unchanged.  hmcstats.nuts holds max_depth and, per sample,
+    depth, nleaves, stop (0 max_depth, 1 U-turn inside the new subtree, 2 U-turn of the tree, 3 divergence), dirs, selected and alpha;
+    acceptstats marks the samples whose selected state is not the start.
+
     `checkpoint` (a file path) with `checkpoint_every` = k > 0: the chain's state -- samples so far, statistics, current
     model and momentum, the RNG state -- is flushed every k samples; if the file exists when the sampler starts, the
     chain RESUMES behind its last flushed sample and draws the same random numbers an uninterrupted run would have
@@ -1036,10 +1079,14 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
                                                      if v is not None]
     if library_rng is not None:
         needing.append(("library_rng", "the library's generator feeds the device chain"))
+    if nuts is not None:
+        needing.append(("nuts", "the No-U-turn sampler is the device chain's"))
     if needing and not device_chain:
         raise ValueError("runHMCSampler: %s needs device_chain=True (%s)" % needing[0])
     if library_rng is not None:
         library_rng = _check_library_rng(library_rng)
+    if nuts is not None:
+        nuts = _check_nuts(nuts, hmcprior, library_rng)
     if mass_lowrank is not None:
         if hmcprior.massType != "diagonal":
             raise ValueError(f"runHMCSampler: mass_lowrank needs massType \"diagonal\", not {hmcprior.massType!r}")
@@ -1059,7 +1106,7 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
         return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank,
-                                 library_rng)
+                                 library_rng, nuts)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -1176,6 +1223,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     fill -- every HMCStatus field of CHAIN_OUTPUTS -- is not gathered: it stays with the chain on the chain's own rank.
     `library_rng=True` (with device_chain=True): chain c draws its numbers in the library as stream c of `seed`,
     runHMCSampler(library_rng=(seed, c)); its hmcstats.rng stays on the chain's own rank like the optional outputs.
+    `nuts={"max_depth": d}` goes through to runHMCSampler with it; hmcstats.nuts stays on the chain's own rank too.
     Chains that carry posterior moments (HMCStatus.moments: device_chain=True, or a `run_chain` that sets them) have
     count, mean[nparam], m2[nparam] packed behind their block, so every rank ends with every chain's moments (mergeMoments,
     gelmanRubin).  A chain's block in the gather is, in doubles (the sum of gatherBlockFields, which packing and unpacking walk),

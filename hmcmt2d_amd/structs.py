@@ -92,6 +92,7 @@ class HMCStatus:
     cov: object = None            # dict count, rows, mean, var, cov, corr: runHMCSampler(..., cov=...)
     adapt: object = None          # dict nwarmup, dt, alpha, dt_final, invM, windows: runHMCSampler(..., adapt=...)
     rng: object = None            # (seed, stream, t) of the library's generator behind the run: runHMCSampler(..., library_rng=(seed, stream))
+    nuts: object = None           # dict max_depth, depth, nleaves, stop, dirs, selected, alpha (per sample): runHMCSampler(..., nuts={"max_depth": d})
 
 
 def initHMCStatus(nsamples: int) -> HMCStatus:

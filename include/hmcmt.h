@@ -490,6 +490,51 @@ extern int hmcmt_chain_sample(hmcmt_ctx* ctx, int32_t Lmin, int32_t Lmax, hmcmt_
 extern int hmcmt_chain_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t Lmin, int32_t Lmax, hmcmt_chain_record* recs, double* models,
                            double* preds, int64_t* done);
 
+/* The No-U-turn sampler on a seeded chain: the trajectory length is chosen per sample (multinomial NUTS, Betancourt 2017, grown leaf
+ * by leaf without recursion).  A sample ends in hmcmt_chain_step's commit, so the moments, the accumulators and a warm-up ride on it
+ * unchanged; nothing above changes its bits.
+ * Draws of sample t beside the momentum's normals (draw t's, as in hmcmt_chain_sample), in the counter scheme above:
+ *   kind 0, doubling j: the block at c0 = 0xC0000000 + j; forward = x2 >> 31, u = U(x0, x1)
+ *   kind 1, the sample's l-th leaf (0-based over the whole tree): the block at c0 = 0x80000000 + l; u = U(x0, x1)
+ * Algorithm.  H = D + M + K, x = M^-1 p, momenta in the forward-time sign, log-weights delta = H0 - H.  The tree starts with both ends
+ * at the start state, rho = p0, logW = 0, the selection the start.  Doubling j builds 2^j leaves from the end `forward` names; a leaf
+ * is one step of hmcmt_leapfrog_device's map (backward: the same map on -p).  Leaf i of the subtree:
+ *   delta not finite or -delta > 1000: the sample stops (stop 3, a divergence)
+ *   logWs = logaddexp(logWs, delta); the leaf becomes the subtree's selection iff u_leaf < exp(delta - logWs) (leaf 0 always); rhos += p
+ *   even i: the checkpoint k = popcount(i >> 1) = (p, x, rhos) is stored
+ *   odd i: for k = popcount(i >> 1) down to k - (trailing ones of i) + 1, span = rhos - rhos_ck[k] + p_ck[k]; the leaf turns iff
+ *          x_ck[k].span <= 0 or x.span <= 0 (stop 1) -- these are the aligned spans [i + 1 - 2^s, i]
+ * A stopped subtree is discarded whole.  A completed one is merged: its selection replaces the tree's iff u_j < exp(min(0, logWs -
+ * logW)); logW = logaddexp(logW, logWs); rho += rhos; the end moves; stop 2 iff x_minus.rho <= 0 or x_plus.rho <= 0; stop 0 at
+ * max_depth doublings.  exp and logaddexp are host double arithmetic.
+ *   hmcmt_chain_nuts_sample  one sample with draw t.  Per leaf one evaluation (whose solver records the host waits for, as in every
+ *                            trajectory), one copy of scalars and one host wait behind it; rec.rec.nfevals =
+ *                            nleaves, plus 1 when the start gradient had to be evaluated.  The next sample finds its start gradient on
+ *                            the device.  Diagonal mass (set or adapted) and HMCMT_MASS_LOWRANK; HMCMT_MASS_WM is HMCMT_EINVAL.  An
+ *                            active warm-up is fed rec.alpha.  The first call allocates the tree's buffers (HMCMT_ENOMEM leaves the
+ *                            chain usable).  t advances by one whether the sample succeeds or fails; a leaf whose evaluation fails
+ *                            returns that code and leaves the chain where it was
+ *   hmcmt_chain_nuts_run     nsamples times hmcmt_chain_nuts_sample, in hmcmt_chain_run's conventions
+ *   hmcmt_rng_nuts           the draws above on the host (forward, u: each may be NULL): no context, no device.  HMCMT_EINVAL for a
+ *                            kind other than 0 / 1, index >= 32 (kind 0) or >= 2^30 (kind 1)
+ * hmcmt_chain_step and hmcmt_chain_sample may follow a NUTS sample and the reverse.  HMCMT_EINVAL: max_depth outside 1 ..
+ * HMCMT_NUTS_DEPTH_MAX, no chain, no seed, NULL rec, a call between hmcmt_grad_device_async and hmcmt_wait. */
+#define HMCMT_NUTS_DEPTH_MAX 10
+typedef struct hmcmt_nuts_record {
+    hmcmt_chain_record rec;   /* accepted = selected != 0; nfevals; K0; K1, D1, M1 at the SELECTED state; D, M after the commit;
+                                 hdif = H0 - H(selected); nsamples, nmoments as ever */
+    int32_t depth;            /* doublings merged into the tree */
+    int32_t nleaves;          /* leapfrog steps taken (<= 2^max_depth - 1) */
+    int32_t stop;             /* 0 max_depth, 1 U-turn inside the new subtree, 2 U-turn of the merged tree, 3 divergence */
+    uint32_t dirs;            /* bit j set: doubling j went forward in time (attempted doublings, the discarded one included) */
+    int64_t selected;         /* signed time index of the selected state, 0 = the start */
+    double  alpha;            /* mean over the leaves of min(1, exp(H0 - H_leaf)); a divergent leaf counts 0 */
+} hmcmt_nuts_record;
+extern int hmcmt_chain_nuts_sample(hmcmt_ctx* ctx, int32_t max_depth, hmcmt_nuts_record* rec, double* m_out, double* pred_out);
+extern int hmcmt_chain_nuts_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t max_depth, hmcmt_nuts_record* recs, double* models,
+                                double* preds, int64_t* done);
+extern int hmcmt_rng_nuts(uint64_t seed, uint32_t stream, uint64_t t, int32_t kind, uint32_t index, int32_t* forward, double* u);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -124,6 +124,35 @@ int hmcmt_debug_extrap(hmcmt_ctx* ctx, int32_t kind, double* out /*[10]*/);
 int hmcmt_debug_guess_capture(hmcmt_ctx* ctx, int32_t enable);
 int hmcmt_debug_guess(hmcmt_ctx* ctx, int32_t kind, double* out);
 
+/* Test hook of the No-U-turn sampler's two kernels (k_nuts_leaf, k_nuts_final; tests/test_gpu_chain_nuts.py): one leaf's pass over n
+ * cells on the caller's DEVICE vectors, so that the kernels are tested without a solve.  The context lends its device and stream only;
+ * n need not be its nAC (1 <= n <= HMCMT_NUTS_HOOK_NMAX: the kernels index cells by int, one grid stride past n included).  backward / other_backward: the end stores its momentum (and x) negated.  x, x_other NULL: the diagonal inv_m.
+ * first: rho_s = p, else rho_s += p.  ck_write: the three vectors (p, x, rho_s) of an even leaf's checkpoint, or NULLs.  ck_due[c]: the
+ * c-th due checkpoint's three vectors, c < ndue <= HMCMT_NUTS_CK_MAX.  merged: rho_next = rho + rho_s and the merged tree's pair.
+ * sums[HMCMT_NUTS_SUMS]: [0] p.x, [1] x.rho_next, [2] x_other.rho_next, [3 + 2c] x_ck.span, [4 + 2c] x.span; rows that are not due
+ * are 0.  Complete on return. */
+#define HMCMT_NUTS_CK_MAX 9
+#define HMCMT_NUTS_SUMS 21
+#define HMCMT_NUTS_HOOK_NMAX 0x40000000
+typedef struct hmcmt_debug_nuts_args {
+    int64_t n;
+    int32_t backward, other_backward, first, merged, ndue, reserved_;
+    const double *p, *x, *inv_m;
+    double* rho_s;
+    double* ck_write[3];
+    const double* ck_due[HMCMT_NUTS_CK_MAX][3];
+    const double* rho;
+    double* rho_next;
+    const double *p_other, *x_other;
+} hmcmt_debug_nuts_args;
+int hmcmt_debug_nuts_leaf(hmcmt_ctx* ctx, const hmcmt_debug_nuts_args* args, double* sums /*[HMCMT_NUTS_SUMS]*/);
+
+/* Measurement only: the solver's work in the leaves of the chain's NUTS samples since the last reset, split by whether a leaf follows
+ * a change of direction (its solves' extrapolated guesses then come from the other end's path).  out[4] (may be NULL) = {iterations,
+ * solves of the leaves that follow a change; iterations, solves of the others}, forward and adjoint together; reset != 0 zeroes the
+ * sums.  It changes no result */
+int hmcmt_debug_nuts_iters(hmcmt_ctx* ctx, int64_t* out /*[4]*/, int32_t reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -69,6 +69,18 @@ struct HmcmtChainRecord
     hdif::Float64
     nsamples::Int64
     nmoments::Int64
+end
+
+# hmcmt_nuts_record of include/hmcmt.h: what hmcmt_chain_nuts_sample reports of one sample -- the chain record at the selected state,
+# then the tree (tests/test_nuts_host.py compares the layout with the ctypes mirror)
+struct HmcmtNutsRecord
+    rec::HmcmtChainRecord
+    depth::Int32
+    nleaves::Int32
+    stop::Int32
+    dirs::UInt32
+    selected::Int64
+    alpha::Float64
 end
 
 # hmcmt_adapt_options and hmcmt_adapt_info of include/hmcmt.h: the warm-up hmcmt_chain_adapt_begin starts and where it stands
@@ -595,6 +607,45 @@ function chain_run!(ctx::HipContext, nsamples::Integer, Lmin::Integer, Lmax::Int
 end
 
 """
+    chain_nuts_sample!(ctx, maxDepth; mOut=nothing, predOut=nothing) -> HmcmtNutsRecord
+    chain_nuts_run!(ctx, nsamples, maxDepth; keepSamples=true) -> (recs, models[nAC, done], preds[nData, done])
+
+The No-U-turn sampler on a seeded chain (hmcmt_chain_nuts_sample, hmcmt_chain_nuts_run, include/hmcmt.h): every sample chooses its
+trajectory length, a tree of at most `maxDepth` (1 .. 10) doublings; the record is the chain record at the selected state plus depth,
+nleaves, stop, dirs, selected and alpha.  Diagonal and low-rank mass.  Same conventions as `chain_sample!` / `chain_run!`;
+`run_chain!(...; seed=(s, c), nuts=maxDepth)` runs the sampler this way.
+"""
+function chain_nuts_sample!(ctx::HipContext, maxDepth::Integer; mOut::Union{Nothing,Vector{Float64}}=nothing,
+                            predOut::Union{Nothing,Vector{ComplexF64}}=nothing)
+    rec = Ref(HmcmtNutsRecord(HmcmtChainRecord(0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0), 0, 0, 0, 0, 0, 0.0))
+    pm = mOut === nothing ? Ptr{Float64}(C_NULL) : pointer(mOut)
+    pp = predOut === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(predOut)
+    rc = GC.@preserve mOut predOut @ccall libhmcmt.hmcmt_chain_nuts_sample(ctx.ptr::Ptr{Cvoid}, Int32(maxDepth)::Int32,
+                                                                          rec::Ref{HmcmtNutsRecord}, pm::Ptr{Float64}, pp::Ptr{ComplexF64})::Cint
+    checkerr(ctx.ptr, rc)
+    return rec[]
+end
+
+function chain_nuts_run!(ctx::HipContext, nsamples::Integer, maxDepth::Integer; keepSamples::Bool=true)
+    recs = Vector{HmcmtNutsRecord}(undef, nsamples)
+    models = keepSamples ? Matrix{Float64}(undef, ctx.nAC, nsamples) : nothing
+    preds = keepSamples ? Matrix{ComplexF64}(undef, ctx.nData, nsamples) : nothing
+    pm = keepSamples ? pointer(models) : Ptr{Float64}(C_NULL)
+    pp = keepSamples ? pointer(preds) : Ptr{ComplexF64}(C_NULL)
+    done = Ref{Int64}(0)
+    rc = GC.@preserve recs models preds @ccall libhmcmt.hmcmt_chain_nuts_run(ctx.ptr::Ptr{Cvoid}, Int64(nsamples)::Int64, Int32(maxDepth)::Int32,
+                                                                            pointer(recs)::Ptr{HmcmtNutsRecord}, pm::Ptr{Float64},
+                                                                            pp::Ptr{ComplexF64}, done::Ref{Int64})::Cint
+    k = Int(done[])
+    resize!(recs, k)
+    if keepSamples
+        models = models[:, 1:k]; preds = preds[:, 1:k]
+    end
+    checkerr(ctx.ptr, rc)
+    return recs, models, preds
+end
+
+"""
     chainHistBegin!(ctx, targets, nbins, lo, hi);  chainHist(ctx, ntarget, nbins) -> (count, counts[nbins, ntarget])
     chainQuantiles(ctx, q, ntarget) -> values[ntarget, nq];  chainDataMomentsBegin!(ctx);  chainDataMoments(ctx) -> (count, mean, m2)
     chain_hist!(ctx, invParam, hmcprior; targets=all cells, nbins=300) -> (targets, nbins, lo, hi)
@@ -774,7 +825,7 @@ end
 chainAdaptEnd!(ctx::HipContext) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_end(ctx.ptr::Ptr{Cvoid})::Cint)
 
 """
-    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, seed=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt])
+    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, seed=nothing, nuts=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt][, nuts])
 
 runHMCSampler (HMCSampler.jl:72-196) through the chain API, step for step what hmcmt2d_amd/sampler.py's device chain does, the
 reference's start included: the chain's state starts at the file's model invParam.strModel (:88), while start and reference model
@@ -793,10 +844,13 @@ at the end.  hmcprior.dt is the start and is not modified.
 samples with `adapt`, whose trace watches every step.  Julia's generator then draws `rhoref` alone, and the chain is sample by sample
 the one runHMCSampler(device_chain=True, library_rng=(s, c)) gives for the same rhoref.  Column it + 1 of hmstats takes its K from
 sample it + 1's record; the last column's K is NaN (that momentum is never drawn).
+`nuts=maxDepth` (with `seed`): the samples are NUTS samples (`chain_nuts_run!`, `chain_nuts_sample!`), hmcprior.timestep is not
+used, the warm-up's alpha is the tree's, and a last result is appended: the vector of the samples' HmcmtNutsRecord.
 """
 function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior, hmcParam::HMCParameter; keepSamples::Bool=true,
                     rhoref::Union{Nothing,Real}=nothing, seed::Union{Nothing,Tuple{<:Integer,<:Integer}}=nothing,
-                    cov::Union{Nothing,NamedTuple}=nothing, adapt::Union{Nothing,NamedTuple}=nothing)
+                    nuts::Union{Nothing,Integer}=nothing, cov::Union{Nothing,NamedTuple}=nothing, adapt::Union{Nothing,NamedTuple}=nothing)
+    (nuts === nothing || seed !== nothing) || error("run_chain!: nuts needs seed=(s, c): the tree's draws are the library's")
     n, nd = ctx.nAC, ctx.nData
     nsamples = hmcprior.totalsamples
     fileModel = Vector{Float64}(invParam.strModel)
@@ -839,7 +893,10 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
     predOut = keepSamples ? Vector{ComplexF64}(undef, nd) : nothing
     Lmin, Lmax = hmcprior.timestep[1], hmcprior.timestep[2]
     # the library's numbers: the whole run in one call, or sample by sample where the warm-up's trace watches every step
-    seededRecs = (seed === nothing || adapt !== nothing) ? nothing : chain_run!(ctx, nsamples, Lmin, Lmax; keepSamples=keepSamples)
+    seededRecs = (seed === nothing || adapt !== nothing) ? nothing :
+                 (nuts === nothing ? chain_run!(ctx, nsamples, Lmin, Lmax; keepSamples=keepSamples) :
+                                     chain_nuts_run!(ctx, nsamples, nuts; keepSamples=keepSamples))
+    nutsRecs = HmcmtNutsRecord[]
     for it = 1:nsamples
         adapt === nothing || (adaptDt[it] = chainAdaptInfo(ctx).dt)
         if seed === nothing
@@ -847,14 +904,22 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
             u = rand()
             rec = chainStep!(ctx, L, u; mOut=mOut, predOut=predOut)
         elseif seededRecs === nothing
-            rec = chain_sample!(ctx, Lmin, Lmax; mOut=mOut, predOut=predOut)
+            rec = nuts === nothing ? chain_sample!(ctx, Lmin, Lmax; mOut=mOut, predOut=predOut) :
+                                     chain_nuts_sample!(ctx, nuts; mOut=mOut, predOut=predOut)
         else
             rec = seededRecs[1][it]
             if keepSamples
                 mOut = seededRecs[2][:, it]; predOut = seededRecs[3][:, it]
             end
         end
-        adapt === nothing || (adaptAlpha[it] = rec.hdif > 0 ? 1.0 : exp(rec.hdif))
+        if nuts !== nothing                                  # (the tree's record wraps the chain record: unwrapped before any field is read)
+            push!(nutsRecs, rec)
+            alphaOf = rec.alpha
+            rec = rec.rec
+        else
+            alphaOf = rec.hdif > 0 ? 1.0 : exp(rec.hdif)
+        end
+        adapt === nothing || (adaptAlpha[it] = alphaOf)
         hmcprior.nfevals += rec.nfevals
         if rec.accepted == 1
             hmcstats.nAccept += 1
@@ -876,14 +941,15 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
         end
     end
     adaptStats = adapt === nothing ? () : ((nwarmup=nwarmup, dt=adaptDt, alpha=adaptAlpha, dtFinal=chainAdaptInfo(ctx).dt, invM=chainMassDiag(ctx)),)
-    cov === nothing && return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), adaptStats...)
+    nutsStats = nuts === nothing ? () : (nutsRecs,)
+    cov === nothing && return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), adaptStats..., nutsStats...)
     if nsamples > hmcprior.burninsamples
         count, cmean, cvar, cmat = chainCov(ctx, length(covRows))
         covStats = (count=count, rows=covRows, mean=cmean, var=cvar, cov=cmat, corr=chainCorr(ctx, length(covRows)))
     else
         covStats = (count=0, rows=covRows, mean=nothing, var=nothing, cov=nothing, corr=nothing)
     end
-    return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats, adaptStats...)
+    return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats, adaptStats..., nutsStats...)
 end
 
 hipWait(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_wait, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
