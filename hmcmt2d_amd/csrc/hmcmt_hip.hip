@@ -267,10 +267,12 @@ struct hmcmt_ctx {
         double *d_r = nullptr, *d_z = nullptr, *d_pp = nullptr, *d_q = nullptr, *d_s = nullptr;   // PCG vectors, scalars [8]
         int* d_map = nullptr;                             // [nzb*nyb] active index of each box cell, -1 frozen
         // HMCMT_MASS_LOWRANK (hmcmt_set_mass_lowrank): buffers of their own, released by mass_lr_release; d_x, d_in, d_out are shared
-        int lrRank = 0;
+        int lrRank = 0, lrCap = 0;                        // directions in force; rows d_lrU, d_lrC and d_lrPart have room for
         double *d_lrS = nullptr, *d_lrU = nullptr;        // [nAC] s = sqrt(invM), [rank][nAC]
         double *d_lrC = nullptr;                          // [2][rank] lambda - 1, lambda^-1/2 - 1
         double *d_lrPart = nullptr;                       // [rank][LFNB] partial sums of the projection
+        std::vector<double> lrLambda;                     // [rank] lambda as given or estimated (hmcmt_chain_mass_lowrank returns these bits)
+        std::vector<double> lrInvM;                       // [nAC] the invM hmcmt_set_mass_lowrank was given; empty: d_invM holds the scales' squares
     } mass;
     // the device-resident HMC chain (hmcmt_chain_*, host_chain.h, kernels_chain.h)
     long long stateGen = 0;               // counts the evaluations and option changes of the context: a chain compares it with the value it left
@@ -341,6 +343,21 @@ struct hmcmt_ctx {
             int windowsDone = 0;
             double alphaLast = 0, alphaSum = 0;
             double *d_mean = nullptr, *d_m2 = nullptr;   // [nAC] each: the window's Welford accumulator (adapt_mass)
+            // hmcmt_chain_adapt_lowrank: the window's stored pairs and the window end's staging (hmcmt_items.h: item_adapt_lr_*)
+            struct Lr {
+                bool on = false;
+                hmcmt_adapt_lowrank_options opt{};
+                long long winStart = 0, stride = 1;   // the open window's first step and thinning
+                int stored = 0, skipped = 0;          // pairs in the open window, pairs it skipped
+                int closedStored = 0;                 // pairs of the window that closed last (its rows stay in the stores until the next pair)
+                double *d_X = nullptr, *d_G = nullptr;          // [max_samples][nAC] draws, full gradients
+                double *d_K = nullptr, *d_B = nullptr;          // [2 max_samples]^2, [2 max_samples][rank]
+                double *d_meanX = nullptr, *d_meanG = nullptr;  // [nAC]
+                double *d_s = nullptr, *d_U = nullptr, *d_c = nullptr, *d_part = nullptr;   // staging: [nAC], [rank][nAC], [2 rank], [rank][LFNB]
+                std::vector<double> hK, hTheta;
+                double times[4] = {0, 0, 0, 0};       // the last window end: ms of the two pairs, host ms up to K on the host, host ms of the check
+                hmcmt_adapt_lowrank_info last{};
+            } lr;
             std::vector<void*> allocs;
         } adapt;
         struct Nuts {                                 // hmcmt_chain_nuts_*: the tree's buffers, allocated at the first NUTS sample, released with the chain
@@ -2951,7 +2968,9 @@ static void mass_lr_release(hmcmt_ctx* ctx) {
     auto& M = ctx->mass;
     mass_lr_free(ctx, {M.d_lrS, M.d_lrU, M.d_lrC, M.d_lrPart});
     M.d_lrS = M.d_lrU = M.d_lrC = M.d_lrPart = nullptr;
-    M.lrRank = 0;
+    M.lrRank = M.lrCap = 0;
+    M.lrLambda.clear();
+    M.lrInvM.clear();
 }
 
 static void mass_release(hmcmt_ctx* ctx) {
@@ -3271,24 +3290,16 @@ int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
     return 0;
 }
 
-// uploads s, U, the two coefficient rows and checks U'U = I with the projection kernel: row j of U projected onto every row
-static int mass_lr_build(hmcmt_ctx* ctx, int rank, const std::vector<double>& s, const double* U, const std::vector<double>& c,
-                         double** d_s, double** d_U, double** d_c, double** d_part, double* defect) {
+// max |U U' - I| of rank directions ALREADY ON THE DEVICE, with the projection kernel: row j of U projected onto every row (d_s and d_c
+// are only carried along: HMCMT_MASS_OP_SQRT reads neither).  One wait.
+static int mass_lr_defect(hmcmt_ctx* ctx, int rank, const double* d_s, const double* d_U, const double* d_c, double* d_part, double* defect) {
     const int n = ctx->v.nAC;
     hipStream_t st = ctx->stream;
-    int rc;
-    if ((rc = dupload(ctx, d_s, s))) return rc;
-    if ((rc = dalloc(ctx, d_U, (size_t)rank * n, false))) return rc;
-    HIPCHK(hipMemcpy(*d_U, U, sizeof(double) * rank * n, hipMemcpyHostToDevice));
-    if ((rc = dupload(ctx, d_c, c))) return rc;
-    if ((rc = dalloc(ctx, d_part, (size_t)rank * LFNB))) return rc;
-    for (double** p : {&ctx->mass.d_x, &ctx->mass.d_in, &ctx->mass.d_out})
-        if (!*p && (rc = dalloc(ctx, p, (size_t)n))) return rc;
     std::vector<double> part((size_t)rank * rank * LFNB);
-    const MassLr m{n, rank, HMCMT_MASS_OP_SQRT, *d_s, *d_U, *d_c, *d_part};
+    const MassLr m{n, rank, HMCMT_MASS_OP_SQRT, d_s, d_U, d_c, d_part};
     for (int j = 0; j < rank; ++j) {
-        hipLaunchKernelGGL(k_mass_lr_project, dim3(LFNB), dim3(256), 0, st, m, *d_U + (size_t)j * n);
-        HIPCHK(hipMemcpyAsync(&part[(size_t)j * rank * LFNB], *d_part, sizeof(double) * rank * LFNB, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_mass_lr_project, dim3(LFNB), dim3(256), 0, st, m, d_U + (size_t)j * n);
+        HIPCHK(hipMemcpyAsync(&part[(size_t)j * rank * LFNB], d_part, sizeof(double) * rank * LFNB, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
@@ -3300,6 +3311,29 @@ static int mass_lr_build(hmcmt_ctx* ctx, int rank, const std::vector<double>& s,
         }
     *defect = worst;
     return 0;
+}
+// the low-rank mass's own buffers for `rank` directions (nothing uploaded), and the three vectors every non-diagonal mass shares
+static int mass_lr_alloc(hmcmt_ctx* ctx, int rank, double** d_s, double** d_U, double** d_c, double** d_part) {
+    const int n = ctx->v.nAC;
+    int rc;
+    if ((rc = dalloc(ctx, d_s, (size_t)n, false))) return rc;             // (s, U and c are written before they are read)
+    if ((rc = dalloc(ctx, d_U, (size_t)rank * n, false))) return rc;
+    if ((rc = dalloc(ctx, d_c, (size_t)2 * rank, false))) return rc;
+    if ((rc = dalloc(ctx, d_part, (size_t)rank * LFNB))) return rc;
+    for (double** p : {&ctx->mass.d_x, &ctx->mass.d_in, &ctx->mass.d_out})
+        if (!*p && (rc = dalloc(ctx, p, (size_t)n))) return rc;
+    return 0;
+}
+// allocates, uploads s, U, the two coefficient rows and checks U U' = I
+static int mass_lr_build(hmcmt_ctx* ctx, int rank, const std::vector<double>& s, const double* U, const std::vector<double>& c,
+                         double** d_s, double** d_U, double** d_c, double** d_part, double* defect) {
+    const int n = ctx->v.nAC;
+    int rc;
+    if ((rc = mass_lr_alloc(ctx, rank, d_s, d_U, d_c, d_part))) return rc;
+    HIPCHK(hipMemcpy(*d_s, s.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(*d_U, U, sizeof(double) * rank * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(*d_c, c.data(), sizeof(double) * 2 * rank, hipMemcpyHostToDevice));
+    return mass_lr_defect(ctx, rank, *d_s, *d_U, *d_c, *d_part, defect);
 }
 
 int hmcmt_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, const double* U, const double* lambda) {
@@ -3359,7 +3393,9 @@ int hmcmt_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, con
     chain_release(ctx);                                     // (a chain belongs to the mass it began with)
     mass_lr_release(ctx);
     M.d_lrS = d_s; M.d_lrU = d_U; M.d_lrC = d_c; M.d_lrPart = d_part;
-    M.lrRank = rank;
+    M.lrRank = M.lrCap = rank;
+    M.lrLambda.assign(lambda, lambda + rank);
+    if (invM) M.lrInvM.assign(invM, invM + n);
     M.kind = HMCMT_MASS_LOWRANK;
     return 0;
 }

@@ -15,6 +15,8 @@
 #if !defined(__HIPCC__)
 #include <algorithm>
 #endif
+#include <cmath>
+#include <vector>
 
 namespace hmcmt {
 
@@ -1397,6 +1399,250 @@ HD bool extrap_weights(const double* a, double* ext, int maxNp, int coldUnlessSm
         ext[EXT_MHEAD] = (double)(((int)ext[EXT_MHEAD] + EXT_NP) % (EXT_NP + 1));
     }
     return keep;
+}
+
+// ----------------------------------------------------------------------------------------------
+// low-rank mass in the warm-up (hmcmt_chain_adapt_lowrank; kernels_chain.h: k_adapt_lr_store, k_adapt_lr_mean, k_adapt_lr_gram,
+// k_adapt_lr_lift, k_adapt_lr_sign; include/hmcmt.h has the algorithm)
+// ----------------------------------------------------------------------------------------------
+// A window stores n <= ADAPT_LR_NMAX pairs (draw, full potential gradient), rows X[i][.], G[i][.] of nAC cells.  With s = sqrt(invM)
+// and W = [Zd; Zg], Zd = (X - mean_X) / s / sqrt(n - 1), Zg = (G - mean_G) s / sqrt(n - 1), the device forms K = W W' ([2n][2n]) and,
+// from the host's B ([2n][r]), U = B' W.  Every sum has one owner and one order: the means add the rows upwards and divide once;
+// K[i][j] is ONE fma chain over the cells upwards from 0 (the workgroup that owns the tile walks all cells); U[k][a] is one fma chain
+// over the rows upwards.  Nothing here can be contracted differently by two compilers: the products stand inside fma, the rest are
+// single operations.
+constexpr int ADAPT_LR_NMIN = 4, ADAPT_LR_NMAX = 128;       // pairs per window: below NMIN the window falls back to the diagonal
+constexpr int ADAPT_LR_TILE = 16;                          // a workgroup owns ADAPT_LR_TILE x ADAPT_LR_TILE outputs of K
+constexpr int ADAPT_LR_STRIP = 64;                         // cells of the two row blocks staged through LDS per pass
+// thinning: the window's length is known when it opens; its i-th step is stored when i % stride == 0
+HD long long item_adapt_lr_stride(long long length, long long maxSamples) { return length <= maxSamples ? 1 : (length + maxSamples - 1) / maxSamples; }
+HD bool item_adapt_lr_due(long long i, long long stride) { return i % stride == 0; }
+// cell a's entry of the full potential gradient g_data + lambda Wm (m - m_ref): the CSR row arithmetic of k_lf_momentum_max
+HD double item_adapt_lr_grad(const double* gdata, double lambda, const long long* wmRow, const long long* wmCol, const double* wmVal,
+                             const double* m, const double* mref, long long a) {
+    double acc = 0.0;
+    for (long long t = wmRow[a]; t < wmRow[a + 1]; ++t) {
+        const long long j = wmCol[t];
+        acc += wmVal[t] * (m[j] - mref[j]);
+    }
+    return gdata[a] + lambda * acc;
+}
+// cell a's mean over the n stored rows, in row order
+HD double item_adapt_lr_mean(const double* R, long long nAC, int n, long long a) {
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) acc += R[(long long)i * nAC + a];
+    return acc / (double)n;
+}
+// W[i][a], i < 2n: the centred draw over s (i < n) or the centred gradient times s; sq = sqrt(n - 1) as a double
+HD double item_adapt_lr_w(const double* X, const double* G, const double* meanX, const double* meanG, const double* s, long long nAC, int n,
+                          double sq, int i, long long a) {
+    if (i < n) return ((X[(long long)i * nAC + a] - meanX[a]) / s[a]) / sq;
+    return ((G[(long long)(i - n) * nAC + a] - meanG[a]) * s[a]) / sq;
+}
+// one term of K[i][j] and of U[k][a]
+HD double item_adapt_lr_dot(double wi, double wj, double acc) { return fma(wi, wj, acc); }
+// U[k][a] = sum_i B[i][k] W[i][a], i upwards
+HD double item_adapt_lr_lift(const double* X, const double* G, const double* meanX, const double* meanG, const double* s, const double* B,
+                             long long nAC, int n, double sq, int r, int k, long long a) {
+    double acc = 0.0;
+    for (int i = 0; i < 2 * n; ++i) acc = item_adapt_lr_dot(B[(long long)i * r + k], item_adapt_lr_w(X, G, meanX, meanG, s, nAC, n, sq, i, a), acc);
+    return acc;
+}
+// the sign convention's comparison: does (|v|, a) beat (best, at)?  The larger magnitude wins, the lower index a tie
+HD bool item_adapt_lr_beats(double v, long long a, double best, long long at) { return v > best || (v == best && a < at); }
+
+// ---- the host's share of a window end, in double (the emulation of tests/emul runs these very functions) ---------------------------
+// Cyclic Jacobi for a symmetric A [n][n] (row-major, destroyed): d[k] ascending, Vt[k][.] the unit eigenvector of d[k].  Rows sweep
+// (p, q), p < q upwards; a rotation is skipped where |a_pq| <= 2^-53 sqrt|a_pp a_qq| or |a_pq| <= 1e-40 |A|_F; the sweeps end with
+// the first one that rotates nothing, after ADAPT_LR_SWEEPS_MAX at the latest.  Returns the sweeps taken: ADAPT_LR_SWEEPS_MAX says not converged.
+constexpr int ADAPT_LR_SWEEPS_MAX = 64;
+inline int item_jacobi_eig(int n, double* A, double* Vt, double* d) {
+    double frob = 0.0;
+    for (long long e = 0; e < (long long)n * n; ++e) frob += A[e] * A[e];
+    const double floorAbs = 1e-40 * sqrt(frob), eps = 1.1102230246251565e-16;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) Vt[(long long)i * n + j] = i == j ? 1.0 : 0.0;
+    int sweep = 0;
+    for (; sweep < ADAPT_LR_SWEEPS_MAX; ++sweep) {
+        long long rotated = 0;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                double* Ap = A + (long long)p * n;
+                double* Aq = A + (long long)q * n;
+                const double apq = Ap[q], app = Ap[p], aqq = Aq[q];
+                if (!(fabs(apq) > eps * sqrt(fabs(app * aqq))) || !(fabs(apq) > floorAbs)) { Ap[q] = Aq[p] = (fabs(apq) > floorAbs ? apq : 0.0); continue; }
+                ++rotated;
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) {
+                    const double akp = Ap[k], akq = Aq[k];
+                    Ap[k] = c * akp - s * akq;
+                    Aq[k] = s * akp + c * akq;
+                }
+                Ap[p] = app - t * apq; Aq[q] = aqq + t * apq; Ap[q] = Aq[p] = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    if (k == p || k == q) continue;
+                    A[(long long)k * n + p] = Ap[k];
+                    A[(long long)k * n + q] = Aq[k];
+                }
+                double* Vp = Vt + (long long)p * n;
+                double* Vq = Vt + (long long)q * n;
+                for (int k = 0; k < n; ++k) {
+                    const double vp = Vp[k], vq = Vq[k];
+                    Vp[k] = c * vp - s * vq;
+                    Vq[k] = s * vp + c * vq;
+                }
+            }
+        if (rotated == 0) break;
+    }
+    // ascending, the lower index first among equals (insertion sort: n <= 256)
+    for (int i = 0; i < n; ++i) d[i] = A[(long long)i * n + i];
+    for (int i = 1; i < n; ++i)
+        for (int j = i; j > 0 && d[j] < d[j - 1]; --j) {
+            const double td = d[j]; d[j] = d[j - 1]; d[j - 1] = td;
+            for (int k = 0; k < n; ++k) { const double tv = Vt[(long long)j * n + k]; Vt[(long long)j * n + k] = Vt[(long long)(j - 1) * n + k]; Vt[(long long)(j - 1) * n + k] = tv; }
+        }
+    return sweep;
+}
+inline void item_adapt_lr_matmul(int m, const double* A, const double* B, double* C) {      // C = A B, all [m][m]
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) C[(size_t)i * m + j] = 0.0;
+    for (int i = 0; i < m; ++i)
+        for (int k = 0; k < m; ++k) {
+            const double a = A[(size_t)i * m + k];
+            for (int j = 0; j < m; ++j) C[(size_t)i * m + j] += a * B[(size_t)k * m + j];
+        }
+}
+struct AdaptLrEstimate {
+    int m = 0, r = 0, fallback = 0;            // dimensions kept of K, directions selected, 1: no estimate (the window ends on the diagonal)
+    double thetaMin = 0, thetaMax = 0;         // over all m
+    std::vector<double> thetaAll;              // [m] ascending
+    std::vector<double> theta;                 // [r] by |ln theta| descending
+    std::vector<double> B;                     // [2n][r]: U = B' W
+};
+// The window end's host maths in three parts, so that the emulation can put another Sigma between the first and the last (the
+// exact-answer test's counter-example); item_adapt_lr_estimate is the three in a row and what the library calls.
+// 1. From K = W W' ([2n][2n]) of n pairs: the m eigenvalues D_i > 1e-10 D_max kept, T = D^-1/2 V' ([m][2n]: T W has orthonormal rows),
+//    and the two covariances projected on them, Cd = Pd Pd' + gamma I and Cg = Pg Pg' + gamma I with [Pd Pg] = T K.  Returns m, 0: none.
+inline int item_adapt_lr_project(int n, const double* K, double gamma, std::vector<double>& T, std::vector<double>& Cd, std::vector<double>& Cg) {
+    const int N2 = 2 * n;
+    if (n < ADAPT_LR_NMIN) return 0;
+    for (size_t e = 0; e < (size_t)N2 * N2; ++e)
+        if (!std::isfinite(K[e])) return 0;
+    std::vector<double> A(K, K + (size_t)N2 * N2), Vt((size_t)N2 * N2), d((size_t)N2);
+    if (item_jacobi_eig(N2, A.data(), Vt.data(), d.data()) >= ADAPT_LR_SWEEPS_MAX) return 0;
+    const double dmax = d[N2 - 1];
+    if (!(dmax > 0.0)) return 0;
+    int first = 0;
+    while (first < N2 && !(d[first] > 1e-10 * dmax)) ++first;
+    const int m = N2 - first;
+    T.assign((size_t)m * N2, 0.0);                          // T = D^-1/2 V'
+    for (int k = 0; k < m; ++k) {
+        const double f = 1.0 / sqrt(d[first + k]);
+        for (int i = 0; i < N2; ++i) T[(size_t)k * N2 + i] = Vt[(size_t)(first + k) * N2 + i] * f;
+    }
+    std::vector<double> P((size_t)m * N2);                 // P = T K = [Pd Pg]
+    for (int k = 0; k < m; ++k)
+        for (int j = 0; j < N2; ++j) {
+            double acc = 0.0;
+            for (int i = 0; i < N2; ++i) acc += T[(size_t)k * N2 + i] * K[(size_t)i * N2 + j];
+            P[(size_t)k * N2 + j] = acc;
+        }
+    Cd.assign((size_t)m * m, 0.0); Cg.assign((size_t)m * m, 0.0);
+    for (int a = 0; a < m; ++a)
+        for (int b = 0; b < m; ++b) {
+            double sd = 0.0, sg = 0.0;
+            for (int j = 0; j < n; ++j) {
+                sd += P[(size_t)a * N2 + j] * P[(size_t)b * N2 + j];
+                sg += P[(size_t)a * N2 + n + j] * P[(size_t)b * N2 + n + j];
+            }
+            Cd[(size_t)a * m + b] = sd + (a == b ? gamma : 0.0);
+            Cg[(size_t)a * m + b] = sg + (a == b ? gamma : 0.0);
+        }
+    return m;
+}
+inline void item_adapt_lr_symmetrise(int m, std::vector<double>& S) {
+    for (int a = 0; a < m; ++a)
+        for (int b = a + 1; b < m; ++b) S[(size_t)a * m + b] = S[(size_t)b * m + a] = 0.5 * (S[(size_t)a * m + b] + S[(size_t)b * m + a]);
+}
+// 2. Sigma = Cg^-1/2 (Cg^1/2 Cd Cg^1/2)^1/2 Cg^-1/2, the symmetric positive definite solution of Sigma Cg Sigma = Cd, and its
+//    eigenpairs: th ascending, Yt[k][.] the eigenvector of th[k].  Evaluated in the eigenbasis of Cg = Q Gamma Q', where the powers of Cg
+//    are diagonal scalings: Cg's eigenvalues reach from gamma up, and a product with a dense Cg^+-1/2 would round its small ones away.
+//    false: an eigensolver that did not converge, an eigenvalue that is not finite and positive.
+inline bool item_adapt_lr_sigma(int m, const std::vector<double>& Cd, const std::vector<double>& Cg, std::vector<double>& Yt, std::vector<double>& th) {
+    std::vector<double> Sig((size_t)m * m), t1((size_t)m * m), t2((size_t)m * m);
+    std::vector<double> Qt((size_t)m * m), g((size_t)m), QtT((size_t)m * m), Zt((size_t)m * m), e((size_t)m);
+    Yt.assign((size_t)m * m, 0.0); th.assign((size_t)m, 0.0);
+    t1 = Cg;
+    if (item_jacobi_eig(m, t1.data(), Qt.data(), g.data()) >= ADAPT_LR_SWEEPS_MAX) return false;
+    for (int k = 0; k < m; ++k) {
+        if (!(g[k] > 0.0) || !std::isfinite(g[k])) return false;
+        g[k] = sqrt(g[k]);
+    }
+    for (int a = 0; a < m; ++a)
+        for (int b = 0; b < m; ++b) QtT[(size_t)a * m + b] = Qt[(size_t)b * m + a];
+    item_adapt_lr_matmul(m, Qt.data(), Cd.data(), t1.data());
+    item_adapt_lr_matmul(m, t1.data(), QtT.data(), t2.data());                // Q' Cd Q
+    item_adapt_lr_symmetrise(m, t2);
+    for (int a = 0; a < m; ++a)
+        for (int b = 0; b < m; ++b) t2[(size_t)a * m + b] = g[a] * t2[(size_t)a * m + b] * g[b];
+    if (item_jacobi_eig(m, t2.data(), Zt.data(), e.data()) >= ADAPT_LR_SWEEPS_MAX) return false;
+    for (int k = 0; k < m; ++k) {
+        if (!(e[k] > 0.0) || !std::isfinite(e[k])) return false;
+        e[k] = sqrt(e[k]);
+    }
+    for (int a = 0; a < m; ++a)
+        for (int b = 0; b < m; ++b) {
+            double acc = 0.0;
+            for (int k = 0; k < m; ++k) acc += Zt[(size_t)k * m + a] * e[k] * Zt[(size_t)k * m + b];
+            Sig[(size_t)a * m + b] = acc / g[a] / g[b];
+        }
+    item_adapt_lr_symmetrise(m, Sig);
+    if (item_jacobi_eig(m, Sig.data(), t1.data(), th.data()) >= ADAPT_LR_SWEEPS_MAX) return false;   // rows of t1: eigenvectors in Cg's eigenbasis
+    item_adapt_lr_matmul(m, t1.data(), Qt.data(), Yt.data());                 // ... and back: Y = Q Yq
+    return true;
+}
+// 3. The selection -- theta > cutoff or theta < 1 / cutoff, by |ln theta| descending, the lower index first among equals, at most rank --
+//    and the coefficients B = T' Y_sel of the selected directions.
+inline AdaptLrEstimate item_adapt_lr_select(int n, int m, const std::vector<double>& T, const std::vector<double>& Yt, const std::vector<double>& th,
+                                            int rank, double cutoff) {
+    AdaptLrEstimate E;
+    E.fallback = 1;
+    const int N2 = 2 * n;
+    for (int k = 0; k < m; ++k)
+        if (!(th[k] > 0.0) || !std::isfinite(th[k])) return E;
+    std::vector<int> sel;
+    for (int k = 0; k < m; ++k)
+        if (th[k] > cutoff || th[k] < 1.0 / cutoff) sel.push_back(k);
+    for (size_t i = 1; i < sel.size(); ++i)
+        for (size_t j = i; j > 0 && fabs(log(th[sel[j]])) > fabs(log(th[sel[j - 1]])); --j) { const int t = sel[j]; sel[j] = sel[j - 1]; sel[j - 1] = t; }
+    if ((int)sel.size() > rank) sel.resize((size_t)rank);
+    const int r = (int)sel.size();
+    E.m = m; E.r = r; E.fallback = 0;
+    E.thetaMin = th[0]; E.thetaMax = th[m - 1];
+    E.thetaAll = th;
+    E.theta.resize((size_t)r);
+    E.B.assign((size_t)N2 * r, 0.0);
+    for (int c = 0; c < r; ++c) {
+        E.theta[c] = th[sel[c]];
+        for (int i = 0; i < N2; ++i) {
+            double acc = 0.0;
+            for (int j = 0; j < m; ++j) acc += T[(size_t)j * N2 + i] * Yt[(size_t)sel[c] * m + j];
+            E.B[(size_t)i * r + c] = acc;
+        }
+    }
+    for (double v : E.B)
+        if (!std::isfinite(v)) { E = AdaptLrEstimate{}; E.fallback = 1; return E; }
+    return E;
+}
+inline AdaptLrEstimate item_adapt_lr_estimate(int n, const double* K, int rank, double cutoff, double gamma) {
+    AdaptLrEstimate none;
+    none.fallback = 1;
+    std::vector<double> T, Cd, Cg, Yt, th;
+    const int m = item_adapt_lr_project(n, K, gamma, T, Cd, Cg);
+    if (m == 0 || !item_adapt_lr_sigma(m, Cd, Cg, Yt, th)) return none;
+    return item_adapt_lr_select(n, m, T, Yt, th, rank, cutoff);
 }
 
 }  // namespace hmcmt

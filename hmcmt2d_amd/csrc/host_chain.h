@@ -263,27 +263,157 @@ static int chain_fail(hmcmt_ctx* ctx, int rc) {
     return rc;
 }
 
+// ---- low-rank mass in the warm-up (hmcmt_chain_adapt_lowrank; hmcmt.h has the algorithm, kernels_chain.h the kernels) -------------
+// a counted step inside a window, behind the Welford kernel: one launch where the step is due, no wait
+static void chain_adapt_lr_store(hmcmt_ctx* ctx) {
+    auto& C = ctx->chain;
+    auto& L = C.adapt.lr;
+    const int n = ctx->v.nAC;
+    const long long i = C.adapt.c - L.winStart;
+    if (i < 0 || !item_adapt_lr_due(i, L.stride) || L.stored >= L.opt.max_samples) return;
+    // (NOT REACHED in this library: both callers set lfHaveGrad behind their decision, also where a foreign evaluation came between two
+    // steps -- the step then evaluated its own start gradient.  Kept so that a future caller without a gradient skips and counts
+    // instead of storing a stale one; `skipped` is 0 in every chain that can be run today)
+    if (!ctx->lfHaveGrad) { ++L.skipped; return; }
+    // the data gradient at the current model: what the next step's start_grad 1 (accepted; a NUTS sample's selection) or 2 (rejected) reuses
+    const double* gdata = C.nextStart == 2 ? ctx->d_gStart : ctx->d_g;
+    LfView lf{n, ctx->d_mref, ctx->d_invM, ctx->d_wmVal, ctx->d_wmRow, ctx->d_wmCol, C.d_m[C.cur], C.d_p, ctx->d_g,
+              ctx->d_lfPart, ctx->d_lfScal, ctx->d_lfFlag, ctx->v.ticks};
+    hipLaunchKernelGGL(k_adapt_lr_store, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, lf, gdata, C.regParam,
+                       L.d_X + (size_t)L.stored * n, L.d_G + (size_t)L.stored * n);
+    ++L.stored;
+}
+
+// K = W W' of n rows on the device into d_K (enqueued): the means and s = sqrt(invM), then the tiles of the upper block triangle
+static AdaptLr chain_adapt_lr_gram(hipStream_t st, int nAC, int n, const double* d_X, const double* d_G, const double* d_invM, double* d_meanX,
+                                   double* d_meanG, double* d_s, double* d_K) {
+    const AdaptLr w{nAC, n, std::sqrt((double)(n - 1)), d_X, d_G, d_meanX, d_meanG, d_s};
+    hipLaunchKernelGGL(k_adapt_lr_mean, dim3((nAC + 255) / 256), dim3(256), 0, st, nAC, n, d_X, d_G, d_invM, d_meanX, d_meanG, d_s);
+    const int T = (2 * n + ADAPT_LR_TILE - 1) / ADAPT_LR_TILE;
+    hipLaunchKernelGGL(k_adapt_lr_gram, dim3(T * (T + 1) / 2), dim3(256), 0, st, w, d_K);
+    return w;
+}
+// U = B' W into d_U with the sign convention (enqueued; B is on the device)
+static void chain_adapt_lr_lift(hipStream_t st, const AdaptLr& w, const double* d_B, int r, double* d_U) {
+    hipLaunchKernelGGL(k_adapt_lr_lift, dim3((w.nAC + 255) / 256), dim3(256), 0, st, w, d_B, r, d_U);
+    hipLaunchKernelGGL(k_adapt_lr_sign, dim3(r), dim3(256), 0, st, w.nAC, d_U);
+}
+
+// A window's end behind k_chain_adapt_mass (hmcmt.h: a. to e.).  It waits for K -- the adaptation's one added wait, once per window --
+// and, where directions were kept, for the orthonormality check's partial sums.  A window that yields no estimate (fewer than four
+// pairs, a non-finite value, an eigensolver that did not converge, defect above 1e-8) ends on the diagonal mass with fallback = 1 and
+// returns 0; a HIP error ends there too but is NOT a fallback: ctx->err names it and HMCMT_EHIP goes back to the step.  Two event pairs
+// time the kernels of every window end (hmcmt_debug_adapt_lowrank_time): four records per window, nothing per step.
+static int chain_adapt_lr_window_end(hmcmt_ctx* ctx) {
+    auto& C = ctx->chain;
+    auto& L = C.adapt.lr;
+    auto& M = ctx->mass;
+    const int nAC = ctx->v.nAC, n = L.stored;
+    hipStream_t st = ctx->stream;
+    hmcmt_adapt_lowrank_info info{};
+    info.windows = L.last.windows + 1;
+    info.stored = n; info.skipped = L.skipped; info.stride = L.stride;
+    info.fallback = 1;
+    int r = 0, rc = 0;
+    auto failed = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return false;
+        (void)hipGetLastError();
+        ctx->err = std::string("hmcmt_chain_adapt_lowrank, window end: ") + what + ": " + hipGetErrorString(e);
+        rc = HMCMT_EHIP;
+        return true;
+    };
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};     // (made and destroyed here: once per window end)
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; }
+    const bool timed = ev[0] && ev[1] && ev[2] && ev[3];
+    for (double& t : L.times) t = 0.0;
+    bool lifted = false;
+    [&]() {
+        if (n < ADAPT_LR_NMIN) return;
+        const auto w0 = std::chrono::steady_clock::now();
+        if (timed) hipEventRecord(ev[0], st);
+        const AdaptLr w = chain_adapt_lr_gram(st, nAC, n, L.d_X, L.d_G, ctx->d_invM, L.d_meanX, L.d_meanG, L.d_s, L.d_K);
+        if (timed) hipEventRecord(ev[1], st);
+        const size_t N2 = (size_t)2 * n;
+        L.hK.resize(N2 * N2);
+        if (failed(hipMemcpyAsync(L.hK.data(), L.d_K, sizeof(double) * N2 * N2, hipMemcpyDeviceToHost, st), "the download of K")) return;
+        if (failed(hipStreamSynchronize(st), "the wait for K")) return;             // the window end's wait
+        const auto t0 = std::chrono::steady_clock::now();
+        L.times[2] = std::chrono::duration<double, std::milli>(t0 - w0).count();
+        const AdaptLrEstimate E = item_adapt_lr_estimate(n, L.hK.data(), L.opt.rank, L.opt.cutoff, L.opt.gamma);
+        const auto t1 = std::chrono::steady_clock::now();
+        info.host_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        if (E.fallback) return;
+        info.dims = E.m; info.theta_min = E.thetaMin; info.theta_max = E.thetaMax;
+        if (E.r == 0) { info.fallback = 0; return; }
+        if (E.r > M.lrCap) return;                           // (cannot happen: the estimate keeps at most opt.rank == lrCap; the buffers are sized by it)
+        std::vector<double> c((size_t)2 * E.r);
+        for (int k = 0; k < E.r; ++k) { c[k] = E.theta[k] - 1.0; c[E.r + k] = 1.0 / std::sqrt(E.theta[k]) - 1.0; }
+        // (the stream is idle behind the wait: the two small uploads are complete when they return)
+        if (failed(hipMemcpy(L.d_B, E.B.data(), sizeof(double) * N2 * E.r, hipMemcpyHostToDevice), "the upload of B")) return;
+        if (failed(hipMemcpy(L.d_c, c.data(), sizeof(double) * 2 * E.r, hipMemcpyHostToDevice), "the upload of the coefficients")) return;
+        if (timed) hipEventRecord(ev[2], st);
+        chain_adapt_lr_lift(st, w, L.d_B, E.r, L.d_U);
+        if (timed) hipEventRecord(ev[3], st);
+        lifted = true;
+        double defect = INFINITY;
+        if (mass_lr_defect(ctx, E.r, L.d_s, L.d_U, L.d_c, L.d_part, &defect)) { rc = HMCMT_EHIP; return; }   // (ctx->err is set)
+        L.times[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        info.defect = defect;
+        if (!(defect <= 1e-8)) return;
+        // filled and checked: now into the mass's own buffers, behind everything that still reads them
+        if (failed(hipMemcpyAsync(M.d_lrS, L.d_s, sizeof(double) * nAC, hipMemcpyDeviceToDevice, st), "the copy of s") ||
+            failed(hipMemcpyAsync(M.d_lrU, L.d_U, sizeof(double) * (size_t)E.r * nAC, hipMemcpyDeviceToDevice, st), "the copy of U") ||
+            failed(hipMemcpyAsync(M.d_lrC, L.d_c, sizeof(double) * 2 * E.r, hipMemcpyDeviceToDevice, st), "the copy of the coefficients")) return;
+        r = E.r;
+        L.hTheta = E.theta;
+        info.fallback = 0;
+    }();
+    if (!rc) {
+        const hipError_t e = hipGetLastError();              // (a launch that failed: not a statistical fallback either)
+        if (failed(e, "a kernel launch")) { r = 0; info.fallback = 1; }
+    }
+    if (timed && !rc && n >= ADAPT_LR_NMIN) {                // (both pairs are complete: the last wait came behind them)
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) L.times[0] = ms;
+        if (lifted && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) L.times[1] = ms;
+        (void)hipGetLastError();
+    }
+    for (auto& e : ev)
+        if (e) hipEventDestroy(e);
+    info.rank = r;
+    M.lrRank = r;
+    if (r > 0) M.lrLambda.assign(L.hTheta.begin(), L.hTheta.begin() + r); else M.lrLambda.clear();
+    M.kind = r > 0 ? HMCMT_MASS_LOWRANK : HMCMT_MASS_DIAGONAL;
+    L.last = info;
+    return rc;
+}
+
 // One counted step of the warm-up (hmcmt.h: 1. to 5.), behind the decision and the commit: launches on the context's stream and scalar
-// host work, no wait.  alpha: the step's acceptance probability min(1, exp(hdif)), a NUTS sample's mean over its leaves.  The mass
-// kernel runs behind the commit, in front of the next k_chain_momentum.
-static void chain_adapt_step(hmcmt_ctx* ctx, double alpha) {
+// host work, no wait -- but for the end of a window of an adaptation upgraded by hmcmt_chain_adapt_lowrank (above).  alpha: the step's
+// acceptance probability min(1, exp(hdif)), a NUTS sample's mean over its leaves.  The mass kernel runs behind the commit, in front of
+// the next k_chain_momentum.  Returns 0, or HMCMT_EHIP where a window end met a HIP error (the adaptation's bookkeeping is complete either way).
+static int chain_adapt_step(hmcmt_ctx* ctx, double alpha) {
     auto& C = ctx->chain;
     auto& A = C.adapt;
     const hmcmt_adapt_options& o = A.opt;
     const int n = ctx->v.nAC;
     hipStream_t st = ctx->stream;
+    int rc = 0;
     A.alphaLast = alpha;
     A.alphaSum += alpha;
     const bool inWindow = o.adapt_mass && A.c >= o.init_buffer && A.c < o.nwarmup - o.term_buffer;
     if (inWindow) {
         ++A.wcount;
         hipLaunchKernelGGL(k_chain_welford, dim3((n + 255) / 256), dim3(256), 0, st, n, C.d_m[C.cur], A.d_mean, A.d_m2, (double)A.wcount);
+        if (A.lr.on) chain_adapt_lr_store(ctx);
     }
     C.dt = item_adapt_dt(item_adapt_update(A.da, alpha, o.delta, o.gamma, o.t0, o.kappa), o.dt_min, o.dt_max);
     if (inWindow && A.c == A.wnext) {
         if (A.wcount >= 2) {
             const double dn = (double)A.wcount, w = dn / (dn + 5.0), f = 1e-3 * 5.0 / (dn + 5.0);
             hipLaunchKernelGGL(k_chain_adapt_mass, dim3((n + 255) / 256), dim3(256), 0, st, n, A.d_m2, dn - 1.0, w, f, ctx->d_invM);
+            if (A.lr.on) rc = chain_adapt_lr_window_end(ctx);
             ++A.windowsDone;
             item_adapt_restart(A.da, C.dt);
         }
@@ -291,11 +421,18 @@ static void chain_adapt_step(hmcmt_ctx* ctx, double alpha) {
         (void)hipMemsetAsync(A.d_m2, 0, sizeof(double) * n, st);
         A.wcount = 0;
         A.wnext = item_adapt_next_window(A.c, &A.wsize, o.nwarmup, o.term_buffer);
+        if (A.lr.on) {                                       // the stores rewind; the next window's length is known now
+            A.lr.winStart = A.c + 1;
+            A.lr.stride = A.wnext >= 0 ? item_adapt_lr_stride(A.wnext - A.c, A.lr.opt.max_samples) : 1;
+            A.lr.closedStored = A.lr.stored;
+            A.lr.stored = A.lr.skipped = 0;
+        }
     }
     if (++A.c == o.nwarmup) {
         if (A.da.t > 0) C.dt = item_adapt_dt(A.da.x_bar, o.dt_min, o.dt_max);
         A.active = false;
     }
+    return rc;
 }
 
 int hmcmt_chain_begin(hmcmt_ctx* ctx, const double* m_start, double dt, double regParam, double lnSigMin, double lnSigMax,
@@ -528,8 +665,9 @@ static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, 
     if (accepted) { C.cur = prop; C.D = D1; C.M = M1; }
     C.nextStart = accepted ? 1 : 2;
     chain_commit(ctx);
-    if (C.adapt.active) chain_adapt_step(ctx, hdif > 0 ? 1.0 : std::exp(hdif));
+    const int arc = C.adapt.active ? chain_adapt_step(ctx, hdif > 0 ? 1.0 : std::exp(hdif)) : 0;
     C.gen = ctx->stateGen;
+    if (arc) return chain_fail(ctx, arc);                    // (the sample stands; the call reports the window end's HIP error)
     rec->accepted = accepted ? 1 : 0;
     rec->nfevals = evals - (startGrad != 0 ? 1 : 0);
     rec->K0 = K0; rec->K1 = K1; rec->D1 = D1; rec->M1 = M1;
@@ -904,8 +1042,9 @@ static int chain_nuts_sample(hmcmt_ctx* ctx, const char* fn, int32_t maxDepth, h
     if (movedOn) { C.cur = prop; C.D = sel[1]; C.M = sel[2]; }
     const double alpha = T.alphaSum / (double)T.nleaves;
     chain_commit(ctx);
-    if (C.adapt.active) chain_adapt_step(ctx, alpha);
+    const int arc = C.adapt.active ? chain_adapt_step(ctx, alpha) : 0;
     C.gen = ctx->stateGen;
+    if (arc) return chain_fail(ctx, arc);                    // (the sample stands; the call reports the window end's HIP error)
     std::memset(rec, 0, sizeof *rec);
     rec->rec.accepted = movedOn ? 1 : 0;
     rec->rec.nfevals = evals;
@@ -1459,6 +1598,240 @@ int hmcmt_chain_adapt_end(hmcmt_ctx* ctx) {
         if (A.da.t > 0) C.dt = item_adapt_dt(A.da.x_bar, A.opt.dt_min, A.opt.dt_max);
         A.active = false;                                    // (the window's buffers go with the chain, or with the next begin call)
     }
+    return 0;
+}
+
+// ---- the low-rank mass of a live chain: the warm-up's upgrade, its info, the between-steps setter and the read-out ----------------
+void hmcmt_default_adapt_lowrank_options(hmcmt_adapt_lowrank_options* o) {
+    if (!o) return;
+    *o = hmcmt_adapt_lowrank_options{};
+    o->rank = 8; o->max_samples = 64; o->cutoff = 2.0; o->gamma = 1e-5;
+}
+
+int hmcmt_chain_adapt_lowrank(hmcmt_ctx* ctx, const hmcmt_adapt_lowrank_options* o) {
+    const char* fn = "hmcmt_chain_adapt_lowrank";
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_adapt_ready(ctx, fn);
+    if (rc) return rc;
+    if (!o) { ctx->err = std::string(fn) + ": options is NULL"; return HMCMT_EINVAL; }
+    auto& A = ctx->chain.adapt;
+    auto& M = ctx->mass;
+    if (!A.active || !A.opt.adapt_mass) { ctx->err = std::string(fn) + ": needs a running adaptation begun with adapt_mass = 1"; return HMCMT_EINVAL; }
+    if (A.c != 0) { ctx->err = std::string(fn) + ": the adaptation has counted a step (call it right behind hmcmt_chain_adapt_begin)"; return HMCMT_EINVAL; }
+    if (A.lr.on) { ctx->err = std::string(fn) + ": the adaptation is upgraded already"; return HMCMT_EINVAL; }
+    if (o->rank < 1 || o->rank > HMCMT_MASS_RANK_MAX || o->max_samples < ADAPT_LR_NMIN || o->max_samples > ADAPT_LR_NMAX ||
+        !std::isfinite(o->cutoff) || !(o->cutoff > 1.0) || !std::isfinite(o->gamma) || !(o->gamma > 0.0)) {
+        ctx->err = std::string(fn) + ": need 1 <= rank <= HMCMT_MASS_RANK_MAX, 4 <= max_samples <= 128, a finite cutoff > 1 and a finite gamma > 0";
+        return HMCMT_EINVAL;
+    }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    const size_t nAC = (size_t)ctx->v.nAC, ms = (size_t)o->max_samples, rk = (size_t)o->rank, D = sizeof(double);
+    decltype(A.lr) L{};
+    std::vector<void*> own;                                  // handed to the adaptation's allocs only when everything is there
+    const std::vector<std::pair<double**, size_t>> bufs = {
+        {&L.d_X, ms * nAC * D}, {&L.d_G, ms * nAC * D}, {&L.d_K, 4 * ms * ms * D}, {&L.d_B, 2 * ms * rk * D}, {&L.d_meanX, nAC * D},
+        {&L.d_meanG, nAC * D}, {&L.d_s, nAC * D}, {&L.d_U, rk * nAC * D}, {&L.d_c, 2 * rk * D}, {&L.d_part, rk * LFNB * D}};
+    for (const auto& b : bufs)
+        if ((rc = chain_acc_zeroed(ctx, fn, own, (void**)b.first, b.second))) break;
+    // the mass's own buffers for `rank` directions (the kind is HMCMT_MASS_DIAGONAL here: adapt_mass = 1 was accepted, so none are held)
+    double *d_s = nullptr, *d_U = nullptr, *d_c = nullptr, *d_part = nullptr;
+    if (!rc && (rc = mass_lr_alloc(ctx, o->rank, &d_s, &d_U, &d_c, &d_part))) {
+        (void)hipGetLastError();
+        mass_lr_free(ctx, {d_s, d_U, d_c, d_part});
+        ctx->err = std::string(fn) + ": device allocation failed";
+        rc = HMCMT_ENOMEM;
+    }
+    if (rc) {                                                // (the diagonal adaptation goes on as it was)
+        const std::string e = ctx->err;
+        (void)hipStreamSynchronize(ctx->stream);
+        chain_acc_free(own);
+        ctx->err = e;
+        return rc;
+    }
+    mass_lr_release(ctx);
+    M.d_lrS = d_s; M.d_lrU = d_U; M.d_lrC = d_c; M.d_lrPart = d_part;
+    M.lrRank = 0; M.lrCap = o->rank;
+    A.allocs.insert(A.allocs.end(), own.begin(), own.end());
+    L.on = true;
+    L.opt = *o;
+    L.winStart = A.opt.init_buffer;
+    L.stride = item_adapt_lr_stride(A.wnext - A.opt.init_buffer + 1, o->max_samples);
+    A.lr = std::move(L);
+    return 0;
+}
+
+int hmcmt_chain_adapt_lowrank_info(hmcmt_ctx* ctx, hmcmt_adapt_lowrank_info* info) {
+    const char* fn = "hmcmt_chain_adapt_lowrank_info";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!info) { ctx->err = std::string(fn) + ": info is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_adapt_ready(ctx, fn);
+    if (rc) return rc;
+    if (!ctx->chain.adapt.lr.on) { ctx->err = std::string(fn) + ": the adaptation was not upgraded (hmcmt_chain_adapt_lowrank)"; return HMCMT_EINVAL; }
+    std::memset(info, 0, sizeof *info);
+    const hmcmt_adapt_lowrank_info& s = ctx->chain.adapt.lr.last;
+    info->windows = s.windows; info->stored = s.stored; info->skipped = s.skipped; info->dims = s.dims; info->rank = s.rank;
+    info->fallback = s.fallback; info->stride = s.stride;
+    info->theta_min = s.theta_min; info->theta_max = s.theta_max; info->defect = s.defect; info->host_ms = s.host_ms;
+    return 0;
+}
+
+int hmcmt_chain_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, const double* U, const double* lambda) {
+    const char* fn = "hmcmt_chain_set_mass_lowrank";
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    auto& C = ctx->chain;
+    auto& M = ctx->mass;
+    if (M.kind == HMCMT_MASS_WM) { ctx->err = std::string(fn) + ": the mass is HMCMT_MASS_WM (hmcmt_set_mass first; it ends the chain)"; return HMCMT_EINVAL; }
+    if (C.adapt.active && C.adapt.opt.adapt_mass) {
+        ctx->err = std::string(fn) + ": an adaptation of the mass is active (hmcmt_chain_adapt_end first)";
+        return HMCMT_EINVAL;
+    }
+    if (rank < 0 || rank > HMCMT_MASS_RANK_MAX) {
+        ctx->err = std::string(fn) + ": rank " + std::to_string(rank) + " is outside 0 .. HMCMT_MASS_RANK_MAX = " + std::to_string(HMCMT_MASS_RANK_MAX);
+        return HMCMT_EINVAL;
+    }
+    if (rank == 0 && !invM) { ctx->err = std::string(fn) + ": rank 0 needs invM"; return HMCMT_EINVAL; }
+    if (rank > 0 && (!U || !lambda)) { ctx->err = std::string(fn) + (!U ? ": U is NULL" : ": lambda is NULL"); return HMCMT_EINVAL; }
+    const int n = ctx->v.nAC;
+    std::vector<double> s((size_t)n), c((size_t)2 * rank);
+    for (int k = 0; k < rank; ++k) {
+        if (!std::isfinite(lambda[k]) || !(lambda[k] > 0.0)) { ctx->err = std::string(fn) + ": lambda[" + std::to_string(k) + "] is not finite and positive"; return HMCMT_EINVAL; }
+        c[k] = lambda[k] - 1.0;
+        c[rank + k] = 1.0 / std::sqrt(lambda[k]) - 1.0;
+    }
+    for (size_t i = 0; i < (size_t)rank * n; ++i)
+        if (!std::isfinite(U[i])) { ctx->err = std::string(fn) + ": U[" + std::to_string(i / n) + "][" + std::to_string(i % n) + "] is not finite"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (a commit may still be reading the mass buffers)
+    if (invM) std::copy(invM, invM + n, s.begin());
+    else if (M.kind == HMCMT_MASS_LOWRANK && !M.lrInvM.empty()) s = M.lrInvM;     // (the scales hmcmt_set_mass_lowrank was given: in force, not in d_invM)
+    else HIPCHK(hipMemcpy(s.data(), ctx->d_invM, sizeof(double) * n, hipMemcpyDeviceToHost));   // (the diagonal in force)
+    for (int a = 0; a < n; ++a)
+        if (!std::isfinite(s[a]) || !(s[a] > 0.0)) { ctx->err = std::string(fn) + ": invM[" + std::to_string(a) + "] is not finite and positive"; return HMCMT_EINVAL; }
+    if (rank == 0) {
+        HIPCHK(hipMemcpy(ctx->d_invM, s.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        mass_lr_release(ctx);
+        M.kind = HMCMT_MASS_DIAGONAL;
+        C.haveMomentum = false;
+        return 0;
+    }
+    const std::vector<double> diag = s;
+    for (int a = 0; a < n; ++a) s[a] = std::sqrt(s[a]);
+    double *d_s = nullptr, *d_U = nullptr, *d_c = nullptr, *d_part = nullptr, defect = 0.0;
+    rc = mass_lr_build(ctx, rank, s, U, c, &d_s, &d_U, &d_c, &d_part, &defect);
+    if (rc || !(defect <= 1e-8)) {                           // (nothing has changed: the mass and the chain stay)
+        const std::string e = ctx->err;
+        mass_lr_free(ctx, {d_s, d_U, d_c, d_part});
+        if (rc) { ctx->err = e; return rc; }
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%.3e", defect);
+        ctx->err = std::string(fn) + ": the rows of U are not orthonormal (max |U'U - I| = " + buf + " > 1e-8)";
+        return HMCMT_EINVAL;
+    }
+    HIPCHK(hipMemcpy(ctx->d_invM, diag.data(), sizeof(double) * n, hipMemcpyHostToDevice));   // (hmcmt_chain_mass_diag stays truthful)
+    mass_lr_release(ctx);
+    M.d_lrS = d_s; M.d_lrU = d_U; M.d_lrC = d_c; M.d_lrPart = d_part;
+    M.lrRank = M.lrCap = rank;
+    M.lrLambda.assign(lambda, lambda + rank);
+    M.kind = HMCMT_MASS_LOWRANK;
+    C.haveMomentum = false;                                  // (its K0 belongs to the old mass)
+    return 0;
+}
+
+int hmcmt_chain_mass_lowrank(hmcmt_ctx* ctx, int32_t* rank, double* invM, double* U, double* lambda, int32_t on_device) {
+    const char* fn = "hmcmt_chain_mass_lowrank";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!rank) { ctx->err = std::string(fn) + ": rank is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    auto& M = ctx->mass;
+    if (M.kind == HMCMT_MASS_WM) { ctx->err = std::string(fn) + ": the mass is HMCMT_MASS_WM"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    hipStream_t st = ctx->stream;
+    const int n = ctx->v.nAC, r = M.kind == HMCMT_MASS_LOWRANK ? M.lrRank : 0;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    *rank = r;
+    if (invM && r > 0 && !M.lrInvM.empty()) HIPCHK(hipMemcpyAsync(invM, M.lrInvM.data(), sizeof(double) * n, on_device ? hipMemcpyHostToDevice : hipMemcpyHostToHost, st));
+    else if (invM) HIPCHK(hipMemcpyAsync(invM, ctx->d_invM, sizeof(double) * n, kind, st));
+    if (r > 0 && U) HIPCHK(hipMemcpyAsync(U, M.d_lrU, sizeof(double) * (size_t)r * n, kind, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (r > 0 && lambda) {                                   // (the bits that were given or estimated, not 1 + the stored lambda - 1)
+        if (on_device) HIPCHK(hipMemcpy(lambda, M.lrLambda.data(), sizeof(double) * r, hipMemcpyHostToDevice));
+        else std::copy(M.lrLambda.begin(), M.lrLambda.begin() + r, lambda);
+    }
+    return 0;
+}
+
+int hmcmt_debug_adapt_lowrank(hmcmt_ctx* ctx, int32_t n, const double* X, const double* G, const double* invM, double* K_out,
+                              const double* B, int32_t r, double* U_out) {
+    const char* fn = "hmcmt_debug_adapt_lowrank";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!ctx->havePrior) { ctx->err = std::string(fn) + ": hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
+    if (!X || !G || !invM || !K_out || n < ADAPT_LR_NMIN || n > ADAPT_LR_NMAX || r < 0 || r > HMCMT_MASS_RANK_MAX || (B && r > 0 && !U_out)) {
+        ctx->err = std::string(fn) + ": need X, G, invM, K_out, 4 <= n <= 128, 0 <= r <= HMCMT_MASS_RANK_MAX and U_out with B";
+        return HMCMT_EINVAL;
+    }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    hipStream_t st = ctx->stream;
+    const size_t nAC = (size_t)ctx->v.nAC, N2 = (size_t)2 * n, D = sizeof(double);
+    const bool lift = B && r > 0;
+    std::vector<void*> own;
+    double *d_X = nullptr, *d_G = nullptr, *d_invM = nullptr, *d_mx = nullptr, *d_mg = nullptr, *d_s = nullptr, *d_K = nullptr, *d_B = nullptr, *d_U = nullptr;
+    int rc = 0;
+    for (const auto& b : std::vector<std::pair<double**, size_t>>{{&d_X, n * nAC * D}, {&d_G, n * nAC * D}, {&d_invM, nAC * D}, {&d_mx, nAC * D},
+                                                                   {&d_mg, nAC * D}, {&d_s, nAC * D}, {&d_K, N2 * N2 * D},
+                                                                   {&d_B, std::max<size_t>(N2 * r, 1) * D}, {&d_U, std::max<size_t>(r * nAC, 1) * D}})
+        if ((rc = chain_acc_zeroed(ctx, fn, own, (void**)b.first, b.second))) break;
+    auto run = [&]() -> int {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(d_X, X, n * nAC * D, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_G, G, n * nAC * D, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_invM, invM, nAC * D, hipMemcpyHostToDevice));
+        if (lift) HIPCHK(hipMemcpy(d_B, B, N2 * r * D, hipMemcpyHostToDevice));
+        const AdaptLr w = chain_adapt_lr_gram(st, (int)nAC, n, d_X, d_G, d_invM, d_mx, d_mg, d_s, d_K);
+        if (lift) chain_adapt_lr_lift(st, w, d_B, r, d_U);
+        HIPCHK(hipMemcpyAsync(K_out, d_K, N2 * N2 * D, hipMemcpyDeviceToHost, st));
+        if (lift) HIPCHK(hipMemcpyAsync(U_out, d_U, r * nAC * D, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    if (!rc) rc = run();
+    const std::string e = ctx->err;
+    (void)hipStreamSynchronize(st);
+    chain_acc_free(own);
+    ctx->err = e;
+    return rc;
+}
+
+int hmcmt_debug_adapt_lowrank_time(hmcmt_ctx* ctx, double* out) {
+    const char* fn = "hmcmt_debug_adapt_lowrank_time";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!out) { ctx->err = std::string(fn) + ": out is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_adapt_ready(ctx, fn);
+    if (rc) return rc;
+    const auto& L = ctx->chain.adapt.lr;
+    if (!L.on) { ctx->err = std::string(fn) + ": the adaptation was not upgraded (hmcmt_chain_adapt_lowrank)"; return HMCMT_EINVAL; }
+    for (int i = 0; i < 4; ++i) out[i] = L.times[i];
+    return 0;
+}
+
+int hmcmt_debug_adapt_lowrank_rows(hmcmt_ctx* ctx, int32_t* n, double* X, double* G) {
+    const char* fn = "hmcmt_debug_adapt_lowrank_rows";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!n) { ctx->err = std::string(fn) + ": n is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_adapt_ready(ctx, fn);
+    if (rc) return rc;
+    const auto& L = ctx->chain.adapt.lr;
+    if (!L.on) { ctx->err = std::string(fn) + ": the adaptation was not upgraded (hmcmt_chain_adapt_lowrank)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    const int rows = L.stored > 0 ? L.stored : L.closedStored;   // (an empty open window: the closed one's rows are still there)
+    const size_t bytes = sizeof(double) * (size_t)rows * ctx->v.nAC;
+    *n = rows;
+    if (X && bytes) HIPCHK(hipMemcpyAsync(X, L.d_X, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (G && bytes) HIPCHK(hipMemcpyAsync(G, L.d_G, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

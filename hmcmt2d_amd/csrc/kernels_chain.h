@@ -178,3 +178,107 @@ __global__ __launch_bounds__(256) void k_chain_corr(long long n, long long nrow,
     if (a >= n) return;
     for (long long r = blockIdx.y; r < nrow; r += gridDim.y) item_chain_corr(tot, q, S, row, n, dN, r, a, corr);
 }
+
+// ---- low-rank mass in the warm-up (hmcmt_chain_adapt_lowrank; arithmetic and its order in hmcmt_items.h: item_adapt_lr_*) ----------
+// Per stored step one launch of nAC threads (k_adapt_lr_store); per window end k_adapt_lr_mean, k_adapt_lr_gram, one download of K,
+// then k_adapt_lr_lift and k_adapt_lr_sign.  The Gram matrix is plain fp64 fma, not v_mfma_f64_16x16x4_f64: the matrix instruction
+// adds its four products per step in an order of its own, which the host instantiation (and the numpy reference, bit for bit) would
+// have to mirror, for a kernel that runs once per window -- the MFMA form was not built, so there is no measurement of it.
+struct AdaptLr {
+    int nAC, n;                          // cells, stored pairs (W has 2n rows)
+    double sq;                           // sqrt(n - 1)
+    const double *X, *G;                 // [n][nAC] the stores
+    const double *meanX, *meanG, *s;     // [nAC]
+};
+// row `slot` of both stores from the chain's current model and the data gradient the decision left: one thread per cell writes both
+__global__ __launch_bounds__(256) void k_adapt_lr_store(LfView L, const double* __restrict__ gdata, double lambda, double* __restrict__ xrow,
+                                                        double* __restrict__ grow) {
+    const int a = TID1;
+    if (a >= L.n) return;
+    xrow[a] = L.m[a];
+    grow[a] = item_adapt_lr_grad(gdata, lambda, L.wmRow, L.wmCol, L.wmVal, L.m, L.mref, a);
+}
+// the stored rows' means and s = sqrt(invM), one thread per cell
+__global__ __launch_bounds__(256) void k_adapt_lr_mean(int nAC, int n, const double* __restrict__ X, const double* __restrict__ G,
+                                                       const double* __restrict__ invM, double* __restrict__ meanX, double* __restrict__ meanG,
+                                                       double* __restrict__ s) {
+    const int a = TID1;
+    if (a >= nAC) return;
+    meanX[a] = item_adapt_lr_mean(X, nAC, n, a);
+    meanG[a] = item_adapt_lr_mean(G, nAC, n, a);
+    s[a] = sqrt(invM[a]);
+}
+// K = W W': workgroup b owns the ADAPT_LR_TILE x ADAPT_LR_TILE tile (bi, bj), bi <= bj, of the upper block triangle and writes its mirror;
+// thread (ti, tj) owns K[i][j] and walks ALL cells upwards, ADAPT_LR_STRIP at a time: the two row blocks of W are formed on the fly
+// (centred, scaled) into LDS, consecutive threads walking the cells of a row
+__global__ __launch_bounds__(256) void k_adapt_lr_gram(AdaptLr w, double* __restrict__ K) {
+    __shared__ double Ws[2][ADAPT_LR_TILE][ADAPT_LR_STRIP + 1];
+    const int N2 = 2 * w.n, T = (N2 + ADAPT_LR_TILE - 1) / ADAPT_LR_TILE;
+    int t = blockIdx.x, bi = 0;
+    while (t >= T - bi) { t -= T - bi; ++bi; }
+    const int bj = bi + t;
+    const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
+    double acc = 0.0;
+    for (int a0 = 0; a0 < w.nAC; a0 += ADAPT_LR_STRIP) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 2 * ADAPT_LR_TILE * ADAPT_LR_STRIP / 256; ++q) {
+            const int e = threadIdx.x + 256 * q;
+            const int blk = e / (ADAPT_LR_TILE * ADAPT_LR_STRIP), row = (e / ADAPT_LR_STRIP) % ADAPT_LR_TILE, col = e % ADAPT_LR_STRIP;
+            const int gi = (blk ? bj : bi) * ADAPT_LR_TILE + row, a = a0 + col;
+            Ws[blk][row][col] = (gi < N2 && a < w.nAC) ? item_adapt_lr_w(w.X, w.G, w.meanX, w.meanG, w.s, w.nAC, w.n, w.sq, gi, a) : 0.0;
+        }
+        __syncthreads();
+        const int lim = min(ADAPT_LR_STRIP, w.nAC - a0);
+        for (int c = 0; c < lim; ++c) acc = item_adapt_lr_dot(Ws[0][ti][c], Ws[1][tj][c], acc);
+    }
+    const int i = bi * ADAPT_LR_TILE + ti, j = bj * ADAPT_LR_TILE + tj;
+    if (i < N2 && j < N2) {
+        K[(long long)i * N2 + j] = acc;
+        if (bi != bj) K[(long long)j * N2 + i] = acc;       // (the diagonal tile's mirror entry has its own thread: the same products, the same bits)
+    }
+}
+// U[k][a] = sum_i B[i][k] W[i][a]: one thread per cell, MASS_LR_CHUNK directions side by side (W[i][a] is formed once per chunk and row)
+__global__ __launch_bounds__(256) void k_adapt_lr_lift(AdaptLr w, const double* __restrict__ B, int r, double* __restrict__ U) {
+    const int a = TID1;
+    if (a >= w.nAC) return;
+    for (int k0 = 0; k0 < r; k0 += MASS_LR_CHUNK) {
+        double acc[MASS_LR_CHUNK];
+#pragma unroll
+        for (int q = 0; q < MASS_LR_CHUNK; ++q) acc[q] = 0.0;
+        for (int i = 0; i < 2 * w.n; ++i) {
+            const double wi = item_adapt_lr_w(w.X, w.G, w.meanX, w.meanG, w.s, w.nAC, w.n, w.sq, i, a);
+#pragma unroll
+            for (int q = 0; q < MASS_LR_CHUNK; ++q)
+                if (k0 + q < r) acc[q] = item_adapt_lr_dot(B[(long long)i * r + k0 + q], wi, acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < MASS_LR_CHUNK; ++q)
+            if (k0 + q < r) U[(long long)(k0 + q) * w.nAC + a] = acc[q];
+    }
+}
+// the sign convention: workgroup k finds direction k's entry of largest magnitude (the lowest index among equals) and flips the
+// direction where that entry is negative
+__global__ __launch_bounds__(256) void k_adapt_lr_sign(int nAC, double* __restrict__ U) {
+    __shared__ double shV[256];
+    __shared__ long long shA[256];
+    double* u = U + (long long)blockIdx.x * nAC;
+    double best = -1.0;
+    long long at = nAC;
+    for (int a = threadIdx.x; a < nAC; a += 256) {
+        const double v = fabs(u[a]);
+        if (item_adapt_lr_beats(v, a, best, at)) { best = v; at = a; }
+    }
+    shV[threadIdx.x] = best; shA[threadIdx.x] = at;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o && item_adapt_lr_beats(shV[threadIdx.x + o], shA[threadIdx.x + o], shV[threadIdx.x], shA[threadIdx.x])) {
+            shV[threadIdx.x] = shV[threadIdx.x + o]; shA[threadIdx.x] = shA[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    const long long top = shA[0];
+    if (top >= nAC || !(u[top] < 0.0)) return;
+    __syncthreads();                                         // (every thread has read u[top] before its owner flips it)
+    for (int a = threadIdx.x; a < nAC; a += 256) u[a] = -u[a];
+}

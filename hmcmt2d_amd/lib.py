@@ -98,6 +98,18 @@ class AdaptInfo(C.Structure):
                 ("s_bar", C.c_double), ("alpha_last", C.c_double), ("alpha_sum", C.c_double)]
 
 
+class AdaptLowrankOptions(C.Structure):
+    """hmcmt_adapt_lowrank_options (include/hmcmt.h): the low-rank upgrade of a warm-up (hmcmt_chain_adapt_lowrank)."""
+    _fields_ = [("rank", C.c_int32), ("max_samples", C.c_int32), ("cutoff", C.c_double), ("gamma", C.c_double)]
+
+
+class AdaptLowrankInfo(C.Structure):
+    """hmcmt_adapt_lowrank_info (include/hmcmt.h): the last closed window of an upgraded warm-up."""
+    _fields_ = [("windows", C.c_int32), ("stored", C.c_int32), ("skipped", C.c_int32), ("dims", C.c_int32), ("rank", C.c_int32),
+                ("fallback", C.c_int32), ("stride", C.c_int64), ("theta_min", C.c_double), ("theta_max", C.c_double),
+                ("defect", C.c_double), ("host_ms", C.c_double)]
+
+
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU."""
     newest = max(os.path.getmtime(f) for f in SOURCES + HEADERS)
@@ -197,6 +209,18 @@ def load_library():
     lib.hmcmt_chain_adapt_begin.argtypes = [vp, C.POINTER(AdaptOptions)]
     lib.hmcmt_chain_adapt_info.argtypes = [vp, C.POINTER(AdaptInfo)]
     lib.hmcmt_chain_adapt_end.argtypes = [vp]
+    lib.hmcmt_default_adapt_lowrank_options.argtypes = [C.POINTER(AdaptLowrankOptions)]
+    lib.hmcmt_default_adapt_lowrank_options.restype = None
+    lib.hmcmt_chain_adapt_lowrank.argtypes = [vp, C.POINTER(AdaptLowrankOptions)]
+    lib.hmcmt_chain_adapt_lowrank_info.argtypes = [vp, C.POINTER(AdaptLowrankInfo)]
+    lib.hmcmt_chain_set_mass_lowrank.argtypes = [vp, c_double_p, C.c_int32, c_double_p, c_double_p]
+    lib.hmcmt_chain_mass_lowrank.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, vp, C.c_int32]
+    lib.hmcmt_debug_adapt_lowrank.argtypes = [vp, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32, c_double_p]
+    lib.hmcmt_debug_adapt_lowrank_rows.argtypes = [vp, C.POINTER(C.c_int32), c_double_p, c_double_p]
+    lib.hmcmt_debug_adapt_lowrank_time.argtypes = [vp, c_double_p]
+    for name in ("hmcmt_chain_adapt_lowrank", "hmcmt_chain_adapt_lowrank_info", "hmcmt_chain_set_mass_lowrank", "hmcmt_chain_mass_lowrank",
+                 "hmcmt_debug_adapt_lowrank", "hmcmt_debug_adapt_lowrank_rows", "hmcmt_debug_adapt_lowrank_time"):
+        getattr(lib, name).restype = C.c_int
     lib.hmcmt_chain_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.hmcmt_chain_momentum.argtypes = [vp, c_double_p, C.POINTER(C.c_double)]
@@ -277,6 +301,9 @@ COV_BATCH_MAX = 16    # include/hmcmt.h: HMCMT_COV_BATCH_MAX
 # ... and the warm-up: the chain's step size and diagonal mass between two steps, and their adaptation
 CHAIN_ADAPT_SYMBOLS = ["hmcmt_chain_set_dt", "hmcmt_chain_set_mass_diag", "hmcmt_chain_mass_diag", "hmcmt_default_adapt_options",
                        "hmcmt_chain_adapt_begin", "hmcmt_chain_adapt_info", "hmcmt_chain_adapt_end"]
+# ... and its low-rank upgrade: directions and factors from the window's draws and gradients, the setter and the read-out of a live chain
+CHAIN_ADAPT_LOWRANK_SYMBOLS = ["hmcmt_default_adapt_lowrank_options", "hmcmt_chain_adapt_lowrank", "hmcmt_chain_adapt_lowrank_info",
+                               "hmcmt_chain_set_mass_lowrank", "hmcmt_chain_mass_lowrank"]
 # ... and the chain's own random numbers: Philox4x32-10 by counter, one call and one wait per sample, one call per run
 CHAIN_RNG_SYMBOLS = ["hmcmt_rng_draw", "hmcmt_rng_normals", "hmcmt_chain_seed", "hmcmt_chain_rng_state", "hmcmt_chain_rng_seek",
                      "hmcmt_chain_normals", "hmcmt_chain_sample", "hmcmt_chain_run"]
@@ -284,9 +311,11 @@ CHAIN_RNG_SYMBOLS = ["hmcmt_rng_draw", "hmcmt_rng_normals", "hmcmt_chain_seed", 
 CHAIN_NUTS_SYMBOLS = ["hmcmt_chain_nuts_sample", "hmcmt_chain_nuts_run", "hmcmt_rng_nuts"]
 NUTS_DEPTH_MAX = 10   # include/hmcmt.h: HMCMT_NUTS_DEPTH_MAX
 NUTS_CK_MAX, NUTS_SUMS = 9, 21   # include/hmcmt_debug.h: HMCMT_NUTS_CK_MAX, HMCMT_NUTS_SUMS
+ADAPT_LOWRANK_KEYS = ("rank", "max_samples", "cutoff", "gamma")
+ADAPT_LOWRANK_NMIN, ADAPT_LOWRANK_NMAX = 4, 128   # include/hmcmt.h: max_samples of hmcmt_adapt_lowrank_options
 ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -298,7 +327,8 @@ DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "
                  "hmcmt_debug_back_post", "hmcmt_debug_persist_precond", "hmcmt_persist_info", "hmcmt_debug_hog", "hmcmt_persist_envelope",
                  "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time",
                  "hmcmt_debug_chain_cov_time", "hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess", "hmcmt_debug_nuts_leaf",
-                 "hmcmt_debug_nuts_iters"]
+                 "hmcmt_debug_nuts_iters", "hmcmt_debug_adapt_lowrank", "hmcmt_debug_adapt_lowrank_rows",
+                 "hmcmt_debug_adapt_lowrank_time"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -346,6 +376,27 @@ def rng_normals(seed, stream, t, n, a0=0):
     if rc != 0:
         raise HmcmtError(rc, "hmcmt_rng_normals: need a0 >= 0, n >= 0 and a0 + n <= 2^31")
     return z
+
+
+def adapt_lowrank_options(options):
+    """hmcmt_adapt_lowrank_options from a dict (or True / None: the defaults); ValueError for an unknown key or a value out of range --
+    checked here so that a wrong request is refused before a context exists (the library checks the same)."""
+    options = {} if options is None or options is True else dict(options)
+    unknown = sorted(set(options) - set(ADAPT_LOWRANK_KEYS))
+    if unknown:
+        raise ValueError(f"adapt lowrank: unknown option(s) {unknown}; known: {list(ADAPT_LOWRANK_KEYS)}")
+    o = AdaptLowrankOptions(rank=8, max_samples=64, cutoff=2.0, gamma=1e-5)
+    for k, v in options.items():
+        setattr(o, k, type(getattr(o, k))(v))
+    if not 1 <= o.rank <= HMCMT_MASS_RANK_MAX:
+        raise ValueError(f"adapt lowrank: rank {o.rank} is outside 1 .. {HMCMT_MASS_RANK_MAX}")
+    if not ADAPT_LOWRANK_NMIN <= o.max_samples <= ADAPT_LOWRANK_NMAX:
+        raise ValueError(f"adapt lowrank: max_samples {o.max_samples} is outside {ADAPT_LOWRANK_NMIN} .. {ADAPT_LOWRANK_NMAX}")
+    if not (np.isfinite(o.cutoff) and o.cutoff > 1.0):
+        raise ValueError(f"adapt lowrank: cutoff {o.cutoff} must be finite and > 1")
+    if not (np.isfinite(o.gamma) and o.gamma > 0.0):
+        raise ValueError(f"adapt lowrank: gamma {o.gamma} must be finite and > 0")
+    return o
 
 
 def lowrank_mass_arrays(nAC, invM, U, lam):
@@ -1158,6 +1209,74 @@ class HipContext:
     def chain_adapt_end(self):
         """Stops a warm-up now: dt = exp(x_bar) as at its regular end."""
         self._check(self.lib.hmcmt_chain_adapt_end(self.h))
+
+    # -- the low-rank mass of a live chain: the warm-up's upgrade, the between-steps setter, the read-out --
+    def chain_adapt_lowrank(self, **options):
+        """Upgrades the warm-up just begun with adapt_mass (chain_adapt_begin, no step counted yet): every window end also estimates
+        the directions U and factors lambda of the low-rank mass from the window's draws and gradients (hmcmt_chain_adapt_lowrank).
+        options: rank (8), max_samples (64), cutoff (2), gamma (1e-5)."""
+        o = adapt_lowrank_options(options)
+        self._check(self.lib.hmcmt_chain_adapt_lowrank(self.h, C.byref(o)))
+        self._adapt_lowrank_max = int(o.max_samples)
+
+    def chain_adapt_lowrank_info(self):
+        """The last closed window of the upgraded warm-up (hmcmt_adapt_lowrank_info as a dict): windows, stored, skipped, dims, rank,
+        fallback, stride, theta_min, theta_max, defect, host_ms."""
+        info = AdaptLowrankInfo()
+        self._check(self.lib.hmcmt_chain_adapt_lowrank_info(self.h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in AdaptLowrankInfo._fields_}
+
+    def chain_set_mass_lowrank(self, invM, U=None, lam=None):
+        """hmcmt_chain_set_mass_lowrank: the low-rank mass between two steps of a live chain (set_mass_lowrank's arguments; the chain
+        and its accumulators go on, a momentum already drawn is dropped).  U None or of rank 0 with invM: back to the plain diagonal."""
+        if U is None or np.asarray(U).size == 0:
+            if invM is None:
+                raise ValueError("chain_set_mass_lowrank: rank 0 needs invM")
+            self._check(self.lib.hmcmt_chain_set_mass_lowrank(self.h, _dp(self._model(invM)), 0, None, None))
+            return
+        invM, U, lam = lowrank_mass_arrays(self.nAC, invM, U, lam)
+        self._check(self.lib.hmcmt_chain_set_mass_lowrank(self.h, None if invM is None else _dp(invM), int(U.shape[0]), _dp(U), _dp(lam)))
+
+    def chain_mass_lowrank(self):
+        """The mass in force (hmcmt_chain_mass_lowrank): (invM [nAC], U [rank, nAC], lam [rank]); rank 0 under the diagonal mass."""
+        rank = C.c_int32(0)
+        invM, U, lam = np.empty(self.nAC), np.empty((HMCMT_MASS_RANK_MAX, self.nAC)), np.empty(HMCMT_MASS_RANK_MAX)
+        self._check(self.lib.hmcmt_chain_mass_lowrank(self.h, C.byref(rank), invM.ctypes.data, U.ctypes.data, lam.ctypes.data, 0))
+        r = int(rank.value)
+        return invM, U[:r].copy(), lam[:r].copy()
+
+    def debug_adapt_lowrank(self, X, G, invM, B=None):
+        """Test hook (hmcmt_debug_adapt_lowrank): K = W W' of the rows X, G [n, nAC] under invM, and with B [2n, r] also U = B' W with
+        the sign convention -- the window end's kernels without a chain.  Returns (K, U or None)."""
+        X, G = np.ascontiguousarray(X, dtype=np.float64), np.ascontiguousarray(G, dtype=np.float64)
+        n = X.shape[0]
+        if X.ndim != 2 or X.shape != G.shape or X.shape[1] != self.nAC:
+            raise ValueError(f"X and G must be [n, nAC = {self.nAC}]; got {X.shape}, {G.shape}")
+        K = np.empty((2 * n, 2 * n))
+        U, r = None, 0
+        if B is not None:
+            B = np.ascontiguousarray(B, dtype=np.float64)
+            if B.ndim != 2 or B.shape[0] != 2 * n:
+                raise ValueError(f"B must be [2n = {2 * n}, r]; got {B.shape}")
+            r = B.shape[1]
+            U = np.empty((r, self.nAC))
+        self._check(self.lib.hmcmt_debug_adapt_lowrank(self.h, n, _dp(X), _dp(G), _dp(self._model(invM)), _dp(K), None if B is None else _dp(B),
+                                                       r, None if U is None else _dp(U)))
+        return K, U
+
+    def debug_adapt_lowrank_time(self):
+        """Measurement (hmcmt_debug_adapt_lowrank_time): the last window end's dict(gram_ms, lift_ms, wait_ms, check_ms)."""
+        out = np.zeros(4)
+        self._check(self.lib.hmcmt_debug_adapt_lowrank_time(self.h, _dp(out)))
+        return dict(zip(("gram_ms", "lift_ms", "wait_ms", "check_ms"), (float(v) for v in out)))
+
+    def debug_adapt_lowrank_rows(self):
+        """Test hook (hmcmt_debug_adapt_lowrank_rows): the open window's stored pairs (X [n, nAC], G [n, nAC])."""
+        cap = getattr(self, "_adapt_lowrank_max", ADAPT_LOWRANK_NMAX)
+        n = C.c_int32(0)
+        X, G = np.empty((cap, self.nAC)), np.empty((cap, self.nAC))
+        self._check(self.lib.hmcmt_debug_adapt_lowrank_rows(self.h, C.byref(n), _dp(X), _dp(G)))
+        return X[:n.value].copy(), G[:n.value].copy()
 
     # -- instrumentation ----------------------------------------------------------------------
     def profile(self, enable=True, every=1):

@@ -617,7 +617,7 @@ def mergeCov(list_of_cov):
             "corr": _corr_of(cov, var, r)}
 
 
-ADAPT_KEYS = ("nwarmup", "mass", "delta", "gamma", "t0", "kappa", "init_buffer", "term_buffer", "base_window", "dt_min", "dt_max")
+ADAPT_KEYS = ("nwarmup", "mass", "delta", "gamma", "t0", "kappa", "init_buffer", "term_buffer", "base_window", "dt_min", "dt_max", "lowrank")
 
 
 def lowRankMassFromSamples(samples, rank=8, cutoff=2.0, invM=None):
@@ -627,7 +627,9 @@ def lowRankMassFromSamples(samples, rank=8, cutoff=2.0, invM=None):
     rule (hmcmt_chain_adapt_begin, step 4): var N / (N + 5) + 1e-3 * 5 / (N + 5) with the unbiased sample variance.  The directions
     are the principal ones of the scaled, centred samples Z = (samples - mean) / s / sqrt(N - 1): the eigenpairs of the N x N matrix
     Z'Z lifted to U = Z v / sigma, lam = sigma^2 the variance along the direction in units of the scales.  At most `rank` pairs with
-    lam > cutoff are kept, largest first -- r may be 0; each direction's entry of largest magnitude is positive.  Needs no device."""
+    lam > cutoff are kept, largest first -- r may be 0; each direction's entry of largest magnitude is positive.  Needs no device.
+    With N << nparam the pure sampling noise of Z'Z has eigenvalues near nparam / N, far above a cutoff of 2, so the trailing
+    directions kept are noise; lowRankMassFromDrawsAndGrads, which also takes the gradients, does not have that floor."""
     X = np.asarray(samples, dtype=np.float64)
     if X.ndim != 2 or X.shape[1] < 2:
         raise ValueError("lowRankMassFromSamples: samples must be [nparam, N] with N >= 2")
@@ -650,6 +652,71 @@ def lowRankMassFromSamples(samples, rank=8, cutoff=2.0, invM=None):
         if U[k, np.argmax(np.abs(U[k]))] < 0:
             U[k] = -U[k]
     return s2, U, lam
+
+
+def lowRankMassFromDrawsAndGrads(samples, grads, invM=None, rank=8, cutoff=2.0, gamma=1e-5):
+    """(invM[nparam], U[r, nparam], lam[r]) of the low-rank-plus-diagonal mass from samples[nparam, N] AND the gradients of the potential
+    at them, grads[nparam, N] (columns = models, 4 <= N): the estimator the library's warm-up runs (hmcmt_chain_adapt_lowrank,
+    include/hmcmt.h), in numpy.  With W = [Zd; Zg] the centred draws over s and the centred gradients times s, both over sqrt(N - 1),
+    it finds in the span of W the symmetric positive definite Sigma with Sigma cov(grad) Sigma = cov(draws) -- for a Gaussian the
+    covariance itself, whatever N -- and keeps at most `rank` of its eigenpairs with theta > cutoff or theta < 1 / cutoff, by
+    |ln theta| descending.  gamma > 0 is added to both projected covariances.  The scales are `invM` where given, else the window rule
+    of lowRankMassFromSamples.  r may be 0; each direction's entry of largest magnitude is positive.  Needs no device.  With
+    numpy.linalg.eigh on the graded matrices involved, theta carries about six digits at the default gamma (the library's Jacobi
+    eigensolver nine): ample for a mass matrix, not for comparing bits."""
+    X, Gr = np.asarray(samples, dtype=np.float64), np.asarray(grads, dtype=np.float64)
+    if X.ndim != 2 or X.shape != Gr.shape or X.shape[1] < 4:
+        raise ValueError("lowRankMassFromDrawsAndGrads: samples and grads must both be [nparam, N] with N >= 4")
+    if int(rank) < 0 or not cutoff > 1.0 or not gamma > 0.0:
+        raise ValueError("lowRankMassFromDrawsAndGrads: need rank >= 0, cutoff > 1 and gamma > 0")
+    nparam, N = X.shape
+    if invM is None:
+        s2 = X.var(axis=1, ddof=1) * (N / (N + 5.0)) + 1e-3 * 5.0 / (N + 5.0)
+    else:
+        s2 = np.array(invM, dtype=np.float64)
+        if s2.shape != (nparam,) or not (np.isfinite(s2).all() and (s2 > 0).all()):
+            raise ValueError(f"lowRankMassFromDrawsAndGrads: invM must hold {nparam} finite positive entries")
+    s = np.sqrt(s2)
+    W = np.vstack([((X - X.mean(axis=1)[:, None]) / s[:, None]).T, ((Gr - Gr.mean(axis=1)[:, None]) * s[:, None]).T]) / np.sqrt(N - 1.0)
+    K = W @ W.T
+    d, V = np.linalg.eigh(K)
+    keep = d > 1e-10 * d.max()
+    T = (V[:, keep] / np.sqrt(d[keep])).T
+    Pd, Pg = T @ K[:, :N], T @ K[:, N:]
+    m = T.shape[0]
+    Cd, Cg = Pd @ Pd.T + gamma * np.eye(m), Pg @ Pg.T + gamma * np.eye(m)
+    g, Q = np.linalg.eigh(Cg)                              # (in Cg's eigenbasis its powers are diagonal scalings)
+    sg = np.sqrt(g)
+    Cq = Q.T @ Cd @ Q
+    e, Z = np.linalg.eigh(sg[:, None] * (0.5 * (Cq + Cq.T)) * sg[None, :])
+    Sq = ((Z * np.sqrt(e)) @ Z.T) / sg[:, None] / sg[None, :]
+    theta, Yq = np.linalg.eigh(0.5 * (Sq + Sq.T))
+    order = np.argsort(-np.abs(np.log(theta)), kind="stable")
+    sel = [i for i in order if theta[i] > cutoff or theta[i] < 1.0 / cutoff][:int(rank)]
+    U = np.ascontiguousarray((W.T @ (T.T @ (Q @ Yq[:, sel]))).T)
+    for k in range(len(sel)):
+        if U[k, np.argmax(np.abs(U[k]))] < 0:
+            U[k] = -U[k]
+    return s2, U, theta[sel]
+
+
+def adaptLowrankPlan(adapt, hmcprior):
+    """The options of HipContext.chain_adapt_lowrank of runHMCSampler's adapt={"lowrank": ...} as a dict, or None where the key is
+    absent, None or False; needs no device.  True means the defaults.  ValueError unless the warm-up adapts the diagonal mass
+    (massType "diagonal" and mass=True, which adaptPlan may have turned off for a short warm-up), and for a value out of range."""
+    from .lib import ADAPT_LOWRANK_KEYS, adapt_lowrank_options
+    lowrank = adapt.get("lowrank")
+    if lowrank is None or lowrank is False:
+        return None
+    if lowrank is not True and not isinstance(lowrank, dict):
+        raise ValueError("runHMCSampler: adapt lowrank must be True or a dict with the keys rank, max_samples, cutoff, gamma")
+    if hmcprior.massType != "diagonal":
+        raise ValueError(f"runHMCSampler: adapt lowrank needs massType \"diagonal\", not {hmcprior.massType!r}")
+    _, opts = adaptPlan(adapt, hmcprior)
+    if not opts["adapt_mass"]:
+        raise ValueError("runHMCSampler: adapt lowrank needs mass=True (and a warm-up of at least 20 steps): it upgrades the adaptation of the diagonal mass")
+    o = adapt_lowrank_options(lowrank)
+    return {k: getattr(o, k) for k in ADAPT_LOWRANK_KEYS}
 
 
 def adaptPlan(adapt, hmcprior):
@@ -795,17 +862,24 @@ class _WarmUp(ChainOutput):
     (hmcmt_chain_adapt_begin, include/hmcmt.h).  Further keys, all optional: gamma, t0, kappa, init_buffer, term_buffer, base_window,
     dt_min, dt_max; see adaptPlan for the window defaults.  hmcprior.dt is the start and is not modified.  hmcstats.adapt is a dict:
     nwarmup, dt[nsamples] (the step size each sample's trajectory used), alpha[nsamples], dt_final, invM (the final diagonal, None
-    without mass) and windows, a list of (end_step, n)."""
+    without mass) and windows, a list of (end_step, n).  `lowrank` (True, or a dict with rank, max_samples, cutoff, gamma; needs mass):
+    every window end also estimates the directions and factors of the low-rank mass from the window's draws and gradients
+    (hmcmt_chain_adapt_lowrank, include/hmcmt.h; no pilot run, no sample history); hmcstats.adapt["lowrank"] then holds the final
+    invM, U[r, nparam], lam[r] and `windows`, the hmcmt_adapt_lowrank_info of every closed window as a dict."""
     name, field, keys, why = "adapt", "adapt", ADAPT_KEYS, "the warm-up runs in the device chain"
 
     def check(self, value, hmcprior):
         adaptPlan(value, hmcprior)
+        adaptLowrankPlan(value, hmcprior)
 
     def begin(self, ctx, value, env):                       # (the warm-up: hmcprior.dt is its start and stays as it is)
         nwarmup, opts = adaptPlan(value, env.hmcprior)
+        lowrank = adaptLowrankPlan(value, env.hmcprior)
         ctx.chain_adapt_begin(nwarmup, **opts)
+        if lowrank is not None:
+            ctx.chain_adapt_lowrank(**lowrank)
         return {"nwarmup": nwarmup, "mass": opts["adapt_mass"], "info": ctx.chain_adapt_info(), "dt": np.full(env.nsamples, np.nan),
-                "alpha": np.zeros(env.nsamples), "windows": []}
+                "alpha": np.zeros(env.nsamples), "windows": [], "lowrank": None if lowrank is None else []}
 
     def step(self, ctx, state, it, rec):
         before, state["info"] = state["info"], ctx.chain_adapt_info()
@@ -814,10 +888,18 @@ class _WarmUp(ChainOutput):
         state["alpha"][it - 1] = rec["alpha"] if "alpha" in rec else (1.0 if rec["hdif"] > 0 else float(np.exp(rec["hdif"])))
         if before["active"] and before["next_window_end"] == before["step"]:      # (this step was its window's last)
             state["windows"].append((it, before["window_count"] + 1))
+            if state["lowrank"] is not None:
+                row = ctx.chain_adapt_lowrank_info()
+                if row["windows"] > len(state["lowrank"]):                        # (a window of fewer than two samples closes nothing)
+                    state["lowrank"].append(row)
 
     def read(self, ctx, state, stats, env):
-        return {"nwarmup": state["nwarmup"], "dt": state["dt"], "alpha": state["alpha"], "dt_final": state["info"]["dt"],
-                "invM": ctx.chain_mass_diag() if state["mass"] else None, "windows": state["windows"]}
+        out = {"nwarmup": state["nwarmup"], "dt": state["dt"], "alpha": state["alpha"], "dt_final": state["info"]["dt"],
+               "invM": ctx.chain_mass_diag() if state["mass"] else None, "windows": state["windows"]}
+        if state["lowrank"] is not None:
+            invM, U, lam = ctx.chain_mass_lowrank()
+            out["lowrank"] = {"invM": invM, "U": U, "lam": lam, "windows": state["lowrank"]}
+        return out
 
 
 CHAIN_OUTPUTS = (_Histograms(), _DataMoments(), _EffectiveSampleSize(), _Covariance(), _WarmUp())

@@ -442,6 +442,75 @@ extern int hmcmt_chain_adapt_begin(hmcmt_ctx* ctx, const hmcmt_adapt_options* o)
 extern int hmcmt_chain_adapt_info(hmcmt_ctx* ctx, hmcmt_adapt_info* info);
 extern int hmcmt_chain_adapt_end(hmcmt_ctx* ctx);
 
+/* Low-rank mass in the warm-up: the directions U and factors Lambda of HMCMT_MASS_LOWRANK (above: M^-1 = S (I + U (Lambda - I) U') S)
+ * estimated inside the adaptation, from the window's draws AND the gradients the decisions leave on the device.  For a Gaussian the
+ * gradients are A^-1 (x - mu), and the symmetric positive definite Sigma with Sigma cov(grad) Sigma = cov(draws) is the covariance
+ * itself; the sampling noise of the two covariances, which at n << nAC swamps the eigenvalues of cov(draws) alone, cancels (the metric
+ * nutpie adapts with).
+ *   hmcmt_chain_adapt_lowrank   upgrades a running adaptation begun with adapt_mass = 1; called after hmcmt_chain_adapt_begin and before
+ *                         that adaptation's first counted step.  It allocates two row stores [max_samples][nAC] (draws, gradients), the
+ *                         Gram buffer [2 max_samples]^2, staging for s, U and the coefficients, and the mass's own low-rank buffers for
+ *                         `rank` directions: (2 max_samples + 2 rank + 7) nAC doubles.  HMCMT_EINVAL, with nothing changed: no such adaptation,
+ *                         one that has counted a step, a value out of range or not finite.  HMCMT_ENOMEM leaves the diagonal adaptation
+ *                         running as it was.
+ *                         Per counted step inside a window (2. above), behind the Welford kernel and with no wait: with L the window's
+ *                         length, known when it opens, stride = ceil(L / max_samples) (1 for L <= max_samples), and the window's i-th
+ *                         step stores a pair when i % stride == 0: the chain's current model and the full potential gradient there,
+ *                         g = g_data + regParam Wm (m - m_ref), g_data the data gradient the decision left on the device (the one the
+ *                         next step's start reuses; a NUTS sample's selected state's).  A rejection repeats a pair.  Were no valid
+ *                         gradient held, the pair would be skipped and counted, nothing evaluated for its sake; a decision always
+ *                         leaves one, also behind a foreign evaluation on the context (the step then evaluated its own start gradient).
+ *                         At a window's end (4. above), behind the kernel that writes invM, with n stored pairs, s = sqrt(invM) of
+ *                         that kernel, W = [Zd; Zg], Zd = (X - mean X) / s / sqrt(n - 1), Zg = (G - mean G) s / sqrt(n - 1), the means
+ *                         over the stored rows in row order:
+ *                           a. device: K = W W' ([2n][2n], fp64, every entry one fma chain over the cells upwards, no atomics)
+ *                           b. ONE WAIT and one download of K (at most 512 KB) -- once per window end, never per step
+ *                           c. host, double, cyclic Jacobi throughout: K = V D V', the m values D_i > 1e-10 D_max kept,
+ *                              T = D^-1/2 V';  Pd = T K[:, :n], Pg = T K[:, n:];  Cd = Pd Pd' + gamma I, Cg = Pg Pg' + gamma I;
+ *                              Sigma = Cg^-1/2 (Cg^1/2 Cd Cg^1/2)^1/2 Cg^-1/2, symmetrised, = Y Theta Y';  the directions with
+ *                              theta > cutoff or theta < 1 / cutoff, by |ln theta| descending (the lower index first among equals), at
+ *                              most `rank`;  B = T' Y_sel ([2n][r])
+ *                           d. device: B up, U[k][a] = sum_i B[i][k] W[i][a] (i upwards by fma), then each direction's sign so that its
+ *                              entry of largest magnitude is positive (the lowest index among equals); the orthonormality check of
+ *                              hmcmt_set_mass_lowrank on the staged U (its read-back is a second, short wait of the window end)
+ *                           e. r >= 1 and defect <= 1e-8: s, U, lambda = theta are copied into the mass's buffers and the kind becomes
+ *                              HMCMT_MASS_LOWRANK; r = 0 or a fallback (fewer than 4 pairs, defect above 1e-8, a non-finite value, an eigensolver
+ *                              that did not converge within 64 sweeps): the
+ *                              kind is HMCMT_MASS_DIAGONAL with the new invM and the directions of an earlier window are dropped
+ *                         Either way the dual averaging restarts and the stores rewind, as the diagonal adaptation does.  A HIP error at a
+ *                         window end is no fallback: the window ends on the diagonal, the sample stands, and its call returns HMCMT_EHIP.  The diagonal
+ *                         kernel keeps writing the context's invM, so hmcmt_chain_mass_diag stays truthful.  At the end of the warm-up
+ *                         the mass stays as the last window left it, until the next hmcmt_set_prior or hmcmt_set_mass.
+ *   hmcmt_chain_adapt_lowrank_info   the last closed window: windows closed so far, pairs stored, stride, skipped, dims (m), rank kept,
+ *                         theta_min / theta_max over all m, defect = max |U U' - I| as measured (0 with no direction), fallback,
+ *                         host_ms of step c.  HMCMT_EINVAL without an upgraded adaptation in this chain
+ *   hmcmt_chain_set_mass_lowrank   the between-steps twin of hmcmt_chain_set_mass_diag: the arguments and checks of
+ *                         hmcmt_set_mass_lowrank (orthonormality included, complete before anything changes), but the chain goes on:
+ *                         a momentum already drawn is dropped; the stored gradient, D and M and every accumulator stay.  rank = 0 with
+ *                         invM (U, lambda ignored) sets a plain diagonal and returns the kind to HMCMT_MASS_DIAGONAL.  invM NULL with rank >= 1:
+ *                         the scales in force.  HMCMT_EINVAL
+ *                         under HMCMT_MASS_WM and while an adaptation of the mass is active.  It exists so that an adapted run can be
+ *                         replayed from its record
+ *   hmcmt_chain_mass_lowrank   reads out the mass in force: *rank (0 under the diagonal mass, then only invM is written), invM [nAC],
+ *                         U [*rank][nAC] (room for HMCMT_MASS_RANK_MAX rows), lambda [*rank]; host, or device pointers for invM, U and
+ *                         lambda with on_device = 1 (rank is always a host pointer); any of invM, U, lambda may be NULL */
+typedef struct hmcmt_adapt_lowrank_options {
+    int32_t rank;          /* most directions kept, 1 .. HMCMT_MASS_RANK_MAX; default 8 */
+    int32_t max_samples;   /* most (draw, gradient) pairs stored per window, 4 .. 128; default 64 */
+    double  cutoff;        /* keep theta > cutoff or theta < 1/cutoff; > 1; default 2 */
+    double  gamma;         /* added to both projected covariances; > 0; default 1e-5 */
+} hmcmt_adapt_lowrank_options;
+typedef struct hmcmt_adapt_lowrank_info {
+    int32_t windows, stored, skipped, dims, rank, fallback;
+    int64_t stride;
+    double  theta_min, theta_max, defect, host_ms;
+} hmcmt_adapt_lowrank_info;
+extern void hmcmt_default_adapt_lowrank_options(hmcmt_adapt_lowrank_options* o);
+extern int hmcmt_chain_adapt_lowrank(hmcmt_ctx* ctx, const hmcmt_adapt_lowrank_options* o);
+extern int hmcmt_chain_adapt_lowrank_info(hmcmt_ctx* ctx, hmcmt_adapt_lowrank_info* info);
+extern int hmcmt_chain_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, const double* U, const double* lambda);
+extern int hmcmt_chain_mass_lowrank(hmcmt_ctx* ctx, int32_t* rank, double* invM, double* U, double* lambda, int32_t on_device);
+
 /* The chain's own random numbers: a seeded chain draws its momenta on the device and its L and u in the library, and waits once per
  * sample.  The generator is Philox4x32-10 (Salmon et al., SC'11: multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
  * 0xBB67AE85, ten rounds), used by counter: a draw is a pure function of four integers and no state is carried.

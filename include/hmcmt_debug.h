@@ -153,6 +153,23 @@ int hmcmt_debug_nuts_leaf(hmcmt_ctx* ctx, const hmcmt_debug_nuts_args* args, dou
  * sums.  It changes no result */
 int hmcmt_debug_nuts_iters(hmcmt_ctx* ctx, int64_t* out /*[4]*/, int32_t reset);
 
+/* Test hooks of the low-rank mass adaptation (hmcmt_chain_adapt_lowrank; tests/test_gpu_chain_adapt_lowrank.py).
+ * hmcmt_debug_adapt_lowrank runs the window end's kernels on rows the caller hands in, without a chain or a solve (the context needs
+ * its prior: the rows have nAC cells): X, G [n][nAC] and invM [nAC] from the host, 4 <= n <= 128; K_out [2n][2n] = W W' (k_adapt_lr_mean,
+ * k_adapt_lr_gram); with B [2n][r], 1 <= r <= HMCMT_MASS_RANK_MAX, also U_out [r][nAC] = B' W (k_adapt_lr_lift, then k_adapt_lr_sign);
+ * B NULL or r = 0: the Gram matrix only.  Complete on return; nothing of the context changes.
+ * hmcmt_debug_adapt_lowrank_rows reads the OPEN window's stores of a running upgraded adaptation: *n pairs, X and G [*n][nAC] (room for
+ * max_samples rows each); while the open window holds none, the rows of the window that closed last, which stay in the stores until
+ * the next pair.  HMCMT_EINVAL without such an adaptation. */
+int hmcmt_debug_adapt_lowrank(hmcmt_ctx* ctx, int32_t n, const double* X, const double* G, const double* invM, double* K_out,
+                              const double* B, int32_t r, double* U_out);
+int hmcmt_debug_adapt_lowrank_rows(hmcmt_ctx* ctx, int32_t* n, double* X, double* G);
+/* Measurement only: the last closed window end of a running upgraded adaptation.  out[4] = {ms of k_adapt_lr_mean + k_adapt_lr_gram,
+ * ms of k_adapt_lr_lift + k_adapt_lr_sign (0 where no direction was lifted) -- HIP events on the context's stream --, host ms from the
+ * first launch to K on the host (the window end's wait), host ms of the uploads, the lift and the orthonormality check with its wait}.
+ * It changes no result */
+int hmcmt_debug_adapt_lowrank_time(hmcmt_ctx* ctx, double* out /*[4]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ using SparseArrays
 using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
-export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, proposeLeapfrog, proposeLeapfrogDevice!,
+export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, chain_adapt_lowrank!, chain_adapt_lowrank_info, chain_set_mass_lowrank!, chain_mass_lowrank, proposeLeapfrog, proposeLeapfrogDevice!,
        hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
@@ -824,6 +824,65 @@ end
 
 chainAdaptEnd!(ctx::HipContext) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_end(ctx.ptr::Ptr{Cvoid})::Cint)
 
+# hmcmt_adapt_lowrank_options and hmcmt_adapt_lowrank_info of include/hmcmt.h, field for field
+struct HmcmtAdaptLowrankOptions
+    rank::Int32
+    max_samples::Int32
+    cutoff::Float64
+    gamma::Float64
+end
+struct HmcmtAdaptLowrankInfo
+    windows::Int32
+    stored::Int32
+    skipped::Int32
+    dims::Int32
+    rank::Int32
+    fallback::Int32
+    stride::Int64
+    theta_min::Float64
+    theta_max::Float64
+    defect::Float64
+    host_ms::Float64
+end
+
+"""
+    chain_adapt_lowrank!(ctx; rank=8, maxSamples=64, cutoff=2.0, gamma=1e-5)
+    chain_adapt_lowrank_info(ctx) -> HmcmtAdaptLowrankInfo
+    chain_set_mass_lowrank!(ctx, invM, U, lam)          # U nAC × r; r = 0 with invM: back to the diagonal
+    chain_mass_lowrank(ctx) -> (invM, U, lam)           # U nAC × r, r = 0 under the diagonal mass
+
+The low-rank mass of a live chain (hmcmt_chain_adapt_lowrank, hmcmt_chain_set_mass_lowrank, hmcmt_chain_mass_lowrank, include/hmcmt.h):
+`chain_adapt_lowrank!` right behind `chainAdaptBegin!(...; adaptMass=true)` makes every window end estimate the directions and
+factors from the window's draws and gradients; `run_chain!(...; adapt=(nwarmup=..., lowrank=(rank=4,)))` does so.
+"""
+function chain_adapt_lowrank!(ctx::HipContext; rank::Integer=8, maxSamples::Integer=64, cutoff::Real=2.0, gamma::Real=1e-5)
+    o = Ref(HmcmtAdaptLowrankOptions(Int32(rank), Int32(maxSamples), Float64(cutoff), Float64(gamma)))
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_lowrank(ctx.ptr::Ptr{Cvoid}, o::Ref{HmcmtAdaptLowrankOptions})::Cint)
+end
+
+function chain_adapt_lowrank_info(ctx::HipContext)
+    info = Ref(HmcmtAdaptLowrankInfo(0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0))
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_adapt_lowrank_info(ctx.ptr::Ptr{Cvoid}, info::Ref{HmcmtAdaptLowrankInfo})::Cint)
+    return info[]
+end
+
+function chain_set_mass_lowrank!(ctx::HipContext, invM::Union{Nothing,Vector{Float64}}, U::Matrix{Float64}, lam::Vector{Float64})
+    size(U, 2) == 0 || size(U, 1) == ctx.nAC || error("chain_set_mass_lowrank!: U must be nAC = $(ctx.nAC) × r")
+    length(lam) == size(U, 2) || error("chain_set_mass_lowrank!: lam must hold one entry per column of U")
+    invM === nothing || length(invM) == ctx.nAC || error("chain_set_mass_lowrank!: invM must hold nAC = $(ctx.nAC) entries")
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_set_mass_lowrank(ctx.ptr::Ptr{Cvoid}, (invM === nothing ? C_NULL : invM)::Ptr{Float64},
+                                                                 Int32(size(U, 2))::Int32, U::Ptr{Float64}, lam::Ptr{Float64})::Cint)
+end
+
+function chain_mass_lowrank(ctx::HipContext)
+    rank = Ref{Int32}(0)
+    invM = Vector{Float64}(undef, ctx.nAC); U = Matrix{Float64}(undef, ctx.nAC, HMCMT_MASS_RANK_MAX); lam = Vector{Float64}(undef, HMCMT_MASS_RANK_MAX)
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_mass_lowrank(ctx.ptr::Ptr{Cvoid}, rank::Ref{Int32}, invM::Ptr{Float64}, U::Ptr{Float64},
+                                                             lam::Ptr{Float64}, Int32(0)::Int32)::Cint)
+    r = Int(rank[])
+    return invM, U[:, 1:r], lam[1:r]
+end
+
 """
     run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, seed=nothing, nuts=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt][, nuts])
 
@@ -875,7 +934,9 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
     if adapt !== nothing
         nwarmup = get(adapt, :nwarmup, hmcprior.burninsamples)
         nwarmup <= hmcprior.burninsamples || error("run_chain!: adapt nwarmup = $(nwarmup) exceeds hmcprior.burninsamples: the moments would mix in warm-up samples")
-        chainAdaptBegin!(ctx, nwarmup; Base.structdiff(adapt, NamedTuple{(:nwarmup,)})...)
+        chainAdaptBegin!(ctx, nwarmup; Base.structdiff(adapt, NamedTuple{(:nwarmup, :lowrank)})...)
+        lowrank = get(adapt, :lowrank, nothing)
+        lowrank === nothing || lowrank === false || chain_adapt_lowrank!(ctx; (lowrank === true ? (;) : lowrank)...)
         adaptDt = fill(NaN, nsamples); adaptAlpha = zeros(nsamples)
     end
     ncols = keepSamples ? nsamples : 0
