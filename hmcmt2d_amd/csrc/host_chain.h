@@ -1835,6 +1835,609 @@ int hmcmt_debug_adapt_lowrank_rows(hmcmt_ctx* ctx, int32_t* n, double* X, double
     return 0;
 }
 
+// ---- checkpoint and resume (hmcmt_chain_save / hmcmt_chain_restore; include/hmcmt.h has the container and every payload) --------------
+// A blob is laid out by ONE function, chain_blob_plan: per section its scalars (8-byte fields) and its arrays as (device pointer, bytes)
+// pieces in the payload's order.  hmcmt_chain_save_size adds the plan up, hmcmt_chain_save walks it.  hmcmt_chain_restore parses the
+// sections back with BlobCursor in the same order, first without a device (chain_blob_check: everything that can be refused) and then
+// with one (chain_blob_build).
+constexpr uint32_t blob_tag(char a, char b, char c, char d) {
+    return (uint32_t)(unsigned char)a | (uint32_t)(unsigned char)b << 8 | (uint32_t)(unsigned char)c << 16 | (uint32_t)(unsigned char)d << 24;
+}
+constexpr uint32_t BLOB_CHAN = blob_tag('C', 'H', 'A', 'N'), BLOB_MASS = blob_tag('M', 'A', 'S', 'S'), BLOB_HIST = blob_tag('H', 'I', 'S', 'T'),
+                   BLOB_DMOM = blob_tag('D', 'M', 'O', 'M'), BLOB_ACOV = blob_tag('A', 'C', 'O', 'V'), BLOB_COV = blob_tag('C', 'O', 'V', ' '),
+                   BLOB_ADPT = blob_tag('A', 'D', 'P', 'T'), BLOB_ADLR = blob_tag('A', 'D', 'L', 'R');
+constexpr uint32_t BLOB_ORDER[] = {BLOB_CHAN, BLOB_MASS, BLOB_HIST, BLOB_DMOM, BLOB_ACOV, BLOB_COV, BLOB_ADPT, BLOB_ADLR};
+constexpr size_t BLOB_HEADER = 64, BLOB_ENTRY = 24;
+constexpr char BLOB_MAGIC[8] = {'H', 'M', 'C', 'M', 'T', 'C', 'K', '\0'};
+static_assert(sizeof(double) == 8 && sizeof(long long) == 8, "a blob's fields are 8 bytes");
+
+static uint64_t blob_checksum(const unsigned char* p, uint64_t bytes) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (uint64_t i = 0; i + 8 <= bytes; i += 8) {
+        uint64_t w;
+        std::memcpy(&w, p + i, 8);
+        h = (h ^ w) * 0x100000001b3ull;
+    }
+    return h;
+}
+
+struct BlobPiece { const void* dev; const void* host; uint64_t bytes; };      // one array: on the device, or (small) on the host
+struct BlobSection {
+    uint32_t tag = 0;
+    std::vector<uint64_t> scal;
+    std::vector<BlobPiece> pieces;
+    void i(long long v) { uint64_t w; std::memcpy(&w, &v, 8); scal.push_back(w); }
+    void f(double v) { uint64_t w; std::memcpy(&w, &v, 8); scal.push_back(w); }
+    void u(uint64_t v) { scal.push_back(v); }
+    void dev(const void* p, uint64_t bytes) { if (bytes) pieces.push_back({p, nullptr, bytes}); }
+    void host(const void* p, uint64_t bytes) { if (bytes) pieces.push_back({nullptr, p, bytes}); }
+    uint64_t bytes() const {
+        uint64_t b = 8 * scal.size();
+        for (const auto& p : pieces) b += (p.bytes + 7) & ~(uint64_t)7;
+        return b;
+    }
+};
+
+// the rows of the low-rank adaptation's stores that a later call can still read
+static int chain_adapt_lr_rows(const hmcmt_ctx::Chain::Adapt::Lr& L) { return L.stored > 0 ? L.stored : L.closedStored; }
+
+// the chain as it stands, section by section (nothing is copied: the pieces point into the context)
+static std::vector<BlobSection> chain_blob_plan(hmcmt_ctx* ctx) {
+    const auto& C = ctx->chain;
+    const auto& M = ctx->mass;
+    const uint64_t n = (uint64_t)ctx->v.nAC, nd2 = 2 * (uint64_t)ctx->v.nData, D = sizeof(double);
+    std::vector<BlobSection> out;
+    {
+        BlobSection s; s.tag = BLOB_CHAN;
+        s.f(C.dt); s.f(C.regParam); s.f(C.lo); s.f(C.hi); s.f(C.D); s.f(C.M);
+        s.i(C.burnin); s.i(C.nsamples); s.i(C.nmoments);
+        s.u(C.seeded ? C.seed : 0); s.u(C.seeded ? C.t : 0);
+        s.u((uint64_t)(C.seeded ? C.stream : 0) | (uint64_t)(C.seeded ? 1 : 0) << 32);
+        s.dev(C.d_m[C.cur], n * D); s.dev(C.d_pred[C.cur], nd2 * D); s.dev(C.d_mean, n * D); s.dev(C.d_m2, n * D);
+        out.push_back(std::move(s));
+    }
+    {
+        BlobSection s; s.tag = BLOB_MASS;
+        const bool lr = M.kind == HMCMT_MASS_LOWRANK, given = lr && !M.lrInvM.empty();
+        const uint64_t r = lr ? (uint64_t)M.lrRank : 0;
+        s.i(M.kind); s.i((long long)r); s.i(M.kind == HMCMT_MASS_WM ? 0 : M.lrCap); s.i(given ? 1 : 0);
+        if (M.kind != HMCMT_MASS_WM) s.dev(ctx->d_invM, n * D);
+        if (lr) { s.dev(M.d_lrS, n * D); s.dev(M.d_lrU, r * n * D); s.host(M.lrLambda.data(), r * D); }
+        if (given) s.host(M.lrInvM.data(), n * D);
+        out.push_back(std::move(s));
+    }
+    if (C.hist.on) {
+        const auto& H = C.hist;
+        BlobSection s; s.tag = BLOB_HIST;
+        s.i(H.ntarget); s.i(H.nbins); s.i(H.count); s.f(H.lo); s.f(H.hi);
+        s.dev(H.d_target, (uint64_t)H.ntarget * 8); s.dev(H.d_counts, (uint64_t)H.ntarget * (uint64_t)H.nbins * sizeof(unsigned int));
+        out.push_back(std::move(s));
+    }
+    if (C.dmom.on) {
+        BlobSection s; s.tag = BLOB_DMOM;
+        s.i(C.dmom.count);
+        s.dev(C.dmom.d_mean, nd2 * D); s.dev(C.dmom.d_m2, nd2 * D);
+        out.push_back(std::move(s));
+    }
+    if (C.acov.on) {
+        const auto& A = C.acov;
+        BlobSection s; s.tag = BLOB_ACOV;
+        const uint64_t vb = (uint64_t)A.ntarget * D, lb = vb * (uint64_t)(A.K + 1);
+        s.i(A.ntarget); s.i(A.d_target ? 0 : 1); s.i(A.K); s.i(A.count);
+        if (A.d_target) s.dev(A.d_target, (uint64_t)A.ntarget * 8);
+        s.dev(A.d_x0, vb); s.dev(A.d_tot, vb); s.dev(A.d_S, lb); s.dev(A.d_H, lb); s.dev(A.d_ring, lb);
+        out.push_back(std::move(s));
+    }
+    if (C.cov.on) {
+        const auto& V = C.cov;
+        BlobSection s; s.tag = BLOB_COV;
+        s.i(V.nrow); s.i(V.d_row ? 0 : 1); s.i(V.B); s.i(V.count); s.i(V.npend);
+        if (V.d_row) s.dev(V.d_row, (uint64_t)V.nrow * 8);
+        s.dev(V.d_x0, n * D); s.dev(V.d_tot, n * D); s.dev(V.d_q, n * D);
+        s.dev(V.d_pend, (uint64_t)V.npend * n * D); s.dev(V.d_S, (uint64_t)V.nrow * n * D);
+        out.push_back(std::move(s));
+    }
+    if (C.adapt.begun) {
+        const auto& A = C.adapt;
+        const hmcmt_adapt_options& o = A.opt;
+        BlobSection s; s.tag = BLOB_ADPT;
+        s.i(o.nwarmup); s.i(o.adapt_mass); s.i(o.init_buffer); s.i(o.term_buffer); s.i(o.base_window);
+        s.f(o.delta); s.f(o.gamma); s.f(o.t0); s.f(o.kappa); s.f(o.dt_min); s.f(o.dt_max);
+        s.f(A.da.mu); s.f(A.da.s_bar); s.f(A.da.x_bar); s.f(A.da.x); s.i(A.da.t);
+        s.i(A.c); s.i(A.wcount); s.i(A.wnext); s.i(A.wsize); s.i(A.windowsDone);
+        s.f(A.alphaLast); s.f(A.alphaSum); s.i(1); s.i(A.active ? 1 : 0);
+        if (o.adapt_mass) { s.dev(A.d_mean, n * D); s.dev(A.d_m2, n * D); }
+        out.push_back(std::move(s));
+        if (A.lr.on) {
+            const auto& L = A.lr;
+            const uint64_t rows = (uint64_t)chain_adapt_lr_rows(L);
+            BlobSection t; t.tag = BLOB_ADLR;
+            t.i(L.opt.rank); t.i(L.opt.max_samples); t.f(L.opt.cutoff); t.f(L.opt.gamma);
+            t.i(L.winStart); t.i(L.stride); t.i(L.stored); t.i(L.skipped); t.i(L.closedStored); t.i((long long)rows);
+            t.i(L.last.windows); t.i(L.last.stored); t.i(L.last.skipped); t.i(L.last.dims); t.i(L.last.rank); t.i(L.last.fallback); t.i(L.last.stride);
+            t.f(L.last.theta_min); t.f(L.last.theta_max); t.f(L.last.defect); t.f(L.last.host_ms);
+            t.dev(L.d_X, rows * n * D); t.dev(L.d_G, rows * n * D);
+            out.push_back(std::move(t));
+        }
+    }
+    return out;
+}
+
+static uint64_t chain_blob_bytes(const std::vector<BlobSection>& plan) {
+    uint64_t b = BLOB_HEADER + BLOB_ENTRY * plan.size() + 8;
+    for (const auto& s : plan) b += s.bytes();
+    return b;
+}
+
+int hmcmt_chain_save_size(hmcmt_ctx* ctx, uint64_t* bytes) {
+    const char* fn = "hmcmt_chain_save_size";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!bytes) { ctx->err = std::string(fn) + ": bytes is NULL"; return HMCMT_EINVAL; }
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    *bytes = chain_blob_bytes(chain_blob_plan(ctx));
+    return 0;
+}
+
+int hmcmt_chain_save(hmcmt_ctx* ctx, void* buf, uint64_t capacity, uint64_t* written) {
+    const char* fn = "hmcmt_chain_save";
+    if (!ctx) return HMCMT_EINVAL;
+    if (written) *written = 0;
+    const int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    const std::vector<BlobSection> plan = chain_blob_plan(ctx);
+    const uint64_t total = chain_blob_bytes(plan);
+    if (written) *written = total;
+    if (!buf || capacity < total) {
+        ctx->err = std::string(fn) + ": the chain needs " + std::to_string(total) + " bytes, the buffer has " + std::to_string(buf ? capacity : 0);
+        return HMCMT_EINVAL;
+    }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    hipStream_t st = ctx->stream;
+    const auto& C = ctx->chain;
+    unsigned char* b = (unsigned char*)buf;
+    auto put = [&](uint64_t at, const void* p, size_t nb) { std::memcpy(b + at, p, nb); };
+    auto put32 = [&](uint64_t at, uint32_t v) { put(at, &v, 4); };
+    auto put64 = [&](uint64_t at, uint64_t v) { put(at, &v, 8); };
+    put(0, BLOB_MAGIC, 8);
+    put32(8, HMCMT_BLOB_VERSION); put32(12, (uint32_t)plan.size());
+    put64(16, total);
+    put64(24, (uint64_t)(long long)ctx->v.nAC); put64(32, (uint64_t)(long long)ctx->v.nData);
+    put32(40, (uint32_t)ctx->mass.kind); put32(44, C.seeded ? 1u : 0u);
+    put64(48, (uint64_t)C.nsamples); put64(56, (uint64_t)C.nmoments);
+    uint64_t at = BLOB_HEADER + BLOB_ENTRY * plan.size();
+    for (size_t k = 0; k < plan.size(); ++k) {
+        const BlobSection& s = plan[k];
+        const uint64_t e = BLOB_HEADER + BLOB_ENTRY * k;
+        put32(e, s.tag); put32(e + 4, 0); put64(e + 8, at); put64(e + 16, s.bytes());
+        put(at, s.scal.data(), 8 * s.scal.size());
+        at += 8 * s.scal.size();
+        for (const BlobPiece& p : s.pieces) {
+            const uint64_t padded = (p.bytes + 7) & ~(uint64_t)7;
+            if (padded != p.bytes) put64(at + padded - 8, 0);                 // (the padding is zero: two saves are the same bytes)
+            if (p.host) put(at, p.host, (size_t)p.bytes);
+            else HIPCHK(hipMemcpyAsync(b + at, p.dev, (size_t)p.bytes, hipMemcpyDeviceToHost, st));
+            at += padded;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    put64(at, blob_checksum(b, at));
+    return 0;
+}
+
+// ---- a blob read back ----------------------------------------------------------------------------------------------------------------
+struct BlobEntry { uint32_t tag; uint64_t offset, bytes; };
+struct BlobParsed {
+    hmcmt_chain_blob_header h{};
+    std::vector<BlobEntry> entries;
+    const BlobEntry* find(uint32_t tag) const {
+        for (const auto& e : entries) if (e.tag == tag) return &e;
+        return nullptr;
+    }
+};
+// reads one payload in its order; ok turns false where the payload is too short
+struct BlobCursor {
+    const unsigned char* p; uint64_t left; bool ok = true;
+    BlobCursor(const unsigned char* b, const BlobEntry& e) : p(b + e.offset), left(e.bytes) {}
+    uint64_t u() { uint64_t w = 0; if (left < 8) { ok = false; return 0; } std::memcpy(&w, p, 8); p += 8; left -= 8; return w; }
+    long long i() { const uint64_t w = u(); long long v; std::memcpy(&v, &w, 8); return v; }
+    double f() { const uint64_t w = u(); double v; std::memcpy(&v, &w, 8); return v; }
+    const unsigned char* arr(uint64_t bytes) {                               // an array of `bytes` bytes, padded to 8
+        const uint64_t padded = (bytes + 7) & ~(uint64_t)7;
+        if (!ok || padded < bytes || left < padded) { ok = false; return nullptr; }
+        const unsigned char* q = p; p += padded; left -= padded; return q;
+    }
+};
+
+// the container alone: magic, version, sizes, the table's consistency, the checksum, CHAN against the header.  why: what is wrong
+static int blob_parse(const void* buf, uint64_t bytes, BlobParsed& P, std::string& why) {
+    const unsigned char* b = (const unsigned char*)buf;
+    auto get32 = [&](uint64_t at) { uint32_t v; std::memcpy(&v, b + at, 4); return v; };
+    auto get64 = [&](uint64_t at) { uint64_t v; std::memcpy(&v, b + at, 8); return v; };
+    if (!buf || bytes < BLOB_HEADER + 2 * BLOB_ENTRY + 8 || bytes % 8) { why = "too short for a blob, or no multiple of 8 bytes"; return HMCMT_EINVAL; }
+    if (std::memcmp(b, BLOB_MAGIC, 8)) { why = "no blob of this library (the magic is not \"HMCMTCK\")"; return HMCMT_EINVAL; }
+    auto& h = P.h;
+    h.version = get32(8); h.nsections = get32(12); h.total_bytes = get64(16);
+    if (h.version != HMCMT_BLOB_VERSION) { why = "version " + std::to_string(h.version) + " (this library reads version 1)"; return HMCMT_EINVAL; }
+    if (h.total_bytes != bytes) { why = "the header says " + std::to_string(h.total_bytes) + " bytes, the buffer has " + std::to_string(bytes); return HMCMT_EINVAL; }
+    if (get64(bytes - 8) != blob_checksum(b, bytes - 8)) { why = "the checksum does not match"; return HMCMT_EINVAL; }
+    if (h.nsections < 2 || h.nsections > HMCMT_BLOB_SECTIONS_MAX || BLOB_HEADER + BLOB_ENTRY * h.nsections + 8 > bytes) { why = "the section count is out of range"; return HMCMT_EINVAL; }
+    std::memcpy(&h.nAC, b + 24, 8); std::memcpy(&h.nData, b + 32, 8);
+    std::memcpy(&h.mass_kind, b + 40, 4); h.seeded = get32(44);
+    std::memcpy(&h.nsamples, b + 48, 8); std::memcpy(&h.nmoments, b + 56, 8);
+    if (h.nAC < 1 || h.nAC > INT32_MAX || h.nData < 0 || h.nData > INT32_MAX / 2 || h.seeded > 1 || h.nsamples < 0 || h.nmoments < 0 || h.nmoments > h.nsamples ||
+        h.mass_kind < HMCMT_MASS_DIAGONAL || h.mass_kind > HMCMT_MASS_LOWRANK) { why = "a header field is out of range"; return HMCMT_EINVAL; }
+    uint64_t at = BLOB_HEADER + BLOB_ENTRY * h.nsections;
+    size_t order = 0;
+    for (uint32_t k = 0; k < h.nsections; ++k) {
+        const uint64_t e = BLOB_HEADER + BLOB_ENTRY * k;
+        const BlobEntry en{get32(e), get64(e + 8), get64(e + 16)};
+        while (order < sizeof BLOB_ORDER / sizeof *BLOB_ORDER && BLOB_ORDER[order] != en.tag) ++order;
+        if (order == sizeof BLOB_ORDER / sizeof *BLOB_ORDER) { why = "section " + std::to_string(k) + ": an unknown tag, a repeated one, or one out of order"; return HMCMT_EINVAL; }
+        ++order;
+        if (get32(e + 4) != 0 || en.offset % 8 || en.bytes % 8 || en.offset != at || en.bytes > bytes - 8 - at) {
+            why = "section " + std::to_string(k) + ": its offset or length is no multiple of 8, overlaps, leaves a gap or runs past the end";
+            return HMCMT_EINVAL;
+        }
+        at += en.bytes;
+        P.entries.push_back(en);
+        h.tags[k] = en.tag; h.section_bytes[k] = en.bytes;
+    }
+    if (at + 8 != bytes) { why = "bytes behind the last section"; return HMCMT_EINVAL; }
+    if (P.entries[0].tag != BLOB_CHAN || P.entries[1].tag != BLOB_MASS) { why = "CHAN and MASS must come first"; return HMCMT_EINVAL; }
+    if (P.find(BLOB_ADLR) && !P.find(BLOB_ADPT)) { why = "ADLR without ADPT"; return HMCMT_EINVAL; }
+    if (P.entries[0].bytes != 96 + 8 * (3 * (uint64_t)h.nAC + 2 * (uint64_t)h.nData)) { why = "CHAN has not the length of nAC and nData"; return HMCMT_EINVAL; }
+    BlobCursor c(b, P.entries[0]);
+    for (int k = 0; k < 7; ++k) (void)c.u();
+    const long long ns = c.i(), nm = c.i();
+    (void)c.u(); (void)c.u();
+    const uint64_t ss = c.u();
+    if (ns != h.nsamples || nm != h.nmoments || (ss >> 32) != h.seeded) { why = "CHAN and the header disagree"; return HMCMT_EINVAL; }
+    return 0;
+}
+
+int hmcmt_chain_blob_info(const void* buf, uint64_t bytes, hmcmt_chain_blob_header* out) {
+    if (!buf || !out) return HMCMT_EINVAL;
+    BlobParsed P;
+    std::string why;
+    const int rc = blob_parse(buf, bytes, P, why);
+    if (rc) return rc;
+    *out = P.h;
+    return 0;
+}
+
+// what a restore reads out of a blob before it touches the context: every scalar, and where the arrays lie
+struct BlobChain {
+    double dt, regParam, lo, hi, D, M;
+    long long burnin, nsamples, nmoments;
+    uint64_t seed, t; uint32_t stream; bool seeded;
+    const unsigned char *m, *pred, *mean, *m2;
+    struct { int kind, rank, cap; bool given; const unsigned char *invM, *s, *U, *lambda, *invM0; } mass{};
+    struct { bool on; long long ntarget, count; int nbins; double lo, hi; const unsigned char *target, *counts; } hist{};
+    struct { bool on; long long count; const unsigned char *mean, *m2; } dmom{};
+    struct { bool on, all; long long ntarget, count; int K; const unsigned char *target, *x0, *tot, *S, *H, *ring; } acov{};
+    struct { bool on, all; long long nrow, count; int B, npend; const unsigned char *row, *x0, *tot, *q, *pend, *S; } cov{};
+    struct { bool on, active; hmcmt_adapt_options opt; AdaptDA da; long long c, wcount, wnext, wsize; int windowsDone; double alphaLast, alphaSum;
+             const unsigned char *mean, *m2; } adapt{};
+    struct { bool on; hmcmt_adapt_lowrank_options opt; long long winStart, stride; int stored, skipped, closedStored, rows;
+             hmcmt_adapt_lowrank_info last; const unsigned char *X, *G; } lr{};
+};
+
+static bool blob_finite(const unsigned char* p, uint64_t n, bool positive) {
+    for (uint64_t k = 0; k < n; ++k) {
+        double v;
+        std::memcpy(&v, p + 8 * k, 8);
+        if (!std::isfinite(v) || (positive && !(v > 0.0))) return false;
+    }
+    return true;
+}
+static bool blob_cells(const unsigned char* p, uint64_t n, long long nAC) {
+    for (uint64_t k = 0; k < n; ++k) {
+        long long v;
+        std::memcpy(&v, p + 8 * k, 8);
+        if (v < 0 || v >= nAC) return false;
+    }
+    return true;
+}
+
+// every section against the context's sizes and the ranges the begin calls check; nothing of the context changes
+static int chain_blob_check(hmcmt_ctx* ctx, const unsigned char* b, const BlobParsed& P, BlobChain& R) {
+    const char* fn = "hmcmt_chain_restore";
+    const long long nAC = ctx->v.nAC, nData = ctx->v.nData;
+    const uint64_t n = (uint64_t)nAC, nd2 = 2 * (uint64_t)nData, D = 8;
+    auto bad = [&](const std::string& what) { ctx->err = std::string(fn) + ": " + what; return HMCMT_EINVAL; };
+    if (P.h.nAC != nAC || P.h.nData != nData)
+        return bad("the blob is of a problem with nAC = " + std::to_string(P.h.nAC) + ", nData = " + std::to_string(P.h.nData) + "; the context has " +
+                   std::to_string(nAC) + ", " + std::to_string(nData));
+    {
+        BlobCursor c(b, P.entries[0]);
+        R.dt = c.f(); R.regParam = c.f(); R.lo = c.f(); R.hi = c.f(); R.D = c.f(); R.M = c.f();
+        R.burnin = c.i(); R.nsamples = c.i(); R.nmoments = c.i();
+        R.seed = c.u(); R.t = c.u();
+        const uint64_t ss = c.u();
+        R.stream = (uint32_t)ss; R.seeded = (ss >> 32) != 0;
+        R.m = c.arr(n * D); R.pred = c.arr(nd2 * D); R.mean = c.arr(n * D); R.m2 = c.arr(n * D);
+        if (!c.ok || c.left) return bad("CHAN: wrong length");
+        if (!(R.dt > 0) || !std::isfinite(R.dt) || !std::isfinite(R.regParam) || !std::isfinite(R.lo) || !std::isfinite(R.hi) || !(R.hi > R.lo) ||
+            R.burnin < 0 || !std::isfinite(R.D) || !std::isfinite(R.M) || !blob_finite(R.m, n, false))
+            return bad("CHAN: need finite dt > 0, regParam, lnSigMax > lnSigMin, D, M, burnin >= 0 and a finite model");
+    }
+    {
+        BlobCursor c(b, P.entries[1]);
+        auto& Q = R.mass;
+        const long long kind = c.i(), rank = c.i(), cap = c.i(), given = c.i();
+        if (!c.ok || kind != P.h.mass_kind || rank < 0 || rank > HMCMT_MASS_RANK_MAX || cap < 0 || cap > HMCMT_MASS_RANK_MAX || (given != 0 && given != 1) ||
+            (kind == HMCMT_MASS_LOWRANK ? (rank < 1 || cap < rank) : (rank != 0 || given != 0)) || (kind == HMCMT_MASS_WM && cap != 0))
+            return bad("MASS: kind, rank or capacity out of range");
+        Q.kind = (int)kind; Q.rank = (int)rank; Q.cap = (int)cap; Q.given = given != 0;
+        if (kind == HMCMT_MASS_WM && ctx->mass.kind != HMCMT_MASS_WM) return bad("the blob was saved under HMCMT_MASS_WM: hmcmt_set_mass(HMCMT_MASS_WM) first");
+        if (kind != HMCMT_MASS_WM) Q.invM = c.arr(n * D);
+        if (kind == HMCMT_MASS_LOWRANK) { Q.s = c.arr(n * D); Q.U = c.arr((uint64_t)rank * n * D); Q.lambda = c.arr((uint64_t)rank * D); }
+        if (Q.given) Q.invM0 = c.arr(n * D);
+        if (!c.ok || c.left) return bad("MASS: wrong length");
+        if ((Q.invM && !blob_finite(Q.invM, n, true)) || (Q.s && !blob_finite(Q.s, n, true)) || (Q.U && !blob_finite(Q.U, (uint64_t)rank * n, false)) ||
+            (Q.lambda && !blob_finite(Q.lambda, (uint64_t)rank, true)) || (Q.invM0 && !blob_finite(Q.invM0, n, true)))
+            return bad("MASS: every scale and lambda must be finite and > 0, every direction finite");
+    }
+    if (const BlobEntry* e = P.find(BLOB_HIST)) {
+        BlobCursor c(b, *e);
+        auto& H = R.hist;
+        H.on = true;
+        H.ntarget = c.i(); const long long nbins = c.i(); H.count = c.i(); H.lo = c.f(); H.hi = c.f();
+        if (!c.ok || H.ntarget < 1 || H.ntarget > INT32_MAX || nbins < 1 || nbins > CHAIN_HIST_MAXBINS || H.count < 0 || !std::isfinite(H.lo) || !std::isfinite(H.hi) ||
+            !(H.hi > H.lo) || !std::isfinite(H.hi - H.lo))
+            return bad("HIST: need ntarget >= 1, 1 <= nbins <= 4096, finite lo < hi and count >= 0");
+        H.nbins = (int)nbins;
+        H.target = c.arr((uint64_t)H.ntarget * 8); H.counts = c.arr((uint64_t)H.ntarget * (uint64_t)nbins * sizeof(unsigned int));
+        if (!c.ok || c.left) return bad("HIST: wrong length");
+        if (!blob_cells(H.target, (uint64_t)H.ntarget, nAC)) return bad("HIST: a target is no active cell");
+    }
+    if (const BlobEntry* e = P.find(BLOB_DMOM)) {
+        BlobCursor c(b, *e);
+        R.dmom.on = true;
+        R.dmom.count = c.i();
+        R.dmom.mean = c.arr(nd2 * D); R.dmom.m2 = c.arr(nd2 * D);
+        if (!c.ok || c.left || R.dmom.count < 0) return bad("DMOM: wrong length or a negative count");
+    }
+    if (const BlobEntry* e = P.find(BLOB_ACOV)) {
+        BlobCursor c(b, *e);
+        auto& A = R.acov;
+        A.on = true;
+        A.ntarget = c.i(); const long long all = c.i(), K = c.i(); A.count = c.i();
+        if (!c.ok || A.ntarget < 1 || A.ntarget > INT32_MAX || (all != 0 && all != 1) || (all && A.ntarget != nAC) || K < 1 || K > CHAIN_ACOV_MAXLAG || A.count < 0)
+            return bad("ACOV: need ntarget >= 1 (all cells: nAC), 1 <= maxlag <= 1023 and count >= 0");
+        A.all = all != 0; A.K = (int)K;
+        const uint64_t vb = (uint64_t)A.ntarget * D, lb = vb * (uint64_t)(K + 1);
+        if (!A.all) A.target = c.arr((uint64_t)A.ntarget * 8);
+        A.x0 = c.arr(vb); A.tot = c.arr(vb); A.S = c.arr(lb); A.H = c.arr(lb); A.ring = c.arr(lb);
+        if (!c.ok || c.left) return bad("ACOV: wrong length");
+        if (A.target && !blob_cells(A.target, (uint64_t)A.ntarget, nAC)) return bad("ACOV: a target is no active cell");
+    }
+    if (const BlobEntry* e = P.find(BLOB_COV)) {
+        BlobCursor c(b, *e);
+        auto& V = R.cov;
+        V.on = true;
+        V.nrow = c.i(); const long long all = c.i(), B = c.i(); V.count = c.i(); const long long npend = c.i();
+        if (!c.ok || V.nrow < 1 || V.nrow > INT32_MAX || (all != 0 && all != 1) || (all && V.nrow != nAC) || B < 1 || B > CHAIN_COV_BATCH_MAX || V.count < 0 ||
+            npend < 0 || npend >= B || npend > V.count)
+            return bad("COV: need nrow >= 1 (all cells: nAC), 1 <= batch <= 16, count >= 0 and 0 <= npend < batch");
+        V.all = all != 0; V.B = (int)B; V.npend = (int)npend;
+        if ((uint64_t)V.nrow > c.left / D / n) return bad("COV: wrong length");      // (nrow * nAC * 8 may not wrap: S alone must fit)
+        if (!V.all) V.row = c.arr((uint64_t)V.nrow * 8);
+        V.x0 = c.arr(n * D); V.tot = c.arr(n * D); V.q = c.arr(n * D); V.pend = c.arr((uint64_t)npend * n * D); V.S = c.arr((uint64_t)V.nrow * n * D);
+        if (!c.ok || c.left) return bad("COV: wrong length");
+        if (V.row && !blob_cells(V.row, (uint64_t)V.nrow, nAC)) return bad("COV: a row is no active cell");
+    }
+    if (const BlobEntry* e = P.find(BLOB_ADPT)) {
+        BlobCursor c(b, *e);
+        auto& A = R.adapt;
+        A.on = true;
+        hmcmt_adapt_options& o = A.opt;
+        o = hmcmt_adapt_options{};
+        o.nwarmup = c.i(); const long long am = c.i(), ib = c.i(), tb = c.i(), bw = c.i();
+        o.delta = c.f(); o.gamma = c.f(); o.t0 = c.f(); o.kappa = c.f(); o.dt_min = c.f(); o.dt_max = c.f();
+        A.da.mu = c.f(); A.da.s_bar = c.f(); A.da.x_bar = c.f(); A.da.x = c.f(); A.da.t = c.i();
+        A.c = c.i(); A.wcount = c.i(); A.wnext = c.i(); A.wsize = c.i(); const long long wd = c.i();
+        A.alphaLast = c.f(); A.alphaSum = c.f(); const long long begun = c.i(), active = c.i();
+        const bool finite = std::isfinite(o.delta) && std::isfinite(o.gamma) && std::isfinite(o.t0) && std::isfinite(o.kappa) && std::isfinite(o.dt_min) &&
+                            std::isfinite(o.dt_max);
+        if (!c.ok || !finite || o.nwarmup < 1 || !(o.delta > 0 && o.delta < 1) || !(o.gamma > 0) || !(o.t0 > 0) || !(o.kappa > 0.5 && o.kappa <= 1) || o.dt_min < 0 ||
+            o.dt_max < 0 || (o.dt_min > 0 && o.dt_max > 0 && o.dt_min > o.dt_max) || (am != 0 && am != 1) || begun != 1 || (active != 0 && active != 1) ||
+            (am && (ib < 0 || tb < 0 || bw < 1 || ib > INT32_MAX || tb > INT32_MAX || bw > INT32_MAX || ib + bw + tb > o.nwarmup)) || A.c < 0 || A.c > o.nwarmup ||
+            A.wcount < 0 || A.wnext < -1 || A.wsize < 0 || wd < 0 || wd > INT32_MAX || A.da.t < 0 || (active && A.c >= o.nwarmup) ||
+            (am && R.mass.kind == HMCMT_MASS_WM))
+            return bad("ADPT: an option or a counter is outside the range hmcmt_chain_adapt_begin accepts");
+        o.adapt_mass = (int)am; o.init_buffer = (int)ib; o.term_buffer = (int)tb; o.base_window = (int)bw;
+        A.windowsDone = (int)wd; A.active = active != 0;
+        if (am) { A.mean = c.arr(n * D); A.m2 = c.arr(n * D); }
+        if (!c.ok || c.left) return bad("ADPT: wrong length");
+    }
+    if (const BlobEntry* e = P.find(BLOB_ADLR)) {
+        BlobCursor c(b, *e);
+        auto& L = R.lr;
+        L.on = true;
+        const long long rank = c.i(), ms = c.i();
+        L.opt = hmcmt_adapt_lowrank_options{};
+        L.opt.cutoff = c.f(); L.opt.gamma = c.f();
+        L.winStart = c.i(); L.stride = c.i(); const long long stored = c.i(), skipped = c.i(), closed = c.i(), rows = c.i();
+        long long w[6];
+        for (long long& v : w) v = c.i();
+        L.last = hmcmt_adapt_lowrank_info{};
+        L.last.stride = c.i(); L.last.theta_min = c.f(); L.last.theta_max = c.f(); L.last.defect = c.f(); L.last.host_ms = c.f();
+        bool ok = c.ok && R.adapt.opt.adapt_mass && rank >= 1 && rank <= HMCMT_MASS_RANK_MAX && ms >= ADAPT_LR_NMIN && ms <= ADAPT_LR_NMAX && std::isfinite(L.opt.cutoff) &&
+                  L.opt.cutoff > 1.0 && std::isfinite(L.opt.gamma) && L.opt.gamma > 0.0 && L.stride >= 1 && stored >= 0 && stored <= ms && skipped >= 0 &&
+                  skipped <= INT32_MAX && closed >= 0 && closed <= ms && rows == (stored > 0 ? stored : closed) && L.winStart >= 0 &&
+                  (!R.adapt.active || R.mass.cap >= rank);
+        for (long long v : w) ok = ok && v >= INT32_MIN && v <= INT32_MAX;
+        if (!ok) return bad("ADLR: an option or a counter is outside the range hmcmt_chain_adapt_lowrank accepts, or the mass has no room for its rank");
+        L.opt.rank = (int)rank; L.opt.max_samples = (int)ms;
+        L.stored = (int)stored; L.skipped = (int)skipped; L.closedStored = (int)closed; L.rows = (int)rows;
+        L.last.windows = (int)w[0]; L.last.stored = (int)w[1]; L.last.skipped = (int)w[2]; L.last.dims = (int)w[3]; L.last.rank = (int)w[4]; L.last.fallback = (int)w[5];
+        L.X = c.arr((uint64_t)rows * n * D); L.G = c.arr((uint64_t)rows * n * D);
+        if (!c.ok || c.left) return bad("ADLR: wrong length");
+    }
+    return 0;
+}
+
+// the chain of a checked blob on the device: the context has no chain when this begins; the caller releases what a failure leaves
+static int chain_blob_build(hmcmt_ctx* ctx, const BlobChain& R) {
+    const char* fn = "hmcmt_chain_restore";
+    auto& C = ctx->chain;
+    auto& M = ctx->mass;
+    const int nAC = ctx->v.nAC, nData = ctx->v.nData;
+    const size_t n = (size_t)nAC, D = sizeof(double), vb = n * D, pb = 2 * (size_t)nData * D;
+    hipStream_t st = ctx->stream;
+    int rc;
+    auto up = [&](void* dst, const unsigned char* src, size_t bytes) -> int {
+        if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+        return 0;
+    };
+    // the mass first: what hmcmt_chain_set_mass_diag / hmcmt_chain_set_mass_lowrank leave, with the blob's bits
+    if (R.mass.kind != HMCMT_MASS_WM) {
+        double *d_s = nullptr, *d_U = nullptr, *d_c = nullptr, *d_part = nullptr;
+        if (R.mass.cap > 0 && (rc = mass_lr_alloc(ctx, R.mass.cap, &d_s, &d_U, &d_c, &d_part))) {
+            (void)hipGetLastError();
+            mass_lr_free(ctx, {d_s, d_U, d_c, d_part});
+            ctx->err = std::string(fn) + ": device allocation failed (the low-rank mass)";
+            return HMCMT_ENOMEM;
+        }
+        mass_lr_release(ctx);
+        M.kind = HMCMT_MASS_DIAGONAL;
+        M.d_lrS = d_s; M.d_lrU = d_U; M.d_lrC = d_c; M.d_lrPart = d_part;
+        M.lrCap = R.mass.cap;
+        if ((rc = up(ctx->d_invM, R.mass.invM, vb))) return rc;
+        if (R.mass.kind == HMCMT_MASS_LOWRANK) {
+            const int r = R.mass.rank;
+            M.lrLambda.resize((size_t)r);
+            std::memcpy(M.lrLambda.data(), R.mass.lambda, (size_t)r * D);
+            std::vector<double> c((size_t)2 * r);
+            for (int k = 0; k < r; ++k) { c[k] = M.lrLambda[k] - 1.0; c[r + k] = 1.0 / std::sqrt(M.lrLambda[k]) - 1.0; }
+            if ((rc = up(d_s, R.mass.s, vb)) || (rc = up(d_U, R.mass.U, (size_t)r * vb))) return rc;
+            HIPCHK(hipMemcpyAsync(d_c, c.data(), (size_t)2 * r * D, hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));                // (c is this scope's)
+            if (R.mass.given) { M.lrInvM.resize(n); std::memcpy(M.lrInvM.data(), R.mass.invM0, vb); }
+            M.lrRank = r;
+            M.kind = HMCMT_MASS_LOWRANK;
+        }
+    }
+    // the chain's own buffers, as hmcmt_chain_begin makes them
+    const std::pair<double**, size_t> bufs[] = {
+        {&C.d_m[0], n}, {&C.d_m[1], n}, {&C.d_p, n}, {&C.d_z, n}, {&C.d_mean, n}, {&C.d_m2, n},
+        {&C.d_pred[0], (size_t)2 * nData}, {&C.d_pred[1], (size_t)2 * nData}, {&C.d_part, (size_t)2 * LFNB}, {&C.d_scal, (size_t)CHAIN_SCAL}};
+    for (const auto& b : bufs)
+        if ((rc = chain_alloc(ctx, b.first, b.second))) { ctx->err = std::string(fn) + ": device allocation failed (the chain)"; return rc; }
+    if (hipHostMalloc((void**)&C.h_rec, sizeof(double) * (CHAIN_REC + LFNB), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        C.h_rec = nullptr;
+        ctx->err = std::string(fn) + ": pinned allocation failed";
+        return HMCMT_ENOMEM;
+    }
+    if ((rc = up(C.d_m[0], R.m, vb)) || (rc = up(C.d_pred[0], R.pred, pb)) || (rc = up(C.d_mean, R.mean, vb)) || (rc = up(C.d_m2, R.m2, vb))) return rc;
+    C.dt = R.dt; C.regParam = R.regParam; C.lo = R.lo; C.hi = R.hi; C.D = R.D; C.M = R.M; C.K0 = 0;
+    C.burnin = R.burnin; C.nsamples = R.nsamples; C.nmoments = R.nmoments;
+    C.seeded = R.seeded; C.seed = R.seed; C.t = R.t; C.stream = R.stream;
+    C.cur = 0; C.nextStart = 0; C.haveMomentum = false;
+    // a list of cells and the buffers of an accumulator: allocated, zeroed where the blob holds only a part, filled
+    auto make = [&](std::vector<void*>& owner, void** p, size_t bytes, const unsigned char* src, size_t have) -> int {
+        int r = have < bytes ? chain_acc_zeroed(ctx, fn, owner, p, std::max<size_t>(bytes, 1)) : chain_acc_alloc(ctx, fn, owner, p, std::max<size_t>(bytes, 1));
+        if (!r && src) r = up(*p, src, have);
+        return r;
+    };
+    if (R.hist.on) {
+        auto& H = C.hist;
+        const size_t cb = (size_t)R.hist.ntarget * (size_t)R.hist.nbins * sizeof(unsigned int);
+        if ((rc = make(H.allocs, (void**)&H.d_target, (size_t)R.hist.ntarget * 8, R.hist.target, (size_t)R.hist.ntarget * 8)) ||
+            (rc = make(H.allocs, (void**)&H.d_counts, cb, R.hist.counts, cb))) return rc;
+        H.ntarget = R.hist.ntarget; H.nbins = R.hist.nbins; H.lo = R.hist.lo; H.hi = R.hist.hi; H.count = R.hist.count;
+        H.scale = (double)H.nbins / (H.hi - H.lo);           // (hmcmt_chain_hist_begin's two expressions)
+        H.w = (H.hi - H.lo) / (double)H.nbins;
+        H.on = true;
+    }
+    if (R.dmom.on) {
+        auto& Q = C.dmom;
+        if ((rc = make(Q.allocs, (void**)&Q.d_mean, pb, R.dmom.mean, pb)) || (rc = make(Q.allocs, (void**)&Q.d_m2, pb, R.dmom.m2, pb))) return rc;
+        Q.count = R.dmom.count;
+        Q.on = true;
+    }
+    if (R.acov.on) {
+        auto& A = C.acov;
+        const size_t tb = (size_t)R.acov.ntarget * D, lb = tb * (size_t)(R.acov.K + 1);
+        if (!R.acov.all && (rc = make(A.allocs, (void**)&A.d_target, tb, R.acov.target, tb))) return rc;
+        if ((rc = make(A.allocs, (void**)&A.d_x0, tb, R.acov.x0, tb)) || (rc = make(A.allocs, (void**)&A.d_tot, tb, R.acov.tot, tb)) ||
+            (rc = make(A.allocs, (void**)&A.d_S, lb, R.acov.S, lb)) || (rc = make(A.allocs, (void**)&A.d_H, lb, R.acov.H, lb)) ||
+            (rc = make(A.allocs, (void**)&A.d_ring, lb, R.acov.ring, lb))) return rc;
+        A.ntarget = R.acov.ntarget; A.K = R.acov.K; A.count = R.acov.count;
+        A.on = true;
+    }
+    if (R.cov.on) {
+        auto& V = C.cov;
+        const size_t rb = (size_t)R.cov.nrow * 8;
+        if (!R.cov.all && (rc = make(V.allocs, (void**)&V.d_row, rb, R.cov.row, rb))) return rc;
+        if ((rc = make(V.allocs, (void**)&V.d_x0, vb, R.cov.x0, vb)) || (rc = make(V.allocs, (void**)&V.d_tot, vb, R.cov.tot, vb)) ||
+            (rc = make(V.allocs, (void**)&V.d_q, vb, R.cov.q, vb)) ||
+            (rc = make(V.allocs, (void**)&V.d_pend, vb * (size_t)R.cov.B, R.cov.pend, vb * (size_t)R.cov.npend)) ||
+            (rc = make(V.allocs, (void**)&V.d_S, vb * (size_t)R.cov.nrow, R.cov.S, vb * (size_t)R.cov.nrow))) return rc;
+        V.nrow = R.cov.nrow; V.B = R.cov.B; V.npend = R.cov.npend; V.count = R.cov.count;
+        V.on = true;
+    }
+    if (R.adapt.on) {
+        auto& A = C.adapt;
+        if (R.adapt.opt.adapt_mass && ((rc = make(A.allocs, (void**)&A.d_mean, vb, R.adapt.mean, vb)) || (rc = make(A.allocs, (void**)&A.d_m2, vb, R.adapt.m2, vb))))
+            return rc;
+        A.opt = R.adapt.opt; A.da = R.adapt.da;
+        A.c = R.adapt.c; A.wcount = R.adapt.wcount; A.wnext = R.adapt.wnext; A.wsize = R.adapt.wsize; A.windowsDone = R.adapt.windowsDone;
+        A.alphaLast = R.adapt.alphaLast; A.alphaSum = R.adapt.alphaSum;
+        if (R.lr.on) {
+            auto& L = A.lr;
+            const size_t ms = (size_t)R.lr.opt.max_samples, rk = (size_t)R.lr.opt.rank, have = (size_t)R.lr.rows * vb;
+            if ((rc = make(A.allocs, (void**)&L.d_X, ms * vb, R.lr.X, have)) || (rc = make(A.allocs, (void**)&L.d_G, ms * vb, R.lr.G, have))) return rc;
+            const std::pair<double**, size_t> stage[] = {{&L.d_K, 4 * ms * ms * D}, {&L.d_B, 2 * ms * rk * D}, {&L.d_meanX, vb}, {&L.d_meanG, vb},
+                                                         {&L.d_s, vb}, {&L.d_U, rk * vb}, {&L.d_c, 2 * rk * D}, {&L.d_part, rk * LFNB * D}};
+            for (const auto& s : stage)
+                if ((rc = chain_acc_zeroed(ctx, fn, A.allocs, (void**)s.first, s.second))) return rc;
+            L.opt = R.lr.opt;
+            L.winStart = R.lr.winStart; L.stride = R.lr.stride;
+            L.stored = R.lr.stored; L.skipped = R.lr.skipped; L.closedStored = R.lr.closedStored;
+            L.last = R.lr.last;
+            L.on = true;
+        }
+        A.begun = true;
+        A.active = R.adapt.active;
+    }
+    HIPCHK(hipStreamSynchronize(st));                        // (the caller's blob is free again on return)
+    HIPCHK(hipGetLastError());
+    ctx->lfHaveGrad = false;
+    C.gen = ctx->stateGen;
+    C.active = true;
+    return 0;
+}
+
+int hmcmt_chain_restore(hmcmt_ctx* ctx, const void* buf, uint64_t bytes) {
+    const char* fn = "hmcmt_chain_restore";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!buf) { ctx->err = std::string(fn) + ": buf is NULL"; return HMCMT_EINVAL; }
+    int rc = chain_ready(ctx, fn, false);
+    if (rc) return rc;
+    if (!ctx->havePrior) { ctx->err = std::string(fn) + ": hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
+    BlobParsed P;
+    BlobChain R{};
+    std::string why;
+    if ((rc = blob_parse(buf, bytes, P, why))) { ctx->err = std::string(fn) + ": " + why; return rc; }
+    if ((rc = chain_blob_check(ctx, (const unsigned char*)buf, P, R))) return rc;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (a commit of the chain this one replaces may still be running)
+    chain_release(ctx);
+    if ((rc = chain_blob_build(ctx, R))) {                   // the context stays usable, without a chain
+        const std::string e = ctx->err;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipGetLastError();
+        chain_release(ctx);
+        ctx->err = e;
+        return rc;
+    }
+    return 0;
+}
+
 int hmcmt_chain_end(hmcmt_ctx* ctx) {
     if (!ctx) return HMCMT_EINVAL;
     if (ctx->statsPending) { ctx->err = "hmcmt_chain_end: an asynchronous evaluation is in flight (hmcmt_wait first)"; return HMCMT_EINVAL; }

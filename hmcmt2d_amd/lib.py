@@ -110,6 +110,13 @@ class AdaptLowrankInfo(C.Structure):
                 ("defect", C.c_double), ("host_ms", C.c_double)]
 
 
+class ChainBlobHeader(C.Structure):
+    """hmcmt_chain_blob_header (include/hmcmt.h): what hmcmt_chain_blob_info reports of a chain's checkpoint blob."""
+    _fields_ = [("version", C.c_uint32), ("nsections", C.c_uint32), ("total_bytes", C.c_uint64), ("nAC", C.c_int64), ("nData", C.c_int64),
+                ("mass_kind", C.c_int32), ("seeded", C.c_uint32), ("nsamples", C.c_int64), ("nmoments", C.c_int64),
+                ("tags", C.c_uint32 * 16), ("section_bytes", C.c_uint64 * 16)]
+
+
 def build_library(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -shared: cross-compiles without a GPU."""
     newest = max(os.path.getmtime(f) for f in SOURCES + HEADERS)
@@ -259,7 +266,11 @@ def load_library():
     lib.hmcmt_debug_nuts_leaf.restype = C.c_int
     lib.hmcmt_debug_nuts_iters.argtypes = [vp, c_int64_p, C.c_int32]
     lib.hmcmt_debug_nuts_iters.restype = C.c_int
-    for name in CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS:
+    lib.hmcmt_chain_save_size.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.hmcmt_chain_save.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.hmcmt_chain_restore.argtypes = [vp, vp, C.c_uint64]
+    lib.hmcmt_chain_blob_info.argtypes = [vp, C.c_uint64, C.POINTER(ChainBlobHeader)]
+    for name in CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
@@ -310,12 +321,14 @@ CHAIN_RNG_SYMBOLS = ["hmcmt_rng_draw", "hmcmt_rng_normals", "hmcmt_chain_seed", 
 # ... and the No-U-turn sampler on a seeded chain: the trajectory length chosen per sample
 CHAIN_NUTS_SYMBOLS = ["hmcmt_chain_nuts_sample", "hmcmt_chain_nuts_run", "hmcmt_rng_nuts"]
 NUTS_DEPTH_MAX = 10   # include/hmcmt.h: HMCMT_NUTS_DEPTH_MAX
+# ... and the chain's checkpoint: one blob out, one blob in, a blob's header without a device
+CHAIN_SAVE_SYMBOLS = ["hmcmt_chain_save_size", "hmcmt_chain_save", "hmcmt_chain_restore", "hmcmt_chain_blob_info"]
 NUTS_CK_MAX, NUTS_SUMS = 9, 21   # include/hmcmt_debug.h: HMCMT_NUTS_CK_MAX, HMCMT_NUTS_SUMS
 ADAPT_LOWRANK_KEYS = ("rank", "max_samples", "cutoff", "gamma")
 ADAPT_LOWRANK_NMIN, ADAPT_LOWRANK_NMAX = 4, 128   # include/hmcmt.h: max_samples of hmcmt_adapt_lowrank_options
 ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -376,6 +389,22 @@ def rng_normals(seed, stream, t, n, a0=0):
     if rc != 0:
         raise HmcmtError(rc, "hmcmt_rng_normals: need a0 >= 0, n >= 0 and a0 + n <= 2^31")
     return z
+
+
+def chain_blob_info(blob):
+    """The header of a chain's checkpoint blob (HipContext.chain_save) as a dict -- version, total_bytes, nAC, nData, mass_kind, seeded,
+    nsamples, nmoments, sections: [(tag, bytes)] in table order, the tags as four-character strings.  hmcmt_chain_blob_info: the
+    container is validated completely (magic, version, lengths, section table, checksum) on the host, no GPU needed; HmcmtError
+    (EINVAL) for anything that is no intact version-1 blob."""
+    lib = load_library()
+    blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
+    h = ChainBlobHeader()
+    rc = lib.hmcmt_chain_blob_info(blob.ctypes.data, blob.size, C.byref(h))
+    if rc != 0:
+        raise HmcmtError(rc, "hmcmt_chain_blob_info: not an intact chain blob of version 1")
+    out = {f: int(getattr(h, f)) for f in ("version", "total_bytes", "nAC", "nData", "mass_kind", "seeded", "nsamples", "nmoments")}
+    out["sections"] = [(int(h.tags[k]).to_bytes(4, "little").decode("ascii"), int(h.section_bytes[k])) for k in range(h.nsections)]
+    return out
 
 
 def adapt_lowrank_options(options):
@@ -875,6 +904,41 @@ class HipContext:
 
     def chain_end(self):
         self._check(self.lib.hmcmt_chain_end(self.h))
+
+    # -- checkpoint and resume (hmcmt_chain_save / hmcmt_chain_restore) ---------------------------
+    def chain_save_size(self):
+        """Bytes of the blob chain_save returns for the chain as it stands."""
+        n = C.c_uint64()
+        self._check(self.lib.hmcmt_chain_save_size(self.h, C.byref(n)))
+        return int(n.value)
+
+    def chain_save(self):
+        """The chain as one blob (uint8 array): state, moments, generator, the mass in force, every accumulator that is on, an
+        adaptation that was begun -- include/hmcmt.h has the format.  A read-out: the chain goes on as if it had not been called."""
+        blob = np.empty(self.chain_save_size(), dtype=np.uint8)
+        n = C.c_uint64()
+        self._check(self.lib.hmcmt_chain_save(self.h, blob.ctypes.data, blob.size, C.byref(n)))
+        assert n.value == blob.size
+        return blob
+
+    def chain_restore(self, blob):
+        """A chain from a blob of chain_save, in place of chain_begin and every accumulator's and adaptation's begin call (after
+        set_prior, and set_mass for a blob saved under HMCMT_MASS_WM).  No evaluation runs; the first sample behind it evaluates its
+        start gradient.  A blob that is refused (HmcmtError EINVAL) leaves a running chain untouched."""
+        blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, dtype=np.uint8)
+        self._check(self.lib.hmcmt_chain_restore(self.h, blob.ctypes.data, blob.size))
+        # the shapes the read-outs of this binding allocate by: what the begin calls would have noted (the blob has passed the library)
+        table = chain_blob_info(blob)["sections"]
+        at = 64 + 24 * len(table)
+        for tag, nbytes in table:
+            head = blob[at:at + 24].view(np.int64)
+            if tag == "HIST":
+                self._hist_shape = (int(head[0]), int(head[1]))
+            elif tag == "ACOV":
+                self._acov_shape = (int(head[2]) + 1, int(head[0]))
+            elif tag == "COV ":
+                self._cov_shape = (int(head[0]), self.nAC)
+            at += nbytes
 
     # -- the chain's own random numbers (hmcmt_chain_seed, hmcmt_chain_sample, hmcmt_chain_run) ----
     def chain_seed(self, seed, stream=0):

@@ -768,6 +768,18 @@ class ChainOutput:
         if unknown:
             raise ValueError(f"runHMCSampler: {self.name} has no key {sorted(unknown)} ({', '.join(self.keys)})")
 
+    # chain_checkpoint=: `dump(state)` is the host state as a dict of arrays and strings for the file (the library's part is in the
+    # blob), `resume(ctx, value, env, saved)` the state behind HipContext.chain_restore, in place of begin -- it makes no begin call.
+    # An output whose state follows from its value alone needs neither: its `plan(value, env)` is the state, and begin adds the call.
+    def dump(self, state):
+        return {}
+
+    def resume(self, ctx, value, env, saved):
+        return self.plan(value, env)
+
+    def plan(self, value, env):
+        return None
+
 
 def _cells(given, nparam=None):
     """a keyword's list of active cells as the library takes it; None: every cell (spelled out where nparam is given)"""
@@ -784,9 +796,12 @@ class _Histograms(ChainOutput):
     histToLog10Rho, mergeHistograms, fileio.writeSitePPD, fileio.getPosteriorQuantileModels."""
     name, field, keys, why = "hist", "hist", ("targets", "nbins", "lo", "hi"), "it is streamed in the device chain's commit"
 
-    def begin(self, ctx, value, env):
+    def plan(self, value, env):
         targets = _cells(value.get("targets"), env.nparam)
-        bins = (int(value.get("nbins", 300)), float(value.get("lo", env.lo)), float(value.get("hi", env.hi)))
+        return (int(value.get("nbins", 300)), float(value.get("lo", env.lo)), float(value.get("hi", env.hi))), targets
+
+    def begin(self, ctx, value, env):
+        bins, targets = self.plan(value, env)
         ctx.chain_hist_begin(targets, *bins)
         return bins, targets
 
@@ -814,8 +829,11 @@ class _EffectiveSampleSize(ChainOutput):
     data misfit of the counted samples.  A chain that ends inside its burn-in gives count 0 and None for the rest.  See acovOf, essFromAcov, mcseOfMean, mergeAcov, fileio.getESSModel.  The draws keep their order."""
     name, field, keys, why = "ess", "ess", ("targets", "maxlag"), "the autocovariances are streamed in the device chain's commit"
 
+    def plan(self, value, env):
+        return _cells(value.get("targets")), int(value.get("maxlag", 63))
+
     def begin(self, ctx, value, env):
-        targets, maxlag = _cells(value.get("targets")), int(value.get("maxlag", 63))
+        targets, maxlag = self.plan(value, env)
         ctx.chain_acov_begin(targets, maxlag)
         return targets, maxlag
 
@@ -843,8 +861,11 @@ class _Covariance(ChainOutput):
     its burn-in gives count 0 and None for the rest.  See covOf, mergeCov, fileio.getCorrelationModel.  The draws keep their order."""
     name, field, keys, why = "cov", "cov", ("rows", "batch"), "the cross moments are streamed in the device chain's commit"
 
+    def plan(self, value, env):
+        return _cells(value.get("rows"))
+
     def begin(self, ctx, value, env):
-        rows = _cells(value.get("rows"))
+        rows = self.plan(value, env)
         ctx.chain_cov_begin(rows, int(value.get("batch", 0)))
         return rows
 
@@ -893,6 +914,18 @@ class _WarmUp(ChainOutput):
                 if row["windows"] > len(state["lowrank"]):                        # (a window of fewer than two samples closes nothing)
                     state["lowrank"].append(row)
 
+    def dump(self, state):
+        import json
+        return {"dt": state["dt"], "alpha": state["alpha"], "windows": np.array(state["windows"], dtype=np.int64).reshape(-1, 2),
+                "info": np.array(json.dumps(state["info"])), "lowrank": np.array(json.dumps(state["lowrank"]))}
+
+    def resume(self, ctx, value, env, saved):
+        import json
+        nwarmup, opts = adaptPlan(value, env.hmcprior)
+        return {"nwarmup": nwarmup, "mass": opts["adapt_mass"], "info": json.loads(str(saved["info"])), "dt": saved["dt"].copy(),
+                "alpha": saved["alpha"].copy(), "windows": [tuple(int(v) for v in w) for w in saved["windows"]],
+                "lowrank": json.loads(str(saved["lowrank"]))}
+
     def read(self, ctx, state, stats, env):
         out = {"nwarmup": state["nwarmup"], "dt": state["dt"], "alpha": state["alpha"], "dt_final": state["info"]["dt"],
                "invM": ctx.chain_mass_diag() if state["mass"] else None, "windows": state["windows"]}
@@ -921,6 +954,91 @@ def _check_mass_lowrank(mass_lowrank, nparam):
     if not (np.isfinite(invM).all() and (invM > 0).all() and np.isfinite(lam).all() and (lam > 0).all() and np.isfinite(U).all()):
         raise ValueError("runHMCSampler: mass_lowrank needs finite positive invM and lam and a finite U")
     return invM, ((invM, U, lam) if U.shape[0] else None)
+
+
+def _chain_fingerprint(invParam, hmcprior, nparam, outputs, invM, mass_lowrank, library_rng, nuts):
+    """What a chain_checkpoint file belongs to: _run_fingerprint's run (sizes, sampler settings, data, weights, reference model) and the
+    device chain's keywords -- the burn-in, library_rng, nuts, every output's value, invM / mass_lowrank."""
+    import hashlib
+
+    def canon(v):
+        if isinstance(v, dict):
+            return "{" + ",".join(f"{k!r}:{canon(v[k])}" for k in sorted(v)) + "}"
+        if isinstance(v, (list, tuple)) and not all(isinstance(x, (bool, int, float, np.integer, np.floating)) for x in v):
+            return "[" + ",".join(canon(x) for x in v) + "]"
+        if isinstance(v, (list, tuple, np.ndarray)):         # numbers: a list and an array of the same values are the same keyword
+            a = np.asarray(v)
+            a = np.ascontiguousarray(a, dtype=np.int64 if a.dtype.kind in "biu" else np.float64)
+            return f"<{a.dtype.str}{a.shape}{hashlib.sha256(a.tobytes()).hexdigest()}>"
+        if isinstance(v, (bool, np.bool_)):
+            return repr(bool(v))
+        if isinstance(v, (int, np.integer)):
+            return repr(int(v))
+        if isinstance(v, (float, np.floating)):
+            return repr(float(v))
+        return repr(v)
+
+    h = hashlib.sha256()
+    h.update(_run_fingerprint(invParam, hmcprior, (nparam, hmcprior.totalsamples)).encode())
+    h.update(canon({"burnin": int(hmcprior.burninsamples), "library_rng": library_rng, "nuts": nuts, "outputs": outputs, "invM": invM,
+                    "mass_lowrank": mass_lowrank}).encode())
+    return h.hexdigest()
+
+
+class _ChainCheckpoint:
+    """runHMCSampler's chain_checkpoint=path, chain_checkpoint_every=k: ONE file, replaced atomically behind every k-th sample and
+    behind the last (tmp file, flush, fsync, os.replace, as _save_checkpoint does).  It holds the library's blob
+    (HipContext.chain_save), the host's part -- sample index, hmstats, acceptstats, the counters, the first column of hmcdata, the NUTS
+    records, every output's host state (ChainOutput.dump), for the host-fed loop the numpy generator's state in front of the next
+    momentum's draw, for the seeded loop the current state's D and M (the next column of hmstats) -- and the run's fingerprint."""
+
+    def __init__(self, path, every, fingerprint):
+        self.path, self.every, self.fingerprint = path, int(every), fingerprint
+
+    def due(self, it, nsamples):
+        return it == nsamples or (self.every > 0 and it % self.every == 0)
+
+    def save(self, ctx, it, stats, hmcprior, data0, begun, rng_state=None, energy=(0.0, 0.0)):
+        import json
+        import os
+        fields = {"blob": ctx.chain_save(), "it": it, "data0": data0, "hmstats": stats.hmstats[:, :it + 1], "acceptstats": stats.acceptstats[:it],
+                  "counts": np.array([stats.nAccept, stats.nReject, hmcprior.nfevals]), "fingerprint": np.array(self.fingerprint),
+                  "rng": np.array(json.dumps(rng_state)), "energy": np.array(energy, dtype=np.float64)}
+        if stats.nuts is not None:
+            fields.update({f"nuts_{f}": stats.nuts[f][:it] for f, _ in NUTS_FIELDS})
+        for out, state in begun:
+            fields.update({f"out_{out.name}_{k}": v for k, v in out.dump(state).items()})
+        tmp = self.path + ".tmp"
+        with open(tmp, "wb") as f:
+            np.savez(f, **fields)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, self.path)
+
+    def load(self):
+        """The file's fields as a dict, or None where there is no file; ValueError for a file of another run."""
+        import os
+        if not os.path.exists(self.path):
+            return None
+        with np.load(self.path) as g:
+            if "fingerprint" not in g.files or str(g["fingerprint"]) != self.fingerprint:
+                raise ValueError(f"{self.path}: chain checkpoint of a different run (sizes, dt / timestep / regParam / sigBounds, burn-in, data, "
+                                 "weights, reference model, library_rng, nuts, an output's value, invM or mass_lowrank differ)")
+            return {k: g[k] for k in g.files}
+
+    def restore(self, ctx, g, stats, hmcprior, begun_of):
+        """The chain and the host's part from a loaded file: returns (it, the outputs' states, the generator's state or None, (D, M))."""
+        import json
+        ctx.chain_restore(g["blob"])
+        it = int(g["it"])
+        stats.hmstats[:, :it + 1] = g["hmstats"]
+        stats.acceptstats[:it] = g["acceptstats"]
+        stats.nAccept, stats.nReject, hmcprior.nfevals = (int(c) for c in g["counts"])
+        if stats.nuts is not None:
+            for f, _ in NUTS_FIELDS:
+                stats.nuts[f][:it] = g[f"nuts_{f}"]
+        begun = begun_of(lambda out: {k[len(f"out_{out.name}_"):]: v for k, v in g.items() if k.startswith(f"out_{out.name}_")})
+        return it, begun, json.loads(str(g["rng"])), tuple(float(v) for v in g["energy"])
 
 
 def _homogeneous_start(invParam, rhoref, rng, verbose):
@@ -983,26 +1101,30 @@ def _check_nuts(nuts, hmcprior, library_rng):
     return depth
 
 
-def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, start, nuts=None):
+def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, start, nuts=None, first=0, flush=None):
     """The loop of _run_device_chain with the library's own random numbers (library_rng = (seed, stream)): chain_seed, then the samples
     through chain_run -- one call for the whole run, blocks of LIBRARY_RNG_BLOCK with verbose (the lines of a block are printed behind
     it), single samples where an output watches every step.  Column `it` of hmstats takes its K from the record of sample it + 1 (K0
     is the kinetic energy of the momentum that sample drew); the last column's is the next draw's, read back through chain_normals and
     chain_momentum, which leaves the generator where it is.  nuts (a max_depth): the samples are NUTS samples through chain_nuts_run
-    -- hmcprior.timestep is not used --, and stats.nuts takes their tree records."""
-    ctx.chain_seed(*library_rng)
-    if nuts is not None:
-        stats.nuts = {"max_depth": nuts, **{f: np.zeros(hmcprior.totalsamples, dtype=t) for f, t in NUTS_FIELDS}}
+    -- hmcprior.timestep is not used --, and stats.nuts takes their tree records (made by the caller).  first > 0: a chain restored
+    behind sample `first`, seed included, with `start` its D and M there.  flush = (due(it), save(it)): a block ends where a
+    checkpoint is due, and the file is written behind it."""
+    if first == 0:
+        ctx.chain_seed(*library_rng)
     nsamples = hmcprior.totalsamples
     Lmin, Lmax = int(hmcprior.timestep[0]), int(hmcprior.timestep[1])
     block = 1 if watching else (LIBRARY_RNG_BLOCK if verbose else max(nsamples, 1))
     D, M = start
-    it = 0
+    it = first
     while it < nsamples:
+        n = min(block, nsamples - it)
+        if flush is not None:
+            n = next(k for k in range(1, n + 1) if k == n or flush[0](it + k))
         if nuts is not None:
-            recs, models, preds = ctx.chain_nuts_run(min(block, nsamples - it), nuts, outputs=keep_samples)
+            recs, models, preds = ctx.chain_nuts_run(n, nuts, outputs=keep_samples)
         else:
-            recs, models, preds = ctx.chain_run(min(block, nsamples - it), Lmin, Lmax, outputs=keep_samples)
+            recs, models, preds = ctx.chain_run(n, Lmin, Lmax, outputs=keep_samples)
         for k, rec in enumerate(recs):
             if nuts is not None:
                 for f, _ in NUTS_FIELDS:
@@ -1023,6 +1145,8 @@ def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watchin
             if keep_samples:
                 hmcmodel[:, it - 1] = models[k]
                 hmcdata[:, it] = preds[k] if rec["accepted"] else hmcdata[:, it - 1]
+        if flush is not None and flush[0](it):
+            flush[1](it, None, (D, M))
     seed, stream, t = ctx.chain_rng_state()
     K = ctx.chain_momentum(ctx.chain_normals(t))             # (host-fed: t stays)
     stats.hmstats[:, nsamples] = [D, M, K, D + M + K]
@@ -1030,12 +1154,13 @@ def _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watchin
 
 
 def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank=None,
-                      library_rng=None, nuts=None):
+                      library_rng=None, nuts=None, chain_checkpoint=None, chain_checkpoint_every=0):
     """runHMCSampler's loop through the chain API of the library (hmcmt_chain_*): model, momentum, predicted data and the posterior
     moments stay on the GPU; per sample nparam normals go up and one record comes back (plus the sample, with keep_samples).
     Draws from `rng` in the host loop's order: the first momentum's normals, rhoref; per sample L, u, the next momentum's normals.
     `outputs`: keyword -> value of the entries of CHAIN_OUTPUTS that are on.  `mass_lowrank`: checked (invM, U, lam) with at least one
-    direction, set behind the prior."""
+    direction, set behind the prior.  `chain_checkpoint`: the file of _ChainCheckpoint; where it exists the chain is restored from it
+    (HipContext.chain_restore in place of both chain_begins and the outputs' begins) and the loop goes on behind the saved sample."""
     from types import SimpleNamespace
     from .lib import HMCMT_MASS_WM
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
@@ -1053,32 +1178,55 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
     if mass_lowrank is not None:
         ctx.set_mass_lowrank(None, mass_lowrank[1], mass_lowrank[2])      # (the scales: the prior's invM, set just above)
     lo, hi = np.log(hmcprior.sigBounds[0]), np.log(hmcprior.sigBounds[1])
-    # the reference takes its first Hamiltonian at the homogeneous model (:100-112) and its first trajectory from the file's
-    startD, startM = ctx.chain_begin(strModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
-    predStart = ctx.chain_state()[2]
-    if not np.array_equal(fileModel, strModel):
-        ctx.chain_begin(fileModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
-        ctx.chain_set_energy(startD, startM)
     nsamples = hmcprior.totalsamples
     env = SimpleNamespace(nparam=nparam, lo=lo, hi=hi, nsamples=nsamples, hmcprior=hmcprior)
-    # (behind the second begin: a begin ends the accumulators)
-    begun = [(out, out.begin(ctx, outputs[out.name], env)) for out in CHAIN_OUTPUTS if out.name in outputs]
-    watching = [(out, state) for out, state in begun if out.step is not None]
     nkeep = nsamples if keep_samples else 0
     hmcmodel = np.zeros((nparam, nkeep))
     hmcdata = np.zeros((ndata, nkeep + 1), dtype=np.complex128)
-    hmcdata[:, 0] = predStart
     stats: HMCStatus = initHMCStatus(nsamples)
+    if nuts is not None:
+        stats.nuts = {"max_depth": nuts, **{f: np.zeros(nsamples, dtype=t) for f, t in NUTS_FIELDS}}
+    on = [out for out in CHAIN_OUTPUTS if out.name in outputs]
+    ck = saved = None
+    if chain_checkpoint:
+        ck = _ChainCheckpoint(chain_checkpoint, chain_checkpoint_every,
+                              _chain_fingerprint(invParam, hmcprior, nparam, outputs, invM, mass_lowrank, library_rng, nuts))
+        saved = ck.load()
+    first, rng_state = 0, None
+    if saved is not None:
+        first, begun, rng_state, energy = ck.restore(ctx, saved, stats, hmcprior,
+                                             lambda state_of: [(out, out.resume(ctx, outputs[out.name], env, state_of(out))) for out in on])
+        hmcdata[:, 0] = saved["data0"]
+        if verbose:
+            print(f"resuming the device chain behind sample {first} of {nsamples} ({chain_checkpoint})")
+    else:
+        # the reference takes its first Hamiltonian at the homogeneous model (:100-112) and its first trajectory from the file's
+        startD, startM = ctx.chain_begin(strModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
+        hmcdata[:, 0] = ctx.chain_state()[2]
+        if not np.array_equal(fileModel, strModel):
+            ctx.chain_begin(fileModel, hmcprior.dt, hmcprior.regParam, lo, hi, burnin=hmcprior.burninsamples)
+            ctx.chain_set_energy(startD, startM)
+        # (behind the second begin: a begin ends the accumulators)
+        begun = [(out, out.begin(ctx, outputs[out.name], env)) for out in on]
+    watching = [(out, state) for out, state in begun if out.step is not None]
+    flush = None if ck is None else ((lambda it: ck.due(it, nsamples)),
+                                     (lambda it, state, energy=(0.0, 0.0): ck.save(ctx, it, stats, hmcprior, hmcdata[:, 0], begun, state, energy)))
     if library_rng is not None:
         # (z, drawn above so that rhoref is the draw it is without the keyword, is not used: every momentum is the library's)
-        _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, (startD, startM), nuts)
+        start = (startD, startM) if first == 0 else energy
+        _run_seeded_chain(ctx, hmcprior, library_rng, verbose, keep_samples, watching, stats, hmcmodel, hmcdata, start, nuts, first, flush)
         stats.moments = ctx.chain_moments()
         for out, state in begun:
             setattr(stats, out.field, out.read(ctx, state, stats, env))
         return hmcmodel, stats, hmcdata
-    startK = ctx.chain_momentum(z)
-    stats.hmstats[:, 0] = [startD, startM, startK, startD + startM + startK]
-    for it in range(1, nsamples + 1):
+    if first == 0:
+        startK = ctx.chain_momentum(z)
+        stats.hmstats[:, 0] = [startD, startM, startK, startD + startM + startK]
+    else:
+        # the momentum of sample first + 1, drawn again from the generator's state in front of it: column `first` holds its K already
+        rng.bit_generator.state = rng_state
+        ctx.chain_momentum(rng.standard_normal(nparam))
+    for it in range(first + 1, nsamples + 1):
         L = int(rng.integers(hmcprior.timestep[0], hmcprior.timestep[1] + 1))
         u = rng.random()
         rec, model, pred = ctx.chain_step(L, u, outputs=keep_samples)
@@ -1092,11 +1240,14 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
             stats.nReject += 1
         if verbose:
             print(_sample_line(it, rec))
+        rng_state = rng.bit_generator.state if flush is not None and flush[0](it) else None
         startK = ctx.chain_momentum(rng.standard_normal(nparam))
         stats.hmstats[:, it] = [rec["D"], rec["M"], startK, rec["D"] + rec["M"] + startK]
         if keep_samples:
             hmcmodel[:, it - 1] = model
             hmcdata[:, it] = pred if rec["accepted"] else hmcdata[:, it - 1]      # (:164-168: a rejection repeats the column)
+        if rng_state is not None:
+            flush[1](it, rng_state)
     stats.moments = ctx.chain_moments()
     for out, state in begun:
         setattr(stats, out.field, out.read(ctx, state, stats, env))
@@ -1106,7 +1257,8 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
                   checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
-                  cov=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None, nuts=None):
+                  cov=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None, nuts=None, chain_checkpoint=None,
+                  chain_checkpoint_every=0):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
 
@@ -1114,8 +1266,21 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     the random numbers are drawn here in the same order, so a seed gives the same chain as the host loop to solver tolerance.
     hmcstats.moments = (count, mean, m2) then holds the streaming posterior moments of the samples behind hmcprior.burninsamples
     (fileio.getPosteriorModelFromMoments).  `keep_samples=False` (with device_chain): no sample comes back -- hmcmodel has zero
-    columns and hmcdata its first column only; the moments are the result.  Checkpointing is not available with device_chain
-    (ValueError): the warm-start history of the solves is part of a device chain's state.
+    columns and hmcdata its first column only; the moments are the result.  `checkpoint=` is refused with device_chain (ValueError):
+    a device chain is checkpointed with `chain_checkpoint=`.
+
+    `chain_checkpoint=path`, `chain_checkpoint_every=k` (with device_chain and keep_samples=False): behind every k-th sample and
+    behind the last, ONE file is replaced atomically.  It holds the library's blob of the chain (hmcmt_chain_save, include/hmcmt.h:
+    state, moments, generator, the mass in force, every accumulator, the warm-up), the host's part (sample index, hmstats, acceptstats,
+    the counters, the NUTS records, the outputs' host state, the numpy generator's state) and the run's fingerprint.  If the file
+    exists when the sampler starts, the chain RESUMES behind the saved sample (hmcmt_chain_restore: no evaluation; the first resumed
+    sample evaluates its start gradient, so hmcprior.nfevals is one more per resume) and draws the numbers the uninterrupted run
+    would have -- both loops, host-fed and library_rng, with and without nuts.  The resumed chain is the uninterrupted one bit for
+    bit on a context whose gradient is a function of the model alone (warm_start "cold", a fixed sweep count), else to solver
+    tolerance: its first solves start cold.  A file of a different run -- _run_fingerprint's run, or another burn-in, library_rng,
+    nuts, output value, invM or mass_lowrank -- is refused (ValueError), and so is the keyword with keep_samples=True: a sample
+    history belongs to the host loop's `checkpoint=`.  A flush waits for the chain and writes the whole blob: choose k by the
+    blob's size.
     The optional outputs of the device chain -- hist=, data_moments=, ess=, cov=, adapt= -- are one entry of CHAIN_OUTPUTS each, and
     each entry's docstring is its paragraph here:
     {CHAIN_OUTPUTS}
@@ -1151,7 +1316,11 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     timestep, regParam, sigBounds, data, weights or reference model -- is refused."""
     _check_solver(hmcprior)
     if device_chain and checkpoint:
-        raise ValueError("runHMCSampler: checkpoint is not available with device_chain=True (use the host loop or device_leapfrog=True)")
+        raise ValueError("runHMCSampler: checkpoint is not available with device_chain=True (use the host loop or device_leapfrog=True; "
+                         "a device chain with keep_samples=False is checkpointed with chain_checkpoint=)")
+    if chain_checkpoint and not (device_chain and not keep_samples):
+        raise ValueError("runHMCSampler: chain_checkpoint needs device_chain=True and keep_samples=False (a sample history belongs to the "
+                         "host loop's checkpoint=)")
     if not keep_samples and not device_chain:
         raise ValueError("runHMCSampler: keep_samples=False needs device_chain=True (only the device chain streams the posterior moments)")
     # (every refusal before the context is touched and the first number is drawn)
@@ -1188,7 +1357,7 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     ctx = ctx or get_context(mtMesh, mtData, invParam, device_id=device_id)
     if device_chain:
         return _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verbose, keep_samples, outputs, invM, mass_lowrank,
-                                 library_rng, nuts)
+                                 library_rng, nuts, chain_checkpoint, chain_checkpoint_every)
     nparam, ndata = len(invParam.strModel), len(invParam.obsData)
     cur = initHMCParameter(nparam)
     diagonal = hmcprior.massType == "diagonal"             # (:80-86)
@@ -1300,7 +1469,7 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     `gather="library"`: the sample blocks are all-gathered by the library's own RCCL entry point
     (hmcmt_allgather_samples, include/hmcmt.h -- what a non-Python host would call) instead of torch's; the process
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
-    Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` becomes
+    Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` and `chain_checkpoint=path` become
     `path.chain<k>` per chain; device_chain=True, keep_samples=False and the device chain's optional outputs).  What those outputs
     fill -- every HMCStatus field of CHAIN_OUTPUTS -- is not gathered: it stays with the chain on the chain's own rank.
     `library_rng=True` (with device_chain=True): chain c draws its numbers in the library as stream c of `seed`,
@@ -1359,8 +1528,9 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                 ctx_c = context_factory(mesh_c, mtData, inv_c, dev_id) if context_factory is not None else \
                     get_context(mesh_c, mtData, inv_c, device_id=dev_id, **ctx_kw)
                 kw = dict(sampler_kw)
-                if kw.get("checkpoint"):                        # one checkpoint file per chain
-                    kw["checkpoint"] = f"{kw['checkpoint']}.chain{c + 1}"
+                for key in ("checkpoint", "chain_checkpoint"):  # one checkpoint file per chain
+                    if kw.get(key):
+                        kw[key] = f"{kw[key]}.chain{c + 1}"
                 if kw.get("library_rng") is True:               # the library's generator: chain c is stream c of the run's seed
                     kw["library_rng"] = (int(seed), c)
                 model, stats, data = runHMCSampler(mesh_c, mtData, inv_c, prior_c, rng, ctx=ctx_c, **kw)

@@ -604,6 +604,84 @@ extern int hmcmt_chain_nuts_run(hmcmt_ctx* ctx, int64_t nsamples, int32_t max_de
                                 double* preds, int64_t* done);
 extern int hmcmt_rng_nuts(uint64_t seed, uint32_t stream, uint64_t t, int32_t kind, uint32_t index, int32_t* forward, double* u);
 
+/* Checkpoint and resume of a chain: everything a chain holds on the device and in the library -- state, moments, generator, the mass
+ * in force, every accumulator that is on, an adaptation that was begun -- as one blob in host memory, and a chain made from such a blob.
+ *   hmcmt_chain_save_size   *bytes = what hmcmt_chain_save writes for the chain as it stands
+ *   hmcmt_chain_save      on a live chain, at any point between two samples.  It waits for the stream and copies into buf; *written
+ *                         (may be NULL) = the blob's length.  capacity too small: HMCMT_EINVAL, *written = the size needed, nothing
+ *                         written.  It is a read-out that changes NOTHING, parked cross-moment commits included (they are saved as
+ *                         they are parked): a chain saved behind every sample gives the bits of one never saved, and two saves in a
+ *                         row give the same bytes
+ *   hmcmt_chain_restore   takes the place of hmcmt_chain_begin and of every accumulator's and adaptation's begin call.  It needs
+ *                         hmcmt_set_prior, a context of the blob's nAC and nData and, for a blob saved under HMCMT_MASS_WM, a context
+ *                         already on that mass (hmcmt_set_mass).  It runs NO evaluation: D, M and the predicted data are the blob's.
+ *                         The blob's mass is installed as hmcmt_chain_set_mass_diag / hmcmt_chain_set_mass_lowrank install theirs (the
+ *                         stored directions are not checked for orthonormality again) and is the context's from then on.  A chain that
+ *                         is running is replaced whole, with the accumulators it had and the blob has not.  The blob is validated
+ *                         completely before anything changes -- container (below), sizes, the mass kind, every range the begin calls
+ *                         check --: HMCMT_EINVAL leaves a running chain untouched.  HMCMT_ENOMEM / HMCMT_EHIP leave the context usable,
+ *                         without a chain.  Which run a blob belongs to (data, weights, reference model) the library does not know: it
+ *                         checks sizes and kinds only
+ *   hmcmt_chain_blob_info validates a blob's container without a context or a device and reports the header's fields, the sections'
+ *                         tags and lengths in table order
+ * NOT in a blob, so not restored: a momentum already drawn (a seeded chain draws its own, a host-fed one is drawn again:
+ * hmcmt_chain_step without hmcmt_chain_momentum is refused); the gradient on the device -- the first sample behind a restore evaluates
+ * its start gradient, so its nfevals is one more than the uninterrupted run's, the ONLY difference in its record; the NUTS tree's
+ * buffers (allocated again by the first NUTS sample); the solver's warm-start history, sweep choice and queue tables; timers, profiles
+ * and debug counters.  On a context whose gradient is a function of the model alone (warm_start cold, a fixed sweep count) the chain
+ * behind a restore continues the saved one bit for bit.
+ * HMCMT_EINVAL: NULL argument; save / save_size: no chain, a call between hmcmt_grad_device_async and hmcmt_wait.
+ *
+ * The container.  Little-endian throughout; every offset and length is a multiple of 8.
+ *     0   char[8]  "HMCMTCK\0"
+ *     8   uint32   version = 1 (any other is refused)        12  uint32  nsections (<= 16)
+ *     16  uint64   total bytes, the checksum included
+ *     24  int64    nAC                                       32  int64   nData
+ *     40  int32    mass kind (HMCMT_MASS_*)                  44  uint32  seeded (0 / 1)
+ *     48  int64    nsamples                                  56  int64   nmoments
+ *     64  nsections x { uint32 tag; uint32 0; uint64 offset; uint64 bytes }
+ *         the payloads, in table order, contiguous: the first at 64 + 24 nsections, each at the end of the one before
+ *     end uint64   checksum: h = 0xcbf29ce484222325; for every preceding 8-byte word w, in order: h = (h ^ w) * 0x100000001b3 (mod 2^64)
+ * A tag is four characters read as a little-endian uint32 ("CHAN" = 0x4e414843).  CHAN and MASS are always there, in this order; then,
+ * each iff its part is on or was begun, HIST, DMOM, ACOV, "COV ", ADPT, ADLR (ADLR only with ADPT).  No tag repeats.
+ * The payloads: scalars first, 8 bytes each (i = int64, f = double, u = uint64), then arrays of doubles (unless said otherwise) in the
+ * device's layout.
+ *   CHAN  f dt, regParam, lnSigMin, lnSigMax, D, M;  i burnin, nsamples, nmoments;  u seed, t;  uint32 stream, seeded;
+ *         m[nAC], pred[2 nData], mean[nAC], m2[nAC]  (the current model, its predicted data, the Welford pair of the moments)
+ *   MASS  i kind, rank (0 unless HMCMT_MASS_LOWRANK), cap (directions the low-rank buffers have room for; 0: none), given (1: the
+ *         scales hmcmt_set_mass_lowrank was given follow);  under HMCMT_MASS_WM nothing more (Wm and its factor are the prior's);
+ *         else invM[nAC] (the diagonal as it stands);  then under HMCMT_MASS_LOWRANK s[nAC], U[rank][nAC], lambda[rank] (the bits
+ *         that were given or estimated);  then, given = 1, invM0[nAC]
+ *   HIST  i ntarget, nbins, count;  f lo, hi;  int64 target[ntarget];  uint32 counts[nbins][ntarget] (bin-major), zero-padded to 8
+ *   DMOM  i count;  mean[2 nData], m2[2 nData]
+ *   ACOV  i ntarget, all (1: every cell, no list), K = maxlag, count;  all = 0: int64 target[ntarget];  x0[ntarget], tot[ntarget],
+ *         S[K + 1][ntarget], H[K + 1][ntarget], ring[K + 1][ntarget]
+ *   COV   i nrow, all, B = batch, count, npend (commits parked);  all = 0: int64 row[nrow];  x0[nAC], tot[nAC], q[nAC],
+ *         pend[npend][nAC], S[nrow][nAC]
+ *   ADPT  i nwarmup, adapt_mass, init_buffer, term_buffer, base_window;  f delta, gamma, t0, kappa, dt_min, dt_max  (the options);
+ *         f mu, s_bar, x_bar, x;  i t  (the dual averaging);  i c (steps adapted), wcount, wnext, wsize, windows_done;
+ *         f alpha_last, alpha_sum;  i begun (1), active;  adapt_mass = 1: mean[nAC], m2[nAC] (the open window's Welford pair)
+ *   ADLR  i rank, max_samples;  f cutoff, gamma  (the options);  i win_start, stride, stored, skipped, closed_stored, rows;
+ *         the last closed window's info: i windows, stored, skipped, dims, rank, fallback, stride;  f theta_min, theta_max, defect,
+ *         host_ms;  X[rows][nAC], G[rows][nAC] (rows = stored, or closed_stored while the open window is empty: the rows a later
+ *         call can still read) */
+#define HMCMT_BLOB_VERSION 1
+#define HMCMT_BLOB_SECTIONS_MAX 16
+typedef struct hmcmt_chain_blob_header {
+    uint32_t version, nsections;
+    uint64_t total_bytes;
+    int64_t  nAC, nData;
+    int32_t  mass_kind;
+    uint32_t seeded;
+    int64_t  nsamples, nmoments;
+    uint32_t tags[HMCMT_BLOB_SECTIONS_MAX];            /* in table order; 0 behind the last */
+    uint64_t section_bytes[HMCMT_BLOB_SECTIONS_MAX];
+} hmcmt_chain_blob_header;
+extern int hmcmt_chain_save_size(hmcmt_ctx* ctx, uint64_t* bytes);
+extern int hmcmt_chain_save(hmcmt_ctx* ctx, void* buf, uint64_t capacity, uint64_t* written);
+extern int hmcmt_chain_restore(hmcmt_ctx* ctx, const void* buf, uint64_t bytes);
+extern int hmcmt_chain_blob_info(const void* buf, uint64_t bytes, hmcmt_chain_blob_header* out);
+
 /* Solution fields of the last evaluation THAT RAN (a call answered from the stored results runs nothing) in the
  * reference's layout: complex[(ny+1)*(nz+1)*nFreq],
  * node index (iz*(ny+1)+iy) fastest, then frequency (MT2DFwdSolver.jl:111-112).  adjoint=1 returns

@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, chain_adapt_lowrank!, chain_adapt_lowrank_info, chain_set_mass_lowrank!, chain_mass_lowrank, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chain_save, chain_restore!, chain_blob_info, HmcmtChainBlobHeader, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -554,6 +554,59 @@ chainSetEnergy!(ctx::HipContext, D::Real, M::Real) =
     checkerr(ctx.ptr, ccall((:hmcmt_chain_set_energy, libhmcmt), Cint, (Ptr{Cvoid}, Float64, Float64), ctx.ptr, Float64(D), Float64(M)))
 
 chainEnd!(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_chain_end, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
+
+# field order and types of hmcmt_chain_blob_header (include/hmcmt.h; checked by tests/test_checkpoint_host.py against the ctypes mirror)
+struct HmcmtChainBlobHeader
+    version::UInt32
+    nsections::UInt32
+    total_bytes::UInt64
+    nAC::Int64
+    nData::Int64
+    mass_kind::Int32
+    seeded::UInt32
+    nsamples::Int64
+    nmoments::Int64
+    tags::NTuple{16,UInt32}
+    section_bytes::NTuple{16,UInt64}
+end
+
+"""
+    chain_save(ctx) -> Vector{UInt8};  chain_restore!(ctx, blob);  chain_blob_info(blob) -> NamedTuple
+
+Checkpoint and resume of the chain (hmcmt_chain_save, hmcmt_chain_restore, hmcmt_chain_blob_info; include/hmcmt.h has the blob's format
+to the byte).  `chain_save` is a read-out: state, moments, generator, the mass in force, every accumulator that is on and an adaptation
+that was begun, as one blob; the chain goes on as if it had not been called.  `chain_restore!` comes behind `setPrior!` (and the mass
+call for M = Wm) IN PLACE OF `chainBegin!` and every accumulator's and adaptation's begin call; it evaluates nothing, and the first
+sample behind it evaluates its start gradient (one evaluation more in its record).  A momentum is not restored: a host-fed chain calls
+`chainMomentum!` again.  `chain_blob_info` validates a blob's container without a context or a GPU: the header's fields and
+`sections`, the (tag, bytes) pairs in table order.
+"""
+function chain_save(ctx::HipContext)
+    n = Ref{UInt64}(0)
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_chain_save_size(ctx.ptr::Ptr{Cvoid}, n::Ref{UInt64})::Cint)
+    blob = Vector{UInt8}(undef, n[])
+    written = Ref{UInt64}(0)
+    rc = GC.@preserve blob @ccall libhmcmt.hmcmt_chain_save(ctx.ptr::Ptr{Cvoid}, pointer(blob)::Ptr{UInt8}, UInt64(length(blob))::UInt64,
+                                                            written::Ref{UInt64})::Cint
+    checkerr(ctx.ptr, rc)
+    return blob
+end
+
+function chain_restore!(ctx::HipContext, blob::Vector{UInt8})
+    rc = GC.@preserve blob @ccall libhmcmt.hmcmt_chain_restore(ctx.ptr::Ptr{Cvoid}, pointer(blob)::Ptr{UInt8}, UInt64(length(blob))::UInt64)::Cint
+    checkerr(ctx.ptr, rc)
+end
+
+function chain_blob_info(blob::Vector{UInt8})
+    h = Ref(HmcmtChainBlobHeader(0, 0, 0, 0, 0, 0, 0, 0, 0, ntuple(_ -> UInt32(0), 16), ntuple(_ -> UInt64(0), 16)))
+    rc = GC.@preserve blob @ccall libhmcmt.hmcmt_chain_blob_info(pointer(blob)::Ptr{UInt8}, UInt64(length(blob))::UInt64,
+                                                                 h::Ref{HmcmtChainBlobHeader})::Cint
+    rc == 0 || error("libhmcmt_hip error $rc: not an intact chain blob of version 1")
+    v = h[]
+    tag(t) = String(UInt8[(t >> s) & 0xff for s in (0, 8, 16, 24)])
+    return (version=v.version, total_bytes=v.total_bytes, nAC=v.nAC, nData=v.nData, mass_kind=v.mass_kind, seeded=v.seeded != 0,
+            nsamples=v.nsamples, nmoments=v.nmoments, sections=[(tag(v.tags[k]), v.section_bytes[k]) for k in 1:v.nsections])
+end
 
 """
     chain_seed!(ctx, seed, stream=0);  chain_rng_state(ctx) -> (seed, stream, t)
