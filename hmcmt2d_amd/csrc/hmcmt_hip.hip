@@ -334,6 +334,20 @@ struct hmcmt_ctx {
             std::vector<void*> allocs;
             ChainTimer timer;                         // every launch of the commit: class 0 k_chain_cov_commit, 1 k_chain_cov_flush
         } cov;
+        struct Sketch {                               // hmcmt_chain_sketch_*: frequent-directions row sketch, cell index fastest (hmcmt_items.h)
+            bool on = false, pivotGiven = false;
+            int ell = 0, fill = 0;                    // rows 0 .. fill - 1 of d_B are in use; row 2 ell is the read-out's mean row
+            long long count = 0, shrinks = 0;
+            double Delta = 0;                         // sum of the shrinks' delta
+            double *d_B = nullptr;                    // [2 ell + 1][nAC]
+            double *d_x0 = nullptr, *d_tot = nullptr, *d_q = nullptr;   // [nAC] pivot, sum of y, sum of y^2
+            double *d_K = nullptr, *d_T = nullptr;    // [2 ell + 1]^2 Gram staging; [2 ell + 1][HMCMT_MASS_RANK_MAX] doubles: T [ell][2 ell] or the PCA's coefficients
+            std::vector<double> hK, hT;               // the host's copy of the Gram matrix; T or the PCA's coefficients while their upload is in flight
+            std::string ended;                        // why a shrink ended the sketch (the read-outs' message); empty: it did not
+            double hostMs = 0;                        // measurement: host ms of the shrinks' eigenproblems while the timer is on
+            std::vector<void*> allocs;
+            ChainTimer timer;                         // class 0 k_chain_sketch_commit, 1 k_chain_sketch_gram and k_chain_sketch_shrink (two launches per shrink)
+        } sketch;
         struct Adapt {                                // hmcmt_chain_adapt_*: warm-up of dt and of the diagonal of M^-1 (hmcmt_items.h: item_adapt_*)
             bool begun = false, active = false;       // begun: in this chain, running or ended (hmcmt_chain_adapt_info)
             hmcmt_adapt_options opt{};

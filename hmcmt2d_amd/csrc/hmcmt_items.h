@@ -1645,4 +1645,122 @@ inline AdaptLrEstimate item_adapt_lr_estimate(int n, const double* K, int rank, 
     return item_adapt_lr_select(n, m, T, Yt, th, rank, cutoff);
 }
 
+// ----------------------------------------------------------------------------------------------
+// the row sketch of the committed models (hmcmt_chain_sketch_*, hmcmt_chain_pca; kernels_chain.h: k_chain_sketch_commit,
+// k_chain_sketch_gram, k_chain_sketch_shrink, k_chain_sketch_mean, k_chain_sketch_lift; include/hmcmt.h has the algorithm)
+// ----------------------------------------------------------------------------------------------
+// Frequent directions: B [2 ell + 1][nAC], cell index fastest.  Counted commit t puts y_t = m - x0 (one subtraction) into row `fill`;
+// at fill == 2 ell the device forms K = B B' (rows 0 .. 2 ell - 1), the host turns its eigenpairs into T [ell][2 ell]
+// (item_chain_sketch_shrink) and the device replaces B by T B.  Row 2 ell is staging of the read-out (sqrt(N) ybar).  Every sum has
+// one owner and one order: K[i][j] is one fma chain over the cells upwards, (T B)[i][a] one fma chain over j upwards.
+constexpr int CHAIN_SKETCH_ELL_MIN = 2, CHAIN_SKETCH_ELL_MAX = 64;
+constexpr int CHAIN_SKETCH_ELL_DEFAULT = 32;
+constexpr int CHAIN_SKETCH_COLS = 64;      // k_chain_sketch_shrink: cells of a workgroup, one per thread (one wavefront); its LDS holds
+                                           //   2 ell x CHAIN_SKETCH_COLS doubles, 64 KiB at ell = 64
+static_assert(2 * CHAIN_SKETCH_ELL_MAX * CHAIN_SKETCH_COLS * sizeof(double) <= 65536, "k_chain_sketch_shrink's columns fit the 64 KiB of dynamic LDS a launch gets by default");
+constexpr int CHAIN_SKETCH_CHUNK = 8;      // output rows a thread of the shrink accumulates side by side (registers, indexed at compile time)
+// commit t (the count before it) of cell a: the sums of hmcmt_chain_cov and the row of this commit
+HD void item_chain_sketch_commit(const double* m, double* x0, double* tot, double* q, double* brow, long long t, int pivotGiven, long long a) {
+    const double x = m[a];
+    if (t == 0 && !pivotGiven) x0[a] = x;
+    const double y = x - x0[a];
+    tot[a] += y;
+    q[a] = fma(y, y, q[a]);
+    brow[a] = y;
+}
+// row gi of the Gram kernel's operand: rows 0 .. nrows - 1 of B, then the extra row (the read-out's mean row)
+HD const double* item_chain_sketch_row(const double* B, const double* extra, long long nAC, int nrows, int gi) {
+    return gi < nrows ? B + (long long)gi * nAC : extra;
+}
+// K[i][j] over all cells upwards (what the tiled kernel computes strip by strip)
+HD double item_chain_sketch_gram(const double* ri, const double* rj, long long nAC) {
+    double acc = 0.0;
+    for (long long a = 0; a < nAC; ++a) acc = item_adapt_lr_dot(ri[a], rj[a], acc);
+    return acc;
+}
+// (T B)[i][a] from cell a's column col[j * stride], j < n2 upwards
+HD double item_chain_sketch_shrink(const double* Trow, const double* col, long long stride, int n2) {
+    double acc = 0.0;
+    for (int j = 0; j < n2; ++j) acc = fma(Trow[j], col[(long long)j * stride], acc);
+    return acc;
+}
+// the read-out's mean row: sqrt(N) ybar[a], sqN = sqrt((double)N) (a division and a product: nothing to contract)
+HD double item_chain_sketch_mean(double tot, double dN, double sqN) {
+    const double ybar = tot / dN;
+    return sqN * ybar;
+}
+// U[k][a] = sum_i coef[i][k] W[i][a], i < nw upwards; W = the filled rows and the mean row
+HD double item_chain_sketch_lift(const double* B, const double* extra, const double* coef, long long nAC, int nrows, int nw, int r, int k, long long a) {
+    double acc = 0.0;
+    for (int i = 0; i < nw; ++i) acc = item_adapt_lr_dot(coef[(long long)i * r + k], item_chain_sketch_row(B, extra, nAC, nrows, i)[a], acc);
+    return acc;
+}
+// The host's share of a shrink, in double.  K [2 ell][2 ell] (destroyed) -> T [ell][2 ell] and delta: with the eigenvalues descending
+// d_0 >= d_1 >= ..., delta = max(d_ell, 0), c_i = d_i > delta ? sqrt((d_i - delta) / d_i) : 0, T[i][j] = c_i V[j][i].  false: K is not
+// finite or the eigensolver did not converge.
+inline bool item_chain_sketch_shrink_T(int ell, double* K, std::vector<double>& T, double* delta) {
+    const int n2 = 2 * ell;
+    for (size_t e = 0; e < (size_t)n2 * n2; ++e)
+        if (!std::isfinite(K[e])) return false;
+    std::vector<double> Vt((size_t)n2 * n2), d((size_t)n2);
+    if (item_jacobi_eig(n2, K, Vt.data(), d.data()) >= ADAPT_LR_SWEEPS_MAX) return false;
+    const double dl = d[n2 - 1 - ell];                      // (d is ascending: the descending d_i is d[n2 - 1 - i])
+    *delta = dl > 0.0 ? dl : 0.0;
+    T.assign((size_t)ell * n2, 0.0);
+    for (int i = 0; i < ell; ++i) {
+        const double di = d[n2 - 1 - i];
+        const double c = di > *delta ? sqrt((di - *delta) / di) : 0.0;
+        for (int j = 0; j < n2; ++j) T[(size_t)i * n2 + j] = c * Vt[(size_t)(n2 - 1 - i) * n2 + j];
+    }
+    return true;
+}
+// The host's share of hmcmt_chain_pca.  G [nw][nw] = W W' with the mean row LAST (destroyed).  G = Q Lambda Q' keeps the m values
+// Lambda_i > 1e-10 Lambda_max; S = Lambda^1/2 Q' J Q Lambda^1/2, J = diag(1, ..., 1, -1), symmetrised; S = Z Theta Z'; the
+// min(rank, #theta > 0) largest theta descending, the lower index first among equals; coef [nw][r] = Q Lambda^-1/2 Z_sel.
+// Returns r >= 0, or -1: G is not finite, an eigensolver did not converge.
+inline int item_chain_sketch_pca(int nw, double* G, int rank, std::vector<double>& theta, std::vector<double>& coef) {
+    for (size_t e = 0; e < (size_t)nw * nw; ++e)
+        if (!std::isfinite(G[e])) return -1;
+    std::vector<double> Qt((size_t)nw * nw), lam((size_t)nw);
+    if (item_jacobi_eig(nw, G, Qt.data(), lam.data()) >= ADAPT_LR_SWEEPS_MAX) return -1;
+    theta.clear(); coef.clear();
+    const double lmax = lam[nw - 1];
+    if (!(lmax > 0.0)) return 0;
+    int first = 0;
+    while (first < nw && !(lam[first] > 1e-10 * lmax)) ++first;
+    const int m = nw - first;
+    std::vector<double> sq((size_t)m), S((size_t)m * m), Zt((size_t)m * m), th((size_t)m);
+    for (int a = 0; a < m; ++a) sq[a] = sqrt(lam[first + a]);
+    for (int a = 0; a < m; ++a)
+        for (int b = 0; b < m; ++b) {
+            double acc = 0.0;
+            for (int i = 0; i < nw; ++i) {
+                const double p = Qt[(size_t)(first + a) * nw + i] * Qt[(size_t)(first + b) * nw + i];
+                acc += i == nw - 1 ? -p : p;
+            }
+            S[(size_t)a * m + b] = sq[a] * acc * sq[b];
+        }
+    item_adapt_lr_symmetrise(m, S);
+    if (item_jacobi_eig(m, S.data(), Zt.data(), th.data()) >= ADAPT_LR_SWEEPS_MAX) return -1;
+    int r = 0;
+    while (r < m && r < rank && th[m - 1 - r] > 0.0) ++r;
+    std::vector<int> sel((size_t)r);
+    for (int c = 0; c < r; ++c) sel[c] = m - 1 - c;
+    for (int c = 1; c < r; ++c)                              // (equal theta: the lower index first)
+        for (int j = c; j > 0 && th[sel[j]] == th[sel[j - 1]] && sel[j] < sel[j - 1]; --j) { const int t = sel[j]; sel[j] = sel[j - 1]; sel[j - 1] = t; }
+    theta.resize((size_t)r);
+    coef.assign((size_t)nw * (r > 1 ? r : 1), 0.0);
+    for (int c = 0; c < r; ++c) {
+        theta[c] = th[sel[c]];
+        for (int i = 0; i < nw; ++i) {
+            double acc = 0.0;
+            for (int a = 0; a < m; ++a) acc += Qt[(size_t)(first + a) * nw + i] / sq[a] * Zt[(size_t)sel[c] * m + a];
+            coef[(size_t)i * r + c] = acc;
+        }
+    }
+    for (double v : coef)
+        if (!std::isfinite(v)) return -1;
+    return r;
+}
+
 }  // namespace hmcmt

@@ -6,12 +6,13 @@
 // one sample = hmcmt_chain_sample, k_chain_draw_momentum in k_chain_momentum's place, nothing up, CHAIN_REC scalars down, one wait.  Launches per sample beyond leapfrog_core's (diagonal mass):
 // k_chain_momentum, k_chain_kinetic, k_chain_final, k_chain_welford; with the optional accumulators of the commit on,
 // k_chain_hist, a second k_chain_welford (the predicted data), k_chain_acov (lagged autocovariances) and k_chain_cov_commit (cross
-// moments; every `batch` commits k_chain_cov_flush) behind them.  During a warm-up (hmcmt_chain_adapt_*) a k_chain_welford on the
+// moments; every `batch` commits k_chain_cov_flush) and k_chain_sketch_commit (the row sketch; every ell commits k_chain_sketch_gram,
+// a wait for its 2 ell x 2 ell result and k_chain_sketch_shrink) behind them.  During a warm-up (hmcmt_chain_adapt_*) a k_chain_welford on the
 // window's buffers inside a window and k_chain_adapt_mass at a window's end follow the commit.  A NUTS sample (hmcmt_chain_nuts_sample,
 // kernels_nuts.h) chooses its trajectory length: per leaf leapfrog_core(L = 1) with its wait for the solver records, k_nuts_leaf, k_nuts_final,
 // NUTS_SCAL scalars down and one wait more; it ends in the same commit.
 //
-// The four accumulators share their host scaffolding, which stands in front of them: ChainTimer (the event pairs of the measurement
+// The accumulators share their host scaffolding, which stands in front of them: ChainTimer (the event pairs of the measurement
 // hooks), chain_acc_alloc / chain_acc_free (each accumulator's struct owns its buffers through `allocs`), chain_acc_ready (the
 // guards of an entry point), chain_cell_list / chain_cell_upload (a begin's list of active cells) and ChainReadout (the outputs of
 // one read-out: the caller's device pointers, or temporaries copied back).  A further accumulator is its kernels, its struct in
@@ -204,11 +205,109 @@ static void chain_cov_flush(hmcmt_ctx* ctx) {
     V.npend = 0;
 }
 
-// ends the commit's optional accumulators (histogram, data moments, autocovariances, cross moments) and frees their buffers
+// ---- the row sketch's buffers, commit and shrink (hmcmt_chain_sketch_*, hmcmt_debug_chain_sketch; the entry points stand behind
+// hmcmt_chain_cov's).  They work on a Sketch of the caller's, so that the debug hook drives the chain's very launches without a chain.
+using ChainSketch = hmcmt_ctx::Chain::Sketch;
+static const ChainAccName CHAIN_SKETCH = {"sketch", "hmcmt_chain_sketch_begin", "the sketch"};
+
+// ends a sketch and frees its buffers; `why` (may be empty) is what the read-outs say from then on
+static void chain_sketch_end(hmcmt_ctx* ctx, ChainSketch& S, const std::string& why) {
+    if (!S.allocs.empty() && ctx->stream) (void)hipStreamSynchronize(ctx->stream);    // (a commit may still be writing a row)
+    S.timer.free(ctx->cfg.device, ctx->stream);
+    chain_acc_free(S.allocs);
+    S = {};
+    S.ended = why;
+}
+
+// the zeroed buffers of hmcmt_chain_sketch_begin in S (which is empty); pivot: nAC host doubles or nullptr
+static int chain_sketch_alloc(hmcmt_ctx* ctx, const char* fn, ChainSketch& S, int ell, const double* pivot) {
+    const size_t n = (size_t)ctx->v.nAC, D = sizeof(double), rows = (size_t)2 * ell + 1;
+    const size_t stage = std::max((size_t)ell * 2 * ell, rows * (size_t)HMCMT_MASS_RANK_MAX);
+    const std::pair<double**, size_t> bufs[] = {{&S.d_B, rows * n * D}, {&S.d_x0, n * D}, {&S.d_tot, n * D}, {&S.d_q, n * D},
+                                                {&S.d_K, rows * rows * D}, {&S.d_T, stage * D}};
+    int rc;
+    for (const auto& b : bufs)
+        if ((rc = chain_acc_zeroed(ctx, fn, S.allocs, (void**)b.first, b.second))) return rc;
+    if (pivot) HIPCHK(hipMemcpyAsync(S.d_x0, pivot, n * D, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (the caller's pivot is free again on return)
+    S.hK.assign(rows * rows, 0.0);
+    S.ell = ell; S.fill = 0; S.count = 0; S.shrinks = 0; S.Delta = 0.0;
+    S.pivotGiven = pivot != nullptr;
+    return 0;
+}
+
+// K = W W' of rows 0 .. nrows - 1 of B (and the mean row behind them) into S.d_K, enqueued
+static SketchRows chain_sketch_gram(hmcmt_ctx* ctx, const ChainSketch& S, int nrows, bool meanRow) {
+    const int nAC = ctx->v.nAC;
+    const SketchRows w{nAC, nrows, nrows + (meanRow ? 1 : 0), S.d_B, meanRow ? S.d_B + (size_t)2 * S.ell * nAC : nullptr};
+    const int T = (w.nw + ADAPT_LR_TILE - 1) / ADAPT_LR_TILE;
+    hipLaunchKernelGGL(k_chain_sketch_gram, dim3(T * (T + 1) / 2), dim3(256), 0, ctx->stream, w, S.d_K);
+    return w;
+}
+
+// The shrink of a full buffer (fill == 2 ell): the Gram kernel, the shrink's ONE wait with K's download, the host's eigenproblem, T's
+// upload, the shrink kernel (enqueued).  K_out [2 ell]^2 / T_out [ell][2 ell]: the debug hook's copies, or nullptr.  Returns 0;
+// HMCMT_EHIP behind a HIP error and HMCMT_EBREAKDOWN where the eigensolver gave up -- both have ended the sketch.
+static int chain_sketch_shrink(hmcmt_ctx* ctx, ChainSketch& S, double* K_out, double* T_out) {
+    hipStream_t st = ctx->stream;
+    const int ell = S.ell, n2 = 2 * ell;
+    const size_t kb = sizeof(double) * (size_t)n2 * n2;
+    auto failed = [&](hipError_t e, const char* what) {
+        if (e == hipSuccess) return false;
+        (void)hipGetLastError();
+        ctx->err = std::string("the sketch's shrink: ") + what + ": " + hipGetErrorString(e) + " (the sketch is ended)";
+        chain_sketch_end(ctx, S, std::string("a HIP error in a shrink (") + what + ") ended the sketch");
+        return true;
+    };
+    bool timed = S.timer.start(st);
+    (void)chain_sketch_gram(ctx, S, n2, false);
+    if (timed) S.timer.stop(st, 1);
+    if (failed(hipMemcpyAsync(S.hK.data(), S.d_K, kb, hipMemcpyDeviceToHost, st), "the download of K")) return HMCMT_EHIP;
+    if (failed(hipStreamSynchronize(st), "the wait for K")) return HMCMT_EHIP;                  // the shrink's wait
+    if (K_out) std::memcpy(K_out, S.hK.data(), kb);
+    const auto h0 = std::chrono::steady_clock::now();
+    std::vector<double>& T = S.hT;                          // (the sketch's: the upload below reads it until the next wait of this stream)
+    double delta = 0.0;
+    const bool ok = item_chain_sketch_shrink_T(ell, S.hK.data(), T, &delta);
+    if (S.timer.timing) S.hostMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
+    if (!ok) {
+        chain_sketch_end(ctx, S, "the eigensolver of a shrink did not converge within its sweeps, or its Gram matrix was not finite: the sketch was ended");
+        return HMCMT_EBREAKDOWN;
+    }
+    if (T_out) std::memcpy(T_out, T.data(), sizeof(double) * T.size());
+    if (failed(hipMemcpyAsync(S.d_T, T.data(), sizeof(double) * T.size(), hipMemcpyHostToDevice, st), "the upload of T")) return HMCMT_EHIP;
+    const long long n = ctx->v.nAC;
+    timed = S.timer.start(st);
+    hipLaunchKernelGGL(k_chain_sketch_shrink, dim3((unsigned)((n + CHAIN_SKETCH_COLS - 1) / CHAIN_SKETCH_COLS)), dim3(CHAIN_SKETCH_COLS),
+                       sizeof(double) * (size_t)n2 * CHAIN_SKETCH_COLS, st, n, ell, S.d_T, S.d_B);
+    if (timed) S.timer.stop(st, 1);
+    if (failed(hipGetLastError(), "a kernel launch")) return HMCMT_EHIP;
+    S.Delta += delta;
+    ++S.shrinks;
+    S.fill = ell;
+    return 0;
+}
+
+// one counted commit of the model d_m: the commit kernel (enqueued) and, when it fills the buffer, the shrink (its results above)
+static int chain_sketch_commit(hmcmt_ctx* ctx, ChainSketch& S, const double* d_m, double* K_out, double* T_out) {
+    hipStream_t st = ctx->stream;
+    const long long n = ctx->v.nAC;
+    const bool timed = S.timer.start(st);
+    hipLaunchKernelGGL(k_chain_sketch_commit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, S.count, S.pivotGiven ? 1 : 0, d_m,
+                       S.d_x0, S.d_tot, S.d_q, S.d_B + (size_t)S.fill * n);
+    if (timed) S.timer.stop(st, 0);
+    ++S.count;
+    if (++S.fill == 2 * S.ell) return chain_sketch_shrink(ctx, S, K_out, T_out);
+    return 0;
+}
+
+// ends the commit's optional accumulators (histogram, data moments, autocovariances, cross moments, sketch) and frees their buffers
 static void chain_acc_release(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     C.acov.timer.free(ctx->cfg.device, ctx->stream);
     C.cov.timer.free(ctx->cfg.device, ctx->stream);
+    if (!C.sketch.allocs.empty()) hipSetDevice(ctx->cfg.device);
+    chain_sketch_end(ctx, C.sketch, "");
     if (!C.hist.allocs.empty() || !C.dmom.allocs.empty() || !C.acov.allocs.empty() || !C.cov.allocs.empty() || !C.adapt.allocs.empty()) {
         hipSetDevice(ctx->cfg.device);
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);      // (a commit may still be counting)
@@ -599,8 +698,9 @@ int hmcmt_chain_step(hmcmt_ctx* ctx, int32_t L, double u, hmcmt_chain_record* re
 }
 
 // The commit of a sample behind its decision, shared by hmcmt_chain_step and the NUTS sample: the counters, the moments and the
-// optional accumulators with the chain's current model -- enqueued, not waited for.
-static void chain_commit(hmcmt_ctx* ctx) {
+// optional accumulators with the chain's current model -- enqueued, not waited for, but for the sketch's shrink once in ell counted
+// commits.  Returns 0, or HMCMT_EHIP where that shrink met a HIP error (the sample stands, the sketch is ended).
+static int chain_commit(hmcmt_ctx* ctx) {
     auto& C = ctx->chain;
     const int n = ctx->v.nAC, nData = ctx->v.nData;
     hipStream_t st = ctx->stream;
@@ -635,7 +735,9 @@ static void chain_commit(hmcmt_ctx* ctx) {
             ++V.count;
             if (++V.npend == V.B) chain_cov_flush(ctx);
         }
+        if (C.sketch.on && chain_sketch_commit(ctx, C.sketch, C.d_m[C.cur], nullptr, nullptr) == HMCMT_EHIP) return HMCMT_EHIP;
     }
+    return 0;
 }
 
 // The step behind its launches: the sample's one wait, the record's checks, the accept test with u, the commit (enqueued), the outputs.
@@ -664,10 +766,11 @@ static int chain_step_decide(hmcmt_ctx* ctx, double u, const ChainStepState& S, 
     const bool accepted = hdif > 0 || u < std::exp(hdif);
     if (accepted) { C.cur = prop; C.D = D1; C.M = M1; }
     C.nextStart = accepted ? 1 : 2;
-    chain_commit(ctx);
-    const int arc = C.adapt.active ? chain_adapt_step(ctx, hdif > 0 ? 1.0 : std::exp(hdif)) : 0;
+    const int src = chain_commit(ctx);
+    const int wrc = C.adapt.active ? chain_adapt_step(ctx, hdif > 0 ? 1.0 : std::exp(hdif)) : 0;
+    const int arc = src ? src : wrc;
     C.gen = ctx->stateGen;
-    if (arc) return chain_fail(ctx, arc);                    // (the sample stands; the call reports the window end's HIP error)
+    if (arc) return chain_fail(ctx, arc);                    // (the sample stands; the call reports the HIP error of the sketch's shrink or the window end)
     rec->accepted = accepted ? 1 : 0;
     rec->nfevals = evals - (startGrad != 0 ? 1 : 0);
     rec->K0 = K0; rec->K1 = K1; rec->D1 = D1; rec->M1 = M1;
@@ -1041,10 +1144,11 @@ static int chain_nuts_sample(hmcmt_ctx* ctx, const char* fn, int32_t maxDepth, h
     const double D0 = C.D, M0 = C.M;
     if (movedOn) { C.cur = prop; C.D = sel[1]; C.M = sel[2]; }
     const double alpha = T.alphaSum / (double)T.nleaves;
-    chain_commit(ctx);
-    const int arc = C.adapt.active ? chain_adapt_step(ctx, alpha) : 0;
+    const int src = chain_commit(ctx);
+    const int wrc = C.adapt.active ? chain_adapt_step(ctx, alpha) : 0;
+    const int arc = src ? src : wrc;
     C.gen = ctx->stateGen;
-    if (arc) return chain_fail(ctx, arc);                    // (the sample stands; the call reports the window end's HIP error)
+    if (arc) return chain_fail(ctx, arc);                    // (the sample stands; the call reports the HIP error of the sketch's shrink or the window end)
     std::memset(rec, 0, sizeof *rec);
     rec->rec.accepted = movedOn ? 1 : 0;
     rec->rec.nfevals = evals;
@@ -1461,6 +1565,199 @@ int hmcmt_debug_chain_cov_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64
     return chain_timer_report(ctx, "hmcmt_debug_chain_cov_time", ctx->chain.cov.on, CHAIN_COV, ctx->chain.cov.timer, enable, ms, launches);
 }
 
+// ---- posterior principal components by a row sketch (k_chain_sketch_*; the commit and the shrink stand in front of chain_acc_release) ----
+int hmcmt_chain_sketch_begin(hmcmt_ctx* ctx, int32_t ell, const double* pivot) {
+    const char* fn = "hmcmt_chain_sketch_begin";
+    if (!ctx) return HMCMT_EINVAL;
+    int rc = chain_ready(ctx, fn, true);
+    if (rc) return rc;
+    static_assert(CHAIN_SKETCH_ELL_MAX == HMCMT_SKETCH_ELL_MAX, "the header's bound is the kernels'");
+    if (ell < CHAIN_SKETCH_ELL_MIN || ell > CHAIN_SKETCH_ELL_MAX) { ctx->err = std::string(fn) + ": need 2 <= ell <= 64"; return HMCMT_EINVAL; }
+    if (pivot)
+        for (int a = 0; a < ctx->v.nAC; ++a)
+            if (!std::isfinite(pivot[a])) { ctx->err = std::string(fn) + ": non-finite pivot"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    auto& S = ctx->chain.sketch;
+    HIPCHK(hipStreamSynchronize(ctx->stream));               // (a commit may still be adding to the sketch this one replaces)
+    chain_sketch_end(ctx, S, "");
+    if ((rc = chain_sketch_alloc(ctx, fn, S, ell, pivot))) {
+        const std::string e = ctx->err;
+        (void)hipGetLastError();
+        chain_sketch_end(ctx, S, "");
+        ctx->err = e;
+        return rc;
+    }
+    S.on = true;
+    return 0;
+}
+
+// the guards of the sketch's read-outs: chain_acc_ready, with the reason where a shrink ended the sketch
+static int chain_sketch_ready(hmcmt_ctx* ctx, const char* fn, bool needCommits) {
+    const auto& S = ctx->chain.sketch;
+    if (!S.on && !S.ended.empty()) {
+        const int rc = chain_ready(ctx, fn, true);
+        if (rc) return rc;
+        ctx->err = std::string(fn) + ": " + S.ended;
+        return HMCMT_EINVAL;
+    }
+    return chain_acc_ready(ctx, fn, S.on, S.count, needCommits, CHAIN_SKETCH);
+}
+
+static void chain_sketch_info(const ChainSketch& S, hmcmt_sketch_info* info) {
+    *info = hmcmt_sketch_info{};
+    info->count = S.count; info->ell = S.ell; info->fill = S.fill; info->shrinks = S.shrinks; info->Delta = S.Delta;
+    info->pivot_given = S.pivotGiven ? 1 : 0;
+}
+
+int hmcmt_chain_sketch(hmcmt_ctx* ctx, hmcmt_sketch_info* info, double* mean, double* var, double* rows, int32_t on_device) {
+    const char* fn = "hmcmt_chain_sketch";
+    if (!ctx) return HMCMT_EINVAL;
+    auto& S = ctx->chain.sketch;
+    int rc = chain_sketch_ready(ctx, fn, mean || var || rows);
+    if (rc) return rc;
+    if (mean || var || rows) {
+        HIPCHK(hipSetDevice(ctx->cfg.device));
+        const long long n = ctx->v.nAC;
+        const size_t mb = sizeof(double) * (size_t)n;
+        if (mean || var) {
+            ChainReadout R(ctx, fn, on_device);
+            double *d_mean = (double*)R.out(mean, mb), *d_var = (double*)R.out(var, mb);
+            if (R.rc) return R.rc;
+            hipLaunchKernelGGL(k_chain_cov_out, chain_cov_grid(ctx, 1), dim3(256), 0, ctx->stream, n, 1LL, (double)S.count, S.d_x0, S.d_tot,
+                               S.d_q, (const double*)nullptr, (const long long*)nullptr, d_mean, d_var, (double*)nullptr);
+            if ((rc = R.finish())) return rc;
+        }
+        if (rows) {
+            HIPCHK(hipMemcpyAsync(rows, S.d_B, mb * (size_t)S.fill, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    if (info) chain_sketch_info(S, info);
+    return 0;
+}
+
+int hmcmt_chain_pca(hmcmt_ctx* ctx, int32_t rank, int32_t* kept, double* lambda, double* U, double* err, int32_t on_device) {
+    const char* fn = "hmcmt_chain_pca";
+    if (!ctx) return HMCMT_EINVAL;
+    auto& S = ctx->chain.sketch;
+    int rc = chain_sketch_ready(ctx, fn, true);
+    if (rc) return rc;
+    if (!kept || rank < 1 || rank > HMCMT_MASS_RANK_MAX) { ctx->err = std::string(fn) + ": need kept and 1 <= rank <= HMCMT_MASS_RANK_MAX"; return HMCMT_EINVAL; }
+    if (S.count < 2) { ctx->err = std::string(fn) + ": the sketch holds " + std::to_string(S.count) + " commit (two at least make a covariance)"; return HMCMT_EINVAL; }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    hipStream_t st = ctx->stream;
+    const long long n = ctx->v.nAC;
+    const int nw = S.fill + 1;
+    const double dN = (double)S.count;
+    hipLaunchKernelGGL(k_chain_sketch_mean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, dN, std::sqrt(dN), S.d_tot, S.d_B + (size_t)2 * S.ell * n);
+    const SketchRows w = chain_sketch_gram(ctx, S, S.fill, true);
+    HIPCHK(hipMemcpyAsync(S.hK.data(), S.d_K, sizeof(double) * (size_t)nw * nw, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                        // the read-out's wait for G
+    HIPCHK(hipGetLastError());
+    std::vector<double> theta;
+    std::vector<double>& coef = S.hT;                       // (the sketch's: the upload below reads it until the next wait of this stream)
+    const int r = item_chain_sketch_pca(nw, S.hK.data(), rank, theta, coef);
+    if (r < 0) { ctx->err = std::string(fn) + ": the Gram matrix is not finite, or an eigensolver did not converge within its sweeps"; return HMCMT_EBREAKDOWN; }
+    if (r > 0) {
+        HIPCHK(hipMemcpyAsync(S.d_T, coef.data(), sizeof(double) * (size_t)nw * r, hipMemcpyHostToDevice, st));
+        ChainReadout R(ctx, fn, on_device);
+        double* d_U = U ? (double*)R.out(U, sizeof(double) * (size_t)r * n) : (double*)R.scratch(sizeof(double) * (size_t)r * n);
+        double* d_part = (double*)R.scratch(sizeof(double) * (size_t)r * LFNB);
+        if (R.rc) return R.rc;
+        hipLaunchKernelGGL(k_chain_sketch_lift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, S.d_T, r, d_U);
+        hipLaunchKernelGGL(k_adapt_lr_sign, dim3(r), dim3(256), 0, st, (int)n, d_U);
+        double defect = 0.0;
+        if ((rc = mass_lr_defect(ctx, r, nullptr, d_U, nullptr, d_part, &defect))) return rc;
+        if (!(defect <= 1e-8)) {
+            ctx->err = std::string(fn) + ": the components are not orthonormal (max |U U' - I| = " + std::to_string(defect) + ")";
+            return HMCMT_EBREAKDOWN;
+        }
+        if ((rc = R.finish())) return rc;
+        if (lambda) {
+            for (double& t : theta) t = t / dN;
+            if (on_device) HIPCHK(hipMemcpy(lambda, theta.data(), sizeof(double) * r, hipMemcpyHostToDevice));
+            else std::copy(theta.begin(), theta.end(), lambda);
+        }
+    }
+    *kept = r;
+    if (err) *err = S.Delta / dN;
+    return 0;
+}
+
+int hmcmt_debug_chain_sketch(hmcmt_ctx* ctx, int32_t ell, int64_t n, const double* rows, const double* pivot, hmcmt_sketch_info* info,
+                             double* x0, double* tot, double* q, double* B_out, int32_t max_shrinks, double* K_out, double* T_out) {
+    const char* fn = "hmcmt_debug_chain_sketch";
+    if (!ctx) return HMCMT_EINVAL;
+    if (!ctx->havePrior) { ctx->err = std::string(fn) + ": hmcmt_set_prior has not been called"; return HMCMT_EINVAL; }
+    int rc = chain_ready(ctx, fn, false);
+    if (rc) return rc;
+    if (!rows || !info || n < 1 || n > 65536 || ell < CHAIN_SKETCH_ELL_MIN || ell > CHAIN_SKETCH_ELL_MAX || max_shrinks < 0 ||
+        (max_shrinks > 0 && (!K_out || !T_out))) {
+        ctx->err = std::string(fn) + ": need rows, info, 1 <= n <= 65536, 2 <= ell <= 64, and K_out and T_out with max_shrinks > 0";
+        return HMCMT_EINVAL;
+    }
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    hipStream_t st = ctx->stream;
+    const size_t nAC = (size_t)ctx->v.nAC, vb = nAC * sizeof(double), n2 = (size_t)2 * ell;
+    ChainSketch S;
+    std::vector<void*> own;
+    double* d_rows = nullptr;
+    auto run = [&]() -> int {
+        int r;
+        if ((r = chain_acc_alloc(ctx, fn, own, (void**)&d_rows, (size_t)n * vb))) return r;
+        if ((r = chain_sketch_alloc(ctx, fn, S, ell, pivot))) return r;
+        HIPCHK(hipMemcpy(d_rows, rows, (size_t)n * vb, hipMemcpyHostToDevice));
+        for (int64_t t = 0; t < n; ++t) {
+            const bool keep = S.shrinks < max_shrinks;
+            r = chain_sketch_commit(ctx, S, d_rows + (size_t)t * nAC, keep ? K_out + (size_t)S.shrinks * n2 * n2 : nullptr,
+                                    keep ? T_out + (size_t)S.shrinks * ell * n2 : nullptr);
+            if (r == HMCMT_EBREAKDOWN) ctx->err = std::string(fn) + ": " + S.ended;
+            if (r) return r;
+        }
+        if (x0) HIPCHK(hipMemcpyAsync(x0, S.d_x0, vb, hipMemcpyDeviceToHost, st));
+        if (tot) HIPCHK(hipMemcpyAsync(tot, S.d_tot, vb, hipMemcpyDeviceToHost, st));
+        if (q) HIPCHK(hipMemcpyAsync(q, S.d_q, vb, hipMemcpyDeviceToHost, st));
+        if (B_out) HIPCHK(hipMemcpyAsync(B_out, S.d_B, vb * (size_t)S.fill, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        chain_sketch_info(S, info);
+        return 0;
+    };
+    rc = run();
+    const std::string e = ctx->err;
+    (void)hipStreamSynchronize(st);
+    chain_sketch_end(ctx, S, "");
+    chain_acc_free(own);
+    ctx->err = e;
+    return rc;
+}
+
+int hmcmt_debug_chain_sketch_sums(hmcmt_ctx* ctx, double* x0, double* tot, double* q, int32_t on_device) {
+    const char* fn = "hmcmt_debug_chain_sketch_sums";
+    if (!ctx) return HMCMT_EINVAL;
+    const auto& S = ctx->chain.sketch;
+    const int rc = chain_sketch_ready(ctx, fn, false);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    const size_t vb = sizeof(double) * (size_t)ctx->v.nAC;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (x0) HIPCHK(hipMemcpyAsync(x0, S.d_x0, vb, kind, ctx->stream));
+    if (tot) HIPCHK(hipMemcpyAsync(tot, S.d_tot, vb, kind, ctx->stream));
+    if (q) HIPCHK(hipMemcpyAsync(q, S.d_q, vb, kind, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int hmcmt_debug_chain_sketch_time(hmcmt_ctx* ctx, int32_t enable, double* ms, int64_t* launches, double* host_ms) {
+    if (!ctx) return HMCMT_EINVAL;
+    auto& S = ctx->chain.sketch;
+    const int rc = chain_timer_report(ctx, "hmcmt_debug_chain_sketch_time", S.on, CHAIN_SKETCH, S.timer, enable, ms, launches);
+    if (rc) return rc;
+    if (host_ms) *host_ms = S.hostMs;
+    if (enable >= 0) S.hostMs = 0.0;
+    return 0;
+}
+
 // ---- the chain's step size and diagonal mass between two steps, and their warm-up adaptation (chain_adapt_step, k_chain_adapt_mass) ----
 int hmcmt_chain_set_dt(hmcmt_ctx* ctx, double dt) {
     const char* fn = "hmcmt_chain_set_dt";
@@ -1845,8 +2142,8 @@ constexpr uint32_t blob_tag(char a, char b, char c, char d) {
 }
 constexpr uint32_t BLOB_CHAN = blob_tag('C', 'H', 'A', 'N'), BLOB_MASS = blob_tag('M', 'A', 'S', 'S'), BLOB_HIST = blob_tag('H', 'I', 'S', 'T'),
                    BLOB_DMOM = blob_tag('D', 'M', 'O', 'M'), BLOB_ACOV = blob_tag('A', 'C', 'O', 'V'), BLOB_COV = blob_tag('C', 'O', 'V', ' '),
-                   BLOB_ADPT = blob_tag('A', 'D', 'P', 'T'), BLOB_ADLR = blob_tag('A', 'D', 'L', 'R');
-constexpr uint32_t BLOB_ORDER[] = {BLOB_CHAN, BLOB_MASS, BLOB_HIST, BLOB_DMOM, BLOB_ACOV, BLOB_COV, BLOB_ADPT, BLOB_ADLR};
+                   BLOB_ADPT = blob_tag('A', 'D', 'P', 'T'), BLOB_ADLR = blob_tag('A', 'D', 'L', 'R'), BLOB_SKCH = blob_tag('S', 'K', 'C', 'H');
+constexpr uint32_t BLOB_ORDER[] = {BLOB_CHAN, BLOB_MASS, BLOB_HIST, BLOB_DMOM, BLOB_ACOV, BLOB_COV, BLOB_ADPT, BLOB_ADLR, BLOB_SKCH};
 constexpr size_t BLOB_HEADER = 64, BLOB_ENTRY = 24;
 constexpr char BLOB_MAGIC[8] = {'H', 'M', 'C', 'M', 'T', 'C', 'K', '\0'};
 static_assert(sizeof(double) == 8 && sizeof(long long) == 8, "a blob's fields are 8 bytes");
@@ -1959,6 +2256,13 @@ static std::vector<BlobSection> chain_blob_plan(hmcmt_ctx* ctx) {
             t.dev(L.d_X, rows * n * D); t.dev(L.d_G, rows * n * D);
             out.push_back(std::move(t));
         }
+    }
+    if (C.sketch.on) {                                       // (the last of the table: every blob without a sketch keeps its bytes)
+        const auto& K = C.sketch;
+        BlobSection s; s.tag = BLOB_SKCH;
+        s.i(K.ell); s.i(K.fill); s.i(K.count); s.i(K.shrinks); s.i(K.pivotGiven ? 1 : 0); s.f(K.Delta);
+        s.dev(K.d_x0, n * D); s.dev(K.d_tot, n * D); s.dev(K.d_q, n * D); s.dev(K.d_B, (uint64_t)K.fill * n * D);
+        out.push_back(std::move(s));
     }
     return out;
 }
@@ -2121,6 +2425,7 @@ struct BlobChain {
              const unsigned char *mean, *m2; } adapt{};
     struct { bool on; hmcmt_adapt_lowrank_options opt; long long winStart, stride; int stored, skipped, closedStored, rows;
              hmcmt_adapt_lowrank_info last; const unsigned char *X, *G; } lr{};
+    struct { bool on, given; int ell, fill; long long count, shrinks; double Delta; const unsigned char *x0, *tot, *q, *B; } sketch{};
 };
 
 static bool blob_finite(const unsigned char* p, uint64_t n, bool positive) {
@@ -2276,6 +2581,21 @@ static int chain_blob_check(hmcmt_ctx* ctx, const unsigned char* b, const BlobPa
         L.X = c.arr((uint64_t)rows * n * D); L.G = c.arr((uint64_t)rows * n * D);
         if (!c.ok || c.left) return bad("ADLR: wrong length");
     }
+    if (const BlobEntry* e = P.find(BLOB_SKCH)) {
+        BlobCursor c(b, *e);
+        auto& K = R.sketch;
+        K.on = true;
+        const long long ell = c.i(), fill = c.i(); K.count = c.i(); K.shrinks = c.i(); const long long given = c.i(); K.Delta = c.f();
+        // (a commit that fills the buffer shrinks it in the same call: a saved fill is below 2 ell, and at least ell behind a shrink)
+        if (!c.ok || ell < CHAIN_SKETCH_ELL_MIN || ell > CHAIN_SKETCH_ELL_MAX || fill < 0 || fill >= 2 * ell || K.count < 0 || K.shrinks < 0 ||
+            (given != 0 && given != 1) || !std::isfinite(K.Delta) || K.Delta < 0.0 || (K.shrinks == 0 ? (fill != K.count || K.Delta != 0.0) : (fill < ell || K.count < 2 * ell)))
+            return bad("SKCH: need 2 <= ell <= 64, 0 <= fill < 2 ell, counters that belong together and a finite Delta >= 0");
+        K.ell = (int)ell; K.fill = (int)fill; K.given = given != 0;
+        K.x0 = c.arr(n * D); K.tot = c.arr(n * D); K.q = c.arr(n * D); K.B = c.arr((uint64_t)fill * n * D);
+        if (!c.ok || c.left) return bad("SKCH: wrong length");
+        if (!blob_finite(K.x0, n, false) || !blob_finite(K.tot, n, false) || !blob_finite(K.q, n, false) || !blob_finite(K.B, (uint64_t)fill * n, false))
+            return bad("SKCH: a pivot, a sum or a row is not finite");
+    }
     return 0;
 }
 
@@ -2403,6 +2723,20 @@ static int chain_blob_build(hmcmt_ctx* ctx, const BlobChain& R) {
         }
         A.begun = true;
         A.active = R.adapt.active;
+    }
+    if (R.sketch.on) {
+        auto& K = C.sketch;
+        const size_t rows = (size_t)2 * R.sketch.ell + 1;
+        const size_t stage = std::max((size_t)R.sketch.ell * 2 * R.sketch.ell, rows * (size_t)HMCMT_MASS_RANK_MAX);
+        if ((rc = make(K.allocs, (void**)&K.d_B, rows * vb, R.sketch.B, (size_t)R.sketch.fill * vb)) ||
+            (rc = make(K.allocs, (void**)&K.d_x0, vb, R.sketch.x0, vb)) || (rc = make(K.allocs, (void**)&K.d_tot, vb, R.sketch.tot, vb)) ||
+            (rc = make(K.allocs, (void**)&K.d_q, vb, R.sketch.q, vb)) ||
+            (rc = chain_acc_zeroed(ctx, fn, K.allocs, (void**)&K.d_K, rows * rows * D)) ||
+            (rc = chain_acc_zeroed(ctx, fn, K.allocs, (void**)&K.d_T, stage * D))) return rc;
+        K.hK.assign(rows * rows, 0.0);
+        K.ell = R.sketch.ell; K.fill = R.sketch.fill; K.count = R.sketch.count; K.shrinks = R.sketch.shrinks; K.Delta = R.sketch.Delta;
+        K.pivotGiven = R.sketch.given;
+        K.on = true;
     }
     HIPCHK(hipStreamSynchronize(st));                        // (the caller's blob is free again on return)
     HIPCHK(hipGetLastError());

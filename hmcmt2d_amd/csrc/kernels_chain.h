@@ -282,3 +282,104 @@ __global__ __launch_bounds__(256) void k_adapt_lr_sign(int nAC, double* __restri
     __syncthreads();                                         // (every thread has read u[top] before its owner flips it)
     for (int a = threadIdx.x; a < nAC; a += 256) u[a] = -u[a];
 }
+
+// ---- the row sketch of the committed models (hmcmt_chain_sketch_*, hmcmt_chain_pca; arithmetic and its order in hmcmt_items.h:
+// item_chain_sketch_*) ----------------------------------------------------------------------------------------------------------------
+// Per counted commit one launch of nAC threads (k_chain_sketch_commit); per ell commits k_chain_sketch_gram, one download of K, one
+// upload of T and k_chain_sketch_shrink; per hmcmt_chain_pca k_chain_sketch_mean, k_chain_sketch_gram, one download, one upload,
+// k_chain_sketch_lift and k_adapt_lr_sign.  The Gram kernel is k_adapt_lr_gram's tiling over plain rows (a sibling, not a template
+// of it: that kernel forms its rows on the fly from four arrays, this one reads them, and a shared body would hide both), in plain
+// fp64 fma for the reason recorded above k_adapt_lr_gram: it runs once per ell commits and its host instantiation is bit for bit.
+struct SketchRows {
+    int nAC, nrows, nw;                  // cells, rows of B taken, rows of the operand (nw = nrows, or nrows + 1 with the extra row)
+    const double* B;                     // [.][nAC]
+    const double* extra;                 // [nAC] the operand's last row, or nullptr
+};
+// one counted commit: thread a owns cell a's pivot, sums and its double in the row of this commit
+__global__ __launch_bounds__(256) void k_chain_sketch_commit(long long n, long long t, int pivotGiven, const double* __restrict__ m,
+                                                             double* __restrict__ x0, double* __restrict__ tot, double* __restrict__ q,
+                                                             double* __restrict__ brow) {
+    const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (a < n) item_chain_sketch_commit(m, x0, tot, q, brow, t, pivotGiven, a);
+}
+// K = W W' [nw][nw]: workgroup b owns the tile (bi, bj), bi <= bj, of the upper block triangle and writes its mirror; thread (ti, tj)
+// owns K[i][j] and walks ALL cells upwards, ADAPT_LR_STRIP at a time through LDS, consecutive threads walking the cells of a row
+__global__ __launch_bounds__(256) void k_chain_sketch_gram(SketchRows w, double* __restrict__ K) {
+    __shared__ double Ws[2][ADAPT_LR_TILE][ADAPT_LR_STRIP + 1];
+    const int N = w.nw, T = (N + ADAPT_LR_TILE - 1) / ADAPT_LR_TILE;
+    int t = blockIdx.x, bi = 0;
+    while (t >= T - bi) { t -= T - bi; ++bi; }
+    const int bj = bi + t;
+    const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
+    double acc = 0.0;
+    for (int a0 = 0; a0 < w.nAC; a0 += ADAPT_LR_STRIP) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 2 * ADAPT_LR_TILE * ADAPT_LR_STRIP / 256; ++q) {
+            const int e = threadIdx.x + 256 * q;
+            const int blk = e / (ADAPT_LR_TILE * ADAPT_LR_STRIP), row = (e / ADAPT_LR_STRIP) % ADAPT_LR_TILE, col = e % ADAPT_LR_STRIP;
+            const int gi = (blk ? bj : bi) * ADAPT_LR_TILE + row, a = a0 + col;
+            Ws[blk][row][col] = (gi < N && a < w.nAC) ? item_chain_sketch_row(w.B, w.extra, w.nAC, w.nrows, gi)[a] : 0.0;
+        }
+        __syncthreads();
+        const int lim = min(ADAPT_LR_STRIP, w.nAC - a0);
+        for (int c = 0; c < lim; ++c) acc = item_adapt_lr_dot(Ws[0][ti][c], Ws[1][tj][c], acc);
+    }
+    const int i = bi * ADAPT_LR_TILE + ti, j = bj * ADAPT_LR_TILE + tj;
+    if (i < N && j < N) {
+        K[(long long)i * N + j] = acc;
+        if (bi != bj) K[(long long)j * N + i] = acc;         // (the diagonal tile's mirror entry has its own thread: the same products, the same bits)
+    }
+}
+// B <- T B in place, rows ell .. 2 ell - 1 zeroed.  Thread = one cell a: it first copies ALL of column a (2 ell doubles, too many for
+// registers) into its own column of the workgroup's LDS ([j][thread]: a wavefront's read of one j is 512 contiguous bytes, no bank
+// conflict), so every later write of column a finds its inputs already taken -- that is what makes the update safe in place.  No
+// thread reads another's column: no barrier.  T[i][j] is the same address for every lane (a scalar load); CHAIN_SKETCH_CHUNK output
+// rows share one LDS read of col[j].  LDS: 2 ell * CHAIN_SKETCH_COLS * 8 bytes, dynamic (64 KiB at ell = 64: two workgroups per CU).
+__global__ __launch_bounds__(CHAIN_SKETCH_COLS) void k_chain_sketch_shrink(long long nAC, int ell, const double* __restrict__ T, double* B) {
+    extern __shared__ double sketchCol[];
+    const long long a = (long long)blockIdx.x * CHAIN_SKETCH_COLS + threadIdx.x;
+    if (a >= nAC) return;
+    const int n2 = 2 * ell;
+    double* col = sketchCol + threadIdx.x;
+    for (int j = 0; j < n2; ++j) col[j * CHAIN_SKETCH_COLS] = B[(long long)j * nAC + a];
+    for (int i0 = 0; i0 < ell; i0 += CHAIN_SKETCH_CHUNK) {
+        double acc[CHAIN_SKETCH_CHUNK];
+#pragma unroll
+        for (int q = 0; q < CHAIN_SKETCH_CHUNK; ++q) acc[q] = 0.0;
+        for (int j = 0; j < n2; ++j) {
+            const double c = col[j * CHAIN_SKETCH_COLS];
+#pragma unroll
+            for (int q = 0; q < CHAIN_SKETCH_CHUNK; ++q)
+                if (i0 + q < ell) acc[q] = fma(T[(long long)(i0 + q) * n2 + j], c, acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < CHAIN_SKETCH_CHUNK; ++q)
+            if (i0 + q < ell) B[(long long)(i0 + q) * nAC + a] = acc[q];
+    }
+    for (int i = ell; i < n2; ++i) B[(long long)i * nAC + a] = 0.0;
+}
+// the read-out's mean row sqrt(N) ybar into the staging row of B, one thread per cell
+__global__ __launch_bounds__(256) void k_chain_sketch_mean(long long n, double dN, double sqN, const double* __restrict__ tot, double* __restrict__ brow) {
+    const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (a < n) brow[a] = item_chain_sketch_mean(tot[a], dN, sqN);
+}
+// U[k][a] = sum_i coef[i][k] W[i][a]: one thread per cell, MASS_LR_CHUNK directions side by side
+__global__ __launch_bounds__(256) void k_chain_sketch_lift(SketchRows w, const double* __restrict__ coef, int r, double* __restrict__ U) {
+    const int a = TID1;
+    if (a >= w.nAC) return;
+    for (int k0 = 0; k0 < r; k0 += MASS_LR_CHUNK) {
+        double acc[MASS_LR_CHUNK];
+#pragma unroll
+        for (int q = 0; q < MASS_LR_CHUNK; ++q) acc[q] = 0.0;
+        for (int i = 0; i < w.nw; ++i) {
+            const double wi = item_chain_sketch_row(w.B, w.extra, w.nAC, w.nrows, i)[a];
+#pragma unroll
+            for (int q = 0; q < MASS_LR_CHUNK; ++q)
+                if (k0 + q < r) acc[q] = item_adapt_lr_dot(coef[(long long)i * r + k0 + q], wi, acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < MASS_LR_CHUNK; ++q)
+            if (k0 + q < r) U[(long long)(k0 + q) * w.nAC + a] = acc[q];
+    }
+}

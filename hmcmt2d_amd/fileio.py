@@ -402,3 +402,39 @@ def readCorrelationModel(path, invParam):
     """The map getCorrelationModel wrote, back as corr[nparam] (to the three digits a .model file keeps)."""
     sigma = readEMModel2D(path).sigma
     return sigma[invParam.activeIdx] - invParam.bgModel[invParam.activeIdx]
+
+
+def getPCAModels(path, sketch_stats, mtMesh, invParam, write=True):
+    """The principal components of the posterior as .model files: sketch_stats = hmcstats.sketch of runHMCSampler(device_chain=True,
+    sketch={...}) (or any dict with lam, U, err and var, e.g. sampler.pcaFromSketch's results put into one).  Component k goes to
+    `path`.pc<k+1>.model: every active cell holds the unit direction's entry (in [-1, 1], its largest one positive) on top of the
+    background, the way getCorrelationModel writes its map; `path`.pca.txt is the table, one line per component: k, lam (the variance
+    of ln sigma along it), explained (lam over the total variance) and err (the bound on lam's distance from the exact eigenvalue).
+    Returns (lam[r], U[r, nparam], explained[r], err)."""
+    nparam = len(invParam.activeIdx)
+    lam = np.asarray(sketch_stats["lam"], dtype=np.float64)
+    U = np.asarray(sketch_stats["U"], dtype=np.float64)
+    if U.ndim != 2 or U.shape != (len(lam), nparam):
+        raise ValueError("getPCAModels: needs lam[r] and U[r, nparam] over every active cell")
+    total = float(np.asarray(sketch_stats["var"], dtype=np.float64).sum())
+    explained = lam / total if total > 0 else np.zeros_like(lam)
+    err = float(sketch_stats["err"])
+    if write:
+        for k in range(len(lam)):
+            sigma = invParam.bgModel.copy(); sigma[invParam.activeIdx] += U[k]
+            mtMesh.sigma = sigma
+            writeEMModel2D(f"{path}.pc{k + 1}.model", mtMesh)
+        with open(f"{path}.pca.txt", "w") as f:
+            f.write("# component  lam  explained  err\n")
+            for k in range(len(lam)):
+                f.write(f"{k + 1:d} {lam[k]:.16e} {explained[k]:.16e} {err:.16e}\n")
+    return lam, U.copy(), explained, err
+
+
+def readPCAModels(path, invParam):
+    """What getPCAModels wrote, back as (lam[r], U[r, nparam], explained[r], err): the table in full precision, the directions to the
+    digits a .model file keeps."""
+    table = np.loadtxt(f"{path}.pca.txt", ndmin=2)
+    idx = invParam.activeIdx
+    U = np.array([readEMModel2D(f"{path}.pc{int(k)}.model").sigma[idx] - invParam.bgModel[idx] for k in table[:, 0]]).reshape(len(table), len(idx))
+    return table[:, 1].copy(), U, table[:, 2].copy(), (float(table[0, 3]) if len(table) else 0.0)

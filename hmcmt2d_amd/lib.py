@@ -110,6 +110,15 @@ class AdaptLowrankInfo(C.Structure):
                 ("defect", C.c_double), ("host_ms", C.c_double)]
 
 
+class SketchInfo(C.Structure):
+    """hmcmt_sketch_info (include/hmcmt.h): the row sketch of the chain's commit as it stands."""
+    _fields_ = [("count", C.c_int64), ("ell", C.c_int32), ("fill", C.c_int32), ("shrinks", C.c_int64), ("Delta", C.c_double),
+                ("pivot_given", C.c_int32), ("reserved_", C.c_int32)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved_"}
+
+
 class ChainBlobHeader(C.Structure):
     """hmcmt_chain_blob_header (include/hmcmt.h): what hmcmt_chain_blob_info reports of a chain's checkpoint blob."""
     _fields_ = [("version", C.c_uint32), ("nsections", C.c_uint32), ("total_bytes", C.c_uint64), ("nAC", C.c_int64), ("nData", C.c_int64),
@@ -251,6 +260,16 @@ def load_library():
     lib.hmcmt_chain_corr.argtypes = [vp, vp, C.c_int32]
     lib.hmcmt_debug_chain_cov_time.argtypes = [vp, C.c_int32, c_double_p, c_int64_p]
     lib.hmcmt_debug_chain_cov_time.restype = C.c_int
+    lib.hmcmt_chain_sketch_begin.argtypes = [vp, C.c_int32, c_double_p]
+    lib.hmcmt_chain_sketch.argtypes = [vp, C.POINTER(SketchInfo), vp, vp, vp, C.c_int32]
+    lib.hmcmt_chain_pca.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), vp, vp, C.POINTER(C.c_double), C.c_int32]
+    lib.hmcmt_debug_chain_sketch.argtypes = [vp, C.c_int32, C.c_int64, c_double_p, c_double_p, C.POINTER(SketchInfo), vp, vp, vp, vp, C.c_int32,
+                                             vp, vp]
+    lib.hmcmt_debug_chain_sketch_sums.argtypes = [vp, vp, vp, vp, C.c_int32]
+    lib.hmcmt_debug_chain_sketch_sums.restype = C.c_int
+    lib.hmcmt_debug_chain_sketch_time.argtypes = [vp, C.c_int32, c_double_p, c_int64_p, C.POINTER(C.c_double)]
+    for name in ("hmcmt_chain_sketch_begin", "hmcmt_chain_sketch", "hmcmt_chain_pca", "hmcmt_debug_chain_sketch", "hmcmt_debug_chain_sketch_time"):
+        getattr(lib, name).restype = C.c_int
     lib.hmcmt_rng_draw.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     lib.hmcmt_rng_normals.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int64, C.c_int64, c_double_p]
     lib.hmcmt_chain_seed.argtypes = [vp, C.c_uint64, C.c_uint32]
@@ -309,6 +328,10 @@ ACOV_MAXLAG = 1023    # include/hmcmt.h: maxlag of hmcmt_chain_acov_begin
 # ... and the fourth one: posterior covariance and correlation between cells
 CHAIN_COV_SYMBOLS = ["hmcmt_chain_cov_begin", "hmcmt_chain_cov", "hmcmt_chain_corr"]
 COV_BATCH_MAX = 16    # include/hmcmt.h: HMCMT_COV_BATCH_MAX
+# ... and the fifth one: a frequent-directions row sketch of the committed models and its principal components
+CHAIN_SKETCH_SYMBOLS = ["hmcmt_chain_sketch_begin", "hmcmt_chain_sketch", "hmcmt_chain_pca"]
+SKETCH_ELL_MAX = 64   # include/hmcmt.h: HMCMT_SKETCH_ELL_MAX
+MASS_RANK_MAX = 32    # include/hmcmt.h: HMCMT_MASS_RANK_MAX
 # ... and the warm-up: the chain's step size and diagonal mass between two steps, and their adaptation
 CHAIN_ADAPT_SYMBOLS = ["hmcmt_chain_set_dt", "hmcmt_chain_set_mass_diag", "hmcmt_chain_mass_diag", "hmcmt_default_adapt_options",
                        "hmcmt_chain_adapt_begin", "hmcmt_chain_adapt_info", "hmcmt_chain_adapt_end"]
@@ -328,7 +351,7 @@ ADAPT_LOWRANK_KEYS = ("rank", "max_samples", "cutoff", "gamma")
 ADAPT_LOWRANK_NMIN, ADAPT_LOWRANK_NMAX = 4, 128   # include/hmcmt.h: max_samples of hmcmt_adapt_lowrank_options
 ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_SKETCH_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -341,7 +364,8 @@ DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "
                  "hmcmt_persist_width", "hmcmt_persist_order", "hmcmt_persist_pack", "hmcmt_mass_info", "hmcmt_debug_chain_acov_time",
                  "hmcmt_debug_chain_cov_time", "hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess", "hmcmt_debug_nuts_leaf",
                  "hmcmt_debug_nuts_iters", "hmcmt_debug_adapt_lowrank", "hmcmt_debug_adapt_lowrank_rows",
-                 "hmcmt_debug_adapt_lowrank_time"]
+                 "hmcmt_debug_adapt_lowrank_time", "hmcmt_debug_chain_sketch", "hmcmt_debug_chain_sketch_sums",
+                 "hmcmt_debug_chain_sketch_time"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
 
 
@@ -938,6 +962,8 @@ class HipContext:
                 self._acov_shape = (int(head[2]) + 1, int(head[0]))
             elif tag == "COV ":
                 self._cov_shape = (int(head[0]), self.nAC)
+            elif tag == "SKCH":
+                self._sketch_ell = int(head[0])
             at += nbytes
 
     # -- the chain's own random numbers (hmcmt_chain_seed, hmcmt_chain_sample, hmcmt_chain_run) ----
@@ -1211,6 +1237,92 @@ class HipContext:
         mean, var, cov = np.empty(shape[1]), np.empty(shape[1]), np.empty(shape)
         self._check(self.lib.hmcmt_chain_cov(self.h, C.byref(n), mean.ctypes.data, var.ctypes.data, cov.ctypes.data, 0))
         return int(n.value), mean, var, cov
+
+    # -- posterior principal components by a row sketch (hmcmt_chain_sketch_*, hmcmt_chain_pca) --
+    def chain_sketch_begin(self, ell=32, pivot=None):
+        """Starts the frequent-directions sketch of the committed models: 2 <= ell <= 64 directions kept through every shrink,
+        2 ell rows of nAC doubles on the device.  pivot[nAC] or None (the model of the first counted commit); sketches of several
+        chains merge only under one given pivot (include/hmcmt.h has the algorithm and its guarantee)."""
+        pv = None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64)
+        if pv is not None and pv.shape != (self.nAC,):
+            raise ValueError(f"chain_sketch_begin: pivot has shape {pv.shape}, not ({self.nAC},)")
+        self._check(self.lib.hmcmt_chain_sketch_begin(self.h, int(ell), None if pv is None else _dp(pv)))
+        self._sketch_ell = int(ell)
+
+    def chain_sketch_info(self):
+        """hmcmt_sketch_info as a dict: count, ell, fill, shrinks, Delta, pivot_given."""
+        info = SketchInfo()
+        self._check(self.lib.hmcmt_chain_sketch(self.h, C.byref(info), None, None, None, 0))
+        return info.as_dict()
+
+    def chain_sketch(self):
+        """The sketch as it stands, a dict: the fields of chain_sketch_info, mean[nAC], var[nAC] (biased, the formulas of chain_cov),
+        rows[fill, nAC] (unshrunk rows included) and x0, tot, q (chain_sketch_sums).  With A the rows y_t = m_t - x0 of the counted commits: 0 <= A'A - rows'rows <= Delta I."""
+        info = self.chain_sketch_info()
+        mean, var, rows = np.empty(self.nAC), np.empty(self.nAC), np.empty((info["fill"], self.nAC))
+        got = SketchInfo()
+        self._check(self.lib.hmcmt_chain_sketch(self.h, C.byref(got), mean.ctypes.data, var.ctypes.data, rows.ctypes.data if rows.size else None, 0))
+        out = got.as_dict()
+        out.update(mean=mean, var=var, rows=rows)
+        out.update(self.chain_sketch_sums())
+        return out
+
+    def chain_sketch_sums(self):
+        """{x0, tot, q} [nAC] of the running sketch -- the pivot, the sum of y and the sum of y^2 that mean and var are made of and that
+        pcaFromSketch and mergeSketches need (hmcmt_debug_chain_sketch_sums)."""
+        x0, tot, q = np.empty(self.nAC), np.empty(self.nAC), np.empty(self.nAC)
+        self._check(self.lib.hmcmt_debug_chain_sketch_sums(self.h, x0.ctypes.data, tot.ctypes.data, q.ctypes.data, 0))
+        return {"x0": x0, "tot": tot, "q": q}
+
+    def chain_sketch_device(self, d_mean=None, d_var=None, d_rows=None):
+        """As chain_sketch into device pointers (ints; each may be None; d_rows has room for 2 ell rows); returns the info dict."""
+        info = SketchInfo()
+        self._check(self.lib.hmcmt_chain_sketch(self.h, C.byref(info), d_mean, d_var, d_rows, 1))
+        return info.as_dict()
+
+    def chain_pca(self, rank=8, d_lambda=None, d_U=None):
+        """(lam[kept], U[kept, nAC], err): the leading eigenpairs of the sketch's centred covariance estimate, descending, and the
+        bound err = Delta / N within which every lam[k] lies of the exact k-th eigenvalue.  With d_lambda / d_U (device pointers as
+        ints, room for rank rows) the results stay on the device and (kept, err) is returned."""
+        kept, err = C.c_int32(), C.c_double()
+        if d_lambda is not None or d_U is not None:
+            self._check(self.lib.hmcmt_chain_pca(self.h, int(rank), C.byref(kept), d_lambda, d_U, C.byref(err), 1))
+            return int(kept.value), float(err.value)
+        rank = int(rank)
+        lam, U = np.empty(max(rank, 1)), np.empty((max(rank, 1), self.nAC))
+        self._check(self.lib.hmcmt_chain_pca(self.h, rank, C.byref(kept), lam.ctypes.data, U.ctypes.data, C.byref(err), 0))
+        k = int(kept.value)
+        return lam[:k].copy(), U[:k].copy(), float(err.value)
+
+    def chain_sketch_timing(self, enable=None):
+        """Measurement only (hmcmt_debug_chain_sketch_time): as chain_cov_timing, classes "commit" and "shrink" (the Gram and the
+        shrink kernel: two launches per shrink), plus "host_ms", the host milliseconds of the shrinks' eigenproblems."""
+        host = C.c_double()
+        ms, launches = np.zeros(2), np.zeros(2, dtype=np.int64)
+        self._check(self.lib.hmcmt_debug_chain_sketch_time(self.h, -1 if enable is None else int(bool(enable)), _dp(ms),
+                                                           launches.ctypes.data_as(c_int64_p), C.byref(host)))
+        out = {k: {"ms": float(ms[i]), "launches": int(launches[i])} for i, k in enumerate(("commit", "shrink"))}
+        out["host_ms"] = float(host.value)
+        return out
+
+    def debug_chain_sketch(self, rows, ell, pivot=None, max_shrinks=None):
+        """Test hook (hmcmt_debug_chain_sketch): rows [n, nAC] through the chain's commit and shrink launches without a chain.  Returns
+        a dict: the info fields, x0, tot, q [nAC], rows [fill, nAC] and, per shrink, K [2 ell, 2 ell] and T [ell, 2 ell]."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.nAC:
+            raise ValueError(f"debug_chain_sketch: rows has shape {rows.shape}, not (n, {self.nAC})")
+        n, ell = rows.shape[0], int(ell)
+        pv = None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64)
+        ns = max(0, (n - ell) // ell) if max_shrinks is None else int(max_shrinks)
+        info = SketchInfo()
+        x0, tot, q, B = np.empty(self.nAC), np.empty(self.nAC), np.empty(self.nAC), np.zeros((2 * max(ell, 1), self.nAC))
+        K, T = np.zeros((max(ns, 1), 2 * ell, 2 * ell)), np.zeros((max(ns, 1), ell, 2 * ell))
+        self._check(self.lib.hmcmt_debug_chain_sketch(self.h, ell, n, _dp(rows), None if pv is None else _dp(pv), C.byref(info),
+                                                      x0.ctypes.data, tot.ctypes.data, q.ctypes.data, B.ctypes.data, ns, K.ctypes.data, T.ctypes.data))
+        out = info.as_dict()
+        got = min(ns, out["shrinks"])
+        out.update(x0=x0, tot=tot, q=q, rows=B[:out["fill"]].copy(), K=K[:got], T=T[:got])
+        return out
 
     def chain_cov_device(self, d_mean=None, d_var=None, d_cov=None):
         """The same into device pointers (int; each may be None) to nAC, nAC and nrow * nAC doubles; returns count."""

@@ -617,6 +617,160 @@ def mergeCov(list_of_cov):
             "corr": _corr_of(cov, var, r)}
 
 
+# ---- the row sketch of the committed models (hmcmt_chain_sketch_*, include/hmcmt.h) in numpy --------------------------------------------
+def _sketch_shrink(B, ell):
+    """one shrink of a full buffer B[2 ell, n] in place: with K = B B' = V diag(d) V', d descending, delta = max(d[ell], 0) and
+    c_i = sqrt((d_i - delta) / d_i) where d_i > delta (else 0), rows 0 .. ell - 1 become c_i v_i' B and the rest zero.  Returns delta."""
+    d, V = np.linalg.eigh(B @ B.T)
+    d, V = d[::-1], V[:, ::-1]
+    delta = max(float(d[ell]), 0.0)
+    big = d[:ell] > delta
+    c = np.where(big, np.sqrt(np.where(big, d[:ell] - delta, 0.0) / np.where(big, d[:ell], 1.0)), 0.0)
+    B[:ell] = (c[:, None] * V[:, :ell].T) @ B
+    B[ell:] = 0.0
+    return delta
+
+
+def _sketch_dict(ell, B, fill, count, shrinks, Delta, x0, tot, q, given):
+    N = float(max(count, 1))
+    return {"count": int(count), "ell": int(ell), "fill": int(fill), "shrinks": int(shrinks), "Delta": float(Delta),
+            "pivot_given": int(bool(given)), "x0": x0, "tot": tot, "q": q, "mean": x0 + tot / N, "var": (q - tot * tot / N) / N,
+            "rows": B[:fill].copy()}
+
+
+def sketchOf(x, ell, pivot=None):
+    """The library's frequent-directions sketch (hmcmt_chain_sketch_begin, include/hmcmt.h) of a sample history x[nparam, N] (columns =
+    committed models, as hmcmodel), in numpy with numpy.linalg.eigh: rows y_t = x_t - x0 (x0 = pivot, or the first column) enter a
+    buffer of 2 ell rows, which is shrunk to ell rows whenever it is full.  Returns a dict like hmcstats.sketch without the principal
+    components: count, ell, fill, shrinks, Delta, pivot_given, x0, tot, q, mean, var, rows[fill, nparam].  With A the N rows y_t:
+    0 <= A'A - rows'rows <= Delta I and Delta <= |A - A_k|_F^2 / (ell - k) for every k < ell."""
+    x = np.asarray(x, dtype=np.float64)
+    ell = int(ell)
+    if x.ndim != 2 or x.shape[1] < 1 or not 2 <= ell <= 64:
+        raise ValueError("sketchOf: needs x[nparam, N] with at least one sample and 2 <= ell <= 64")
+    n, N = x.shape
+    x0 = x[:, 0].copy() if pivot is None else np.array(pivot, dtype=np.float64)
+    if x0.shape != (n,) or not np.isfinite(x0).all():
+        raise ValueError(f"sketchOf: pivot must hold {n} finite entries")
+    B, tot, q = np.zeros((2 * ell, n)), np.zeros(n), np.zeros(n)
+    fill, shrinks, Delta = 0, 0, 0.0
+    for t in range(N):
+        y = x[:, t] - x0
+        tot += y
+        q += y * y
+        B[fill] = y
+        fill += 1
+        if fill == 2 * ell:
+            Delta += _sketch_shrink(B, ell)
+            shrinks += 1
+            fill = ell
+    return _sketch_dict(ell, B, fill, N, shrinks, Delta, x0, tot, q, pivot is not None)
+
+
+def _sketch_sums(sketch, who):
+    """(N, ybar[nparam]) of a sketch dict: from its x0 and tot, or from mean - x0"""
+    N = int(sketch["count"])
+    if sketch.get("tot") is not None:
+        return N, np.asarray(sketch["tot"], dtype=np.float64) / N
+    if sketch.get("x0") is None:
+        raise ValueError(f"{who}: the sketch carries neither tot nor its pivot x0")
+    return N, np.asarray(sketch["mean"], dtype=np.float64) - np.asarray(sketch["x0"], dtype=np.float64)
+
+
+def _sketch_eig(W, rank):
+    """the `rank` largest positive eigenpairs (theta descending, U[r, n] rows) of W' J W, J = diag(1, ..., 1, -1), by the Gram route
+    of hmcmt_chain_pca: G = W W' = Q Lambda Q' with Lambda_i > 1e-10 Lambda_max kept, S = Lambda^1/2 Q' J Q Lambda^1/2 = Z Theta Z',
+    U = (Q Lambda^-1/2 Z_sel)' W; each direction's entry of largest magnitude is positive"""
+    lamG, Q = np.linalg.eigh(W @ W.T)
+    if not lamG[-1] > 0.0:
+        return np.zeros(0), np.zeros((0, W.shape[1]))
+    keep = lamG > 1e-10 * lamG[-1]
+    lamG, Q = lamG[keep], Q[:, keep]
+    J = np.ones(W.shape[0])
+    J[-1] = -1.0
+    sq = np.sqrt(lamG)
+    S = sq[:, None] * (Q.T @ (J[:, None] * Q)) * sq[None, :]
+    th, Z = np.linalg.eigh(0.5 * (S + S.T))
+    order = [i for i in np.argsort(-th, kind="stable") if th[i] > 0.0][:int(rank)]
+    U = np.ascontiguousarray(((Q / sq[None, :]) @ Z[:, order]).T @ W)
+    for k in range(len(order)):
+        if U[k, np.argmax(np.abs(U[k]))] < 0:
+            U[k] = -U[k]
+    return th[order], U
+
+
+def pcaFromSketch(sketch, rank=8):
+    """(lam[r], U[r, nparam], err) from a sketch dict (sketchOf, mergeSketches, hmcstats.sketch): the leading eigenpairs of the centred
+    covariance estimate (rows'rows - N ybar ybar') / N by hmcmt_chain_pca's Gram route in numpy, lam descending, and err = Delta / N:
+    every lam[k] lies within err of the k-th eigenvalue of the exact (biased) covariance of the counted commits."""
+    N, ybar = _sketch_sums(sketch, "pcaFromSketch")
+    if N < 2 or not 1 <= int(rank):
+        raise ValueError("pcaFromSketch: needs a sketch of two commits at least and rank >= 1")
+    W = np.vstack([np.asarray(sketch["rows"], dtype=np.float64), np.sqrt(float(N)) * ybar])
+    th, U = _sketch_eig(W, rank)
+    return th / N, U, float(sketch["Delta"]) / N
+
+
+def mergeSketches(list_of_sketches):
+    """Pools the sketches of several chains (hmcstats.sketch, sketchOf): they must share ell and a GIVEN pivot, byte for byte, since
+    their rows are differences from it.  The rows are stacked into one buffer of 2 ell rows, shrunk whenever it is full; tot, q, N and
+    Delta add, and Delta also takes the merge's own shrinks, so the pooled guarantee 0 <= A'A - rows'rows <= Delta I holds for the
+    concatenated rows.  Returns a dict like sketchOf's, with nchains."""
+    chains = [c for c in list_of_sketches if c is not None and int(c["count"]) > 0]
+    if not chains:
+        raise ValueError("mergeSketches: no chain with a counted sample")
+    ell = int(chains[0]["ell"])
+    x0 = np.ascontiguousarray(chains[0]["x0"], dtype=np.float64)
+    for c in chains:
+        if not int(c["pivot_given"]) or c.get("x0") is None or c.get("tot") is None or c.get("q") is None:
+            raise ValueError("mergeSketches: every sketch needs a given pivot and its x0, tot and q")
+        if int(c["ell"]) != ell or np.ascontiguousarray(c["x0"], dtype=np.float64).tobytes() != x0.tobytes():
+            raise ValueError("mergeSketches: the sketches differ in ell or in their pivot")
+    n = x0.size
+    B, tot, q = np.zeros((2 * ell, n)), np.zeros(n), np.zeros(n)
+    fill, shrinks, Delta, N = 0, 0, 0.0, 0
+    for c in chains:
+        tot += np.asarray(c["tot"], dtype=np.float64)
+        q += np.asarray(c["q"], dtype=np.float64)
+        N += int(c["count"])
+        Delta += float(c["Delta"])
+        shrinks += int(c["shrinks"])
+        for row in np.asarray(c["rows"], dtype=np.float64):
+            B[fill] = row
+            fill += 1
+            if fill == 2 * ell:
+                Delta += _sketch_shrink(B, ell)
+                shrinks += 1
+                fill = ell
+    out = _sketch_dict(ell, B, fill, N, shrinks, Delta, x0.copy(), tot, q, True)
+    out["nchains"] = len(chains)
+    return out
+
+
+def lowRankMassFromSketch(sketch, invM=None, rank=8, cutoff=2.0):
+    """(invM[nparam], U[r, nparam], lam[r]) in the convention of lowRankMassFromSamples, from a sketch dict instead of a sample
+    history: the scales are `invM` where given, else the library's window rule on the sketch's variance; the directions are the
+    eigenpairs of S^-1 C S^-1, C = (rows'rows - N ybar ybar') / (N - 1), found in the sketch's span by hmcmt_chain_pca's Gram route.
+    At most `rank` pairs with lam > cutoff are kept, largest first.  Where nothing was shrunk it is lowRankMassFromSamples of the
+    same samples up to rounding; behind shrinks every lam is low by at most Delta / (N - 1) / min(invM).  The result can be handed to
+    runHMCSampler(mass_lowrank=...)."""
+    N, ybar = _sketch_sums(sketch, "lowRankMassFromSketch")
+    if N < 2 or int(rank) < 0:
+        raise ValueError("lowRankMassFromSketch: needs a sketch of two commits at least and rank >= 0")
+    nparam = ybar.size
+    if invM is None:
+        s2 = np.asarray(sketch["var"], dtype=np.float64) * (N / (N - 1.0)) * (N / (N + 5.0)) + 1e-3 * 5.0 / (N + 5.0)
+    else:
+        s2 = np.array(invM, dtype=np.float64)
+        if s2.shape != (nparam,) or not (np.isfinite(s2).all() and (s2 > 0).all()):
+            raise ValueError(f"lowRankMassFromSketch: invM must hold {nparam} finite positive entries")
+    W = np.vstack([np.asarray(sketch["rows"], dtype=np.float64), np.sqrt(float(N)) * ybar]) / np.sqrt(s2)[None, :]
+    th, U = _sketch_eig(W, max(int(rank), 1))
+    lam = th / (N - 1.0)
+    keep = [k for k in range(len(lam)) if lam[k] > cutoff][:int(rank)]
+    return s2, np.ascontiguousarray(U[keep]), lam[keep]
+
+
 ADAPT_KEYS = ("nwarmup", "mass", "delta", "gamma", "t0", "kappa", "init_buffer", "term_buffer", "base_window", "dt_min", "dt_max", "lowrank")
 
 
@@ -935,7 +1089,57 @@ class _WarmUp(ChainOutput):
         return out
 
 
-CHAIN_OUTPUTS = (_Histograms(), _DataMoments(), _EffectiveSampleSize(), _Covariance(), _WarmUp())
+class _Sketch(ChainOutput):
+    """`sketch={...}` (with device_chain): a frequent-directions row sketch of the committed models, streamed in the commit, and from
+    it the leading principal components of the posterior covariance -- the joint structure that `cov` gives only as a full matrix --
+    in 2 ell rows of nparam doubles.  Keys, all optional: `ell` (2 .. 64, default 32: directions kept through every shrink), `rank`
+    (1 .. 32, default 8: components returned) and `pivot` (nparam values the rows are differences from; default the first counted
+    model; sketches of several chains merge only under one given pivot).  hmcstats.sketch is a dict: count, ell, fill, shrinks, Delta,
+    pivot_given, x0, tot, q, mean, var, rows[fill, nparam], lam[r], U[r, nparam], err and explained = lam / var.sum().  Every lam[k]
+    lies within err = Delta / count of the exact k-th eigenvalue of the counted samples' covariance (hmcmt_chain_pca, include/hmcmt.h).
+    A chain that ends inside its burn-in gives count 0 and None for the arrays; one counted sample gives no components.  Where
+    the library refuses the components (HMCMT_EBREAKDOWN: directions not orthonormal to 1e-8, which a requested component whose
+    variance is lost in rounding beside the first can cause; ask for a smaller rank) lam, U and err stay None and `pca_error` holds
+    the library's message: pcaFromSketch still works on the rest.  The sketch
+    adds one wait per ell counted samples.  See sketchOf, pcaFromSketch, mergeSketches, lowRankMassFromSketch, fileio.getPCAModels.
+    The draws keep their order."""
+    name, field, keys, why = "sketch", "sketch", ("ell", "rank", "pivot"), "the sketch is streamed in the device chain's commit"
+
+    def check(self, value, hmcprior):
+        super().check(value, hmcprior)
+        from .lib import MASS_RANK_MAX, SKETCH_ELL_MAX
+        if not 2 <= int(value.get("ell", 32)) <= SKETCH_ELL_MAX or not 1 <= int(value.get("rank", 8)) <= MASS_RANK_MAX:
+            raise ValueError(f"runHMCSampler: sketch needs 2 <= ell <= {SKETCH_ELL_MAX} and 1 <= rank <= {MASS_RANK_MAX}")
+
+    def plan(self, value, env):
+        pivot = value.get("pivot")
+        return int(value.get("ell", 32)), int(value.get("rank", 8)), None if pivot is None else np.array(pivot, dtype=np.float64)
+
+    def begin(self, ctx, value, env):
+        state = self.plan(value, env)
+        ctx.chain_sketch_begin(state[0], state[2])
+        return state
+
+    def read(self, ctx, state, stats, env):
+        out = ctx.chain_sketch_info()
+        out.update({k: None for k in ("x0", "tot", "q", "mean", "var", "rows", "lam", "U", "err", "explained", "pca_error")})
+        if out["count"] > 0:
+            out.update(ctx.chain_sketch())
+        if out["count"] > 1:
+            from .lib import HmcmtError
+            try:
+                out["lam"], out["U"], out["err"] = ctx.chain_pca(state[1])
+            except HmcmtError as e:
+                if e.code != -11:                            # (HMCMT_EBREAKDOWN: the sketch stands, the components are refused)
+                    raise
+                out["pca_error"] = str(e)
+            else:
+                total = float(out["var"].sum())
+                out["explained"] = out["lam"] / total if total > 0 else np.zeros_like(out["lam"])
+        return out
+
+
+CHAIN_OUTPUTS = (_Histograms(), _DataMoments(), _EffectiveSampleSize(), _Covariance(), _Sketch(), _WarmUp())
 
 
 def _check_mass_lowrank(mass_lowrank, nparam):
@@ -1257,7 +1461,7 @@ def _run_device_chain(mtMesh, mtData, invParam, hmcprior, rng, rhoref, ctx, verb
 def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx: HipContext | None = None,
                   verbose=False, reuse_forward=True, device_leapfrog=False, device_id=None,
                   checkpoint=None, checkpoint_every=0, device_chain=False, keep_samples=True, hist=None, data_moments=False, ess=None,
-                  cov=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None, nuts=None, chain_checkpoint=None,
+                  cov=None, sketch=None, adapt=None, invM=None, mass_lowrank=None, library_rng=None, nuts=None, chain_checkpoint=None,
                   chain_checkpoint_every=0):
     """Returns (hmcmodel[nparam, nsamples], hmcstats, hmcdata[ndata, nsamples+1]).  The chain runs on GPU `device_id`
     (default: `default_device()`, i.e. LOCAL_RANK) unless a context is passed in.
@@ -1281,7 +1485,7 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     nuts, output value, invM or mass_lowrank -- is refused (ValueError), and so is the keyword with keep_samples=True: a sample
     history belongs to the host loop's `checkpoint=`.  A flush waits for the chain and writes the whole blob: choose k by the
     blob's size.
-    The optional outputs of the device chain -- hist=, data_moments=, ess=, cov=, adapt= -- are one entry of CHAIN_OUTPUTS each, and
+    The optional outputs of the device chain -- hist=, data_moments=, ess=, cov=, sketch=, adapt= -- are one entry of CHAIN_OUTPUTS each, and
     each entry's docstring is its paragraph here:
     {CHAIN_OUTPUTS}
     `invM=array` (with device_chain): the diagonal of M^-1 the chain starts with instead of ones, for example an earlier run's
@@ -1324,7 +1528,7 @@ def runHMCSampler(mtMesh, mtData, invParam, hmcprior, rng=None, rhoref=None, ctx
     if not keep_samples and not device_chain:
         raise ValueError("runHMCSampler: keep_samples=False needs device_chain=True (only the device chain streams the posterior moments)")
     # (every refusal before the context is touched and the first number is drawn)
-    outputs = {k: v for k, v in (("hist", hist), ("data_moments", {} if data_moments else None), ("ess", ess), ("cov", cov), ("adapt", adapt)) if v is not None}
+    outputs = {k: v for k, v in (("hist", hist), ("data_moments", {} if data_moments else None), ("ess", ess), ("cov", cov), ("sketch", sketch), ("adapt", adapt)) if v is not None}
     on = [out for out in CHAIN_OUTPUTS if out.name in outputs]
     needing = [(out.name, out.why) for out in on] + [(k, "it is the device chain's mass") for k, v in (("invM", invM), ("mass_lowrank", mass_lowrank))
                                                      if v is not None]
@@ -1431,11 +1635,41 @@ if runHMCSampler.__doc__:                                   # (python -OO has no
 
 
 # --------------------------------------------------------------------------------------------
-def gatherBlockFields(nparam, ncols, nsamples, ndata, with_moments):
-    """One chain's block in parallelHMCSampler's all-gather: its fields in order, (name, number of doubles).  Their sum is the block."""
+SKETCH_INFO_KEYS = ("count", "ell", "fill", "shrinks", "Delta", "pivot_given")
+
+
+def gatherBlockFields(nparam, ncols, nsamples, ndata, with_moments, sketch_ell=0):
+    """One chain's block in parallelHMCSampler's all-gather: its fields in order, (name, number of doubles).  Their sum is the block.
+    sketch_ell > 0 (the chains run with sketch={...}): the chain's row sketch behind the rest -- its six counters (SKETCH_INFO_KEYS),
+    x0, tot, q and room for its 2 ell rows."""
     fields = [("model", nparam * ncols), ("hmstats", 4 * (nsamples + 1)), ("acceptstats", nsamples), ("data", 2 * ndata * (ncols + 1)),
               ("secs_and_flag", 2)]
-    return fields + ([("count", 1), ("mean", nparam), ("m2", nparam)] if with_moments else [])
+    fields += [("count", 1), ("mean", nparam), ("m2", nparam)] if with_moments else []
+    if sketch_ell:
+        fields += [("sketch_info", len(SKETCH_INFO_KEYS)), ("sketch_x0", nparam), ("sketch_tot", nparam), ("sketch_q", nparam),
+                   ("sketch_rows", 2 * int(sketch_ell) * nparam)]
+    return fields
+
+
+def _sketch_pack(sk, ell, nparam):
+    """a chain's hmcstats.sketch as the five sketch fields of its gather block (a chain that counted nothing: zeros but for ell)"""
+    rows = np.zeros((2 * ell, nparam))
+    if sk is None or int(sk["count"]) == 0:
+        return {"sketch_info": [0, ell, 0, 0, 0.0, 0], "sketch_x0": np.zeros(nparam), "sketch_tot": np.zeros(nparam),
+                "sketch_q": np.zeros(nparam), "sketch_rows": rows}
+    rows[:int(sk["fill"])] = sk["rows"]
+    return {"sketch_info": [float(sk[k]) for k in SKETCH_INFO_KEYS], "sketch_x0": sk["x0"], "sketch_tot": sk["tot"], "sketch_q": sk["q"],
+            "sketch_rows": rows}
+
+
+def _sketch_unpack(part, nparam):
+    """the sketch dict of a gathered block (sketchOf's keys), or None for a chain that counted nothing"""
+    info = part["sketch_info"]
+    count, ell, fill, shrinks, pivot_given = (int(round(info[i])) for i in (0, 1, 2, 3, 5))
+    if count == 0:
+        return None
+    return _sketch_dict(ell, part["sketch_rows"].reshape(2 * ell, nparam), fill, count, shrinks, float(info[4]), part["sketch_x0"].copy(),
+                        part["sketch_tot"].copy(), part["sketch_q"].copy(), pivot_given)
 
 
 def _block_views(buf, fields):
@@ -1471,7 +1705,12 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
     group then only carries the 128-byte RCCL id from rank 0 to the others.  Works without a process group too (one rank).
     Further keyword arguments go to runHMCSampler (e.g. device_leapfrog=True; `checkpoint=path` and `chain_checkpoint=path` become
     `path.chain<k>` per chain; device_chain=True, keep_samples=False and the device chain's optional outputs).  What those outputs
-    fill -- every HMCStatus field of CHAIN_OUTPUTS -- is not gathered: it stays with the chain on the chain's own rank.
+    fill -- every HMCStatus field of CHAIN_OUTPUTS -- is not gathered: it stays with the chain on the chain's own rank.  The one
+    exception is `sketch={...}`: every chain is given the same pivot, the start model invParam.strModel (unless the keyword names
+    one), each chain's sketch -- counters, x0, tot, q, rows: (2 ell + 3) nparam + 6 doubles -- travels behind its block, so every rank
+    ends with every chain's hmcstats.sketch (another rank's chain without lam and U), and rank 0 pools them: the first chain's
+    hmcstats.sketch["merged"] is mergeSketches of all chains with the pooled lam, U, err and explained (pcaFromSketch); None where
+    fewer than two samples were counted in all.
     `library_rng=True` (with device_chain=True): chain c draws its numbers in the library as stream c of `seed`,
     runHMCSampler(library_rng=(seed, c)); its hmcstats.rng stays on the chain's own rank like the optional outputs.
     `nuts={"max_depth": d}` goes through to runHMCSampler with it; hmcstats.nuts stays on the chain's own rank too.
@@ -1533,6 +1772,9 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                         kw[key] = f"{kw[key]}.chain{c + 1}"
                 if kw.get("library_rng") is True:               # the library's generator: chain c is stream c of the run's seed
                     kw["library_rng"] = (int(seed), c)
+                if kw.get("sketch") is not None and kw["sketch"].get("pivot") is None:
+                    # one pivot for every chain, the start model's: their sketches are pooled behind the gather (mergeSketches)
+                    kw["sketch"] = {**kw["sketch"], "pivot": np.array(invParam.strModel, dtype=np.float64)}
                 model, stats, data = runHMCSampler(mesh_c, mtData, inv_c, prior_c, rng, ctx=ctx_c, **kw)
             finally:
                 release_context(inv_c)
@@ -1570,7 +1812,9 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
         ncols, with_moments = int(lay[0]), bool(lay[1])
     ndata = len(invParam.obsData)
     per = (nchains + world - 1) // world                   # chain slots per rank (padded)
-    fields = gatherBlockFields(nparam, ncols, nsamples, ndata, with_moments)
+    sketch_kw = sampler_kw.get("sketch")                    # (a keyword: every rank sees it alike)
+    sketch_ell = int(sketch_kw.get("ell", 32)) if sketch_kw is not None else 0
+    fields = gatherBlockFields(nparam, ncols, nsamples, ndata, with_moments, sketch_ell)
     blk = sum(size for _, size in fields)
 
     def pack(slot):
@@ -1582,6 +1826,8 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                     "data": data.reshape(-1).view(np.float64), "secs_and_flag": [secs, 1.0]}
             if with_moments:
                 part.update(zip(("count", "mean", "m2"), stats.moments))
+            if sketch_ell:
+                part.update(_sketch_pack(getattr(stats, "sketch", None), sketch_ell, nparam))
             for name, view in _block_views(buf, fields).items():
                 view[:] = np.reshape(part[name], -1)
         return buf
@@ -1622,6 +1868,26 @@ def parallelHMCSampler(mtMesh, mtData, invParam, hmcprior, pids=None, seed=0, ou
                 for out in CHAIN_OUTPUTS:
                     setattr(hmcstats[c], out.field, getattr(results[c][1], out.field, None))
                 hmcstats[c].rng = getattr(results[c][1], "rng", None)
+            elif sketch_ell:                                 # another rank's chain: its sketch came with the block (no components)
+                hmcstats[c].sketch = _sketch_unpack(part, nparam)
+    if sketch_ell and rank == 0 and nchains > 0:
+        # the chains share one pivot (one_chain): rank 0 pools their sketches and takes the pooled principal components.  The pooled
+        # dict goes to the FIRST chain's hmcstats.sketch["merged"]; None where no chain counted two samples
+        gathered = []
+        for r in range(world):
+            for s in range(per):
+                if r + s * world < nchains:
+                    gathered.append(_sketch_unpack(_block_views(allbuf[r, s], fields), nparam))
+        merged = None
+        counted = [g for g in gathered if g is not None]
+        if sum(int(g["count"]) for g in counted) >= 2 and all(int(g["pivot_given"]) for g in counted):
+            merged = mergeSketches(gathered)
+            lam, U, err = pcaFromSketch(merged, int(sketch_kw.get("rank", 8)))
+            total = float(merged["var"].sum())
+            merged.update(lam=lam, U=U, err=err, explained=lam / total if total > 0 else np.zeros_like(lam))
+        if hmcstats[0].sketch is None:
+            hmcstats[0].sketch = {"count": 0}
+        hmcstats[0].sketch["merged"] = merged
     if outdir is not None and rank == 0:
         from .fileio import outputHMCSamples
         for c in range(nchains):

@@ -90,6 +90,7 @@ class HMCStatus:
     dataMoments: object = None    # (count, mean[ndata], m2[ndata]) of the predicted data: runHMCSampler(..., data_moments=True)
     ess: object = None            # dict count, maxlag, targets, mean, acov, tau, ess, window, misfit: runHMCSampler(..., ess=...)
     cov: object = None            # dict count, rows, mean, var, cov, corr: runHMCSampler(..., cov=...)
+    sketch: object = None         # dict count, ell, fill, shrinks, Delta, mean, var, rows, lam, U, err, explained: runHMCSampler(..., sketch=...)
     adapt: object = None          # dict nwarmup, dt, alpha, dt_final, invM, windows: runHMCSampler(..., adapt=...)
     rng: object = None            # (seed, stream, t) of the library's generator behind the run: runHMCSampler(..., library_rng=(seed, stream))
     nuts: object = None           # dict max_depth, depth, nleaves, stop, dirs, selected, alpha (per sample): runHMCSampler(..., nuts={"max_depth": d})

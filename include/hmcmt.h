@@ -375,6 +375,67 @@ extern int hmcmt_chain_cov_begin(hmcmt_ctx* ctx, int64_t nrow, const int64_t* ro
 extern int hmcmt_chain_cov(hmcmt_ctx* ctx, int64_t* count, double* mean, double* var, double* cov, int32_t on_device);
 extern int hmcmt_chain_corr(hmcmt_ctx* ctx, double* corr, int32_t on_device);
 
+/* Posterior principal components from the chain's commit by a row sketch (optional, a fifth accumulator under the rules above: fed
+ * by the commits behind the burn-in from its begin call on, a rejection's repeat included, with its own count N; nothing above
+ * changes when it is off, and every record, model, moment, histogram, autocovariance and cross moment keeps its bits when it is on).
+ * The method is frequent directions (Liberty 2013; Ghashami, Liberty, Phillips, Woodruff 2016): 2 ell rows of nAC doubles stand for
+ * the N x nAC matrix A of the rows y_t, with a deterministic error bound that every read-out reports.
+ *   hmcmt_chain_sketch_begin  2 <= ell <= HMCMT_SKETCH_ELL_MAX.  pivot[nAC] (host, finite) or NULL: the model of the first counted
+ *                         commit, the convention of the accumulators above; sketches of several chains can be merged only under one
+ *                         given pivot.  Allocates and zeroes B[2 ell + 1][nAC], x0, tot, q[nAC] and the staging of the Gram matrix
+ *                         ([2 ell + 1]^2) and of the coefficients -- about 8 (2 ell + 4) nAC bytes.  On HMCMT_ENOMEM the chain goes on
+ *                         without the sketch.  A second call replaces the first sketch
+ *       Per counted commit t = 0, 1, ... one kernel, one thread per cell a:
+ *           y = m[a] - x0[a] (one subtraction);  tot[a] += y;  q[a] = fma(y, y, q[a]);  B[fill][a] = y;   then ++fill.
+ *       The shrink, when fill == 2 ell, in the same call:
+ *         a. device: K = B B' over the rows 0 .. 2 ell - 1 in fp64, every entry ONE fma chain over the cells upwards from 0, no atomics;
+ *         b. ONE wait and one download of K (at most 128 KB);
+ *         c. host, double: cyclic Jacobi (the warm-up estimator's), the eigenvalues taken descending d_0 >= d_1 >= ...;
+ *            delta = max(d_ell, 0);  c_i = d_i > delta ? sqrt((d_i - delta) / d_i) : 0 for i < ell;  T[i][j] = c_i V[j][i] ([ell][2 ell]);
+ *            Delta += delta;  ++shrinks;
+ *         d. device: T is uploaded; B'[i][a] = sum_j T[i][j] B[j][a], j upwards by fma from 0, IN PLACE: the thread that owns cell a
+ *            has copied all of column a aside before it writes any of it; rows ell .. 2 ell - 1 are zeroed and fill = ell.
+ *       So the sketch adds one wait per ell counted commits and none otherwise.  A HIP error in a shrink is handled as at a window end
+ *       of the low-rank warm-up: the sample stands, its call returns HMCMT_EHIP, the sketch is ended.  An eigensolver that does not
+ *       converge within its 64 sweeps (or a Gram matrix that is not finite) ends the sketch too, the call returns what it would have;
+ *       the read-outs below then return HMCMT_EINVAL with a message that says so.
+ *       The guarantee, in exact arithmetic: 0 <= A'A - B'B <= Delta I in the positive semidefinite order, and
+ *       Delta <= |A - A_k|_F^2 / (ell - k) for every k < ell (A_k the best rank-k approximation of A).
+ *   hmcmt_chain_sketch    info (may be NULL) = {count N, ell, fill, shrinks, Delta, pivot_given}; mean[nAC] = x0 + tot / N and
+ *                         var[nAC] = (q - (tot tot) / N) / N in the formulas of hmcmt_chain_cov; rows[fill][nAC], the sketch as it
+ *                         stands, unshrunk rows included (room for 2 ell rows).  Each may be NULL; on_device as for hmcmt_chain_cov;
+ *                         complete on return; nothing is changed by reading.  HMCMT_EINVAL when N = 0 and an array is asked for
+ *   hmcmt_chain_pca       the leading eigenpairs of the centred covariance estimate (B'B - N ybar ybar') / N, ybar = tot / N;
+ *                         1 <= rank <= HMCMT_MASS_RANK_MAX.  Device: row 2 ell of B = sqrt(N) ybar; G = W W' over W = the filled rows
+ *                         and that row (the shrink's Gram kernel).  One wait, then host: G = Q Lambda Q' keeping the m values
+ *                         Lambda_i > 1e-10 Lambda_max; S = Lambda^1/2 Q' J Q Lambda^1/2 with J = diag(1, ..., 1, -1), symmetrised;
+ *                         S = Z Theta Z'; the min(rank, #theta > 0) largest theta are kept, descending, the lower index first among
+ *                         equals; coefficients Q Lambda^-1/2 Z_sel.  Device: U[k][a] = sum_i coef[i][k] W[i][a], i upwards by fma; a
+ *                         direction's entry of largest magnitude (the lowest index among equals) is positive; the orthonormality
+ *                         defect max |U U' - I| is computed as hmcmt_set_mass_lowrank computes it.  *kept = the directions returned,
+ *                         lambda[kept] = theta_k / N, U[kept][nAC] (room for rank rows; lambda and U may be NULL, device pointers with
+ *                         on_device), *err = Delta / N (may be NULL; kept and err are always host).  Every returned lambda[k] lies
+ *                         within err of the k-th eigenvalue of the exact centred covariance of the counted commits, in exact
+ *                         arithmetic: Weyl's inequality on the guarantee above, since both matrices subtract the same rank-one term.
+ *                         It does not change the sketch (it writes the staging row 2 ell, which no commit reads), so two calls in a
+ *                         row return the same bytes.  HMCMT_EINVAL for N < 2; HMCMT_EBREAKDOWN for a defect above 1e-8, a Gram matrix
+ *                         that is not finite or an eigensolver that did not converge
+ * hmcmt_chain_begin (also over a running chain), hmcmt_chain_end, hmcmt_set_prior and hmcmt_set_mass end the sketch and release its
+ * buffers; a step that fails touches nothing.  HMCMT_EINVAL: NULL context, ell or rank outside the above, a non-finite pivot, no chain,
+ * no sketch begun, a call between hmcmt_grad_device_async and hmcmt_wait.  Results repeat bitwise (every sum has one owner thread and
+ * one order: no atomics). */
+#define HMCMT_SKETCH_ELL_MAX 64
+typedef struct hmcmt_sketch_info {
+    int64_t count;         /* N: counted commits in the sketch */
+    int32_t ell, fill;     /* fill: rows in use, 0 .. 2 ell - 1 */
+    int64_t shrinks;
+    double  Delta;         /* sum of the shrinks' delta: the bound on A'A - B'B */
+    int32_t pivot_given, reserved_;
+} hmcmt_sketch_info;
+extern int hmcmt_chain_sketch_begin(hmcmt_ctx* ctx, int32_t ell, const double* pivot);
+extern int hmcmt_chain_sketch(hmcmt_ctx* ctx, hmcmt_sketch_info* info, double* mean, double* var, double* rows, int32_t on_device);
+extern int hmcmt_chain_pca(hmcmt_ctx* ctx, int32_t rank, int32_t* kept, double* lambda, double* U, double* err, int32_t on_device);
+
 /* The chain's step size and diagonal mass between two steps, and their warm-up adaptation (optional: with no call below, every
  * record, moment and accumulator keeps its bits).
  *   hmcmt_chain_set_dt    replaces the chain's dt (finite, > 0) between two steps.  The chain, its accumulators, a momentum already
@@ -643,7 +704,8 @@ extern int hmcmt_rng_nuts(uint64_t seed, uint32_t stream, uint64_t t, int32_t ki
  *         the payloads, in table order, contiguous: the first at 64 + 24 nsections, each at the end of the one before
  *     end uint64   checksum: h = 0xcbf29ce484222325; for every preceding 8-byte word w, in order: h = (h ^ w) * 0x100000001b3 (mod 2^64)
  * A tag is four characters read as a little-endian uint32 ("CHAN" = 0x4e414843).  CHAN and MASS are always there, in this order; then,
- * each iff its part is on or was begun, HIST, DMOM, ACOV, "COV ", ADPT, ADLR (ADLR only with ADPT).  No tag repeats.
+ * each iff its part is on or was begun, HIST, DMOM, ACOV, "COV ", ADPT, ADLR (ADLR only with ADPT), SKCH (the last of the table, so
+ * that every blob without a sketch keeps its bytes and its order).  No tag repeats.
  * The payloads: scalars first, 8 bytes each (i = int64, f = double, u = uint64), then arrays of doubles (unless said otherwise) in the
  * device's layout.
  *   CHAN  f dt, regParam, lnSigMin, lnSigMax, D, M;  i burnin, nsamples, nmoments;  u seed, t;  uint32 stream, seeded;
@@ -664,7 +726,10 @@ extern int hmcmt_rng_nuts(uint64_t seed, uint32_t stream, uint64_t t, int32_t ki
  *   ADLR  i rank, max_samples;  f cutoff, gamma  (the options);  i win_start, stride, stored, skipped, closed_stored, rows;
  *         the last closed window's info: i windows, stored, skipped, dims, rank, fallback, stride;  f theta_min, theta_max, defect,
  *         host_ms;  X[rows][nAC], G[rows][nAC] (rows = stored, or closed_stored while the open window is empty: the rows a later
- *         call can still read) */
+ *         call can still read)
+ *   SKCH  i ell, fill, count, shrinks, pivot_given;  f Delta;  x0[nAC], tot[nAC], q[nAC], B[fill][nAC]  (the row sketch; refused
+ *         unless 2 <= ell <= 64, 0 <= fill < 2 ell -- a commit that fills the buffer shrinks it in the same call --, the counters
+ *         belong together, Delta is finite and >= 0 and every array is finite) */
 #define HMCMT_BLOB_VERSION 1
 #define HMCMT_BLOB_SECTIONS_MAX 16
 typedef struct hmcmt_chain_blob_header {

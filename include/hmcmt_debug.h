@@ -170,6 +170,23 @@ int hmcmt_debug_adapt_lowrank_rows(hmcmt_ctx* ctx, int32_t* n, double* X, double
  * It changes no result */
 int hmcmt_debug_adapt_lowrank_time(hmcmt_ctx* ctx, double* out /*[4]*/);
 
+/* Test hook of the row sketch (hmcmt_chain_sketch_begin; tests/test_gpu_chain_sketch.py): feeds the n host rows[n][nAC] (1 <= n <=
+ * 65536) as committed models through the chain's very commit and shrink launches, without a chain or a solve (the context needs its
+ * prior: the rows have nAC cells); pivot as for hmcmt_chain_sketch_begin.  info and, each may be NULL, x0, tot, q [nAC] and
+ * B_out [info->fill][nAC] (room for 2 ell rows) are the sketch behind the last row; of the first max_shrinks shrinks K_out
+ * [max_shrinks][2 ell][2 ell] receives the Gram matrix and T_out [max_shrinks][ell][2 ell] the host's T (both needed with
+ * max_shrinks > 0).  Complete on return; nothing of the context changes.  HMCMT_EBREAKDOWN where a shrink's eigensolver gave up. */
+int hmcmt_debug_chain_sketch(hmcmt_ctx* ctx, int32_t ell, int64_t n, const double* rows, const double* pivot, hmcmt_sketch_info* info,
+                             double* x0, double* tot, double* q, double* B_out, int32_t max_shrinks, double* K_out, double* T_out);
+/* The three vectors the running sketch's mean and variance are made of: x0 (the pivot), tot (the sum of y) and q (the sum of y^2), nAC
+ * doubles each (each may be NULL; device pointers with on_device).  sampler.pcaFromSketch and mergeSketches work from them.  A
+ * read-out: nothing changes.  HMCMT_EINVAL without a sketch */
+int hmcmt_debug_chain_sketch_sums(hmcmt_ctx* ctx, double* x0, double* tot, double* q, int32_t on_device);
+/* Measurement only: the same as hmcmt_debug_chain_cov_time for the running sketch: of each pair [0] the k_chain_sketch_commit launches,
+ * [1] the k_chain_sketch_gram and k_chain_sketch_shrink launches (two per shrink); *host_ms (may be NULL) the host milliseconds of
+ * the shrinks' eigenproblems since the last switch.  It changes no result */
+int hmcmt_debug_chain_sketch_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]*/, int64_t* launches /*[2]*/, double* host_ms);
+
 #ifdef __cplusplus
 }
 #endif

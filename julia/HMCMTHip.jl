@@ -26,7 +26,7 @@ using SparseArrays
 using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
-export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, chain_adapt_lowrank!, chain_adapt_lowrank_info, chain_set_mass_lowrank!, chain_mass_lowrank, proposeLeapfrog, proposeLeapfrogDevice!,
+export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, chain_adapt_lowrank!, chain_adapt_lowrank_info, chain_set_mass_lowrank!, chain_mass_lowrank, chain_sketch_begin!, chain_sketch_info, chain_sketch, chain_pca, HmcmtSketchInfo, proposeLeapfrog, proposeLeapfrogDevice!,
        hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chain_save, chain_restore!, chain_blob_info, HmcmtChainBlobHeader, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
@@ -838,6 +838,65 @@ function chain_cov!(ctx::HipContext; rows::Vector{<:Integer}=Int[], batch::Integ
 end
 
 """
+    chain_sketch_begin!(ctx; ell=32, pivot=nothing);  chain_sketch(ctx) -> (info, mean[nAC], var[nAC], rows[nAC, fill])
+    chain_pca(ctx, rank) -> (lam[kept], U[nAC, kept], err)
+
+Posterior principal components from the chain's commit by a frequent-directions row sketch (hmcmt_chain_sketch_*, hmcmt_chain_pca,
+include/hmcmt.h): 2 ell rows of nAC doubles stand for the counted commits' differences from the pivot (`pivot` = nAC values, or
+`nothing`: the first counted model), shrunk to ell rows whenever the buffer is full -- one wait per ell counted commits.  `info` is the
+HmcmtSketchInfo (count, ell, fill, shrinks, Delta, pivot_given); `rows` and `U` come back in C's row-major layout, i.e. with Julia's
+first index running over the cells: column k is row k.  Every lam[k] lies within err = Delta / count of the k-th eigenvalue of the exact
+(biased) covariance of the counted commits.  Call the begin function behind `chainBegin!` (which ends the sketch) and in front of the
+first `chainMomentum!`; `run_chain!(...; sketch=(; ell=32, rank=8))` does both ends.
+"""
+struct HmcmtSketchInfo
+    count::Int64
+    ell::Int32
+    fill::Int32
+    shrinks::Int64
+    Delta::Float64
+    pivot_given::Int32
+    reserved_::Int32
+end
+
+function chain_sketch_begin!(ctx::HipContext; ell::Integer=32, pivot::Union{Nothing,Vector{Float64}}=nothing)
+    pivot === nothing || length(pivot) == ctx.nAC || error("chain_sketch_begin!: pivot needs $(ctx.nAC) entries")
+    ptr = pivot === nothing ? Ptr{Float64}(C_NULL) : pointer(pivot)
+    rc = GC.@preserve pivot @ccall libhmcmt.hmcmt_chain_sketch_begin(ctx.ptr::Ptr{Cvoid}, Int32(ell)::Int32, ptr::Ptr{Float64})::Cint
+    checkerr(ctx.ptr, rc)
+    return Int(ell)
+end
+
+function chain_sketch_info(ctx::HipContext)
+    info = Ref(HmcmtSketchInfo(0, 0, 0, 0, 0.0, 0, 0))
+    rc = @ccall libhmcmt.hmcmt_chain_sketch(ctx.ptr::Ptr{Cvoid}, info::Ref{HmcmtSketchInfo}, C_NULL::Ptr{Float64}, C_NULL::Ptr{Float64},
+                                            C_NULL::Ptr{Float64}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return info[]
+end
+
+function chain_sketch(ctx::HipContext)
+    fill = Int(chain_sketch_info(ctx).fill)
+    info = Ref(HmcmtSketchInfo(0, 0, 0, 0, 0.0, 0, 0))
+    mean = Vector{Float64}(undef, ctx.nAC); var = Vector{Float64}(undef, ctx.nAC)
+    rows = Matrix{Float64}(undef, ctx.nAC, fill)
+    rc = @ccall libhmcmt.hmcmt_chain_sketch(ctx.ptr::Ptr{Cvoid}, info::Ref{HmcmtSketchInfo}, mean::Ptr{Float64}, var::Ptr{Float64},
+                                            rows::Ptr{Float64}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return info[], mean, var, rows
+end
+
+function chain_pca(ctx::HipContext, rank::Integer)
+    kept = Ref{Int32}(0); err = Ref{Float64}(0.0)
+    lam = Vector{Float64}(undef, rank); U = Matrix{Float64}(undef, ctx.nAC, rank)
+    rc = @ccall libhmcmt.hmcmt_chain_pca(ctx.ptr::Ptr{Cvoid}, Int32(rank)::Int32, kept::Ref{Int32}, lam::Ptr{Float64}, U::Ptr{Float64},
+                                         err::Ref{Float64}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    k = Int(kept[])
+    return lam[1:k], U[:, 1:k], err[]
+end
+
+"""
     chainSetDt!(ctx, dt);  chainSetMassDiag!(ctx, invM);  chainMassDiag(ctx) -> invM[nAC]
     chainAdaptBegin!(ctx, nwarmup; adaptMass=true, initBuffer=75, termBuffer=50, baseWindow=25, delta=0.8, gamma=0.05, t0=10.0,
                      kappa=0.75, dtMin=0.0, dtMax=0.0);  chainAdaptInfo(ctx) -> HmcmtAdaptInfo;  chainAdaptEnd!(ctx)
@@ -937,7 +996,7 @@ function chain_mass_lowrank(ctx::HipContext)
 end
 
 """
-    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, seed=nothing, nuts=nothing, cov=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, adapt][, nuts])
+    run_chain!(ctx, invParam, hmcprior, hmcParam; keepSamples=true, rhoref=nothing, seed=nothing, nuts=nothing, cov=nothing, sketch=nothing, adapt=nothing) -> (hmcmodel, hmcstats, hmcdata, moments[, cov][, sketch][, adapt][, nuts])
 
 runHMCSampler (HMCSampler.jl:72-196) through the chain API, step for step what hmcmt2d_amd/sampler.py's device chain does, the
 reference's start included: the chain's state starts at the file's model invParam.strModel (:88), while start and reference model
@@ -948,6 +1007,8 @@ rhoref; per sample L, u, the next momentum's normals.  `keepSamples=false`: no s
 hmcdata its first only); `moments` = (count, mean, m2) of the samples behind hmcprior.burninsamples either way.
 `cov=(rows=Int[], batch=0)` (both optional; see `chainCovBegin!`) streams the posterior covariance beside the moments and appends a fifth
 result, the named tuple (count, rows, mean, var, cov, corr) -- `nothing` for the arrays of a chain that ends inside its burn-in.
+`sketch=(; ell=32, rank=8)` (both optional, and `pivot`; see `chain_sketch_begin!`) streams the row sketch beside the moments and appends
+the named tuple (info, mean, var, rows, lam, U, err) -- `nothing` for the arrays of a chain that counted fewer than two samples.
 `adapt=(nwarmup=hmcprior.burninsamples, ...)` (the keywords of `chainAdaptBegin!`, all optional) warms the chain up over its first
 `nwarmup <= hmcprior.burninsamples` samples and appends a last result, the named tuple (nwarmup, dt, alpha, dtFinal, invM): the step
 size each sample's trajectory used, each sample's acceptance probability, the adapted step size and the diagonal of M^-1 in force
@@ -961,7 +1022,8 @@ used, the warm-up's alpha is the tree's, and a last result is appended: the vect
 """
 function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior, hmcParam::HMCParameter; keepSamples::Bool=true,
                     rhoref::Union{Nothing,Real}=nothing, seed::Union{Nothing,Tuple{<:Integer,<:Integer}}=nothing,
-                    nuts::Union{Nothing,Integer}=nothing, cov::Union{Nothing,NamedTuple}=nothing, adapt::Union{Nothing,NamedTuple}=nothing)
+                    nuts::Union{Nothing,Integer}=nothing, cov::Union{Nothing,NamedTuple}=nothing, sketch::Union{Nothing,NamedTuple}=nothing,
+                    adapt::Union{Nothing,NamedTuple}=nothing)
     (nuts === nothing || seed !== nothing) || error("run_chain!: nuts needs seed=(s, c): the tree's draws are the library's")
     n, nd = ctx.nAC, ctx.nData
     nsamples = hmcprior.totalsamples
@@ -984,6 +1046,7 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
         chainSetEnergy!(ctx, D, M)
     end
     covRows = cov === nothing ? Int[] : first(chain_cov!(ctx; rows=Vector{Int}(get(cov, :rows, Int[])), batch=get(cov, :batch, 0)))
+    sketch === nothing || chain_sketch_begin!(ctx; ell=get(sketch, :ell, 32), pivot=get(sketch, :pivot, nothing))
     if adapt !== nothing
         nwarmup = get(adapt, :nwarmup, hmcprior.burninsamples)
         nwarmup <= hmcprior.burninsamples || error("run_chain!: adapt nwarmup = $(nwarmup) exceeds hmcprior.burninsamples: the moments would mix in warm-up samples")
@@ -1056,14 +1119,24 @@ function run_chain!(ctx::HipContext, invParam::InvDataModel, hmcprior::HMCPrior,
     end
     adaptStats = adapt === nothing ? () : ((nwarmup=nwarmup, dt=adaptDt, alpha=adaptAlpha, dtFinal=chainAdaptInfo(ctx).dt, invM=chainMassDiag(ctx)),)
     nutsStats = nuts === nothing ? () : (nutsRecs,)
-    cov === nothing && return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), adaptStats..., nutsStats...)
+    sketchStats = ()
+    if sketch !== nothing
+        if nsamples > hmcprior.burninsamples + 1
+            sinfo, smean, svar, srows = chain_sketch(ctx)
+            slam, sU, serr = chain_pca(ctx, get(sketch, :rank, 8))
+            sketchStats = ((info=sinfo, mean=smean, var=svar, rows=srows, lam=slam, U=sU, err=serr),)
+        else
+            sketchStats = ((info=chain_sketch_info(ctx), mean=nothing, var=nothing, rows=nothing, lam=nothing, U=nothing, err=nothing),)
+        end
+    end
+    cov === nothing && return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), sketchStats..., adaptStats..., nutsStats...)
     if nsamples > hmcprior.burninsamples
         count, cmean, cvar, cmat = chainCov(ctx, length(covRows))
         covStats = (count=count, rows=covRows, mean=cmean, var=cvar, cov=cmat, corr=chainCorr(ctx, length(covRows)))
     else
         covStats = (count=0, rows=covRows, mean=nothing, var=nothing, cov=nothing, corr=nothing)
     end
-    return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats, adaptStats..., nutsStats...)
+    return (hmcmodel, hmcstats, hmcdata, chainMoments(ctx), covStats, sketchStats..., adaptStats..., nutsStats...)
 end
 
 hipWait(ctx::HipContext) = checkerr(ctx.ptr, ccall((:hmcmt_wait, libhmcmt), Cint, (Ptr{Cvoid},), ctx.ptr))
