@@ -12,7 +12,7 @@ from .invsetup import setupInverseDataModel, setActiveElement, compDataWeightMat
 from .fileio import (readEMModel2D, writeEMModel2D, readMT2DData, writeMT2DData, readstartupFile,
                      outputHMCSamples, getPosteriorModel, getPosteriorModelFromMoments)
 from .sampler import (compDataGradient, compDataMisfit, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, getHamiltonian, proposeLeapfrog, proposeLeapfrogDevice,
-                      runHMCSampler,
+                      runHMCSampler, findMAP,
                       parallelHMCSampler, getKineticEnergy, getKineticGradient, getMomentumVector,
                       setMassMatrix, checkParameterBound, get_context, release_context, mergeMoments, gelmanRubin)
 from .lib import HipContext, HmcmtError, build_library

@@ -65,6 +65,7 @@ constexpr int VBLOCK = HMCMT_VBLOCK;        // threads of the vector kernels (bu
 #include "kernels_mass.h"
 #include "kernels_chain.h"
 #include "kernels_nuts.h"
+#include "kernels_map.h"
 #include "kernels_jac.h"
 #include "kernels_jvp.h"
 
@@ -390,7 +391,27 @@ struct hmcmt_ctx {
             std::vector<void*> allocs;
         } nuts;
     } chain;
-    int solveFail = 0;                    // status a system of the last solve gave up with (mapped failure word), 0 = none
+    // the MAP optimiser (hmcmt_map_*, host_map.h, kernels_map.h): state, trial and history on the device, the scalars of the decisions here
+    struct Map {
+        bool active = false;
+        int status = 0, cap = 0;              // cap: the history the ring and the small matrices have room for
+        hmcmt_map_options opt{};
+        int cur = 0;                          // d_m[cur], d_g[cur], d_pred[cur]: the state, [cur ^ 1]: the trial
+        double *d_m[2] = {nullptr, nullptr}, *d_g[2] = {nullptr, nullptr}, *d_pred[2] = {nullptr, nullptr};
+        double *d_gd = nullptr, *d_pg = nullptr, *d_d = nullptr;   // [nAC] the trial's data gradient, the projected gradient, the direction
+        double *d_ring = nullptr;             // [2 cap][nAC]
+        double *d_part = nullptr;             // [MAP_PART_ROWS][LFNB]
+        double *d_SY = nullptr, *d_YY = nullptr;   // [cap][cap] by slot
+        double *d_cs = nullptr;               // [MAP_COEF + MAP_SCAL] the coefficient block, then the trial's scalars
+        double *h_rec = nullptr;              // pinned copy of d_cs
+        int head = 0, count = 0;
+        long long iter = 0;
+        double regParam = 0, lo = 0, hi = 0;
+        double phi = 0, D = 0, M = 0, pginf0 = 0, pginf = 0, pg2 = 0;
+        int nbound = 0;
+        std::vector<void*> allocs;
+    } map;
+    int solveFail = 0;                   // status a system of the last solve gave up with (mapped failure word), 0 = none
     // persistent solve kernel (kernels_persist.h)
     unsigned long long persistTag = 0;    // ... the tag base of the next launch
     long long* d_pstamps = nullptr;       // HMCMT_STAMPS=persist
@@ -1758,6 +1779,7 @@ __global__ __launch_bounds__(64) void k_hog(long long ticks, int* started) {
 extern "C" {
 
 static void chain_release(hmcmt_ctx* ctx);      // (host_chain.h)
+static void map_release(hmcmt_ctx* ctx);        // (host_map.h)
 
 void hmcmt_default_options(hmcmt_options* o) {
     if (!o) return;
@@ -1863,6 +1885,7 @@ int hmcmt_destroy(hmcmt_ctx* ctx) {
         hipFree(ctx->sv.stamps);
     }
     chain_release(ctx);
+    map_release(ctx);
     for (void* p : ctx->allocs) hipFree(p);
     for (void* p : ctx->blk.allocs) hipFree(p);
     for (void* p : ctx->blk.hostAllocs) hipHostFree(p);
@@ -3245,6 +3268,7 @@ int hmcmt_set_prior(hmcmt_ctx* ctx, const double* mref, const int64_t* rowptr, c
     int rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the previous prior)
     chain_release(ctx);                                     // (a chain belongs to the prior it began with)
+    map_release(ctx);                                       // (... and so does a MAP run)
     mass_lr_release(ctx);                                   // (... and so does a low-rank mass: its scales default to this prior's invM)
     if (ctx->mass.kind == HMCMT_MASS_LOWRANK) ctx->mass.kind = HMCMT_MASS_DIAGONAL;
     // a repeated call replaces the previous prior: its buffers are released, not kept until hmcmt_destroy
@@ -3292,6 +3316,7 @@ int hmcmt_set_mass(hmcmt_ctx* ctx, int32_t kind) {
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));              // (a trajectory may still be reading the mass buffers)
     chain_release(ctx);                                     // (... and to the mass)
+    map_release(ctx);
     ctx->mass.kind = HMCMT_MASS_DIAGONAL;
     mass_lr_release(ctx);
     if (kind == HMCMT_MASS_DIAGONAL) return 0;
@@ -3394,6 +3419,7 @@ int hmcmt_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, con
         mass_lr_free(ctx, {d_s, d_U, d_c, d_part});
         if (rc) {                                           // (out of memory: the context is left on the diagonal mass)
             chain_release(ctx);
+            map_release(ctx);
             mass_lr_release(ctx);
             M.kind = HMCMT_MASS_DIAGONAL;
             ctx->err = e;
@@ -3405,6 +3431,7 @@ int hmcmt_set_mass_lowrank(hmcmt_ctx* ctx, const double* invM, int32_t rank, con
         return HMCMT_EINVAL;                                // (nothing has changed: the mass and a running chain stay)
     }
     chain_release(ctx);                                     // (a chain belongs to the mass it began with)
+    map_release(ctx);
     mass_lr_release(ctx);
     M.d_lrS = d_s; M.d_lrU = d_U; M.d_lrC = d_c; M.d_lrPart = d_part;
     M.lrRank = M.lrCap = rank;
@@ -3603,6 +3630,7 @@ int hmcmt_leapfrog(hmcmt_ctx* ctx, const double* m0, const double* p0, double dt
 }
 
 #include "host_chain.h"
+#include "host_map.h"
 
 }  // extern "C"
 

@@ -1763,4 +1763,103 @@ inline int item_chain_sketch_pca(int nw, double* G, int rank, std::vector<double
     return r;
 }
 
+// ----------------------------------------------------------------------------------------------
+// the MAP optimiser (hmcmt_map_*, kernels_map.h, host_map.h; include/hmcmt.h has the algorithm): projected L-BFGS in the compact form
+// ----------------------------------------------------------------------------------------------
+// The ring holds H slots: rows [0, H) the s of the slots, rows [H, 2 H) their y, n doubles each.  Pair i of `count`, oldest first, sits in
+// slot (head + i) % H; S'Y and Y'Y ([H][H]) are indexed by SLOT.  Projection row q < count is s_q, row count + q is y_q.  Every sum has one
+// owner and one order (a thread walks its cells upwards with fma, wave_sum's tree, the four waves as item_mass_lr_block, the CHAIN_NB
+// workgroups in index order); every product that feeds a sum stands inside fma, the rest are single operations.
+constexpr int MAP_HISTORY_MAX = 32;                        // == HMCMT_MAP_HISTORY_MAX
+constexpr int MAP_ROWS_MAX = 2 * MAP_HISTORY_MAX;
+// rows of the partial sums [MAP_PART_ROWS][CHAIN_NB]: the projections, then the pass's own
+enum { MAP_P_X0 = MAP_ROWS_MAX, MAP_P_X1, MAP_P_X2, MAP_P_X3, MAP_P_X4, MAP_P_MAX, MAP_P_NB, MAP_PART_ROWS };
+// what the coefficient step leaves [MAP_COEF]: gamma (H0, or the step scale without pairs), the flag "not a descent direction" (the pairs were
+// set aside), g'd, |pg|inf, |pg|2^2, |B|, the pairs the expansion uses, then a [H] and w = -gamma p [H] by pair
+enum { MC_GAMMA = 0, MC_FLAG, MC_GTD, MC_PGINF, MC_PG2, MC_NB, MC_USED, MC_A = 8, MC_W = MC_A + MAP_HISTORY_MAX, MAP_COEF = MC_W + MAP_HISTORY_MAX };
+// what a trial's pass leaves [MAP_SCAL]: D, M, g's, s'y, s's, y'y and, of the TRIAL state, |pg|2^2, |pg|inf, |B|
+enum { MS_D = 0, MS_M, MS_GTS, MS_STY, MS_STS, MS_YTY, MS_PG2, MS_PGINF, MS_NB, MAP_SCAL };
+struct MapRing { const double* rows; long long n; int H, head, count; };
+HD int item_map_slot(const MapRing& R, int i) { return (R.head + i) % R.H; }
+HD const double* item_map_row(const MapRing& R, int q) {
+    return q < R.count ? R.rows + (long long)item_map_slot(R, q) * R.n : R.rows + (long long)(R.H + item_map_slot(R, q - R.count)) * R.n;
+}
+// cell a is in the active set B: on a bound with the gradient pushing outwards
+HD bool item_map_bound(double m, double g, double lo, double hi) { return (m <= lo && g > 0.0) || (m >= hi && g < 0.0); }
+HD double item_map_pg(const double* m, const double* g, double lo, double hi, long long a) { return item_map_bound(m[a], g[a], lo, hi) ? 0.0 : g[a]; }
+// cell a's terms of the projections q0 .. q0 + nq - 1 (nq <= MASS_LR_CHUNK) of the vector whose entry there is x
+HD void item_map_proj_acc(const MapRing& R, int q0, int nq, double x, long long a, double (&acc)[MASS_LR_CHUNK]) {
+#pragma unroll
+    for (int q = 0; q < MASS_LR_CHUNK; ++q)
+        if (q < nq) acc[q] = fma(item_map_row(R, q0 + q)[a], x, acc[q]);
+}
+// The coefficient algebra of one direction (Byrd, Nocedal, Schnabel 1994, eq. 3.13 with H0 = gamma I): R = the upper triangle of S'Y,
+// Dg its diagonal; p = R^-1 S'pg, a = R^-T ((Dg + gamma Y'Y) p - gamma Y'pg), H pg = gamma pg + S a - gamma Y p.  t [2 count]: S'pg then
+// Y'pg.  g'd = -pg'H pg, since d is -H pg off B and pg is 0 on B.  Without pairs, or when g'd is not negative with pairs (the flag),
+// d = -pg min(1, 1 / |pg|inf).  Serial on purpose: two triangular solves of at most 32 unknowns are dependency chains.
+HD void item_map_coef(const MapRing& R, const double* SY, const double* YY, const double* t, double pg2, double pginf, double nb, double* out) {
+    const int c = R.count, H = R.H;
+    for (int i = 0; i < MAP_COEF; ++i) out[i] = 0.0;
+    out[MC_PGINF] = pginf; out[MC_PG2] = pg2; out[MC_NB] = nb;
+    const double g0 = pginf > 1.0 ? 1.0 / pginf : 1.0;
+    bool ok = false;
+    if (c > 0) {
+        const int nn = item_map_slot(R, c - 1);
+        const double gamma = SY[nn * H + nn] / YY[nn * H + nn];
+        double p[MAP_HISTORY_MAX], a[MAP_HISTORY_MAX];
+        for (int i = c - 1; i >= 0; --i) {
+            const int si = item_map_slot(R, i);
+            double acc = t[i];
+            for (int j = i + 1; j < c; ++j) acc = fma(-SY[si * H + item_map_slot(R, j)], p[j], acc);
+            p[i] = acc / SY[si * H + si];
+        }
+        for (int i = 0; i < c; ++i) {
+            const int si = item_map_slot(R, i);
+            double z = -t[c + i];
+            for (int j = 0; j < c; ++j) z = fma(YY[si * H + item_map_slot(R, j)], p[j], z);
+            a[i] = fma(gamma, z, SY[si * H + si] * p[i]);
+        }
+        for (int i = 0; i < c; ++i) {
+            const int si = item_map_slot(R, i);
+            double acc = a[i];
+            for (int j = 0; j < i; ++j) acc = fma(-SY[item_map_slot(R, j) * H + si], a[j], acc);
+            a[i] = acc / SY[si * H + si];
+        }
+        double h = gamma * pg2;
+        for (int i = 0; i < c; ++i) h = fma(a[i], t[i], h);
+        for (int i = 0; i < c; ++i) { out[MC_A + i] = a[i]; out[MC_W + i] = -(gamma * p[i]); h = fma(out[MC_W + i], t[c + i], h); }
+        ok = -h < 0.0 && gamma > 0.0 && gamma <= 1.7976931348623157e308;
+        if (ok) { out[MC_GAMMA] = gamma; out[MC_GTD] = -h; out[MC_USED] = (double)c; }
+        else out[MC_FLAG] = 1.0;
+    }
+    if (!ok) { out[MC_GAMMA] = g0; out[MC_GTD] = -(g0 * pg2); out[MC_USED] = 0.0; }
+}
+// d[a] = -(gamma pg + sum_i s_i a_i + sum_i y_i w_i), pairs upwards, S before Y; exactly 0 on B
+HD double item_map_dir(const MapRing& R, const double* coef, double pg, bool bound, long long a) {
+    if (bound) return 0.0;
+    const int used = (int)coef[MC_USED];
+    double acc = coef[MC_GAMMA] * pg;
+    for (int i = 0; i < used; ++i) acc = fma(item_map_row(R, i)[a], coef[MC_A + i], acc);
+    for (int i = 0; i < used; ++i) acc = fma(item_map_row(R, R.count + i)[a], coef[MC_W + i], acc);
+    return -acc;
+}
+// the trial's entry: clip(m + alpha d)
+HD double item_map_clip(double m, double alpha, double d, double lo, double hi) {
+    const double t = fma(alpha, d, m);
+    return t < lo ? lo : (t > hi ? hi : t);
+}
+// One cell of a trial's pass behind its evaluation: the full gradient g1 = g_data + lambda Wm (m1 - m_ref) (item_adapt_lr_grad) is written,
+// and with s = m1 - m0, y = g1 - g0 (0 where there is no state yet: g0 == nullptr) the terms of g0's, s'y, s's, y'y and of the trial
+// state's |pg|2^2 are added to acc[0 .. 5); returns the trial state's pg[a] (*bound: cell a is in its B)
+HD double item_map_trial(const double* m0, const double* g0, const double* m1, double g1, double lo, double hi, long long a, double (&acc)[5], bool* bound) {
+    if (g0) {
+        const double s = m1[a] - m0[a], y = g1 - g0[a];
+        acc[0] = fma(g0[a], s, acc[0]); acc[1] = fma(s, y, acc[1]); acc[2] = fma(s, s, acc[2]); acc[3] = fma(y, y, acc[3]);
+    }
+    *bound = item_map_bound(m1[a], g1, lo, hi);
+    const double pg = *bound ? 0.0 : g1;
+    acc[4] = fma(pg, pg, acc[4]);
+    return pg;
+}
+
 }  // namespace hmcmt

@@ -17,7 +17,7 @@ SO_PATH = os.environ.get("HMCMT_LIB_PATH") or os.path.join(HERE, "libhmcmt_hip.s
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = [os.path.join(CSRC, "hmcmt_hip.hip"), os.path.join(CSRC, "mumps_shim.hip"), os.path.join(CSRC, "comm.hip")]
 HEADERS = [os.path.join(CSRC, h) for h in ("hmcmt_math.h", "hmcmt_items.h", "hmcmt_host.h", "kernels_cocg.h", "kernels_fdm.h",
-                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_chain.h", "kernels_nuts.h", "kernels_jac.h", "kernels_jvp.h", "host_jacobian.h", "host_chain.h", "hmcmt_knobs.h")] + \
+                                            "kernels_fused.h", "kernels_persist.h", "kernels_persist4.h", "kernels_path.h", "kernels_mass.h", "kernels_chain.h", "kernels_nuts.h", "kernels_map.h", "kernels_jac.h", "kernels_jvp.h", "host_jacobian.h", "host_chain.h", "host_map.h", "hmcmt_knobs.h")] + \
           [os.path.join(HERE, "..", "include", h) for h in ("hmcmt.h", "hmcmt_debug.h", "hmcmt_mumps.h")]
 
 HMCMT_NCAT = 8
@@ -124,6 +124,33 @@ class ChainBlobHeader(C.Structure):
     _fields_ = [("version", C.c_uint32), ("nsections", C.c_uint32), ("total_bytes", C.c_uint64), ("nAC", C.c_int64), ("nData", C.c_int64),
                 ("mass_kind", C.c_int32), ("seeded", C.c_uint32), ("nsamples", C.c_int64), ("nmoments", C.c_int64),
                 ("tags", C.c_uint32 * 16), ("section_bytes", C.c_uint64 * 16)]
+
+
+class MapOptions(C.Structure):
+    """hmcmt_map_options (include/hmcmt.h): the options of a MAP run (hmcmt_map_begin)."""
+    _fields_ = [("history", C.c_int32), ("max_backtracks", C.c_int32), ("c1", C.c_double), ("shrink", C.c_double),
+                ("curv_eps", C.c_double), ("gtol", C.c_double)]
+
+
+class MapRecord(C.Structure):
+    """hmcmt_map_record (include/hmcmt.h): what hmcmt_map_begin / hmcmt_map_step report of the state they return."""
+    _fields_ = [("iter", C.c_int32), ("status", C.c_int32), ("nfevals", C.c_int32), ("backtracks", C.c_int32), ("resets", C.c_int32),
+                ("npairs", C.c_int32), ("pair_stored", C.c_int32), ("nbound", C.c_int32), ("alpha", C.c_double), ("gamma", C.c_double),
+                ("phi", C.c_double), ("D", C.c_double), ("M", C.c_double), ("pg_inf", C.c_double), ("pg_2", C.c_double),
+                ("gTd", C.c_double), ("sTy", C.c_double), ("phi_trial", C.c_double * 16)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_[:-1]}
+        d["phi_trial"] = np.array(self.phi_trial[:])
+        return d
+
+
+class DebugMapArgs(C.Structure):
+    """hmcmt_debug_map_args (include/hmcmt_debug.h): the host vectors of one direction."""
+    _fields_ = [("n", C.c_int64), ("history", C.c_int32), ("head", C.c_int32), ("count", C.c_int32), ("reserved_", C.c_int32),
+                ("rows", C.c_void_p), ("sy", C.c_void_p), ("yy", C.c_void_p), ("m", C.c_void_p), ("g", C.c_void_p),
+                ("lo", C.c_double), ("hi", C.c_double), ("alpha", C.c_double),
+                ("pg", C.c_void_p), ("d", C.c_void_p), ("mt", C.c_void_p), ("sums", C.c_void_p)]
 
 
 def build_library(force=False, verbose=False):
@@ -291,6 +318,17 @@ def load_library():
     lib.hmcmt_chain_blob_info.argtypes = [vp, C.c_uint64, C.POINTER(ChainBlobHeader)]
     for name in CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS:
         getattr(lib, name).restype = C.c_int
+    lib.hmcmt_map_default_options.argtypes = [C.POINTER(MapOptions)]
+    lib.hmcmt_map_default_options.restype = None
+    lib.hmcmt_map_begin.argtypes = [vp, c_double_p, C.c_double, C.c_double, C.c_double, C.POINTER(MapOptions), C.POINTER(MapRecord)]
+    lib.hmcmt_map_step.argtypes = [vp, C.POINTER(MapRecord)]
+    lib.hmcmt_map_run.argtypes = [vp, C.c_int32, C.POINTER(MapRecord), C.POINTER(C.c_int32)]
+    lib.hmcmt_map_state.argtypes = [vp, vp, vp, vp, C.c_int32]
+    lib.hmcmt_map_end.argtypes = [vp]
+    lib.hmcmt_debug_map_direction.argtypes = [vp, C.POINTER(DebugMapArgs)]
+    lib.hmcmt_debug_map_rows.argtypes = [vp, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]
+    for name in MAP_SYMBOLS[1:] + ["hmcmt_debug_map_direction", "hmcmt_debug_map_rows"]:
+        getattr(lib, name).restype = C.c_int
     lib.hmcmt_debug_fdm_fwd.argtypes = [vp, c_double_p, c_double_p]
     lib.hmcmt_debug_back_post.argtypes = [vp, c_double_p, c_double_p, c_double_p, c_double_p]
     lib.hmcmt_debug_extrap.argtypes = [vp, C.c_int32, c_double_p]
@@ -346,12 +384,19 @@ CHAIN_NUTS_SYMBOLS = ["hmcmt_chain_nuts_sample", "hmcmt_chain_nuts_run", "hmcmt_
 NUTS_DEPTH_MAX = 10   # include/hmcmt.h: HMCMT_NUTS_DEPTH_MAX
 # ... and the chain's checkpoint: one blob out, one blob in, a blob's header without a device
 CHAIN_SAVE_SYMBOLS = ["hmcmt_chain_save_size", "hmcmt_chain_save", "hmcmt_chain_restore", "hmcmt_chain_blob_info"]
+# the MAP model on the device: projected L-BFGS over the library's gradient
+MAP_SYMBOLS = ["hmcmt_map_default_options", "hmcmt_map_begin", "hmcmt_map_step", "hmcmt_map_run", "hmcmt_map_state", "hmcmt_map_end"]
+MAP_HISTORY_MAX = 32          # include/hmcmt.h: HMCMT_MAP_HISTORY_MAX
+MAP_RUNNING, MAP_CONVERGED, MAP_STALLED = 0, 1, 2
+MAP_STATUS = {MAP_RUNNING: "RUNNING", MAP_CONVERGED: "CONVERGED", MAP_STALLED: "STALLED"}
+MAP_OPTION_KEYS = ("history", "max_backtracks", "c1", "shrink", "curv_eps", "gtol")
+MAP_HOOK_NMAX, MAP_SUMS = 0x40000000, 136   # include/hmcmt_debug.h: HMCMT_MAP_HOOK_NMAX, HMCMT_MAP_SUMS
 NUTS_CK_MAX, NUTS_SUMS = 9, 21   # include/hmcmt_debug.h: HMCMT_NUTS_CK_MAX, HMCMT_NUTS_SUMS
 ADAPT_LOWRANK_KEYS = ("rank", "max_samples", "cutoff", "gamma")
 ADAPT_LOWRANK_NMIN, ADAPT_LOWRANK_NMAX = 4, 128   # include/hmcmt.h: max_samples of hmcmt_adapt_lowrank_options
 ADAPT_OPTION_KEYS = ("adapt_mass", "init_buffer", "term_buffer", "base_window", "delta", "gamma", "t0", "kappa", "dt_min", "dt_max")
 # include/hmcmt.h: the drop-in boundary
-PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_SKETCH_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
+PRODUCT_SYMBOLS = JVP_SYMBOLS + CHAIN_SYMBOLS + CHAIN_HIST_SYMBOLS + CHAIN_ACOV_SYMBOLS + CHAIN_COV_SYMBOLS + CHAIN_SKETCH_SYMBOLS + CHAIN_ADAPT_SYMBOLS + CHAIN_ADAPT_LOWRANK_SYMBOLS + CHAIN_RNG_SYMBOLS + CHAIN_NUTS_SYMBOLS + CHAIN_SAVE_SYMBOLS + MAP_SYMBOLS + ["hmcmt_default_options", "hmcmt_create", "hmcmt_destroy", "hmcmt_last_error",
                    "hmcmt_set_options", "hmcmt_get_stats", "hmcmt_get_iters", "hmcmt_grad", "hmcmt_forward",
                    "hmcmt_grad_device", "hmcmt_forward_device", "hmcmt_grad_device_async", "hmcmt_wait",
                    "hmcmt_set_prior", "hmcmt_set_mass", "hmcmt_set_mass_lowrank", "hmcmt_mass_apply", "hmcmt_leapfrog", "hmcmt_leapfrog_device", "hmcmt_get_fields",
@@ -365,8 +410,35 @@ DEBUG_SYMBOLS = ["hmcmt_profile", "hmcmt_profile_every", "hmcmt_profile_read", "
                  "hmcmt_debug_chain_cov_time", "hmcmt_debug_extrap", "hmcmt_debug_guess_capture", "hmcmt_debug_guess", "hmcmt_debug_nuts_leaf",
                  "hmcmt_debug_nuts_iters", "hmcmt_debug_adapt_lowrank", "hmcmt_debug_adapt_lowrank_rows",
                  "hmcmt_debug_adapt_lowrank_time", "hmcmt_debug_chain_sketch", "hmcmt_debug_chain_sketch_sums",
-                 "hmcmt_debug_chain_sketch_time"]
+                 "hmcmt_debug_chain_sketch_time", "hmcmt_debug_map_direction", "hmcmt_debug_map_rows"]
 EXPORTED_SYMBOLS = PRODUCT_SYMBOLS + DEBUG_SYMBOLS
+
+
+def map_options(**kw):
+    """hmcmt_map_options from the library's defaults (hmcmt_map_default_options: no device needed) and the given keys, checked against
+    the ranges of include/hmcmt.h before any call that touches the device: ValueError names the first one out of range."""
+    unknown = sorted(set(kw) - set(MAP_OPTION_KEYS))
+    if unknown:
+        raise ValueError(f"unknown MAP option(s) {unknown}; the options are {MAP_OPTION_KEYS}")
+    o = MapOptions()
+    load_library().hmcmt_map_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k in ("history", "max_backtracks"):
+            if int(v) != v:
+                raise ValueError(f"MAP option {k} must be an integer")
+            v = int(v)
+        else:
+            v = float(v)
+        setattr(o, k, v)
+    if not 1 <= o.history <= MAP_HISTORY_MAX:
+        raise ValueError(f"MAP option history must be within 1 .. {MAP_HISTORY_MAX}")
+    if not 0 <= o.max_backtracks <= 15:
+        raise ValueError("MAP option max_backtracks must be within 0 .. 15")
+    if not 0 < o.c1 < 1 or not 0 < o.shrink < 1:
+        raise ValueError("MAP options c1 and shrink must lie strictly between 0 and 1")
+    if not (np.isfinite(o.curv_eps) and o.curv_eps >= 0 and np.isfinite(o.gtol) and o.gtol >= 0):
+        raise ValueError("MAP options curv_eps and gtol must be finite and not negative")
+    return o
 
 
 def _dp(a):
@@ -928,6 +1000,79 @@ class HipContext:
 
     def chain_end(self):
         self._check(self.lib.hmcmt_chain_end(self.h))
+
+    # -- the MAP model on the device (hmcmt_map_*) -----------------------------------------------
+    def map_begin(self, m_start, regParam, lnSigMin, lnSigMax, **options):
+        """Starts a MAP run at clip(m_start) (after set_prior): one gradient evaluation there.  options: history, max_backtracks, c1,
+        shrink, curv_eps, gtol (include/hmcmt.h; checked here first).  Returns the record of the start state as a dict."""
+        o = map_options(**options)
+        for name, v in (("regParam", regParam), ("lnSigMin", lnSigMin), ("lnSigMax", lnSigMax)):
+            if not np.isfinite(v):
+                raise ValueError(f"{name} must be finite")
+        rec = MapRecord()
+        self._check(self.lib.hmcmt_map_begin(self.h, _dp(self._model(m_start)), float(regParam), float(lnSigMin), float(lnSigMax),
+                                             C.byref(o), C.byref(rec)))
+        self._map_history = o.history
+        return rec.as_dict()
+
+    def map_step(self):
+        """One iteration (direction, line search, pair, commit); the record as a dict.  HmcmtError EINVAL once the run has ended."""
+        rec = MapRecord()
+        self._check(self.lib.hmcmt_map_step(self.h, C.byref(rec)))
+        return rec.as_dict()
+
+    def map_run(self, maxiter):
+        """Iterates until the status leaves RUNNING or maxiter steps are made; the records as a list of dicts."""
+        recs = (MapRecord * max(int(maxiter), 1))()
+        n = C.c_int32(0)
+        self._check(self.lib.hmcmt_map_run(self.h, int(maxiter), recs, C.byref(n)))
+        return [recs[k].as_dict() for k in range(n.value)]
+
+    def map_state(self):
+        """(model, full gradient, predicted data) of the run's current state."""
+        m, g = np.empty(self.nAC), np.empty(self.nAC)
+        pred = np.empty(self.nData, dtype=np.complex128)
+        self._check(self.lib.hmcmt_map_state(self.h, m.ctypes.data, g.ctypes.data, pred.ctypes.data, 0))
+        return m, g, (pred.real.copy() if self.args.real_data else pred)
+
+    def map_state_device(self, d_m=None, d_grad=None, d_pred=None):
+        """The same into device pointers (ints; each may be None)."""
+        self._check(self.lib.hmcmt_map_state(self.h, d_m, d_grad, d_pred, 1))
+
+    def map_end(self):
+        self._check(self.lib.hmcmt_map_end(self.h))
+
+    def debug_map_direction(self, rows, head, count, sy, yy, m, g, lo, hi, alpha=1.0):
+        """Test hook (hmcmt_debug_map_direction): the direction's three kernels on host vectors of any length n.  rows [2 history, n]
+        (None with count = 0: history 1), sy, yy [history, history] by slot.  Returns dict(pg, d, mt, coef [72], proj [2 count])."""
+        m = np.ascontiguousarray(m, dtype=np.float64); g = np.ascontiguousarray(g, dtype=np.float64)
+        n = m.shape[0]
+        a = DebugMapArgs()
+        keep = [m, g]
+        if rows is None:
+            H = 1
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.float64); sy = np.ascontiguousarray(sy, dtype=np.float64)
+            yy = np.ascontiguousarray(yy, dtype=np.float64)
+            H = rows.shape[0] // 2
+            if rows.shape != (2 * H, n) or sy.shape != (H, H) or yy.shape != (H, H):
+                raise ValueError("rows must be [2 history, n], sy and yy [history, history]")
+            keep += [rows, sy, yy]
+            a.rows, a.sy, a.yy = rows.ctypes.data, sy.ctypes.data, yy.ctypes.data
+        pg, d, mt, sums = np.empty(n), np.empty(n), np.empty(n), np.empty(MAP_SUMS)
+        a.n, a.history, a.head, a.count = n, H, int(head), int(count)
+        a.m, a.g, a.lo, a.hi, a.alpha = m.ctypes.data, g.ctypes.data, float(lo), float(hi), float(alpha)
+        a.pg, a.d, a.mt, a.sums = pg.ctypes.data, d.ctypes.data, mt.ctypes.data, sums.ctypes.data
+        self._check(self.lib.hmcmt_debug_map_direction(self.h, C.byref(a)))
+        return {"pg": pg, "d": d, "mt": mt, "coef": sums[:72].copy(), "proj": sums[72:72 + 2 * int(count)].copy()}
+
+    def debug_map_rows(self):
+        """Test hook (hmcmt_debug_map_rows): dict(history, head, count, iter, rows [2 history, nAC], sy, yy [history, history]) of the run."""
+        H = getattr(self, "_map_history", MAP_HISTORY_MAX)
+        info = (C.c_int32 * 4)()
+        rows, sy, yy = np.empty((2 * H, self.nAC)), np.empty((H, H)), np.empty((H, H))
+        self._check(self.lib.hmcmt_debug_map_rows(self.h, info, _dp(rows), _dp(sy), _dp(yy)))
+        return {"history": info[0], "head": info[1], "count": info[2], "iter": info[3], "rows": rows, "sy": sy, "yy": yy}
 
     # -- checkpoint and resume (hmcmt_chain_save / hmcmt_chain_restore) ---------------------------
     def chain_save_size(self):

@@ -84,6 +84,36 @@ def _check_solver(hmcprior):
 
 
 # --------------------------------------------------------------------------------------------
+def findMAP(mtMesh, mtData, invParam, hmcprior, m0=None, ctx: HipContext | None = None, maxiter=50, **options):
+    """The MAP model of D + M on the GPU (hmcmt_map_*: projected L-BFGS, model, gradient and history device-resident) -> (model,
+    MAPStatus).  Starts from invParam.strModel when m0 is None; regParam and the bounds are hmcprior's; options: history,
+    max_backtracks, c1, shrink, curv_eps, gtol.  A run may end STALLED well above the minimum where the reference's gradient is not the
+    derivative of its misfit (boundaries close to the receivers); it never accepts a rise.  To start a chain at the model, write it into
+    invParam.strModel, from which runHMCSampler runs its first trajectory; fileio's model writer saves it like any other model."""
+    from .lib import MAP_STATUS, MAP_RUNNING, map_options
+    from .structs import MAPStatus
+    _check_solver(hmcprior)
+    map_options(**options)                                   # (ValueError before anything touches the device)
+    if int(maxiter) < 0:
+        raise ValueError("maxiter must not be negative")
+    ctx = ctx or get_context(mtMesh, mtData, invParam)
+    nparam = len(invParam.strModel)
+    start = np.asarray(invParam.strModel if m0 is None else m0, dtype=np.float64)
+    ctx.set_prior(invParam.refModel, invParam.Wm, np.ones(nparam))
+    lo, hi = np.log(hmcprior.sigBounds[0]), np.log(hmcprior.sigBounds[1])
+    recs = [ctx.map_begin(start, hmcprior.regParam, lo, hi, **options)]
+    if recs[0]["status"] == MAP_RUNNING and maxiter > 0:
+        recs += ctx.map_run(int(maxiter))
+    model, _, pred = ctx.map_state()
+    ctx.map_end()
+    col = lambda k, t=float: np.array([r[k] for r in recs], dtype=t)
+    st = MAPStatus(MAP_STATUS[recs[-1]["status"]], int(recs[-1]["iter"]), int(col("nfevals", int).sum()), col("phi"), col("D"), col("M"),
+                   col("pg_inf"), col("pg_2"), col("alpha"), col("backtracks", int), col("resets", int), col("npairs", int),
+                   col("pair_stored", bool), col("nbound", int), col("nfevals", int), pred)
+    return model, st
+
+
+# --------------------------------------------------------------------------------------------
 def compDataGradient(mtMesh, mtData, invParam, hmcprior, ctx: HipContext | None = None):
     """m = invParam.strModel -> (predData, dataMisfit, dataGrad)."""
     _check_solver(hmcprior)

@@ -96,6 +96,28 @@ class HMCStatus:
     nuts: object = None           # dict max_depth, depth, nleaves, stop, dirs, selected, alpha (per sample): runHMCSampler(..., nuts={"max_depth": d})
 
 
+@dataclass
+class MAPStatus:
+    """What sampler.findMAP returns beside the model: the records of hmcmt_map_begin (row 0) and of every hmcmt_map_step, as arrays.
+    Not a struct of the reference, which has no optimiser."""
+    status: str                   # "RUNNING" (maxiter reached), "CONVERGED" or "STALLED" (no step lowers the objective)
+    niter: int                    # accepted steps
+    nfevals: int                  # gradient evaluations, the start's included
+    phi: np.ndarray               # [nrec] D + M
+    dataMisfit: np.ndarray        # [nrec] D
+    mnorm: np.ndarray             # [nrec] M
+    pgInf: np.ndarray             # [nrec] max norm of the projected gradient
+    pg2: np.ndarray               # [nrec] its 2-norm
+    alpha: np.ndarray             # [nrec] accepted step length (0: none)
+    backtracks: np.ndarray        # [nrec] int
+    resets: np.ndarray            # [nrec] int
+    npairs: np.ndarray            # [nrec] int
+    pairStored: np.ndarray        # [nrec] bool
+    nbound: np.ndarray            # [nrec] int: cells held at a bound
+    evals: np.ndarray             # [nrec] int: evaluations of each call
+    predData: object = None       # predicted data at the returned model
+
+
 def initHMCStatus(nsamples: int) -> HMCStatus:
     """HMCStruct.jl:144-155."""
     return HMCStatus(0, 0, np.zeros(nsamples, dtype=bool), np.zeros((4, nsamples + 1)))

@@ -836,6 +836,60 @@ int hmcmt_jvp_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int3
 int hmcmt_jtvp_block_device(hmcmt_ctx* ctx, const double* d_U, int32_t nvec, int32_t wrt, double* d_JTU, hmcmt_stats* st);
 int hmcmt_gn_hessvec_block_device(hmcmt_ctx* ctx, const double* d_V, int32_t nvec, int32_t wrt, double* d_HV, hmcmt_stats* st);
 
+/* The MAP model on the device: projected L-BFGS over the gradient the library computes (host_map.h, kernels_map.h).
+ * Model, gradient and history never leave the GPU; the host waits once per trial evaluation and decides from a handful of scalars.
+ * Objective (what the chain calls D + M): Phi(m) = D(m) + 0.5 regParam (m - m_ref)' Wm (m - m_ref), g = g_data + regParam Wm (m - m_ref),
+ * lnSigMin <= m <= lnSigMax; m_ref and Wm are hmcmt_set_prior's.  State: m, g, Phi, D, M, the predicted data, a ring of at most
+ * `history` pairs (s, y).  One iteration (hmcmt_map_step):
+ *   1. B = {a : (m_a <= lo and g_a > 0) or (m_a >= hi and g_a < 0)}; pg = g off B, 0 on B.
+ *   2. d = -H pg with the L-BFGS inverse Hessian of the stored pairs, oldest to newest, H0 = gamma I, gamma = s'y / y'y of the newest pair
+ *      (compact form: R = upper triangle of S'Y, Dg its diagonal, p = R^-1 S'pg, a = R^-T ((Dg + gamma Y'Y) p - gamma Y'pg),
+ *      H pg = gamma pg + S a - gamma Y p); without pairs d = -pg min(1, 1 / |pg|inf); then d = 0 on B.  If g'd >= 0 with pairs stored,
+ *      the pairs are dropped and d is the direction without pairs (a reset).
+ *   3. Line search from alpha = 1: the trial is m_t = clip(m + alpha d, lo, hi), ONE full gradient evaluation there; accepted iff Phi_t is
+ *      finite and Phi_t <= Phi + c1 g'(m_t - m); else alpha <- shrink alpha, at most max_backtracks shrinkings (max_backtracks + 1 trials).
+ *      All trials failed with pairs stored: the pairs are dropped (a reset) and step 2 runs once more.  All failed without pairs: status
+ *      HMCMT_MAP_STALLED, and m, g, Phi, D, M and the predicted data are bit for bit what they were.  (The reference's gradient is not
+ *      everywhere the derivative of its misfit -- DESIGN.md section 2 -- so a run may stall well above the minimum; it never accepts a rise.)
+ *   4. s = m_t - m, y = g_t - g are stored iff s'y > curv_eps |s|2 |y|2; a full ring overwrites its oldest pair.
+ *   5. m, g, Phi, D, M and the predicted data become the trial's; status HMCMT_MAP_CONVERGED when |pg|inf <= gtol max(1, |pg0|inf) at
+ *      the new state (pg0: at hmcmt_map_begin's, where the same test runs).
+ * A trial whose evaluation fails (HMCMT_ENOCONV, HMCMT_EBREAKDOWN) makes the step return that code; the state and the pairs stay
+ * untouched and the next step starts afresh (hmcmt_chain_step's rule).
+ * hmcmt_map_begin needs hmcmt_set_prior (else HMCMT_EINVAL), clips m_start into the bounds, evaluates once and owns its buffers;
+ * HMCMT_ENOMEM leaves the context usable; a begin over a live run reuses its buffers when `history` fits them.  hmcmt_set_prior,
+ * hmcmt_set_mass* and hmcmt_destroy end the run.  A run and a chain may live on one context: both evaluate, so the chain's next step
+ * re-evaluates its start gradient; a MAP step after foreign evaluations needs nothing, it keeps its own g.  Every MAP call that
+ * evaluates ends a linearisation point.  Between hmcmt_grad_device_async and hmcmt_wait every MAP call is HMCMT_EINVAL, as are a step
+ * of a run whose status is not HMCMT_MAP_RUNNING, NULL or non-finite arguments and options out of range (1 <= history <=
+ * HMCMT_MAP_HISTORY_MAX, 0 <= max_backtracks <= 15, 0 < c1 < 1, 0 < shrink < 1, curv_eps >= 0, gtol >= 0).
+ * The record describes the state the call returns: iter (0 from begin), status, nfevals (evaluations of this call), backtracks
+ * (shrinkings of the last round), resets, npairs (stored after the call), pair_stored, nbound (|B|), alpha (accepted; 0 when stalled),
+ * gamma and gTd of the last round's direction, phi = D + M, |pg|inf, |pg|2, sTy of the accepted step, and phi_trial: Phi of the last
+ * round's trials in order, NaN beyond.  hmcmt_map_run iterates until a status other than HMCMT_MAP_RUNNING or maxiter steps, recs
+ * [maxiter] (may be NULL), *ndone the steps made; a failed step ends it with that step's code.  hmcmt_map_state: the current model,
+ * full gradient [nAC] and predicted data [2 nData] (each may be NULL; device pointers with on_device); it answers in every status. */
+#define HMCMT_MAP_HISTORY_MAX 32
+#define HMCMT_MAP_RUNNING 0
+#define HMCMT_MAP_CONVERGED 1
+#define HMCMT_MAP_STALLED 2
+typedef struct hmcmt_map_options {
+    int32_t history, max_backtracks;
+    double c1, shrink, curv_eps, gtol;
+} hmcmt_map_options;
+typedef struct hmcmt_map_record {
+    int32_t iter, status, nfevals, backtracks, resets, npairs, pair_stored, nbound;
+    double alpha, gamma, phi, D, M, pg_inf, pg_2, gTd, sTy;
+    double phi_trial[16];
+} hmcmt_map_record;
+void hmcmt_map_default_options(hmcmt_map_options* o);   /* history 8, max_backtracks 10, c1 1e-4, shrink 0.5, curv_eps 1e-10, gtol 1e-5 */
+int hmcmt_map_begin(hmcmt_ctx* ctx, const double* m_start, double regParam, double lnSigMin, double lnSigMax,
+                    const hmcmt_map_options* options /* NULL: the defaults */, hmcmt_map_record* rec0 /* may be NULL */);
+int hmcmt_map_step(hmcmt_ctx* ctx, hmcmt_map_record* rec);
+int hmcmt_map_run(hmcmt_ctx* ctx, int32_t maxiter, hmcmt_map_record* recs, int32_t* ndone);
+int hmcmt_map_state(hmcmt_ctx* ctx, double* m, double* grad, double* pred, int32_t on_device);
+int hmcmt_map_end(hmcmt_ctx* ctx);
+
 /* All-gather of the chains' sample blocks over RCCL (xGMI inside a node): one process per GPU, one communicator per
  * process.  Replaces parallelHMCSampler's collection of the workers' results (HMCSampler/parallelHMC.jl:23-45:
  * remotecall_fetch of hmcmodel / hmcstats / hmcdata per worker) for hosts that hold their chains in this library:

@@ -187,6 +187,27 @@ int hmcmt_debug_chain_sketch_sums(hmcmt_ctx* ctx, double* x0, double* tot, doubl
  * the shrinks' eigenproblems since the last switch.  It changes no result */
 int hmcmt_debug_chain_sketch_time(hmcmt_ctx* ctx, int32_t enable, double* ms /*[2]*/, int64_t* launches /*[2]*/, double* host_ms);
 
+/* Test hooks of the MAP optimiser (hmcmt_map_*; tests/test_gpu_map.py).  hmcmt_debug_map_direction runs the direction's three kernels
+ * (k_map_project, k_map_coef, k_map_expand) on HOST vectors, without a run or a solve: the context lends its device and stream only, n
+ * need not be its nAC (1 <= n <= HMCMT_MAP_HOOK_NMAX).  The ring: history slots, rows [2 history][n] (row k the s of slot k, row
+ * history + k its y), pair i of count, oldest first, in slot (head + i) % history; sy, yy [history][history] = S'Y and Y'Y by slot
+ * (rows, sy, yy may be NULL with count = 0).  Outputs (each may be NULL): pg, d, mt [n]; sums [HMCMT_MAP_SUMS] = the coefficient block
+ * {gamma, flag "not a descent direction", g'd, |pg|inf, |pg|2^2, |B|, pairs used, 0, a [32], w = -gamma p [32]}, then the 2 count
+ * projections S'pg, Y'pg (0 beyond).  Complete on return; nothing of the context changes.
+ * hmcmt_debug_map_rows reads a live run: info [4] = {history, head, count, iterations}; rows [2 history][nAC], sy, yy
+ * [history][history] (each may be NULL).  HMCMT_EINVAL without a run. */
+#define HMCMT_MAP_HOOK_NMAX 0x40000000
+#define HMCMT_MAP_SUMS 136
+typedef struct hmcmt_debug_map_args {
+    int64_t n;
+    int32_t history, head, count, reserved_;
+    const double *rows, *sy, *yy, *m, *g;
+    double lo, hi, alpha;
+    double *pg, *d, *mt, *sums;
+} hmcmt_debug_map_args;
+int hmcmt_debug_map_direction(hmcmt_ctx* ctx, const hmcmt_debug_map_args* args);
+int hmcmt_debug_map_rows(hmcmt_ctx* ctx, int32_t* info /*[4]*/, double* rows, double* sy, double* yy);
+
 #ifdef __cplusplus
 }
 #endif

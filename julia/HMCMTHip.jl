@@ -27,7 +27,7 @@ using Distributed              # myid
 using HMCMT.HMCFileIO, HMCMT.HMCStruct, HMCMT.HMCUtility
 
 export HipContext, hipContext, compDataGradient, compJacMat, compJacTMat, compJacMatVec, compJacTMatVec, compJacMatMat, compJacTMatMat, hipLinearize!, hipGNHessVec, hipGNHessMat, hipSensitivity, hipForward, setPrior!, set_mass_lowrank!, chain_adapt_lowrank!, chain_adapt_lowrank_info, chain_set_mass_lowrank!, chain_mass_lowrank, chain_sketch_begin!, chain_sketch_info, chain_sketch, chain_pca, HmcmtSketchInfo, proposeLeapfrog, proposeLeapfrogDevice!,
-       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chain_save, chain_restore!, chain_blob_info, HmcmtChainBlobHeader, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
+       hipWait, HmcmtChainRecord, chainBegin!, chainMomentum!, chainStep!, chainState, chainMoments, chainSetEnergy!, chainEnd!, chain_save, chain_restore!, chain_blob_info, HmcmtChainBlobHeader, chainHistBegin!, chainHist, chainQuantiles, chainDataMomentsBegin!, chainDataMoments, chain_hist!, chainAcovBegin!, chainAcov, chainEss, chain_ess!, chainCovBegin!, chainCov, chainCorr, chain_cov!, HmcmtAdaptOptions, HmcmtAdaptInfo, chainSetDt!, chainSetMassDiag!, chainMassDiag, chainAdaptBegin!, chainAdaptInfo, chainAdaptEnd!, chain_seed!, chain_rng_state, HmcmtMapOptions, HmcmtMapRecord, map_options, map_begin!, map_step!, map_run!, map_state, map_end!, find_map, chain_sample!, chain_run!, chain_nuts_sample!, chain_nuts_run!, HmcmtNutsRecord, run_chain!, hipStats, hipGuard, hipPersistInfo, hipPersistWidth, hipPersistEnvelope, hipPersistOrder, hipPersistPack, hipNextCuShare, destroy!, commId, SampleComm, allgatherSamples
 
 const libhmcmt = get(ENV, "HMCMT_HIP_LIB", joinpath(@__DIR__, "..", "hmcmt2d_amd", "libhmcmt_hip.so"))
 
@@ -1274,6 +1274,108 @@ function hipPersistEnvelope(ny::Integer, nz::Integer; cus_per_xcd::Integer = 32,
     rc = ccall((:hmcmt_persist_envelope, libhmcmt), Cint, (Int64, Int64, Int32, Int64, Ptr{Int64}), ny, nz, Int32(cus_per_xcd), nsystems, out)
     rc == 0 || error("hmcmt_persist_envelope: invalid sizes")
     return (column_parts = out[1], threads_half = out[2], workgroups_per_system = out[3], slab_modes = out[4], lds_bytes = out[5], slots_per_xcd = out[6])
+end
+
+# hmcmt_map_options and hmcmt_map_record of include/hmcmt.h: the options of a MAP run and what hmcmt_map_begin / hmcmt_map_step report
+# of the state they return (tests/test_map_host.py compares the fields with the ctypes mirrors)
+struct HmcmtMapOptions
+    history::Int32
+    max_backtracks::Int32
+    c1::Float64
+    shrink::Float64
+    curv_eps::Float64
+    gtol::Float64
+end
+
+struct HmcmtMapRecord
+    iter::Int32
+    status::Int32
+    nfevals::Int32
+    backtracks::Int32
+    resets::Int32
+    npairs::Int32
+    pair_stored::Int32
+    nbound::Int32
+    alpha::Float64
+    gamma::Float64
+    phi::Float64
+    D::Float64
+    M::Float64
+    pg_inf::Float64
+    pg_2::Float64
+    gTd::Float64
+    sTy::Float64
+    phi_trial::NTuple{16,Float64}
+end
+const MAP_RUNNING = Int32(0); const MAP_CONVERGED = Int32(1); const MAP_STALLED = Int32(2)
+blankMapRecord() = HmcmtMapRecord(0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, ntuple(_ -> NaN, 16))
+
+"""
+    map_options(; history=8, max_backtracks=10, c1=1e-4, shrink=0.5, curv_eps=1e-10, gtol=1e-5) -> HmcmtMapOptions
+    map_begin!(ctx, mStart, regParam, lnSigMin, lnSigMax; options...) -> HmcmtMapRecord
+    map_step!(ctx) -> HmcmtMapRecord;  map_run!(ctx, maxiter) -> Vector{HmcmtMapRecord}
+    map_state(ctx) -> (m, grad, pred);  map_end!(ctx)
+    find_map(ctx, invParam, hmcprior; m0=nothing, maxiter=50, options...) -> (model, records)
+
+The MAP model on the device (hmcmt_map_*, include/hmcmt.h): projected L-BFGS over the library's gradient of D + M, model, gradient and
+history in GPU memory, one wait per trial evaluation.  Call `setPrior!` first.  A run ends CONVERGED, STALLED (no step lowers the
+objective: the reference's gradient is not everywhere the derivative of its misfit) or at `maxiter`.  `find_map` starts from
+`invParam.strModel`, takes regParam and the bounds from `hmcprior`, and returns the model with the records; to start a chain there,
+write the model into `invParam.strModel`, from which `runHMCSampler` runs its first trajectory.
+"""
+function map_options(; kw...)
+    o = Ref(HmcmtMapOptions(0, 0, 0.0, 0.0, 0.0, 0.0))
+    @ccall libhmcmt.hmcmt_map_default_options(o::Ref{HmcmtMapOptions})::Cvoid
+    d = o[]
+    get_(k, v) = haskey(kw, k) ? kw[k] : v
+    return HmcmtMapOptions(Int32(get_(:history, d.history)), Int32(get_(:max_backtracks, d.max_backtracks)), Float64(get_(:c1, d.c1)),
+                           Float64(get_(:shrink, d.shrink)), Float64(get_(:curv_eps, d.curv_eps)), Float64(get_(:gtol, d.gtol)))
+end
+
+function map_begin!(ctx::HipContext, mStart::Vector{Float64}, regParam::Real, lnSigMin::Real, lnSigMax::Real; kw...)
+    o = Ref(map_options(; kw...))
+    rec = Ref(blankMapRecord())
+    rc = GC.@preserve mStart @ccall libhmcmt.hmcmt_map_begin(ctx.ptr::Ptr{Cvoid}, pointer(mStart)::Ptr{Float64}, Float64(regParam)::Float64,
+                                                            Float64(lnSigMin)::Float64, Float64(lnSigMax)::Float64,
+                                                            o::Ref{HmcmtMapOptions}, rec::Ref{HmcmtMapRecord})::Cint
+    checkerr(ctx.ptr, rc)
+    return rec[]
+end
+
+function map_step!(ctx::HipContext)
+    rec = Ref(blankMapRecord())
+    checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_map_step(ctx.ptr::Ptr{Cvoid}, rec::Ref{HmcmtMapRecord})::Cint)
+    return rec[]
+end
+
+function map_run!(ctx::HipContext, maxiter::Integer)
+    recs = Vector{HmcmtMapRecord}(undef, max(maxiter, 1))
+    done = Ref{Int32}(0)
+    rc = GC.@preserve recs @ccall libhmcmt.hmcmt_map_run(ctx.ptr::Ptr{Cvoid}, Int32(maxiter)::Int32, pointer(recs)::Ptr{HmcmtMapRecord},
+                                                        done::Ref{Int32})::Cint
+    resize!(recs, Int(done[]))
+    checkerr(ctx.ptr, rc)
+    return recs
+end
+
+function map_state(ctx::HipContext)
+    m = Vector{Float64}(undef, ctx.nAC); g = Vector{Float64}(undef, ctx.nAC)
+    pred = Vector{ComplexF64}(undef, ctx.nData)
+    rc = GC.@preserve m g pred @ccall libhmcmt.hmcmt_map_state(ctx.ptr::Ptr{Cvoid}, pointer(m)::Ptr{Float64}, pointer(g)::Ptr{Float64},
+                                                              pointer(pred)::Ptr{ComplexF64}, Int32(0)::Int32)::Cint
+    checkerr(ctx.ptr, rc)
+    return m, g, pred
+end
+
+map_end!(ctx::HipContext) = checkerr(ctx.ptr, @ccall libhmcmt.hmcmt_map_end(ctx.ptr::Ptr{Cvoid})::Cint)
+
+function find_map(ctx::HipContext, invParam, hmcprior; m0::Union{Nothing,Vector{Float64}}=nothing, maxiter::Integer=50, kw...)
+    mStart = m0 === nothing ? Vector{Float64}(invParam.strModel) : m0
+    rec0 = map_begin!(ctx, mStart, hmcprior.regParam, log(hmcprior.sigBounds[1]), log(hmcprior.sigBounds[2]); kw...)
+    recs = vcat([rec0], rec0.status == MAP_RUNNING ? map_run!(ctx, maxiter) : HmcmtMapRecord[])
+    m, _, _ = map_state(ctx)
+    map_end!(ctx)
+    return m, recs
 end
 
 """
